@@ -10,11 +10,16 @@ with ONE all-reduce of the 6-double statistics record over RCCL, enqueued behind
 stream: no host round trip per step.  Inputs are a handful of scalars, so nothing crosses PCIe in the
 timed region.  A bare `--gpus N` (no WORLD_SIZE in the environment) starts the N ranks itself.
 
-Extra objects on the line (N = 1 only, all measured in this run):
+A plain run sets up, warms up, times the K steps and prints the line; `--dump-outputs DIR` writes, before the line,
+what the last timed step computed (see dump_outputs).  Beside the headline, every run carries
   device          name / arch / CUs / clock / HBM total and free (mcamd_get_device_info; inc/tool.cuh:56-88,176-188)
   roofline        the dominant kernel against the VALU issue roofline (this path has ~zero HBM traffic and no
                   matrix work): W issue slots per path-step (counted from the ISA of the library that is loaded;
-                  refused when the count was taken from other sources) x measured path-steps/s
+                  refused when the count was taken from other sources) x measured path-steps/s, from the timed
+                  steps' own HIP events
+
+`--full` adds the side measurements below, each of which takes runs of its own (N = 1 only, all measured in this run;
+the `--no-*` options drop single legs of it):
   sweep           the north-star path counts 1M / 10M / 100M x {fp64, fp32}, in-register, each with kernel time,
                   whole-call time and roofline fraction
   roofline_store  BASELINE configs[2] (100M paths x 252 steps fp32 stored step-major + the payoff vector,
@@ -23,6 +28,7 @@ Extra objects on the line (N = 1 only, all measured in this run):
                   S_T control variate, fp64
   cfg1            BASELINE configs[0] on this host: closed form (1M evaluations) and the reference's serial MC
   cpu_baseline    the reference's own CPU Monte Carlo (oracle/_ref) or the oracle port, timed on this host
+  roofline.same_run_ceiling  (--workload store) the same store stream with nothing simulated, 3 launches
 Other workloads: --workload store | nmc | vanilla1 | european252_f32 (see --help).
 """
 from __future__ import annotations
@@ -58,6 +64,12 @@ W_FLOOR = {"price_f64": 62.5, "price_f32": 22.25, "nmc_wave_f64_window": 72.5}
 
 METRIC = "MC paths/sec, European call (price error vs closed-form BS reported)"
 
+# --dump-outputs: the statistics a caller receives in its result record, in this order
+RESULT_FIELDS = ("sum", "sumsq", "n", "price", "std_err", "ci_lo", "ci_hi")
+# device arrays longer than this are dumped at this many fixed positions (at most 3 x 16 MB per run)
+DUMP_SAMPLE = 1 << 21
+DUMP_SEED = 1234
+
 
 def parse(argv=None):
     ap = argparse.ArgumentParser()
@@ -77,6 +89,13 @@ def parse(argv=None):
                     help="nested MC: the reference's bullet window B=120, P1=10, P2=50 (hello.cu:11-13), or the "
                          "European-window variant (B=0, P2=N_STEPS) whose work count is deterministic")
     ap.add_argument("--nmc-strategy", default="wave", choices=["wave", "block", "fused"])
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / "
+                         "float64); arrays of more than 2^21 elements as a fixed seeded sample of 2^21 positions")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (N = 1: sweep, product form, store roofline, accuracy, bullet and "
+                         "nested-MC legs, CPU baselines; --workload store: the same-run store ceiling); the --no-* options "
+                         "below drop single legs of it.  Off: the run times the headline steps only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-store-roofline", action="store_true")
     ap.add_argument("--no-sweep", action="store_true")
@@ -90,7 +109,10 @@ def parse(argv=None):
     ap.add_argument("--rehearse-launch", action="store_true",
                     help="launcher test only: spawn the ranks, rendezvous, shard and all-reduce the path counts, price "
                          "nothing (needs no GPU); the line carries value null and \"rehearsal\": true")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------
@@ -279,6 +301,23 @@ def valu_roofline(W, stale, key, kernel, lane_steps_per_s, traffic_key=None, ext
 def median(xs):
     xs = sorted(xs)
     return xs[len(xs) // 2]
+
+
+def dump_outputs(out_dir: str, arrays) -> None:
+    """--dump-outputs: writes each (values, dtype) of `arrays` as <out_dir>/<name>.npy.  A device tensor of more than
+    DUMP_SAMPLE elements is gathered at DUMP_SAMPLE positions of its flat view, drawn from DUMP_SEED and sorted, so the
+    positions depend on the array's size alone and two builds run with the same arguments compare element for element."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    for name, (values, dtype) in arrays.items():
+        if isinstance(values, torch.Tensor):
+            flat = values.reshape(-1)
+            if flat.numel() > DUMP_SAMPLE:
+                idx = np.sort(np.random.default_rng(DUMP_SEED).choice(flat.numel(), DUMP_SAMPLE, replace=False))
+                flat = flat[torch.from_numpy(idx).to(flat.device)]
+            values = flat.cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(values, dtype=dtype))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -580,6 +619,19 @@ def main(argv=None):
         kernel_ms = ctx.enqueued_kernel_ms(min(args.steps, 64))
         fin = capi.finalize_stats(stats[args.steps - 1, :6].tolist(), opt.r, opt.T)
 
+    # what a caller of the timed path receives from the last timed step (rank 0: the reduced statistics, its own
+    # shard of any per-path or per-point array), written before any --full leg can overwrite the buffers
+    if rank == 0 and args.dump_outputs:
+        out = {"result": ([float(getattr(fin, f)) for f in RESULT_FIELDS], "float64")}
+        if is_price:
+            out["stats"] = (stats[args.steps - 1, :6], "float64")
+        elif wl == "store":
+            out.update(trajectories=(traj, "float32"), payoffs=(payoffs, "float32"))
+        else:
+            out.update(outer_prices=(nmc["traj"], "float64"), window_counts=(nmc["cnt"], "float64"),
+                       point_prices=(nmc["out"], "float64"))
+        dump_outputs(args.dump_outputs, out)
+
     line = None
     if rank == 0:
         units = n_total * args.steps
@@ -638,7 +690,7 @@ def main(argv=None):
                                 "frac": ach / PEAK_HBM_GBS, "traffic": pmc_traffic_bytes("store_kernel<float"),
                                 "kernel": "store_kernel<float,false,STEP_MAJOR,vec>",
                                 "algorithmic_bytes_per_launch": bytes_per_launch}
-            if per_gpu % 4 == 0:   # the same store stream with nothing simulated, right after the timed steps: this box's ceiling
+            if args.full and per_gpu % 4 == 0:   # the same store stream with nothing simulated, right after the timed steps: this box's ceiling
                 cs = [ctx.diag_store_pattern(per_gpu, n_steps, capi.F32, traj, payoffs) for _ in range(3)]
                 cms = sum(cs) / len(cs)
                 line["roofline"]["same_run_ceiling"] = {"kernel_ms": cms, "launches": len(cs),
@@ -652,15 +704,15 @@ def main(argv=None):
                                              "price_kernel<double, false, true, 0>" if f64 else "price_kernel<float, false, true, 0>",
                                              build_id=capi.build_id())
 
-    solo = rank == 0 and world == 1
+    side = rank == 0 and world == 1 and args.full   # the side legs below each take runs of their own
 
-    if solo and wl == "european252" and not args.no_store_roofline and args.store_leg_first:
+    if side and wl == "european252" and not args.no_store_roofline and args.store_leg_first:
         line["roofline_store"] = store_leg(ctx, capi, torch, opt, "right after the headline")
 
     # the north-star sweep: 1M / 10M / 100M paths x 252 steps, in-register, both precisions.  Synchronous calls
     # (mcamd_price_paths): kernel_ms = HIP events around the simulation kernel, call_ms = host wall time of the whole
     # call (launches + final reduce + 16-byte copy + sync), so call_ms - kernel_ms is the per-call overhead.
-    if solo and wl == "european252" and not args.no_sweep:
+    if side and wl == "european252" and not args.no_sweep:
         sweep = []
         for p_, key in ((capi.F64, "price_f64"), (capi.F32, "price_f32")):
             for n in (1_000_000, 10_000_000, 100_000_000):
@@ -689,7 +741,7 @@ def main(argv=None):
     # and the form whose terminal price is the same bits as the store kernel's last row.  Reported beside the headline
     # (which sums the log-returns and exponentiates once: same draws, same scheme).  Measured BEFORE the store pass: the
     # clock stays low for a while after 100 GB of stores.
-    if solo and wl == "european252":
+    if side and wl == "european252":
         ks = []
         for i in range(12):
             rl = ctx.price_paths(opt, capi.make_sim(n_total, n_steps, prec, 1234 + i, lo, per_gpu, flags=capi.FLAG_PRODUCT_FORM))
@@ -699,13 +751,13 @@ def main(argv=None):
                                      "std_err": rl.std_err, "abs_err_vs_bs": abs(rl.price - BS_EXACT),
                                      "valu_slots_per_path_step": W.get("price_f64_product")}
 
-    if solo and wl == "european252" and not args.no_store_roofline and not args.store_leg_first:
+    if side and wl == "european252" and not args.no_store_roofline and not args.store_leg_first:
         line["roofline_store"] = store_leg(ctx, capi, torch, opt, "after the sweep and the product-form leg")
 
     # "price within 1e-4 of closed form" on a 252-step BASELINE shape: the plain estimator would need > 2.6e10 paths
     # (sigma_payoff = 16.1), so this uses the engine's variance reduction — antithetic pairs + S_T control variate,
     # the same kernel family — on 1e9 samples (BASELINE configs[4]'s count; a sample = one antithetic PAIR), fp64.
-    if solo and wl == "european252" and not args.no_accuracy:
+    if side and wl == "european252" and not args.no_accuracy:
         fl = capi.FLAG_ANTITHETIC | capi.FLAG_CONTROL_VARIATE
         n_acc = args.accuracy_pairs
         t_acc = time.perf_counter()
@@ -730,7 +782,7 @@ def main(argv=None):
     # the reference's bullet option (hello.cu:11-13: B = 120, P1 = 10, P2 = 50) on configs[1]'s shape, 10M paths x 252
     # steps, fp64: the window closes for most paths after ~51 steps, and from 3.1M paths on the library prices such
     # jobs with its lane-compacting kernel (csrc/price_impl.hpp)
-    if solo and wl == "european252" and not args.no_nmc:
+    if side and wl == "european252" and not args.no_nmc:
         try:
             optb = capi.make_option(**OPTION, **BULLET)
             rb_ = [ctx.price_paths(optb, capi.make_sim(n_total, n_steps, prec, 1234 + i, lo, per_gpu)) for i in range(6)]
@@ -745,7 +797,7 @@ def main(argv=None):
     # BASELINE configs[3] beside the headline: nested MC, 65 536 outer x 252 steps x 1000 inner paths, fp64, with the
     # reference's bullet window (hello.cu:11-13), two-launch route (outer store + wave-per-point inner stage), one
     # untimed and two timed passes (~0.2 s each).  `--workload nmc` is the full line for this config.
-    if solo and wl == "european252" and not args.no_nmc:
+    if side and wl == "european252" and not args.no_nmc:
         try:
             n4, s4, i4 = 65_536, 252, 1000
             opt4 = capi.make_option(**OPTION, **BULLET)
@@ -776,7 +828,7 @@ def main(argv=None):
         except Exception as e:  # the headline must survive a failure of the side measurement
             line["nmc_config4"] = {"error": str(e)}
 
-    if solo and not args.no_cpu_baseline:
+    if side and not args.no_cpu_baseline:
         if wl == "nmc":
             line["cpu_baseline"] = cpu_nmc_baseline(nmc["win"], per_gpu, n_steps, nmc["n_inner"], nmc["traj"], nmc["cnt"])
         else:

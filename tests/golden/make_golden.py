@@ -12,6 +12,9 @@ Fixtures are DATA (inputs + expected outputs):
                             (inc/testing.cuh:75-91, oracle/_ref/libref_cpumc.so) returns on them
   rocrand_philox_kat.json   rocRAND 7.2 Philox4x32-10 raw words / normal4 / normal_double2,
                             executed on the host (tests/golden/gen_rocrand_kat.cpp)
+  ref_library.json          what oracle/_ref returns on the inputs of the tests that compare against the
+                            reference's own code (tests/test_oracle.py, tests/test_capi_cpu.py), so that
+                            they run wherever the repository is checked out
 """
 import ctypes as C
 import json
@@ -89,12 +92,68 @@ def rocrand_kat():
         return json.loads(subprocess.check_output([exe]))
 
 
+def closed_form_fresh_args():
+    """The (S0, K, T, r, sigma) tuples of tests/test_oracle.py's fresh-input closed-form test, fp32 values."""
+    rng = np.random.default_rng(7)
+    out = []
+    for _ in range(2000):
+        S0 = np.float32(rng.uniform(10, 300))
+        out.append((float(S0), float(np.float32(S0 * rng.uniform(0.4, 2.0))), float(np.float32(rng.uniform(0.02, 5))),
+                    float(np.float32(rng.uniform(0, 0.2))), float(np.float32(rng.uniform(0.03, 1.0)))))
+    return out
+
+
+def ref_library():
+    bs, mc = o.ref_bs(), o.ref_cpumc()
+    assert bs is not None and mc is not None, "oracle/_ref missing: run oracle/build_ref.sh"
+    pf = C.POINTER(C.c_float)
+
+    def normals(seed, n):
+        z = np.zeros(n, dtype=np.float32)
+        mc.ref_mt19937_normals(seed, n, z.ctypes.data_as(pf))
+        return z
+
+    def array_pricer(z, n_paths, n_steps):
+        dt = np.float32(1.0) / np.float32(n_steps)
+        pay = np.zeros(n_paths, dtype=np.float32)
+        mean = mc.ref_simulateOptionPriceCPU_array(n_paths, n_steps, z.ctypes.data_as(pf), 100.0, 0.2,
+                                                   float(np.sqrt(dt, dtype=np.float32)), 0.1, 100.0, float(dt),
+                                                   pay.ctypes.data_as(pf))
+        return f32(mean), [float(x) for x in pay]
+
+    array_driven = []
+    for seed, n_paths, n_steps in ((1, 64, 1), (2, 33, 100), (3, 7, 252)):
+        z = normals(seed, n_paths * n_steps)
+        mean, pay = array_pricer(z, n_paths, n_steps)
+        array_driven.append({"mt19937_seed": seed, "n_paths": n_paths, "n_steps": n_steps,
+                             "normals": [float(x) for x in z], "ref_payoffs": pay, "ref_mean_undiscounted": mean})
+    cpu_mc = []
+    for n_paths, n_steps, seed in ((1000, 1, 7), (257, 12, 1234), (64, 100, 99)):
+        mean, pay = array_pricer(normals(seed, n_paths * n_steps), n_paths, n_steps)
+        cpu_mc.append({"mt19937_seed": seed, "n_paths": n_paths, "n_steps": n_steps, "ref_payoffs": pay,
+                       "ref_mean_undiscounted": mean})
+    n = 200_000
+    return {"source": "oracle/_ref (reference inc/BlackandScholes.hpp, inc/tool.cuh:13-26,104-173, inc/testing.cuh:75-91 "
+                      "compiled by oracle/build_ref.sh); normals: std::mt19937 + std::normal_distribution<float>",
+            "sizeof_OptionData": int(mc.ref_sizeof_OptionData()),
+            "closed_form_fresh": {"inputs": "tests/golden/make_golden.py closed_form_fresh_args()",
+                                  "ref_call_f32": [f32(bs.ref_black_scholes_CPU(*a)) for a in closed_form_fresh_args()]},
+            "array_driven_fresh": array_driven,
+            "cpu_mc_seeded": cpu_mc,
+            "bullet_normals": {"mt19937_seed": 5, "n_paths": 50, "n_steps": 10,
+                               "normals": [float(x) for x in normals(5, 500)]},
+            "unseeded_mc": {"paths": n,
+                            "bullet_B120_P1_10_P2_50_100_steps": f32(mc.ref_simulateBulletOptionPriceCPU(
+                                100.0, 1.0, 100.0, 0.1, 0.2, 120.0, 10, 50, n, 100)),
+                            "european_1_step": f32(mc.ref_simulateOptionPriceCPU(100.0, 1.0, 100.0, 0.1, 0.2, n))}}
+
+
 def main():
     o.build_ref()
     for name, fn in (("bs_closed_form.json", closed_form), ("array_driven.json", array_driven),
-                     ("rocrand_philox_kat.json", rocrand_kat)):
+                     ("rocrand_philox_kat.json", rocrand_kat), ("ref_library.json", ref_library)):
         with open(os.path.join(HERE, name), "w") as f:
-            json.dump(fn(), f, indent=1)
+            json.dump(fn(), f, indent=None if name == "ref_library.json" else 1)
         print("wrote", name)
 
 

@@ -15,6 +15,14 @@ REQUIRED = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 def test_bench_help_runs_without_gpu():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True)
     assert out.returncode == 0 and "--gpus" in out.stdout and "--steps" in out.stdout and "--warmup" in out.stdout
+    assert "--full" in out.stdout and "--dump-outputs" in out.stdout
+
+
+def test_bench_refuses_a_run_without_timed_steps():
+    """ms_per_step is the time of one timed step: a run with none has no such figure."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True)
+    assert out.returncode == 2 and "--steps" in out.stderr
+    assert not [l for l in out.stdout.splitlines() if l.startswith("{")]
 
 
 def _bench_module():
@@ -23,6 +31,23 @@ def _bench_module():
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod
+
+
+def test_dump_outputs_samples_large_arrays_at_fixed_positions(tmp_path):
+    import numpy as np
+    import torch
+    b = _bench_module()
+    big = torch.arange(b.DUMP_SAMPLE + 12348, dtype=torch.float64).view(-1, 5)    # values = flat positions
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), {"big": (big, "float32"), "small": (big[:3, 0], "float64"),
+                                           "host": ([1.0, 2.5], "float64")})
+    s = np.load(tmp_path / "a" / "big.npy")
+    assert s.dtype == np.float32 and s.shape == (b.DUMP_SAMPLE,)
+    assert (np.diff(s) > 0).all() and s[0] >= 0 and s[-1] < big.numel()          # distinct positions, in order
+    np.testing.assert_array_equal(np.load(tmp_path / "b" / "big.npy"), s)       # the same positions every run
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "small.npy"), [0.0, 5.0, 10.0])
+    h = np.load(tmp_path / "a" / "host.npy")
+    assert h.dtype == np.float64 and h.tolist() == [1.0, 2.5]
 
 
 def test_launcher_command_is_the_drivers_multi_rank_form():
@@ -77,7 +102,7 @@ def test_bare_gpus_n_fails_loudly_without_n_devices():
 def test_bench_emits_one_json_line_with_roofline_and_cpu_baseline():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
                           "--paths", "1000000", "--cpu-sample-paths", "20000", "--no-store-roofline",
-                          "--no-accuracy", "--no-sweep", "--no-nmc"], capture_output=True, text=True, timeout=600)
+                          "--no-accuracy", "--no-sweep", "--no-nmc", "--full"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -147,7 +172,8 @@ def test_two_ranks_sharing_the_card_reproduce_the_one_rank_job(workload, strateg
 def test_store_workload_line_carries_its_same_run_ceiling():
     """`--workload store` (BASELINE configs[2]'s kernel at a small path count): the HBM roofline object names the bytes,
     and beside it the pure-store pass of the same shape measured in the same process."""
-    d = _bench_line(["--workload", "store", "--paths", "4000000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"])
+    d = _bench_line(["--workload", "store", "--paths", "4000000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+                     "--full"])
     rl = d["roofline"]
     assert rl["bound"] == "hbm" and rl["unit"] == "GB/s" and rl["peak"] == 8000.0 and d["dtype"] == "f32"
     assert rl["algorithmic_bytes_per_launch"] >= 4_000_000 * 252 * 4 + 4_000_000 * 4
@@ -155,3 +181,53 @@ def test_store_workload_line_carries_its_same_run_ceiling():
     c = rl["same_run_ceiling"]
     assert c["kernel_ms"] > 0 and c["GB_per_s"] > 500 and 0.3 < rl["frac_of_same_run_store_ceiling"] < 1.3
     assert abs(d["price"] - 13.2697) < 0.2
+
+
+FULL_ONLY = ["sweep", "product_form_mode", "roofline_store", "accuracy_252", "accuracy_demo", "bullet_252", "nmc_config4",
+             "cpu_baseline", "cpu_baseline_port", "cfg1"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("workload", ["european252", "store", "nmc"])
+def test_plain_run_dumps_what_its_last_timed_step_computed(workload, tmp_path):
+    """Without --full the line carries the headline and nothing that takes runs of its own.  --dump-outputs writes the
+    last timed step's result (and the arrays behind it, sampled at fixed positions when large) as .npy files; a second
+    run with the same arguments writes the same values."""
+    import numpy as np
+    paths = {"european252": 1_000_000, "store": 100_000, "nmc": 64}[workload]
+    argv = ["--workload", workload, "--paths", str(paths), "--steps", "3", "--warmup", "1"]
+    d = _bench_line([*argv, "--dump-outputs", str(tmp_path / "a")])
+    for k in REQUIRED:
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    for k in FULL_ONLY:
+        assert k not in d, k
+    assert "same_run_ceiling" not in d["roofline"]
+    a = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    res = a["result"]
+    assert res.dtype == np.float64 and res.shape == (7,)          # sum, sumsq, n, price, std_err, ci_lo, ci_hi
+    if workload == "european252":
+        assert set(a) == {"result", "stats"} and a["stats"].shape == (6,)   # sum, sumsq, sum_c, sum_cc, sum_yc, n
+        assert res[2] == a["stats"][5] == paths and res[0] == a["stats"][0]
+        assert res[3] == d["price"] and res[4] == d["std_err"]
+    elif workload == "store":
+        assert set(a) == {"result", "trajectories", "payoffs"} and res[2] == paths and res[3] == d["price"]
+        assert a["trajectories"].dtype == np.float32 and a["trajectories"].shape == (1 << 21,)   # 25.2M: sampled
+        assert a["payoffs"].dtype == np.float32 and a["payoffs"].shape == (paths,)
+        assert (a["trajectories"] > 0).all() and (a["payoffs"] >= 0).all()
+    else:
+        assert set(a) == {"result", "outer_prices", "window_counts", "point_prices"}
+        for k in ("outer_prices", "window_counts", "point_prices"):
+            assert a[k].dtype == np.float64 and a[k].shape == (paths * 252,)
+        assert res[2] == paths * 252 and res[3] == d["mean_point_price"]
+        assert abs(a["point_prices"].mean() - res[3]) <= 1e-12 * res[3]
+        c = a["window_counts"]
+        assert (c == np.round(c)).all() and c.min() >= 0 and c.max() <= 252
+    _bench_line([*argv, "--dump-outputs", str(tmp_path / "b")])
+    b = {k: np.load(tmp_path / "b" / (k + ".npy")) for k in a}
+    for k in sorted(a, key=lambda k: k == "result"):
+        if k == "result" and workload == "nmc":
+            # points leave the work queue in a different order each run: their sum is equal up to that order
+            np.testing.assert_allclose(b[k], a[k], rtol=1e-12, atol=0, err_msg=k)
+        else:
+            np.testing.assert_array_equal(b[k], a[k], err_msg=k)

@@ -128,22 +128,17 @@ def test_product_does_not_reach_into_the_oracle():
                     assert "pyoracle" not in text and "liboracle" not in text and "oracle/" not in text, (d, f)
 
 
-def test_cpu_mc_f32_is_the_reference_arithmetic_bit_for_bit(lib, oracle):
+def test_cpu_mc_f32_is_the_reference_arithmetic_bit_for_bit(lib, golden):
     """mcamd_cpu_mc_f32 restates inc/tool.cuh:104-173 with a seed.  The reference's own build (oracle/_ref) holds the same
     recurrence with the normals as an input (inc/testing.cuh:75-91) and the std::mt19937 / std::normal_distribution<float>
-    stream: feeding one into the other must reproduce the seeded pricer's fp32 payoff sum exactly."""
-    ref = oracle.ref_cpumc()
-    if ref is None:
-        pytest.skip("oracle/_ref not built (no /root/reference on this machine)")
-    for n, steps, seed in ((1000, 1, 7), (257, 12, 1234), (64, 100, 99)):
-        normals = np.zeros(n * steps, dtype=np.float32)
-        ref.ref_mt19937_normals(seed, n * steps, normals.ctypes.data_as(C.POINTER(C.c_float)))
-        pay = np.zeros(n, dtype=np.float32)
-        dt = np.float32(1.0) / np.float32(steps)
-        ref.ref_simulateOptionPriceCPU_array.restype = C.c_float
-        mean = ref.ref_simulateOptionPriceCPU_array(n, steps, normals.ctypes.data_as(C.POINTER(C.c_float)), 100.0, 0.2,
-                                                    float(np.sqrt(dt)), 0.1, 100.0, float(dt),
-                                                    pay.ctypes.data_as(C.POINTER(C.c_float)))
+    stream: feeding one into the other must reproduce the seeded pricer's fp32 payoff sum exactly.  What the reference
+    returns is recorded in tests/golden/ref_library.json (tests/golden/make_golden.py)."""
+    g = golden("ref_library.json")
+    for c in g["cpu_mc_seeded"]:
+        n, steps, seed = c["n_paths"], c["n_steps"], c["mt19937_seed"]
+        pay = np.array(c["ref_payoffs"], dtype=np.float32)
+        mean = c["ref_mean_undiscounted"]
+        assert pay.size == n
         price, total = capi.cpu_mc_f32(capi.make_option(), n, steps, seed)
         want_total = np.float32(0.0)
         for p_ in pay:
@@ -154,9 +149,10 @@ def test_cpu_mc_f32_is_the_reference_arithmetic_bit_for_bit(lib, oracle):
             abs(price - math.exp(-0.1) * float(want_total) / n) < 1e-5 * price
     # window: a bullet job against a plain-python restatement on the same stream
     opt = capi.make_option(B=101.0, P1=2, P2=7, use_window=1)
-    n, steps, seed = 50, 10, 5
-    normals = np.zeros(n * steps, dtype=np.float32)
-    ref.ref_mt19937_normals(seed, n * steps, normals.ctypes.data_as(C.POINTER(C.c_float)))
+    b = g["bullet_normals"]
+    n, steps, seed = b["n_paths"], b["n_steps"], b["mt19937_seed"]
+    assert (n, steps, seed) == (50, 10, 5)
+    normals = np.array(b["normals"], dtype=np.float32)
     f = np.float32
     dt = f(1.0) / f(steps)
     drift, vol = (f(0.1) - (f(0.2) * f(0.2)) / f(2)) * dt, f(0.2) * np.sqrt(dt, dtype=np.float32)

@@ -1,9 +1,8 @@
 """Pins the CPU oracle (oracle/oracle.c) against every golden vector available for the hot
 path: the reference's closed form and array-driven pricer (fixtures generated from
 oracle/_ref, i.e. the reference's own code compiled here), rocRAND's Philox known answers,
-and — when oracle/_ref is present — the reference libraries themselves on fresh inputs.
+and the reference libraries' outputs on further inputs (recorded from oracle/_ref in ref_library.json).
 CPU only."""
-import ctypes as C
 import math
 
 import numpy as np
@@ -38,16 +37,15 @@ def test_closed_form_f64_vs_f32_within_published_error(oracle, golden):
     assert abs(oracle.bs_call_f64(100, 100, 1, 0.1, 0.2) - 13.269676584660893) < 1e-11
 
 
-def test_closed_form_against_reference_library_fresh_inputs(oracle):
-    L = oracle.ref_bs()
-    if L is None:
-        pytest.skip("oracle/_ref not built (no /root/reference on this machine)")
+def test_closed_form_against_reference_library_fresh_inputs(oracle, golden):
+    # the reference's black_scholes_CPU on these inputs (tests/golden/make_golden.py closed_form_fresh_args)
+    want = golden("ref_library.json")["closed_form_fresh"]["ref_call_f32"]
     rng = np.random.default_rng(7)
-    for _ in range(2000):
+    for i in range(2000):
         S0 = np.float32(rng.uniform(10, 300))
         args = (float(S0), float(np.float32(S0 * rng.uniform(0.4, 2.0))), float(np.float32(rng.uniform(0.02, 5))),
                 float(np.float32(rng.uniform(0, 0.2))), float(np.float32(rng.uniform(0.03, 1.0))))
-        assert np.float32(oracle.bs_call_f32(*args)) == np.float32(L.ref_black_scholes_CPU(*args)), args
+        assert np.float32(oracle.bs_call_f32(*args)) == np.float32(want[i]), args
 
 
 # ---------------- array-driven pricer: inc/testing.cuh:75-91 ----------------
@@ -66,23 +64,15 @@ def test_array_driven_survey_vector(oracle, golden):
     assert abs(c["ref_mean_undiscounted"] - 10.180830) < 5e-6
 
 
-def test_array_driven_against_reference_library_fresh_inputs(oracle):
-    L = oracle.ref_cpumc()
-    if L is None:
-        pytest.skip("oracle/_ref not built (no /root/reference on this machine)")
-    assert L.ref_sizeof_OptionData() == 48  # inc/tool.cuh:13-26: 12 x 4 bytes
-    pf = C.POINTER(C.c_float)
-    for seed, n_paths, n_steps in ((1, 64, 1), (2, 33, 100), (3, 7, 252)):
-        z = np.zeros(n_paths * n_steps, dtype=np.float32)
-        L.ref_mt19937_normals(seed, z.size, z.ctypes.data_as(pf))
-        dt = np.float32(1.0) / np.float32(n_steps)
-        sq = np.sqrt(dt, dtype=np.float32)
-        pay = np.zeros(n_paths, dtype=np.float32)
-        m = L.ref_simulateOptionPriceCPU_array(n_paths, n_steps, z.ctypes.data_as(pf), 100.0, 0.2, float(sq), 0.1, 100.0,
-                                               float(dt), pay.ctypes.data_as(pf))
-        m2, pay2 = oracle.price_from_normals(z, n_paths, n_steps, 100.0, 0.2, 0.1, 100.0, 1.0)
-        assert np.array_equal(pay, pay2)
-        assert np.float32(m) == np.float32(m2)
+def test_array_driven_against_reference_library_fresh_inputs(oracle, golden):
+    g = golden("ref_library.json")
+    assert g["sizeof_OptionData"] == 48  # inc/tool.cuh:13-26: 12 x 4 bytes
+    for c in g["array_driven_fresh"]:   # the reference's mt19937 normals and its array-driven pricer's output on them
+        z = np.array(c["normals"], dtype=np.float32)
+        assert z.size == c["n_paths"] * c["n_steps"]
+        m2, pay2 = oracle.price_from_normals(z, c["n_paths"], c["n_steps"], 100.0, 0.2, 0.1, 100.0, 1.0)
+        assert np.array_equal(np.array(c["ref_payoffs"], dtype=np.float32), pay2)
+        assert np.float32(c["ref_mean_undiscounted"]) == np.float32(m2)
 
 
 def test_array_driven_empty_input(oracle):
@@ -185,17 +175,16 @@ def test_mc_bullet_window_and_counts(oracle):
     assert abs(fin["price"] - 4.839) < 4 * fin["std_err"] + 0.05
 
 
-def test_mc_bullet_statistical_agreement_with_reference_cpu(oracle):
-    L = oracle.ref_cpumc()
-    if L is None:
-        pytest.skip("oracle/_ref not built (no /root/reference on this machine)")
-    n = 200_000
-    ref = L.ref_simulateBulletOptionPriceCPU(100.0, 1.0, 100.0, 0.1, 0.2, 120.0, 10, 50, n, 100)
+def test_mc_bullet_statistical_agreement_with_reference_cpu(oracle, golden):
+    u = golden("ref_library.json")["unseeded_mc"]   # one run of the reference's (unseeded) CPU pricers
+    n = u["paths"]
+    assert n == 200_000
+    ref = u["bullet_B120_P1_10_P2_50_100_steps"]
     p = oracle.make_params(**BENCH, B=120.0, P1=10, P2=50, n_paths=n, n_steps=100, seed=77, use_window=1)
     res = oracle.mc_paths(p, 32, 0, n, threads=oracle.max_threads())
     fin = oracle.finalize(res["sum"], res["sumsq"], n, p.r, p.T)
     assert abs(fin["price"] - ref) < 5 * math.sqrt(2) * fin["std_err"]
-    ref1 = L.ref_simulateOptionPriceCPU(100.0, 1.0, 100.0, 0.1, 0.2, n)
+    ref1 = u["european_1_step"]
     assert abs(ref1 - oracle.bs_call_f64(100, 100, 1, 0.1, 0.2)) < 5 * 16.109 / math.sqrt(n)
 
 

@@ -12,7 +12,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 python3 -c "import sys; sys.path.insert(0, '$R'); import importlib; print(importlib.import_module('monte-carlo-project-cuda_amd').capi.build_id())" > "$OUT/build_id.txt"
 case "$MODE" in
-  default) BENCH=(python3 "$R/bench.py" --steps 40 --warmup 5 --no-cpu-baseline --no-accuracy --no-sweep --no-nmc) ;;
+  default) BENCH=(python3 "$R/bench.py" --steps 40 --warmup 5 --full --no-cpu-baseline --no-accuracy --no-sweep --no-nmc) ;;
   nmc)     BENCH=(python3 "$R/bench.py" --workload nmc --steps 1 --warmup 1 --no-cpu-baseline) ;;
   nmc_all) BENCH=(python3 "$R/tools/nmc_strategies.py") ;;
   nmc_eu)  BENCH=(python3 "$R/bench.py" --workload nmc --nmc-window european --steps 1 --warmup 0 --no-cpu-baseline) ;;
