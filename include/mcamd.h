@@ -358,6 +358,73 @@ int mcamd_group_nmc_fused(mcamd_group *group, const mcamd_option *opt, const mca
                           int layout, void *const *d_prices, int32_t *const *d_counts, void *const *d_point_prices,
                           mcamd_result *res);
 
+/* ---- Greeks: in-kernel sensitivities of the call price ----
+ * One call simulates the job's paths once and returns the price and five sensitivities with their standard errors:
+ * every path contributes one undiscounted sample of each (formed once per path, in fp64 from the path-precision state),
+ * the kernel sums them and their squares in fp64, and value = D * mean, std_err = D * sqrt(s^2 / n) with
+ * D = exp(-r T) (the full T, as everywhere in the engine).  The paths are mcamd_price_paths' (same Philox stream =
+ * global path id, same arithmetic), so the price sample is the same payoff and any sharding gives the same sums up to
+ * fp64 summation order; a finite difference of mcamd_price_paths calls with the same seed (common random numbers)
+ * is an independent check.  New (the reference has no sensitivities).
+ * Notation: S_s = Sk if Sk > 0 else S0 (start of the simulated segment), T_h = (n_steps - Tk) dt the simulated
+ * horizon, L = ln(S_T / S_s), z_i the path's normals.  Sensitivities are with respect to S_s, v, r and — theta —
+ * the maturity (theta = -dV/dT).
+ *   MCAMD_GREEKS_PATHWISE (European, use_window = 0, only): the pair-sum loop of mcamd_price_paths plus an epilogue.
+ *     delta 1{S_T>K} S_T / S_s;  gamma (mixed pathwise-LR) 1{S_T>K} K (L - (r - v^2/2) T_h) / (S_s^2 v^2 T_h);
+ *     vega 1{S_T>K} S_T (L - (r + v^2/2) T_h) / v;  rho -T (S_T-K)+ + 1{S_T>K} S_T T_h;
+ *     theta r (S_T-K)+ - 1{S_T>K} S_T ((r - v^2/2) + (L - (r - v^2/2) T) / (2T)), defined only when Tk == 0 and
+ *     opt->dt == 0 (the simulated horizon is the maturity); NaN otherwise.
+ *   MCAMD_GREEKS_LIKELIHOOD_RATIO (any payoff; y the payoff, the bullet window included — its payoff is discontinuous
+ *     in the barrier count, which makes pathwise estimators wrong there):
+ *     delta y z_1 / (S_s v sqrt(dt));  gamma y ((z_1^2 - 1) / (S_s^2 v^2 dt) - z_1 / (S_s^2 v sqrt(dt)));
+ *     vega y sum_i ((z_i^2 - 1) / v - z_i sqrt(dt));  rho y (sum_i z_i sqrt(dt) / v - T);  theta NaN.
+ *     The LR variance grows as the step shrinks (gamma like 1 / dt): prefer pathwise wherever it applies.  A bullet
+ *     job runs one path per thread without lane compaction (its wavefronts still stop once every window is closed).
+ *   MCAMD_GREEKS_AUTO: pathwise without a window, likelihood ratio with one.
+ * Requirements: v > 0; sim->flags 0 or MCAMD_FLAG_LOG_SPACE (MCAMD_FLAG_ANTITHETIC, _CONTROL_VARIATE, _PRODUCT_FORM
+ * and _SEPARATE_REDUCE are MCAMD_ERR_INVALID for now); MCAMD_GREEKS_PATHWISE with use_window = 1 is MCAMD_ERR_INVALID.
+ * Other argument checks are mcamd_price_paths'.  An empty shard returns an all-zero record. */
+#define MCAMD_GREEKS_AUTO 0
+#define MCAMD_GREEKS_PATHWISE 1
+#define MCAMD_GREEKS_LIKELIHOOD_RATIO 2
+
+#define MCAMD_GREEK_PRICE 0
+#define MCAMD_GREEK_DELTA 1
+#define MCAMD_GREEK_GAMMA 2
+#define MCAMD_GREEK_VEGA 3
+#define MCAMD_GREEK_RHO 4
+#define MCAMD_GREEK_THETA 5
+
+typedef struct mcamd_greeks {
+    double value[6];    /* D * mean, indexed MCAMD_GREEK_*; theta NaN where it is not defined */
+    double std_err[6];  /* D * sqrt(s^2 / n) */
+    double sum[6];      /* the shard's raw fp64 sums of the undiscounted samples (what a multi-GPU caller all-reduces) */
+    double sumsq[6];    /* and of their squares */
+    uint64_t n;         /* paths */
+    int32_t method;     /* MCAMD_GREEKS_PATHWISE or MCAMD_GREEKS_LIKELIHOOD_RATIO: the estimator actually used */
+    float kernel_ms;    /* HIP-event time of the kernel (it finishes its own sum: the whole call's device work) */
+    float total_ms;
+    uint32_t grid;      /* launch shape the engine chose */
+    uint32_t block;
+    int32_t reserved;
+} mcamd_greeks;
+
+int mcamd_price_greeks(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, int method, mcamd_greeks *out);
+/* Asynchronous form: d_stats (device, >= 16 doubles) receives [0..12) the (sum, sumsq) pairs of price, delta, gamma,
+ * vega, rho, theta in that order, [12] = n, [13..16) = 0 — one all-reduce of 16 doubles carries a shard.  Until the
+ * kernel has written it, the record reads NaN.  mcamd_enqueued_kernel_ms covers this call. */
+int mcamd_price_greeks_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, int method,
+                               double *d_stats);
+/* Host: value / std_err / sums / n of a (possibly all-reduced) 16-double Greeks record; theta_defined = 0 reports
+ * theta as NaN.  method, timings and launch shape are left 0. */
+int mcamd_finalize_greeks_stats(const double stats[16], double r, double T, int theta_defined, mcamd_greeks *out);
+/* The group form: shards as mcamd_group_price_paths, ONE all-reduce of the 16-double record. */
+int mcamd_group_price_greeks(mcamd_group *group, const mcamd_option *opt, const mcamd_sim *sim, int method,
+                             mcamd_greeks *out);
+/* Host closed form (Black-Scholes call, exact erfc form): out = {price, N(d1), phi(d1) / (S v sqrt(T)),
+ * S phi(d1) sqrt(T), K T e^{-rT} N(d2), -S phi(d1) v / (2 sqrt(T)) - r K e^{-rT} N(d2)} in MCAMD_GREEK_* order. */
+int mcamd_bs_greeks_f64(double S0, double K, double T, double r, double v, double out[6]);
+
 /* Host: discount + mean + standard error + 95% CI from (sum, sumsq, n) — after an all-reduce
  * over shards, or directly.  Fills price/std_err/ci_* (and copies sum/sumsq/n) in *res. */
 int mcamd_finalize(double sum, double sumsq, uint64_t n, double r, double T, mcamd_result *res);

@@ -19,6 +19,10 @@ STEP_MAJOR, PATH_MAJOR = 0, 1
 NMC_WAVE_PER_POINT, NMC_BLOCK_PER_POINT, NMC_BLOCK_PER_POINT_PLAIN = 0, 1, 2
 FLAG_LOG_SPACE, FLAG_ANTITHETIC, FLAG_CONTROL_VARIATE, FLAG_SEPARATE_REDUCE, FLAG_PRODUCT_FORM = 1, 2, 4, 8, 16
 REDUCE_SEQUENTIAL, REDUCE_FIRST_ADD, REDUCE_UNROLL_LAST, REDUCE_GRID_STRIDE = 3, 4, 5, 6
+GREEKS_AUTO, GREEKS_PATHWISE, GREEKS_LIKELIHOOD_RATIO = 0, 1, 2
+GREEK_PRICE, GREEK_DELTA, GREEK_GAMMA, GREEK_VEGA, GREEK_RHO, GREEK_THETA = range(6)
+GREEK_NAMES = ("price", "delta", "gamma", "vega", "rho", "theta")
+GREEKS_STATS = 16   # doubles of a Greeks statistics record: six (sum, sumsq) pairs, n, zeros
 
 # every symbol include/mcamd.h declares
 EXPORTS = [
@@ -30,7 +34,8 @@ EXPORTS = [
     "mcamd_group_nmc_inner", "mcamd_group_nmc_fused", "mcamd_simulate_trajectories_enqueue", "mcamd_diag_store_pattern", "mcamd_nmc_inner_enqueue",
     "mcamd_nmc_fused_enqueue", "mcamd_finalize_nmc_stats", "mcamd_simulate_trajectories", "mcamd_price_from_normals",
     "mcamd_generate_normals", "mcamd_reduce_sum", "mcamd_reduce_partials", "mcamd_cpu_mc_f32", "mcamd_nmc_inner", "mcamd_nmc_fused", "mcamd_finalize", "mcamd_finalize_cv", "mcamd_cnd_f32",
-    "mcamd_bs_call_f32", "mcamd_bs_call_f64",
+    "mcamd_bs_call_f32", "mcamd_bs_call_f64", "mcamd_price_greeks", "mcamd_price_greeks_enqueue",
+    "mcamd_finalize_greeks_stats", "mcamd_group_price_greeks", "mcamd_bs_greeks_f64",
 ]
 
 
@@ -55,6 +60,17 @@ class Result(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class Greeks(C.Structure):
+    """mcamd_greeks: value / std_err / raw sums of price, delta, gamma, vega, rho, theta (indexed GREEK_*)."""
+    _fields_ = [("value", C.c_double * 6), ("std_err", C.c_double * 6), ("sum", C.c_double * 6),
+                ("sumsq", C.c_double * 6), ("n", C.c_uint64), ("method", C.c_int32), ("kernel_ms", C.c_float),
+                ("total_ms", C.c_float), ("grid", C.c_uint32), ("block", C.c_uint32), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        """{name: (value, std_err)} of the six quantities"""
+        return {name: (self.value[i], self.std_err[i]) for i, name in enumerate(GREEK_NAMES)}
 
 
 class DeviceInfo(C.Structure):
@@ -133,6 +149,11 @@ def load() -> C.CDLL:
     L.mcamd_bs_call_f32.restype = f32
     L.mcamd_bs_call_f64.argtypes = [f64] * 5
     L.mcamd_bs_call_f64.restype = f64
+    L.mcamd_price_greeks.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), i32, C.POINTER(Greeks)]
+    L.mcamd_price_greeks_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), i32, vp]
+    L.mcamd_finalize_greeks_stats.argtypes = [C.POINTER(f64), f64, f64, i32, C.POINTER(Greeks)]
+    L.mcamd_group_price_greeks.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), i32, C.POINTER(Greeks)]
+    L.mcamd_bs_greeks_f64.argtypes = [f64, f64, f64, f64, f64, C.POINTER(f64)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("mcamd_abi_version",):
@@ -191,6 +212,21 @@ def finalize_nmc_stats(stats6) -> Result:
     arr = (C.c_double * 6)(*[float(x) for x in stats6])
     _check(load().mcamd_finalize_nmc_stats(arr, C.byref(res)))
     return res
+
+
+def finalize_greeks_stats(stats16, r, T, theta_defined=True) -> Greeks:
+    """Greeks of a (possibly all-reduced) 16-double record left by Context.price_greeks_enqueue."""
+    out = Greeks()
+    arr = (C.c_double * GREEKS_STATS)(*[float(x) for x in stats16])
+    _check(load().mcamd_finalize_greeks_stats(arr, r, T, int(theta_defined), C.byref(out)))
+    return out
+
+
+def bs_greeks_f64(S0, K, T, r, sigma):
+    """closed-form (price, delta, gamma, vega, rho, theta) of the call"""
+    arr = (C.c_double * 6)()
+    _check(load().mcamd_bs_greeks_f64(S0, K, T, r, sigma, arr))
+    return list(arr)
 
 
 def cpu_mc_f32(opt: Option, n_paths: int, n_steps: int, seed: int = 0, from_random_device: bool = False):
@@ -260,6 +296,15 @@ class Context:
     def price_paths_enqueue(self, opt: Option, sim: Sim, stats) -> None:
         """Asynchronous: leaves {sum, sumsq, sum_c, sum_cc, sum_yc, n} in the device tensor `stats` (>= 6 doubles)."""
         _check(self._L.mcamd_price_paths_enqueue(self._h, C.byref(opt), C.byref(sim), _ptr(stats)))
+
+    def price_greeks(self, opt: Option, sim: Sim, method: int = GREEKS_AUTO) -> Greeks:
+        out = Greeks()
+        _check(self._L.mcamd_price_greeks(self._h, C.byref(opt), C.byref(sim), method, C.byref(out)))
+        return out
+
+    def price_greeks_enqueue(self, opt: Option, sim: Sim, stats, method: int = GREEKS_AUTO) -> None:
+        """Asynchronous: leaves the 16-double Greeks record in the device tensor `stats` (finalize_greeks_stats)."""
+        _check(self._L.mcamd_price_greeks_enqueue(self._h, C.byref(opt), C.byref(sim), method, _ptr(stats)))
 
     def enqueued_kernel_ms(self, n_last: int):
         arr = (C.c_float * n_last)()
@@ -360,6 +405,11 @@ class Group:
         res = Result()
         _check(self._L.mcamd_group_price_paths(self._h, C.byref(opt), C.byref(sim), C.byref(res)))
         return res
+
+    def price_greeks(self, opt: Option, sim: Sim, method: int = GREEKS_AUTO) -> Greeks:
+        out = Greeks()
+        _check(self._L.mcamd_group_price_greeks(self._h, C.byref(opt), C.byref(sim), method, C.byref(out)))
+        return out
 
     def shard(self, sim: Sim, i: int):
         """(first global path id, number of paths) device i of the group works on for this job."""

@@ -3,6 +3,7 @@
 // the launchers of launch.hpp on the context's stream; there is no CPU fallback of any kind — a
 // call either runs the gfx950 kernels or returns an error.
 #include "launch.hpp"
+#include "greeks.hpp"
 
 #include "mcamd.h"
 
@@ -16,6 +17,7 @@
 static_assert(sizeof(mcamd_option) == 88 && sizeof(mcamd_sim) == 48 && sizeof(mcamd_result) == 128 &&
                   sizeof(mcamd_device_info) == 384,
               "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
+static_assert(sizeof(mcamd_greeks) == 224, "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
 
 namespace {
 
@@ -64,6 +66,8 @@ struct mcamd_ctx {
     double *h_out_dev = nullptr;            // h_out as the device addresses it (a self-finishing kernel writes there)
     uint32_t compute_units = 0;
     double *h_out = nullptr;       // pinned, 8 doubles
+    double *h_greeks = nullptr;    // pinned, 16 doubles: the Greeks kernel's statistics record (mcamd_price_greeks)
+    double *h_greeks_dev = nullptr;
     // asynchronous calls: a ring of event pairs around the simulation kernel of the last kRing enqueues
     static constexpr uint32_t kRing = 64;
     hipEvent_t ring0[kRing] = {}, ring1[kRing] = {};
@@ -328,10 +332,10 @@ void fill_nmc_result(mcamd_result *res, uint64_t n_points, uint32_t grid)
 }
 
 // Asynchronous calls: an empty shard leaves all-zero statistics, still ordered on the stream.
-int enqueue_empty(mcamd_ctx *ctx, double *d_stats)
+int enqueue_empty(mcamd_ctx *ctx, double *d_stats, int stats_doubles = 6)
 {
     const uint32_t slot = static_cast<uint32_t>(ctx->n_enqueued % mcamd_ctx::kRing);
-    HIP_TRY(hipMemsetAsync(d_stats, 0, 6 * sizeof(double), ctx->stream));
+    HIP_TRY(hipMemsetAsync(d_stats, 0, stats_doubles * sizeof(double), ctx->stream));
     HIP_TRY(hipEventRecord(ctx->ring0[slot], ctx->stream));
     HIP_TRY(hipEventRecord(ctx->ring1[slot], ctx->stream));
     ctx->n_enqueued++;
@@ -355,6 +359,80 @@ int enqueue_with_stats(mcamd_ctx *ctx, uint32_t grid, int rec, double n_value, d
     else if (how == Finish::kReduce) HIP_TRY(mcamd::launch_final_reduce(ctx->d_partials, grid, rec, d_stats, ctx->stream, n_value));
     ctx->n_enqueued++;
     return MCAMD_OK;
+}
+
+// The estimator a Greeks call runs: AUTO is pathwise without a window and likelihood ratio with one.  0 on a bad request.
+int greeks_method(const mcamd_option *opt, int method)
+{
+    if (method == MCAMD_GREEKS_AUTO) return opt->use_window ? MCAMD_GREEKS_LIKELIHOOD_RATIO : MCAMD_GREEKS_PATHWISE;
+    if (method == MCAMD_GREEKS_PATHWISE) return opt->use_window ? 0 : MCAMD_GREEKS_PATHWISE;
+    return method == MCAMD_GREEKS_LIKELIHOOD_RATIO ? method : 0;
+}
+
+// argument checks, estimator and job of the Greeks calls (shared by the synchronous call and the enqueue form)
+int prepare_greeks(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, int method, mcamd::GreeksJob *job,
+                   int *used)
+{
+    // the Greeks-specific refusals first: they depend on the request alone, not on a device
+    if (!opt || !sim) return fail(MCAMD_ERR_INVALID, "opt and sim must be non-NULL");
+    if (sim->flags & ~MCAMD_FLAG_LOG_SPACE)
+        return fail(MCAMD_ERR_INVALID, "Greeks take flags 0 or MCAMD_FLAG_LOG_SPACE only, got %d", sim->flags);
+    *used = greeks_method(opt, method);
+    if (*used == 0)
+        return fail(MCAMD_ERR_INVALID, method == MCAMD_GREEKS_PATHWISE
+                                           ? "pathwise Greeks are wrong for the bullet window's discontinuous payoff: use "
+                                             "MCAMD_GREEKS_LIKELIHOOD_RATIO (or AUTO) with use_window = 1"
+                                           : "unknown Greeks method %d", method);
+    const double S_s = (opt->Sk == 0.0) ? opt->S0 : opt->Sk;
+    if (!(opt->v > 0.0) || !(S_s > 0.0))
+        return fail(MCAMD_ERR_INVALID, "Greeks need v > 0 and a positive start price (v = %g, S = %g)", opt->v, S_s);
+    mcamd_result dummy;
+    if (int rc = check_common(ctx, opt, sim, &dummy)) return rc;
+    job->path = make_job(opt, sim);
+    job->path.logspace = true;
+    job->path.vr = 0;
+    job->lr = *used == MCAMD_GREEKS_LIKELIHOOD_RATIO;
+    const double dt = opt->dt > 0.0 ? opt->dt : opt->T / static_cast<double>(sim->n_steps);
+    const double v = opt->v, r = opt->r, T = opt->T, T_h = dt * static_cast<double>(job->path.n_sim);
+    mcamd::GreeksConsts &g = job->g;
+    g.K = opt->K;
+    g.S_s = S_s;
+    g.T = T;
+    g.r = r;
+    g.v = v;
+    g.T_h = T_h;
+    g.mu_h = (r - 0.5 * v * v) * T_h;
+    g.nu_h = (r + 0.5 * v * v) * T_h;
+    g.gamma_pw = 1.0 / (S_s * S_s * v * v * T_h);
+    g.theta_mu = r - 0.5 * v * v;
+    g.theta_mu_T = g.theta_mu * T;
+    g.inv_2T = 0.5 / T;
+    g.inv_scale = 0.0;   // set by the launcher: the unit of the path precision's exponent
+    g.sqrt_dt = std::sqrt(dt);
+    g.delta_lr = 1.0 / (S_s * v * g.sqrt_dt);
+    g.gamma_lr1 = 1.0 / (S_s * S_s * v * v * dt);
+    g.gamma_lr2 = 1.0 / (S_s * S_s * v * g.sqrt_dt);
+    g.theta_on = (*used == MCAMD_GREEKS_PATHWISE && opt->Tk == 0 && opt->dt == 0.0) ? 1 : 0;
+    return MCAMD_OK;
+}
+
+void finalize_greeks_into(const double stats[16], double r, double T, int theta_defined, mcamd_greeks *out)
+{
+    const double disc = std::exp(-r * T);
+    const uint64_t n = static_cast<uint64_t>(std::llround(stats[mcamd::kGreeksRecord]));
+    const double N = static_cast<double>(n);
+    out->n = n;
+    for (int k = 0; k < mcamd::kGreeks; ++k) {
+        const double sum = stats[2 * k], sumsq = stats[2 * k + 1];
+        const double mean = n ? sum / N : 0.0;
+        double var = n > 1 ? (sumsq - N * mean * mean) / (N - 1.0) : 0.0;
+        if (var < 0.0) var = 0.0;
+        out->sum[k] = sum;
+        out->sumsq[k] = sumsq;
+        out->value[k] = disc * mean;
+        out->std_err[k] = n ? disc * std::sqrt(var / N) : 0.0;
+    }
+    if (!theta_defined) out->value[MCAMD_GREEK_THETA] = out->std_err[MCAMD_GREEK_THETA] = std::nan("");
 }
 
 }  // namespace
@@ -435,6 +513,8 @@ int mcamd_ctx_create(int device, void *hip_stream, mcamd_ctx **out)
     ctx->compute_units = static_cast<uint32_t>(prop.multiProcessorCount);
     if (e == hipSuccess) e = hipHostMalloc(&ctx->h_out, 8 * sizeof(double), hipHostMallocDefault);
     if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void **>(&ctx->h_out_dev), ctx->h_out, 0);
+    if (e == hipSuccess) e = hipHostMalloc(&ctx->h_greeks, mcamd::kGreeksStats * sizeof(double), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void **>(&ctx->h_greeks_dev), ctx->h_greeks, 0);
     if (e != hipSuccess) {
         mcamd_ctx_destroy(ctx);
         return fail(MCAMD_ERR_HIP, "context setup: %s", hipGetErrorString(e));
@@ -452,6 +532,7 @@ int mcamd_ctx_destroy(mcamd_ctx *ctx)
     if (ctx->d_out) (void)hipFree(ctx->d_out);
     if (ctx->d_queue) (void)hipFree(ctx->d_queue);
     if (ctx->h_out) (void)hipHostFree(ctx->h_out);
+    if (ctx->h_greeks) (void)hipHostFree(ctx->h_greeks);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     if (ctx->ev2) (void)hipEventDestroy(ctx->ev2);
@@ -852,6 +933,86 @@ int mcamd_cpu_mc_f32(const mcamd_option *opt, uint64_t n_paths, uint32_t n_steps
     }
     if (payoff_sum) *payoff_sum = sum;
     *price = expf(-r * T) * sum / static_cast<float>(n_paths);
+    return MCAMD_OK;
+}
+
+int mcamd_price_greeks(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, int method, mcamd_greeks *out)
+{
+    if (!out) return fail(MCAMD_ERR_INVALID, "out is NULL");
+    std::memset(out, 0, sizeof *out);
+    mcamd::GreeksJob job;
+    int used = 0;
+    if (int rc = prepare_greeks(ctx, opt, sim, method, &job, &used)) return rc;
+    out->method = used;
+    if (sim->n_paths_local == 0) return MCAMD_OK;  // empty shard: all-zero record
+    HIP_TRY(hipSetDevice(ctx->device));
+    const uint32_t grid = mcamd::greeks_grid(job);
+    if (int rc = ensure_partials(ctx, grid, mcamd::kGreeksRecord)) return rc;
+    // the kernel's last workgroup writes the record into pinned host memory; a NaN left there means it never did
+    // (e.g. an arrival ticket that was not zero at launch): fail loudly instead of returning the previous call's sums
+    for (int k = 0; k < mcamd::kGreeksStats; ++k) ctx->h_greeks[k] = std::nan("");
+    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+    HIP_TRY(mcamd::launch_greeks(job, ctx->d_partials, grid, ctx->h_greeks_dev, ctx->d_ticket, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipEventElapsedTime(&out->kernel_ms, ctx->ev0, ctx->ev1));
+    double stats[mcamd::kGreeksStats];
+    std::memcpy(stats, ctx->h_greeks, sizeof stats);
+    if (std::isnan(stats[0]) || std::isnan(stats[mcamd::kGreeksRecord]))
+        return fail(MCAMD_ERR_HIP, "Greeks kernel left no result (its last workgroup did not finish the sum)");
+    const float kms = out->kernel_ms;
+    finalize_greeks_into(stats, opt->r, opt->T, job.g.theta_on, out);
+    out->kernel_ms = out->total_ms = kms;   // one launch is the whole call
+    out->grid = grid;
+    out->block = 256;
+    return MCAMD_OK;
+}
+
+int mcamd_price_greeks_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, int method,
+                               double *d_stats)
+{
+    mcamd::GreeksJob job;
+    int used = 0;
+    if (int rc = prepare_greeks(ctx, opt, sim, method, &job, &used)) return rc;
+    if (!d_stats) return fail(MCAMD_ERR_INVALID, "d_stats is NULL");
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (sim->n_paths_local == 0) return enqueue_empty(ctx, d_stats, mcamd::kGreeksStats);
+    const uint32_t grid = mcamd::greeks_grid(job);
+    // NaN (all-ones bytes) until the kernel has written the record
+    HIP_TRY(hipMemsetAsync(d_stats, 0xFF, mcamd::kGreeksStats * sizeof(double), ctx->stream));
+    return enqueue_with_stats(ctx, grid, mcamd::kGreeksRecord, static_cast<double>(sim->n_paths_local), d_stats,
+                              Finish::kFolded, [&] {
+                                  return mcamd::launch_greeks(job, ctx->d_partials, grid, d_stats, ctx->d_ticket,
+                                                              ctx->stream);
+                              });
+}
+
+int mcamd_finalize_greeks_stats(const double stats[16], double r, double T, int theta_defined, mcamd_greeks *out)
+{
+    if (!stats || !out) return fail(MCAMD_ERR_INVALID, "stats and out must be non-NULL");
+    std::memset(out, 0, sizeof *out);
+    finalize_greeks_into(stats, r, T, theta_defined, out);
+    return MCAMD_OK;
+}
+
+int mcamd_bs_greeks_f64(double S0, double K, double T, double r, double v, double out[6])
+{
+    if (!out) return fail(MCAMD_ERR_INVALID, "out is NULL");
+    if (!(S0 > 0.0) || !(K > 0.0) || !(T > 0.0) || !(v > 0.0) || !std::isfinite(S0) || !std::isfinite(K) ||
+        !std::isfinite(T) || !std::isfinite(r) || !std::isfinite(v))
+        return fail(MCAMD_ERR_INVALID, "closed-form Greeks need finite S0, K, T, v > 0 and a finite r");
+    const double sqrtT = std::sqrt(T);
+    const double d1 = (std::log(S0 / K) + (r + 0.5 * v * v) * T) / (v * sqrtT);
+    const double d2 = d1 - v * sqrtT;
+    const double Nd1 = 0.5 * std::erfc(-d1 / std::sqrt(2.0)), Nd2 = 0.5 * std::erfc(-d2 / std::sqrt(2.0));
+    const double phi = std::exp(-0.5 * d1 * d1) / std::sqrt(2.0 * M_PI);
+    const double Kdisc = K * std::exp(-r * T);
+    out[MCAMD_GREEK_PRICE] = mcamd_bs_call_f64(S0, K, T, r, v);
+    out[MCAMD_GREEK_DELTA] = Nd1;
+    out[MCAMD_GREEK_GAMMA] = phi / (S0 * v * sqrtT);
+    out[MCAMD_GREEK_VEGA] = S0 * phi * sqrtT;
+    out[MCAMD_GREEK_RHO] = Kdisc * T * Nd2;
+    out[MCAMD_GREEK_THETA] = -S0 * phi * v / (2.0 * sqrtT) - r * Kdisc * Nd2;
     return MCAMD_OK;
 }
 
