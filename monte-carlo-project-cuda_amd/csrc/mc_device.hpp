@@ -387,11 +387,15 @@ struct PairSum<float> {
         acc = __builtin_fmaf(t1, __builtin_amdgcn_sinf(r1), acc);
         return __builtin_fmaf(t2, __builtin_amdgcn_sinf(r2), acc);
     }
-    __device__ __forceinline__ static float head(const MathCtx<float> &, const PhiloxKeys &key, uint64_t subsequence,
+    __device__ __forceinline__ static float head(const MathCtx<float> &m, const PhiloxKeys &key, uint64_t subsequence,
                                                   uint64_t block, uint32_t n)
     {
+        return head_words(philox_block(key, subsequence, block), m, n);
+    }
+    // head() on the block's four Philox words
+    __device__ __forceinline__ static float head_words(const U4 &w, const MathCtx<float> &, uint32_t n)
+    {
         constexpr float kInvSqrt2 = 0.70710678118654752f;
-        const U4 w = philox_block(key, subsequence, block);
         float t, rev;
         if (n == 1) {   // z0 alone: the sine member of the first pair
             polar(w.x, w.y, 0.0f, t, rev);
@@ -413,7 +417,11 @@ struct PairSum<double> {
     __device__ __forceinline__ static double add_block(double acc, const MathCtx<double> &m, const PhiloxKeys &key,
                                                         uint64_t subsequence, uint64_t block)
     {
-        const U4 w = philox_block(key, subsequence, block);
+        return add_words(acc, philox_block(key, subsequence, block), m);
+    }
+    // add_block() on the block's four Philox words
+    __device__ __forceinline__ static double add_words(double acc, const U4 &w, const MathCtx<double> &m)
+    {
         const double u = f64::u53(w.x, w.y, 0x1p-53);
         const double r = f64::sqrt_unclamped(f64::neg2log(u, m.t.log_tab));   // strictly positive argument (fast64.hpp)
         return __builtin_fma(r, f64::sin_bits_rotated<false>(w.z, w.w, m.t.sincos_tab, nullptr), acc);
@@ -422,7 +430,10 @@ struct PairSum<double> {
     __device__ __forceinline__ static double head(const MathCtx<double> &m, const PhiloxKeys &key, uint64_t subsequence,
                                                    uint64_t block, uint32_t)
     {
-        const U4 w = philox_block(key, subsequence, block);
+        return head_words(philox_block(key, subsequence, block), m);
+    }
+    __device__ __forceinline__ static double head_words(const U4 &w, const MathCtx<double> &m)
+    {
         const double u = f64::u53(w.x, w.y, 0x1p-53);
         const double r = f64::sqrt_unclamped(f64::neg2log(u, m.t.log_tab));
         double cs;

@@ -42,7 +42,7 @@ int main(int argc, char **argv)
         const uint32_t z = static_cast<uint32_t>(b), w = static_cast<uint32_t>(b >> 32);
         if (i % 7 == 0) { y = 0xffffffffu; x |= 0xfffff000u; }  // u close to 1
         if (i % 11 == 0) { y &= 0xfffu; }                         // small u
-        if (i == 1) { x = 0xffffffffu; y = 0xffffffffu; }         // u == 1 exactly
+        if (i == 1) { x = 0x001fffffu; y = 0xffffffffu; }         // u == 1 exactly (v1 = x ^ (y << 21) = 2^53 - 1)
         if (i == 2) { x = 0; y = 0; }                             // u == 2^-53
         const double u = u53(x, y, 0x1p-53);
         const uint64_t v1 = static_cast<uint64_t>(x) ^ (static_cast<uint64_t>(y) << 21);
@@ -84,7 +84,9 @@ int main(int argc, char **argv)
         if (erc > e_rotc) e_rotc = erc;
         if (sin_bits_rotated<false>(zz, ww, rot, nullptr) != rs) e_rot = 1.0;
         // a whole pair sum as PairSum<double> forms it, against the sum of the two normals, relative to the radius
-        if (aa > 0) {
+        // (u == 1: -2 ln u is the biased table term 4e-18, not 0, so the radius is 2e-9 — a bound of its own)
+        if (u == 1.0) { if (!(std::fabs(sqrt_unclamped(aa) * rs) <= 3e-9)) e_pair = 1.0; }
+        else if (aa > 0) {
             const double r = sqrt_unclamped(aa);
             const long double want = sqrtl(want_a) * (sinl(ang) + cosl(ang));
             const double ep = std::fabs(static_cast<double>(static_cast<long double>(r * rs) * SQ2 - want)) / (1.0 + static_cast<double>(sqrtl(want_a)));
