@@ -425,6 +425,79 @@ int mcamd_group_price_greeks(mcamd_group *group, const mcamd_option *opt, const 
  * S phi(d1) sqrt(T), K T e^{-rT} N(d2), -S phi(d1) v / (2 sqrt(T)) - r K e^{-rT} N(d2)} in MCAMD_GREEK_* order. */
 int mcamd_bs_greeks_f64(double S0, double K, double T, double r, double v, double out[6]);
 
+/* ---- American / Bermudan options: least-squares Monte Carlo (Longstaff and Schwartz, 2001) ----
+ * A put or call on GBM that may be exercised every k-th step.  dt = T / n_steps; exercise dates j = 1..M at steps
+ * s_j = j k (M = n_steps / k; date M is maturity), t_j = s_j dt, d_j = exp(-r t_j); S_{p,j} is path p after step s_j
+ * (the product-form path of mcamd_simulate_trajectories, in the path precision; regression arithmetic is fp64 on
+ * (double) S); h(S) = max(K - S, 0) for a put, max(S - K, 0) for a call; basis phi(S) = (1, u, .., u^(m-1)) with
+ * u = S / K - 1, m = n_basis.
+ *  1. Training (the backward sweep) on n_train paths of train_seed, global ids 0..n_train-1, stored whole on this
+ *     context's device: V_p = d_M h(S_{p,M}); for j = M-1 .. 1, over I_j = {p : h(S_{p,j}) > 0}, solve
+ *     (sum phi phi^T) beta_j = sum V_p phi by Cholesky of the Jacobi-scaled matrix; date j is not regressed (no
+ *     exercise there) when |I_j| < 4 m or a scaled pivot is <= 1e-12; otherwise V_p = d_j h(S_{p,j}) for the p of
+ *     I_j with d_j h(S_{p,j}) > phi(S_{p,j}) . beta_j.  The mean of V is the in-sample estimate (biased high).
+ *  2. Pricing on the job's shard (sim->seed, global ids path_offset + i): a path's sample is d_j h(S) at the first
+ *     regressed date j < M where h > 0 and d_j h(S) > phi(S) . beta_j, else d_M h(S_M).  The mean is the
+ *     out-of-sample estimate (biased low: the rule is fitted on other paths); its SE is an honest one.
+ * Both passes decide through one device function, so with train_seed == sim->seed and n_train == n_paths they
+ * see the same paths and make the same decisions.  Samples are discounted where they are paid: the estimates are
+ * plain means (no exp(-rT) factor).  Exercise at t = 0: where h(S0) exceeds an estimate, h(S0) is reported in its
+ * place with std_err 0, and immediate_exercise is set.  Multi-GPU: every rank trains identically with the same
+ * train_seed and prices its own shard; the raw sums (sum, sumsq, n, n_early, sum_t_exercise) add over shards.
+ * Requirements (MCAMD_ERR_INVALID before any device work): payoff 0/1, n_basis in {0, 2, 3, 4}, k >= 1 with
+ * n_steps % k == 0, reserved == 0, n_train >= 1, M <= 4096, use_window == 0, Tk == 0, Sk == 0, opt->dt == 0, v > 0,
+ * sim->flags 0, MCAMD_FLAG_LOG_SPACE or MCAMD_FLAG_PRODUCT_FORM (the product form runs either way), d_work and
+ * res non-NULL, work_bytes >= mcamd_american_workspace_bytes.  An empty pricing shard still trains and returns
+ * n = 0.  New (the reference prices European-style claims only). */
+#define MCAMD_PAYOFF_CALL 0
+#define MCAMD_PAYOFF_PUT 1
+
+typedef struct mcamd_american {
+    int32_t payoff;            /* MCAMD_PAYOFF_* */
+    uint32_t exercise_every;   /* k >= 1, n_steps % k == 0; k == n_steps: European exercise */
+    uint32_t n_basis;          /* 2..4; 0 = 3 */
+    uint32_t reserved;         /* must be 0 */
+    uint64_t n_train;          /* training paths, simulated whole on this context's device */
+    uint64_t train_seed;       /* may equal sim->seed (then the two passes see the same paths) */
+} mcamd_american;
+
+typedef struct mcamd_american_result {
+    double price;              /* out-of-sample estimate sum / n (h(S0) where that is larger) */
+    double std_err;            /* sqrt(s^2 / n) (0 where h(S0) was taken) */
+    double ci_lo, ci_hi;       /* price -/+ 1.96 std_err */
+    double sum, sumsq;         /* the shard's raw fp64 sums of the discounted samples */
+    uint64_t n;                /* paths priced (the shard) */
+    double in_sample_price;    /* mean of V over the training paths (h(S0) where that is larger) */
+    double in_sample_std_err;
+    double in_sample_sum, in_sample_sumsq;  /* sum of V and of V^2 */
+    uint64_t n_train;
+    uint64_t n_early;          /* paths of the shard exercised before maturity */
+    double sum_t_exercise;     /* sum of their exercise times t_j */
+    uint32_t n_dates;          /* M */
+    uint32_t n_regressed;      /* dates 1..M-1 with a fitted exercise rule */
+    int32_t immediate_exercise;/* 1: h(S0) exceeded an estimate and replaced it */
+    float train_ms;            /* HIP-event times: trajectory store + backward sweep */
+    float price_ms;            /* pricing kernel */
+    float total_ms;            /* the whole call's device work */
+    uint32_t grid;             /* pricing kernel's launch shape */
+    uint32_t block;
+    uint32_t train_grid;       /* backward sweep's workgroups per launch */
+    int32_t reserved;
+} mcamd_american_result;
+
+/* Bytes of the caller-owned device workspace of mcamd_price_american: with A(x) = x rounded up to 256,
+ *   256 + A(n_steps n_train sizeof(path precision))   stored training trajectories (step-major)
+ *       + A(8 n_train)                                  V
+ *       + A(8 (8 (M + 1) + 32))                          coefficient table (8 doubles per date) + two records
+ *       + A(8 max(2 G_store, 12 G_sweep))                block records
+ * G_store = min(max(ceil(ceil(n_train / V) / 256), 1), 2^20) with V = 4 (fp32) / 2 (fp64), G_sweep = min(ceil(n_train /
+ * 256), 8192).  Any alignment of d_work is accepted (the leading 256 bytes absorb it). */
+int mcamd_american_workspace_bytes(const mcamd_american *am, const mcamd_sim *sim, uint64_t *bytes);
+/* h_coeffs (nullable, host): M rows of n_basis + 1 doubles, row j-1 = beta_j then 1 (regressed) or 0; rows of dates
+ * without a rule (and row M, maturity) hold NaN coefficients and 0. */
+int mcamd_price_american(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_american *am,
+                         void *d_work, uint64_t work_bytes, double *h_coeffs, mcamd_american_result *res);
+
 /* Host: discount + mean + standard error + 95% CI from (sum, sumsq, n) — after an all-reduce
  * over shards, or directly.  Fills price/std_err/ci_* (and copies sum/sumsq/n) in *res. */
 int mcamd_finalize(double sum, double sumsq, uint64_t n, double r, double T, mcamd_result *res);

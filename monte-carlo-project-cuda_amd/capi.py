@@ -23,6 +23,7 @@ GREEKS_AUTO, GREEKS_PATHWISE, GREEKS_LIKELIHOOD_RATIO = 0, 1, 2
 GREEK_PRICE, GREEK_DELTA, GREEK_GAMMA, GREEK_VEGA, GREEK_RHO, GREEK_THETA = range(6)
 GREEK_NAMES = ("price", "delta", "gamma", "vega", "rho", "theta")
 GREEKS_STATS = 16   # doubles of a Greeks statistics record: six (sum, sumsq) pairs, n, zeros
+PAYOFF_CALL, PAYOFF_PUT = 0, 1
 
 # every symbol include/mcamd.h declares
 EXPORTS = [
@@ -36,6 +37,7 @@ EXPORTS = [
     "mcamd_generate_normals", "mcamd_reduce_sum", "mcamd_reduce_partials", "mcamd_cpu_mc_f32", "mcamd_nmc_inner", "mcamd_nmc_fused", "mcamd_finalize", "mcamd_finalize_cv", "mcamd_cnd_f32",
     "mcamd_bs_call_f32", "mcamd_bs_call_f64", "mcamd_price_greeks", "mcamd_price_greeks_enqueue",
     "mcamd_finalize_greeks_stats", "mcamd_group_price_greeks", "mcamd_bs_greeks_f64",
+    "mcamd_american_workspace_bytes", "mcamd_price_american",
 ]
 
 
@@ -71,6 +73,26 @@ class Greeks(C.Structure):
     def as_dict(self):
         """{name: (value, std_err)} of the six quantities"""
         return {name: (self.value[i], self.std_err[i]) for i, name in enumerate(GREEK_NAMES)}
+
+
+class American(C.Structure):
+    """mcamd_american: exercise rule and training set of mcamd_price_american."""
+    _fields_ = [("payoff", C.c_int32), ("exercise_every", C.c_uint32), ("n_basis", C.c_uint32),
+                ("reserved", C.c_uint32), ("n_train", C.c_uint64), ("train_seed", C.c_uint64)]
+
+
+class AmericanResult(C.Structure):
+    """mcamd_american_result: out-of-sample and in-sample estimates, raw shard sums, dates, timings."""
+    _fields_ = [("price", C.c_double), ("std_err", C.c_double), ("ci_lo", C.c_double), ("ci_hi", C.c_double),
+                ("sum", C.c_double), ("sumsq", C.c_double), ("n", C.c_uint64), ("in_sample_price", C.c_double),
+                ("in_sample_std_err", C.c_double), ("in_sample_sum", C.c_double), ("in_sample_sumsq", C.c_double),
+                ("n_train", C.c_uint64), ("n_early", C.c_uint64), ("sum_t_exercise", C.c_double),
+                ("n_dates", C.c_uint32), ("n_regressed", C.c_uint32), ("immediate_exercise", C.c_int32),
+                ("train_ms", C.c_float), ("price_ms", C.c_float), ("total_ms", C.c_float), ("grid", C.c_uint32),
+                ("block", C.c_uint32), ("train_grid", C.c_uint32), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class DeviceInfo(C.Structure):
@@ -154,6 +176,9 @@ def load() -> C.CDLL:
     L.mcamd_finalize_greeks_stats.argtypes = [C.POINTER(f64), f64, f64, i32, C.POINTER(Greeks)]
     L.mcamd_group_price_greeks.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), i32, C.POINTER(Greeks)]
     L.mcamd_bs_greeks_f64.argtypes = [f64, f64, f64, f64, f64, C.POINTER(f64)]
+    L.mcamd_american_workspace_bytes.argtypes = [C.POINTER(American), C.POINTER(Sim), C.POINTER(u64)]
+    L.mcamd_price_american.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(American), vp, u64,
+                                       C.POINTER(f64), C.POINTER(AmericanResult)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("mcamd_abi_version",):
@@ -176,6 +201,17 @@ def make_sim(n_paths, n_steps=1, precision=F64, seed=1234, path_offset=0, n_path
              n_paths_inner=0, flags=0) -> Sim:
     return Sim(n_paths, path_offset, n_paths if n_paths_local is None else n_paths_local, n_steps, n_paths_inner,
                seed, precision, flags)
+
+
+def make_american(payoff=PAYOFF_PUT, exercise_every=1, n_basis=0, n_train=100_000, train_seed=4321) -> American:
+    return American(payoff, exercise_every, n_basis, 0, n_train, train_seed)
+
+
+def american_workspace_bytes(am: American, sim: Sim) -> int:
+    """bytes of the device workspace mcamd_price_american needs for this rule, training set and step count"""
+    b = C.c_uint64(0)
+    _check(load().mcamd_american_workspace_bytes(C.byref(am), C.byref(sim), C.byref(b)))
+    return b.value
 
 
 def _ptr(t):
@@ -305,6 +341,22 @@ class Context:
     def price_greeks_enqueue(self, opt: Option, sim: Sim, stats, method: int = GREEKS_AUTO) -> None:
         """Asynchronous: leaves the 16-double Greeks record in the device tensor `stats` (finalize_greeks_stats)."""
         _check(self._L.mcamd_price_greeks_enqueue(self._h, C.byref(opt), C.byref(sim), method, _ptr(stats)))
+
+    def price_american(self, opt: Option, sim: Sim, am: American, work, coeffs: bool = False):
+        """Least-squares Monte Carlo price of an American / Bermudan put or call (mcamd_price_american).  work: a device
+        tensor of at least american_workspace_bytes(am, sim) bytes.  Returns the AmericanResult, and with coeffs=True
+        also the (M, n_basis + 1) array of per-date coefficients and regressed flags."""
+        res = AmericanResult()
+        nb = am.n_basis or 3
+        M = sim.n_steps // am.exercise_every if am.exercise_every else 0
+        arr = (C.c_double * (M * (nb + 1)))() if coeffs and M > 0 else None
+        nbytes = work.numel() * work.element_size() if work is not None else 0
+        _check(self._L.mcamd_price_american(self._h, C.byref(opt), C.byref(sim), C.byref(am), _ptr(work), nbytes, arr,
+                                            C.byref(res)))
+        if not coeffs:
+            return res
+        import numpy as np
+        return res, np.ctypeslib.as_array(arr).reshape(M, nb + 1).copy()
 
     def enqueued_kernel_ms(self, n_last: int):
         arr = (C.c_float * n_last)()

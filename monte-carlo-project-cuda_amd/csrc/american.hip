@@ -1,0 +1,365 @@
+// american.hip — least-squares Monte Carlo (Longstaff and Schwartz, 2001) for gfx950, both path precisions: the
+// backward sweep over the stored training trajectories and the out-of-sample pricing pass.
+//
+// Notation of include/mcamd.h: dates j = 1..M at steps s_j = j k, S_j the price after step s_j (stored row s_j - 1),
+// h the exercise value, u = S / K - 1, phi = (1, u, .., u^(m-1)), d_j = exp(-r t_j).  Regression arithmetic is fp64 on
+// (double) S whatever the path precision.
+//
+// Sweep, launch j (j = M-1 .. 0), one grid-stride pass over the n_train training paths:
+//   1. every workgroup reads the record launch j+1 finished and solves date j+1's 2..4-unknown normal equations —
+//      uniform and redundant, so every workgroup holds identical bits; workgroup 0 writes the table row of date j+1;
+//   2. each path applies date j+1's decision to V (launch M-1 sets V = d_M h(S_M) instead);
+//   3. each path adds to date j's record: the power sums P_0..P_6 of u, sum V u^q (q < 4) and |I_j| over the paths in
+//      the money at date j (launch 0: sum V and sum V^2, the in-sample estimate).  block_sumN + grid_finish sum the
+//      record in a fixed order and the last workgroup writes it to the workspace: no host round trip between dates.
+// Pricing: one path per thread, the product-form loop of the store kernel (same Philox blocks, same PathState), the
+// price evaluated at exercise dates only; a wavefront leaves the step loop once every lane's path has stopped.
+//
+// Both passes decide through am_exercise, so a path whose stored row and in-register price are the same bits (the
+// same path: train_seed == seed) is exercised at the same date by both.
+#include "american.hpp"
+#include "path_consts.hpp"
+
+#include <algorithm>
+
+namespace mcamd {
+
+__device__ __forceinline__ double am_payoff(bool put, double K, double S)
+{
+    const double x = put ? K - S : S - K;
+    return x > 0.0 ? x : 0.0;
+}
+
+// phi(S) . beta by Horner, with explicit fused multiply-adds (no contraction choice left to the compiler)
+template <int MB>
+__device__ __forceinline__ double am_continuation(const double (&beta)[MB], double u)
+{
+    double c = beta[MB - 1];
+#pragma unroll
+    for (int q = MB - 2; q >= 0; --q) c = __builtin_fma(c, u, beta[q]);
+    return c;
+}
+
+// The exercise decision of both passes at a regressed date: true (y = d h(S)) when h(S) > 0 and d h(S) beats the
+// fitted continuation value phi(S) . beta.
+template <int MB>
+__device__ __forceinline__ bool am_exercise(const double (&beta)[MB], double disc, double K, bool put, double S,
+                                            double &y)
+{
+    const double h = am_payoff(put, K, S);
+    if (!(h > 0.0)) return false;
+    y = disc * h;
+    return y > am_continuation<MB>(beta, S / K - 1.0);
+}
+
+// Normal equations of one date from its record: A = Hankel(P_0..P_{2m-2}), b = (sum V u^q).  Jacobi scaling
+// D = diag(A)^(-1/2), Cholesky of D A D, two triangular solves, beta = D z.  Returns false — date not regressed — when
+// |I_j| < 4 m, a diagonal entry is not positive or a scaled pivot is <= 1e-12 (NaN records included: the comparisons
+// are written so that NaN fails them).
+template <int MB>
+__device__ __forceinline__ bool am_solve(const double *__restrict__ rec, double (&beta)[MB])
+{
+    bool ok = rec[11] >= 4.0 * MB;
+    double D[MB];
+#pragma unroll
+    for (int a = 0; a < MB; ++a) {
+        const double d = rec[2 * a];
+        ok = ok && d > 0.0;
+        D[a] = d > 0.0 ? 1.0 / sqrt(d) : 0.0;
+    }
+    double L[MB][MB];
+#pragma unroll
+    for (int c = 0; c < MB; ++c) {
+        double s = rec[2 * c] * D[c] * D[c];
+#pragma unroll
+        for (int q = 0; q < c; ++q) s -= L[c][q] * L[c][q];
+        ok = ok && s > 1e-12;
+        const double l = sqrt(s > 1e-12 ? s : 1.0);
+        L[c][c] = l;
+#pragma unroll
+        for (int r = c + 1; r < MB; ++r) {
+            double t = rec[r + c] * D[r] * D[c];
+#pragma unroll
+            for (int q = 0; q < c; ++q) t -= L[r][q] * L[c][q];
+            L[r][c] = t / l;
+        }
+    }
+    double y[MB];
+#pragma unroll
+    for (int a = 0; a < MB; ++a) {
+        double t = rec[7 + a] * D[a];
+#pragma unroll
+        for (int q = 0; q < a; ++q) t -= L[a][q] * y[q];
+        y[a] = t / L[a][a];
+    }
+#pragma unroll
+    for (int a = MB - 1; a >= 0; --a) {
+        double t = y[a];
+#pragma unroll
+        for (int q = a + 1; q < MB; ++q) t -= L[q][a] * beta[q];
+        beta[a] = t / L[a][a];
+    }
+#pragma unroll
+    for (int a = 0; a < MB; ++a) beta[a] *= D[a];
+    return ok;
+}
+
+template <typename T>
+struct AmSweepArgs {
+    const T *traj;           // step-major rows of n training paths
+    double *V;
+    double *table;
+    const double *rec_in;    // the record of date j+1 (unused by launch M-1)
+    uint64_t n;
+    uint64_t row_next;       // stored row of date j+1
+    uint64_t row_j;          // stored row of date j (j >= 1)
+    double K;
+    double disc_next, t_next;   // d_{j+1}, t_{j+1} (host-computed)
+    uint32_t j, M;
+    int put;
+    GridFinish fin;          // fin.out: the record slot of date j
+};
+
+template <typename T, int MB>
+__global__ __launch_bounds__(kBlock) void am_sweep_kernel(AmSweepArgs<T> a, double *__restrict__ partials)
+{
+    const bool put = a.put != 0;
+    const bool first = a.j + 1 == a.M;
+    double beta[MB];
+#pragma unroll
+    for (int q = 0; q < MB; ++q) beta[q] = 0.0;
+    const bool regressed = first ? false : am_solve<MB>(a.rec_in, beta);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        double *row = a.table + static_cast<uint64_t>(a.j + 1) * kAmRow;
+#pragma unroll
+        for (int q = 0; q < kAmMaxBasis; ++q) row[q] = (regressed && q < MB) ? beta[q < MB ? q : 0] : __builtin_nan("");
+        row[4] = regressed ? 1.0 : 0.0;
+        row[5] = a.disc_next;
+        row[6] = a.t_next;
+        row[7] = 0.0;
+    }
+    double acc[kAmRecord];
+#pragma unroll
+    for (int q = 0; q < kAmRecord; ++q) acc[q] = 0.0;
+    const T *__restrict__ next = a.traj + a.row_next * a.n;
+    const T *__restrict__ cur = a.traj + a.row_j * a.n;
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
+    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < a.n; i += stride) {
+        const double Sn = static_cast<double>(next[i]);
+        double v;
+        if (first) {
+            v = a.disc_next * am_payoff(put, a.K, Sn);
+        } else {
+            v = a.V[i];
+            double y;
+            if (regressed && am_exercise<MB>(beta, a.disc_next, a.K, put, Sn, y)) v = y;
+        }
+        if (a.j > 0) {
+            const double S = static_cast<double>(cur[i]);
+            if (am_payoff(put, a.K, S) > 0.0) {
+                const double u = S / a.K - 1.0;
+                double p = 1.0;
+#pragma unroll
+                for (int q = 0; q < 7; ++q) {
+                    acc[q] += p;
+                    if (q < kAmMaxBasis) acc[7 + q] = __builtin_fma(v, p, acc[7 + q]);
+                    p *= u;
+                }
+                acc[11] += 1.0;
+            }
+            a.V[i] = v;
+        } else {
+            acc[0] += v;
+            acc[1] = __builtin_fma(v, v, acc[1]);
+        }
+    }
+    block_sumN<kBlock, kAmRecord>(acc);
+    grid_finish<kBlock, kAmRecord>(acc, partials, a.fin);
+}
+
+template <typename T>
+struct AmPriceArgs {
+    StepConsts<T> c;
+    const double *table;
+    uint64_t seed;
+    uint64_t path_offset;
+    uint64_t n_local;
+    double K;
+    uint32_t k, M;
+    int put;
+    GridFinish fin;
+};
+
+template <typename T, int MB>
+__global__ __launch_bounds__(kBlock) void am_price_kernel(AmPriceArgs<T> a, double *__restrict__ partials)
+{
+    constexpr int NB = Normals<T>::kPerBlock;
+    const MathCtx<T> m = MathCtx<T>::init();
+    const PhiloxKeys key = PhiloxKeys::make(a.seed);
+    const StepConsts<T> c = resident(a.c);
+    const bool put = a.put != 0;
+    const uint32_t n_full = c.n_sim / NB;         // Philox blocks whose NB steps are all simulated
+    const uint32_t rem = c.n_sim - n_full * NB;   // steps of the last, partial block
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
+    double acc[kAmPriceRecord];
+#pragma unroll
+    for (int q = 0; q < kAmPriceRecord; ++q) acc[q] = 0.0;
+    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < a.n_local; i += stride) {
+        const uint64_t subsequence = a.path_offset + i;
+        PathState<T> ps = PathState<T>::start(c.S_start);
+        bool live = true;
+        double y = 0.0;
+        uint32_t ex_date = 0;            // date of an exercise before maturity, 0: none
+        uint32_t date = 0, until = a.k;  // the same for every lane of the wavefront
+        auto step = [&](T x) {
+            ps.step(x, m);
+            if (--until != 0) return;
+            until = a.k;
+            ++date;
+            const double *row = a.table + static_cast<uint64_t>(date) * kAmRow;
+            if (date == a.M) {
+                if (live) y = row[5] * am_payoff(put, a.K, static_cast<double>(ps.value(m)));
+                live = false;
+            } else if (row[4] != 0.0) {
+                double beta[MB];
+#pragma unroll
+                for (int q = 0; q < MB; ++q) beta[q] = row[q];
+                double ye;
+                if (live && am_exercise<MB>(beta, row[5], a.K, put, static_cast<double>(ps.value(m)), ye)) {
+                    y = ye;
+                    live = false;
+                    ex_date = date;
+                }
+            }
+        };
+        bool running = true;
+        for (uint32_t b = 0; b < n_full; ++b) {
+            Exponents<T> ex;
+            ex.fill(m, c, key, subsequence, b);
+#pragma unroll
+            for (int j = 0; j < NB; ++j) step(ex.x[j]);
+            if (__builtin_amdgcn_ballot_w64(live) == 0) {   // every lane's path has stopped
+                running = false;
+                break;
+            }
+        }
+        if (rem && running) {
+            Exponents<T> ex;
+            ex.fill(m, c, key, subsequence, n_full);
+#pragma unroll
+            for (int j = 0; j < NB - 1; ++j)
+                if (static_cast<uint32_t>(j) < rem) step(ex.x[j]);
+        }
+        acc[0] += y;
+        acc[1] = __builtin_fma(y, y, acc[1]);
+        if (ex_date != 0) {
+            acc[2] += 1.0;
+            acc[3] += a.table[static_cast<uint64_t>(ex_date) * kAmRow + 6];
+        }
+        acc[4] += 1.0;
+    }
+    block_sumN<kBlock, kAmPriceRecord>(acc);
+    grid_finish<kBlock, kAmPriceRecord>(acc, partials, a.fin);
+}
+
+static uint64_t align256(uint64_t x) { return (x + 255) & ~static_cast<uint64_t>(255); }
+
+uint32_t american_sweep_grid(uint64_t n_train)
+{
+    const uint64_t blocks = (n_train + kBlock - 1) / kBlock;
+    return static_cast<uint32_t>(blocks < 1 ? 1 : (blocks < kFoldMaxRecords ? blocks : kFoldMaxRecords));
+}
+
+uint32_t american_price_grid(uint64_t n_local)
+{
+    return american_sweep_grid(n_local);   // one path per thread, capped so that the last workgroup finishes the sum
+}
+
+AmLayout american_layout(uint64_t n_train, uint32_t n_steps, uint32_t M, int precision)
+{
+    const uint64_t elem = precision == 32 ? 4 : 8;
+    const uint64_t partials = std::max<uint64_t>(2ull * store_grid(n_train, precision),
+                                                 static_cast<uint64_t>(kAmRecord) * american_sweep_grid(n_train));
+    AmLayout l;
+    l.traj = 0;
+    l.V = l.traj + align256(static_cast<uint64_t>(n_steps) * n_train * elem);
+    l.table = l.V + align256(8 * n_train);
+    l.partials = l.table + align256(8 * (static_cast<uint64_t>(kAmRow) * (M + 1) + 2 * kAmRecordSlot));
+    l.total = 256 + l.partials + align256(8 * partials);
+    return l;
+}
+
+template <typename T, int MB>
+static hipError_t sweep_t(const AmJob &job, const void *traj, double *V, double *table, double *records,
+                          double *partials, uint32_t grid, unsigned int *ticket, hipStream_t stream)
+{
+    AmSweepArgs<T> a;
+    a.traj = static_cast<const T *>(traj);
+    a.V = V;
+    a.table = table;
+    a.n = job.n_train;
+    a.K = job.path.K;
+    a.M = job.M;
+    a.put = job.put;
+    const dim3 g(grid), b(kBlock);
+    for (uint32_t j = job.M; j-- > 0;) {
+        const uint32_t jn = j + 1;
+        const uint64_t s_next = static_cast<uint64_t>(jn) * job.k;
+        a.j = j;
+        a.rec_in = records + ((jn & 1) ? kAmRecordSlot : 0);
+        a.row_next = s_next - 1;
+        a.row_j = j > 0 ? static_cast<uint64_t>(j) * job.k - 1 : 0;
+        a.t_next = static_cast<double>(s_next) * job.dt;
+        a.disc_next = std::exp(-job.r * a.t_next);
+        a.fin = GridFinish{records + ((j & 1) ? kAmRecordSlot : 0), ticket, -1.0};
+        hipLaunchKernelGGL((am_sweep_kernel<T, MB>), g, b, 0, stream, a, partials);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+template <typename T, int MB>
+static hipError_t price_t(const AmJob &job, const double *table, double *d_partials, uint32_t grid, double *out,
+                          unsigned int *ticket, hipStream_t stream)
+{
+    AmPriceArgs<T> a;
+    a.c = make_consts<T>(job.path);
+    a.table = table;
+    a.seed = job.path.seed;
+    a.path_offset = job.path.path_offset;
+    a.n_local = job.path.n_local;
+    a.K = job.path.K;
+    a.k = job.k;
+    a.M = job.M;
+    a.put = job.put;
+    a.fin = GridFinish{out, ticket, -1.0};
+    hipLaunchKernelGGL((am_price_kernel<T, MB>), dim3(grid), dim3(kBlock), 0, stream, a, d_partials);
+    return hipGetLastError();
+}
+
+#define MCAMD_AM_DISPATCH(FN, ...)                                                                       \
+    switch (job.n_basis) {                                                                            \
+    case 2: return job.path.precision == 32 ? FN<float, 2>(__VA_ARGS__) : FN<double, 2>(__VA_ARGS__); \
+    case 3: return job.path.precision == 32 ? FN<float, 3>(__VA_ARGS__) : FN<double, 3>(__VA_ARGS__); \
+    case 4: return job.path.precision == 32 ? FN<float, 4>(__VA_ARGS__) : FN<double, 4>(__VA_ARGS__); \
+    default: return hipErrorInvalidValue;                                                             \
+    }
+
+hipError_t launch_american_sweep(const AmJob &job, const void *traj, double *V, double *table, double *records,
+                                 double *partials, uint32_t grid, unsigned int *ticket, hipStream_t stream)
+{
+    if (!ticket || grid > kFoldMaxRecords || job.M == 0 || job.M > kAmMaxDates) return hipErrorInvalidValue;
+    MCAMD_AM_DISPATCH(sweep_t, job, traj, V, table, records, partials, grid, ticket, stream)
+}
+
+hipError_t launch_american_price(const AmJob &job, const double *table, double *d_partials, uint32_t grid, double *out,
+                                 unsigned int *ticket, hipStream_t stream)
+{
+    if (!out || !ticket || grid > kFoldMaxRecords) return hipErrorInvalidValue;
+    MCAMD_AM_DISPATCH(price_t, job, table, d_partials, grid, out, ticket, stream)
+}
+
+#undef MCAMD_AM_DISPATCH
+
+}  // namespace mcamd

@@ -4,6 +4,7 @@
 // call either runs the gfx950 kernels or returns an error.
 #include "launch.hpp"
 #include "greeks.hpp"
+#include "american.hpp"
 
 #include "mcamd.h"
 
@@ -13,11 +14,14 @@
 #include <cstring>
 #include <random>
 #include <string>
+#include <vector>
 
 static_assert(sizeof(mcamd_option) == 88 && sizeof(mcamd_sim) == 48 && sizeof(mcamd_result) == 128 &&
                   sizeof(mcamd_device_info) == 384,
               "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
 static_assert(sizeof(mcamd_greeks) == 224, "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
+static_assert(sizeof(mcamd_american) == 32 && sizeof(mcamd_american_result) == 152,
+              "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
 
 namespace {
 
@@ -433,6 +437,42 @@ void finalize_greeks_into(const double stats[16], double r, double T, int theta_
         out->std_err[k] = n ? disc * std::sqrt(var / N) : 0.0;
     }
     if (!theta_defined) out->value[MCAMD_GREEK_THETA] = out->std_err[MCAMD_GREEK_THETA] = std::nan("");
+}
+
+// The refusals of the American calls that depend on the request's shape alone (shared with the workspace-size query):
+// dates and basis size on success.
+int check_american_shape(const mcamd_sim *sim, const mcamd_american *am, uint32_t *M, int *n_basis)
+{
+    if (am->payoff != MCAMD_PAYOFF_CALL && am->payoff != MCAMD_PAYOFF_PUT)
+        return fail(MCAMD_ERR_INVALID, "payoff must be MCAMD_PAYOFF_CALL (0) or MCAMD_PAYOFF_PUT (1), got %d", am->payoff);
+    if (am->n_basis != 0 && (am->n_basis < 2 || am->n_basis > static_cast<uint32_t>(mcamd::kAmMaxBasis)))
+        return fail(MCAMD_ERR_INVALID, "n_basis must be 2, 3 or 4 (0 = 3), got %u", am->n_basis);
+    if (am->reserved != 0) return fail(MCAMD_ERR_INVALID, "am->reserved must be 0, got %u", am->reserved);
+    if (sim->precision != MCAMD_F32 && sim->precision != MCAMD_F64)
+        return fail(MCAMD_ERR_INVALID, "precision must be MCAMD_F32 (32) or MCAMD_F64 (64), got %d", sim->precision);
+    if (sim->n_steps == 0) return fail(MCAMD_ERR_INVALID, "n_steps must be >= 1");
+    if (am->exercise_every == 0 || sim->n_steps % am->exercise_every != 0)
+        return fail(MCAMD_ERR_INVALID, "exercise_every = %u must be >= 1 and divide n_steps = %u", am->exercise_every,
+                    sim->n_steps);
+    if (am->n_train == 0) return fail(MCAMD_ERR_INVALID, "n_train must be >= 1");
+    const uint32_t dates = sim->n_steps / am->exercise_every;
+    if (dates > mcamd::kAmMaxDates)
+        return fail(MCAMD_ERR_INVALID, "n_steps / exercise_every = %u exercise dates; at most %u are supported", dates,
+                    mcamd::kAmMaxDates);
+    if (static_cast<long double>(am->n_train) * sim->n_steps * 8.0L >= 9.2e18L)
+        return fail(MCAMD_ERR_INVALID, "n_train * n_steps overflows the training workspace's 64-bit size");
+    *M = dates;
+    *n_basis = am->n_basis ? static_cast<int>(am->n_basis) : 3;
+    return MCAMD_OK;
+}
+
+// h(S0) replaces an estimate it exceeds (exercise at t = 0); returns whether it did
+bool floor_at_immediate(double h0, double *price, double *std_err)
+{
+    if (!(h0 > *price)) return false;
+    *price = h0;
+    *std_err = 0.0;
+    return true;
 }
 
 }  // namespace
@@ -1013,6 +1053,145 @@ int mcamd_bs_greeks_f64(double S0, double K, double T, double r, double v, doubl
     out[MCAMD_GREEK_VEGA] = S0 * phi * sqrtT;
     out[MCAMD_GREEK_RHO] = Kdisc * T * Nd2;
     out[MCAMD_GREEK_THETA] = -S0 * phi * v / (2.0 * sqrtT) - r * Kdisc * Nd2;
+    return MCAMD_OK;
+}
+
+int mcamd_american_workspace_bytes(const mcamd_american *am, const mcamd_sim *sim, uint64_t *bytes)
+{
+    if (!am || !sim || !bytes) return fail(MCAMD_ERR_INVALID, "am, sim and bytes must be non-NULL");
+    *bytes = 0;
+    uint32_t M = 0;
+    int n_basis = 0;
+    if (int rc = check_american_shape(sim, am, &M, &n_basis)) return rc;
+    *bytes = mcamd::american_layout(am->n_train, sim->n_steps, M, sim->precision).total;
+    return MCAMD_OK;
+}
+
+int mcamd_price_american(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_american *am,
+                         void *d_work, uint64_t work_bytes, double *h_coeffs, mcamd_american_result *res)
+{
+    // every refusal that depends on the request alone comes before the context is looked at
+    if (!opt || !sim || !am || !res) return fail(MCAMD_ERR_INVALID, "opt, sim, am and res must be non-NULL");
+    std::memset(res, 0, sizeof *res);
+    uint32_t M = 0;
+    int n_basis = 0;
+    if (int rc = check_american_shape(sim, am, &M, &n_basis)) return rc;
+    if (opt->use_window) return fail(MCAMD_ERR_INVALID, "American options take no bullet window: use_window must be 0");
+    if (opt->Tk != 0 || opt->Sk != 0.0)
+        return fail(MCAMD_ERR_INVALID, "American options start at t = 0: Tk and Sk must be 0 (Tk = %d, Sk = %g)", opt->Tk,
+                    opt->Sk);
+    if (opt->dt != 0.0) return fail(MCAMD_ERR_INVALID, "American options step dt = T / n_steps: opt->dt must be 0");
+    if (!(opt->v > 0.0) || !(opt->S0 > 0.0) || !(opt->K > 0.0))
+        return fail(MCAMD_ERR_INVALID, "American options need v > 0, S0 > 0 and K > 0 (v = %g, S0 = %g, K = %g)", opt->v,
+                    opt->S0, opt->K);
+    if (sim->flags != 0 && sim->flags != MCAMD_FLAG_LOG_SPACE && sim->flags != MCAMD_FLAG_PRODUCT_FORM)
+        return fail(MCAMD_ERR_INVALID, "American options take flags 0, MCAMD_FLAG_LOG_SPACE or MCAMD_FLAG_PRODUCT_FORM, "
+                                       "got %d", sim->flags);
+    if (!d_work) return fail(MCAMD_ERR_INVALID, "d_work is NULL");
+    const mcamd::AmLayout lay = mcamd::american_layout(am->n_train, sim->n_steps, M, sim->precision);
+    if (work_bytes < lay.total)
+        return fail(MCAMD_ERR_INVALID, "work_bytes = %llu is below the %llu bytes the workspace needs "
+                                       "(mcamd_american_workspace_bytes)",
+                    static_cast<unsigned long long>(work_bytes), static_cast<unsigned long long>(lay.total));
+    mcamd_result dummy;
+    if (int rc = check_common(ctx, opt, sim, &dummy)) return rc;
+
+    HIP_TRY(hipSetDevice(ctx->device));
+    char *base = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(d_work) + 255) & ~static_cast<uintptr_t>(255));
+    void *traj = base + lay.traj;
+    double *V = reinterpret_cast<double *>(base + lay.V);
+    double *table = reinterpret_cast<double *>(base + lay.table);
+    double *records = table + static_cast<uint64_t>(mcamd::kAmRow) * (M + 1);
+    double *w_partials = reinterpret_cast<double *>(base + lay.partials);
+
+    mcamd::AmJob job;
+    job.path = make_job(opt, sim);
+    job.path.window = false;
+    job.path.logspace = false;   // the product form: St at every date, the same bits as the stored rows
+    job.path.vr = 0;
+    job.put = am->payoff == MCAMD_PAYOFF_PUT ? 1 : 0;
+    job.n_basis = n_basis;
+    job.k = am->exercise_every;
+    job.M = M;
+    job.r = opt->r;
+    job.dt = opt->T / static_cast<double>(sim->n_steps);
+    job.n_train = am->n_train;
+    mcamd::PathJob train = job.path;
+    train.seed = am->train_seed;
+    train.path_offset = 0;
+    train.n_local = am->n_train;
+
+    const uint64_t n_local = sim->n_paths_local;
+    const uint32_t store_grid = mcamd::store_grid(am->n_train, sim->precision);
+    const uint32_t sweep_grid = mcamd::american_sweep_grid(am->n_train);
+    const uint32_t price_grid = mcamd::american_price_grid(n_local);
+    if (n_local)
+        if (int rc = ensure_partials(ctx, price_grid, mcamd::kAmPriceRecord)) return rc;
+    // NaN (all-ones bytes in the record slots, NaN in the pinned record) until a kernel has written the record: a sum
+    // that never finished cannot pass as an earlier call's
+    HIP_TRY(hipMemsetAsync(records, 0xFF, 2 * mcamd::kAmRecordSlot * sizeof(double), ctx->stream));
+    for (int k = 0; k < mcamd::kAmPriceRecord; ++k) ctx->h_out[k] = std::nan("");
+    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+    HIP_TRY(mcamd::launch_store(train, MCAMD_STEP_MAJOR, traj, nullptr, nullptr, w_partials, store_grid, ctx->stream));
+    HIP_TRY(mcamd::launch_american_sweep(job, traj, V, table, records, w_partials, sweep_grid, ctx->d_ticket,
+                                         ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+    if (n_local)
+        HIP_TRY(mcamd::launch_american_price(job, table, ctx->d_partials, price_grid, ctx->h_out_dev, ctx->d_ticket,
+                                             ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ev2, ctx->stream));
+    std::vector<double> host(static_cast<size_t>(mcamd::kAmRow) * (M + 1) + 2 * mcamd::kAmRecordSlot);
+    HIP_TRY(hipMemcpyAsync(host.data(), table, host.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipEventElapsedTime(&res->train_ms, ctx->ev0, ctx->ev1));
+    HIP_TRY(hipEventElapsedTime(&res->price_ms, ctx->ev1, ctx->ev2));
+    HIP_TRY(hipEventElapsedTime(&res->total_ms, ctx->ev0, ctx->ev2));
+
+    const double *in_rec = host.data() + static_cast<size_t>(mcamd::kAmRow) * (M + 1);   // launch 0's slot
+    if (std::isnan(in_rec[0]) || std::isnan(in_rec[1]))
+        return fail(MCAMD_ERR_HIP, "backward sweep left no in-sample record (its last workgroup did not finish the sum)");
+    double rec[mcamd::kAmPriceRecord] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    if (n_local) {
+        std::memcpy(rec, ctx->h_out, sizeof rec);
+        for (double x : rec)
+            if (std::isnan(x))
+                return fail(MCAMD_ERR_HIP, "American pricing kernel left no result (its last workgroup did not finish "
+                                           "the sum)");
+    }
+    mcamd_result out, in;
+    finalize_into(rec[0], rec[1], n_local, 0.0, 1.0, &out);   // samples are discounted where paid: D = 1
+    finalize_into(in_rec[0], in_rec[1], am->n_train, 0.0, 1.0, &in);
+    res->price = out.price;
+    res->std_err = out.std_err;
+    res->sum = rec[0];
+    res->sumsq = rec[1];
+    res->n = n_local;
+    res->n_early = static_cast<uint64_t>(std::llround(rec[2]));
+    res->sum_t_exercise = rec[3];
+    res->in_sample_price = in.price;
+    res->in_sample_std_err = in.std_err;
+    res->in_sample_sum = in_rec[0];
+    res->in_sample_sumsq = in_rec[1];
+    res->n_train = am->n_train;
+    const double h0 = std::fmax(job.put ? opt->K - opt->S0 : opt->S0 - opt->K, 0.0);
+    bool immediate = floor_at_immediate(h0, &res->in_sample_price, &res->in_sample_std_err);
+    if (n_local) immediate = floor_at_immediate(h0, &res->price, &res->std_err) || immediate;
+    res->immediate_exercise = immediate ? 1 : 0;
+    res->ci_lo = res->price - 1.959963984540054 * res->std_err;
+    res->ci_hi = res->price + 1.959963984540054 * res->std_err;
+    res->n_dates = M;
+    for (uint32_t j = 1; j < M; ++j) res->n_regressed += host[static_cast<size_t>(j) * mcamd::kAmRow + 4] != 0.0 ? 1 : 0;
+    if (h_coeffs) {
+        for (uint32_t j = 1; j <= M; ++j) {
+            const double *row = host.data() + static_cast<size_t>(j) * mcamd::kAmRow;
+            double *dst = h_coeffs + static_cast<size_t>(j - 1) * (n_basis + 1);
+            for (int q = 0; q < n_basis; ++q) dst[q] = row[4] != 0.0 ? row[q] : std::nan("");
+            dst[n_basis] = row[4];
+        }
+    }
+    res->grid = n_local ? price_grid : 0;
+    res->block = 256;
+    res->train_grid = sweep_grid;
     return MCAMD_OK;
 }
 
