@@ -67,11 +67,10 @@ struct mcamd_ctx {
     double *d_out = nullptr;       // 8 doubles
     unsigned long long *d_queue = nullptr;  // task counter of the wave-per-point nested-MC kernel
     unsigned int *d_ticket = nullptr;       // arrival counter of kernels that finish their own sum (in d_queue's allocation)
-    double *h_out_dev = nullptr;            // h_out as the device addresses it (a self-finishing kernel writes there)
     uint32_t compute_units = 0;
-    double *h_out = nullptr;       // pinned, 8 doubles
-    double *h_greeks = nullptr;    // pinned, 16 doubles: the Greeks kernel's statistics record (mcamd_price_greeks)
-    double *h_greeks_dev = nullptr;
+    static constexpr int kRecord = 16;      // doubles of h_rec: the widest final record (Greeks' statistics layout)
+    double *h_rec = nullptr;                // pinned: the final record of a synchronous call
+    double *h_rec_dev = nullptr;            // h_rec as the device addresses it (a self-finishing kernel writes there)
     // asynchronous calls: a ring of event pairs around the simulation kernel of the last kRing enqueues
     static constexpr uint32_t kRing = 64;
     hipEvent_t ring0[kRing] = {}, ring1[kRing] = {};
@@ -79,6 +78,8 @@ struct mcamd_ctx {
 };
 
 namespace {
+
+constexpr double kZ95 = 1.959963984540054;   // two-sided 95 % quantile of the standard normal
 
 int ensure_partials(mcamd_ctx *ctx, uint32_t records, int record_doubles = 2)
 {
@@ -92,10 +93,10 @@ int ensure_partials(mcamd_ctx *ctx, uint32_t records, int record_doubles = 2)
     return MCAMD_OK;
 }
 
-int check_common(const mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_result *res)
+int check_common(const mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim)
 {
     if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
-    if (!opt || !sim || !res) return fail(MCAMD_ERR_INVALID, "opt, sim and res must be non-NULL");
+    if (!opt || !sim) return fail(MCAMD_ERR_INVALID, "opt and sim must be non-NULL");
     if (sim->precision != MCAMD_F32 && sim->precision != MCAMD_F64)
         return fail(MCAMD_ERR_INVALID, "precision must be MCAMD_F32 (32) or MCAMD_F64 (64), got %d", sim->precision);
     if (sim->n_steps == 0) return fail(MCAMD_ERR_INVALID, "n_steps must be >= 1");
@@ -127,6 +128,17 @@ int check_common(const mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim 
     return MCAMD_OK;
 }
 
+// check_common plus the refusals of the calls that run plain paths (no variance reduction) and, but for
+// mcamd_price_from_normals, take a trajectory layout
+int check_plain(const mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, int layout = MCAMD_STEP_MAJOR)
+{
+    if (int rc = check_common(ctx, opt, sim)) return rc;
+    if (sim->flags & (MCAMD_FLAG_ANTITHETIC | MCAMD_FLAG_CONTROL_VARIATE))
+        return fail(MCAMD_ERR_INVALID, "variance-reduction flags apply to mcamd_price_paths only");
+    if (layout != MCAMD_STEP_MAJOR && layout != MCAMD_PATH_MAJOR)
+        return fail(MCAMD_ERR_INVALID, "layout must be MCAMD_STEP_MAJOR or MCAMD_PATH_MAJOR");
+    return MCAMD_OK;
+}
 mcamd::PathJob make_job(const mcamd_option *opt, const mcamd_sim *sim)
 {
     mcamd::PathJob j;
@@ -160,65 +172,83 @@ void zero_result(mcamd_result *res)
     std::memset(res, 0, sizeof *res);
 }
 
-// How the block records of the kernel just enqueued reach the host.
+// How the block records of a call's simulation kernel reach the host.
 enum class Finish {
-    kFolded,    // the kernel summed them itself and wrote the final record into ctx->h_out (pinned host memory)
-    kSmall,     // separate launch of the same sum (launch_small_final), then a copy
-    kReduce     // separate 1024-thread reduction (launch_final_reduce), then a copy
+    kFolded,    // the kernel sums them itself and writes the final record where FinishSpec::out points
+    kSmall,     // separate launch of the same sum (launch_small_final)
+    kReduce     // separate 1024-thread reduction (launch_final_reduce)
 };
 
-// final reduce of the block records -> host, with event timing; fills the raw sums + timings
-int finish(mcamd_ctx *ctx, uint32_t records, mcamd_result *res, int record_doubles = 2, Finish how = Finish::kReduce)
+// One device call as both drivers (run_sync, run_enqueue) see it.  launch(fs) enqueues the simulation kernel on
+// ctx->stream; fs.out and fs.ticket are set when how == kFolded.
+template <typename Launch>
+struct DeviceCall {
+    uint64_t n;      // paths (nested MC: points) of the shard, the statistics layout's n; 0: empty shard, nothing runs
+    uint32_t grid;   // block records the kernel writes
+    int rec;         // doubles per block record
+    int stats;       // doubles of the statistics layout an enqueue leaves in d_stats: 6, or 16 for Greeks
+    Finish how;
+    Launch launch;
+};
+template <typename Launch>
+DeviceCall(uint64_t, uint32_t, int, int, Finish, Launch) -> DeviceCall<Launch>;
+
+struct NoLaunch {
+    hipError_t operator()(const mcamd::FinishSpec &) const { return hipSuccess; }
+};
+DeviceCall<NoLaunch> empty_call(int stats = 6)
 {
-    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-    if (how != Finish::kFolded) {
-        if (how == Finish::kSmall)
-            HIP_TRY(mcamd::launch_small_final(ctx->d_partials, records, record_doubles, ctx->d_out, ctx->stream));
-        else
-            HIP_TRY(mcamd::launch_final_reduce(ctx->d_partials, records, record_doubles, ctx->d_out, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(ctx->h_out, ctx->d_out, record_doubles * sizeof(double), hipMemcpyDeviceToHost,
-                               ctx->stream));
-        HIP_TRY(hipEventRecord(ctx->ev2, ctx->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipEventElapsedTime(&res->kernel_ms, ctx->ev0, ctx->ev1));
-    if (how == Finish::kFolded) res->total_ms = res->kernel_ms;   // one launch is the whole call
-    else HIP_TRY(hipEventElapsedTime(&res->total_ms, ctx->ev0, ctx->ev2));
-    res->sum = ctx->h_out[0];
-    res->sumsq = ctx->h_out[1];
-    if (record_doubles == 5) {
-        res->sum_c = ctx->h_out[2];
-        res->sum_cc = ctx->h_out[3];
-        res->sum_yc = ctx->h_out[4];
-    }
-    if (record_doubles == mcamd::kNmcRecord) {
-        res->work_steps = 64.0 * ctx->h_out[2];  // wave-steps x 64 lanes
-        res->live_steps = ctx->h_out[3];
-    }
-    return MCAMD_OK;
+    return {0, 0, 2, stats, Finish::kReduce, {}};
 }
 
-void finalize_cv_into(const double s[5], uint64_t n, double r, double T, mcamd_result *res);
-void finalize_into(double sum, double sumsq, uint64_t n, double r, double T, mcamd_result *res);
-
-// Common tail of the pricing calls: final reduce + copy + sync, then price / SE / CI from the shard's sums,
-// keeping the event timings and the launch shape in the result.
-int finish_pricing(mcamd_ctx *ctx, uint32_t grid, int record_doubles, const mcamd_option *opt, const mcamd_sim *sim,
-                   mcamd_result *res, Finish how = Finish::kReduce)
+// A self-finishing kernel's final record is filled with all-ones bits before the launch.  No finished sum has that
+// pattern (a NaN the arithmetic makes is the canonical one), so finding it after the sync means the kernel's last
+// workgroup never wrote the record, e.g. because the arrival ticket was not zero at launch.  Bits, not isnan: an fp32
+// job that saturates can sum to a genuine NaN, and that is a result.
+void arm_record(double *rec, int n)
 {
-    if (int rc = finish(ctx, grid, res, record_doubles, how)) return rc;
-    const float kms = res->kernel_ms, tms = res->total_ms;
-    if (record_doubles == 5) {
-        const double sums[5] = {res->sum, res->sumsq, res->sum_c, res->sum_cc, res->sum_yc};
-        finalize_cv_into(sums, sim->n_paths_local, opt->r, opt->T, res);
-    } else {
-        finalize_into(res->sum, res->sumsq, sim->n_paths_local, opt->r, opt->T, res);
+    std::memset(rec, 0xFF, n * sizeof(double));
+}
+
+bool record_unwritten(const double *rec, int n)
+{
+    for (int k = 0; k < n; ++k) {
+        uint64_t bits;
+        std::memcpy(&bits, rec + k, sizeof bits);
+        if (bits == ~0ull) return true;
     }
-    res->kernel_ms = kms;
-    res->total_ms = tms;
-    res->grid = grid;
-    res->block = 256;
-    return MCAMD_OK;
+    return false;
+}
+
+// disc x the mean of n samples and its standard error, from their sum and sum of squares
+struct Estimate {
+    double value, std_err;
+};
+Estimate estimate(double sum, double sumsq, uint64_t n, double disc)
+{
+    const double N = static_cast<double>(n);
+    const double mean = n ? sum / N : 0.0;
+    double var = n > 1 ? (sumsq - N * mean * mean) / (N - 1.0) : 0.0;
+    if (var < 0.0) var = 0.0;
+    return {disc * mean, n ? disc * std::sqrt(var / N) : 0.0};
+}
+
+template <typename Result>   // mcamd_result, mcamd_american_result
+void set_ci(Result *res)
+{
+    res->ci_lo = res->price - kZ95 * res->std_err;
+    res->ci_hi = res->price + kZ95 * res->std_err;
+}
+
+void finalize_into(double sum, double sumsq, uint64_t n, double r, double T, mcamd_result *res)
+{
+    const Estimate e = estimate(sum, sumsq, n, std::exp(-r * T));
+    res->sum = sum;
+    res->sumsq = sumsq;
+    res->n = n;
+    res->price = e.value;
+    res->std_err = e.std_err;
+    set_ci(res);
 }
 
 void finalize_cv_into(const double s[5], uint64_t n, double r, double T, mcamd_result *res)
@@ -244,61 +274,171 @@ void finalize_cv_into(const double s[5], uint64_t n, double r, double T, mcamd_r
     res->cv_rho = rho;
     res->price = disc * (ybar - beta * cbar);
     res->std_err = disc * std::sqrt(var_res / N);
-    res->ci_lo = res->price - 1.959963984540054 * res->std_err;
-    res->ci_hi = res->price + 1.959963984540054 * res->std_err;
+    set_ci(res);
 }
 
-void finalize_into(double sum, double sumsq, uint64_t n, double r, double T, mcamd_result *res)
+// price / SE / CI of a pricing record: {sum, sumsq} or, with the control variate, the five sums
+void finalize_record(const double *rec, bool control_variate, uint64_t n, double r, double T, mcamd_result *res)
+{
+    if (control_variate) finalize_cv_into(rec, n, r, T, res);
+    else finalize_into(rec[0], rec[1], n, r, T, res);
+}
+
+// a nested-MC record over n points: the mean point price is the scalar diagnostic of the wrappers
+// (inc/wrappers.cuh:185-189,316-321)
+void finalize_nmc_into(const double rec[mcamd::kNmcRecord], uint64_t n, mcamd_result *res)
+{
+    res->sum = rec[0];
+    res->sumsq = rec[1];
+    res->work_steps = 64.0 * rec[2];   // wave-steps x 64 lanes
+    res->live_steps = rec[3];
+    res->n = n;
+    res->price = n ? res->sum / static_cast<double>(n) : 0.0;
+}
+
+void finalize_greeks_into(const double stats[16], double r, double T, int theta_defined, mcamd_greeks *out)
 {
     const double disc = std::exp(-r * T);
-    const double N = static_cast<double>(n);
-    const double mean = n ? sum / N : 0.0;
-    double var = n > 1 ? (sumsq - N * mean * mean) / (N - 1.0) : 0.0;
-    if (var < 0.0) var = 0.0;
-    const double se = n ? disc * std::sqrt(var / N) : 0.0;
-    res->sum = sum;
-    res->sumsq = sumsq;
-    res->n = n;
-    res->price = disc * mean;
-    res->std_err = se;
-    res->ci_lo = res->price - 1.959963984540054 * se;
-    res->ci_hi = res->price + 1.959963984540054 * se;
+    const uint64_t n = static_cast<uint64_t>(std::llround(stats[mcamd::kGreeksRecord]));
+    out->n = n;
+    for (int k = 0; k < mcamd::kGreeks; ++k) {
+        const Estimate e = estimate(stats[2 * k], stats[2 * k + 1], n, disc);
+        out->sum[k] = stats[2 * k];
+        out->sumsq[k] = stats[2 * k + 1];
+        out->value[k] = e.value;
+        out->std_err[k] = e.std_err;
+    }
+    if (!theta_defined) out->value[MCAMD_GREEK_THETA] = out->std_err[MCAMD_GREEK_THETA] = std::nan("");
 }
 
-// argument checks and job of the trajectory store (shared by the synchronous call and the enqueue form)
-int prepare_store(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, int layout, const void *d_traj,
-                         const int32_t *d_counts, mcamd::PathJob *job)
+// Synchronous driver.  The kernel runs between ev0 and ev1 and finishes into the pinned record (kFolded: one launch is
+// the whole call, total_ms = kernel_ms), or a separate sum into d_out and one copy run up to ev2.  After the wait,
+// fill(record) fills *res from the final record; then the timings and the launch shape.  res must be zeroed by the
+// caller: an empty shard leaves it so.
+template <typename Launch, typename Result, typename Fill>
+int run_sync(mcamd_ctx *ctx, const DeviceCall<Launch> &call, Result *res, Fill fill)
 {
-    mcamd_result dummy;
-    if (int rc = check_common(ctx, opt, sim, &dummy)) return rc;
-    if (sim->flags & (MCAMD_FLAG_ANTITHETIC | MCAMD_FLAG_CONTROL_VARIATE))
-        return fail(MCAMD_ERR_INVALID, "variance-reduction flags apply to mcamd_price_paths only");
-    if (layout != MCAMD_STEP_MAJOR && layout != MCAMD_PATH_MAJOR)
-        return fail(MCAMD_ERR_INVALID, "layout must be MCAMD_STEP_MAJOR or MCAMD_PATH_MAJOR");
-    if (sim->n_paths_local == 0) return MCAMD_OK;
-    if (!d_traj) return fail(MCAMD_ERR_INVALID, "d_traj is NULL");
-    *job = make_job(opt, sim);
-    if (d_counts && !job->window) {
-        // counts requested for a European payoff: count against B but let every count pay
-        job->window = true;
-        job->P1 = INT32_MIN;
-        job->P2 = INT32_MAX;
+    if (call.n == 0) return MCAMD_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int rc = ensure_partials(ctx, call.grid, call.rec)) return rc;
+    const bool folded = call.how == Finish::kFolded;
+    mcamd::FinishSpec fs;
+    if (folded) {
+        fs.out = ctx->h_rec_dev;
+        fs.ticket = ctx->d_ticket;
+        arm_record(ctx->h_rec, mcamd_ctx::kRecord);
     }
+    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+    HIP_TRY(call.launch(fs));
+    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+    if (!folded) {
+        if (call.how == Finish::kSmall)
+            HIP_TRY(mcamd::launch_small_final(ctx->d_partials, call.grid, call.rec, ctx->d_out, ctx->stream));
+        else
+            HIP_TRY(mcamd::launch_final_reduce(ctx->d_partials, call.grid, call.rec, ctx->d_out, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(ctx->h_rec, ctx->d_out, call.rec * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipEventRecord(ctx->ev2, ctx->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    float kernel_ms = 0.0f, total_ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&kernel_ms, ctx->ev0, ctx->ev1));
+    if (folded) total_ms = kernel_ms;
+    else HIP_TRY(hipEventElapsedTime(&total_ms, ctx->ev0, ctx->ev2));
+    double record[mcamd_ctx::kRecord];
+    std::memcpy(record, ctx->h_rec, sizeof record);
+    if (folded && record_unwritten(record, call.rec))
+        return fail(MCAMD_ERR_HIP, "the kernel left no result (its last workgroup did not finish the sum)");
+    fill(static_cast<const double *>(record));
+    res->kernel_ms = kernel_ms;
+    res->total_ms = total_ms;
+    res->grid = call.grid;
+    res->block = mcamd::kBlockThreads;
     return MCAMD_OK;
 }
 
-// argument checks and job of the nested-MC calls (inner stage and fused; shared by the synchronous calls and the
-// enqueue forms).  fused: d_prices / d_counts are outputs and outer_seed must differ from the inner seed.
-int prepare_nmc(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, int layout, int variant, bool fused,
-                       uint64_t outer_seed, const void *d_prices, const int32_t *d_counts, const void *d_point_prices,
-                       mcamd::NmcJob *job)
+// Asynchronous driver: the kernel runs between a pair of ring events, and its record reaches d_stats in the statistics
+// layout with n_value = n, from the kernel itself (kFolded) or from the separate sum.  Nothing waits on the host but the
+// growth of the scratch buffer.  An empty shard leaves all-zero statistics, still ordered on the stream.
+template <typename Launch>
+int run_enqueue(mcamd_ctx *ctx, const DeviceCall<Launch> &call, double *d_stats)
 {
-    mcamd_result dummy;
-    if (int rc = check_common(ctx, opt, sim, &dummy)) return rc;
-    if (sim->flags & (MCAMD_FLAG_ANTITHETIC | MCAMD_FLAG_CONTROL_VARIATE))
-        return fail(MCAMD_ERR_INVALID, "variance-reduction flags apply to mcamd_price_paths only");
-    if (layout != MCAMD_STEP_MAJOR && layout != MCAMD_PATH_MAJOR)
-        return fail(MCAMD_ERR_INVALID, "layout must be MCAMD_STEP_MAJOR or MCAMD_PATH_MAJOR");
+    if (!d_stats) return fail(MCAMD_ERR_INVALID, "d_stats is NULL");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const uint32_t slot = static_cast<uint32_t>(ctx->n_enqueued % mcamd_ctx::kRing);
+    if (call.n == 0) {
+        HIP_TRY(hipMemsetAsync(d_stats, 0, call.stats * sizeof(double), ctx->stream));
+        HIP_TRY(hipEventRecord(ctx->ring0[slot], ctx->stream));
+        HIP_TRY(hipEventRecord(ctx->ring1[slot], ctx->stream));
+        ctx->n_enqueued++;
+        return MCAMD_OK;
+    }
+    const double n_value = static_cast<double>(call.n);
+    // growing the scratch buffer frees the old one: wait for work that may still read it
+    if (static_cast<uint64_t>(call.grid) * call.rec > ctx->partial_capacity) HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (int rc = ensure_partials(ctx, call.grid, call.rec)) return rc;
+    mcamd::FinishSpec fs;
+    if (call.how == Finish::kFolded) {
+        fs.out = d_stats;
+        fs.ticket = ctx->d_ticket;
+        fs.n_value = n_value;
+    }
+    HIP_TRY(hipEventRecord(ctx->ring0[slot], ctx->stream));
+    HIP_TRY(call.launch(fs));
+    HIP_TRY(hipEventRecord(ctx->ring1[slot], ctx->stream));
+    if (call.how == Finish::kSmall)
+        HIP_TRY(mcamd::launch_small_final(ctx->d_partials, call.grid, call.rec, d_stats, ctx->stream, n_value));
+    else if (call.how == Finish::kReduce)
+        HIP_TRY(mcamd::launch_final_reduce(ctx->d_partials, call.grid, call.rec, d_stats, ctx->stream, n_value));
+    ctx->n_enqueued++;
+    return MCAMD_OK;
+}
+
+// The prepare_* steps below hold the argument checks and the job of a call with a synchronous and an enqueue form.
+// Once every check has passed they hand the DeviceCall to drive (the form's driver) and return what it returns.
+
+template <typename Drive>
+int prepare_paths(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, Drive drive)
+{
+    if (int rc = check_common(ctx, opt, sim)) return rc;
+    if (sim->n_paths_local == 0) return drive(empty_call());
+    const mcamd::PathJob job = make_job(opt, sim);
+    const uint32_t grid = mcamd::price_grid(job, ctx->compute_units);
+    // few records: the kernel's last workgroup sums them and writes the result itself — one launch and no copy per
+    // call (the reference's shape, inc/trajectories.cuh:77-111 + one cudaMemcpy)
+    const Finish how = grid > mcamd::kFoldMaxRecords ? Finish::kReduce
+                       : (sim->flags & MCAMD_FLAG_SEPARATE_REDUCE) ? Finish::kSmall : Finish::kFolded;
+    return drive(DeviceCall{job.n_local, grid, (job.vr & 2) ? 5 : 2, 6, how, [&](const mcamd::FinishSpec &fs) {
+        return mcamd::launch_price(job, ctx->compute_units, ctx->d_partials, ctx->d_queue, grid, fs, ctx->stream);
+    }});
+}
+
+template <typename Drive>
+int prepare_store(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, int layout, void *d_traj,
+                  int32_t *d_counts, void *d_payoffs, Drive drive)
+{
+    if (int rc = check_plain(ctx, opt, sim, layout)) return rc;
+    if (sim->n_paths_local == 0) return drive(empty_call());
+    if (!d_traj) return fail(MCAMD_ERR_INVALID, "d_traj is NULL");
+    mcamd::PathJob job = make_job(opt, sim);
+    if (d_counts && !job.window) {
+        // counts requested for a European payoff: count against B but let every count pay
+        job.window = true;
+        job.P1 = INT32_MIN;
+        job.P2 = INT32_MAX;
+    }
+    const uint32_t grid = mcamd::store_grid(job.n_local, job.precision);
+    return drive(DeviceCall{job.n_local, grid, 2, 6, Finish::kReduce, [&](const mcamd::FinishSpec &) {
+        return mcamd::launch_store(job, layout, d_traj, d_counts, d_payoffs, ctx->d_partials, grid, ctx->stream);
+    }});
+}
+
+// The nested-MC calls: the inner stage (variant) and the fused one (outer_seed, which must differ from the inner seed;
+// d_prices / d_counts are its outputs: the fused entry points pass them non-const).
+template <typename Drive>
+int prepare_nmc(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, int layout, int variant, bool fused,
+                uint64_t outer_seed, const void *d_prices, const int32_t *d_counts, void *d_point_prices, Drive drive)
+{
+    if (int rc = check_plain(ctx, opt, sim, layout)) return rc;
     if (!fused && variant != MCAMD_NMC_WAVE_PER_POINT && variant != MCAMD_NMC_BLOCK_PER_POINT &&
         variant != MCAMD_NMC_BLOCK_PER_POINT_PLAIN)
         return fail(MCAMD_ERR_INVALID, "unknown nested-MC variant %d", variant);
@@ -313,76 +453,42 @@ int prepare_nmc(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, i
     if (top >= 18446744073709551615.0L)
         return fail(MCAMD_ERR_INVALID, "(path_offset + n_paths_local) * n_steps * n_paths_inner overflows the 64-bit "
                                        "Philox subsequence");
-    if (sim->n_paths_local == 0) return MCAMD_OK;
+    if (sim->n_paths_local == 0) return drive(empty_call());
     if (!d_prices || !d_point_prices) return fail(MCAMD_ERR_INVALID, "d_prices and d_point_prices must be non-NULL");
     if (opt->use_window && !d_counts) return fail(MCAMD_ERR_INVALID, "bullet window needs d_counts");
     const uint64_t n_points = sim->n_paths_local * static_cast<uint64_t>(sim->n_steps);
     if (n_points / sim->n_steps != sim->n_paths_local) return fail(MCAMD_ERR_INVALID, "point count overflows");
-    job->path = make_job(opt, sim);
-    job->n_inner = sim->n_paths_inner;
-    job->discount = std::exp(-opt->r * opt->T);
-    job->n_points = n_points;
-    job->compute_units = ctx->compute_units;
-    return MCAMD_OK;
+    mcamd::NmcJob job;
+    job.path = make_job(opt, sim);
+    job.n_inner = sim->n_paths_inner;
+    job.discount = std::exp(-opt->r * opt->T);
+    job.n_points = n_points;
+    job.compute_units = ctx->compute_units;
+    if (fused) {
+        const uint32_t grid = mcamd::nmc_fused_grid(job);
+        return drive(DeviceCall{n_points, grid, mcamd::kNmcRecord, 6, Finish::kReduce, [&](const mcamd::FinishSpec &) {
+            return mcamd::launch_nmc_fused(job, outer_seed, layout, const_cast<void *>(d_prices),
+                                           const_cast<int32_t *>(d_counts), d_point_prices, ctx->d_partials, ctx->d_queue,
+                                           grid, ctx->stream);
+        }});
+    }
+    const uint32_t grid = mcamd::nmc_grid(job, variant);
+    return drive(DeviceCall{n_points, grid, mcamd::kNmcRecord, 6, Finish::kReduce, [&](const mcamd::FinishSpec &) {
+        return mcamd::launch_nmc_inner(job, layout, variant, d_prices, d_counts, d_point_prices, ctx->d_partials,
+                                       ctx->d_queue, grid, ctx->stream);
+    }});
 }
 
-// host tail of the nested-MC calls: the scalar diagnostic of the wrappers (inc/wrappers.cuh:185-189,316-321)
-void fill_nmc_result(mcamd_result *res, uint64_t n_points, uint32_t grid)
+// The Greeks calls.  The kernel always finishes its own sum (greeks_grid caps the grid) into the 16-double statistics
+// record; the request-only refusals come before the context is looked at.
+template <typename Drive>
+int prepare_greeks(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, int method, Drive drive)
 {
-    res->n = n_points;
-    res->price = n_points ? res->sum / static_cast<double>(n_points) : 0.0;  // mean point price (diagnostic)
-    res->grid = grid;
-    res->block = 256;
-}
-
-// Asynchronous calls: an empty shard leaves all-zero statistics, still ordered on the stream.
-int enqueue_empty(mcamd_ctx *ctx, double *d_stats, int stats_doubles = 6)
-{
-    const uint32_t slot = static_cast<uint32_t>(ctx->n_enqueued % mcamd_ctx::kRing);
-    HIP_TRY(hipMemsetAsync(d_stats, 0, stats_doubles * sizeof(double), ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ring0[slot], ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ring1[slot], ctx->stream));
-    ctx->n_enqueued++;
-    return MCAMD_OK;
-}
-
-// Asynchronous calls: `launch` enqueues the simulation kernel (grid blocks, one record of rec doubles each, into
-// ctx->d_partials) between a pair of ring events; the final reduce then leaves {record, zeros.., n_value} — the
-// 6-double statistics layout — in d_stats.  Nothing waits on the host.
-template <typename Launch>
-int enqueue_with_stats(mcamd_ctx *ctx, uint32_t grid, int rec, double n_value, double *d_stats, Finish how, Launch launch)
-{
-    const uint32_t slot = static_cast<uint32_t>(ctx->n_enqueued % mcamd_ctx::kRing);
-    // growing the scratch buffer frees the old one: wait for work that may still read it
-    if (static_cast<uint64_t>(grid) * rec > ctx->partial_capacity) HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (int rc = ensure_partials(ctx, grid, rec)) return rc;
-    HIP_TRY(hipEventRecord(ctx->ring0[slot], ctx->stream));
-    HIP_TRY(launch());
-    HIP_TRY(hipEventRecord(ctx->ring1[slot], ctx->stream));
-    if (how == Finish::kSmall) HIP_TRY(mcamd::launch_small_final(ctx->d_partials, grid, rec, d_stats, ctx->stream, n_value));
-    else if (how == Finish::kReduce) HIP_TRY(mcamd::launch_final_reduce(ctx->d_partials, grid, rec, d_stats, ctx->stream, n_value));
-    ctx->n_enqueued++;
-    return MCAMD_OK;
-}
-
-// The estimator a Greeks call runs: AUTO is pathwise without a window and likelihood ratio with one.  0 on a bad request.
-int greeks_method(const mcamd_option *opt, int method)
-{
-    if (method == MCAMD_GREEKS_AUTO) return opt->use_window ? MCAMD_GREEKS_LIKELIHOOD_RATIO : MCAMD_GREEKS_PATHWISE;
-    if (method == MCAMD_GREEKS_PATHWISE) return opt->use_window ? 0 : MCAMD_GREEKS_PATHWISE;
-    return method == MCAMD_GREEKS_LIKELIHOOD_RATIO ? method : 0;
-}
-
-// argument checks, estimator and job of the Greeks calls (shared by the synchronous call and the enqueue form)
-int prepare_greeks(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, int method, mcamd::GreeksJob *job,
-                   int *used)
-{
-    // the Greeks-specific refusals first: they depend on the request alone, not on a device
     if (!opt || !sim) return fail(MCAMD_ERR_INVALID, "opt and sim must be non-NULL");
     if (sim->flags & ~MCAMD_FLAG_LOG_SPACE)
         return fail(MCAMD_ERR_INVALID, "Greeks take flags 0 or MCAMD_FLAG_LOG_SPACE only, got %d", sim->flags);
-    *used = greeks_method(opt, method);
-    if (*used == 0)
+    const mcamd::GreeksRule rule = mcamd::greeks_rule(*opt, method);
+    if (rule.method == 0)
         return fail(MCAMD_ERR_INVALID, method == MCAMD_GREEKS_PATHWISE
                                            ? "pathwise Greeks are wrong for the bullet window's discontinuous payoff: use "
                                              "MCAMD_GREEKS_LIKELIHOOD_RATIO (or AUTO) with use_window = 1"
@@ -390,15 +496,16 @@ int prepare_greeks(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim
     const double S_s = (opt->Sk == 0.0) ? opt->S0 : opt->Sk;
     if (!(opt->v > 0.0) || !(S_s > 0.0))
         return fail(MCAMD_ERR_INVALID, "Greeks need v > 0 and a positive start price (v = %g, S = %g)", opt->v, S_s);
-    mcamd_result dummy;
-    if (int rc = check_common(ctx, opt, sim, &dummy)) return rc;
-    job->path = make_job(opt, sim);
-    job->path.logspace = true;
-    job->path.vr = 0;
-    job->lr = *used == MCAMD_GREEKS_LIKELIHOOD_RATIO;
+    if (int rc = check_common(ctx, opt, sim)) return rc;
+    if (sim->n_paths_local == 0) return drive(empty_call(mcamd::kGreeksStats));
+    mcamd::GreeksJob job;
+    job.path = make_job(opt, sim);
+    job.path.logspace = true;
+    job.path.vr = 0;
+    job.lr = rule.method == MCAMD_GREEKS_LIKELIHOOD_RATIO;
     const double dt = opt->dt > 0.0 ? opt->dt : opt->T / static_cast<double>(sim->n_steps);
-    const double v = opt->v, r = opt->r, T = opt->T, T_h = dt * static_cast<double>(job->path.n_sim);
-    mcamd::GreeksConsts &g = job->g;
+    const double v = opt->v, r = opt->r, T = opt->T, T_h = dt * static_cast<double>(job.path.n_sim);
+    mcamd::GreeksConsts &g = job.g;
     g.K = opt->K;
     g.S_s = S_s;
     g.T = T;
@@ -416,29 +523,13 @@ int prepare_greeks(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim
     g.delta_lr = 1.0 / (S_s * v * g.sqrt_dt);
     g.gamma_lr1 = 1.0 / (S_s * S_s * v * v * dt);
     g.gamma_lr2 = 1.0 / (S_s * S_s * v * g.sqrt_dt);
-    g.theta_on = (*used == MCAMD_GREEKS_PATHWISE && opt->Tk == 0 && opt->dt == 0.0) ? 1 : 0;
-    return MCAMD_OK;
+    g.theta_on = rule.theta_defined;
+    const uint32_t grid = mcamd::greeks_grid(job);
+    return drive(DeviceCall{job.path.n_local, grid, mcamd::kGreeksRecord, mcamd::kGreeksStats, Finish::kFolded,
+                            [&](const mcamd::FinishSpec &fs) {
+                                return mcamd::launch_greeks(job, ctx->d_partials, grid, fs.out, fs.ticket, ctx->stream);
+                            }});
 }
-
-void finalize_greeks_into(const double stats[16], double r, double T, int theta_defined, mcamd_greeks *out)
-{
-    const double disc = std::exp(-r * T);
-    const uint64_t n = static_cast<uint64_t>(std::llround(stats[mcamd::kGreeksRecord]));
-    const double N = static_cast<double>(n);
-    out->n = n;
-    for (int k = 0; k < mcamd::kGreeks; ++k) {
-        const double sum = stats[2 * k], sumsq = stats[2 * k + 1];
-        const double mean = n ? sum / N : 0.0;
-        double var = n > 1 ? (sumsq - N * mean * mean) / (N - 1.0) : 0.0;
-        if (var < 0.0) var = 0.0;
-        out->sum[k] = sum;
-        out->sumsq[k] = sumsq;
-        out->value[k] = disc * mean;
-        out->std_err[k] = n ? disc * std::sqrt(var / N) : 0.0;
-    }
-    if (!theta_defined) out->value[MCAMD_GREEK_THETA] = out->std_err[MCAMD_GREEK_THETA] = std::nan("");
-}
-
 // The refusals of the American calls that depend on the request's shape alone (shared with the workspace-size query):
 // dates and basis size on success.
 int check_american_shape(const mcamd_sim *sim, const mcamd_american *am, uint32_t *M, int *n_basis)
@@ -548,13 +639,14 @@ int mcamd_ctx_create(int device, void *hip_stream, mcamd_ctx **out)
     }
     if (e == hipSuccess) e = hipMalloc(&ctx->d_out, 8 * sizeof(double));
     if (e == hipSuccess) e = hipMalloc(&ctx->d_queue, 64);
-    if (e == hipSuccess) e = hipMemset(ctx->d_queue, 0, 64);   // the ticket must be zero at a kernel's first launch
+    // the ticket must be zero at a kernel's first launch: zeroed on the context's stream, so that the zeroing is
+    // ordered before that launch also on a caller's non-blocking stream
+    if (e == hipSuccess) e = hipMemsetAsync(ctx->d_queue, 0, 64, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e == hipSuccess) ctx->d_ticket = reinterpret_cast<unsigned int *>(ctx->d_queue + 2);
     ctx->compute_units = static_cast<uint32_t>(prop.multiProcessorCount);
-    if (e == hipSuccess) e = hipHostMalloc(&ctx->h_out, 8 * sizeof(double), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void **>(&ctx->h_out_dev), ctx->h_out, 0);
-    if (e == hipSuccess) e = hipHostMalloc(&ctx->h_greeks, mcamd::kGreeksStats * sizeof(double), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void **>(&ctx->h_greeks_dev), ctx->h_greeks, 0);
+    if (e == hipSuccess) e = hipHostMalloc(&ctx->h_rec, mcamd_ctx::kRecord * sizeof(double), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void **>(&ctx->h_rec_dev), ctx->h_rec, 0);
     if (e != hipSuccess) {
         mcamd_ctx_destroy(ctx);
         return fail(MCAMD_ERR_HIP, "context setup: %s", hipGetErrorString(e));
@@ -571,8 +663,7 @@ int mcamd_ctx_destroy(mcamd_ctx *ctx)
     if (ctx->d_partials) (void)hipFree(ctx->d_partials);
     if (ctx->d_out) (void)hipFree(ctx->d_out);
     if (ctx->d_queue) (void)hipFree(ctx->d_queue);
-    if (ctx->h_out) (void)hipHostFree(ctx->h_out);
-    if (ctx->h_greeks) (void)hipHostFree(ctx->h_greeks);
+    if (ctx->h_rec) (void)hipHostFree(ctx->h_rec);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     if (ctx->ev2) (void)hipEventDestroy(ctx->ev2);
@@ -658,105 +749,46 @@ int mcamd_memcpy_to_device(mcamd_ctx *ctx, void *d_dst, const void *h_src, uint6
 
 int mcamd_price_paths(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, mcamd_result *res)
 {
-    if (int rc = check_common(ctx, opt, sim, res)) return rc;
+    if (!res) return fail(MCAMD_ERR_INVALID, "opt, sim and res must be non-NULL");
     zero_result(res);
-    if (sim->n_paths_local == 0) return MCAMD_OK;  // empty shard: all-zero statistics
-    HIP_TRY(hipSetDevice(ctx->device));
-    const mcamd::PathJob job = make_job(opt, sim);
-    const int rec = (job.vr & 2) ? 5 : 2;
-    const uint32_t grid = mcamd::price_grid(job, ctx->compute_units);
-    if (int rc = ensure_partials(ctx, grid, rec)) return rc;
-    // few records: the kernel's last workgroup sums them and writes the result straight into pinned host memory —
-    // one launch and no copy per call (the reference's shape, inc/trajectories.cuh:77-111 + one cudaMemcpy)
-    const Finish how = grid > mcamd::kFoldMaxRecords ? Finish::kReduce
-                       : (sim->flags & MCAMD_FLAG_SEPARATE_REDUCE) ? Finish::kSmall : Finish::kFolded;
-    mcamd::FinishSpec fs;
-    if (how == Finish::kFolded) {
-        fs.out = ctx->h_out_dev;
-        fs.ticket = ctx->d_ticket;
-    }
-    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
-    HIP_TRY(mcamd::launch_price(job, ctx->compute_units, ctx->d_partials, ctx->d_queue, grid, fs, ctx->stream));
-    return finish_pricing(ctx, grid, rec, opt, sim, res, how);
+    return prepare_paths(ctx, opt, sim, [&](const auto &call) {
+        return run_sync(ctx, call, res, [&](const double *rec) {
+            finalize_record(rec, call.rec == 5, sim->n_paths_local, opt->r, opt->T, res);
+        });
+    });
 }
 
 int mcamd_price_paths_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, double *d_stats)
 {
-    mcamd_result dummy;
-    if (int rc = check_common(ctx, opt, sim, &dummy)) return rc;
-    if (!d_stats) return fail(MCAMD_ERR_INVALID, "d_stats is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (sim->n_paths_local == 0) return enqueue_empty(ctx, d_stats);
-    const mcamd::PathJob job = make_job(opt, sim);
-    const int rec = (job.vr & 2) ? 5 : 2;
-    const uint32_t grid = mcamd::price_grid(job, ctx->compute_units);
-    const Finish how = grid > mcamd::kFoldMaxRecords ? Finish::kReduce
-                       : (sim->flags & MCAMD_FLAG_SEPARATE_REDUCE) ? Finish::kSmall : Finish::kFolded;
-    mcamd::FinishSpec fs;
-    if (how == Finish::kFolded) {   // the kernel leaves the statistics record in d_stats itself
-        fs.out = d_stats;
-        fs.ticket = ctx->d_ticket;
-        fs.n_value = static_cast<double>(sim->n_paths_local);
-    }
-    return enqueue_with_stats(ctx, grid, rec, static_cast<double>(sim->n_paths_local), d_stats, how, [&] {
-        return mcamd::launch_price(job, ctx->compute_units, ctx->d_partials, ctx->d_queue, grid, fs, ctx->stream);
-    });
+    return prepare_paths(ctx, opt, sim, [&](const auto &call) { return run_enqueue(ctx, call, d_stats); });
 }
 
 int mcamd_simulate_trajectories_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, int layout,
                                         void *d_traj, int32_t *d_counts, void *d_payoffs, double *d_stats)
 {
-    mcamd::PathJob job;
-    if (int rc = prepare_store(ctx, opt, sim, layout, d_traj, d_counts, &job)) return rc;
-    if (!d_stats) return fail(MCAMD_ERR_INVALID, "d_stats is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (sim->n_paths_local == 0) return enqueue_empty(ctx, d_stats);
-    const uint32_t grid = mcamd::store_grid(job.n_local, job.precision);
-    return enqueue_with_stats(ctx, grid, 2, static_cast<double>(sim->n_paths_local), d_stats, Finish::kReduce, [&] {
-        return mcamd::launch_store(job, layout, d_traj, d_counts, d_payoffs, ctx->d_partials, grid, ctx->stream);
-    });
+    return prepare_store(ctx, opt, sim, layout, d_traj, d_counts, d_payoffs,
+                         [&](const auto &call) { return run_enqueue(ctx, call, d_stats); });
 }
 
 int mcamd_nmc_inner_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, int layout, int variant,
                             const void *d_prices, const int32_t *d_counts, void *d_point_prices, double *d_stats)
 {
-    mcamd::NmcJob job;
-    if (int rc = prepare_nmc(ctx, opt, sim, layout, variant, false, 0, d_prices, d_counts, d_point_prices, &job)) return rc;
-    if (!d_stats) return fail(MCAMD_ERR_INVALID, "d_stats is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (sim->n_paths_local == 0) return enqueue_empty(ctx, d_stats);
-    const uint32_t grid = mcamd::nmc_grid(job, variant);
-    return enqueue_with_stats(ctx, grid, mcamd::kNmcRecord, static_cast<double>(job.n_points), d_stats, Finish::kReduce, [&] {
-        return mcamd::launch_nmc_inner(job, layout, variant, d_prices, d_counts, d_point_prices, ctx->d_partials,
-                                       ctx->d_queue, grid, ctx->stream);
-    });
+    return prepare_nmc(ctx, opt, sim, layout, variant, false, 0, d_prices, d_counts, d_point_prices,
+                       [&](const auto &call) { return run_enqueue(ctx, call, d_stats); });
 }
 
 int mcamd_nmc_fused_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, uint64_t outer_seed, int layout,
                             void *d_prices, int32_t *d_counts, void *d_point_prices, double *d_stats)
 {
-    mcamd::NmcJob job;
-    if (int rc = prepare_nmc(ctx, opt, sim, layout, 0, true, outer_seed, d_prices, d_counts, d_point_prices, &job)) return rc;
-    if (!d_stats) return fail(MCAMD_ERR_INVALID, "d_stats is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (sim->n_paths_local == 0) return enqueue_empty(ctx, d_stats);
-    const uint32_t grid = mcamd::nmc_fused_grid(job);
-    return enqueue_with_stats(ctx, grid, mcamd::kNmcRecord, static_cast<double>(job.n_points), d_stats, Finish::kReduce, [&] {
-        return mcamd::launch_nmc_fused(job, outer_seed, layout, d_prices, d_counts, d_point_prices, ctx->d_partials,
-                                       ctx->d_queue, grid, ctx->stream);
-    });
+    return prepare_nmc(ctx, opt, sim, layout, 0, true, outer_seed, d_prices, d_counts, d_point_prices,
+                       [&](const auto &call) { return run_enqueue(ctx, call, d_stats); });
 }
 
 int mcamd_finalize_nmc_stats(const double stats[6], mcamd_result *res)
 {
     if (!stats || !res) return fail(MCAMD_ERR_INVALID, "stats and res must be non-NULL");
     zero_result(res);
-    res->sum = stats[0];
-    res->sumsq = stats[1];
-    res->work_steps = 64.0 * stats[2];   // wave-steps x 64 lanes
-    res->live_steps = stats[3];
-    res->n = static_cast<uint64_t>(std::llround(stats[5]));
-    res->price = res->n ? res->sum / static_cast<double>(res->n) : 0.0;
+    finalize_nmc_into(stats, static_cast<uint64_t>(std::llround(stats[5])), res);
     return MCAMD_OK;
 }
 
@@ -778,9 +810,7 @@ int mcamd_finalize_stats(const double stats[6], double r, double T, int control_
 {
     if (!stats || !res) return fail(MCAMD_ERR_INVALID, "stats and res must be non-NULL");
     zero_result(res);
-    const uint64_t n = static_cast<uint64_t>(std::llround(stats[5]));
-    if (control_variate) finalize_cv_into(stats, n, r, T, res);
-    else finalize_into(stats[0], stats[1], n, r, T, res);
+    finalize_record(stats, control_variate != 0, static_cast<uint64_t>(std::llround(stats[5])), r, T, res);
     return MCAMD_OK;
 }
 
@@ -788,16 +818,12 @@ int mcamd_simulate_trajectories(mcamd_ctx *ctx, const mcamd_option *opt, const m
                                 void *d_traj, int32_t *d_counts, void *d_payoffs, mcamd_result *res)
 {
     if (!res) return fail(MCAMD_ERR_INVALID, "opt, sim and res must be non-NULL");
-    mcamd::PathJob job;
-    if (int rc = prepare_store(ctx, opt, sim, layout, d_traj, d_counts, &job)) return rc;
     zero_result(res);
-    if (sim->n_paths_local == 0) return MCAMD_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const uint32_t grid = mcamd::store_grid(job.n_local, job.precision);
-    if (int rc = ensure_partials(ctx, grid)) return rc;
-    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
-    HIP_TRY(mcamd::launch_store(job, layout, d_traj, d_counts, d_payoffs, ctx->d_partials, grid, ctx->stream));
-    return finish_pricing(ctx, grid, 2, opt, sim, res);
+    return prepare_store(ctx, opt, sim, layout, d_traj, d_counts, d_payoffs, [&](const auto &call) {
+        return run_sync(ctx, call, res, [&](const double *rec) {
+            finalize_into(rec[0], rec[1], sim->n_paths_local, opt->r, opt->T, res);
+        });
+    });
 }
 
 int mcamd_diag_store_pattern(mcamd_ctx *ctx, uint64_t n_paths_local, uint32_t n_steps, int precision, void *d_traj,
@@ -826,19 +852,19 @@ int mcamd_diag_store_pattern(mcamd_ctx *ctx, uint64_t n_paths_local, uint32_t n_
 int mcamd_price_from_normals(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const void *d_normals,
                              void *d_payoffs, mcamd_result *res)
 {
-    if (int rc = check_common(ctx, opt, sim, res)) return rc;
-    if (sim->flags & (MCAMD_FLAG_ANTITHETIC | MCAMD_FLAG_CONTROL_VARIATE))
-        return fail(MCAMD_ERR_INVALID, "variance-reduction flags apply to mcamd_price_paths only");
+    if (!res) return fail(MCAMD_ERR_INVALID, "opt, sim and res must be non-NULL");
+    if (int rc = check_plain(ctx, opt, sim)) return rc;
     zero_result(res);
     if (sim->n_paths_local == 0) return MCAMD_OK;
     if (!d_normals) return fail(MCAMD_ERR_INVALID, "d_normals is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
     const mcamd::PathJob job = make_job(opt, sim);
     const uint32_t grid = mcamd::array_grid(job.n_local);
-    if (int rc = ensure_partials(ctx, grid)) return rc;
-    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
-    HIP_TRY(mcamd::launch_from_normals(job, d_normals, d_payoffs, ctx->d_partials, grid, ctx->stream));
-    return finish_pricing(ctx, grid, 2, opt, sim, res);
+    const DeviceCall call{job.n_local, grid, 2, 6, Finish::kReduce, [&](const mcamd::FinishSpec &) {
+        return mcamd::launch_from_normals(job, d_normals, d_payoffs, ctx->d_partials, grid, ctx->stream);
+    }};
+    return run_sync(ctx, call, res, [&](const double *rec) {
+        finalize_into(rec[0], rec[1], sim->n_paths_local, opt->r, opt->T, res);
+    });
 }
 
 int mcamd_generate_normals(mcamd_ctx *ctx, uint64_t seed, uint64_t n, int precision, void *d_out, float *kernel_ms)
@@ -868,15 +894,13 @@ int mcamd_reduce_sum(mcamd_ctx *ctx, const void *d_in, uint64_t n, int precision
     if (kernel_ms) *kernel_ms = 0.0f;
     if (n == 0) return MCAMD_OK;
     if (!d_in) return fail(MCAMD_ERR_INVALID, "d_in is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
     const uint32_t grid = mcamd::reduce_grid(n, variant);
-    if (int rc = ensure_partials(ctx, grid)) return rc;
+    const DeviceCall call{n, grid, 2, 6, Finish::kReduce, [&](const mcamd::FinishSpec &) {
+        return mcamd::launch_reduce(d_in, n, precision, variant, ctx->d_partials, grid, ctx->stream);
+    }};
     mcamd_result tmp;
     zero_result(&tmp);
-    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
-    HIP_TRY(mcamd::launch_reduce(d_in, n, precision, variant, ctx->d_partials, grid, ctx->stream));
-    if (int rc = finish(ctx, grid, &tmp)) return rc;
-    *sum = tmp.sum;
+    if (int rc = run_sync(ctx, call, &tmp, [&](const double *rec) { *sum = rec[0]; })) return rc;
     if (kernel_ms) *kernel_ms = tmp.kernel_ms;
     return MCAMD_OK;
 }
@@ -885,38 +909,20 @@ int mcamd_nmc_inner(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *si
                     const void *d_prices, const int32_t *d_counts, void *d_point_prices, mcamd_result *res)
 {
     if (!res) return fail(MCAMD_ERR_INVALID, "opt, sim and res must be non-NULL");
-    mcamd::NmcJob job;
-    if (int rc = prepare_nmc(ctx, opt, sim, layout, variant, false, 0, d_prices, d_counts, d_point_prices, &job)) return rc;
     zero_result(res);
-    if (sim->n_paths_local == 0) return MCAMD_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const uint32_t grid = mcamd::nmc_grid(job, variant);
-    if (int rc = ensure_partials(ctx, grid, mcamd::kNmcRecord)) return rc;
-    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
-    HIP_TRY(mcamd::launch_nmc_inner(job, layout, variant, d_prices, d_counts, d_point_prices, ctx->d_partials,
-                                    ctx->d_queue, grid, ctx->stream));
-    if (int rc = finish(ctx, grid, res, mcamd::kNmcRecord)) return rc;
-    fill_nmc_result(res, job.n_points, grid);
-    return MCAMD_OK;
+    return prepare_nmc(ctx, opt, sim, layout, variant, false, 0, d_prices, d_counts, d_point_prices, [&](const auto &call) {
+        return run_sync(ctx, call, res, [&](const double *rec) { finalize_nmc_into(rec, call.n, res); });
+    });
 }
 
 int mcamd_nmc_fused(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, uint64_t outer_seed, int layout,
                     void *d_prices, int32_t *d_counts, void *d_point_prices, mcamd_result *res)
 {
     if (!res) return fail(MCAMD_ERR_INVALID, "opt, sim and res must be non-NULL");
-    mcamd::NmcJob job;
-    if (int rc = prepare_nmc(ctx, opt, sim, layout, 0, true, outer_seed, d_prices, d_counts, d_point_prices, &job)) return rc;
     zero_result(res);
-    if (sim->n_paths_local == 0) return MCAMD_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const uint32_t grid = mcamd::nmc_fused_grid(job);
-    if (int rc = ensure_partials(ctx, grid, mcamd::kNmcRecord)) return rc;
-    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
-    HIP_TRY(mcamd::launch_nmc_fused(job, outer_seed, layout, d_prices, d_counts, d_point_prices, ctx->d_partials,
-                                    ctx->d_queue, grid, ctx->stream));
-    if (int rc = finish(ctx, grid, res, mcamd::kNmcRecord)) return rc;
-    fill_nmc_result(res, job.n_points, grid);
-    return MCAMD_OK;
+    return prepare_nmc(ctx, opt, sim, layout, 0, true, outer_seed, d_prices, d_counts, d_point_prices, [&](const auto &call) {
+        return run_sync(ctx, call, res, [&](const double *rec) { finalize_nmc_into(rec, call.n, res); });
+    });
 }
 
 int mcamd_reduce_partials(mcamd_ctx *ctx, const void *d_in, uint64_t n, int precision, int variant, uint32_t n_blocks,
@@ -980,51 +986,25 @@ int mcamd_price_greeks(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim 
 {
     if (!out) return fail(MCAMD_ERR_INVALID, "out is NULL");
     std::memset(out, 0, sizeof *out);
-    mcamd::GreeksJob job;
-    int used = 0;
-    if (int rc = prepare_greeks(ctx, opt, sim, method, &job, &used)) return rc;
-    out->method = used;
-    if (sim->n_paths_local == 0) return MCAMD_OK;  // empty shard: all-zero record
-    HIP_TRY(hipSetDevice(ctx->device));
-    const uint32_t grid = mcamd::greeks_grid(job);
-    if (int rc = ensure_partials(ctx, grid, mcamd::kGreeksRecord)) return rc;
-    // the kernel's last workgroup writes the record into pinned host memory; a NaN left there means it never did
-    // (e.g. an arrival ticket that was not zero at launch): fail loudly instead of returning the previous call's sums
-    for (int k = 0; k < mcamd::kGreeksStats; ++k) ctx->h_greeks[k] = std::nan("");
-    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
-    HIP_TRY(mcamd::launch_greeks(job, ctx->d_partials, grid, ctx->h_greeks_dev, ctx->d_ticket, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipEventElapsedTime(&out->kernel_ms, ctx->ev0, ctx->ev1));
-    double stats[mcamd::kGreeksStats];
-    std::memcpy(stats, ctx->h_greeks, sizeof stats);
-    if (std::isnan(stats[0]) || std::isnan(stats[mcamd::kGreeksRecord]))
-        return fail(MCAMD_ERR_HIP, "Greeks kernel left no result (its last workgroup did not finish the sum)");
-    const float kms = out->kernel_ms;
-    finalize_greeks_into(stats, opt->r, opt->T, job.g.theta_on, out);
-    out->kernel_ms = out->total_ms = kms;   // one launch is the whole call
-    out->grid = grid;
-    out->block = 256;
-    return MCAMD_OK;
+    return prepare_greeks(ctx, opt, sim, method, [&](const auto &call) {
+        const mcamd::GreeksRule rule = mcamd::greeks_rule(*opt, method);
+        out->method = rule.method;
+        return run_sync(ctx, call, out, [&](const double *stats) {
+            finalize_greeks_into(stats, opt->r, opt->T, rule.theta_defined, out);
+        });
+    });
 }
 
 int mcamd_price_greeks_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, int method,
                                double *d_stats)
 {
-    mcamd::GreeksJob job;
-    int used = 0;
-    if (int rc = prepare_greeks(ctx, opt, sim, method, &job, &used)) return rc;
-    if (!d_stats) return fail(MCAMD_ERR_INVALID, "d_stats is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (sim->n_paths_local == 0) return enqueue_empty(ctx, d_stats, mcamd::kGreeksStats);
-    const uint32_t grid = mcamd::greeks_grid(job);
-    // NaN (all-ones bytes) until the kernel has written the record
-    HIP_TRY(hipMemsetAsync(d_stats, 0xFF, mcamd::kGreeksStats * sizeof(double), ctx->stream));
-    return enqueue_with_stats(ctx, grid, mcamd::kGreeksRecord, static_cast<double>(sim->n_paths_local), d_stats,
-                              Finish::kFolded, [&] {
-                                  return mcamd::launch_greeks(job, ctx->d_partials, grid, d_stats, ctx->d_ticket,
-                                                              ctx->stream);
-                              });
+    return prepare_greeks(ctx, opt, sim, method, [&](const auto &call) {
+        if (call.n && d_stats) {   // NaN (all-ones bytes) until the kernel has written the record
+            HIP_TRY(hipSetDevice(ctx->device));
+            HIP_TRY(hipMemsetAsync(d_stats, 0xFF, mcamd::kGreeksStats * sizeof(double), ctx->stream));
+        }
+        return run_enqueue(ctx, call, d_stats);
+    });
 }
 
 int mcamd_finalize_greeks_stats(const double stats[16], double r, double T, int theta_defined, mcamd_greeks *out)
@@ -1093,8 +1073,7 @@ int mcamd_price_american(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_si
         return fail(MCAMD_ERR_INVALID, "work_bytes = %llu is below the %llu bytes the workspace needs "
                                        "(mcamd_american_workspace_bytes)",
                     static_cast<unsigned long long>(work_bytes), static_cast<unsigned long long>(lay.total));
-    mcamd_result dummy;
-    if (int rc = check_common(ctx, opt, sim, &dummy)) return rc;
+    if (int rc = check_common(ctx, opt, sim)) return rc;
 
     HIP_TRY(hipSetDevice(ctx->device));
     char *base = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(d_work) + 255) & ~static_cast<uintptr_t>(255));
@@ -1127,17 +1106,17 @@ int mcamd_price_american(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_si
     const uint32_t price_grid = mcamd::american_price_grid(n_local);
     if (n_local)
         if (int rc = ensure_partials(ctx, price_grid, mcamd::kAmPriceRecord)) return rc;
-    // NaN (all-ones bytes in the record slots, NaN in the pinned record) until a kernel has written the record: a sum
-    // that never finished cannot pass as an earlier call's
+    // all-ones bits in the record slots and the pinned record until a kernel has written the record: a sum that never
+    // finished cannot pass as an earlier call's
     HIP_TRY(hipMemsetAsync(records, 0xFF, 2 * mcamd::kAmRecordSlot * sizeof(double), ctx->stream));
-    for (int k = 0; k < mcamd::kAmPriceRecord; ++k) ctx->h_out[k] = std::nan("");
+    arm_record(ctx->h_rec, mcamd::kAmPriceRecord);
     HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
     HIP_TRY(mcamd::launch_store(train, MCAMD_STEP_MAJOR, traj, nullptr, nullptr, w_partials, store_grid, ctx->stream));
     HIP_TRY(mcamd::launch_american_sweep(job, traj, V, table, records, w_partials, sweep_grid, ctx->d_ticket,
                                          ctx->stream));
     HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
     if (n_local)
-        HIP_TRY(mcamd::launch_american_price(job, table, ctx->d_partials, price_grid, ctx->h_out_dev, ctx->d_ticket,
+        HIP_TRY(mcamd::launch_american_price(job, table, ctx->d_partials, price_grid, ctx->h_rec_dev, ctx->d_ticket,
                                              ctx->stream));
     HIP_TRY(hipEventRecord(ctx->ev2, ctx->stream));
     std::vector<double> host(static_cast<size_t>(mcamd::kAmRow) * (M + 1) + 2 * mcamd::kAmRecordSlot);
@@ -1148,27 +1127,25 @@ int mcamd_price_american(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_si
     HIP_TRY(hipEventElapsedTime(&res->total_ms, ctx->ev0, ctx->ev2));
 
     const double *in_rec = host.data() + static_cast<size_t>(mcamd::kAmRow) * (M + 1);   // launch 0's slot
-    if (std::isnan(in_rec[0]) || std::isnan(in_rec[1]))
+    if (record_unwritten(in_rec, 2))
         return fail(MCAMD_ERR_HIP, "backward sweep left no in-sample record (its last workgroup did not finish the sum)");
     double rec[mcamd::kAmPriceRecord] = {0.0, 0.0, 0.0, 0.0, 0.0};
     if (n_local) {
-        std::memcpy(rec, ctx->h_out, sizeof rec);
-        for (double x : rec)
-            if (std::isnan(x))
-                return fail(MCAMD_ERR_HIP, "American pricing kernel left no result (its last workgroup did not finish "
-                                           "the sum)");
+        std::memcpy(rec, ctx->h_rec, sizeof rec);
+        if (record_unwritten(rec, mcamd::kAmPriceRecord))
+            return fail(MCAMD_ERR_HIP, "American pricing kernel left no result (its last workgroup did not finish "
+                                       "the sum)");
     }
-    mcamd_result out, in;
-    finalize_into(rec[0], rec[1], n_local, 0.0, 1.0, &out);   // samples are discounted where paid: D = 1
-    finalize_into(in_rec[0], in_rec[1], am->n_train, 0.0, 1.0, &in);
-    res->price = out.price;
+    const Estimate out = estimate(rec[0], rec[1], n_local, 1.0);   // samples are discounted where paid: D = 1
+    const Estimate in = estimate(in_rec[0], in_rec[1], am->n_train, 1.0);
+    res->price = out.value;
     res->std_err = out.std_err;
     res->sum = rec[0];
     res->sumsq = rec[1];
     res->n = n_local;
     res->n_early = static_cast<uint64_t>(std::llround(rec[2]));
     res->sum_t_exercise = rec[3];
-    res->in_sample_price = in.price;
+    res->in_sample_price = in.value;
     res->in_sample_std_err = in.std_err;
     res->in_sample_sum = in_rec[0];
     res->in_sample_sumsq = in_rec[1];
@@ -1177,8 +1154,7 @@ int mcamd_price_american(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_si
     bool immediate = floor_at_immediate(h0, &res->in_sample_price, &res->in_sample_std_err);
     if (n_local) immediate = floor_at_immediate(h0, &res->price, &res->std_err) || immediate;
     res->immediate_exercise = immediate ? 1 : 0;
-    res->ci_lo = res->price - 1.959963984540054 * res->std_err;
-    res->ci_hi = res->price + 1.959963984540054 * res->std_err;
+    set_ci(res);
     res->n_dates = M;
     for (uint32_t j = 1; j < M; ++j) res->n_regressed += host[static_cast<size_t>(j) * mcamd::kAmRow + 4] != 0.0 ? 1 : 0;
     if (h_coeffs) {
@@ -1190,7 +1166,7 @@ int mcamd_price_american(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_si
         }
     }
     res->grid = n_local ? price_grid : 0;
-    res->block = 256;
+    res->block = mcamd::kBlockThreads;
     res->train_grid = sweep_grid;
     return MCAMD_OK;
 }

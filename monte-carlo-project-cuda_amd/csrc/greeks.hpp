@@ -8,6 +8,7 @@
 #pragma once
 
 #include "launch.hpp"
+#include "mcamd.h"
 
 namespace mcamd {
 
@@ -39,6 +40,22 @@ struct GreeksJob {
     GreeksConsts g;
     bool lr;            // likelihood-ratio kernel (else pathwise: window-less only)
 };
+
+// The estimator a Greeks request runs and whether its theta is defined.  AUTO is pathwise without a window and likelihood
+// ratio with one; pathwise with a window, or an unknown method, is refused (method = 0).  Pathwise theta differentiates
+// the whole horizon, so it is defined only from t = 0 (Tk == 0) with dt = T / n_steps; the host reports NaN otherwise.
+struct GreeksRule {
+    int method;
+    int theta_defined;
+};
+inline GreeksRule greeks_rule(const mcamd_option &opt, int method)
+{
+    int used = 0;
+    if (method == MCAMD_GREEKS_AUTO) used = opt.use_window ? MCAMD_GREEKS_LIKELIHOOD_RATIO : MCAMD_GREEKS_PATHWISE;
+    else if (method == MCAMD_GREEKS_PATHWISE) used = opt.use_window ? 0 : MCAMD_GREEKS_PATHWISE;
+    else if (method == MCAMD_GREEKS_LIKELIHOOD_RATIO) used = method;
+    return {used, (used == MCAMD_GREEKS_PATHWISE && opt.Tk == 0 && opt.dt == 0.0) ? 1 : 0};
+}
 
 // Launch shape: the pathwise kernel takes price_grid's shape of the window-less pair-sum loop, the LR kernel that of
 // one path per thread; both are capped at kFoldMaxRecords workgroups (they grid-stride beyond), so the kernel always

@@ -8,6 +8,7 @@
 // summation order.  RCCL is loaded with dlopen when the first group is created: libmcamd.so keeps no link-time
 // dependency on it, and a process that already carries an RCCL (PyTorch ships its own) reuses that one.
 #include "mcamd.h"
+#include "greeks.hpp"
 
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>
@@ -91,8 +92,7 @@ struct mcamd_group {
     std::vector<int> devices;
     std::vector<mcamd_ctx *> ctx;
     std::vector<hipStream_t> streams;
-    std::vector<double *> d_stats;  // 8 doubles per device
-    std::vector<double *> d_greeks; // 16 doubles per device: the Greeks statistics record
+    std::vector<double *> d_stats;  // 16 doubles per device: the statistics record (6 doubles, 16 for Greeks)
     std::vector<ncclComm_t> comms;
 };
 
@@ -119,12 +119,11 @@ mcamd_sim shard_of(const mcamd_sim &sim, int R, int i)
 }
 
 // The shape every group call shares: device i enqueues its shard (enqueue(i, shard) -> one of the *_enqueue entry
-// points, which leaves a statistics record of NS doubles in bufs[i]: 6 in g->d_stats, 16 in g->d_greeks), then the one
-// collective of the path sums the records over the devices, every device is waited for, and the reduced record comes
-// back to the host.
-template <int NS, typename Enqueue>
-int run_sharded(mcamd_group *g, const mcamd_sim *sim, const std::vector<double *> &bufs, double *stats, float *kernel_ms,
-                Enqueue enqueue)
+// points, which leaves a statistics record of n_stats doubles in g->d_stats[i]), then the one collective of the path
+// sums the records over the devices, every device is waited for, and the reduced record comes back to the host, where
+// finalize(stats) fills *res.  The timings are the slowest device's simulation kernel.
+template <typename Result, typename Enqueue, typename Finalize>
+int run_sharded(mcamd_group *g, const mcamd_sim *sim, int n_stats, Result *res, Enqueue enqueue, Finalize finalize)
 {
     const int R = static_cast<int>(g->devices.size());
     for (int i = 0; i < R; ++i) {
@@ -141,7 +140,7 @@ int run_sharded(mcamd_group *g, const mcamd_sim *sim, const std::vector<double *
     if (ne == ncclSuccess) {
         ncclResult_t first = ncclSuccess;
         for (int i = 0; i < R && first == ncclSuccess; ++i)
-            first = g_rccl.AllReduce(bufs[i], bufs[i], NS, ncclDouble, ncclSum, g->comms[i], g->streams[i]);
+            first = g_rccl.AllReduce(g->d_stats[i], g->d_stats[i], n_stats, ncclDouble, ncclSum, g->comms[i], g->streams[i]);
         const ncclResult_t end = g_rccl.GroupEnd();
         ne = first != ncclSuccess ? first : end;
     }
@@ -156,15 +155,20 @@ int run_sharded(mcamd_group *g, const mcamd_sim *sim, const std::vector<double *
         if (e != hipSuccess && sync_err == hipSuccess) sync_err = e;
     }
     if (sync_err != hipSuccess) return hip_fail(sync_err, "group synchronise");
-    *kernel_ms = 0.0f;
+    float kernel_ms = 0.0f;
     for (int i = 0; i < R; ++i) {
         float ms = 0.0f;
         if (int rc = mcamd_enqueued_kernel_ms(g->ctx[i], 1, &ms)) return rc;
-        *kernel_ms = std::fmax(*kernel_ms, ms);
+        kernel_ms = std::fmax(kernel_ms, ms);
     }
+    double stats[16] = {0};
     hipError_t e = hipSetDevice(g->devices[0]);
-    if (e == hipSuccess) e = hipMemcpy(stats, bufs[0], NS * sizeof(double), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(stats, g->d_stats[0], n_stats * sizeof(double), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return hip_fail(e, "group result copy");
+    if (int rc = finalize(static_cast<const double *>(stats))) return rc;
+    res->kernel_ms = kernel_ms;
+    res->total_ms = kernel_ms;
+    res->block = mcamd::kBlockThreads;
     return MCAMD_OK;
 }
 
@@ -190,18 +194,16 @@ int mcamd_group_create(int n_devices, const int *devices, mcamd_group **out)
     for (int i = 0; i < n_devices; ++i) {
         mcamd_ctx *c = nullptr;
         hipStream_t s = nullptr;
-        double *d = nullptr, *dg = nullptr;
+        double *d = nullptr;
         int rc = MCAMD_OK;
         hipError_t e = hipSetDevice(g->devices[i]);
         if (e == hipSuccess) e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipMalloc(&d, 8 * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc(&dg, 16 * sizeof(double));
+        if (e == hipSuccess) e = hipMalloc(&d, 16 * sizeof(double));
         if (e != hipSuccess) rc = hip_fail(e, "group device setup");
         if (!rc) rc = mcamd_ctx_create(g->devices[i], s, &c);
         g->ctx.push_back(c);
         g->streams.push_back(s);
         g->d_stats.push_back(d);
-        g->d_greeks.push_back(dg);
         if (rc) {
             mcamd_group_destroy(g);
             return rc;
@@ -228,7 +230,6 @@ int mcamd_group_destroy(mcamd_group *g)
         (void)hipSetDevice(g->devices[i]);
         if (g->ctx[i]) (void)mcamd_ctx_destroy(g->ctx[i]);
         if (g->d_stats[i]) (void)hipFree(g->d_stats[i]);
-        if (g->d_greeks[i]) (void)hipFree(g->d_greeks[i]);
         if (g->streams[i]) (void)hipStreamDestroy(g->streams[i]);
     }
     delete g;
@@ -264,38 +265,27 @@ int mcamd_group_shard(mcamd_group *g, const mcamd_sim *sim, int i, uint64_t *pat
 int mcamd_group_price_paths(mcamd_group *g, const mcamd_option *opt, const mcamd_sim *sim, mcamd_result *res)
 {
     if (!g || !opt || !sim || !res) return mcamd_set_error_(MCAMD_ERR_INVALID, "group, opt, sim and res must be non-NULL");
-    double stats[8] = {0};
-    float kernel_ms = 0.0f;
-    if (int rc = run_sharded<6>(g, sim, g->d_stats, stats, &kernel_ms, [&](int i, const mcamd_sim &s) {
-            return mcamd_price_paths_enqueue(g->ctx[i], opt, &s, g->d_stats[i]);
-        }))
-        return rc;
-    if (int rc = mcamd_finalize_stats(stats, opt->r, opt->T, (sim->flags & MCAMD_FLAG_CONTROL_VARIATE) != 0, res)) return rc;
-    res->kernel_ms = kernel_ms;  // slowest device's simulation kernel
-    res->total_ms = kernel_ms;
-    res->block = 256;
-    return MCAMD_OK;
+    return run_sharded(
+        g, sim, 6, res,
+        [&](int i, const mcamd_sim &s) { return mcamd_price_paths_enqueue(g->ctx[i], opt, &s, g->d_stats[i]); },
+        [&](const double *stats) {
+            return mcamd_finalize_stats(stats, opt->r, opt->T, (sim->flags & MCAMD_FLAG_CONTROL_VARIATE) != 0, res);
+        });
 }
 
 int mcamd_group_price_greeks(mcamd_group *g, const mcamd_option *opt, const mcamd_sim *sim, int method, mcamd_greeks *out)
 {
     if (!g || !opt || !sim || !out) return mcamd_set_error_(MCAMD_ERR_INVALID, "group, opt, sim and out must be non-NULL");
-    double stats[16] = {0};
-    float kernel_ms = 0.0f;
-    if (int rc = run_sharded<16>(g, sim, g->d_greeks, stats, &kernel_ms, [&](int i, const mcamd_sim &s) {
-            return mcamd_price_greeks_enqueue(g->ctx[i], opt, &s, method, g->d_greeks[i]);
-        }))
-        return rc;
-    // every shard accepted the job, so the method is valid: AUTO is pathwise without a window, LR with one
-    const int used = method == MCAMD_GREEKS_AUTO ? (opt->use_window ? MCAMD_GREEKS_LIKELIHOOD_RATIO : MCAMD_GREEKS_PATHWISE)
-                                                 : method;
-    const int theta_defined = used == MCAMD_GREEKS_PATHWISE && opt->Tk == 0 && opt->dt == 0.0;
-    if (int rc = mcamd_finalize_greeks_stats(stats, opt->r, opt->T, theta_defined, out)) return rc;
-    out->method = used;
-    out->kernel_ms = kernel_ms;  // slowest device's kernel
-    out->total_ms = kernel_ms;
-    out->block = 256;
-    return MCAMD_OK;
+    return run_sharded(
+        g, sim, 16, out,
+        [&](int i, const mcamd_sim &s) { return mcamd_price_greeks_enqueue(g->ctx[i], opt, &s, method, g->d_stats[i]); },
+        [&](const double *stats) {
+            // every shard accepted the job, so the rule gives a valid method
+            const mcamd::GreeksRule rule = mcamd::greeks_rule(*opt, method);
+            if (int rc = mcamd_finalize_greeks_stats(stats, opt->r, opt->T, rule.theta_defined, out)) return rc;
+            out->method = rule.method;
+            return MCAMD_OK;
+        });
 }
 
 int mcamd_group_simulate_trajectories(mcamd_group *g, const mcamd_option *opt, const mcamd_sim *sim, int layout,
@@ -304,19 +294,14 @@ int mcamd_group_simulate_trajectories(mcamd_group *g, const mcamd_option *opt, c
 {
     if (!g || !opt || !sim || !res) return mcamd_set_error_(MCAMD_ERR_INVALID, "group, opt, sim and res must be non-NULL");
     if (!d_traj && sim->n_paths_local) return mcamd_set_error_(MCAMD_ERR_INVALID, "d_traj (one device pointer per device) is NULL");
-    double stats[8] = {0};
-    float kernel_ms = 0.0f;
-    if (int rc = run_sharded<6>(g, sim, g->d_stats, stats, &kernel_ms, [&](int i, const mcamd_sim &s) {
+    return run_sharded(
+        g, sim, 6, res,
+        [&](int i, const mcamd_sim &s) {
             return mcamd_simulate_trajectories_enqueue(g->ctx[i], opt, &s, layout, d_traj ? d_traj[i] : nullptr,
                                                        d_counts ? d_counts[i] : nullptr, d_payoffs ? d_payoffs[i] : nullptr,
                                                        g->d_stats[i]);
-        }))
-        return rc;
-    if (int rc = mcamd_finalize_stats(stats, opt->r, opt->T, 0, res)) return rc;
-    res->kernel_ms = kernel_ms;
-    res->total_ms = kernel_ms;
-    res->block = 256;
-    return MCAMD_OK;
+        },
+        [&](const double *stats) { return mcamd_finalize_stats(stats, opt->r, opt->T, 0, res); });
 }
 
 int mcamd_group_nmc_inner(mcamd_group *g, const mcamd_option *opt, const mcamd_sim *sim, int layout, int variant,
@@ -326,19 +311,14 @@ int mcamd_group_nmc_inner(mcamd_group *g, const mcamd_option *opt, const mcamd_s
     if (!g || !opt || !sim || !res) return mcamd_set_error_(MCAMD_ERR_INVALID, "group, opt, sim and res must be non-NULL");
     if ((!d_prices || !d_point_prices) && sim->n_paths_local)
         return mcamd_set_error_(MCAMD_ERR_INVALID, "d_prices and d_point_prices (one device pointer per device) must be non-NULL");
-    double stats[8] = {0};
-    float kernel_ms = 0.0f;
-    if (int rc = run_sharded<6>(g, sim, g->d_stats, stats, &kernel_ms, [&](int i, const mcamd_sim &s) {
+    return run_sharded(
+        g, sim, 6, res,
+        [&](int i, const mcamd_sim &s) {
             return mcamd_nmc_inner_enqueue(g->ctx[i], opt, &s, layout, variant, d_prices ? d_prices[i] : nullptr,
                                            d_counts ? d_counts[i] : nullptr, d_point_prices ? d_point_prices[i] : nullptr,
                                            g->d_stats[i]);
-        }))
-        return rc;
-    if (int rc = mcamd_finalize_nmc_stats(stats, res)) return rc;
-    res->kernel_ms = kernel_ms;
-    res->total_ms = kernel_ms;
-    res->block = 256;
-    return MCAMD_OK;
+        },
+        [&](const double *stats) { return mcamd_finalize_nmc_stats(stats, res); });
 }
 
 int mcamd_group_nmc_fused(mcamd_group *g, const mcamd_option *opt, const mcamd_sim *sim, uint64_t outer_seed, int layout,
@@ -347,19 +327,14 @@ int mcamd_group_nmc_fused(mcamd_group *g, const mcamd_option *opt, const mcamd_s
     if (!g || !opt || !sim || !res) return mcamd_set_error_(MCAMD_ERR_INVALID, "group, opt, sim and res must be non-NULL");
     if ((!d_prices || !d_point_prices) && sim->n_paths_local)
         return mcamd_set_error_(MCAMD_ERR_INVALID, "d_prices and d_point_prices (one device pointer per device) must be non-NULL");
-    double stats[8] = {0};
-    float kernel_ms = 0.0f;
-    if (int rc = run_sharded<6>(g, sim, g->d_stats, stats, &kernel_ms, [&](int i, const mcamd_sim &s) {
+    return run_sharded(
+        g, sim, 6, res,
+        [&](int i, const mcamd_sim &s) {
             return mcamd_nmc_fused_enqueue(g->ctx[i], opt, &s, outer_seed, layout, d_prices ? d_prices[i] : nullptr,
                                            d_counts ? d_counts[i] : nullptr, d_point_prices ? d_point_prices[i] : nullptr,
                                            g->d_stats[i]);
-        }))
-        return rc;
-    if (int rc = mcamd_finalize_nmc_stats(stats, res)) return rc;
-    res->kernel_ms = kernel_ms;
-    res->total_ms = kernel_ms;
-    res->block = 256;
-    return MCAMD_OK;
+        },
+        [&](const double *stats) { return mcamd_finalize_nmc_stats(stats, res); });
 }
 
 }  // extern "C"

@@ -25,6 +25,7 @@ struct PathJob {
 };
 
 constexpr uint32_t kMaxGrid = 1u << 20;  // blocks; beyond this the kernels grid-stride
+constexpr uint32_t kBlockThreads = 256;  // threads per workgroup of every kernel (mc_device.hpp kBlock; reported as block)
 
 // number of partial records (one per block) a launch with this many local paths writes
 // compute_units: of the device the job runs on (0: 256).  d_queue: one 64-bit word of device memory, used (and zeroed on
