@@ -434,7 +434,7 @@ int mcamd_bs_greeks_f64(double S0, double K, double T, double r, double v, doubl
  *  1. Training (the backward sweep) on n_train paths of train_seed, global ids 0..n_train-1, stored whole on this
  *     context's device: V_p = d_M h(S_{p,M}); for j = M-1 .. 1, over I_j = {p : h(S_{p,j}) > 0}, solve
  *     (sum phi phi^T) beta_j = sum V_p phi by Cholesky of the Jacobi-scaled matrix; date j is not regressed (no
- *     exercise there) when |I_j| < 4 m or a scaled pivot is <= 1e-12; otherwise V_p = d_j h(S_{p,j}) for the p of
+ *     exercise there) when |I_j| < 4 m or a scaled pivot is <= 1e-10; otherwise V_p = d_j h(S_{p,j}) for the p of
  *     I_j with d_j h(S_{p,j}) > phi(S_{p,j}) . beta_j.  The mean of V is the in-sample estimate (biased high).
  *  2. Pricing on the job's shard (sim->seed, global ids path_offset + i): a path's sample is d_j h(S) at the first
  *     regressed date j < M where h > 0 and d_j h(S) > phi(S) . beta_j, else d_M h(S_M).  The mean is the

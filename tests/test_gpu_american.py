@@ -3,7 +3,10 @@
   * restatement: the engine's stored trajectories (mcamd_simulate_trajectories, same Philox stream and product form)
     run through the numpy restatement of tests/american_restate.py: numpy's own regression reproduces the engine's
     continuation values (1e-9 of their scale), the same dates are regressed, and applying the engine's coefficients
-    gives its in-sample and out-of-sample sums (1e-12 relative) and its early-exercise count exactly;
+    gives its in-sample and out-of-sample sums (1e-12 relative) and its early-exercise count exactly — at the
+    flagship shape, over a matrix of payoff x exercise_every x n_basis x precision x step-count remainders, on jobs
+    larger than the capped grids (the grid-stride loops stride), and on jobs where only some dates are regressed
+    (by the count rule, by the pivot rule);
   * structure: the same paths in both passes give the same estimate; shards add up; two calls are bit-identical;
   * accuracy: the Bermudan put of Longstaff-Schwartz Table 1 against a CRR tree exercising at the same dates, and
     the known limits (American call without dividends, European exercise, deep out of the money, fp32 vs fp64)."""
@@ -45,10 +48,12 @@ def run(ctx, opt, sim, am, coeffs=True):
     return ctx.price_american(opt, sim, am, work, coeffs=coeffs)
 
 
-def stored_rows(ctx, opt, n, n_steps, prec, seed):
-    traj = torch.empty(n * n_steps, dtype=TORCH_T[prec], device="cuda")
-    ctx.simulate_trajectories(opt, capi.make_sim(n, n_steps, prec, seed=seed, flags=capi.FLAG_PRODUCT_FORM), traj)
-    return traj.view(n_steps, n).cpu().numpy().astype(np.float64)
+def stored_rows(ctx, opt, n, n_steps, prec, seed, path_offset=0, n_local=None):
+    n_local = n if n_local is None else n_local
+    traj = torch.empty(n_local * n_steps, dtype=TORCH_T[prec], device="cuda")
+    ctx.simulate_trajectories(opt, capi.make_sim(n, n_steps, prec, seed=seed, flags=capi.FLAG_PRODUCT_FORM,
+                                                 path_offset=path_offset, n_paths_local=n_local), traj)
+    return traj.view(n_steps, n_local).cpu().numpy().astype(np.float64)
 
 
 def unpack(coeffs):
@@ -93,6 +98,135 @@ def test_sweep_and_pricing_restate_exactly(ctx, prec):
     assert res.train_ms > 0 and res.price_ms > 0 and res.total_ms >= res.price_ms and res.block == 256
     # low-biased out of sample, high-biased in sample: the two bracket each other within a few SE
     assert abs(res.price - res.in_sample_price) < 5 * (res.std_err + res.in_sample_std_err)
+
+
+def restate(ctx, opt, sim, am):
+    """The assertions of test_sweep_and_pricing_restate_exactly for any job: the engine's table and sums against the
+    restatement of its own stored paths.  A date is expected regressed when |I_j| >= 4m and the exact smallest scaled
+    pivot of its restated record is above the threshold; a date whose exact pivot lies in ar.BAND (the engine's own
+    pivot is a rounded one) may go either way and is counted.  Coefficients: 1e-9 of the scale of the continuation
+    values, and C 2^-53 / pivot where that is larger (pivots below 2e-6; the bound of the solver's accuracy ladder,
+    tests/test_gpu_american_solver.py).  Returns what the callers assert their preconditions on."""
+    n_steps, prec, k = sim.n_steps, sim.precision, am.exercise_every
+    m, put = am.n_basis or 3, am.payoff == capi.PAYOFF_PUT
+    res, coeffs = run(ctx, opt, sim, am)
+    beta, flags = unpack(coeffs)
+    M, t, disc = ar.dates(opt.T, opt.r, n_steps, k)
+    assert res.n_dates == M == n_steps // k and coeffs.shape == (M, m + 1) and not flags[-1]
+    assert np.isnan(beta[~flags]).all() and np.isfinite(beta[flags]).all()
+    assert res.n_regressed == flags[:-1].sum() and res.n_train == am.n_train and res.n == sim.n_paths_local
+    assert res.grid == min(-(-sim.n_paths_local // 256), 8192) and res.train_grid == min(-(-am.n_train // 256), 8192)
+
+    rows = stored_rows(ctx, opt, am.n_train, n_steps, prec, am.train_seed)
+    pivots, band = {}, []
+    V, per_date = ar.sweep(rows, opt.K, put, k, m, disc, beta, flags, pivots)
+    for j, ok, itm, c_np, c_gpu in per_date:
+        n_itm, piv = pivots[j]
+        if piv is not None and ar.BAND[0] <= piv <= ar.BAND[1]:
+            band.append(j)
+            continue
+        assert ok == flags[j - 1], (j, n_itm, piv, flags[j - 1])
+        if ok:
+            scale = np.abs(c_gpu).max()
+            tol = max(1e-9, ar.C_DEVICE * ar.EPS / piv)
+            assert np.abs(c_np - c_gpu).max() <= tol * scale, (j, piv, np.abs(c_np - c_gpu).max(), scale)
+    assert math.isclose(res.in_sample_sum, V.sum(), rel_tol=1e-12), (res.in_sample_sum, V.sum())
+    assert math.isclose(res.in_sample_sumsq, (V * V).sum(), rel_tol=1e-12)
+
+    rows = stored_rows(ctx, opt, sim.n_paths, n_steps, prec, sim.seed, sim.path_offset, sim.n_paths_local)
+    y, ex_date, t_ex, margin = ar.forward(rows, opt.K, put, k, m, disc, t, beta, flags)
+    assert margin > 1e-12, margin   # no decision within rounding of its boundary: the counts must then agree
+    assert math.isclose(res.sum, y.sum(), rel_tol=1e-12), (res.sum, y.sum())
+    assert math.isclose(res.sumsq, (y * y).sum(), rel_tol=1e-12)
+    assert res.n_early == int((ex_date > 0).sum())
+    assert math.isclose(res.sum_t_exercise, t_ex.sum(), rel_tol=1e-12, abs_tol=0.0 if res.n_early else 1e-300)
+    assert flags[ex_date[ex_date > 0] - 1].all()   # nobody exercises at a date that is not regressed
+    return dict(res=res, flags=flags, pivots=pivots, band=band, ex_date=ex_date, y=y)
+
+
+PUT, CALL = capi.PAYOFF_PUT, capi.PAYOFF_CALL
+assert (capi.F64, capi.F32) == (64, 32)
+# what the matrix covers is checked on every CPU run (tests/test_american_solver_cpu.py)
+SHAPES = [(PUT if put else CALL, k, m, prec, n_steps) for put, k, m, prec, n_steps in ar.SHAPES]
+
+
+@pytest.mark.parametrize("payoff,k,m,prec,n_steps", SHAPES)
+def test_shape_matrix_restates_exactly(ctx, payoff, k, m, prec, n_steps):
+    # in the money either way, so that most dates are regressed and paths do stop early
+    opt = capi.make_option(S0=37.0 if payoff == PUT else 43.0, T=1.0, v=0.3, **LS)
+    am = capi.make_american(payoff=payoff, exercise_every=k, n_basis=m, n_train=60_000, train_seed=1000 + n_steps)
+    out = restate(ctx, opt, capi.make_sim(50_001, n_steps, prec, seed=2000 + n_steps), am)
+    assert out["flags"][:-1].all() and not out["band"]
+    if payoff == PUT:
+        assert out["res"].n_early > 0.2 * out["res"].n
+        assert len(np.unique(out["ex_date"])) > min(n_steps // k, 8) // 2   # exercise spread over the dates
+
+
+@pytest.mark.parametrize("prec,k", [(capi.F64, 1), (capi.F32, 3)])
+def test_grids_that_stride_restate_exactly(ctx, prec, k):
+    # both capped grids (8192 workgroups of 256) loop: a second, ragged trip in the sweep and in the pricing pass
+    n_train, n_local, offset = 2_300_017, 4_200_011, 1_000_003
+    assert min(n_train, n_local) > 8192 * 256 and all(n % 256 and n % 64 for n in (n_train, n_local))
+    opt = capi.make_option(S0=38.0, T=1.0, v=0.25, **LS)
+    am = capi.make_american(exercise_every=k, n_train=n_train, train_seed=91)
+    sim = capi.make_sim(offset + n_local + 12_345, 12, prec, seed=92, path_offset=offset, n_paths_local=n_local)
+    assert capi.american_workspace_bytes(am, sim) < 300e6
+    out = restate(ctx, opt, sim, am)
+    assert out["res"].grid == out["res"].train_grid == 8192
+    assert out["flags"][:-1].all() and out["res"].n_early > 0.1 * n_local
+    # the second trip's paths exercise like the first's
+    early = out["ex_date"] > 0
+    assert abs(early[8192 * 256:].mean() - early[:8192 * 256].mean()) < 0.01
+
+
+@pytest.mark.parametrize("prec", [capi.F64, capi.F32])
+def test_count_rule_leaves_some_dates_out(ctx, prec):
+    """An out-of-the-money put: the first dates have no or few training paths in the money.  Dates with fewer than 4m
+    are not regressed and the pricing pass walks past them; the first regressed ones fit a dozen points."""
+    m = 3
+    opt = capi.make_option(S0=50.0, T=1.0, v=0.2, **LS)
+    am = capi.make_american(exercise_every=1, n_basis=m, n_train=100_000, train_seed=301)
+    out = restate(ctx, opt, capi.make_sim(400_003, 100, prec, seed=302), am)
+    counts = {j: n for j, (n, _) in out["pivots"].items()}
+    few = [j for j, n in counts.items() if 0 < n < 4 * m]
+    small = [j for j, n in counts.items() if 4 * m <= n < 100]
+    assert few and small and any(n == 0 for n in counts.values()), sorted(counts.items())[:20]
+    assert not out["flags"][np.array(few) - 1].any() and out["flags"][np.array(small) - 1].all()
+    assert not out["band"] and 0 < out["res"].n_early and out["res"].immediate_exercise == 0
+    assert out["res"].n_regressed == sum(n >= 4 * m for n in counts.values())
+
+
+# v places the j^3 ladder of pivots with dates 1 and 2 below the band, date 3 in it and date 4 above (numpy paths of
+# the same law give 4.2e-12, 3.3e-11, 1.1e-10, 2.8e-10 at dates 1..4; the test asserts what the engine's paths give)
+PIVOT_JOB = dict(S0=30.0, v=0.0443, n_steps=200, n_train=50_000)
+
+
+def test_pivot_rule_leaves_some_dates_out(ctx):
+    """A deep in-the-money, low-volatility put with 200 dates and four basis functions: every training path is in the
+    money at every date, and at the first dates the prices sit so close together (u = -0.25 +- a few 1e-3, some 50 000 of them) that the
+    scaled pivot is below the threshold.  The smallest pivot grows like j^3 from date to date, by less than the
+    band's factor 4 from the second date on, so no choice of volatility or seed keeps every date out of the band
+    [0.5, 2] x threshold and has two dates below it: dates in the band may go either way (as in the solver's ladder),
+    and at most 2 % of the dates may lie there."""
+    m, n_steps = 4, PIVOT_JOB["n_steps"]
+    opt = capi.make_option(S0=PIVOT_JOB["S0"], T=1.0, v=PIVOT_JOB["v"], **LS)
+    am = capi.make_american(exercise_every=1, n_basis=m, n_train=PIVOT_JOB["n_train"], train_seed=401)
+    out = restate(ctx, opt, capi.make_sim(100_003, n_steps, capi.F64, seed=402), am)
+    piv = out["pivots"]
+    assert all(n == am.n_train for n, _ in piv.values())   # the count rule plays no part
+    below = [j for j, (_, p) in piv.items() if p < ar.BAND[0]]
+    above = [j for j, (_, p) in piv.items() if p > ar.BAND[1]]
+    assert len(below) >= 2 and len(above) >= 20 and len(out["band"]) <= 0.02 * (n_steps - 1), \
+        (len(below), len(above), out["band"])
+    assert not out["flags"][np.array(below) - 1].any() and out["flags"][np.array(above) - 1].all()
+    # some regressed dates are close enough to the threshold for the accuracy bound to be the one that is applied
+    assert sum(piv[j][1] < 2e-6 for j in above) >= 3
+    # a threshold ten times higher would be noticed: it would leave out a date that is regressed here
+    assert sum(piv[j][1] < 0.5e-9 for j in above) >= 1, sorted(piv.items())[:8]
+    res = out["res"]
+    assert res.immediate_exercise == 1 and res.price == 10.0
+    # whole wavefronts stop at the first regressed date, long before the last Philox block
+    assert res.n_early > 0.9 * res.n and np.median(out["ex_date"]) < n_steps // 4
 
 
 @pytest.mark.parametrize("prec,k,payoff", [(capi.F64, 1, capi.PAYOFF_PUT), (capi.F32, 5, capi.PAYOFF_PUT),
