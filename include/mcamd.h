@@ -439,6 +439,7 @@ int mcamd_bs_greeks_f64(double S0, double K, double T, double r, double v, doubl
  *  2. Pricing on the job's shard (sim->seed, global ids path_offset + i): a path's sample is d_j h(S) at the first
  *     regressed date j < M where h > 0 and d_j h(S) > phi(S) . beta_j, else d_M h(S_M).  The mean is the
  *     out-of-sample estimate (biased low: the rule is fitted on other paths); its SE is an honest one.
+ *     mcamd_american_upper_bound turns the same rule into an estimate biased HIGH, whatever its inner sample size.
  * Both passes decide through one device function, so with train_seed == sim->seed and n_train == n_paths they
  * see the same paths and make the same decisions.  Samples are discounted where they are paid: the estimates are
  * plain means (no exp(-rT) factor).  Exercise at t = 0: where h(S0) exceeds an estimate, h(S0) is reported in its
@@ -497,6 +498,78 @@ int mcamd_american_workspace_bytes(const mcamd_american *am, const mcamd_sim *si
  * without a rule (and row M, maturity) hold NaN coefficients and 0. */
 int mcamd_price_american(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_american *am,
                          void *d_work, uint64_t work_bytes, double *h_coeffs, mcamd_american_result *res);
+
+/* ---- The dual (upper) bound of a fitted exercise rule: Andersen and Broadie (2004), after Rogers and Haugh-Kogan ----
+ * Additive to ABI version 5: first carried by the build that ships csrc/american_dual.hip (no struct of an earlier
+ * call changed, so MCAMD_ABI_VERSION stays 5; a caller finds out with dlsym).
+ * mcamd_price_american's out-of-sample estimate is biased LOW.  This call turns the same rule into an estimate that
+ * is biased HIGH, with an honest standard error, so that the two bracket the price.  Notation as above, plus date 0:
+ * t = 0, S_{p,0} = S0, d_0 = 1.  Everything is discounted to t = 0.
+ *   Z_{p,j} = d_j h(S_{p,j}), j = 1..M, on the shard's OUTER paths (sim->seed, global ids path_offset + p; the
+ *       product-form paths of mcamd_simulate_trajectories in the path precision).
+ *   e_{p,j}, the rule says stop: for 1 <= j < M, date j is flagged regressed and d_j h(S) > phi(S) . beta_j with
+ *       h(S) > 0 — the one device function both passes of mcamd_price_american decide with; e_{p,M} = 1.
+ *   Point (p, j), j = 0..M-1: n_inner continuation paths start at S_{p,j}, run the remaining n_steps - s_j steps and
+ *       are each paid d_i h(S) at the first date i > j where the rule says stop.  Q_{p,j} is the mean of the n_inner
+ *       samples (summed in a fixed order: the same bits in every run and under any sharding).  Streams: seed =
+ *       inner_seed, Philox subsequence ((path_offset + p) M + j) n_inner + i for continuation path i, from block 0
+ *       (the convention of mcamd_nmc_inner: a shard draws what the whole job would).
+ *   L_{p,j} = Z_{p,j} where e_{p,j}, else Q_{p,j};  pi_{p,0} = 0, pi_{p,j} = pi_{p,j-1} + L_{p,j} - Q_{p,j-1}.
+ *   Dual sample u_p = max_{1 <= j <= M} (Z_{p,j} - pi_{p,j}); where e_{p,j} holds the term is evaluated as
+ *       Q_{p,j-1} - pi_{p,j-1}, which it equals (so with one date, u_p is Q_{p,0} bit for bit).
+ *   upper = mean of u_p over the shard, std_err = sqrt(s^2 / n).
+ * Every Q is conditionally unbiased, so pi is a martingale and upper is biased HIGH whatever n_inner is: inner noise
+ * only loosens the bound.  sum_q0 / n is a second LOW-biased estimate from the same rule.  The outer paths must be
+ * independent of the paths the rule was fitted on (another seed than train_seed): the rule must not have seen their
+ * future.  This is NOT enforced.  Exercise at t = 0: where h(S0) exceeds upper it is reported in its place with
+ * std_err 0 and immediate_exercise set.  Multi-GPU: every rank bounds its shard; sum, sumsq, n and sum_q0 add.
+ * sim describes the OUTER job (n_paths, path_offset, n_paths_local, seed, n_steps, precision); am->payoff,
+ * exercise_every and n_basis as for mcamd_price_american, n_train and train_seed are ignored.  h_coeffs (host) is the
+ * rule in exactly the layout mcamd_price_american returns: M rows of n_basis + 1 doubles, beta_j then 1 or 0; the
+ * coefficients of a row flagged 0 are not read, and row M's flag is ignored (maturity always pays).
+ * Requirements (MCAMD_ERR_INVALID before any device work): those of mcamd_price_american on opt, sim, payoff,
+ * exercise_every, n_basis and am->reserved, plus n_inner >= 1, dual->reserved == 0, h_coeffs non-NULL, every flag
+ * exactly 0 or 1, finite coefficients in every row flagged 1, (path_offset + n_paths_local) M n_inner < 2^64.  An
+ * empty shard returns zeros and launches nothing. */
+typedef struct mcamd_american_dual {
+    uint32_t n_inner;      /* continuation paths per point, >= 1 */
+    uint32_t reserved;     /* must be 0 */
+    uint64_t inner_seed;   /* should differ from sim->seed */
+} mcamd_american_dual;
+
+typedef struct mcamd_american_dual_result {
+    double upper;              /* sum / n (h(S0) where that is larger) */
+    double std_err;            /* sqrt(s^2 / n) (0 where h(S0) was taken) */
+    double ci_hi;              /* upper + 1.96 std_err */
+    double sum, sumsq;         /* the shard's raw fp64 sums of u_p: what a multi-GPU caller all-reduces */
+    uint64_t n;                /* outer paths (the shard) */
+    double sum_q0;             /* sum of Q_{p,0}: a second lower-bound estimate from the same rule */
+    double work_steps;         /* continuation kernel: 64 x the steps each wavefront ran */
+    double live_steps;         /* continuation kernel: lane-steps of paths that had not stopped yet */
+    uint32_t n_dates;          /* M */
+    int32_t immediate_exercise;/* 1: h(S0) exceeded the estimate and replaced it */
+    float outer_ms;            /* HIP-event times: store of the outer paths */
+    float inner_ms;            /* continuation kernel */
+    float scan_ms;             /* martingale scan */
+    float total_ms;            /* the whole call's device work */
+    uint32_t grid;             /* continuation kernel's launch shape */
+    uint32_t block;
+} mcamd_american_dual_result;
+
+/* Bytes of the caller-owned device workspace of mcamd_american_upper_bound: with A(x) = x rounded up to 256 and
+ * n = sim->n_paths_local,
+ *   256 + A(n_steps n sizeof(path precision))        stored outer trajectories (step-major)
+ *       + A(8 M n)                                     Q (used when d_cont is NULL)
+ *       + A(8 8 (M + 1))                               coefficient table (8 doubles per date, dates 0..M)
+ *       + A(8 max(2 G_store, 2 G_cont, 4 G_scan))      block records
+ * G_store = min(max(ceil(ceil(n / V) / 256), 1), 2^20) with V = 4 (fp32) / 2 (fp64), G_cont = min(max(M n, 1), 8192),
+ * G_scan = min(max(ceil(n / 256), 1), 8192).  Any alignment of d_work is accepted. */
+int mcamd_american_dual_workspace_bytes(const mcamd_american *am, const mcamd_sim *sim,
+                                        const mcamd_american_dual *dual, uint64_t *bytes);
+/* d_cont (nullable, device): receives Q, M x n_paths_local doubles, Q_{p,j} at [j * n_paths_local + p]. */
+int mcamd_american_upper_bound(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                               const mcamd_american *am, const mcamd_american_dual *dual, const double *h_coeffs,
+                               void *d_work, uint64_t work_bytes, double *d_cont, mcamd_american_dual_result *res);
 
 /* Host: discount + mean + standard error + 95% CI from (sum, sumsq, n) — after an all-reduce
  * over shards, or directly.  Fills price/std_err/ci_* (and copies sum/sumsq/n) in *res. */

@@ -15,10 +15,11 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(PKG, "libmcamd.so")
-SOURCES = ["price_f64.hip", "price_f32.hip", "store.hip", "aux.hip", "nmc.hip", "greeks.hip", "american.hip", "capi.cpp",
-           "group.cpp"]
+SOURCES = ["price_f64.hip", "price_f32.hip", "store.hip", "aux.hip", "nmc.hip", "greeks.hip", "american.hip",
+           "american_dual.hip", "capi.cpp", "group.cpp"]
 HEADERS = ["launch.hpp", "mc_device.hpp", "path_consts.hpp", "fast64.hpp", "tables64.inc", "tables64_consts.inc",
-           "price_impl.hpp", "nmc_compact.hpp", "greeks.hpp", "american.hpp", "american_device.hpp"]
+           "price_impl.hpp", "nmc_compact.hpp", "greeks.hpp", "american.hpp", "american_device.hpp",
+           "american_dual.hpp"]
 ARCH = "gfx950"
 
 

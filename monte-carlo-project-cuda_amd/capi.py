@@ -38,6 +38,7 @@ EXPORTS = [
     "mcamd_bs_call_f32", "mcamd_bs_call_f64", "mcamd_price_greeks", "mcamd_price_greeks_enqueue",
     "mcamd_finalize_greeks_stats", "mcamd_group_price_greeks", "mcamd_bs_greeks_f64",
     "mcamd_american_workspace_bytes", "mcamd_price_american",
+    "mcamd_american_dual_workspace_bytes", "mcamd_american_upper_bound",
 ]
 
 
@@ -90,6 +91,23 @@ class AmericanResult(C.Structure):
                 ("n_dates", C.c_uint32), ("n_regressed", C.c_uint32), ("immediate_exercise", C.c_int32),
                 ("train_ms", C.c_float), ("price_ms", C.c_float), ("total_ms", C.c_float), ("grid", C.c_uint32),
                 ("block", C.c_uint32), ("train_grid", C.c_uint32), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class AmericanDual(C.Structure):
+    """mcamd_american_dual: the nested sample of mcamd_american_upper_bound."""
+    _fields_ = [("n_inner", C.c_uint32), ("reserved", C.c_uint32), ("inner_seed", C.c_uint64)]
+
+
+class AmericanDualResult(C.Structure):
+    """mcamd_american_dual_result: the dual (upper) estimate, raw shard sums, lane-step counts, timings."""
+    _fields_ = [("upper", C.c_double), ("std_err", C.c_double), ("ci_hi", C.c_double), ("sum", C.c_double),
+                ("sumsq", C.c_double), ("n", C.c_uint64), ("sum_q0", C.c_double), ("work_steps", C.c_double),
+                ("live_steps", C.c_double), ("n_dates", C.c_uint32), ("immediate_exercise", C.c_int32),
+                ("outer_ms", C.c_float), ("inner_ms", C.c_float), ("scan_ms", C.c_float), ("total_ms", C.c_float),
+                ("grid", C.c_uint32), ("block", C.c_uint32)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -179,6 +197,11 @@ def load() -> C.CDLL:
     L.mcamd_american_workspace_bytes.argtypes = [C.POINTER(American), C.POINTER(Sim), C.POINTER(u64)]
     L.mcamd_price_american.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(American), vp, u64,
                                        C.POINTER(f64), C.POINTER(AmericanResult)]
+    L.mcamd_american_dual_workspace_bytes.argtypes = [C.POINTER(American), C.POINTER(Sim), C.POINTER(AmericanDual),
+                                                      C.POINTER(u64)]
+    L.mcamd_american_upper_bound.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(American),
+                                             C.POINTER(AmericanDual), C.POINTER(f64), vp, u64, vp,
+                                             C.POINTER(AmericanDualResult)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("mcamd_abi_version",):
@@ -211,6 +234,17 @@ def american_workspace_bytes(am: American, sim: Sim) -> int:
     """bytes of the device workspace mcamd_price_american needs for this rule, training set and step count"""
     b = C.c_uint64(0)
     _check(load().mcamd_american_workspace_bytes(C.byref(am), C.byref(sim), C.byref(b)))
+    return b.value
+
+
+def make_american_dual(n_inner=256, inner_seed=8765) -> AmericanDual:
+    return AmericanDual(n_inner, 0, inner_seed)
+
+
+def american_dual_workspace_bytes(am: American, sim: Sim, dual: AmericanDual) -> int:
+    """bytes of the device workspace mcamd_american_upper_bound needs for this outer shard and these dates"""
+    b = C.c_uint64(0)
+    _check(load().mcamd_american_dual_workspace_bytes(C.byref(am), C.byref(sim), C.byref(dual), C.byref(b)))
     return b.value
 
 
@@ -357,6 +391,28 @@ class Context:
             return res
         import numpy as np
         return res, np.ctypeslib.as_array(arr).reshape(M, nb + 1).copy()
+
+    def american_upper_bound(self, opt: Option, sim: Sim, am: American, dual: AmericanDual, coeffs, work,
+                             cont=None) -> AmericanDualResult:
+        """Andersen-Broadie dual (upper) bound of the exercise rule `coeffs` (mcamd_american_upper_bound): the
+        (M, n_basis + 1) array price_american returns, or one of the caller's own.  work: a device tensor of at least
+        american_dual_workspace_bytes(am, sim, dual) bytes; cont: optional device tensor of M * n_paths_local doubles
+        that receives the continuation values Q[j, p]."""
+        import numpy as np
+        res = AmericanDualResult()
+        table = None
+        if coeffs is not None:
+            table = np.ascontiguousarray(coeffs, dtype=np.float64)
+            nb = am.n_basis or 3
+            M = sim.n_steps // am.exercise_every if am.exercise_every else 0
+            if table.size != M * (nb + 1):
+                raise ValueError(f"coeffs holds {table.size} doubles; {M} dates x ({nb} + 1) expected")
+        nbytes = work.numel() * work.element_size() if work is not None else 0
+        _check(self._L.mcamd_american_upper_bound(
+            self._h, C.byref(opt), C.byref(sim), C.byref(am), C.byref(dual),
+            None if table is None else table.ctypes.data_as(C.POINTER(C.c_double)), _ptr(work), nbytes, _ptr(cont),
+            C.byref(res)))
+        return res
 
     def enqueued_kernel_ms(self, n_last: int):
         arr = (C.c_float * n_last)()

@@ -5,6 +5,7 @@
 #include "launch.hpp"
 #include "greeks.hpp"
 #include "american.hpp"
+#include "american_dual.hpp"
 
 #include "mcamd.h"
 
@@ -21,6 +22,8 @@ static_assert(sizeof(mcamd_option) == 88 && sizeof(mcamd_sim) == 48 && sizeof(mc
               "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
 static_assert(sizeof(mcamd_greeks) == 224, "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
 static_assert(sizeof(mcamd_american) == 32 && sizeof(mcamd_american_result) == 152,
+              "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
+static_assert(sizeof(mcamd_american_dual) == 16 && sizeof(mcamd_american_dual_result) == 104,
               "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
 
 namespace {
@@ -61,7 +64,7 @@ struct mcamd_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
     double *d_partials = nullptr;  // one record (2 or 5 doubles) per block
     uint64_t partial_capacity = 0; // in doubles
     double *d_out = nullptr;       // 8 doubles
@@ -557,6 +560,29 @@ int check_american_shape(const mcamd_sim *sim, const mcamd_american *am, uint32_
     return MCAMD_OK;
 }
 
+// The refusals of the dual-bound calls that depend on the request's shape alone (shared with the workspace-size query).
+// am->n_train and am->train_seed play no part: the rule comes in as a table.
+int check_dual_shape(const mcamd_sim *sim, const mcamd_american *am, const mcamd_american_dual *dual, uint32_t *M,
+                     int *n_basis)
+{
+    mcamd_american shape = *am;
+    shape.n_train = 1;
+    if (int rc = check_american_shape(sim, &shape, M, n_basis)) return rc;
+    if (dual->n_inner == 0) return fail(MCAMD_ERR_INVALID, "n_inner must be >= 1");
+    if (dual->reserved != 0) return fail(MCAMD_ERR_INVALID, "dual->reserved must be 0, got %u", dual->reserved);
+    if (sim->path_offset + sim->n_paths_local < sim->path_offset)
+        return fail(MCAMD_ERR_INVALID, "path_offset + n_paths_local overflows 64 bits");
+    // continuation path i of point (g, j) draws Philox subsequence (g M + j) n_inner + i: the shard's largest one
+    // must fit 64 bits
+    const long double top = static_cast<long double>(sim->path_offset + sim->n_paths_local) * *M * dual->n_inner;
+    if (top >= 18446744073709551615.0L)
+        return fail(MCAMD_ERR_INVALID, "(path_offset + n_paths_local) * dates * n_inner overflows the 64-bit Philox "
+                                       "subsequence");
+    if (static_cast<long double>(sim->n_paths_local) * sim->n_steps * 8.0L >= 9.2e18L)
+        return fail(MCAMD_ERR_INVALID, "n_paths_local * n_steps overflows the workspace's 64-bit size");
+    return MCAMD_OK;
+}
+
 // h(S0) replaces an estimate it exceeds (exercise at t = 0); returns whether it did
 bool floor_at_immediate(double h0, double *price, double *std_err)
 {
@@ -633,6 +659,7 @@ int mcamd_ctx_create(int device, void *hip_stream, mcamd_ctx **out)
     hipError_t e = hipEventCreate(&ctx->ev0);
     if (e == hipSuccess) e = hipEventCreate(&ctx->ev1);
     if (e == hipSuccess) e = hipEventCreate(&ctx->ev2);
+    if (e == hipSuccess) e = hipEventCreate(&ctx->ev3);
     for (uint32_t i = 0; i < mcamd_ctx::kRing && e == hipSuccess; ++i) {
         e = hipEventCreate(&ctx->ring0[i]);
         if (e == hipSuccess) e = hipEventCreate(&ctx->ring1[i]);
@@ -667,6 +694,7 @@ int mcamd_ctx_destroy(mcamd_ctx *ctx)
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     if (ctx->ev2) (void)hipEventDestroy(ctx->ev2);
+    if (ctx->ev3) (void)hipEventDestroy(ctx->ev3);
     for (uint32_t i = 0; i < mcamd_ctx::kRing; ++i) {
         if (ctx->ring0[i]) (void)hipEventDestroy(ctx->ring0[i]);
         if (ctx->ring1[i]) (void)hipEventDestroy(ctx->ring1[i]);
@@ -1168,6 +1196,138 @@ int mcamd_price_american(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_si
     res->grid = n_local ? price_grid : 0;
     res->block = mcamd::kBlockThreads;
     res->train_grid = sweep_grid;
+    return MCAMD_OK;
+}
+
+int mcamd_american_dual_workspace_bytes(const mcamd_american *am, const mcamd_sim *sim,
+                                        const mcamd_american_dual *dual, uint64_t *bytes)
+{
+    if (!am || !sim || !dual || !bytes) return fail(MCAMD_ERR_INVALID, "am, sim, dual and bytes must be non-NULL");
+    *bytes = 0;
+    uint32_t M = 0;
+    int n_basis = 0;
+    if (int rc = check_dual_shape(sim, am, dual, &M, &n_basis)) return rc;
+    *bytes = mcamd::american_dual_layout(sim->n_paths_local, sim->n_steps, M, sim->precision).total;
+    return MCAMD_OK;
+}
+
+int mcamd_american_upper_bound(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_american *am,
+                               const mcamd_american_dual *dual, const double *h_coeffs, void *d_work,
+                               uint64_t work_bytes, double *d_cont, mcamd_american_dual_result *res)
+{
+    // every refusal that depends on the request alone comes before the context is looked at
+    if (!opt || !sim || !am || !dual || !res)
+        return fail(MCAMD_ERR_INVALID, "opt, sim, am, dual and res must be non-NULL");
+    std::memset(res, 0, sizeof *res);
+    uint32_t M = 0;
+    int n_basis = 0;
+    if (int rc = check_dual_shape(sim, am, dual, &M, &n_basis)) return rc;
+    if (opt->use_window) return fail(MCAMD_ERR_INVALID, "American options take no bullet window: use_window must be 0");
+    if (opt->Tk != 0 || opt->Sk != 0.0)
+        return fail(MCAMD_ERR_INVALID, "American options start at t = 0: Tk and Sk must be 0 (Tk = %d, Sk = %g)", opt->Tk,
+                    opt->Sk);
+    if (opt->dt != 0.0) return fail(MCAMD_ERR_INVALID, "American options step dt = T / n_steps: opt->dt must be 0");
+    if (!(opt->v > 0.0) || !(opt->S0 > 0.0) || !(opt->K > 0.0))
+        return fail(MCAMD_ERR_INVALID, "American options need v > 0, S0 > 0 and K > 0 (v = %g, S0 = %g, K = %g)", opt->v,
+                    opt->S0, opt->K);
+    if (sim->flags != 0 && sim->flags != MCAMD_FLAG_LOG_SPACE && sim->flags != MCAMD_FLAG_PRODUCT_FORM)
+        return fail(MCAMD_ERR_INVALID, "American options take flags 0, MCAMD_FLAG_LOG_SPACE or MCAMD_FLAG_PRODUCT_FORM, "
+                                       "got %d", sim->flags);
+    if (!h_coeffs) return fail(MCAMD_ERR_INVALID, "h_coeffs is NULL: the rule is what mcamd_price_american wrote");
+    for (uint32_t j = 1; j <= M; ++j) {
+        const double *row = h_coeffs + static_cast<size_t>(j - 1) * (n_basis + 1);
+        if (row[n_basis] != 0.0 && row[n_basis] != 1.0)
+            return fail(MCAMD_ERR_INVALID, "h_coeffs: the regressed flag of date %u must be 0 or 1, got %g", j, row[n_basis]);
+        if (row[n_basis] == 1.0)
+            for (int q = 0; q < n_basis; ++q)
+                if (!std::isfinite(row[q]))
+                    return fail(MCAMD_ERR_INVALID, "h_coeffs: date %u is flagged regressed but coefficient %d is not "
+                                                   "finite", j, q);
+    }
+    if (!d_work) return fail(MCAMD_ERR_INVALID, "d_work is NULL");
+    const uint64_t n_local = sim->n_paths_local;
+    const mcamd::AmDualLayout lay = mcamd::american_dual_layout(n_local, sim->n_steps, M, sim->precision);
+    if (work_bytes < lay.total)
+        return fail(MCAMD_ERR_INVALID, "work_bytes = %llu is below the %llu bytes the workspace needs "
+                                       "(mcamd_american_dual_workspace_bytes)",
+                    static_cast<unsigned long long>(work_bytes), static_cast<unsigned long long>(lay.total));
+    if (int rc = check_common(ctx, opt, sim)) return rc;
+    res->n_dates = M;
+    res->block = mcamd::kBlockThreads;
+    if (n_local == 0) return MCAMD_OK;
+
+    HIP_TRY(hipSetDevice(ctx->device));
+    char *base = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(d_work) + 255) & ~static_cast<uintptr_t>(255));
+    void *traj = base + lay.traj;
+    double *Q = d_cont ? d_cont : reinterpret_cast<double *>(base + lay.cont);
+    double *table = reinterpret_cast<double *>(base + lay.table);
+    double *w_partials = reinterpret_cast<double *>(base + lay.partials);
+
+    mcamd::AmDualJob job;
+    job.path = make_job(opt, sim);
+    job.path.window = false;
+    job.path.logspace = false;   // the product form: St at every date, the same bits as the stored rows
+    job.path.vr = 0;
+    job.put = am->payoff == MCAMD_PAYOFF_PUT ? 1 : 0;
+    job.n_basis = n_basis;
+    job.k = am->exercise_every;
+    job.M = M;
+    job.n_inner = dual->n_inner;
+    job.inner_seed = dual->inner_seed;
+
+    // the device table in the layout (and with the host expressions) of the backward sweep: beta, flag, d_j, t_j
+    const double dt = opt->T / static_cast<double>(sim->n_steps);
+    std::vector<double> host(static_cast<size_t>(mcamd::kAmRow) * (M + 1), 0.0);
+    for (uint32_t j = 0; j <= M; ++j) {
+        double *row = host.data() + static_cast<size_t>(j) * mcamd::kAmRow;
+        const double *src = j ? h_coeffs + static_cast<size_t>(j - 1) * (n_basis + 1) : nullptr;
+        const bool regressed = j >= 1 && j < M && src[n_basis] == 1.0;
+        for (int q = 0; q < mcamd::kAmMaxBasis; ++q) row[q] = (regressed && q < n_basis) ? src[q] : std::nan("");
+        row[4] = regressed ? 1.0 : 0.0;
+        row[6] = static_cast<double>(static_cast<uint64_t>(j) * am->exercise_every) * dt;
+        row[5] = std::exp(-opt->r * row[6]);
+        row[7] = 0.0;
+    }
+
+    const uint32_t store_grid = mcamd::store_grid(n_local, sim->precision);
+    const uint32_t cont_grid = mcamd::american_cont_grid(static_cast<uint64_t>(M) * n_local);
+    const uint32_t scan_grid = mcamd::american_scan_grid(n_local);
+    constexpr int kRec = mcamd::kAmDualRecord + mcamd::kAmContRecord;
+    static_assert(kRec <= mcamd_ctx::kRecord, "the pinned record holds both kernels' records");
+    arm_record(ctx->h_rec, kRec);
+    HIP_TRY(hipMemcpyAsync(table, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+    HIP_TRY(mcamd::launch_store(job.path, MCAMD_STEP_MAJOR, traj, nullptr, nullptr, w_partials, store_grid, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+    HIP_TRY(mcamd::launch_american_cont(job, traj, table, Q, w_partials, cont_grid, ctx->h_rec_dev + mcamd::kAmDualRecord,
+                                        ctx->d_ticket, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ev2, ctx->stream));
+    HIP_TRY(mcamd::launch_american_dual_scan(job, traj, table, Q, w_partials, scan_grid, ctx->h_rec_dev, ctx->d_ticket,
+                                             ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ev3, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipEventElapsedTime(&res->outer_ms, ctx->ev0, ctx->ev1));
+    HIP_TRY(hipEventElapsedTime(&res->inner_ms, ctx->ev1, ctx->ev2));
+    HIP_TRY(hipEventElapsedTime(&res->scan_ms, ctx->ev2, ctx->ev3));
+    HIP_TRY(hipEventElapsedTime(&res->total_ms, ctx->ev0, ctx->ev3));
+
+    double rec[kRec];
+    std::memcpy(rec, ctx->h_rec, sizeof rec);
+    if (record_unwritten(rec, kRec))
+        return fail(MCAMD_ERR_HIP, "the dual-bound kernels left no result (a last workgroup did not finish its sum)");
+    const Estimate up = estimate(rec[0], rec[1], n_local, 1.0);   // samples are discounted where paid: D = 1
+    res->upper = up.value;
+    res->std_err = up.std_err;
+    res->sum = rec[0];
+    res->sumsq = rec[1];
+    res->sum_q0 = rec[2];
+    res->n = n_local;
+    res->work_steps = 64.0 * rec[mcamd::kAmDualRecord];   // wave-steps x 64 lanes
+    res->live_steps = rec[mcamd::kAmDualRecord + 1];
+    const double h0 = std::fmax(job.put ? opt->K - opt->S0 : opt->S0 - opt->K, 0.0);
+    res->immediate_exercise = floor_at_immediate(h0, &res->upper, &res->std_err) ? 1 : 0;
+    res->ci_hi = res->upper + kZ95 * res->std_err;
+    res->grid = cont_grid;
     return MCAMD_OK;
 }
 
