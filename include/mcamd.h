@@ -571,6 +571,66 @@ int mcamd_american_upper_bound(mcamd_ctx *ctx, const mcamd_option *opt, const mc
                                const mcamd_american *am, const mcamd_american_dual *dual, const double *h_coeffs,
                                void *d_work, uint64_t work_bytes, double *d_cont, mcamd_american_dual_result *res);
 
+/* ---- Single-barrier options: down / up, knock-out / knock-in, call / put, discrete or continuous monitoring ----
+ * Additive to ABI version 5: first carried by the build that ships csrc/barrier.hip (no struct of an earlier call
+ * changed, so MCAMD_ABI_VERSION stays 5; a caller finds out with dlsym).  opt->B is the barrier level.
+ * Notation of mcamd_price_paths: dt = T / n_steps; x_i = (r - v^2/2) dt + v sqrt(dt) z_i with z_i the path's normals
+ * (Philox subsequence = the GLOBAL path id; the exponents are the ones mcamd_price_paths steps with); X_0 = 0,
+ * X_i = X_{i-1} + x_i; S_T = S0 e^{X_n}; b = ln(B / S0).
+ *   Hit test at step end i = 1..n:  down  b > X_i  (the comparison the bullet count makes, strict: the two agree path
+ *       for path);  up  X_i > b.
+ *   Distance:  d_i = X_i - b (down) or b - X_i (up);  d_0 = |b|.
+ *   Survival weight w:
+ *       MCAMD_MONITOR_DISCRETE    w = prod_i 1{no hit at i}
+ *       MCAMD_MONITOR_CONTINUOUS  w = prod_i 1{no hit at i} f_i,  f_i = 1 - exp(-q_i),  q_i = 2 d_{i-1} d_i / (v^2 dt),
+ *           and f_i is DEFINED as exactly 1 where q_i >= Q, Q = 38 (fp64) / 18 (fp32) in natural-log units: there
+ *           e^{-q} is below 2^-54 / 2^-25 and 1 - e^{-q} rounds to 1 anyway.  The rule is part of the definition, so a
+ *           restatement skips the same factors the kernel skips.
+ *   h(S) = (S - K)+ for MCAMD_PAYOFF_CALL, (K - S)+ for MCAMD_PAYOFF_PUT.
+ *   Sample:  knock-out  y = w h(S_T);  knock-in  y = (1 - w) h(S_T).  No rebate.
+ *   price = exp(-rT) mean(y), std_err as in mcamd_finalize.
+ * f_i is the probability that the Brownian bridge between two step ends stays on the live side, so the continuous w is
+ * the conditional survival probability given the skeleton: nothing extra is drawn, and the sample is unbiased for the
+ * continuously monitored barrier at EVERY n_steps (n_steps = 1 included).  The discrete sample prices the barrier
+ * monitored at the n step ends.  Discrete DOWN_OUT / DOWN_IN calls are the bullet window's P1 = P2 = 0 and
+ * P1 = 1, P2 = n_steps, sample for sample.
+ * d_samples (nullable, device): n_paths_local values of the path precision; [local path] receives y.
+ * res: sum / sumsq / n / price / std_err / ci_*, kernel_ms / total_ms / grid / block; work_steps = 64 x the steps each
+ * wavefront ran (a knock-out wavefront leaves the step loop once every lane is knocked; a knock-in runs to maturity:
+ * it needs S_T), live_steps = the lane-steps of paths not yet knocked; the other fields are 0.
+ * The enqueue form leaves {sum, sumsq, 0, 0, 0, n} in d_stats (device, >= 6 doubles): mcamd_finalize_stats and one
+ * all-reduce of 6 doubles serve it unchanged, and mcamd_enqueued_kernel_ms covers it.
+ * Requirements (MCAMD_ERR_INVALID before any device work and before the context is looked at): opt, sim, barrier, res
+ * non-NULL; kind, payoff, monitoring in range; reserved == 0; B > 0; S0 strictly on the live side (down: S0 > B, up:
+ * S0 < B); use_window, P1, P2, Ik, Sk, Tk and opt->dt all 0; v > 0; sim->flags 0 or MCAMD_FLAG_LOG_SPACE; and what
+ * mcamd_price_paths refuses on sim.  An empty shard returns zeros and launches nothing.
+ * There is no mcamd_group_* form and no shim name: the reference has no such product.  Multi-GPU: every rank prices
+ * its shard (a path's sample depends on its global id alone); the 6-double records add.  New. */
+#define MCAMD_BARRIER_DOWN_OUT 0
+#define MCAMD_BARRIER_DOWN_IN 1
+#define MCAMD_BARRIER_UP_OUT 2
+#define MCAMD_BARRIER_UP_IN 3
+
+#define MCAMD_MONITOR_DISCRETE 0
+#define MCAMD_MONITOR_CONTINUOUS 1
+
+typedef struct mcamd_barrier {
+    int32_t kind;        /* MCAMD_BARRIER_* */
+    int32_t payoff;      /* MCAMD_PAYOFF_* */
+    int32_t monitoring;  /* MCAMD_MONITOR_* */
+    int32_t reserved;    /* must be 0 */
+} mcamd_barrier;
+
+int mcamd_price_barrier(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_barrier *barrier,
+                        void *d_samples, mcamd_result *res);
+int mcamd_price_barrier_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                                const mcamd_barrier *barrier, void *d_samples, double *d_stats);
+/* Host closed form of the CONTINUOUSLY monitored barrier, all eight kind x payoff cases, rebate 0, no dividends
+ * (Reiner and Rubinstein 1991; Merton 1973).  MCAMD_ERR_INVALID for an S0 on the knocked side (or on the barrier),
+ * non-positive S0, K, B, T or v, or a bad enum. */
+int mcamd_barrier_price_f64(double S0, double K, double B, double T, double r, double v, int kind, int payoff,
+                            double *price);
+
 /* Host: discount + mean + standard error + 95% CI from (sum, sumsq, n) — after an all-reduce
  * over shards, or directly.  Fills price/std_err/ci_* (and copies sum/sumsq/n) in *res. */
 int mcamd_finalize(double sum, double sumsq, uint64_t n, double r, double T, mcamd_result *res);

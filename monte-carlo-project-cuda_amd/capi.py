@@ -24,6 +24,8 @@ GREEK_PRICE, GREEK_DELTA, GREEK_GAMMA, GREEK_VEGA, GREEK_RHO, GREEK_THETA = rang
 GREEK_NAMES = ("price", "delta", "gamma", "vega", "rho", "theta")
 GREEKS_STATS = 16   # doubles of a Greeks statistics record: six (sum, sumsq) pairs, n, zeros
 PAYOFF_CALL, PAYOFF_PUT = 0, 1
+BARRIER_DOWN_OUT, BARRIER_DOWN_IN, BARRIER_UP_OUT, BARRIER_UP_IN = 0, 1, 2, 3
+MONITOR_DISCRETE, MONITOR_CONTINUOUS = 0, 1
 
 # every symbol include/mcamd.h declares
 EXPORTS = [
@@ -39,6 +41,7 @@ EXPORTS = [
     "mcamd_finalize_greeks_stats", "mcamd_group_price_greeks", "mcamd_bs_greeks_f64",
     "mcamd_american_workspace_bytes", "mcamd_price_american",
     "mcamd_american_dual_workspace_bytes", "mcamd_american_upper_bound",
+    "mcamd_price_barrier", "mcamd_price_barrier_enqueue", "mcamd_barrier_price_f64",
 ]
 
 
@@ -111,6 +114,11 @@ class AmericanDualResult(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class Barrier(C.Structure):
+    """mcamd_barrier: which single barrier mcamd_price_barrier prices, and how it is monitored."""
+    _fields_ = [("kind", C.c_int32), ("payoff", C.c_int32), ("monitoring", C.c_int32), ("reserved", C.c_int32)]
 
 
 class DeviceInfo(C.Structure):
@@ -202,6 +210,9 @@ def load() -> C.CDLL:
     L.mcamd_american_upper_bound.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(American),
                                              C.POINTER(AmericanDual), C.POINTER(f64), vp, u64, vp,
                                              C.POINTER(AmericanDualResult)]
+    L.mcamd_price_barrier.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Barrier), vp, C.POINTER(Result)]
+    L.mcamd_price_barrier_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Barrier), vp, vp]
+    L.mcamd_barrier_price_f64.argtypes = [f64, f64, f64, f64, f64, f64, i32, i32, C.POINTER(f64)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("mcamd_abi_version",):
@@ -246,6 +257,17 @@ def american_dual_workspace_bytes(am: American, sim: Sim, dual: AmericanDual) ->
     b = C.c_uint64(0)
     _check(load().mcamd_american_dual_workspace_bytes(C.byref(am), C.byref(sim), C.byref(dual), C.byref(b)))
     return b.value
+
+
+def make_barrier(kind=BARRIER_DOWN_OUT, payoff=PAYOFF_CALL, monitoring=MONITOR_CONTINUOUS) -> Barrier:
+    return Barrier(kind, payoff, monitoring, 0)
+
+
+def barrier_price_f64(S0, K, B, T, r, sigma, kind=BARRIER_DOWN_OUT, payoff=PAYOFF_CALL) -> float:
+    """closed form of the continuously monitored single barrier (Reiner-Rubinstein), rebate 0"""
+    p = C.c_double(0)
+    _check(load().mcamd_barrier_price_f64(S0, K, B, T, r, sigma, kind, payoff, C.byref(p)))
+    return p.value
 
 
 def _ptr(t):
@@ -375,6 +397,19 @@ class Context:
     def price_greeks_enqueue(self, opt: Option, sim: Sim, stats, method: int = GREEKS_AUTO) -> None:
         """Asynchronous: leaves the 16-double Greeks record in the device tensor `stats` (finalize_greeks_stats)."""
         _check(self._L.mcamd_price_greeks_enqueue(self._h, C.byref(opt), C.byref(sim), method, _ptr(stats)))
+
+    def price_barrier(self, opt: Option, sim: Sim, barrier: Barrier, samples=None) -> Result:
+        """Single-barrier option (mcamd_price_barrier); opt.B is the level.  samples: optional device tensor of
+        n_paths_local values of the path precision that receives each path's undiscounted sample."""
+        res = Result()
+        _check(self._L.mcamd_price_barrier(self._h, C.byref(opt), C.byref(sim), C.byref(barrier), _ptr(samples),
+                                           C.byref(res)))
+        return res
+
+    def price_barrier_enqueue(self, opt: Option, sim: Sim, barrier: Barrier, stats, samples=None) -> None:
+        """Asynchronous: leaves {sum, sumsq, 0, 0, 0, n} in the device tensor `stats` (>= 6 doubles; finalize_stats)."""
+        _check(self._L.mcamd_price_barrier_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(barrier),
+                                                   _ptr(samples), _ptr(stats)))
 
     def price_american(self, opt: Option, sim: Sim, am: American, work, coeffs: bool = False):
         """Least-squares Monte Carlo price of an American / Bermudan put or call (mcamd_price_american).  work: a device

@@ -1,0 +1,161 @@
+// barrier.hip — single-barrier options for gfx950 (both path precisions): down / up, knock-out / knock-in, call / put,
+// monitored at the step ends (discrete) or all the time (continuous, by the Brownian-bridge survival weight).
+//
+// Definitions (include/mcamd.h, mcamd_price_barrier): X_i = ln(S_i / S0) after step i, b = ln(B / S0); a path is hit at
+// step end i when b > X_i (down) or X_i > b (up); d_i = X_i - b (down) or b - X_i (up), d_0 = |b|.  The survival weight
+// w is the product over the steps of 1{no hit at i} and — continuous monitoring — of f_i = 1 - exp(-q_i) with
+// q_i = 2 d_{i-1} d_i / (v^2 dt), where f_i is DEFINED as 1 for q_i >= Q (Q = 38 in fp64, 18 in fp32: there
+// exp(-q) < 2^-54 / 2^-25 and 1 - exp(-q) rounds to 1 anyway).  The sample is w h(S_T) (knock-out) or (1 - w) h(S_T)
+// (knock-in), formed once per path in fp64.
+//
+// The loop is the log-space window form of simulate_sample: per Philox block one Exponents<T>::fill, per step
+// acc += x, one subtract for d, the strict compare.  The bridge factor costs one multiply-multiply-compare per step
+// and an exponential only where a live lane has q < Q; that skip is decided per wavefront (one ballot), and paths
+// spend most of their steps far from the barrier.  A knock-out wavefront leaves the step loop at the first block end
+// where every lane is knocked; a knock-in runs to maturity, because it needs S_T.
+#include "barrier.hpp"
+#include "path_consts.hpp"
+
+namespace mcamd {
+
+template <typename T>
+struct BarrierArgs {
+    StepConsts<T> c;   // logB = b in exponent units; K, S_start, drift, vol, n_sim
+    T kq;              // fp64: 2 u^2 / (v^2 dt), u = ln 2 / 65536: q = kq d d' in natural-log units (f64::mul_exp's)
+                       // fp32: 2 ln 2 / (v^2 dt): q = kq d d' in log2 units (v_exp_f32's)
+    T q_cut;           // Q in the units of q
+    int put;
+    uint64_t seed;
+    uint64_t path_offset;
+    uint64_t n_local;
+    T *samples;        // nullable
+    GridFinish fin;
+};
+
+// 1 - exp(-q), q >= 0 in the units BarrierArgs::kq leaves it in
+__device__ __forceinline__ float bridge_factor(float q, const MathCtx<float> &)
+{
+    return 1.0f - __builtin_amdgcn_exp2f(-q);
+}
+__device__ __forceinline__ double bridge_factor(double q, const MathCtx<double> &m)
+{
+    return 1.0 - f64::mul_exp(1.0, -q, m.t.exp_hi_tab, m.t.exp_lo_tab);
+}
+
+template <typename T, bool UP, bool CONT, bool OUT>
+__global__ __launch_bounds__(kBlock) void barrier_kernel(BarrierArgs<T> a, double *__restrict__ partials)
+{
+    constexpr int NB = Exponents<T>::kPerBlock;
+    const MathCtx<T> m = MathCtx<T>::init();
+    const PhiloxKeys key = PhiloxKeys::make(a.seed);
+    const StepConsts<T> c = resident(a.c);
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
+    const uint32_t n_full = c.n_sim / NB;
+    const uint32_t rem = c.n_sim - n_full * NB;
+    const T d0 = UP ? c.logB : -c.logB;   // |b|: the spot is strictly on the live side (checked on the host)
+    double acc4[kBarrierRecord] = {0.0, 0.0, 0.0, 0.0};
+    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < a.n_local; i += stride) {
+        const uint64_t subsequence = a.path_offset + i;
+        T acc = T(0);        // X so far, in exponent units
+        T d_prev = d0;
+        T w = T(1);          // the bridge factors so far (CONT); the hits are in `alive`
+        bool alive = true;
+        uint32_t live = 0;   // steps this path entered not yet knocked
+        uint32_t steps_run = c.n_sim;
+        bool rem_live = true;
+        Exponents<T> ex;
+        auto step = [&](T x) {
+            live += alive ? 1u : 0u;
+            acc += x;
+            const T d = UP ? c.logB - acc : acc - c.logB;
+            const bool hit = UP ? (acc > c.logB) : (c.logB > acc);
+            alive = alive && !hit;
+            if (CONT) {
+                const T q = a.kq * d_prev * d;
+                const bool close_by = alive && (q < a.q_cut);
+                if (__builtin_amdgcn_ballot_w64(close_by) != 0) {   // wave-uniform: most steps take no exponential at all
+                    const T f = bridge_factor(q, m);
+                    w = close_by ? w * f : w;
+                }
+                d_prev = d;
+            }
+        };
+        for (uint32_t k = 0; k < n_full; ++k) {
+            ex.fill(m, c, key, subsequence, k);
+#pragma unroll
+            for (int j = 0; j < NB; ++j) step(ex.x[j]);
+            if (OUT && __builtin_amdgcn_ballot_w64(alive) == 0) {
+                steps_run = (k + 1) * NB;
+                rem_live = false;
+                break;
+            }
+        }
+        if (rem && rem_live) {
+            ex.fill(m, c, key, subsequence, n_full);
+#pragma unroll
+            for (int j = 0; j < NB - 1; ++j)
+                if (static_cast<uint32_t>(j) < rem) step(ex.x[j]);
+        }
+        const T St = exp_of_logreturn(c.S_start, acc, m);
+        T h = a.put ? c.K - St : St - c.K;
+        h = h > T(0) ? h : T(0);
+        const double wd = alive ? static_cast<double>(w) : 0.0;
+        // a knocked path of a knock-out pays 0 whatever its (possibly unfinished) price is
+        const double y = OUT ? (alive ? wd * static_cast<double>(h) : 0.0) : (1.0 - wd) * static_cast<double>(h);
+        if (a.samples) a.samples[i] = static_cast<T>(y);
+        acc4[0] += y;
+        acc4[1] = __builtin_fma(y, y, acc4[1]);
+        // a wavefront's active lanes are a prefix (path ids grow with the lane): lane 0 counts the wavefront's steps
+        if ((threadIdx.x & (kWave - 1)) == 0) acc4[2] += static_cast<double>(steps_run);
+        acc4[3] += static_cast<double>(live);
+    }
+    if (a.fin.n_value >= 0.0) acc4[2] = acc4[3] = 0.0;   // the 6-double statistics layout has no slot for the counters
+    block_sumN<kBlock, kBarrierRecord>(acc4);
+    grid_finish<kBlock, kBarrierRecord>(acc4, partials, a.fin);
+}
+
+uint32_t barrier_grid(const BarrierJob &job)
+{
+    const uint64_t blocks = clamp_grid((job.path.n_local + kBlock - 1) / kBlock);
+    return static_cast<uint32_t>(blocks < kFoldMaxRecords ? blocks : kFoldMaxRecords);
+}
+
+template <typename T, bool UP, bool CONT>
+static void launch_barrier_k(const BarrierJob &j, const BarrierArgs<T> &a, double *d_partials, uint32_t grid,
+                             hipStream_t stream)
+{
+    const dim3 g(grid), b(kBlock);
+    if (j.out) hipLaunchKernelGGL((barrier_kernel<T, UP, CONT, true>), g, b, 0, stream, a, d_partials);
+    else hipLaunchKernelGGL((barrier_kernel<T, UP, CONT, false>), g, b, 0, stream, a, d_partials);
+}
+
+template <typename T>
+static hipError_t launch_barrier_t(const BarrierJob &j, double *d_partials, uint32_t grid, const FinishSpec &fs,
+                                   hipStream_t stream)
+{
+    // natural log per exponent unit (make_consts' units), and per unit of q
+    const double u = sizeof(T) == 4 ? 0.69314718055994531 : 1.0 / f64::kExpScale;
+    const double q_unit = sizeof(T) == 4 ? 0.69314718055994531 : 1.0;
+    const double q_cut = sizeof(T) == 4 ? 18.0 : 38.0;
+    const BarrierArgs<T> a{make_consts<T>(j.path), static_cast<T>(j.kq * u * u / q_unit), static_cast<T>(q_cut / q_unit),
+                           j.put ? 1 : 0, j.path.seed, j.path.path_offset, j.path.n_local,
+                           static_cast<T *>(j.d_samples), GridFinish{fs.out, fs.ticket, fs.n_value}};
+    if (j.up) {
+        if (j.continuous) launch_barrier_k<T, true, true>(j, a, d_partials, grid, stream);
+        else launch_barrier_k<T, true, false>(j, a, d_partials, grid, stream);
+    } else {
+        if (j.continuous) launch_barrier_k<T, false, true>(j, a, d_partials, grid, stream);
+        else launch_barrier_k<T, false, false>(j, a, d_partials, grid, stream);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_barrier(const BarrierJob &job, double *d_partials, uint32_t grid, const FinishSpec &finish,
+                          hipStream_t stream)
+{
+    if (!finish.out || !finish.ticket || grid == 0 || grid > kFoldMaxRecords) return hipErrorInvalidValue;
+    return job.path.precision == 32 ? launch_barrier_t<float>(job, d_partials, grid, finish, stream)
+                                    : launch_barrier_t<double>(job, d_partials, grid, finish, stream);
+}
+
+}  // namespace mcamd

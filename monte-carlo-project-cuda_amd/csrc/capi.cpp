@@ -6,6 +6,7 @@
 #include "greeks.hpp"
 #include "american.hpp"
 #include "american_dual.hpp"
+#include "barrier.hpp"
 
 #include "mcamd.h"
 
@@ -25,6 +26,7 @@ static_assert(sizeof(mcamd_american) == 32 && sizeof(mcamd_american_result) == 1
               "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
 static_assert(sizeof(mcamd_american_dual) == 16 && sizeof(mcamd_american_dual_result) == 104,
               "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
+static_assert(sizeof(mcamd_barrier) == 16, "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
 
 namespace {
 
@@ -96,10 +98,9 @@ int ensure_partials(mcamd_ctx *ctx, uint32_t records, int record_doubles = 2)
     return MCAMD_OK;
 }
 
-int check_common(const mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim)
+// what every path call refuses on the request alone (opt and sim non-NULL)
+int check_request(const mcamd_option *opt, const mcamd_sim *sim)
 {
-    if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
-    if (!opt || !sim) return fail(MCAMD_ERR_INVALID, "opt and sim must be non-NULL");
     if (sim->precision != MCAMD_F32 && sim->precision != MCAMD_F64)
         return fail(MCAMD_ERR_INVALID, "precision must be MCAMD_F32 (32) or MCAMD_F64 (64), got %d", sim->precision);
     if (sim->n_steps == 0) return fail(MCAMD_ERR_INVALID, "n_steps must be >= 1");
@@ -129,6 +130,13 @@ int check_common(const mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim 
                         "(per step < 700, per path < 20000)", per_step, sim->n_steps);
     }
     return MCAMD_OK;
+}
+
+int check_common(const mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim)
+{
+    if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
+    if (!opt || !sim) return fail(MCAMD_ERR_INVALID, "opt and sim must be non-NULL");
+    return check_request(opt, sim);
 }
 
 // check_common plus the refusals of the calls that run plain paths (no variance reduction) and, but for
@@ -581,6 +589,64 @@ int check_dual_shape(const mcamd_sim *sim, const mcamd_american *am, const mcamd
     if (static_cast<long double>(sim->n_paths_local) * sim->n_steps * 8.0L >= 9.2e18L)
         return fail(MCAMD_ERR_INVALID, "n_paths_local * n_steps overflows the workspace's 64-bit size");
     return MCAMD_OK;
+}
+
+// The refusals of the barrier calls that depend on the request's enums and levels alone (shared with the closed form).
+int check_barrier_kind(double S0, double B, int kind, int payoff)
+{
+    if (kind < MCAMD_BARRIER_DOWN_OUT || kind > MCAMD_BARRIER_UP_IN)
+        return fail(MCAMD_ERR_INVALID, "barrier kind must be MCAMD_BARRIER_DOWN_OUT (0) .. MCAMD_BARRIER_UP_IN (3), got %d",
+                    kind);
+    if (payoff != MCAMD_PAYOFF_CALL && payoff != MCAMD_PAYOFF_PUT)
+        return fail(MCAMD_ERR_INVALID, "payoff must be MCAMD_PAYOFF_CALL (0) or MCAMD_PAYOFF_PUT (1), got %d", payoff);
+    if (!(B > 0.0) || !std::isfinite(B)) return fail(MCAMD_ERR_INVALID, "the barrier level B must be positive, got %g", B);
+    const bool up = kind == MCAMD_BARRIER_UP_OUT || kind == MCAMD_BARRIER_UP_IN;
+    if (!(S0 > 0.0) || !std::isfinite(S0) || !(up ? S0 < B : S0 > B))
+        return fail(MCAMD_ERR_INVALID, "the spot must lie strictly on the live side of the barrier: %s (S0 = %g, B = %g)",
+                    up ? "an up-barrier needs 0 < S0 < B" : "a down-barrier needs S0 > B", S0, B);
+    return MCAMD_OK;
+}
+
+// The barrier calls.  The kernel always finishes its own sum (barrier_grid caps the grid); every refusal that depends
+// on the request alone comes before the context is looked at.
+template <typename Drive>
+int prepare_barrier(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_barrier *bar,
+                    void *d_samples, Drive drive)
+{
+    if (!opt || !sim || !bar) return fail(MCAMD_ERR_INVALID, "opt, sim and barrier must be non-NULL");
+    if (bar->monitoring != MCAMD_MONITOR_DISCRETE && bar->monitoring != MCAMD_MONITOR_CONTINUOUS)
+        return fail(MCAMD_ERR_INVALID, "monitoring must be MCAMD_MONITOR_DISCRETE (0) or MCAMD_MONITOR_CONTINUOUS (1), "
+                                       "got %d", bar->monitoring);
+    if (bar->reserved != 0) return fail(MCAMD_ERR_INVALID, "barrier->reserved must be 0, got %d", bar->reserved);
+    if (int rc = check_barrier_kind(opt->S0, opt->B, bar->kind, bar->payoff)) return rc;
+    if (opt->use_window || opt->P1 != 0 || opt->P2 != 0 || opt->Ik != 0)
+        return fail(MCAMD_ERR_INVALID, "barrier options take no bullet window: use_window, P1, P2 and Ik must be 0");
+    if (opt->Tk != 0 || opt->Sk != 0.0)
+        return fail(MCAMD_ERR_INVALID, "barrier options start at t = 0: Tk and Sk must be 0 (Tk = %d, Sk = %g)", opt->Tk,
+                    opt->Sk);
+    if (opt->dt != 0.0) return fail(MCAMD_ERR_INVALID, "barrier options step dt = T / n_steps: opt->dt must be 0");
+    if (!(opt->v > 0.0)) return fail(MCAMD_ERR_INVALID, "barrier options need v > 0 (v = %g)", opt->v);
+    if (sim->flags & ~MCAMD_FLAG_LOG_SPACE)
+        return fail(MCAMD_ERR_INVALID, "barrier options take flags 0 or MCAMD_FLAG_LOG_SPACE only, got %d", sim->flags);
+    if (int rc = check_request(opt, sim)) return rc;
+    if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
+    if (sim->n_paths_local == 0) return drive(empty_call());
+    mcamd::BarrierJob job;
+    job.path = make_job(opt, sim);
+    job.path.window = false;
+    job.path.logspace = true;
+    job.path.vr = 0;
+    job.up = bar->kind == MCAMD_BARRIER_UP_OUT || bar->kind == MCAMD_BARRIER_UP_IN;
+    job.out = bar->kind == MCAMD_BARRIER_DOWN_OUT || bar->kind == MCAMD_BARRIER_UP_OUT;
+    job.continuous = bar->monitoring == MCAMD_MONITOR_CONTINUOUS;
+    job.put = bar->payoff == MCAMD_PAYOFF_PUT;
+    job.kq = 2.0 / (opt->v * opt->v * (opt->T / static_cast<double>(sim->n_steps)));
+    job.d_samples = d_samples;
+    const uint32_t grid = mcamd::barrier_grid(job);
+    return drive(DeviceCall{job.path.n_local, grid, mcamd::kBarrierRecord, 6, Finish::kFolded,
+                            [&](const mcamd::FinishSpec &fs) {
+                                return mcamd::launch_barrier(job, ctx->d_partials, grid, fs, ctx->stream);
+                            }});
 }
 
 // h(S0) replaces an estimate it exceeds (exercise at t = 0); returns whether it did
@@ -1328,6 +1394,60 @@ int mcamd_american_upper_bound(mcamd_ctx *ctx, const mcamd_option *opt, const mc
     res->immediate_exercise = floor_at_immediate(h0, &res->upper, &res->std_err) ? 1 : 0;
     res->ci_hi = res->upper + kZ95 * res->std_err;
     res->grid = cont_grid;
+    return MCAMD_OK;
+}
+
+int mcamd_price_barrier(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_barrier *barrier,
+                        void *d_samples, mcamd_result *res)
+{
+    if (!res) return fail(MCAMD_ERR_INVALID, "opt, sim, barrier and res must be non-NULL");
+    zero_result(res);
+    return prepare_barrier(ctx, opt, sim, barrier, d_samples, [&](const auto &call) {
+        return run_sync(ctx, call, res, [&](const double *rec) {
+            finalize_into(rec[0], rec[1], sim->n_paths_local, opt->r, opt->T, res);
+            res->work_steps = 64.0 * rec[2];   // wave-steps x 64 lanes
+            res->live_steps = rec[3];
+        });
+    });
+}
+
+int mcamd_price_barrier_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                                const mcamd_barrier *barrier, void *d_samples, double *d_stats)
+{
+    return prepare_barrier(ctx, opt, sim, barrier, d_samples,
+                           [&](const auto &call) { return run_enqueue(ctx, call, d_stats); });
+}
+
+// Reiner and Rubinstein (1991) / Merton (1973): the continuously monitored single barrier without rebate or dividends,
+// from the four terms A..D of the standard presentation (phi = 1 call / -1 put, eta = 1 down / -1 up).
+int mcamd_barrier_price_f64(double S0, double K, double B, double T, double r, double v, int kind, int payoff,
+                            double *price)
+{
+    if (!price) return fail(MCAMD_ERR_INVALID, "price is NULL");
+    *price = 0.0;
+    if (!(K > 0.0) || !(T > 0.0) || !(v > 0.0) || !std::isfinite(K) || !std::isfinite(T) || !std::isfinite(r) ||
+        !std::isfinite(v))
+        return fail(MCAMD_ERR_INVALID, "the barrier closed form needs finite K, T, v > 0 and a finite r");
+    if (int rc = check_barrier_kind(S0, B, kind, payoff)) return rc;
+    const bool up = kind == MCAMD_BARRIER_UP_OUT || kind == MCAMD_BARRIER_UP_IN;
+    const bool out = kind == MCAMD_BARRIER_DOWN_OUT || kind == MCAMD_BARRIER_UP_OUT;
+    const double phi = payoff == MCAMD_PAYOFF_PUT ? -1.0 : 1.0, eta = up ? -1.0 : 1.0;
+    const double s = v * std::sqrt(T), mu = (r - 0.5 * v * v) / (v * v), Kd = K * std::exp(-r * T);
+    const auto N = [](double x) { return 0.5 * std::erfc(-x / std::sqrt(2.0)); };
+    const double x1 = std::log(S0 / K) / s + (1.0 + mu) * s, x2 = std::log(S0 / B) / s + (1.0 + mu) * s;
+    const double y1 = std::log(B * B / (S0 * K)) / s + (1.0 + mu) * s, y2 = std::log(B / S0) / s + (1.0 + mu) * s;
+    const double p0 = std::pow(B / S0, 2.0 * mu), p1 = p0 * (B / S0) * (B / S0);
+    const double tA = phi * S0 * N(phi * x1) - phi * Kd * N(phi * x1 - phi * s);
+    const double tB = phi * S0 * N(phi * x2) - phi * Kd * N(phi * x2 - phi * s);
+    const double tC = phi * S0 * p1 * N(eta * y1) - phi * Kd * p0 * N(eta * y1 - eta * s);
+    const double tD = phi * S0 * p1 * N(eta * y2) - phi * Kd * p0 * N(eta * y2 - eta * s);
+    // the knock-in; the knock-out is the vanilla price (term A) less it.  Which combination depends on whether the
+    // strike lies on the live side of the barrier for this payoff.
+    const bool call = phi > 0.0;
+    double in;
+    if (call != up) in = (call ? K >= B : K <= B) ? tC : tA - tB + tD;          // down call, up put
+    else in = (call ? K >= B : K <= B) ? tA : tB - tC + tD;                     // up call, down put
+    *price = out ? tA - in : in;
     return MCAMD_OK;
 }
 
