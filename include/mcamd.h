@@ -631,6 +631,69 @@ int mcamd_price_barrier_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const m
 int mcamd_barrier_price_f64(double S0, double K, double B, double T, double r, double v, int kind, int payoff,
                             double *price);
 
+/* ---- Lookback options: floating or fixed strike, call or put, discrete or continuous monitoring ----
+ * Additive to ABI version 5: first carried by the build that ships csrc/lookback.hip (no struct of an earlier call
+ * changed, so MCAMD_ABI_VERSION stays 5; a caller finds out with dlsym).
+ * Notation of mcamd_price_barrier: dt = T / n_steps; x_i = (r - v^2/2) dt + v sqrt(dt) z_i with z_i the path's normals
+ * (Philox subsequence = the GLOBAL path id, blocks 0, 1, ...; the exponents are the ones mcamd_price_paths steps
+ * with); X_0 = 0, X_i = X_{i-1} + x_i; S_T = S0 e^{X_n}.  The option is newly issued: E_0 = 0, so the extremum
+ * includes S0.  A call on floating strike and a put on fixed strike need the minimum of X, the other two the maximum;
+ * a path tracks only the extremum it needs, S_E = S0 e^{E_n} (S_max or S_min).
+ *   MCAMD_MONITOR_DISCRETE    E_i = max(E_{i-1}, X_i)  (min for the minimum)
+ *   MCAMD_MONITOR_CONTINUOUS  for the maximum:  E^ = max(E_{i-1}, X_i),  q_i = 2 (E^ - X_{i-1})(E^ - X_i) / (v^2 dt);
+ *       where q_i < Q:  m_i = (X_{i-1} + X_i + sqrt(x_i^2 - 2 v^2 dt ln U_i)) / 2  and  E_i = max(E^, m_i);
+ *       elsewhere E_i = E^.  For the minimum:  E^ = min(E_{i-1}, X_i),  q_i = 2 (X_{i-1} - E^)(X_i - E^) / (v^2 dt),
+ *       the root enters m_i with a minus sign and E_i = min(E^, m_i).
+ *       Q = 22.25 (fp32) / 36.75 (fp64) in natural-log units, just above 32 ln 2 / 53 ln 2 = -ln of the smallest
+ *       uniform the generator produces.  m_i lies beyond E^ exactly when U_i < e^{-q_i}, so above Q no U that can
+ *       be drawn moves the extremum and the rule changes no sample; it is part of the definition all the same, so
+ *       that the kernel may skip the logarithm and the root there and a restatement skips the same steps.
+ *   The uniforms come from the same key and subsequence as the normals, at Philox block 2^63 + k with k the normal
+ *   block of the step (n_steps is 32-bit: the normals never get there).  fp32: word j of that block serves step
+ *   4k + j, U = fma(word, 2^-32, 2^-32) in float (rocRAND's float uniform; it may round to 1, which is harmless).
+ *   fp64: words (x, y) serve step 2k and (z, w) step 2k + 1, U = ((x ^ (y << 21)) + 1) 2^-53 (rocRAND's double
+ *   uniform).  A shard therefore draws exactly what the whole job would.
+ *   Sample, formed once per path in fp64 from the path-precision S_T and S_E (both through the same exponential, so a
+ *   floating-strike path whose extremum is its last point pays exactly 0):
+ *       MCAMD_LOOKBACK_FLOATING  call  y = S_T - S_min     put  y = S_max - S_T      (opt->K is ignored)
+ *       MCAMD_LOOKBACK_FIXED     call  y = (S_max - K)+    put  y = (K - S_min)+
+ *   price = exp(-rT) mean(y), std_err as in mcamd_finalize.
+ * m_i is a draw from the law of the maximum of the Brownian bridge between the two step ends (its distribution
+ * function inverted at U_i), and the bridges of different steps are independent given the step ends, so the continuous
+ * sample is unbiased for the continuously monitored lookback at EVERY n_steps (n_steps = 1 included).  The discrete
+ * sample prices the lookback monitored at t = 0 and the n step ends.
+ * d_samples (nullable, device): n_paths_local values of the path precision; [local path] receives y.
+ * res: sum / sumsq / n / price / std_err / ci_*, kernel_ms / total_ms / grid / block; work_steps = 64 x the steps each
+ * wavefront ran (there is no early exit), live_steps = the lane-steps that formed m_i (continuous) or 0 (discrete);
+ * the other fields are 0.
+ * The enqueue form leaves {sum, sumsq, 0, 0, 0, n} in d_stats (device, >= 6 doubles): mcamd_finalize_stats and one
+ * all-reduce of 6 doubles serve it unchanged, and mcamd_enqueued_kernel_ms covers it.
+ * Requirements (MCAMD_ERR_INVALID before any device work and before the context is looked at): opt, sim, lookback, res
+ * non-NULL; strike, payoff, monitoring in range; reserved == 0; fixed strike: K finite and positive; use_window, P1,
+ * P2, Ik, Sk, Tk and opt->dt all 0; v > 0; sim->flags 0 or MCAMD_FLAG_LOG_SPACE; and what mcamd_price_paths refuses on
+ * sim.  opt->B is ignored.  An empty shard returns zeros and launches nothing.
+ * There is no mcamd_group_* form and no shim name: the reference has no such product.  Multi-GPU: every rank prices
+ * its shard (a path's sample depends on its global id alone); the 6-double records add.  New. */
+#define MCAMD_LOOKBACK_FLOATING 0
+#define MCAMD_LOOKBACK_FIXED 1
+
+typedef struct mcamd_lookback {
+    int32_t strike;      /* MCAMD_LOOKBACK_* */
+    int32_t payoff;      /* MCAMD_PAYOFF_* */
+    int32_t monitoring;  /* MCAMD_MONITOR_* */
+    int32_t reserved;    /* must be 0 */
+} mcamd_lookback;
+
+int mcamd_price_lookback(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_lookback *lookback,
+                         void *d_samples, mcamd_result *res);
+int mcamd_price_lookback_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                                 const mcamd_lookback *lookback, void *d_samples, double *d_stats);
+/* Host closed form of the CONTINUOUSLY monitored, newly issued lookback without dividends (floating strike: Goldman,
+ * Sosin and Gatto 1979; fixed strike: Conze and Viswanathan 1991).  K is ignored for MCAMD_LOOKBACK_FLOATING.
+ * MCAMD_ERR_INVALID for a bad enum, a non-positive or non-finite S0, T or v (and K for a fixed strike), a non-finite r,
+ * and r == 0: the formulas carry v^2 / (2r), and their limit at r = 0 is left out on purpose. */
+int mcamd_lookback_price_f64(double S0, double K, double T, double r, double v, int strike, int payoff, double *price);
+
 /* Host: discount + mean + standard error + 95% CI from (sum, sumsq, n) — after an all-reduce
  * over shards, or directly.  Fills price/std_err/ci_* (and copies sum/sumsq/n) in *res. */
 int mcamd_finalize(double sum, double sumsq, uint64_t n, double r, double T, mcamd_result *res);

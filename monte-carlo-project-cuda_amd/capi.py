@@ -26,6 +26,7 @@ GREEKS_STATS = 16   # doubles of a Greeks statistics record: six (sum, sumsq) pa
 PAYOFF_CALL, PAYOFF_PUT = 0, 1
 BARRIER_DOWN_OUT, BARRIER_DOWN_IN, BARRIER_UP_OUT, BARRIER_UP_IN = 0, 1, 2, 3
 MONITOR_DISCRETE, MONITOR_CONTINUOUS = 0, 1
+LOOKBACK_FLOATING, LOOKBACK_FIXED = 0, 1
 
 # every symbol include/mcamd.h declares
 EXPORTS = [
@@ -42,6 +43,7 @@ EXPORTS = [
     "mcamd_american_workspace_bytes", "mcamd_price_american",
     "mcamd_american_dual_workspace_bytes", "mcamd_american_upper_bound",
     "mcamd_price_barrier", "mcamd_price_barrier_enqueue", "mcamd_barrier_price_f64",
+    "mcamd_price_lookback", "mcamd_price_lookback_enqueue", "mcamd_lookback_price_f64",
 ]
 
 
@@ -119,6 +121,11 @@ class AmericanDualResult(C.Structure):
 class Barrier(C.Structure):
     """mcamd_barrier: which single barrier mcamd_price_barrier prices, and how it is monitored."""
     _fields_ = [("kind", C.c_int32), ("payoff", C.c_int32), ("monitoring", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Lookback(C.Structure):
+    """mcamd_lookback: which lookback mcamd_price_lookback prices, and how the extremum is monitored."""
+    _fields_ = [("strike", C.c_int32), ("payoff", C.c_int32), ("monitoring", C.c_int32), ("reserved", C.c_int32)]
 
 
 class DeviceInfo(C.Structure):
@@ -213,6 +220,9 @@ def load() -> C.CDLL:
     L.mcamd_price_barrier.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Barrier), vp, C.POINTER(Result)]
     L.mcamd_price_barrier_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Barrier), vp, vp]
     L.mcamd_barrier_price_f64.argtypes = [f64, f64, f64, f64, f64, f64, i32, i32, C.POINTER(f64)]
+    L.mcamd_price_lookback.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Lookback), vp, C.POINTER(Result)]
+    L.mcamd_price_lookback_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Lookback), vp, vp]
+    L.mcamd_lookback_price_f64.argtypes = [f64, f64, f64, f64, f64, i32, i32, C.POINTER(f64)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("mcamd_abi_version",):
@@ -267,6 +277,17 @@ def barrier_price_f64(S0, K, B, T, r, sigma, kind=BARRIER_DOWN_OUT, payoff=PAYOF
     """closed form of the continuously monitored single barrier (Reiner-Rubinstein), rebate 0"""
     p = C.c_double(0)
     _check(load().mcamd_barrier_price_f64(S0, K, B, T, r, sigma, kind, payoff, C.byref(p)))
+    return p.value
+
+
+def make_lookback(strike=LOOKBACK_FLOATING, payoff=PAYOFF_CALL, monitoring=MONITOR_CONTINUOUS) -> Lookback:
+    return Lookback(strike, payoff, monitoring, 0)
+
+
+def lookback_price_f64(S0, K, T, r, sigma, strike=LOOKBACK_FLOATING, payoff=PAYOFF_CALL) -> float:
+    """closed form of the continuously monitored, newly issued lookback (Goldman-Sosin-Gatto, Conze-Viswanathan)"""
+    p = C.c_double(0)
+    _check(load().mcamd_lookback_price_f64(S0, K, T, r, sigma, strike, payoff, C.byref(p)))
     return p.value
 
 
@@ -410,6 +431,19 @@ class Context:
         """Asynchronous: leaves {sum, sumsq, 0, 0, 0, n} in the device tensor `stats` (>= 6 doubles; finalize_stats)."""
         _check(self._L.mcamd_price_barrier_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(barrier),
                                                    _ptr(samples), _ptr(stats)))
+
+    def price_lookback(self, opt: Option, sim: Sim, lookback: Lookback, samples=None) -> Result:
+        """Lookback option (mcamd_price_lookback).  samples: optional device tensor of n_paths_local values of the path
+        precision that receives each path's undiscounted sample."""
+        res = Result()
+        _check(self._L.mcamd_price_lookback(self._h, C.byref(opt), C.byref(sim), C.byref(lookback), _ptr(samples),
+                                            C.byref(res)))
+        return res
+
+    def price_lookback_enqueue(self, opt: Option, sim: Sim, lookback: Lookback, stats, samples=None) -> None:
+        """Asynchronous: leaves {sum, sumsq, 0, 0, 0, n} in the device tensor `stats` (>= 6 doubles; finalize_stats)."""
+        _check(self._L.mcamd_price_lookback_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(lookback),
+                                                    _ptr(samples), _ptr(stats)))
 
     def price_american(self, opt: Option, sim: Sim, am: American, work, coeffs: bool = False):
         """Least-squares Monte Carlo price of an American / Bermudan put or call (mcamd_price_american).  work: a device

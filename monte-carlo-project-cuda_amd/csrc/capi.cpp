@@ -7,6 +7,7 @@
 #include "american.hpp"
 #include "american_dual.hpp"
 #include "barrier.hpp"
+#include "lookback.hpp"
 
 #include "mcamd.h"
 
@@ -27,6 +28,7 @@ static_assert(sizeof(mcamd_american) == 32 && sizeof(mcamd_american_result) == 1
 static_assert(sizeof(mcamd_american_dual) == 16 && sizeof(mcamd_american_dual_result) == 104,
               "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
 static_assert(sizeof(mcamd_barrier) == 16, "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
+static_assert(sizeof(mcamd_lookback) == 16, "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
 
 namespace {
 
@@ -646,6 +648,66 @@ int prepare_barrier(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *si
     return drive(DeviceCall{job.path.n_local, grid, mcamd::kBarrierRecord, 6, Finish::kFolded,
                             [&](const mcamd::FinishSpec &fs) {
                                 return mcamd::launch_barrier(job, ctx->d_partials, grid, fs, ctx->stream);
+                            }});
+}
+
+// The refusals of the lookback calls that depend on the product alone (shared with the closed form).
+int check_lookback_kind(double K, int strike, int payoff)
+{
+    if (strike != MCAMD_LOOKBACK_FLOATING && strike != MCAMD_LOOKBACK_FIXED)
+        return fail(MCAMD_ERR_INVALID, "strike must be MCAMD_LOOKBACK_FLOATING (0) or MCAMD_LOOKBACK_FIXED (1), got %d",
+                    strike);
+    if (payoff != MCAMD_PAYOFF_CALL && payoff != MCAMD_PAYOFF_PUT)
+        return fail(MCAMD_ERR_INVALID, "payoff must be MCAMD_PAYOFF_CALL (0) or MCAMD_PAYOFF_PUT (1), got %d", payoff);
+    if (strike == MCAMD_LOOKBACK_FIXED && (!(K > 0.0) || !std::isfinite(K)))
+        return fail(MCAMD_ERR_INVALID, "a fixed-strike lookback needs a finite K > 0, got %g", K);
+    return MCAMD_OK;
+}
+
+// The lookback calls.  The kernel always finishes its own sum (lookback_grid caps the grid); every refusal that depends
+// on the request alone comes before the context is looked at.
+template <typename Drive>
+int prepare_lookback(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_lookback *lb,
+                     void *d_samples, Drive drive)
+{
+    if (!opt || !sim || !lb) return fail(MCAMD_ERR_INVALID, "opt, sim and lookback must be non-NULL");
+    if (lb->monitoring != MCAMD_MONITOR_DISCRETE && lb->monitoring != MCAMD_MONITOR_CONTINUOUS)
+        return fail(MCAMD_ERR_INVALID, "monitoring must be MCAMD_MONITOR_DISCRETE (0) or MCAMD_MONITOR_CONTINUOUS (1), "
+                                       "got %d", lb->monitoring);
+    if (lb->reserved != 0) return fail(MCAMD_ERR_INVALID, "lookback->reserved must be 0, got %d", lb->reserved);
+    if (int rc = check_lookback_kind(opt->K, lb->strike, lb->payoff)) return rc;
+    if (opt->use_window || opt->P1 != 0 || opt->P2 != 0 || opt->Ik != 0)
+        return fail(MCAMD_ERR_INVALID, "lookback options take no bullet window: use_window, P1, P2 and Ik must be 0");
+    if (opt->Tk != 0 || opt->Sk != 0.0)
+        return fail(MCAMD_ERR_INVALID, "lookback options start at t = 0: Tk and Sk must be 0 (Tk = %d, Sk = %g)", opt->Tk,
+                    opt->Sk);
+    if (opt->dt != 0.0) return fail(MCAMD_ERR_INVALID, "lookback options step dt = T / n_steps: opt->dt must be 0");
+    if (!(opt->v > 0.0)) return fail(MCAMD_ERR_INVALID, "lookback options need v > 0 (v = %g)", opt->v);
+    if (sim->flags & ~MCAMD_FLAG_LOG_SPACE)
+        return fail(MCAMD_ERR_INVALID, "lookback options take flags 0 or MCAMD_FLAG_LOG_SPACE only, got %d", sim->flags);
+    const bool fixed = lb->strike == MCAMD_LOOKBACK_FIXED;
+    mcamd_option seen = *opt;   // a floating strike ignores K, and every lookback ignores B
+    if (!fixed) seen.K = 0.0;
+    seen.B = 0.0;
+    if (int rc = check_request(&seen, sim)) return rc;
+    if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
+    if (sim->n_paths_local == 0) return drive(empty_call());
+    mcamd::LookbackJob job;
+    job.path = make_job(&seen, sim);
+    job.path.window = false;
+    job.path.logspace = true;
+    job.path.vr = 0;
+    job.fixed = fixed;
+    job.put = lb->payoff == MCAMD_PAYOFF_PUT;
+    job.maximum = fixed ? !job.put : job.put;   // fixed call and floating put look at the maximum
+    job.continuous = lb->monitoring == MCAMD_MONITOR_CONTINUOUS;
+    job.K = seen.K;
+    job.v2dt = opt->v * opt->v * (opt->T / static_cast<double>(sim->n_steps));
+    job.d_samples = d_samples;
+    const uint32_t grid = mcamd::lookback_grid(job);
+    return drive(DeviceCall{job.path.n_local, grid, mcamd::kLookbackRecord, 6, Finish::kFolded,
+                            [&](const mcamd::FinishSpec &fs) {
+                                return mcamd::launch_lookback(job, ctx->d_partials, grid, fs, ctx->stream);
                             }});
 }
 
@@ -1448,6 +1510,65 @@ int mcamd_barrier_price_f64(double S0, double K, double B, double T, double r, d
     if (call != up) in = (call ? K >= B : K <= B) ? tC : tA - tB + tD;          // down call, up put
     else in = (call ? K >= B : K <= B) ? tA : tB - tC + tD;                     // up call, down put
     *price = out ? tA - in : in;
+    return MCAMD_OK;
+}
+
+int mcamd_price_lookback(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_lookback *lookback,
+                         void *d_samples, mcamd_result *res)
+{
+    if (!res) return fail(MCAMD_ERR_INVALID, "opt, sim, lookback and res must be non-NULL");
+    zero_result(res);
+    return prepare_lookback(ctx, opt, sim, lookback, d_samples, [&](const auto &call) {
+        return run_sync(ctx, call, res, [&](const double *rec) {
+            finalize_into(rec[0], rec[1], sim->n_paths_local, opt->r, opt->T, res);
+            res->work_steps = 64.0 * rec[2];   // wave-steps x 64 lanes
+            res->live_steps = rec[3];
+        });
+    });
+}
+
+int mcamd_price_lookback_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                                 const mcamd_lookback *lookback, void *d_samples, double *d_stats)
+{
+    return prepare_lookback(ctx, opt, sim, lookback, d_samples,
+                            [&](const auto &call) { return run_enqueue(ctx, call, d_stats); });
+}
+
+// Goldman, Sosin and Gatto (1979) for the floating strike, Conze and Viswanathan (1991) for the fixed one: the
+// continuously monitored, newly issued lookback without dividends.  A fixed strike on the side of the spot the extremum
+// has already passed (call: K <= S0, put: K >= S0) is the opposite floating lookback plus a forward.
+int mcamd_lookback_price_f64(double S0, double K, double T, double r, double v, int strike, int payoff, double *price)
+{
+    if (!price) return fail(MCAMD_ERR_INVALID, "price is NULL");
+    *price = 0.0;
+    if (!(S0 > 0.0) || !(T > 0.0) || !(v > 0.0) || !std::isfinite(S0) || !std::isfinite(T) || !std::isfinite(r) ||
+        !std::isfinite(v))
+        return fail(MCAMD_ERR_INVALID, "the lookback closed form needs finite S0, T, v > 0 and a finite r");
+    if (r == 0.0)
+        return fail(MCAMD_ERR_INVALID, "the lookback closed form carries v^2 / (2r): r == 0 is not covered");
+    if (int rc = check_lookback_kind(K, strike, payoff)) return rc;
+    const bool put = payoff == MCAMD_PAYOFF_PUT;
+    const double sq = std::sqrt(T), s = v * sq, D = std::exp(-r * T), G = std::exp(r * T);
+    const double lam = v * v / (2.0 * r), shift = 2.0 * r * sq / v;
+    const auto N = [](double x) { return 0.5 * std::erfc(-x / std::sqrt(2.0)); };
+    const double a = (r + 0.5 * v * v) * T / s;
+    const auto floating = [&](bool is_put) {
+        if (is_put) return S0 * D * N(-a + s) - S0 * N(-a) + S0 * D * lam * (-N(a - shift) + G * N(a));
+        return S0 * N(a) - S0 * D * N(a - s) + S0 * D * lam * (N(-a + shift) - G * N(-a));
+    };
+    if (strike == MCAMD_LOOKBACK_FLOATING) {
+        *price = floating(put);
+        return MCAMD_OK;
+    }
+    const double d = (std::log(S0 / K) + (r + 0.5 * v * v) * T) / s;
+    const double pw = std::pow(S0 / K, -2.0 * r / (v * v));
+    if (!put) {
+        if (K > S0) *price = S0 * N(d) - K * D * N(d - s) + S0 * D * lam * (-pw * N(d - shift) + G * N(d));
+        else *price = floating(true) + S0 - K * D;
+    } else {
+        if (K < S0) *price = K * D * N(-d + s) - S0 * N(-d) + S0 * D * lam * (pw * N(-d + shift) - G * N(-d));
+        else *price = floating(false) + K * D - S0;
+    }
     return MCAMD_OK;
 }
 
