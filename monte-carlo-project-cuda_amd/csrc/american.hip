@@ -185,22 +185,11 @@ __global__ __launch_bounds__(kBlock) void am_price_kernel(AmPriceArgs<T> a, doub
 
 static uint64_t align256(uint64_t x) { return (x + 255) & ~static_cast<uint64_t>(255); }
 
-uint32_t american_sweep_grid(uint64_t n_train)
-{
-    const uint64_t blocks = (n_train + kBlock - 1) / kBlock;
-    return static_cast<uint32_t>(blocks < 1 ? 1 : (blocks < kFoldMaxRecords ? blocks : kFoldMaxRecords));
-}
-
-uint32_t american_price_grid(uint64_t n_local)
-{
-    return american_sweep_grid(n_local);   // one path per thread, capped so that the last workgroup finishes the sum
-}
-
 AmLayout american_layout(uint64_t n_train, uint32_t n_steps, uint32_t M, int precision)
 {
     const uint64_t elem = precision == 32 ? 4 : 8;
     const uint64_t partials = std::max<uint64_t>(2ull * store_grid(n_train, precision),
-                                                 static_cast<uint64_t>(kAmRecord) * american_sweep_grid(n_train));
+                                                 static_cast<uint64_t>(kAmRecord) * one_path_per_thread_grid(n_train));
     AmLayout l;
     l.traj = 0;
     l.V = l.traj + align256(static_cast<uint64_t>(n_steps) * n_train * elem);

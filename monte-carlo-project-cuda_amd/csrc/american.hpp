@@ -35,9 +35,7 @@ struct AmLayout {
 };
 AmLayout american_layout(uint64_t n_train, uint32_t n_steps, uint32_t M, int precision);
 
-uint32_t american_sweep_grid(uint64_t n_train);
-uint32_t american_price_grid(uint64_t n_local);
-
+// Both passes run on one_path_per_thread_grid (launch.hpp): of n_train the sweep, of n_local the pricing kernel.
 // The M sweep launches.  traj: n_steps x n_train stored rows; V: n_train doubles; table: (M + 1) x kAmRow doubles;
 // records: two record slots (kAmRecordSlot doubles each; launch j writes slot j & 1, launch 0's is the in-sample
 // {sum V, sum V^2}); partials: grid x kAmRecord doubles; ticket: the context's zeroed arrival counter.

@@ -187,18 +187,13 @@ uint32_t american_cont_grid(uint64_t n_points)
     return static_cast<uint32_t>(n_points < 1 ? 1 : (n_points < kFoldMaxRecords ? n_points : kFoldMaxRecords));
 }
 
-uint32_t american_scan_grid(uint64_t n_local)
-{
-    return american_price_grid(n_local);
-}
-
 AmDualLayout american_dual_layout(uint64_t n_local, uint32_t n_steps, uint32_t M, int precision)
 {
     const uint64_t elem = precision == 32 ? 4 : 8;
     const uint64_t partials = std::max<uint64_t>(
         2ull * store_grid(n_local, precision),
         std::max<uint64_t>(static_cast<uint64_t>(kAmContRecord) * american_cont_grid(static_cast<uint64_t>(M) * n_local),
-                           static_cast<uint64_t>(kAmDualRecord) * american_scan_grid(n_local)));
+                           static_cast<uint64_t>(kAmDualRecord) * one_path_per_thread_grid(n_local)));
     AmDualLayout l;
     l.traj = 0;
     l.cont = l.traj + align256(static_cast<uint64_t>(n_steps) * n_local * elem);

@@ -30,7 +30,7 @@ struct AmDualLayout {
 AmDualLayout american_dual_layout(uint64_t n_local, uint32_t n_steps, uint32_t M, int precision);
 
 uint32_t american_cont_grid(uint64_t n_points);   // one workgroup per point, capped: the workgroups stride
-uint32_t american_scan_grid(uint64_t n_local);    // one outer path per thread, capped likewise
+// (the scan runs on one_path_per_thread_grid(n_local))
 
 // Q[j * n_local + p], j = 0..M-1: the mean of the n_inner continuation samples of point (p, j).  traj: the stored
 // outer rows (n_steps x n_local); table: (M + 1) x kAmRow doubles (rows 1..M: beta, flag, d_j, t_j); out receives the

@@ -114,12 +114,6 @@ __global__ __launch_bounds__(kBlock) void barrier_kernel(BarrierArgs<T> a, doubl
     grid_finish<kBlock, kBarrierRecord>(acc4, partials, a.fin);
 }
 
-uint32_t barrier_grid(const BarrierJob &job)
-{
-    const uint64_t blocks = clamp_grid((job.path.n_local + kBlock - 1) / kBlock);
-    return static_cast<uint32_t>(blocks < kFoldMaxRecords ? blocks : kFoldMaxRecords);
-}
-
 template <typename T, bool UP, bool CONT>
 static void launch_barrier_k(const BarrierJob &j, const BarrierArgs<T> &a, double *d_partials, uint32_t grid,
                              hipStream_t stream)
@@ -133,9 +127,8 @@ template <typename T>
 static hipError_t launch_barrier_t(const BarrierJob &j, double *d_partials, uint32_t grid, const FinishSpec &fs,
                                    hipStream_t stream)
 {
-    // natural log per exponent unit (make_consts' units), and per unit of q
-    const double u = sizeof(T) == 4 ? 0.69314718055994531 : 1.0 / f64::kExpScale;
-    const double q_unit = sizeof(T) == 4 ? 0.69314718055994531 : 1.0;
+    const double u = exponent_unit<T>();   // and the natural log per unit of q:
+    const double q_unit = sizeof(T) == 4 ? kLn2 : 1.0;
     const double q_cut = sizeof(T) == 4 ? 18.0 : 38.0;
     const BarrierArgs<T> a{make_consts<T>(j.path), static_cast<T>(j.kq * u * u / q_unit), static_cast<T>(q_cut / q_unit),
                            j.put ? 1 : 0, j.path.seed, j.path.path_offset, j.path.n_local,
@@ -153,7 +146,7 @@ static hipError_t launch_barrier_t(const BarrierJob &j, double *d_partials, uint
 hipError_t launch_barrier(const BarrierJob &job, double *d_partials, uint32_t grid, const FinishSpec &finish,
                           hipStream_t stream)
 {
-    if (!finish.out || !finish.ticket || grid == 0 || grid > kFoldMaxRecords) return hipErrorInvalidValue;
+    if (!finish_ok(finish, grid)) return hipErrorInvalidValue;
     return job.path.precision == 32 ? launch_barrier_t<float>(job, d_partials, grid, finish, stream)
                                     : launch_barrier_t<double>(job, d_partials, grid, finish, stream);
 }

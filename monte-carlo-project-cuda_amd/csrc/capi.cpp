@@ -180,6 +180,47 @@ mcamd::PathJob make_job(const mcamd_option *opt, const mcamd_sim *sim)
     return j;
 }
 
+// The job of a call that runs plain paths whatever the flags say: no variance reduction, the given window and form.
+mcamd::PathJob make_plain_job(const mcamd_option *opt, const mcamd_sim *sim, bool window, bool logspace)
+{
+    mcamd::PathJob j = make_job(opt, sim);
+    j.window = window;
+    j.logspace = logspace;
+    j.vr = 0;
+    return j;
+}
+
+// What a plain product that starts at the spot ("American", "barrier", "lookback" options) refuses of the option and
+// the flags.  american: the rules of the two American calls, which read only use_window of the window fields, price
+// off S0 and K as well, and take the product form; the others allow MCAMD_FLAG_LOG_SPACE alone.
+int check_spot_start(const char *name, bool american, const mcamd_option *opt, const mcamd_sim *sim)
+{
+    const int allowed_flags = american ? MCAMD_FLAG_LOG_SPACE | MCAMD_FLAG_PRODUCT_FORM : MCAMD_FLAG_LOG_SPACE;
+    if (american) {
+        if (opt->use_window)
+            return fail(MCAMD_ERR_INVALID, "%s options take no bullet window: use_window must be 0", name);
+    } else if (opt->use_window || opt->P1 != 0 || opt->P2 != 0 || opt->Ik != 0) {
+        return fail(MCAMD_ERR_INVALID, "%s options take no bullet window: use_window, P1, P2 and Ik must be 0", name);
+    }
+    if (opt->Tk != 0 || opt->Sk != 0.0)
+        return fail(MCAMD_ERR_INVALID, "%s options start at t = 0: Tk and Sk must be 0 (Tk = %d, Sk = %g)", name,
+                    opt->Tk, opt->Sk);
+    if (opt->dt != 0.0) return fail(MCAMD_ERR_INVALID, "%s options step dt = T / n_steps: opt->dt must be 0", name);
+    if (american) {
+        if (!(opt->v > 0.0) || !(opt->S0 > 0.0) || !(opt->K > 0.0))
+            return fail(MCAMD_ERR_INVALID, "%s options need v > 0, S0 > 0 and K > 0 (v = %g, S0 = %g, K = %g)", name,
+                        opt->v, opt->S0, opt->K);
+    } else if (!(opt->v > 0.0)) {
+        return fail(MCAMD_ERR_INVALID, "%s options need v > 0 (v = %g)", name, opt->v);
+    }
+    if ((sim->flags & ~allowed_flags) || sim->flags == (MCAMD_FLAG_LOG_SPACE | MCAMD_FLAG_PRODUCT_FORM))
+        return fail(MCAMD_ERR_INVALID, american ? "%s options take flags 0, MCAMD_FLAG_LOG_SPACE or "
+                                                  "MCAMD_FLAG_PRODUCT_FORM, got %d"
+                                                : "%s options take flags 0 or MCAMD_FLAG_LOG_SPACE only, got %d",
+                    name, sim->flags);
+    return MCAMD_OK;
+}
+
 void zero_result(mcamd_result *res)
 {
     std::memset(res, 0, sizeof *res);
@@ -288,6 +329,14 @@ void finalize_cv_into(const double s[5], uint64_t n, double r, double T, mcamd_r
     res->price = disc * (ybar - beta * cbar);
     res->std_err = disc * std::sqrt(var_res / N);
     set_ci(res);
+}
+
+// a price record with the work counters behind it: {sum, sumsq, wave-steps, live lane-steps}
+void finalize_counted_into(const double rec[4], uint64_t n, double r, double T, mcamd_result *res)
+{
+    finalize_into(rec[0], rec[1], n, r, T, res);
+    res->work_steps = 64.0 * rec[2];   // wave-steps x 64 lanes
+    res->live_steps = rec[3];
 }
 
 // price / SE / CI of a pricing record: {sum, sumsq} or, with the control variate, the five sums
@@ -512,9 +561,7 @@ int prepare_greeks(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim
     if (int rc = check_common(ctx, opt, sim)) return rc;
     if (sim->n_paths_local == 0) return drive(empty_call(mcamd::kGreeksStats));
     mcamd::GreeksJob job;
-    job.path = make_job(opt, sim);
-    job.path.logspace = true;
-    job.path.vr = 0;
+    job.path = make_plain_job(opt, sim, opt->use_window != 0, true);
     job.lr = rule.method == MCAMD_GREEKS_LIKELIHOOD_RATIO;
     const double dt = opt->dt > 0.0 ? opt->dt : opt->T / static_cast<double>(sim->n_steps);
     const double v = opt->v, r = opt->r, T = opt->T, T_h = dt * static_cast<double>(job.path.n_sim);
@@ -609,8 +656,8 @@ int check_barrier_kind(double S0, double B, int kind, int payoff)
     return MCAMD_OK;
 }
 
-// The barrier calls.  The kernel always finishes its own sum (barrier_grid caps the grid); every refusal that depends
-// on the request alone comes before the context is looked at.
+// The barrier calls.  The kernel always finishes its own sum (one_path_per_thread_grid caps the grid); every refusal
+// that depends on the request alone comes before the context is looked at.
 template <typename Drive>
 int prepare_barrier(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_barrier *bar,
                     void *d_samples, Drive drive)
@@ -621,30 +668,19 @@ int prepare_barrier(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *si
                                        "got %d", bar->monitoring);
     if (bar->reserved != 0) return fail(MCAMD_ERR_INVALID, "barrier->reserved must be 0, got %d", bar->reserved);
     if (int rc = check_barrier_kind(opt->S0, opt->B, bar->kind, bar->payoff)) return rc;
-    if (opt->use_window || opt->P1 != 0 || opt->P2 != 0 || opt->Ik != 0)
-        return fail(MCAMD_ERR_INVALID, "barrier options take no bullet window: use_window, P1, P2 and Ik must be 0");
-    if (opt->Tk != 0 || opt->Sk != 0.0)
-        return fail(MCAMD_ERR_INVALID, "barrier options start at t = 0: Tk and Sk must be 0 (Tk = %d, Sk = %g)", opt->Tk,
-                    opt->Sk);
-    if (opt->dt != 0.0) return fail(MCAMD_ERR_INVALID, "barrier options step dt = T / n_steps: opt->dt must be 0");
-    if (!(opt->v > 0.0)) return fail(MCAMD_ERR_INVALID, "barrier options need v > 0 (v = %g)", opt->v);
-    if (sim->flags & ~MCAMD_FLAG_LOG_SPACE)
-        return fail(MCAMD_ERR_INVALID, "barrier options take flags 0 or MCAMD_FLAG_LOG_SPACE only, got %d", sim->flags);
+    if (int rc = check_spot_start("barrier", false, opt, sim)) return rc;
     if (int rc = check_request(opt, sim)) return rc;
     if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
     if (sim->n_paths_local == 0) return drive(empty_call());
     mcamd::BarrierJob job;
-    job.path = make_job(opt, sim);
-    job.path.window = false;
-    job.path.logspace = true;
-    job.path.vr = 0;
+    job.path = make_plain_job(opt, sim, false, true);
     job.up = bar->kind == MCAMD_BARRIER_UP_OUT || bar->kind == MCAMD_BARRIER_UP_IN;
     job.out = bar->kind == MCAMD_BARRIER_DOWN_OUT || bar->kind == MCAMD_BARRIER_UP_OUT;
     job.continuous = bar->monitoring == MCAMD_MONITOR_CONTINUOUS;
     job.put = bar->payoff == MCAMD_PAYOFF_PUT;
     job.kq = 2.0 / (opt->v * opt->v * (opt->T / static_cast<double>(sim->n_steps)));
     job.d_samples = d_samples;
-    const uint32_t grid = mcamd::barrier_grid(job);
+    const uint32_t grid = mcamd::one_path_per_thread_grid(job.path.n_local);
     return drive(DeviceCall{job.path.n_local, grid, mcamd::kBarrierRecord, 6, Finish::kFolded,
                             [&](const mcamd::FinishSpec &fs) {
                                 return mcamd::launch_barrier(job, ctx->d_partials, grid, fs, ctx->stream);
@@ -664,8 +700,8 @@ int check_lookback_kind(double K, int strike, int payoff)
     return MCAMD_OK;
 }
 
-// The lookback calls.  The kernel always finishes its own sum (lookback_grid caps the grid); every refusal that depends
-// on the request alone comes before the context is looked at.
+// The lookback calls.  The kernel always finishes its own sum (one_path_per_thread_grid caps the grid); every refusal
+// that depends on the request alone comes before the context is looked at.
 template <typename Drive>
 int prepare_lookback(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_lookback *lb,
                      void *d_samples, Drive drive)
@@ -676,15 +712,7 @@ int prepare_lookback(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *s
                                        "got %d", lb->monitoring);
     if (lb->reserved != 0) return fail(MCAMD_ERR_INVALID, "lookback->reserved must be 0, got %d", lb->reserved);
     if (int rc = check_lookback_kind(opt->K, lb->strike, lb->payoff)) return rc;
-    if (opt->use_window || opt->P1 != 0 || opt->P2 != 0 || opt->Ik != 0)
-        return fail(MCAMD_ERR_INVALID, "lookback options take no bullet window: use_window, P1, P2 and Ik must be 0");
-    if (opt->Tk != 0 || opt->Sk != 0.0)
-        return fail(MCAMD_ERR_INVALID, "lookback options start at t = 0: Tk and Sk must be 0 (Tk = %d, Sk = %g)", opt->Tk,
-                    opt->Sk);
-    if (opt->dt != 0.0) return fail(MCAMD_ERR_INVALID, "lookback options step dt = T / n_steps: opt->dt must be 0");
-    if (!(opt->v > 0.0)) return fail(MCAMD_ERR_INVALID, "lookback options need v > 0 (v = %g)", opt->v);
-    if (sim->flags & ~MCAMD_FLAG_LOG_SPACE)
-        return fail(MCAMD_ERR_INVALID, "lookback options take flags 0 or MCAMD_FLAG_LOG_SPACE only, got %d", sim->flags);
+    if (int rc = check_spot_start("lookback", false, opt, sim)) return rc;
     const bool fixed = lb->strike == MCAMD_LOOKBACK_FIXED;
     mcamd_option seen = *opt;   // a floating strike ignores K, and every lookback ignores B
     if (!fixed) seen.K = 0.0;
@@ -693,10 +721,7 @@ int prepare_lookback(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *s
     if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
     if (sim->n_paths_local == 0) return drive(empty_call());
     mcamd::LookbackJob job;
-    job.path = make_job(&seen, sim);
-    job.path.window = false;
-    job.path.logspace = true;
-    job.path.vr = 0;
+    job.path = make_plain_job(&seen, sim, false, true);
     job.fixed = fixed;
     job.put = lb->payoff == MCAMD_PAYOFF_PUT;
     job.maximum = fixed ? !job.put : job.put;   // fixed call and floating put look at the maximum
@@ -704,7 +729,7 @@ int prepare_lookback(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *s
     job.K = seen.K;
     job.v2dt = opt->v * opt->v * (opt->T / static_cast<double>(sim->n_steps));
     job.d_samples = d_samples;
-    const uint32_t grid = mcamd::lookback_grid(job);
+    const uint32_t grid = mcamd::one_path_per_thread_grid(job.path.n_local);
     return drive(DeviceCall{job.path.n_local, grid, mcamd::kLookbackRecord, 6, Finish::kFolded,
                             [&](const mcamd::FinishSpec &fs) {
                                 return mcamd::launch_lookback(job, ctx->d_partials, grid, fs, ctx->stream);
@@ -1212,17 +1237,7 @@ int mcamd_price_american(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_si
     uint32_t M = 0;
     int n_basis = 0;
     if (int rc = check_american_shape(sim, am, &M, &n_basis)) return rc;
-    if (opt->use_window) return fail(MCAMD_ERR_INVALID, "American options take no bullet window: use_window must be 0");
-    if (opt->Tk != 0 || opt->Sk != 0.0)
-        return fail(MCAMD_ERR_INVALID, "American options start at t = 0: Tk and Sk must be 0 (Tk = %d, Sk = %g)", opt->Tk,
-                    opt->Sk);
-    if (opt->dt != 0.0) return fail(MCAMD_ERR_INVALID, "American options step dt = T / n_steps: opt->dt must be 0");
-    if (!(opt->v > 0.0) || !(opt->S0 > 0.0) || !(opt->K > 0.0))
-        return fail(MCAMD_ERR_INVALID, "American options need v > 0, S0 > 0 and K > 0 (v = %g, S0 = %g, K = %g)", opt->v,
-                    opt->S0, opt->K);
-    if (sim->flags != 0 && sim->flags != MCAMD_FLAG_LOG_SPACE && sim->flags != MCAMD_FLAG_PRODUCT_FORM)
-        return fail(MCAMD_ERR_INVALID, "American options take flags 0, MCAMD_FLAG_LOG_SPACE or MCAMD_FLAG_PRODUCT_FORM, "
-                                       "got %d", sim->flags);
+    if (int rc = check_spot_start("American", true, opt, sim)) return rc;
     if (!d_work) return fail(MCAMD_ERR_INVALID, "d_work is NULL");
     const mcamd::AmLayout lay = mcamd::american_layout(am->n_train, sim->n_steps, M, sim->precision);
     if (work_bytes < lay.total)
@@ -1240,10 +1255,8 @@ int mcamd_price_american(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_si
     double *w_partials = reinterpret_cast<double *>(base + lay.partials);
 
     mcamd::AmJob job;
-    job.path = make_job(opt, sim);
-    job.path.window = false;
-    job.path.logspace = false;   // the product form: St at every date, the same bits as the stored rows
-    job.path.vr = 0;
+    // the product form: St at every date, the same bits as the stored rows
+    job.path = make_plain_job(opt, sim, false, false);
     job.put = am->payoff == MCAMD_PAYOFF_PUT ? 1 : 0;
     job.n_basis = n_basis;
     job.k = am->exercise_every;
@@ -1258,8 +1271,8 @@ int mcamd_price_american(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_si
 
     const uint64_t n_local = sim->n_paths_local;
     const uint32_t store_grid = mcamd::store_grid(am->n_train, sim->precision);
-    const uint32_t sweep_grid = mcamd::american_sweep_grid(am->n_train);
-    const uint32_t price_grid = mcamd::american_price_grid(n_local);
+    const uint32_t sweep_grid = mcamd::one_path_per_thread_grid(am->n_train);
+    const uint32_t price_grid = mcamd::one_path_per_thread_grid(n_local);
     if (n_local)
         if (int rc = ensure_partials(ctx, price_grid, mcamd::kAmPriceRecord)) return rc;
     // all-ones bits in the record slots and the pinned record until a kernel has written the record: a sum that never
@@ -1350,17 +1363,7 @@ int mcamd_american_upper_bound(mcamd_ctx *ctx, const mcamd_option *opt, const mc
     uint32_t M = 0;
     int n_basis = 0;
     if (int rc = check_dual_shape(sim, am, dual, &M, &n_basis)) return rc;
-    if (opt->use_window) return fail(MCAMD_ERR_INVALID, "American options take no bullet window: use_window must be 0");
-    if (opt->Tk != 0 || opt->Sk != 0.0)
-        return fail(MCAMD_ERR_INVALID, "American options start at t = 0: Tk and Sk must be 0 (Tk = %d, Sk = %g)", opt->Tk,
-                    opt->Sk);
-    if (opt->dt != 0.0) return fail(MCAMD_ERR_INVALID, "American options step dt = T / n_steps: opt->dt must be 0");
-    if (!(opt->v > 0.0) || !(opt->S0 > 0.0) || !(opt->K > 0.0))
-        return fail(MCAMD_ERR_INVALID, "American options need v > 0, S0 > 0 and K > 0 (v = %g, S0 = %g, K = %g)", opt->v,
-                    opt->S0, opt->K);
-    if (sim->flags != 0 && sim->flags != MCAMD_FLAG_LOG_SPACE && sim->flags != MCAMD_FLAG_PRODUCT_FORM)
-        return fail(MCAMD_ERR_INVALID, "American options take flags 0, MCAMD_FLAG_LOG_SPACE or MCAMD_FLAG_PRODUCT_FORM, "
-                                       "got %d", sim->flags);
+    if (int rc = check_spot_start("American", true, opt, sim)) return rc;
     if (!h_coeffs) return fail(MCAMD_ERR_INVALID, "h_coeffs is NULL: the rule is what mcamd_price_american wrote");
     for (uint32_t j = 1; j <= M; ++j) {
         const double *row = h_coeffs + static_cast<size_t>(j - 1) * (n_basis + 1);
@@ -1392,10 +1395,8 @@ int mcamd_american_upper_bound(mcamd_ctx *ctx, const mcamd_option *opt, const mc
     double *w_partials = reinterpret_cast<double *>(base + lay.partials);
 
     mcamd::AmDualJob job;
-    job.path = make_job(opt, sim);
-    job.path.window = false;
-    job.path.logspace = false;   // the product form: St at every date, the same bits as the stored rows
-    job.path.vr = 0;
+    // the product form: St at every date, the same bits as the stored rows
+    job.path = make_plain_job(opt, sim, false, false);
     job.put = am->payoff == MCAMD_PAYOFF_PUT ? 1 : 0;
     job.n_basis = n_basis;
     job.k = am->exercise_every;
@@ -1419,7 +1420,7 @@ int mcamd_american_upper_bound(mcamd_ctx *ctx, const mcamd_option *opt, const mc
 
     const uint32_t store_grid = mcamd::store_grid(n_local, sim->precision);
     const uint32_t cont_grid = mcamd::american_cont_grid(static_cast<uint64_t>(M) * n_local);
-    const uint32_t scan_grid = mcamd::american_scan_grid(n_local);
+    const uint32_t scan_grid = mcamd::one_path_per_thread_grid(n_local);
     constexpr int kRec = mcamd::kAmDualRecord + mcamd::kAmContRecord;
     static_assert(kRec <= mcamd_ctx::kRecord, "the pinned record holds both kernels' records");
     arm_record(ctx->h_rec, kRec);
@@ -1466,9 +1467,7 @@ int mcamd_price_barrier(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim
     zero_result(res);
     return prepare_barrier(ctx, opt, sim, barrier, d_samples, [&](const auto &call) {
         return run_sync(ctx, call, res, [&](const double *rec) {
-            finalize_into(rec[0], rec[1], sim->n_paths_local, opt->r, opt->T, res);
-            res->work_steps = 64.0 * rec[2];   // wave-steps x 64 lanes
-            res->live_steps = rec[3];
+            finalize_counted_into(rec, sim->n_paths_local, opt->r, opt->T, res);
         });
     });
 }
@@ -1520,9 +1519,7 @@ int mcamd_price_lookback(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_si
     zero_result(res);
     return prepare_lookback(ctx, opt, sim, lookback, d_samples, [&](const auto &call) {
         return run_sync(ctx, call, res, [&](const double *rec) {
-            finalize_into(rec[0], rec[1], sim->n_paths_local, opt->r, opt->T, res);
-            res->work_steps = 64.0 * rec[2];   // wave-steps x 64 lanes
-            res->live_steps = rec[3];
+            finalize_counted_into(rec, sim->n_paths_local, opt->r, opt->T, res);
         });
     });
 }

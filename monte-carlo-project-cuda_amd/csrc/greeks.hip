@@ -177,15 +177,13 @@ __global__ __launch_bounds__(kBlock) void greeks_lr_kernel(GreeksArgs<T> a, doub
 
 uint32_t greeks_grid(const GreeksJob &job)
 {
-    uint64_t blocks;
     if (!job.lr) {
-        blocks = price_grid(job.path, 0);   // window-less log-space job: the pair-sum loop's shape
-    } else {
-        const uint64_t per_thread = job.path.n_sim >= 32 ? 1 : (32 + job.path.n_sim - 1) / job.path.n_sim;
-        const uint64_t threads = (job.path.n_local + per_thread - 1) / per_thread;
-        blocks = clamp_grid((threads + kBlock - 1) / kBlock);
+        const uint32_t blocks = price_grid(job.path, 0);   // window-less log-space job: the pair-sum loop's shape
+        return blocks < kFoldMaxRecords ? blocks : kFoldMaxRecords;
     }
-    return static_cast<uint32_t>(blocks < kFoldMaxRecords ? blocks : kFoldMaxRecords);
+    // short paths: enough grid-stride trips per thread for 32 steps
+    const uint64_t per_thread = job.path.n_sim >= 32 ? 1 : (32 + job.path.n_sim - 1) / job.path.n_sim;
+    return one_path_per_thread_grid((job.path.n_local + per_thread - 1) / per_thread);
 }
 
 template <typename T>
@@ -193,7 +191,7 @@ static hipError_t launch_greeks_t(const GreeksJob &j, double *d_partials, uint32
                                   unsigned int *ticket, hipStream_t stream)
 {
     GreeksConsts gc = j.g;
-    gc.inv_scale = sizeof(T) == 4 ? 0.69314718055994531 : 1.0 / f64::kExpScale;   // make_consts' exponent units
+    gc.inv_scale = exponent_unit<T>();
     const GreeksArgs<T> a{make_consts<T>(j.path), gc, j.path.seed, j.path.path_offset, j.path.n_local,
                           GridFinish{out, ticket, -1.0}};
     const dim3 g(grid), b(kBlock);

@@ -45,6 +45,18 @@ struct FinishSpec {
 // One workgroup of 256 threads sums up to this many records in a few microseconds; beyond it the separate
 // 1024-thread reduction is faster than the lone last workgroup.
 constexpr uint32_t kFoldMaxRecords = 8192;
+// Launch shape of the kernels that take one path (or training path) per thread and always finish their own sum: capped
+// at kFoldMaxRecords workgroups, the threads grid-stride beyond.
+inline uint32_t one_path_per_thread_grid(uint64_t n)
+{
+    const uint64_t blocks = (n + kBlockThreads - 1) / kBlockThreads;
+    return static_cast<uint32_t>(blocks < 1 ? 1 : (blocks < kFoldMaxRecords ? blocks : kFoldMaxRecords));
+}
+// what a self-finishing launcher needs of its finish and grid
+inline bool finish_ok(const FinishSpec &finish, uint32_t grid)
+{
+    return finish.out && finish.ticket && grid != 0 && grid <= kFoldMaxRecords;
+}
 
 hipError_t launch_price(const PathJob &job, uint32_t compute_units, double *d_partials, unsigned long long *d_queue,
                         uint32_t grid, const FinishSpec &finish, hipStream_t stream);

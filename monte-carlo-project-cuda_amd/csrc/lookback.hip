@@ -154,12 +154,6 @@ __global__ __launch_bounds__(kBlock) void lookback_kernel(LookbackArgs<T> a, dou
     grid_finish<kBlock, kLookbackRecord>(acc4, partials, a.fin);
 }
 
-uint32_t lookback_grid(const LookbackJob &job)
-{
-    const uint64_t blocks = clamp_grid((job.path.n_local + kBlock - 1) / kBlock);
-    return static_cast<uint32_t>(blocks < kFoldMaxRecords ? blocks : kFoldMaxRecords);
-}
-
 template <typename T, bool MAXIMUM>
 static void launch_lookback_k(const LookbackJob &j, const LookbackArgs<T> &a, double *d_partials, uint32_t grid,
                               hipStream_t stream)
@@ -173,10 +167,10 @@ template <typename T>
 static hipError_t launch_lookback_t(const LookbackJob &j, double *d_partials, uint32_t grid, const FinishSpec &fs,
                                     hipStream_t stream)
 {
-    // natural log per exponent unit (make_consts' units); what the precision's logarithm of U has to be multiplied by
-    // to give -2 ln U (v_log_f32 is a log2; f64::neg2log is -2 ln already)
-    const double u = sizeof(T) == 4 ? 0.69314718055994531 : 1.0 / f64::kExpScale;
-    const double log_unit = sizeof(T) == 4 ? 2.0 * 0.69314718055994531 : 1.0;
+    // log_unit: what the precision's logarithm of U has to be multiplied by to give -2 ln U (v_log_f32 is a log2;
+    // f64::neg2log is -2 ln already)
+    const double u = exponent_unit<T>();
+    const double log_unit = sizeof(T) == 4 ? 2.0 * kLn2 : 1.0;
     const double q_cut = sizeof(T) == 4 ? 22.25 : 36.75;
     const LookbackArgs<T> a{make_consts<T>(j.path), static_cast<T>(2.0 * u * u / j.v2dt),
                             static_cast<T>(j.v2dt * log_unit / (u * u)), static_cast<T>(q_cut), j.K, j.fixed ? 1 : 0,
@@ -190,7 +184,7 @@ static hipError_t launch_lookback_t(const LookbackJob &j, double *d_partials, ui
 hipError_t launch_lookback(const LookbackJob &job, double *d_partials, uint32_t grid, const FinishSpec &finish,
                            hipStream_t stream)
 {
-    if (!finish.out || !finish.ticket || grid == 0 || grid > kFoldMaxRecords) return hipErrorInvalidValue;
+    if (!finish_ok(finish, grid)) return hipErrorInvalidValue;
     return job.path.precision == 32 ? launch_lookback_t<float>(job, d_partials, grid, finish, stream)
                                     : launch_lookback_t<double>(job, d_partials, grid, finish, stream);
 }

@@ -24,14 +24,11 @@ struct LookbackJob {
     void *d_samples;   // nullable: n_local samples of the path precision
 };
 
-// Launch shape: one path per thread, capped at kFoldMaxRecords workgroups (the threads grid-stride beyond), so the
-// kernel always finishes its own sum.
-uint32_t lookback_grid(const LookbackJob &job);
-
-// Enqueues the kernel.  finish.out: where the final record goes (device memory, or pinned host memory the device can
-// write); finish.ticket: the context's zeroed arrival counter; d_partials: grid x kLookbackRecord doubles.  With
-// finish.n_value >= 0 (the enqueue form) the record is the 6-double statistics layout {sum, sumsq, 0, 0, 0, n}: it has
-// no slot for the two step counters, which are then left out of the sum.
+// Enqueues the kernel on a grid of one_path_per_thread_grid(n_local) workgroups.  finish.out: where the final record
+// goes (device memory, or pinned host memory the device can write); finish.ticket: the context's zeroed arrival
+// counter; d_partials: grid x kLookbackRecord doubles.  With finish.n_value >= 0 (the enqueue form) the record is the
+// 6-double statistics layout {sum, sumsq, 0, 0, 0, n}: it has no slot for the two step counters, which are then left
+// out of the sum.
 hipError_t launch_lookback(const LookbackJob &job, double *d_partials, uint32_t grid, const FinishSpec &finish,
                            hipStream_t stream);
 

@@ -9,6 +9,16 @@
 
 namespace mcamd {
 
+constexpr double kLn2 = 0.69314718055994531;
+
+// Natural log per exponent unit: ln 2 for fp32's log2 units, ln 2 / 65536 for fp64's.  make_consts' scale is the
+// reciprocal, kept as its own literals: 1 / unit does not round to them.
+template <typename T>
+inline double exponent_unit()
+{
+    return sizeof(T) == 4 ? kLn2 : 1.0 / f64::kExpScale;
+}
+
 template <typename T>
 inline StepConsts<T> make_consts(const PathJob &j)
 {
