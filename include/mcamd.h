@@ -694,6 +694,97 @@ int mcamd_price_lookback_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const 
  * and r == 0: the formulas carry v^2 / (2r), and their limit at r = 0 is left out on purpose. */
 int mcamd_lookback_price_f64(double S0, double K, double T, double r, double v, int strike, int payoff, double *price);
 
+/* ---- Basket, spread and rainbow options on d = 1..8 correlated assets ----
+ * Additive to ABI version 5: first carried by the build that ships csrc/basket.hip (no struct of an earlier call
+ * changed, so MCAMD_ABI_VERSION stays 5; a caller finds out with dlsym).
+ * r, T, K and the barrier level B come from opt; opt->S0 and opt->v are ignored (the assets' own are in *basket), and
+ * opt->B is ignored without a barrier.  d = basket->n_assets; j, k = 0..d-1 index assets; dt = T / n_steps.
+ *   Correlation.  L is the lower Cholesky factor of corr[:d, :d] (corr[8 j + k] = rho_jk), computed on the host in
+ *       fp64.
+ *   Step.  x_{j,i} = (r - v_j^2/2) dt + sum_{k <= j} (v_j sqrt(dt) L_jk) z_{i,k}, accumulated as a chain of fused
+ *       multiply-adds in ascending k that starts from the drift.  The coefficients v_j sqrt(dt) L_jk and the drifts
+ *       reach the kernel in the exponent units of the precision (log2 units in fp32, 2^-16 octaves in fp64), narrowed
+ *       once on the host.
+ *   Log-price.  X_{j,0} = 0, X_{j,i} = X_{j,i-1} + x_{j,i};  S_{j,i} = S0_j e^{X_{j,i}}.
+ *   Normals.  z_{i,k} is normal number i d + k of the path's stream: Philox subsequence = the GLOBAL path id, block
+ *       (i d + k) / NB, slot (i d + k) % NB in the order mcamd_generate_normals and the other products use (NB = 4 in
+ *       fp32, 2 in fp64).  With d = 1 these are the normals mcamd_price_barrier and mcamd_price_lookback step with.
+ *   Aggregate A_i of the prices after step i:
+ *       MCAMD_BASKET_ARITHMETIC  A = sum_j w_j S_j      (w_j of any sign: spreads, exchange options)
+ *       MCAMD_BASKET_GEOMETRIC   A = prod_j S_j^{w_j}   = exp(sum_j w_j (ln S0_j + X_j))
+ *       MCAMD_BASKET_BEST_OF     A = max_j w_j S_j      = exp(max_j (ln(w_j S0_j) + X_j))   (w_j > 0; w_j = 1 / S0_j:
+ *       MCAMD_BASKET_WORST_OF    A = min_j w_j S_j      = exp(min_j (ln(w_j S0_j) + X_j))    performances)
+ *       Geometric, best-of and worst-of aggregate in log space in the path precision (the geometric sum is a chain of
+ *       fused multiply-adds in ascending j that starts from sum_j w_j ln S0_j) and take one exponential per path;
+ *       arithmetic takes d exponentials per path at maturity only, S_j in the path precision, and sums w_j S_j in
+ *       fp64 in ascending j by fused multiply-adds from 0.
+ *   Sample, formed once per path in fp64:  call  y = (A_n - K)+;  put  y = (K - A_n)+.
+ *   Barrier (MCAMD_BASKET_BEST_OF and MCAMD_BASKET_WORST_OF only), monitored at the n_steps step ends only: the hit
+ *       test compares the log aggregate with ln B in the path precision; "down" hits at A_i <= B, "up" at A_i >= B.
+ *       Knock-out pays y if the path never hit, knock-in pays y if it hit.  No rebate.  There is no continuous
+ *       monitoring, on purpose: the law of the extremum of a minimum (or maximum) over correlated Brownian bridges has
+ *       no closed form to weight or sample a step with.
+ *   price = exp(-rT) mean(y), std_err as in mcamd_finalize.
+ * The sample is the exact law of correlated geometric Brownian motion at the step ends for every n_steps, so terminal
+ * products are unbiased at n_steps = 1.
+ * d_samples (nullable, device): n_paths_local values of the path precision; [local path] receives y.
+ * res: sum / sumsq / n / price / std_err / ci_*, kernel_ms / total_ms / grid / block; work_steps = 64 x the steps each
+ * wavefront ran (a knock-out wavefront leaves the step loop once every lane has hit), live_steps = the lane-steps of
+ * paths not yet hit (0 without a barrier); the other fields are 0.
+ * The enqueue form leaves {sum, sumsq, 0, 0, 0, n} in d_stats (device, >= 6 doubles): mcamd_finalize_stats and one
+ * all-reduce of 6 doubles serve it unchanged, and mcamd_enqueued_kernel_ms covers it.
+ * Requirements (MCAMD_ERR_INVALID before any device work and before the context is looked at): opt, sim, basket, res
+ * non-NULL; n_assets in 1..MCAMD_BASKET_MAX_ASSETS; kind, payoff, barrier in range; reserved[0] == reserved[1] == 0;
+ * every S0_j and v_j finite and positive; every w_j finite, and positive for best-of / worst-of, not all zero for
+ * arithmetic / geometric; K finite and >= 0; corr with a diagonal of exactly 1, exactly symmetric, no entry beyond
+ * +-1, and positive definite: every Cholesky pivot (the square of the diagonal entry of L) above 1e-12 — the rule is
+ * arbitrary but fixed, and it refuses rho = +-1 (use fewer assets); a barrier needs best-of or worst-of, B > 0 and A_0
+ * strictly on the live side (down: A_0 > B, up: A_0 < B); use_window, P1, P2, Ik, Sk, Tk and opt->dt all 0;
+ * sim->flags 0 or MCAMD_FLAG_LOG_SPACE; and what mcamd_price_paths refuses on sim.  corr entries beyond n_assets
+ * are ignored, as are S0, v and w beyond it.  An empty shard returns zeros and launches nothing.
+ * There is no mcamd_group_* form and no shim name: the reference has no such product.  Multi-GPU: every rank prices
+ * its shard (a path's sample depends on its global id alone); the 6-double records add.  New. */
+#define MCAMD_BASKET_MAX_ASSETS 8
+#define MCAMD_BASKET_ARITHMETIC 0
+#define MCAMD_BASKET_GEOMETRIC 1
+#define MCAMD_BASKET_BEST_OF 2
+#define MCAMD_BASKET_WORST_OF 3
+
+#define MCAMD_BASKET_NO_BARRIER 0
+#define MCAMD_BASKET_DOWN_OUT 1
+#define MCAMD_BASKET_DOWN_IN 2
+#define MCAMD_BASKET_UP_OUT 3
+#define MCAMD_BASKET_UP_IN 4
+
+typedef struct mcamd_basket {
+    int32_t n_assets;    /* d, 1..MCAMD_BASKET_MAX_ASSETS */
+    int32_t kind;        /* MCAMD_BASKET_ARITHMETIC .. MCAMD_BASKET_WORST_OF */
+    int32_t payoff;      /* MCAMD_PAYOFF_* */
+    int32_t barrier;     /* MCAMD_BASKET_NO_BARRIER .. MCAMD_BASKET_UP_IN */
+    int32_t reserved[2]; /* must be 0 */
+    double S0[8];        /* spots */
+    double v[8];         /* volatilities */
+    double w[8];         /* weights */
+    double corr[64];     /* correlations, row-major with stride 8 */
+} mcamd_basket;
+
+int mcamd_price_basket(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_basket *basket,
+                       void *d_samples, mcamd_result *res);
+int mcamd_price_basket_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                               const mcamd_basket *basket, void *d_samples, double *d_stats);
+/* Host closed form of the geometric basket of any d, a lognormal: ln A_T is normal with mean
+ * m = sum_j w_j (ln S0_j + (r - v_j^2/2) T) and variance s^2 = T w'(v o corr o v)w, so the call is
+ * e^{-rT} (e^{m + s^2/2} N(d1) - K N(d1 - s)) with d1 = (m - ln K) / s + s (K = 0: the discounted forward).  kind,
+ * barrier and reserved of *basket are not read; payoff is.  Refuses what mcamd_price_basket refuses of n_assets, payoff,
+ * S0, v, w (not all zero), corr, K, T and r. */
+int mcamd_basket_geometric_price_f64(const mcamd_basket *basket, double K, double T, double r, double *price);
+/* Host closed form of the option to exchange b S2 for a S1, (a S1 - b S2)+ (Margrabe 1978), with a_S1 = a S1(0) and
+ * b_S2 = b S2(0) both positive: a_S1 N(d1) - b_S2 N(d2), d1 = (ln(a_S1 / b_S2) + s^2 T / 2) / (s sqrt T),
+ * d2 = d1 - s sqrt T, s^2 = v1^2 + v2^2 - 2 rho v1 v2.  The rate drops out.  It is mcamd_price_basket's arithmetic call
+ * with w = (a, -b) and K = 0.  MCAMD_ERR_INVALID for non-finite or non-positive a_S1, b_S2, T, v1 or v2, or rho not
+ * strictly inside (-1, 1). */
+int mcamd_exchange_price_f64(double a_S1, double b_S2, double T, double v1, double v2, double rho, double *price);
+
 /* Host: discount + mean + standard error + 95% CI from (sum, sumsq, n) — after an all-reduce
  * over shards, or directly.  Fills price/std_err/ci_* (and copies sum/sumsq/n) in *res. */
 int mcamd_finalize(double sum, double sumsq, uint64_t n, double r, double T, mcamd_result *res);

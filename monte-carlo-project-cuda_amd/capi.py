@@ -27,6 +27,9 @@ PAYOFF_CALL, PAYOFF_PUT = 0, 1
 BARRIER_DOWN_OUT, BARRIER_DOWN_IN, BARRIER_UP_OUT, BARRIER_UP_IN = 0, 1, 2, 3
 MONITOR_DISCRETE, MONITOR_CONTINUOUS = 0, 1
 LOOKBACK_FLOATING, LOOKBACK_FIXED = 0, 1
+BASKET_MAX_ASSETS = 8
+BASKET_ARITHMETIC, BASKET_GEOMETRIC, BASKET_BEST_OF, BASKET_WORST_OF = 0, 1, 2, 3
+BASKET_NO_BARRIER, BASKET_DOWN_OUT, BASKET_DOWN_IN, BASKET_UP_OUT, BASKET_UP_IN = 0, 1, 2, 3, 4
 
 # every symbol include/mcamd.h declares
 EXPORTS = [
@@ -44,6 +47,7 @@ EXPORTS = [
     "mcamd_american_dual_workspace_bytes", "mcamd_american_upper_bound",
     "mcamd_price_barrier", "mcamd_price_barrier_enqueue", "mcamd_barrier_price_f64",
     "mcamd_price_lookback", "mcamd_price_lookback_enqueue", "mcamd_lookback_price_f64",
+    "mcamd_price_basket", "mcamd_price_basket_enqueue", "mcamd_basket_geometric_price_f64", "mcamd_exchange_price_f64",
 ]
 
 
@@ -126,6 +130,14 @@ class Barrier(C.Structure):
 class Lookback(C.Structure):
     """mcamd_lookback: which lookback mcamd_price_lookback prices, and how the extremum is monitored."""
     _fields_ = [("strike", C.c_int32), ("payoff", C.c_int32), ("monitoring", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Basket(C.Structure):
+    """mcamd_basket: the assets (spots, volatilities, weights, correlations with row stride 8), the aggregate and the
+    optional barrier mcamd_price_basket prices."""
+    _fields_ = [("n_assets", C.c_int32), ("kind", C.c_int32), ("payoff", C.c_int32), ("barrier", C.c_int32),
+                ("reserved", C.c_int32 * 2), ("S0", C.c_double * 8), ("v", C.c_double * 8), ("w", C.c_double * 8),
+                ("corr", C.c_double * 64)]
 
 
 class DeviceInfo(C.Structure):
@@ -223,6 +235,10 @@ def load() -> C.CDLL:
     L.mcamd_price_lookback.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Lookback), vp, C.POINTER(Result)]
     L.mcamd_price_lookback_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Lookback), vp, vp]
     L.mcamd_lookback_price_f64.argtypes = [f64, f64, f64, f64, f64, i32, i32, C.POINTER(f64)]
+    L.mcamd_price_basket.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Basket), vp, C.POINTER(Result)]
+    L.mcamd_price_basket_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Basket), vp, vp]
+    L.mcamd_basket_geometric_price_f64.argtypes = [C.POINTER(Basket), f64, f64, f64, C.POINTER(f64)]
+    L.mcamd_exchange_price_f64.argtypes = [f64, f64, f64, f64, f64, f64, C.POINTER(f64)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("mcamd_abi_version",):
@@ -288,6 +304,33 @@ def lookback_price_f64(S0, K, T, r, sigma, strike=LOOKBACK_FLOATING, payoff=PAYO
     """closed form of the continuously monitored, newly issued lookback (Goldman-Sosin-Gatto, Conze-Viswanathan)"""
     p = C.c_double(0)
     _check(load().mcamd_lookback_price_f64(S0, K, T, r, sigma, strike, payoff, C.byref(p)))
+    return p.value
+
+
+def make_basket(S0, v, w, corr, kind=BASKET_ARITHMETIC, payoff=PAYOFF_CALL, barrier=BASKET_NO_BARRIER) -> Basket:
+    """S0, v, w: d values each (d = len(S0), at most BASKET_MAX_ASSETS); corr: d x d (nested sequences or an array)."""
+    d = len(S0)
+    if not 1 <= d <= BASKET_MAX_ASSETS or len(v) != d or len(w) != d or len(corr) != d or any(len(row) != d for row in corr):
+        raise ValueError(f"a basket takes 1..{BASKET_MAX_ASSETS} assets and S0, v, w of d and corr of d x d values")
+    b = Basket(d, kind, payoff, barrier)
+    for j in range(d):
+        b.S0[j], b.v[j], b.w[j] = float(S0[j]), float(v[j]), float(w[j])
+        for k in range(d):
+            b.corr[8 * j + k] = float(corr[j][k])
+    return b
+
+
+def basket_geometric_price_f64(basket: Basket, K, T, r) -> float:
+    """closed form of the geometric basket (a lognormal); basket.payoff selects call or put"""
+    p = C.c_double(0)
+    _check(load().mcamd_basket_geometric_price_f64(C.byref(basket), K, T, r, C.byref(p)))
+    return p.value
+
+
+def exchange_price_f64(a_S1, b_S2, T, v1, v2, rho) -> float:
+    """Margrabe's closed form of (a S1 - b S2)+, with a_S1 = a S1(0) and b_S2 = b S2(0)"""
+    p = C.c_double(0)
+    _check(load().mcamd_exchange_price_f64(a_S1, b_S2, T, v1, v2, rho, C.byref(p)))
     return p.value
 
 
@@ -444,6 +487,20 @@ class Context:
         """Asynchronous: leaves {sum, sumsq, 0, 0, 0, n} in the device tensor `stats` (>= 6 doubles; finalize_stats)."""
         _check(self._L.mcamd_price_lookback_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(lookback),
                                                     _ptr(samples), _ptr(stats)))
+
+    def price_basket(self, opt: Option, sim: Sim, basket: Basket, samples=None) -> Result:
+        """Basket, spread or rainbow option on correlated assets (mcamd_price_basket): r, T, K and the barrier level B
+        come from opt.  samples: optional device tensor of n_paths_local values of the path precision that receives
+        each path's undiscounted sample."""
+        res = Result()
+        _check(self._L.mcamd_price_basket(self._h, C.byref(opt), C.byref(sim), C.byref(basket), _ptr(samples),
+                                          C.byref(res)))
+        return res
+
+    def price_basket_enqueue(self, opt: Option, sim: Sim, basket: Basket, stats, samples=None) -> None:
+        """Asynchronous: leaves {sum, sumsq, 0, 0, 0, n} in the device tensor `stats` (>= 6 doubles; finalize_stats)."""
+        _check(self._L.mcamd_price_basket_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(basket),
+                                                  _ptr(samples), _ptr(stats)))
 
     def price_american(self, opt: Option, sim: Sim, am: American, work, coeffs: bool = False):
         """Least-squares Monte Carlo price of an American / Bermudan put or call (mcamd_price_american).  work: a device

@@ -1,0 +1,230 @@
+// basket.hip — options on d = 1..8 correlated assets for gfx950 (both path precisions): arithmetic and geometric
+// baskets (spreads and exchange options are arithmetic baskets with a negative weight), best-of and worst-of, call or
+// put; best-of and worst-of optionally with a barrier on the aggregate, tested at the step ends.
+//
+// Definitions (include/mcamd.h, mcamd_price_basket): X_{j,i} = ln(S_{j,i} / S0_j) after step i, X_{j,0} = 0,
+// X_{j,i} = X_{j,i-1} + x_{j,i}, x_{j,i} = drift_j + sum_{k <= j} c_jk z_{i,k} with c_jk = v_j sqrt(dt) L_jk and L the
+// lower Cholesky factor of the correlation matrix; the sum is a chain of fused multiply-adds in ascending k that starts
+// from the drift.  z_{i,k} is normal number i d + k of the path's stream: Philox block (i d + k) / NB, slot
+// (i d + k) % NB of Normals<T>::z.  With d = 1 that is the normal the barrier and lookback kernels step with.
+//
+// The loop walks the stream in whole Philox blocks: G = NB / gcd(D, NB) steps consume G D / NB whole blocks, so a
+// group of G steps is unrolled with the block boundaries at compile-time positions, and the last n_steps % G steps run
+// the same code under a wave-uniform count.  Per step: D (D + 1) / 2 fused multiply-adds, D adds and — monitored — D
+// adds, D - 1 max / min and one compare, all in log space: no exponential before maturity.  The D accumulators, the D
+// drifts and the D (D + 1) / 2 coefficients stay in registers (D is a template argument): in fp32 in VECTOR registers
+// (a scalar operand doubles the issue time of v_fma_f32: vgpr_resident), in fp64 wherever the compiler puts them (an
+// fp64 instruction takes its cycles whatever its operands).  Kind, payoff, barrier side and knock-in / knock-out are
+// wave-uniform selects.  A knock-out wavefront leaves the loop at the first group end where every lane has hit.
+#include "basket.hpp"
+#include "path_consts.hpp"
+
+namespace mcamd {
+
+template <typename T, int D>
+struct BasketArgs {
+    T drift[D];                // exponent units
+    T coef[D * (D + 1) / 2];   // exponent units, [j (j + 1) / 2 + k]
+    T log_w[D];                // best / worst: ln(w_j S0_j) in exponent units; geometric: [0] = sum_j w_j ln S0_j, likewise
+    T w_t[D];                  // geometric: the weights in the path precision
+    T S0[D];                   // arithmetic: the spots in the path precision
+    T logB;                    // ln B in exponent units
+    double w[D];               // arithmetic: the weights
+    double K;
+    int kind, put, up, out;
+    uint32_t n_steps;
+    uint64_t seed;
+    uint64_t path_offset;
+    uint64_t n_local;
+    T *samples;                // nullable
+    GridFinish fin;
+};
+
+constexpr int gcd_c(int a, int b) { return b == 0 ? a : gcd_c(b, a % b); }
+
+__device__ __forceinline__ float bk_max(float a, float b) { return __builtin_fmaxf(a, b); }
+__device__ __forceinline__ double bk_max(double a, double b) { return __builtin_fmax(a, b); }
+__device__ __forceinline__ float bk_min(float a, float b) { return __builtin_fminf(a, b); }
+__device__ __forceinline__ double bk_min(double a, double b) { return __builtin_fmin(a, b); }
+// Where the loop's constants live.  fp32: in vector registers, because a scalar operand doubles the issue time of the
+// full-rate v_fma_f32 / v_add_f32 (vgpr_resident).  fp64: a scalar operand costs nothing, but D + D (D + 1) / 2 doubles
+// are 2 D + D (D + 1) scalar registers, and beyond D = 2 they no longer fit beside the kernel's other scalars — the
+// compiler then spills them to vector-register lanes and reads them back one v_readlane at a time inside the step (up
+// to 203 spills at D = 7, and scratch).  From D = 3 they are therefore moved to vector registers once per kernel.
+template <int D>
+__device__ __forceinline__ float bk_resident(float s) { return vgpr_resident(s); }
+template <int D>
+__device__ __forceinline__ double bk_resident(double s)
+{
+    if (D >= 3) asm volatile("" : "+v"(s));
+    return s;
+}
+
+template <typename T, int D, bool MONITORED>
+__global__ __launch_bounds__(kBlock) void basket_kernel(BasketArgs<T, D> a, double *__restrict__ partials)
+{
+    constexpr int NB = Normals<T>::kPerBlock;
+    constexpr int G = NB / gcd_c(D, NB);   // steps that consume whole blocks
+    constexpr int BPG = G * D / NB;        // the blocks they consume
+    constexpr int NC = D * (D + 1) / 2;
+    const MathCtx<T> m = MathCtx<T>::init();
+    const PhiloxKeys key = PhiloxKeys::make(a.seed);
+    T drift[D], coef[NC], log_w[D];
+#pragma unroll
+    for (int j = 0; j < D; ++j) drift[j] = bk_resident<D>(a.drift[j]);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) coef[c] = bk_resident<D>(a.coef[c]);
+#pragma unroll
+    for (int j = 0; j < D; ++j) log_w[j] = MONITORED ? bk_resident<D>(a.log_w[j]) : a.log_w[j];
+    const bool best = a.kind == kBasketBestOf;
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
+    const uint32_t n_groups = a.n_steps / G;
+    const uint32_t rem = a.n_steps - n_groups * G;
+    double acc4[kBasketRecord] = {0.0, 0.0, 0.0, 0.0};
+    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < a.n_local; i += stride) {
+        const uint64_t subsequence = a.path_offset + i;
+        T X[D];              // ln(S_j / S0_j) so far, in exponent units
+#pragma unroll
+        for (int j = 0; j < D; ++j) X[j] = T(0);
+        bool alive = true;   // not yet hit
+        uint32_t live = 0;   // steps this path entered not yet hit
+        uint32_t steps_run = a.n_steps;
+        Normals<T> nz;
+        // the log of the best or the worst of the weighted prices, in exponent units
+        auto extreme = [&]() {
+            T l = log_w[0] + X[0];
+#pragma unroll
+            for (int j = 1; j < D; ++j) l = best ? bk_max(l, log_w[j] + X[j]) : bk_min(l, log_w[j] + X[j]);
+            return l;
+        };
+        // steps g G .. g G + count - 1 (count <= G, wave-uniform): normals g G D .. of the stream
+        auto group = [&](uint32_t g, uint32_t count) {
+            const uint64_t first_block = static_cast<uint64_t>(g) * BPG;
+#pragma unroll
+            for (int s = 0; s < G; ++s) {
+                if (static_cast<uint32_t>(s) < count) {
+                    T x[D];
+#pragma unroll
+                    for (int j = 0; j < D; ++j) x[j] = drift[j];
+#pragma unroll
+                    for (int k = 0; k < D; ++k) {
+                        const int flat = s * D + k;   // a compile-time position once unrolled
+                        if (flat % NB == 0) nz.fill(m, key, subsequence, first_block + flat / NB);
+                        const T z = nz.z[flat % NB];
+#pragma unroll
+                        for (int j = k; j < D; ++j) x[j] = fma_t(coef[j * (j + 1) / 2 + k], z, x[j]);
+                    }
+#pragma unroll
+                    for (int j = 0; j < D; ++j) X[j] += x[j];
+                    if (MONITORED) {
+                        live += alive ? 1u : 0u;
+                        const T l = extreme();
+                        const bool hit = a.up ? (l >= a.logB) : (l <= a.logB);
+                        alive = alive && !hit;
+                    }
+                }
+            }
+        };
+        bool finished = true;
+        for (uint32_t g = 0; g < n_groups; ++g) {
+            group(g, G);
+            if (MONITORED && a.out && __builtin_amdgcn_ballot_w64(alive) == 0) {
+                steps_run = (g + 1) * G;
+                finished = false;
+                break;
+            }
+        }
+        if (rem && finished) group(n_groups, rem);
+        // the aggregate at maturity, in fp64 from path-precision values
+        double A;
+        if (a.kind == kBasketArithmetic) {
+            A = 0.0;
+#pragma unroll
+            for (int j = 0; j < D; ++j)
+                A = __builtin_fma(a.w[j], static_cast<double>(exp_of_logreturn(a.S0[j], X[j], m)), A);
+        } else {
+            T l;
+            if (a.kind == kBasketGeometric) {
+                l = a.log_w[0];
+#pragma unroll
+                for (int j = 0; j < D; ++j) l = fma_t(a.w_t[j], X[j], l);
+            } else {
+                l = extreme();
+            }
+            A = static_cast<double>(exp_of_logreturn(T(1), l, m));
+        }
+        double y = a.put ? a.K - A : A - a.K;
+        y = y > 0.0 ? y : 0.0;
+        // a knocked-out path pays 0 whatever its (possibly unfinished) prices are
+        if (MONITORED) y = (alive == (a.out != 0)) ? y : 0.0;
+        if (a.samples) a.samples[i] = static_cast<T>(y);
+        acc4[0] += y;
+        acc4[1] = __builtin_fma(y, y, acc4[1]);
+        // a wavefront's active lanes are a prefix (path ids grow with the lane): lane 0 counts the wavefront's steps
+        if ((threadIdx.x & (kWave - 1)) == 0) acc4[2] += static_cast<double>(steps_run);
+        acc4[3] += static_cast<double>(live);
+    }
+    if (a.fin.n_value >= 0.0) acc4[2] = acc4[3] = 0.0;   // the 6-double statistics layout has no slot for the counters
+    block_sumN<kBlock, kBasketRecord>(acc4);
+    grid_finish<kBlock, kBasketRecord>(acc4, partials, a.fin);
+}
+
+template <typename T, int D>
+static hipError_t launch_basket_d(const BasketJob &j, double *d_partials, uint32_t grid, const FinishSpec &fs,
+                                  hipStream_t stream)
+{
+    const double u = exponent_unit<T>();   // natural log per exponent unit
+    BasketArgs<T, D> a{};
+    for (int q = 0; q < D; ++q) {
+        a.drift[q] = static_cast<T>(j.drift[q] / u);
+        a.log_w[q] = static_cast<T>(j.log_w[q] / u);
+        a.w_t[q] = static_cast<T>(j.w[q]);
+        a.S0[q] = static_cast<T>(j.S0[q]);
+        a.w[q] = j.w[q];
+    }
+    for (int c = 0; c < D * (D + 1) / 2; ++c) a.coef[c] = static_cast<T>(j.coef[c] / u);
+    a.logB = static_cast<T>(j.logB / u);
+    a.K = j.K;
+    a.kind = j.kind;
+    a.put = j.put ? 1 : 0;
+    a.up = j.up ? 1 : 0;
+    a.out = j.out ? 1 : 0;
+    a.n_steps = j.path.n_sim;
+    a.seed = j.path.seed;
+    a.path_offset = j.path.path_offset;
+    a.n_local = j.path.n_local;
+    a.samples = static_cast<T *>(j.d_samples);
+    a.fin = GridFinish{fs.out, fs.ticket, fs.n_value};
+    const dim3 g(grid), b(kBlock);
+    if (j.monitored) hipLaunchKernelGGL((basket_kernel<T, D, true>), g, b, 0, stream, a, d_partials);
+    else hipLaunchKernelGGL((basket_kernel<T, D, false>), g, b, 0, stream, a, d_partials);
+    return hipGetLastError();
+}
+
+template <typename T>
+static hipError_t launch_basket_t(const BasketJob &j, double *d_partials, uint32_t grid, const FinishSpec &fs,
+                                  hipStream_t stream)
+{
+    switch (j.d) {
+    case 1: return launch_basket_d<T, 1>(j, d_partials, grid, fs, stream);
+    case 2: return launch_basket_d<T, 2>(j, d_partials, grid, fs, stream);
+    case 3: return launch_basket_d<T, 3>(j, d_partials, grid, fs, stream);
+    case 4: return launch_basket_d<T, 4>(j, d_partials, grid, fs, stream);
+    case 5: return launch_basket_d<T, 5>(j, d_partials, grid, fs, stream);
+    case 6: return launch_basket_d<T, 6>(j, d_partials, grid, fs, stream);
+    case 7: return launch_basket_d<T, 7>(j, d_partials, grid, fs, stream);
+    case 8: return launch_basket_d<T, 8>(j, d_partials, grid, fs, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_basket(const BasketJob &job, double *d_partials, uint32_t grid, const FinishSpec &finish,
+                         hipStream_t stream)
+{
+    if (!finish_ok(finish, grid)) return hipErrorInvalidValue;
+    if (job.monitored && job.kind != kBasketBestOf && job.kind != kBasketWorstOf) return hipErrorInvalidValue;
+    return job.path.precision == 32 ? launch_basket_t<float>(job, d_partials, grid, finish, stream)
+                               : launch_basket_t<double>(job, d_partials, grid, finish, stream);
+}
+
+}  // namespace mcamd

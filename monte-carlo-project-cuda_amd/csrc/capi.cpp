@@ -8,6 +8,7 @@
 #include "american_dual.hpp"
 #include "barrier.hpp"
 #include "lookback.hpp"
+#include "basket.hpp"
 
 #include "mcamd.h"
 
@@ -29,6 +30,7 @@ static_assert(sizeof(mcamd_american_dual) == 16 && sizeof(mcamd_american_dual_re
               "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
 static_assert(sizeof(mcamd_barrier) == 16, "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
 static_assert(sizeof(mcamd_lookback) == 16, "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
+static_assert(sizeof(mcamd_basket) == 728, "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
 
 namespace {
 
@@ -733,6 +735,138 @@ int prepare_lookback(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *s
     return drive(DeviceCall{job.path.n_local, grid, mcamd::kLookbackRecord, 6, Finish::kFolded,
                             [&](const mcamd::FinishSpec &fs) {
                                 return mcamd::launch_lookback(job, ctx->d_partials, grid, fs, ctx->stream);
+                            }});
+}
+
+// The refusals of the basket calls that depend on the assets alone (shared with the geometric closed form).  Leaves the
+// lower Cholesky factor of corr[:d, :d] in L (row-major, stride 8; entries above the diagonal 0).
+int check_basket_assets(const mcamd_basket *b, bool positive_weights, double L[64])
+{
+    const int d = b->n_assets;
+    if (d < 1 || d > MCAMD_BASKET_MAX_ASSETS)
+        return fail(MCAMD_ERR_INVALID, "n_assets must be 1..%d, got %d", MCAMD_BASKET_MAX_ASSETS, d);
+    if (b->payoff != MCAMD_PAYOFF_CALL && b->payoff != MCAMD_PAYOFF_PUT)
+        return fail(MCAMD_ERR_INVALID, "payoff must be MCAMD_PAYOFF_CALL (0) or MCAMD_PAYOFF_PUT (1), got %d", b->payoff);
+    bool any_weight = false;
+    for (int j = 0; j < d; ++j) {
+        if (!(b->S0[j] > 0.0) || !std::isfinite(b->S0[j]) || !(b->v[j] > 0.0) || !std::isfinite(b->v[j]))
+            return fail(MCAMD_ERR_INVALID, "basket assets need finite S0 > 0 and v > 0 (asset %d: S0 = %g, v = %g)", j,
+                        b->S0[j], b->v[j]);
+        if (!std::isfinite(b->w[j])) return fail(MCAMD_ERR_INVALID, "basket weight %d is not finite", j);
+        if (positive_weights && !(b->w[j] > 0.0))
+            return fail(MCAMD_ERR_INVALID, "best-of and worst-of need every weight > 0 (w[%d] = %g)", j, b->w[j]);
+        any_weight = any_weight || b->w[j] != 0.0;
+    }
+    if (!any_weight) return fail(MCAMD_ERR_INVALID, "every basket weight is 0");
+    for (int j = 0; j < d; ++j) {
+        if (b->corr[8 * j + j] != 1.0)
+            return fail(MCAMD_ERR_INVALID, "corr[%d][%d] must be exactly 1, got %g", j, j, b->corr[8 * j + j]);
+        for (int k = 0; k < j; ++k) {
+            const double rho = b->corr[8 * j + k];
+            if (rho != b->corr[8 * k + j])
+                return fail(MCAMD_ERR_INVALID, "corr must be exactly symmetric: [%d][%d] = %g, [%d][%d] = %g", j, k, rho,
+                            k, j, b->corr[8 * k + j]);
+            if (!(rho >= -1.0 && rho <= 1.0))
+                return fail(MCAMD_ERR_INVALID, "corr[%d][%d] = %g lies beyond +-1", j, k, rho);
+        }
+    }
+    std::memset(L, 0, 64 * sizeof(double));
+    for (int j = 0; j < d; ++j) {
+        for (int k = 0; k <= j; ++k) {
+            double s = b->corr[8 * j + k];
+            for (int q = 0; q < k; ++q) s -= L[8 * j + q] * L[8 * k + q];
+            if (k < j) {
+                L[8 * j + k] = s / L[8 * k + k];
+            } else {
+                if (!(s > 1e-12))
+                    return fail(MCAMD_ERR_INVALID, "corr is not positive definite: Cholesky pivot %d is %g (must exceed "
+                                                   "1e-12; a correlation of +-1 is refused: use fewer assets)", j, s);
+                L[8 * j + j] = std::sqrt(s);
+            }
+        }
+    }
+    return MCAMD_OK;
+}
+
+// The basket calls.  The kernel always finishes its own sum (one_path_per_thread_grid caps the grid); every refusal
+// that depends on the request alone comes before the context is looked at.
+template <typename Drive>
+int prepare_basket(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_basket *bk,
+                   void *d_samples, Drive drive)
+{
+    if (!opt || !sim || !bk) return fail(MCAMD_ERR_INVALID, "opt, sim and basket must be non-NULL");
+    if (bk->kind < MCAMD_BASKET_ARITHMETIC || bk->kind > MCAMD_BASKET_WORST_OF)
+        return fail(MCAMD_ERR_INVALID, "basket kind must be MCAMD_BASKET_ARITHMETIC (0) .. MCAMD_BASKET_WORST_OF (3), "
+                                       "got %d", bk->kind);
+    if (bk->barrier < MCAMD_BASKET_NO_BARRIER || bk->barrier > MCAMD_BASKET_UP_IN)
+        return fail(MCAMD_ERR_INVALID, "basket barrier must be MCAMD_BASKET_NO_BARRIER (0) .. MCAMD_BASKET_UP_IN (4), "
+                                       "got %d", bk->barrier);
+    if (bk->reserved[0] != 0 || bk->reserved[1] != 0)
+        return fail(MCAMD_ERR_INVALID, "basket->reserved must be 0, got {%d, %d}", bk->reserved[0], bk->reserved[1]);
+    const bool extreme = bk->kind == MCAMD_BASKET_BEST_OF || bk->kind == MCAMD_BASKET_WORST_OF;
+    double L[64];
+    if (int rc = check_basket_assets(bk, extreme, L)) return rc;
+    if (!std::isfinite(opt->K) || !(opt->K >= 0.0))
+        return fail(MCAMD_ERR_INVALID, "a basket option needs a finite K >= 0, got %g", opt->K);
+    const int d = bk->n_assets;
+    const bool monitored = bk->barrier != MCAMD_BASKET_NO_BARRIER;
+    const bool up = bk->barrier == MCAMD_BASKET_UP_OUT || bk->barrier == MCAMD_BASKET_UP_IN;
+    if (monitored) {
+        if (!extreme)
+            return fail(MCAMD_ERR_INVALID, "a basket barrier needs MCAMD_BASKET_BEST_OF or MCAMD_BASKET_WORST_OF, got "
+                                           "kind %d", bk->kind);
+        if (!(opt->B > 0.0) || !std::isfinite(opt->B))
+            return fail(MCAMD_ERR_INVALID, "the barrier level B must be positive, got %g", opt->B);
+        double A0 = bk->w[0] * bk->S0[0];
+        for (int j = 1; j < d; ++j)
+            A0 = bk->kind == MCAMD_BASKET_BEST_OF ? std::fmax(A0, bk->w[j] * bk->S0[j]) : std::fmin(A0, bk->w[j] * bk->S0[j]);
+        if (!std::isfinite(A0) || !(up ? A0 < opt->B : A0 > opt->B))
+            return fail(MCAMD_ERR_INVALID, "the aggregate must start strictly on the live side of the barrier: %s "
+                                           "(A_0 = %g, B = %g)", up ? "an up-barrier needs A_0 < B" : "a down-barrier needs A_0 > B",
+                        A0, opt->B);
+    }
+    // what the option itself contributes is r, T, K and B: the spot-start rules and those of mcamd_price_paths see the
+    // first asset in the place of opt->S0 and opt->v, which are ignored
+    mcamd_option seen = *opt;
+    seen.S0 = bk->S0[0];
+    seen.v = bk->v[0];
+    if (!monitored) seen.B = 0.0;
+    if (int rc = check_spot_start("basket", false, &seen, sim)) return rc;
+    for (int j = 0; j < d; ++j) {   // the fp64 exponent range, asset by asset: |x_j| <= |drift_j| + v_j sqrt(dt) sqrt(d) max_k |z_k|
+                                    // (a row of L has unit length)
+        seen.v = bk->v[j] * std::sqrt(static_cast<double>(d));
+        if (int rc = check_request(&seen, sim)) return rc;
+        seen.v = bk->v[j];
+        if (int rc = check_request(&seen, sim)) return rc;
+    }
+    if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
+    if (sim->n_paths_local == 0) return drive(empty_call());
+    mcamd::BasketJob job{};
+    job.path = make_plain_job(&seen, sim, false, true);
+    job.d = d;
+    job.kind = bk->kind;
+    job.put = bk->payoff == MCAMD_PAYOFF_PUT;
+    job.monitored = monitored;
+    job.up = up;
+    job.out = bk->barrier == MCAMD_BASKET_DOWN_OUT || bk->barrier == MCAMD_BASKET_UP_OUT;
+    const double dt = opt->T / static_cast<double>(sim->n_steps), sqdt = std::sqrt(dt);
+    double log_sum = 0.0;
+    for (int j = 0; j < d; ++j) {
+        job.drift[j] = (opt->r - 0.5 * bk->v[j] * bk->v[j]) * dt;
+        for (int k = 0; k <= j; ++k) job.coef[j * (j + 1) / 2 + k] = bk->v[j] * sqdt * L[8 * j + k];
+        job.S0[j] = bk->S0[j];
+        job.w[j] = bk->w[j];
+        job.log_w[j] = extreme ? std::log(bk->w[j] * bk->S0[j]) : 0.0;
+        log_sum += bk->w[j] * std::log(bk->S0[j]);
+    }
+    if (bk->kind == MCAMD_BASKET_GEOMETRIC) job.log_w[0] = log_sum;
+    job.K = opt->K;
+    job.logB = monitored ? std::log(opt->B) : 0.0;
+    job.d_samples = d_samples;
+    const uint32_t grid = mcamd::one_path_per_thread_grid(job.path.n_local);
+    return drive(DeviceCall{job.path.n_local, grid, mcamd::kBasketRecord, 6, Finish::kFolded,
+                            [&](const mcamd::FinishSpec &fs) {
+                                return mcamd::launch_basket(job, ctx->d_partials, grid, fs, ctx->stream);
                             }});
 }
 
@@ -1566,6 +1700,75 @@ int mcamd_lookback_price_f64(double S0, double K, double T, double r, double v, 
         if (K < S0) *price = K * D * N(-d + s) - S0 * N(-d) + S0 * D * lam * (pw * N(-d + shift) - G * N(-d));
         else *price = floating(false) + K * D - S0;
     }
+    return MCAMD_OK;
+}
+
+int mcamd_price_basket(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_basket *basket,
+                       void *d_samples, mcamd_result *res)
+{
+    if (!res) return fail(MCAMD_ERR_INVALID, "opt, sim, basket and res must be non-NULL");
+    zero_result(res);
+    return prepare_basket(ctx, opt, sim, basket, d_samples, [&](const auto &call) {
+        return run_sync(ctx, call, res, [&](const double *rec) {
+            finalize_counted_into(rec, sim->n_paths_local, opt->r, opt->T, res);
+        });
+    });
+}
+
+int mcamd_price_basket_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                               const mcamd_basket *basket, void *d_samples, double *d_stats)
+{
+    return prepare_basket(ctx, opt, sim, basket, d_samples,
+                          [&](const auto &call) { return run_enqueue(ctx, call, d_stats); });
+}
+
+// The geometric basket is a lognormal: ln A_T ~ N(m, s^2), m = sum_j w_j (ln S0_j + (r - v_j^2/2) T),
+// s^2 = T w'(v o corr o v) w.
+int mcamd_basket_geometric_price_f64(const mcamd_basket *basket, double K, double T, double r, double *price)
+{
+    if (!price) return fail(MCAMD_ERR_INVALID, "price is NULL");
+    *price = 0.0;
+    if (!basket) return fail(MCAMD_ERR_INVALID, "basket is NULL");
+    double L[64];
+    if (int rc = check_basket_assets(basket, false, L)) return rc;
+    if (!std::isfinite(K) || !(K >= 0.0)) return fail(MCAMD_ERR_INVALID, "a basket option needs a finite K >= 0, got %g", K);
+    if (!(T > 0.0) || !std::isfinite(T) || !std::isfinite(r))
+        return fail(MCAMD_ERR_INVALID, "the geometric closed form needs a finite T > 0 and a finite r");
+    const int d = basket->n_assets;
+    double mean = 0.0, var = 0.0;
+    for (int j = 0; j < d; ++j) {
+        mean += basket->w[j] * (std::log(basket->S0[j]) + (r - 0.5 * basket->v[j] * basket->v[j]) * T);
+        for (int k = 0; k < d; ++k)
+            var += basket->w[j] * basket->v[j] * basket->corr[8 * j + k] * basket->v[k] * basket->w[k];
+    }
+    var *= T;
+    const double s = std::sqrt(var > 0.0 ? var : 0.0), D = std::exp(-r * T), F = std::exp(mean + 0.5 * var);
+    const bool put = basket->payoff == MCAMD_PAYOFF_PUT;
+    const auto N = [](double x) { return 0.5 * std::erfc(-x / std::sqrt(2.0)); };
+    if (K == 0.0 || !(s > 0.0)) {   // a forward: A_T > 0 = K always, or A_T is not random (weights that cancel)
+        const double fwd = K == 0.0 ? F : std::exp(mean);
+        *price = D * std::fmax(put ? K - fwd : fwd - K, 0.0);
+        return MCAMD_OK;
+    }
+    const double d1 = (mean - std::log(K)) / s + s, d2 = d1 - s;
+    *price = put ? D * (K * N(-d2) - F * N(-d1)) : D * (F * N(d1) - K * N(d2));
+    return MCAMD_OK;
+}
+
+// Margrabe (1978): the option to exchange b S2 for a S1.
+int mcamd_exchange_price_f64(double a_S1, double b_S2, double T, double v1, double v2, double rho, double *price)
+{
+    if (!price) return fail(MCAMD_ERR_INVALID, "price is NULL");
+    *price = 0.0;
+    if (!(a_S1 > 0.0) || !(b_S2 > 0.0) || !(T > 0.0) || !(v1 > 0.0) || !(v2 > 0.0) || !std::isfinite(a_S1) ||
+        !std::isfinite(b_S2) || !std::isfinite(T) || !std::isfinite(v1) || !std::isfinite(v2))
+        return fail(MCAMD_ERR_INVALID, "the exchange closed form needs finite a S1, b S2, T, v1, v2 > 0");
+    if (!(rho > -1.0 && rho < 1.0))
+        return fail(MCAMD_ERR_INVALID, "the exchange closed form needs -1 < rho < 1, got %g", rho);
+    const double s = std::sqrt((v1 * v1 + v2 * v2 - 2.0 * rho * v1 * v2) * T);
+    const auto N = [](double x) { return 0.5 * std::erfc(-x / std::sqrt(2.0)); };
+    const double d1 = std::log(a_S1 / b_S2) / s + 0.5 * s;
+    *price = a_S1 * N(d1) - b_S2 * N(d1 - s);
     return MCAMD_OK;
 }
 
