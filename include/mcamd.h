@@ -785,6 +785,81 @@ int mcamd_basket_geometric_price_f64(const mcamd_basket *basket, double K, doubl
  * strictly inside (-1, 1). */
 int mcamd_exchange_price_f64(double a_S1, double b_S2, double T, double v1, double v2, double rho, double *price);
 
+/* ---- Asian (average-rate) options: arithmetic or geometric average, fixed or floating strike, call or put ----
+ * Additive to ABI version 5: first carried by the build that ships csrc/asian.hip (no struct of an earlier call
+ * changed, so MCAMD_ABI_VERSION stays 5; a caller finds out with dlsym).
+ * Notation of mcamd_price_lookback: dt = T / n_steps; x_i is the exponent of step i, (r - v^2/2) dt + v sqrt(dt) z_i
+ * with z_i the path's normals (Philox subsequence = the GLOBAL path id, blocks 0, 1, ...; the exponents are the ones
+ * mcamd_price_paths steps with); X_0 = 0, X_i = X_{i-1} + x_i in the path precision.  The averaging dates are the step
+ * ends i = 1..n and, with include_spot, t = 0: m = n + include_spot dates.
+ *   MCAMD_ASIAN_ARITHMETIC  prices in the product form of the trajectory-store kernel: P_0 = S0, P_i = P_{i-1} e^{x_i},
+ *       so P_i is bit for bit what mcamd_simulate_trajectories stores for that path.  Their sum is accumulated in fp64
+ *       in ascending i from S0 (include_spot) or 0; A = sum / m in fp64; S_T = P_n.
+ *   MCAMD_ASIAN_GEOMETRIC   L = sum_{i=1..n} X_i, accumulated in the path precision in ascending i (the spot
+ *       contributes 0); G = S0 e^{L (1/m)} with 1/m narrowed once on the host, and S_T = S0 e^{X_n}, both through the
+ *       exponential that ends a log-space path of mcamd_price_paths.  A floating-strike job with n = 1 and no spot
+ *       therefore pays exactly 0.  No exponential is taken inside the step loop.
+ *   Sample, formed once per path in fp64 (G in place of A for the geometric average):
+ *       MCAMD_ASIAN_FIXED     call  y = (A - K)+      put  y = (K - A)+      (average price)
+ *       MCAMD_ASIAN_FLOATING  call  y = (S_T - A)+    put  y = (A - S_T)+    (average strike; opt->K is ignored)
+ *   price = exp(-rT) mean(y), std_err as in mcamd_finalize.
+ *   MCAMD_ASIAN_CONTROL_GEOMETRIC (arithmetic jobs only): the kernel carries L beside the prices and forms g, the
+ *       geometric sample of the same strike, payoff and include_spot exactly as the geometric job forms it in fp64;
+ *       c = g - mu_g with mu_g = e^{rT} mcamd_asian_geometric_price_f64(...) computed on the host in fp64.  The call
+ *       returns sum, sumsq, sum_c, sum_cc, sum_yc and finalizes as mcamd_finalize_cv does (cv_beta and cv_rho are
+ *       filled).  The two payoffs correlate at 0.999 and more for usual inputs, which shrinks the standard error
+ *       25 to 40 times.
+ * The exponents are the exact law of geometric Brownian motion at the step ends, so the discrete average is sampled
+ * without bias at every n_steps (n_steps = 1 included).
+ * d_samples (nullable, device): n_paths_local values of the path precision; [local path] receives y, never the
+ * control-adjusted value.
+ * res: sum / sumsq / n / price / std_err / ci_*, kernel_ms / total_ms / grid / block; with the control also sum_c /
+ * sum_cc / sum_yc / cv_beta / cv_rho; work_steps = 64 x the steps each wavefront ran (there is no early exit),
+ * live_steps = 0; the other fields are 0.
+ * The enqueue form leaves {sum y, sum y^2, sum c, sum c^2, sum y c, n} in d_stats (device, >= 6 doubles; the three
+ * middle entries are 0 without the control): mcamd_finalize_stats (control_variate = 1 for a controlled job) and one
+ * all-reduce of 6 doubles serve it unchanged, and mcamd_enqueued_kernel_ms covers it.
+ * Requirements (MCAMD_ERR_INVALID before any device work and before the context is looked at): opt, sim, asian, res
+ * non-NULL; average, strike, payoff, include_spot, control in range; reserved == 0; no control on a geometric job;
+ * fixed strike: K finite and positive; use_window, P1, P2, Ik, Sk, Tk and opt->dt all 0; v > 0; sim->flags 0 or
+ * MCAMD_FLAG_LOG_SPACE; and what mcamd_price_paths refuses on sim (a controlled job also needs S0 > 0, for mu_g).
+ * opt->B is ignored.  An empty shard returns zeros and launches nothing; its enqueue form writes a zero record in
+ * stream order.
+ * There is no mcamd_group_* form and no shim name: the reference has no such product.  Multi-GPU: every rank prices
+ * its shard (a path's sample depends on its global id alone); the 6-double records add.  New. */
+#define MCAMD_ASIAN_ARITHMETIC 0
+#define MCAMD_ASIAN_GEOMETRIC 1
+#define MCAMD_ASIAN_FIXED 0      /* average price:  call (A - K)+,   put (K - A)+ */
+#define MCAMD_ASIAN_FLOATING 1   /* average strike: call (S_T - A)+, put (A - S_T)+; opt->K ignored */
+#define MCAMD_ASIAN_CONTROL_NONE 0
+#define MCAMD_ASIAN_CONTROL_GEOMETRIC 1   /* arithmetic jobs only */
+
+typedef struct mcamd_asian {
+    int32_t average;       /* MCAMD_ASIAN_ARITHMETIC / MCAMD_ASIAN_GEOMETRIC */
+    int32_t strike;        /* MCAMD_ASIAN_FIXED / MCAMD_ASIAN_FLOATING */
+    int32_t payoff;        /* MCAMD_PAYOFF_* */
+    int32_t include_spot;  /* 0 / 1: t = 0 is an averaging date */
+    int32_t control;       /* MCAMD_ASIAN_CONTROL_* */
+    int32_t reserved;      /* must be 0 */
+} mcamd_asian;
+
+int mcamd_price_asian(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_asian *asian,
+                      void *d_samples, mcamd_result *res);
+int mcamd_price_asian_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_asian *asian,
+                              void *d_samples, double *d_stats);
+/* Host closed form of the DISCRETE geometric average of the definitions above (a lognormal at every n_steps), no
+ * dividends.  With mu = r - v^2/2:  M = ln S0 + mu dt n(n+1) / (2m),  s^2 = v^2 dt n(n+1)(2n+1) / (6 m^2);
+ *   fixed call    e^{-rT} (e^{M + s^2/2} N(d1) - K N(d1 - s)),  d1 = (M - ln K) / s + s;
+ *   floating call e^{-rT} (F1 N(d1) - F2 N(d1 - s_f)),  F1 = S0 e^{rT},  F2 = e^{M + s^2/2},
+ *                 s_f^2 = v^2 T + s^2 - v^2 dt n(n+1) / m,  d1 = (ln(F1 / F2) + s_f^2 / 2) / s_f;  0 where s_f^2 <= 0
+ *                 (n = 1 without the spot: the average is S_T itself);
+ *   puts by parity: call - e^{-rT} (F2 - K), and call - e^{-rT} (F1 - F2).
+ * N is the erfc form of mcamd_bs_call_f64.  K is ignored for MCAMD_ASIAN_FLOATING.  MCAMD_ERR_INVALID for a bad enum
+ * or include_spot, n_steps == 0, a non-positive or non-finite S0, T or v (and K for a fixed strike) and a non-finite
+ * r. */
+int mcamd_asian_geometric_price_f64(double S0, double K, double T, double r, double v, uint32_t n_steps,
+                                    int include_spot, int strike, int payoff, double *price);
+
 /* Host: discount + mean + standard error + 95% CI from (sum, sumsq, n) — after an all-reduce
  * over shards, or directly.  Fills price/std_err/ci_* (and copies sum/sumsq/n) in *res. */
 int mcamd_finalize(double sum, double sumsq, uint64_t n, double r, double T, mcamd_result *res);

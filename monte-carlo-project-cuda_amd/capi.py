@@ -27,6 +27,9 @@ PAYOFF_CALL, PAYOFF_PUT = 0, 1
 BARRIER_DOWN_OUT, BARRIER_DOWN_IN, BARRIER_UP_OUT, BARRIER_UP_IN = 0, 1, 2, 3
 MONITOR_DISCRETE, MONITOR_CONTINUOUS = 0, 1
 LOOKBACK_FLOATING, LOOKBACK_FIXED = 0, 1
+ASIAN_ARITHMETIC, ASIAN_GEOMETRIC = 0, 1
+ASIAN_FIXED, ASIAN_FLOATING = 0, 1
+ASIAN_CONTROL_NONE, ASIAN_CONTROL_GEOMETRIC = 0, 1
 BASKET_MAX_ASSETS = 8
 BASKET_ARITHMETIC, BASKET_GEOMETRIC, BASKET_BEST_OF, BASKET_WORST_OF = 0, 1, 2, 3
 BASKET_NO_BARRIER, BASKET_DOWN_OUT, BASKET_DOWN_IN, BASKET_UP_OUT, BASKET_UP_IN = 0, 1, 2, 3, 4
@@ -48,6 +51,7 @@ EXPORTS = [
     "mcamd_price_barrier", "mcamd_price_barrier_enqueue", "mcamd_barrier_price_f64",
     "mcamd_price_lookback", "mcamd_price_lookback_enqueue", "mcamd_lookback_price_f64",
     "mcamd_price_basket", "mcamd_price_basket_enqueue", "mcamd_basket_geometric_price_f64", "mcamd_exchange_price_f64",
+    "mcamd_price_asian", "mcamd_price_asian_enqueue", "mcamd_asian_geometric_price_f64",
 ]
 
 
@@ -138,6 +142,13 @@ class Basket(C.Structure):
     _fields_ = [("n_assets", C.c_int32), ("kind", C.c_int32), ("payoff", C.c_int32), ("barrier", C.c_int32),
                 ("reserved", C.c_int32 * 2), ("S0", C.c_double * 8), ("v", C.c_double * 8), ("w", C.c_double * 8),
                 ("corr", C.c_double * 64)]
+
+
+class Asian(C.Structure):
+    """mcamd_asian: which average mcamd_price_asian takes, over which dates, against which strike, and whether the
+    geometric average serves as control variate."""
+    _fields_ = [("average", C.c_int32), ("strike", C.c_int32), ("payoff", C.c_int32), ("include_spot", C.c_int32),
+                ("control", C.c_int32), ("reserved", C.c_int32)]
 
 
 class DeviceInfo(C.Structure):
@@ -239,6 +250,9 @@ def load() -> C.CDLL:
     L.mcamd_price_basket_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Basket), vp, vp]
     L.mcamd_basket_geometric_price_f64.argtypes = [C.POINTER(Basket), f64, f64, f64, C.POINTER(f64)]
     L.mcamd_exchange_price_f64.argtypes = [f64, f64, f64, f64, f64, f64, C.POINTER(f64)]
+    L.mcamd_price_asian.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Asian), vp, C.POINTER(Result)]
+    L.mcamd_price_asian_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Asian), vp, vp]
+    L.mcamd_asian_geometric_price_f64.argtypes = [f64, f64, f64, f64, f64, C.c_uint32, i32, i32, i32, C.POINTER(f64)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("mcamd_abi_version",):
@@ -331,6 +345,18 @@ def exchange_price_f64(a_S1, b_S2, T, v1, v2, rho) -> float:
     """Margrabe's closed form of (a S1 - b S2)+, with a_S1 = a S1(0) and b_S2 = b S2(0)"""
     p = C.c_double(0)
     _check(load().mcamd_exchange_price_f64(a_S1, b_S2, T, v1, v2, rho, C.byref(p)))
+    return p.value
+
+
+def make_asian(average=ASIAN_ARITHMETIC, strike=ASIAN_FIXED, payoff=PAYOFF_CALL, include_spot=0,
+               control=ASIAN_CONTROL_NONE) -> Asian:
+    return Asian(average, strike, payoff, include_spot, control, 0)
+
+
+def asian_geometric_price_f64(S0, K, T, r, sigma, n_steps, include_spot=0, strike=ASIAN_FIXED, payoff=PAYOFF_CALL) -> float:
+    """closed form of the discrete geometric-average option over the n_steps step ends (and t = 0 with include_spot)"""
+    p = C.c_double(0)
+    _check(load().mcamd_asian_geometric_price_f64(S0, K, T, r, sigma, n_steps, include_spot, strike, payoff, C.byref(p)))
     return p.value
 
 
@@ -487,6 +513,20 @@ class Context:
         """Asynchronous: leaves {sum, sumsq, 0, 0, 0, n} in the device tensor `stats` (>= 6 doubles; finalize_stats)."""
         _check(self._L.mcamd_price_lookback_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(lookback),
                                                     _ptr(samples), _ptr(stats)))
+
+    def price_asian(self, opt: Option, sim: Sim, asian: Asian, samples=None) -> Result:
+        """Asian option (mcamd_price_asian).  samples: optional device tensor of n_paths_local values of the path
+        precision; receives the undiscounted sample of every path (never the control-adjusted value)."""
+        res = Result()
+        _check(self._L.mcamd_price_asian(self._h, C.byref(opt), C.byref(sim), C.byref(asian), _ptr(samples),
+                                         C.byref(res)))
+        return res
+
+    def price_asian_enqueue(self, opt: Option, sim: Sim, asian: Asian, stats, samples=None) -> None:
+        """Asynchronous: leaves {sum y, sum y^2, sum c, sum c^2, sum y c, n} in the device tensor `stats` (>= 6 doubles;
+        finalize_stats, with control_variate=True for a controlled job)."""
+        _check(self._L.mcamd_price_asian_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(asian), _ptr(samples),
+                                                 _ptr(stats)))
 
     def price_basket(self, opt: Option, sim: Sim, basket: Basket, samples=None) -> Result:
         """Basket, spread or rainbow option on correlated assets (mcamd_price_basket): r, T, K and the barrier level B

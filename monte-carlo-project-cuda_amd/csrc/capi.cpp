@@ -9,6 +9,7 @@
 #include "barrier.hpp"
 #include "lookback.hpp"
 #include "basket.hpp"
+#include "asian.hpp"
 
 #include "mcamd.h"
 
@@ -31,6 +32,7 @@ static_assert(sizeof(mcamd_american_dual) == 16 && sizeof(mcamd_american_dual_re
 static_assert(sizeof(mcamd_barrier) == 16, "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
 static_assert(sizeof(mcamd_lookback) == 16, "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
 static_assert(sizeof(mcamd_basket) == 728, "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
+static_assert(sizeof(mcamd_asian) == 24, "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
 
 namespace {
 
@@ -735,6 +737,110 @@ int prepare_lookback(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *s
     return drive(DeviceCall{job.path.n_local, grid, mcamd::kLookbackRecord, 6, Finish::kFolded,
                             [&](const mcamd::FinishSpec &fs) {
                                 return mcamd::launch_lookback(job, ctx->d_partials, grid, fs, ctx->stream);
+                            }});
+}
+
+// The refusals of the Asian calls that depend on the product alone (shared with the closed form).
+int check_asian_kind(double K, int strike, int payoff, int include_spot)
+{
+    if (strike != MCAMD_ASIAN_FIXED && strike != MCAMD_ASIAN_FLOATING)
+        return fail(MCAMD_ERR_INVALID, "strike must be MCAMD_ASIAN_FIXED (0) or MCAMD_ASIAN_FLOATING (1), got %d", strike);
+    if (payoff != MCAMD_PAYOFF_CALL && payoff != MCAMD_PAYOFF_PUT)
+        return fail(MCAMD_ERR_INVALID, "payoff must be MCAMD_PAYOFF_CALL (0) or MCAMD_PAYOFF_PUT (1), got %d", payoff);
+    if (include_spot != 0 && include_spot != 1)
+        return fail(MCAMD_ERR_INVALID, "include_spot must be 0 or 1, got %d", include_spot);
+    if (strike == MCAMD_ASIAN_FIXED && (!(K > 0.0) || !std::isfinite(K)))
+        return fail(MCAMD_ERR_INVALID, "a fixed-strike Asian option needs a finite K > 0, got %g", K);
+    return MCAMD_OK;
+}
+
+// The discrete geometric average of geometric Brownian motion over the step ends i = 1..n (and t = 0 with
+// include_spot; m dates in all) is lognormal: ln G ~ N(M, s^2) with M = ln S0 + mu dt n(n+1) / (2m) and
+// s^2 = v^2 dt n(n+1)(2n+1) / (6 m^2), mu = r - v^2/2.  The floating strike exchanges G for S_T, two lognormals with
+// covariance v^2 dt n(n+1) / (2m) of their logarithms (Margrabe's form on the forwards).
+int asian_geometric_price(double S0, double K, double T, double r, double v, uint32_t n_steps, int include_spot,
+                          int strike, int payoff, double *price)
+{
+    *price = 0.0;
+    if (!(S0 > 0.0) || !(T > 0.0) || !(v > 0.0) || !std::isfinite(S0) || !std::isfinite(T) || !std::isfinite(r) ||
+        !std::isfinite(v))
+        return fail(MCAMD_ERR_INVALID, "the geometric Asian closed form needs finite S0, T, v > 0 and a finite r");
+    if (n_steps == 0) return fail(MCAMD_ERR_INVALID, "n_steps must be >= 1");
+    if (int rc = check_asian_kind(K, strike, payoff, include_spot)) return rc;
+    const double n = static_cast<double>(n_steps), m = n + include_spot, dt = T / n;
+    const double mu = r - 0.5 * v * v, D = std::exp(-r * T);
+    const double M = std::log(S0) + mu * dt * n * (n + 1.0) / (2.0 * m);
+    const double s2 = v * v * dt * n * (n + 1.0) * (2.0 * n + 1.0) / (6.0 * m * m);
+    const double F = std::exp(M + 0.5 * s2);   // E[G]
+    const auto N = [](double x) { return 0.5 * std::erfc(-x / std::sqrt(2.0)); };
+    const bool put = payoff == MCAMD_PAYOFF_PUT;
+    if (strike == MCAMD_ASIAN_FIXED) {
+        const double s = std::sqrt(s2);
+        const double d1 = (M - std::log(K)) / s + s;
+        const double call = D * (F * N(d1) - K * N(d1 - s));
+        *price = put ? call - D * (F - K) : call;
+        return MCAMD_OK;
+    }
+    const double sf2 = v * v * T + s2 - v * v * dt * n * (n + 1.0) / m;
+    // one step without the spot: the average IS S_T, and the option pays nothing
+    if ((n_steps == 1 && !include_spot) || !(sf2 > 0.0)) return MCAMD_OK;
+    const double F1 = S0 * std::exp(r * T), sf = std::sqrt(sf2);
+    const double d1 = (std::log(F1 / F) + 0.5 * sf2) / sf;
+    const double call = D * (F1 * N(d1) - F * N(d1 - sf));
+    *price = put ? call - D * (F1 - F) : call;
+    return MCAMD_OK;
+}
+
+// The Asian calls.  The kernel always finishes its own sum (one_path_per_thread_grid caps the grid); every refusal
+// that depends on the request alone comes before the context is looked at.
+template <typename Drive>
+int prepare_asian(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_asian *as, void *d_samples,
+                  Drive drive)
+{
+    if (!opt || !sim || !as) return fail(MCAMD_ERR_INVALID, "opt, sim and asian must be non-NULL");
+    if (as->average != MCAMD_ASIAN_ARITHMETIC && as->average != MCAMD_ASIAN_GEOMETRIC)
+        return fail(MCAMD_ERR_INVALID, "average must be MCAMD_ASIAN_ARITHMETIC (0) or MCAMD_ASIAN_GEOMETRIC (1), got %d",
+                    as->average);
+    if (as->control != MCAMD_ASIAN_CONTROL_NONE && as->control != MCAMD_ASIAN_CONTROL_GEOMETRIC)
+        return fail(MCAMD_ERR_INVALID, "control must be MCAMD_ASIAN_CONTROL_NONE (0) or MCAMD_ASIAN_CONTROL_GEOMETRIC "
+                                       "(1), got %d", as->control);
+    if (as->reserved != 0) return fail(MCAMD_ERR_INVALID, "asian->reserved must be 0, got %d", as->reserved);
+    if (int rc = check_asian_kind(opt->K, as->strike, as->payoff, as->include_spot)) return rc;
+    const bool arithmetic = as->average == MCAMD_ASIAN_ARITHMETIC;
+    const bool control = as->control == MCAMD_ASIAN_CONTROL_GEOMETRIC;
+    if (control && !arithmetic)
+        return fail(MCAMD_ERR_INVALID, "the geometric control variate serves arithmetic jobs only: a geometric job takes "
+                                       "control = MCAMD_ASIAN_CONTROL_NONE");
+    if (int rc = check_spot_start("Asian", false, opt, sim)) return rc;
+    const bool floating = as->strike == MCAMD_ASIAN_FLOATING;
+    mcamd_option seen = *opt;   // a floating strike ignores K, and every Asian option ignores B
+    if (floating) seen.K = 0.0;
+    seen.B = 0.0;
+    if (int rc = check_request(&seen, sim)) return rc;
+    double control_mean = 0.0;
+    if (control) {
+        double geo;
+        if (int rc = asian_geometric_price(opt->S0, seen.K, opt->T, opt->r, opt->v, sim->n_steps, as->include_spot,
+                                           as->strike, as->payoff, &geo))
+            return rc;
+        control_mean = std::exp(opt->r * opt->T) * geo;
+    }
+    if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
+    if (sim->n_paths_local == 0) return drive(empty_call());
+    mcamd::AsianJob job;
+    job.path = make_plain_job(&seen, sim, false, true);
+    job.arithmetic = arithmetic;
+    job.control = control;
+    job.floating = floating;
+    job.put = as->payoff == MCAMD_PAYOFF_PUT;
+    job.include_spot = as->include_spot != 0;
+    job.K = seen.K;
+    job.control_mean = control_mean;
+    job.d_samples = d_samples;
+    const uint32_t grid = mcamd::one_path_per_thread_grid(job.path.n_local);
+    return drive(DeviceCall{job.path.n_local, grid, mcamd::kAsianRecord, 6, Finish::kFolded,
+                            [&](const mcamd::FinishSpec &fs) {
+                                return mcamd::launch_asian(job, ctx->d_partials, grid, fs, ctx->stream);
                             }});
 }
 
@@ -1770,6 +1876,34 @@ int mcamd_exchange_price_f64(double a_S1, double b_S2, double T, double v1, doub
     const double d1 = std::log(a_S1 / b_S2) / s + 0.5 * s;
     *price = a_S1 * N(d1) - b_S2 * N(d1 - s);
     return MCAMD_OK;
+}
+
+int mcamd_price_asian(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_asian *asian,
+                      void *d_samples, mcamd_result *res)
+{
+    if (!res) return fail(MCAMD_ERR_INVALID, "opt, sim, asian and res must be non-NULL");
+    zero_result(res);
+    return prepare_asian(ctx, opt, sim, asian, d_samples, [&](const auto &call) {
+        return run_sync(ctx, call, res, [&](const double *rec) {
+            // {sum y, sum y^2, sum c, sum c^2, sum y c, wave-steps}
+            finalize_record(rec, asian->control == MCAMD_ASIAN_CONTROL_GEOMETRIC, sim->n_paths_local, opt->r, opt->T, res);
+            res->work_steps = 64.0 * rec[mcamd::kAsianRecord - 1];   // wave-steps x 64 lanes
+        });
+    });
+}
+
+int mcamd_price_asian_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_asian *asian,
+                              void *d_samples, double *d_stats)
+{
+    return prepare_asian(ctx, opt, sim, asian, d_samples,
+                         [&](const auto &call) { return run_enqueue(ctx, call, d_stats); });
+}
+
+int mcamd_asian_geometric_price_f64(double S0, double K, double T, double r, double v, uint32_t n_steps,
+                                    int include_spot, int strike, int payoff, double *price)
+{
+    if (!price) return fail(MCAMD_ERR_INVALID, "price is NULL");
+    return asian_geometric_price(S0, K, T, r, v, n_steps, include_spot, strike, payoff, price);
 }
 
 int mcamd_finalize(double sum, double sumsq, uint64_t n, double r, double T, mcamd_result *res)
