@@ -16,6 +16,8 @@ import math
 
 import numpy as np
 
+from deep_inputs import DEEP, SHALLOW
+
 ARITHMETIC, GEOMETRIC, BEST_OF, WORST_OF = 0, 1, 2, 3
 KINDS = (ARITHMETIC, GEOMETRIC, BEST_OF, WORST_OF)
 CALL, PUT = 0, 1
@@ -166,16 +168,22 @@ def geometric_lognormal(S0, v, w, corr, K, T, r, put):
 R, T_ = 0.05, 1.0
 N_JOB, OFFSET, N_LOCAL, SEED = 20_000, 5003, 4096, 77
 DS, STEPS = (1, 2, 3, 5, 8), (1, 2, 7, 50)
+# The widths DS leaves out.  In fp32 d = 6 is the only width whose group is 2 steps of 3 blocks and d = 7 the only one of
+# 4 steps of 7 blocks; d = 6 and 7 are also the widths with the most coefficients held in registers.
+MORE_DS = (4, 6, 7)
+assert SHALLOW == (SEED, OFFSET, N_JOB)   # (seed, first path, paths of the job); DEEP: tests/deep_inputs.py
+DEEP_STEPS = 7                            # the step count of every case on the DEEP inputs
 # A path whose restated min_i |ln A_i - ln B| is below MARGIN is left out of the elementwise comparison of a barrier
 # case, and a case may leave out at most CAP of its paths: both are those of tests/test_gpu_barrier.py.
 MARGIN, CAP = 2e-5, 0.01
 # B = 0.8 for the down barriers.  An up barrier needs A_0 < B, and A_0 = 1 here (w_j = 1 / S0_j): it takes the mirror
 # image 1 / 0.8.
 LEVEL = {DOWN_OUT: 0.8, DOWN_IN: 0.8, UP_OUT: 1.25, UP_IN: 1.25}
-# Largest elementwise difference between two restatements over every case of test 1 of tests/test_gpu_basket.py
-# (float64 against longdouble for the fp64 kernels, float32 against float64 for the fp32 kernels; margin paths of the
-# barrier cases left out), measured by tests/test_basket_cpu.py on an x86-64 CPU (80-bit longdouble) and recorded in
-# DESIGN section 15.  The test there fails if a measurement exceeds its record.
+# Largest elementwise difference between two restatements over the 480 cases of test 1 of tests/test_gpu_basket.py on
+# d in DS (float64 against longdouble for the fp64 kernels, float32 against float64 for the fp32 kernels; margin paths
+# of the barrier cases left out), measured by tests/test_basket_cpu.py on an x86-64 CPU (80-bit longdouble) and recorded
+# in DESIGN section 15.  The test there fails if a measurement exceeds its record.  The other cases of test 1
+# (MORE_CASES, DEEP_CASES) are measured there too and stay below it: they take the same tolerance.
 SPREAD = {F64: 4.1e-13, F32: 2.3e-4}
 
 
@@ -227,16 +235,17 @@ def stream(prec, seed=SEED, first=OFFSET, n=N_LOCAL, n_normals=max(DS) * max(STE
 _restated = {}
 
 
-def compare(prec, kind, payoff, barrier, d, n_steps):
+def compare(prec, kind, payoff, barrier, d, n_steps, where=SHALLOW):
     """The restatement of one case of the GPU test's elementwise comparison on its inputs, CPU only: (samples to compare
     with as float64, the restatement in the kernel's precision, paths kept, largest difference between the two
     restatements over the kept paths).  An fp64 kernel is compared with the float64 restatement and an fp32 kernel
-    with the float64 one too."""
-    key = (prec, kind, payoff, barrier, d, n_steps)
+    with the float64 one too.  where: SHALLOW or DEEP, the seed and the first path the normals are drawn for."""
+    key = (prec, kind, payoff, barrier, d, n_steps, where)
     if key not in _restated:
         S0, v, corr = inputs(d)
         w, K = weights(kind, d)
-        z = stream(prec)
+        # the deep cases all have DEEP_STEPS steps: no more of the stream is drawn than they read
+        z = stream(prec) if where == SHALLOW else stream(prec, where[0], where[1], n_normals=max(DS) * DEEP_STEPS)
         B = LEVEL.get(barrier, 0.0)
         own = samples(z, n_steps, S0, v, w, corr, K, T_, R, kind, payoff, barrier, B, NP_T[prec])
         other = samples(z, n_steps, S0, v, w, corr, K, T_, R, kind, payoff, barrier, B,
@@ -248,6 +257,14 @@ def compare(prec, kind, payoff, barrier, d, n_steps):
     return _restated[key]
 
 
-PLAIN_CASES = [(kind, CALL if (kind + d) % 2 else PUT, NO_BARRIER, d, n) for kind in KINDS for d in DS for n in STEPS]
-BARRIER_CASES = [(kind, PUT if barrier in (DOWN_OUT, DOWN_IN) else CALL, barrier, d, n)
-                 for kind in (BEST_OF, WORST_OF) for barrier in BARRIERS for d in DS for n in STEPS]
+def cases(ds, steps):
+    """every kind without a barrier, and best-of and worst-of with every barrier direction, at each width and step count"""
+    plain = [(kind, CALL if (kind + d) % 2 else PUT, NO_BARRIER, d, n) for kind in KINDS for d in ds for n in steps]
+    barrier = [(kind, PUT if barrier in (DOWN_OUT, DOWN_IN) else CALL, barrier, d, n)
+               for kind in (BEST_OF, WORST_OF) for barrier in BARRIERS for d in ds for n in steps]
+    return plain, barrier
+
+
+PLAIN_CASES, BARRIER_CASES = cases(DS, STEPS)
+MORE_CASES = sum(cases(MORE_DS, STEPS), [])                       # on the SHALLOW inputs: 144 cases
+DEEP_CASES = sum(cases(tuple(range(1, 9)), (DEEP_STEPS,)), [])    # on the DEEP inputs: 96 cases

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import asian_restate as ar
+from deep_inputs import check_deep_draws_differ
 
 pkg = importlib.import_module("monte-carlo-project-cuda_amd")
 capi = pkg.capi
@@ -268,6 +269,22 @@ def test_recorded_restatement_spread(bits):
     got = ar.measure_spread(bits)
     print(f"fp{bits}: largest restatement difference {got:.4e}, record {ar.RECORD['spread'][bits]:.4e}")
     assert 0 < got <= ar.RECORD["spread"][bits]
+
+
+@pytest.mark.parametrize("bits", [64, 32])
+def test_recorded_restatement_spread_of_the_added_inputs(bits):
+    """5 steps, and 7 steps on the deep inputs: measured as the record above is, recorded beside it, and below it —
+    which is why GPU test 1 holds these cases to the tolerance made of RECORD["spread"]"""
+    got = ar.measure_spread(bits, ar.MORE_INPUTS)
+    print(f"fp{bits}: largest restatement difference {got:.4e}, record {ar.RECORD['spread_more'][bits]:.4e}")
+    assert 0 < got <= ar.RECORD["spread_more"][bits] <= ar.RECORD["spread"][bits]
+
+
+@pytest.mark.parametrize("bits", [64, 32])
+def test_deep_normals_are_those_of_neither_shallow_word(bits):
+    """What makes the deep cases worth running: the deep normals share nothing with the streams a dropped high word
+    of the path id or of the seed lands on (tests/deep_inputs.py)."""
+    check_deep_draws_differ(lambda seed, first: ar.oracle_normals(bits, seed, first, 64, 7))
 
 
 def test_recorded_correlation():

@@ -1,7 +1,10 @@
 """GPU tests of the Asian pricer (mcamd_price_asian).  Run with -m gpu on an MI355X.
 
   1. samples, elementwise through d_samples, against the numpy restatement (tests/asian_restate.py) on normals drawn
-     from the oracle's rocRAND-exact generator for (seed, global path id, block);
+     from the oracle's rocRAND-exact generator for (seed, global path id, block): 50, 7 and 5 steps on 4096 paths at
+     global ids 5003.. under seed 77, and 7 steps on the deep inputs, ids 2^33 + 5003.. of a job of 2^40 paths under
+     seed 2^40 + 77.  These step counts leave 2, 3, 1 and 3 of the 4 normals of a path's last Philox block in fp32 and
+     0, 1, 1 and 1 of its 2 in fp64;
   2. the arithmetic average against the prices mcamd_simulate_trajectories stores;  3. geometric jobs against the closed
   form within 4 SE at n_steps 1, 12 and 252;  4. one step without the spot is mcamd_price_paths;  5. the control
   variate;  6. shards;  7. repeatability and the enqueue form;  8. flags, ignored fields and the empty shard.
@@ -12,7 +15,9 @@ tests/test_asian_cpu.py): four times the largest elementwise difference between 
 include_spot x n_steps cases on the test's own inputs — S0 = 100, r = 0.1, v = 0.2, T = 1, K = 100; 50 and 7 steps, 4096
 paths at global ids 5003.., seed 77 — floored at 1e-11 of the sample (fp64) and 2e-3 absolute (fp32).  Recorded:
 4 x 2.0e-13 = 8.0e-13 absolute for fp64; 4 x 1.3e-4 = 5.2e-4 for fp32, i.e. the 2e-3 floor decides there.  The sample is
-continuous in every input, so NO path is left out."""
+continuous in every input, so NO path is left out.  The 64 cases at 5 steps and on the deep inputs take the same
+tolerance: their restatements differ by 7.1e-14 (fp64) and 4.8e-5 (fp32) at most, recorded as RECORD["spread_more"] and
+measured again by the same CPU test, which also holds them below the record above."""
 import importlib
 import itertools
 import math
@@ -91,23 +96,34 @@ def mu_g(n_steps, strike, payoff, spot, K=ar.K_ATM):
 
 # ---- 1. samples against the restatement ----------------------------------------------------------------------------------
 
-CASES = [(prec, n_steps, average) + p for prec in PRECS for n_steps in ar.STEPS
-         for average in (ar.ARITHMETIC, ar.GEOMETRIC) for p in ar.PRODUCTS]
+def cases(inputs):
+    return [(prec, n_steps, average) + p + (where,) for prec in PRECS for n_steps, where in inputs
+            for average in (ar.ARITHMETIC, ar.GEOMETRIC) for p in ar.PRODUCTS]
 
 
-@pytest.mark.parametrize("prec,n_steps,average,strike,payoff,spot", CASES)
-def test_samples_against_the_restatement(ctx, prec, n_steps, average, strike, payoff, spot):
+def _case(case):
+    """the ids of the 50- and 7-step cases on the shallow inputs are those pytest gave them before there were deep ones"""
+    return pytest.param(*case, id="-".join(str(x) for x in case[:-1]) + ("-deep" if case[-1] == ar.DEEP else ""))
+
+
+CASES = [_case(c) for c in cases(ar.INPUTS) + cases(ar.MORE_INPUTS)]
+
+
+@pytest.mark.parametrize("prec,n_steps,average,strike,payoff,spot,where", CASES)
+def test_samples_against_the_restatement(ctx, prec, n_steps, average, strike, payoff, spot, where):
     bits = 64 if prec == capi.F64 else 32
-    z = ar.oracle_normals(bits, ar.SEED, ar.OFFSET, ar.N_LOCAL, n_steps)
+    seed, first, n_job = where
+    z = ar.oracle_normals(bits, seed, first, ar.N_LOCAL, n_steps)
     own = np.asarray(ar.restate(z, average, strike, payoff, spot, NP_T[prec])["y"], dtype=np.float64)
     want = own if prec == capi.F64 else ar.restate(z, average, strike, payoff, spot, np.float64)["y"]
     tol = elementwise_tolerance(prec, want)
-    sim = capi.make_sim(ar.N_JOB, n_steps, prec, seed=ar.SEED, path_offset=ar.OFFSET, n_paths_local=ar.N_LOCAL)
+    sim = capi.make_sim(n_job, n_steps, prec, seed=seed, path_offset=first, n_paths_local=ar.N_LOCAL)
     res, got = run(ctx, option(), sim, capi.make_asian(average, strike, payoff, spot))
     assert np.isfinite(got).all() and res.n == ar.N_LOCAL and res.block == 256 and res.grid == ar.N_LOCAL // 256
     err = np.abs(got - want)
     k = int(np.argmax(err - tol))
-    print(f"prec {prec} n_steps {n_steps} average {average} strike {strike} payoff {payoff} spot {spot}: tolerance "
+    print(f"prec {prec} n_steps {n_steps} average {average} strike {strike} payoff {payoff} spot {spot} first path "
+          f"{first}: tolerance "
           f"{tol.min():.3e}..{tol.max():.3e}, worst deviation {err.max():.3e}, nonzero samples {(want != 0).mean():.3f}")
     assert (err <= tol).all(), (k, got[k], want[k], tol[k])   # every path: nothing is left out
     assert 0.3 < (want != 0).mean()

@@ -1,7 +1,10 @@
 """GPU tests of the single-barrier pricer (mcamd_price_barrier).  Run with -m gpu on an MI355X.
 
   1. samples, elementwise through d_samples, against the numpy restatement (tests/barrier_restate.py) on normals drawn
-     from the oracle's rocRAND-exact generator for (seed, global path id, block);
+     from the oracle's rocRAND-exact generator for (seed, global path id, block): 50, 3 and 5 steps on 4096 paths at
+     global ids 5003.. under seed 77, and 7 steps on the deep inputs, ids 2^33 + 5003.. of a job of 2^40 paths under
+     seed 2^40 + 77.  The last, partial Philox block of a path is a branch of its own in the kernel: these step counts
+     leave 2, 3, 1 and 3 of its 4 normals in fp32 and 0, 1, 1 and 1 of its 2 in fp64;
   2. the discrete down-barrier calls against the bullet window of mcamd_price_paths; in + out = European;
   3. continuous monitoring against the Reiner-Rubinstein closed form within 4 SE at n_steps 1, 12 and 252;
   4. discrete >= continuous sample for sample;  5. shards;  6. repeatability and the enqueue form;
@@ -15,7 +18,12 @@ monitoring cases on the test's own inputs — S0 = K = 100, r = 0.1, v = 0.2, T 
 Measured on an x86-64 CPU (80-bit longdouble): 4 x 2.74e-13 = 1.10e-12 absolute for fp64; 4 x 8.73e-5 = 3.5e-4 for
 fp32, i.e. the 2e-3 floor decides there.  A path whose restated min_i |d_i| is below MARGIN = 2e-5 (natural-log units) is
 left out: the hit test is a discontinuity no arithmetic reproduces to the last bit, and a bridge factor's relative
-error grows like ulp(X) / d.  The restatement leaves out at most 0.46 % of a case's paths on these inputs (cap: 1 %)."""
+error grows like ulp(X) / d.  The restatement leaves out at most 0.46 % of a case's paths on these inputs (cap: 1 %).
+The tolerance is taken from the 50-step inputs alone.  On the other inputs of test 1 (MORE_INPUTS) the restatements
+differ by less — at most 8.6e-14 (fp64) and 4.7e-5 (fp32), 0.10 % of a case left out, at least 3.8 % of a case's samples
+non-zero — which test_added_inputs_stay_under_the_spread_and_the_cap asserts; like the exclusion-cap check it runs no
+kernel, but it lives in this module and so runs with -m gpu.  One step is not among them:
+a knock-in pays nothing then."""
 import importlib
 import itertools
 import math
@@ -24,6 +32,7 @@ import numpy as np
 import pytest
 
 import barrier_restate as br
+from deep_inputs import DEEP, SHALLOW, check_deep_draws_differ
 
 pytestmark = pytest.mark.gpu
 
@@ -37,6 +46,8 @@ CAP = 0.01
 BASE = dict(S0=100.0, K=100.0, r=0.1, v=0.2, T=1.0)
 B_DOWN, B_UP = 92.0, 110.0
 N_JOB, OFFSET, N_LOCAL, N_STEPS, SEED = 20_000, 5003, 4096, 50, 77
+assert SHALLOW == (SEED, OFFSET, N_JOB)   # (seed, first path, paths of the job); DEEP: tests/deep_inputs.py
+MORE_INPUTS = ((3, SHALLOW), (5, SHALLOW), (7, DEEP))                        # (n_steps, where) beside (N_STEPS, SHALLOW)
 
 
 def level(kind):
@@ -86,20 +97,34 @@ def compare(prec, kind, payoff, monitoring, z):
 _spread = {}
 
 
-def elementwise_tolerance(prec, want):
-    """Absolute tolerance per element: 4 x the largest restatement difference over the 16 cases of test 1's inputs,
-    floored at 1e-11 of the sample (fp64) / 2e-3 (fp32).  From the restatement alone."""
+def measured_spread(prec):
+    """the largest restatement difference over the 16 cases of test 1's 50-step inputs"""
     if prec not in _spread:
         z = normals(prec, SEED, OFFSET, N_LOCAL, N_STEPS)
         _spread[prec] = max(compare(prec, kind, payoff, monitoring, z)[3]
                             for kind, payoff, monitoring in itertools.product(br.KINDS, (br.CALL, br.PUT),
                                                                               (br.DISCRETE, br.CONTINUOUS)))
+    return _spread[prec]
+
+
+def elementwise_tolerance(prec, want):
+    """Absolute tolerance per element: 4 x the largest restatement difference over the 16 cases of test 1's inputs,
+    floored at 1e-11 of the sample (fp64) / 2e-3 (fp32).  From the restatement alone."""
     if prec == capi.F64:
-        return np.maximum(4.0 * _spread[prec], 1e-11 * np.abs(want))
-    return np.full(want.shape, max(4.0 * _spread[prec], 2e-3))
+        return np.maximum(4.0 * measured_spread(prec), 1e-11 * np.abs(want))
+    return np.full(want.shape, max(4.0 * measured_spread(prec), 2e-3))
 
 
 CASES = list(itertools.product((capi.F64, capi.F32), br.KINDS, (br.CALL, br.PUT), (br.DISCRETE, br.CONTINUOUS)))
+
+
+def _name(case, n_steps, where):
+    return "-".join(str(x) for x in case) + f"-{n_steps}" + ("-deep" if where == DEEP else "")
+
+
+# the ids of the 50-step cases are those pytest gave them before there were others
+SAMPLE_CASES = [pytest.param(*c, N_STEPS, SHALLOW, id="-".join(str(x) for x in c)) for c in CASES] + \
+               [pytest.param(*c, n_steps, where, id=_name(c, n_steps, where)) for n_steps, where in MORE_INPUTS for c in CASES]
 
 
 def test_restatement_stays_under_the_exclusion_cap():
@@ -111,6 +136,30 @@ def test_restatement_stays_under_the_exclusion_cap():
         worst = max(worst, 1.0 - keep.mean())
         assert 1.0 - keep.mean() <= CAP
     print(f"largest excluded fraction {worst:.4f}")
+
+
+def test_added_inputs_stay_under_the_spread_and_the_cap():
+    """no kernel runs: on MORE_INPUTS the two restatements differ by no more than on the inputs the tolerance is taken
+    from, leave out less than 1 % of every case, and more than 2 % of every case's samples are non-zero"""
+    for n_steps, where in MORE_INPUTS:
+        spreads, left_out, nonzero = {capi.F64: 0.0, capi.F32: 0.0}, 0.0, 1.0
+        for prec, kind, payoff, monitoring in CASES:
+            z = normals(prec, where[0], where[1], N_LOCAL, n_steps)
+            keep, want, own, spread = compare(prec, kind, payoff, monitoring, z)
+            spreads[prec] = max(spreads[prec], spread)
+            left_out, nonzero = max(left_out, 1.0 - keep.mean()), min(nonzero, (want != 0).mean())
+            assert spread <= measured_spread(prec), (n_steps, where, prec, kind, payoff, monitoring, spread)
+            assert 1.0 - keep.mean() <= CAP and 0.02 < (want != 0).mean()
+        print(f"n_steps {n_steps} first path {where[1]}: largest restatement difference {spreads[capi.F64]:.3e} (fp64; the "
+              f"tolerance's {measured_spread(capi.F64):.3e}) {spreads[capi.F32]:.3e} (fp32; {measured_spread(capi.F32):.3e}), "
+              f"largest excluded fraction {left_out:.4f}, smallest non-zero share {nonzero:.3f}")
+
+
+@pytest.mark.parametrize("prec", [capi.F64, capi.F32])
+def test_deep_normals_are_those_of_neither_shallow_word(prec):
+    """no kernel runs.  What makes the deep cases worth running: the deep normals share nothing with the streams a
+    dropped high word of the path id or of the seed lands on (tests/deep_inputs.py)."""
+    check_deep_draws_differ(lambda seed, first: normals(prec, seed, first, 64, 7))
 
 
 torch = pytest.importorskip("torch")
@@ -148,19 +197,21 @@ def full_work(n, n_steps):
 
 # ---- 1. samples against the restatement ----------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("prec,kind,payoff,monitoring", CASES)
-def test_samples_against_the_restatement(ctx, prec, kind, payoff, monitoring):
-    z = normals(prec, SEED, OFFSET, N_LOCAL, N_STEPS)
+@pytest.mark.parametrize("prec,kind,payoff,monitoring,n_steps,where", SAMPLE_CASES)
+def test_samples_against_the_restatement(ctx, prec, kind, payoff, monitoring, n_steps, where):
+    seed, first, n_job = where
+    z = normals(prec, seed, first, N_LOCAL, n_steps)
     keep, want, own, spread = compare(prec, kind, payoff, monitoring, z)
     tol = elementwise_tolerance(prec, want)
     excluded = 1.0 - keep.mean()
     assert excluded <= CAP, excluded
-    sim = capi.make_sim(N_JOB, N_STEPS, prec, seed=SEED, path_offset=OFFSET, n_paths_local=N_LOCAL)
+    sim = capi.make_sim(n_job, n_steps, prec, seed=seed, path_offset=first, n_paths_local=N_LOCAL)
     res, got = run(ctx, option(kind), sim, capi.make_barrier(kind, payoff, monitoring))
     assert np.isfinite(got).all() and res.n == N_LOCAL and res.block == 256 and res.grid == N_LOCAL // 256
     err = np.abs(got - want)
     k = int(np.argmax(np.where(keep, err - tol, -np.inf)))
-    print(f"prec {prec} kind {kind} payoff {payoff} monitoring {monitoring}: restatement spread {spread:.3e}, "
+    print(f"prec {prec} kind {kind} payoff {payoff} monitoring {monitoring} n_steps {n_steps} first path {first}: "
+          f"restatement spread {spread:.3e}, "
           f"tolerance {tol[keep].min():.3e}..{tol[keep].max():.3e}, worst kept deviation {err[keep].max():.3e}, "
           f"excluded {excluded:.4f}, nonzero samples {(want != 0).mean():.3f}")
     assert (err[keep] <= tol[keep]).all(), (k, got[k], want[k], tol[k])
@@ -174,7 +225,7 @@ def test_samples_against_the_restatement(ctx, prec, kind, payoff, monitoring):
     assert (res.price, res.std_err, res.ci_lo, res.ci_hi) == (fin.price, fin.std_err, fin.ci_lo, fin.ci_hi)
     assert res.sum_c == res.sum_cc == res.sum_yc == res.cv_beta == res.cv_rho == 0.0
     # live lane-steps are the restated ones, but for the paths left out (each can differ by at most every step)
-    assert abs(res.live_steps - own["live"].sum()) <= N_STEPS * int((~keep).sum())
+    assert abs(res.live_steps - own["live"].sum()) <= n_steps * int((~keep).sum())
 
 
 # ---- 2. agreement with what exists -------------------------------------------------------------------------------------------

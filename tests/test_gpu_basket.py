@@ -1,20 +1,30 @@
 """GPU tests of the basket pricer (mcamd_price_basket).  Run with -m gpu on an MI355X.
 
   1. samples, elementwise through d_samples, against the numpy restatement (tests/basket_restate.py) on the oracle's
-     rocRAND-exact normals for (seed, global path id, block), all kinds, d in {1, 2, 3, 5, 8}, 1, 2, 7 and 50 steps, and
-     with every barrier direction on best-of and worst-of;  2. d = 1 against mcamd_price_barrier;  3. knock-in plus
-     knock-out is the unmonitored sample, bit for bit;  4. the closed forms within 4 SE;  5. the ordering of the
-     aggregates, sample by sample;  6. shards and the grid-stride loop;  7. repeatability, the enqueue form, the empty
-     shard and refusals with a live context.
+     rocRAND-exact normals for (seed, global path id, block), all kinds and every barrier direction on best-of and
+     worst-of: every width d = 1..8 at 1, 2, 7 and 50 steps, 4096 paths at global ids 5003.. under seed 77, and every
+     width again at 7 steps on the deep inputs, ids 2^33 + 5003.. of a job of 2^40 paths under seed 2^40 + 77;
+  2. d = 1 against mcamd_price_barrier;  3. knock-in plus knock-out is the unmonitored sample, bit for bit;  4. the
+  closed forms within 4 SE;  5. the ordering of the aggregates, sample by sample;  6. shards and the grid-stride loop;
+  7. repeatability, the enqueue form, the empty shard and refusals with a live context.  3, 5, 6 and 7 take one of
+  d = 4, 6, 7 each beside d from {2, 3, 5, 8}.
 
-Tolerance of 1, 2 and 5 (basket_restate.elementwise_tolerance; it comes from the restatement alone, measured on the
-CPU by tests/test_basket_cpu.py and recorded in basket_restate.SPREAD and DESIGN section 15): four times the largest
+All 32 kernels (d = 1..8, both precisions, with and without monitoring) are compared elementwise.  The group of steps a
+kernel unrolls is G = NB / gcd(d, NB) steps of G d / NB Philox blocks (NB = 2 normals a block in fp64, 4 in fp32): in
+fp32 d = 6 alone has 2 steps of 3 blocks and d = 7 alone 4 steps of 7.  1, 2, 7 and 50 steps leave n_steps % G = 1, 0,
+1, 0 where G = 2 and 1, 2, 3, 2 where G = 4 (odd d in fp32): every remainder but a whole number of groups of 4, which
+runs no code that 7 and 50 steps do not.
+
+Tolerance of 1, 2 and 5 (basket_restate.elementwise_tolerance; it comes from the restatement alone, measured on the CPU
+by tests/test_basket_cpu.py and recorded in basket_restate.SPREAD and DESIGN section 15): four times the largest
 elementwise difference between the float64 and longdouble restatements (fp64 kernels: 4 x 4.1e-13 = 1.6e-12 absolute),
-or between the float32 and float64 restatements (fp32 kernels: 4 x 2.3e-4 = 9.2e-4), over all 480 cases of test 1 on
-its own inputs, floored at 1e-11 of the sample (fp64) and 2e-3 absolute (fp32) as tests/test_gpu_lookback.py floors its
-own; in fp32 the floor decides.  A barrier path whose restated min_i |ln A_i - ln B| is below MARGIN = 2e-5 in either
-restatement is left out (at most 0.54 % of a case's paths on these inputs; cap 1 %): the hit is a discontinuity no
-arithmetic reproduces to the last bit."""
+or between the float32 and float64 restatements (fp32 kernels: 4 x 2.3e-4 = 9.2e-4), over the 480 cases of test 1 with d
+in {1, 2, 3, 5, 8} on ids 5003.., floored at 1e-11 of the sample (fp64) and 2e-3 absolute (fp32) as
+tests/test_gpu_lookback.py floors its own; in fp32 the floor decides.  The 288 cases with d in {4, 6, 7} and the 192
+deep cases are measured there too (test_elementwise_spread_and_exclusions_of_the_added_gpu_cases) and stay below those
+records, so they take the same tolerance.  A barrier path whose restated min_i |ln A_i - ln B| is below MARGIN = 2e-5 in
+either restatement is left out (at most 0.54 % of a case's paths on these inputs; cap 1 %): the hit is a discontinuity
+no arithmetic reproduces to the last bit."""
 import importlib
 import math
 
@@ -75,22 +85,34 @@ def full_work(n, n_steps):
 
 # ---- 1. samples against the restatement ----------------------------------------------------------------------------------
 
+def _case(case, where=br.SHALLOW):
+    """the ids of the cases on the shallow inputs are those pytest gave them before there were deep ones"""
+    name = "-".join(str(x) for x in case)
+    return pytest.param(*case, where, id=(name + "-deep") if where == br.DEEP else name)
+
+
+SAMPLE_CASES = [_case(c) for c in br.PLAIN_CASES + br.BARRIER_CASES + br.MORE_CASES] + \
+               [_case(c, br.DEEP) for c in br.DEEP_CASES]
+
+
 @pytest.mark.parametrize("prec", PRECS)
-@pytest.mark.parametrize("kind,payoff,barrier,d,n_steps", br.PLAIN_CASES + br.BARRIER_CASES)
-def test_samples_against_the_restatement(ctx, prec, kind, payoff, barrier, d, n_steps):
-    want, own, keep, spread = br.compare(prec, kind, payoff, barrier, d, n_steps)
+@pytest.mark.parametrize("kind,payoff,barrier,d,n_steps,where", SAMPLE_CASES)
+def test_samples_against_the_restatement(ctx, prec, kind, payoff, barrier, d, n_steps, where):
+    seed, first, n_job = where
+    want, own, keep, spread = br.compare(prec, kind, payoff, barrier, d, n_steps, where)
     tol = br.elementwise_tolerance(prec, want)
     excluded = 1.0 - keep.mean()
     assert excluded <= br.CAP, excluded
     K = br.weights(kind, d)[1]
-    sim = capi.make_sim(br.N_JOB, n_steps, prec, seed=br.SEED, path_offset=br.OFFSET, n_paths_local=br.N_LOCAL)
+    sim = capi.make_sim(n_job, n_steps, prec, seed=seed, path_offset=first, n_paths_local=br.N_LOCAL)
     res, got = run(ctx, option(K, br.LEVEL.get(barrier, 0.0)), sim, make(kind, payoff, barrier, d))
     assert np.isfinite(got).all() and res.n == br.N_LOCAL and res.block == 256 and res.grid == br.N_LOCAL // 256
     err = np.abs(got - want)
     k = int(np.argmax(np.where(keep, err - tol, -np.inf)))
-    print(f"prec {prec} kind {kind} payoff {payoff} barrier {barrier} d {d} n_steps {n_steps}: restatement spread "
-          f"{spread:.3e}, tolerance {tol.min():.3e}..{tol.max():.3e}, worst deviation {err[keep].max():.3e}, left out "
-          f"{excluded:.4f}, nonzero {(want != 0).mean():.3f}, live {res.live_steps:.0f} restated {own['live'].sum()}")
+    print(f"prec {prec} kind {kind} payoff {payoff} barrier {barrier} d {d} n_steps {n_steps} first path {first}: "
+          f"restatement spread {spread:.3e}, tolerance {tol.min():.3e}..{tol.max():.3e}, worst deviation "
+          f"{err[keep].max():.3e}, left out {excluded:.4f}, nonzero {(want != 0).mean():.3f}, live {res.live_steps:.0f} "
+          f"restated {own['live'].sum()}")
     assert (err[keep] <= tol[keep]).all(), (k, got[k], want[k], tol[k])
     # the sums are those of the kept paths plus the GPU's own left-out samples
     ref = np.where(keep, np.asarray(own["y"], dtype=np.float64), got)
@@ -146,7 +168,8 @@ def test_one_asset_is_the_discrete_single_barrier(ctx, prec, barrier, kind1, pay
 # ---- 3. in plus out ------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("prec", PRECS)
-@pytest.mark.parametrize("kind,d,n_steps", [(br.WORST_OF, 3, 7), (br.BEST_OF, 5, 50), (br.WORST_OF, 8, 13)])
+@pytest.mark.parametrize("kind,d,n_steps", [(br.WORST_OF, 3, 7), (br.BEST_OF, 5, 50), (br.WORST_OF, 8, 13),
+                                            (br.BEST_OF, 6, 7)])
 def test_in_plus_out_is_the_unmonitored_sample(ctx, prec, kind, d, n_steps):
     n = 20_000
     sim = capi.make_sim(n, n_steps, prec, seed=12)
@@ -202,7 +225,7 @@ def test_closed_forms(ctx, prec, n_steps, case):
 # ---- 5. the ordering of the aggregates -----------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("prec", PRECS)
-@pytest.mark.parametrize("d,n_steps", [(2, 1), (5, 7), (8, 50)])
+@pytest.mark.parametrize("d,n_steps", [(2, 1), (5, 7), (8, 50), (7, 7)])
 def test_worst_arithmetic_best_and_geometric_arithmetic(ctx, prec, d, n_steps):
     """min <= mean <= max of the performances and geometric <= arithmetic mean, exactly so in exact arithmetic: calls
     struck at 0 are the aggregates themselves, compared within the elementwise tolerance"""
@@ -227,7 +250,8 @@ def test_worst_arithmetic_best_and_geometric_arithmetic(ctx, prec, d, n_steps):
 def test_shards_reproduce_the_whole_job(ctx, prec, cut):
     """bit for bit: a path's normals depend on its global id alone"""
     n, n_steps = 4099, 7
-    for kind, barrier, d in ((br.ARITHMETIC, br.NO_BARRIER, 3), (br.WORST_OF, br.DOWN_IN, 5)):
+    for kind, barrier, d in ((br.ARITHMETIC, br.NO_BARRIER, 3), (br.WORST_OF, br.DOWN_IN, 5),
+                             (br.BEST_OF, br.UP_OUT, 7)):
         K = br.weights(kind, d)[1]
         opt, bk = option(K, br.LEVEL.get(barrier, 0.0)), make(kind, br.PUT, barrier, d)
         whole, y = run(ctx, opt, capi.make_sim(n, n_steps, prec, seed=3), bk)
@@ -256,7 +280,8 @@ def test_the_grid_stride_loop(ctx):
 # ---- 7. repeatability, the enqueue form, the empty shard, refusals ---------------------------------------------------------
 
 @pytest.mark.parametrize("prec", PRECS)
-@pytest.mark.parametrize("kind,barrier,d", [(br.ARITHMETIC, br.NO_BARRIER, 8), (br.WORST_OF, br.DOWN_OUT, 3)])
+@pytest.mark.parametrize("kind,barrier,d", [(br.ARITHMETIC, br.NO_BARRIER, 8), (br.WORST_OF, br.DOWN_OUT, 3),
+                                                (br.GEOMETRIC, br.NO_BARRIER, 4)])
 def test_same_bits_twice_and_from_the_enqueue_form(ctx, prec, kind, barrier, d):
     n, n_steps = 3000, 13
     K = br.weights(kind, d)[1]

@@ -1,18 +1,25 @@
 """GPU tests of the lookback pricer (mcamd_price_lookback).  Run with -m gpu on an MI355X.
 
   1. samples, elementwise through d_samples, against the numpy restatement (tests/lookback_restate.py) on normals and
-     uniforms drawn from the oracle's rocRAND-exact generator for (seed, global path id, block / 2^63 + block);
+     uniforms drawn from the oracle's rocRAND-exact generator for (seed, global path id, block / 2^63 + block): 50, 1, 3
+     and 5 steps on 4096 paths at global ids 5003.. under seed 77, and 7 steps on the deep inputs, ids 2^33 + 5003.. of
+     a job of 2^40 paths under seed 2^40 + 77.  The last, partial Philox block of a path is a branch of its own in the
+     kernel, with its own block of uniforms: these step counts leave 2, 1, 3, 1 and 3 of its 4 steps in fp32 and 0, 1,
+     1, 1 and 1 of its 2 in fp64;
   2. per-path identities on the GPU's own samples;  3. continuous monitoring against the closed form within 4 SE at
   n_steps 1, 12 and 252;  4. one discrete step is the European call struck at the spot;  5. shards;
   6. repeatability and the enqueue form;  7. the work counters;  8. flags and the empty shard.
 
 Tolerance of 1 (compare / elementwise_tolerance below; it comes from the restatement alone, computed on the CPU): four
 times the largest elementwise difference between the float64 and longdouble restatements (fp64 kernels), or between
-the float32 and float64 restatements (fp32 kernels), over all 24 strike x payoff x monitoring x K cases on the test's
+the float32 and float64 restatements (fp32 kernels), over all 16 strike x payoff x monitoring x K cases on the test's
 own inputs — S0 = 100, r = 0.1, v = 0.2, T = 1, K = 100 and, for the fixed strike, also 95 and 105; 50 steps, 4096
 paths at global ids 5003.., seed 77 — floored at 1e-11 of the sample (fp64) and 2e-3 absolute (fp32).  Measured on an
 x86-64 CPU (80-bit longdouble): 4 x 7.06e-14 = 2.8e-13 absolute for fp64; 4 x 5.06e-5 = 2.0e-4 for fp32, i.e. the
-2e-3 floor decides there.  The sample is continuous in every input, so NO path is left out.
+2e-3 floor decides there.  The sample is continuous in every input, so NO path is left out.  The tolerance is still
+taken from the 50-step inputs alone.  On the other inputs of test 1 (MORE_INPUTS) the restatements differ by less — at most
+6.4e-14 (fp64) and 4.5e-5 (fp32) — and disagree on no live count, which test_added_inputs_stay_under_the_spreads asserts
+(it runs no kernel, but lives in this module and so runs with -m gpu).
 
 The live counter (test 1 too): the kernel's lane-steps with q < Q against the restated count.  q is a product of two
 differences, and a step whose q lies within rounding of Q can fall on either side; the restatements of two dtypes
@@ -28,6 +35,7 @@ import numpy as np
 import pytest
 
 import lookback_restate as lr
+from deep_inputs import DEEP, SHALLOW, check_deep_draws_differ
 
 pytestmark = pytest.mark.gpu
 
@@ -38,6 +46,8 @@ NP_T = {capi.F64: np.float64, capi.F32: np.float32}
 SUM_RTOL = {capi.F64: 1e-11, capi.F32: 2e-5}
 BASE = dict(S0=100.0, r=0.1, v=0.2, T=1.0)
 N_JOB, OFFSET, N_LOCAL, N_STEPS, SEED = 20_000, 5003, 4096, 50, 77
+assert SHALLOW == (SEED, OFFSET, N_JOB)   # (seed, first path, paths of the job); DEEP: tests/deep_inputs.py
+MORE_INPUTS = ((1, SHALLOW), (3, SHALLOW), (5, SHALLOW), (7, DEEP))          # (n_steps, where) beside (N_STEPS, SHALLOW)
 PRECS = (capi.F64, capi.F32)
 
 
@@ -95,6 +105,15 @@ PRODUCT_CASES = [(strike, payoff, monitoring, K)
                  for K in ((100.0, 95.0, 105.0) if strike == lr.FIXED else (100.0,))]
 CASES = [(prec,) + c for prec in PRECS for c in PRODUCT_CASES]
 
+
+def _name(case, n_steps, where):
+    return "-".join(str(x) for x in case) + f"-{n_steps}" + ("-deep" if where == DEEP else "")
+
+
+# the ids of the 50-step cases are those pytest gave them before there were others
+SAMPLE_CASES = [pytest.param(*c, N_STEPS, SHALLOW, id="-".join(str(x) for x in c)) for c in CASES] + \
+               [pytest.param(*c, n_steps, where, id=_name(c, n_steps, where)) for n_steps, where in MORE_INPUTS for c in CASES]
+
 _spread = {}
 
 
@@ -126,6 +145,28 @@ def test_restatement_spreads():
         spread, flips = measured(prec)
         print(f"prec {prec}: largest restatement difference {spread:.3e}, largest live-count disagreement {flips}")
         assert spread > 0 and flips <= 64
+
+
+def test_added_inputs_stay_under_the_spreads():
+    """no kernel runs: on MORE_INPUTS the two restatements differ by no more than on the inputs the tolerance is taken
+    from, and four times their disagreement on a live count stays within the bound on the kernel's"""
+    for n_steps, where in MORE_INPUTS:
+        worst = {}
+        for prec, *case in CASES:
+            z, u = draws(prec, where[0], where[1], N_LOCAL, n_steps)
+            want, own, spread, flips = compare(prec, *case, z, u)
+            assert np.isfinite(want).all() and spread <= measured(prec)[0], (n_steps, where, prec, case, spread)
+            assert 4 * flips <= live_tolerance(prec), (n_steps, where, prec, case, flips)
+            worst[prec] = max(worst.get(prec, (0.0, 0)), (spread, flips))
+        print(f"n_steps {n_steps} first path {where[1]}: largest restatement difference and live-count disagreement "
+              f"{worst[capi.F64]} (fp64; the tolerance's {measured(capi.F64)}) {worst[capi.F32]} (fp32; {measured(capi.F32)})")
+
+
+@pytest.mark.parametrize("prec", PRECS)
+def test_deep_draws_are_those_of_neither_shallow_word(prec):
+    """no kernel runs.  What makes the deep cases worth running: the deep normals and uniforms share nothing with the
+    streams a dropped high word of the path id or of the seed lands on (tests/deep_inputs.py)."""
+    check_deep_draws_differ(lambda seed, first: draws(prec, seed, first, 64, 7))
 
 
 torch = pytest.importorskip("torch")
@@ -174,23 +215,27 @@ def terminal_prices(ctx, sim, K=100.0):
 
 # ---- 1. samples against the restatement ----------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("prec,strike,payoff,monitoring,K", CASES)
-def test_samples_against_the_restatement(ctx, prec, strike, payoff, monitoring, K):
-    z, u = draws(prec, SEED, OFFSET, N_LOCAL, N_STEPS)
+@pytest.mark.parametrize("prec,strike,payoff,monitoring,K,n_steps,where", SAMPLE_CASES)
+def test_samples_against_the_restatement(ctx, prec, strike, payoff, monitoring, K, n_steps, where):
+    seed, first, n_job = where
+    z, u = draws(prec, seed, first, N_LOCAL, n_steps)
     want, own, spread, flips = compare(prec, strike, payoff, monitoring, K, z, u)
     tol = elementwise_tolerance(prec, want)
-    sim = capi.make_sim(N_JOB, N_STEPS, prec, seed=SEED, path_offset=OFFSET, n_paths_local=N_LOCAL)
+    sim = capi.make_sim(n_job, n_steps, prec, seed=seed, path_offset=first, n_paths_local=N_LOCAL)
     res, got = run(ctx, option(K), sim, capi.make_lookback(strike, payoff, monitoring))
     assert np.isfinite(got).all() and res.n == N_LOCAL and res.block == 256 and res.grid == N_LOCAL // 256
     err = np.abs(got - want)
     k = int(np.argmax(err - tol))
     want_live = int(own["live"].sum())
-    print(f"prec {prec} strike {strike} payoff {payoff} monitoring {monitoring} K {K}: restatement spread {spread:.3e}, "
+    print(f"prec {prec} strike {strike} payoff {payoff} monitoring {monitoring} K {K} n_steps {n_steps} first path {first}: "
+          f"restatement spread {spread:.3e}, "
           f"tolerance {tol.min():.3e}..{tol.max():.3e}, worst deviation {err.max():.3e}, "
           f"nonzero samples {(want != 0).mean():.3f}, live {res.live_steps:.0f} restated {want_live} "
           f"(restatements disagree on {flips}, bound {live_tolerance(prec)})")
     assert (err <= tol).all(), (k, got[k], want[k], tol[k])   # every path: nothing is left out
-    assert 0.3 < (want != 0).mean()
+    # not a vacuous comparison (the restatement's own samples).  One discrete step of the fixed put struck at 95 pays
+    # where S_1 < 95 only, with probability N((ln 0.95 - 0.08) / 0.2) = 0.256: 0.2 is 8 standard errors of 4096 paths below
+    assert (0.3 if n_steps > 1 else 0.2) < (want != 0).mean()
     ref = np.asarray(own["y"], dtype=np.float64)
     rt = SUM_RTOL[prec]
     assert abs(res.sum - ref.sum()) <= rt * abs(ref.sum()), (res.sum, ref.sum())
@@ -199,11 +244,13 @@ def test_samples_against_the_restatement(ctx, prec, strike, payoff, monitoring, 
     assert (res.price, res.std_err, res.ci_lo, res.ci_hi) == (fin.price, fin.std_err, fin.ci_lo, fin.ci_hi)
     assert res.sum_c == res.sum_cc == res.sum_yc == res.cv_beta == res.cv_rho == 0.0
     # 7 (the half that needs the restatement): the counters
-    assert res.work_steps == full_work(N_LOCAL, N_STEPS)
+    assert res.work_steps == full_work(N_LOCAL, n_steps)
     if monitoring == lr.DISCRETE:
         assert res.live_steps == 0.0
     else:
-        assert 0 < want_live < N_LOCAL * N_STEPS and abs(res.live_steps - want_live) <= live_tolerance(prec)
+        # the first step has q = 0 (E_0 = X_0, so one of the two distances is 0): every lane forms its bridge extremum
+        assert 0 < want_live and (want_live < N_LOCAL * n_steps) == (n_steps > 1)
+        assert abs(res.live_steps - want_live) <= live_tolerance(prec)
 
 
 # ---- 2. identities on the GPU's own samples ----------------------------------------------------------------------------------
