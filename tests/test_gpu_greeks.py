@@ -5,12 +5,37 @@
     tolerance is relative to the sum of the terms' magnitudes: 1e-10 in fp64; in fp32 the allowances of the
     price_paths oracle tests (2e-5 for the price, 2e-3 where a path within rounding of the strike or the barrier can
     flip an indicator);
-  * statistics: |estimate - closed form| <= 4.5 SE, and every SE below a stated fraction of the value."""
+  * statistics: |estimate - closed form| <= 4.5 SE, and every SE below a stated fraction of the value;
+  * path by path (test_every_path_restates): a Greeks call has no per-path output, but a shard of one path is that
+    path's six samples.  256 consecutive paths from ids 5003.. under seed 77 and from ids 2^33 + 5003.. of a 2^40-path
+    job under seed 2^40 + 77, at 1, 2, 3, 5, 6, 7 simulated steps: every remainder of the last Philox block, and the LR
+    kernel's branch for a path shorter than one block (fp32: 1 to 3 steps, fp64: 1).  Cases, restatements, tolerance
+    and the paths left out in fp32: tests/greeks_cases.py; what they rest on is checked without a kernel in
+    tests/test_greeks_cpu.py;
+  * small shards (test_small_shards_and_what_each_adds): n_paths_local of 1..5, 63..65, 255..257 and 513, each record
+    and the difference of consecutive records against exactly the restated paths;
+  * the short-path launch rule (test_short_lr_paths_walk_the_grid_stride): ceil(32 / n_sim) paths a thread.
+
+The per-path tolerance is four times the largest elementwise difference between two restatements, floored at 1e-10
+(fp64) / 2e-5 for the price and 2e-3 for the others (fp32) of max(|q|, mean |q| of the case).  Largest restatement
+differences, measured on an x86-64 CPU (80-bit longdouble), price delta gamma vega rho theta:
+    pathwise  fp64 3.4e-14 4.2e-16 1.0e-16 2.6e-13 1.5e-14 2.9e-14    fp32 2.6e-5 2.9e-7 5.7e-8 1.6e-4 1.6e-5 2.4e-5
+    LR        fp64 3.4e-14 8.5e-15 3.4e-15 2.2e-12 6.5e-13 -          fp32 2.8e-5 5.0e-6 1.1e-6 1.7e-3 4.7e-4 -
+so the floor decides everywhere but for the fp32 price of the cases with a small mean price (the restarts and dt = 1/50:
+4 x 2.8e-5 = 1.1e-4 against 2e-5 x 3.6 to 5.5).  Largest
+deviations of the kernels from the float64 restatement on an MI355X, over all cases, same order:
+    pathwise  fp64 8.5e-14 8.9e-16 1.7e-16 5.7e-13 3.7e-14 5.0e-14    fp32 4.4e-5 4.0e-7 1.2e-7 1.9e-4 1.2e-5 1.8e-5
+    LR        fp64 8.5e-14 1.8e-14 5.3e-15 5.2e-12 1.4e-12 -          fp32 2.0e-5 8.2e-6 1.2e-6 1.4e-3 4.1e-4 -
+The fp32 price comes closest to its tolerance, at 0.22 of it; the pathwise kernel's pair sums (about an ulp per pair off
+rocRAND's two normals) fit the fp32 floors as they are, and no floor is widened."""
 import importlib
 import math
 
 import numpy as np
 import pytest
+
+import greeks_cases as gc
+from greeks_restate import restate
 
 pytestmark = pytest.mark.gpu
 
@@ -36,53 +61,6 @@ def ctx():
     yield c
     c.close()
     torch.cuda.set_stream(torch.cuda.default_stream())
-
-
-def normals(oracle, prec, seed, path_ids, n_sim):
-    """[len(path_ids), n_sim] normals of the engine's stream: subsequence = global path id, blocks from 0"""
-    nb = 2 if prec == capi.F64 else 4
-    blocks = (n_sim + nb - 1) // nb
-    gen = oracle.normal2_f64 if prec == capi.F64 else oracle.normal4_f32
-    z = np.empty((len(path_ids), blocks * nb))
-    for i, p in enumerate(path_ids):
-        for b in range(blocks):
-            z[i, b * nb:(b + 1) * nb] = gen(seed, int(p), b)
-    return z[:, :n_sim]
-
-
-def restate(oracle, opt, sim, method):
-    """per-path samples [n, 6] of the six estimators, in fp64 from the engine's normals"""
-    n_sim = sim.n_steps - opt.Tk
-    dt = opt.dt if opt.dt > 0 else opt.T / sim.n_steps
-    S_s = opt.Sk if opt.Sk != 0 else opt.S0
-    r, v, T, K = opt.r, opt.v, opt.T, opt.K
-    Th = n_sim * dt
-    z = normals(oracle, sim.precision, sim.seed, range(sim.path_offset, sim.path_offset + sim.n_paths_local), n_sim)
-    logs = np.cumsum((r - 0.5 * v * v) * dt + v * math.sqrt(dt) * z, axis=1)
-    L = logs[:, -1]
-    St = S_s * np.exp(L)
-    y = np.maximum(St - K, 0.0)
-    if opt.use_window:
-        logB = math.log(opt.B / S_s) if opt.B > 0 else -np.inf
-        count = opt.Ik + (logB > logs).sum(axis=1)
-        y = np.where((count >= opt.P1) & (count <= opt.P2), y, 0.0)
-    q = np.zeros((len(y), 6))
-    q[:, 0] = y
-    if method == PW:
-        itm = St > K
-        q[:, 1] = np.where(itm, St / S_s, 0.0)
-        q[:, 2] = np.where(itm, K * (L - (r - v * v / 2) * Th) / (S_s ** 2 * v * v * Th), 0.0)
-        q[:, 3] = np.where(itm, St * (L - (r + v * v / 2) * Th) / v, 0.0)
-        q[:, 4] = -T * y + np.where(itm, St * Th, 0.0)
-        if opt.Tk == 0 and opt.dt == 0:
-            q[:, 5] = r * y - np.where(itm, St * ((r - v * v / 2) + (L - (r - v * v / 2) * T) / (2 * T)), 0.0)
-    else:
-        z1, sz, szz, sq = z[:, 0], z.sum(axis=1), (z * z).sum(axis=1), math.sqrt(dt)
-        q[:, 1] = y * z1 / (S_s * v * sq)
-        q[:, 2] = y * ((z1 * z1 - 1) / (S_s ** 2 * v * v * dt) - z1 / (S_s ** 2 * v * sq))
-        q[:, 3] = y * ((szz - n_sim) / v - sq * sz)
-        q[:, 4] = y * (sz * sq / v - T)
-    return q
 
 
 def assert_record(got, q, prec, window):
@@ -117,7 +95,7 @@ def test_record_restates_exactly(ctx, oracle, prec, method, extra, n_steps, n, l
     sim = capi.make_sim(lo + n + 10, n_steps, prec, seed=4321, path_offset=lo, n_paths_local=n)
     got = ctx.price_greeks(opt, sim, method)
     assert got.n == n and got.method == method and got.kernel_ms > 0 and got.grid >= 1 and got.block == 256
-    assert_record(got, restate(oracle, opt, sim, method), prec, bool(opt.use_window))
+    assert_record(got, restate(oracle, opt, sim, method).q, prec, bool(opt.use_window))
 
 
 # fp32 LR without a window steps another loop than the pair-sum pricer (rounding ~1e-6 per path): fp64 only there.
@@ -247,3 +225,105 @@ def test_theta_conventions_and_refusals(ctx):
         ctx.price_greeks(capi.make_option(S0=100.0, T=1.0, K=100.0, r=0.1, v=900.0), capi.make_sim(1000, 1, capi.F64))
     with pytest.raises(capi.McamdError):
         ctx.price_greeks_enqueue(capi.make_option(**BENCH), sim, None)
+
+
+# ---- path by path: shards of one path (inputs, restatements and tolerance: tests/greeks_cases.py) ---------------------------
+
+def enqueue_records(ctx, opt, sims, method):
+    """the 16-double statistics records of the shards `sims`, [len(sims), 16]: one launch each, one synchronize"""
+    stats = torch.full((len(sims), capi.GREEKS_STATS), float("nan"), dtype=torch.float64, device="cuda")
+    for row, sim in zip(stats, sims):
+        ctx.price_greeks_enqueue(opt, sim, row, method)
+    torch.cuda.synchronize()
+    return stats.cpu().numpy()
+
+
+def square_tolerance(want, tol):
+    """what |q - want| <= tol allows q^2 to differ from want^2 by: twice the relative bound, and its square"""
+    return 2.0 * tol * np.abs(want) + tol * tol
+
+
+def report(name, prec, err, tol, left):
+    worst = np.where(left, 0.0, err).max(axis=0)
+    share = np.where(left, 0.0, err / np.maximum(tol, 1e-300)).max(axis=0)
+    print(f"{name} prec {prec}: left out {left.any(axis=1).sum()}; largest deviation (and share of its tolerance) " +
+          "  ".join(f"{n} {w:.2e} ({s:.3f})" for n, w, s in zip(capi.GREEK_NAMES, worst, share)))
+
+
+@pytest.mark.parametrize("prec", gc.PRECS)
+@pytest.mark.parametrize("case", gc.CASES, ids=lambda c: c.name)
+def test_every_path_restates(ctx, prec, case):
+    """n_paths_local = 1 and path_offset = id: sum[k] is the path's sample q_k and sumsq[k] its square"""
+    want, tol, left = gc.wanted(case, prec)
+    assert left.any(axis=1).sum() <= gc.MAX_LEFT_OUT and not (prec == capi.F64 and left.any())
+    first = case.where[1]
+    rec = enqueue_records(ctx, gc.option(case), [gc.sim(case, prec, first=first + i, n_local=1) for i in range(gc.N_PATHS)],
+                          case.method)
+    assert np.isfinite(rec).all() and (rec[:, 12] == 1).all() and not rec[:, 13:].any()
+    got, gotsq = rec[:, 0:12:2], rec[:, 1:12:2]
+    err = np.abs(got - want)
+    report(case.name, prec, err, tol, left)
+    bad = np.argwhere(~((err <= tol) | left))
+    assert len(bad) == 0, [(first + i, capi.GREEK_NAMES[k], got[i, k], want[i, k], tol[i, k]) for i, k in bad[:8]]
+    assert ((np.abs(gotsq - want * want) <= square_tolerance(want, tol)) | left).all()
+    assert np.allclose(gotsq, got * got, rtol=1e-15, atol=0.0)    # one path: the record's square is its sum's
+
+
+@pytest.mark.parametrize("prec", gc.PRECS)
+@pytest.mark.parametrize("case", gc.SHARD_CASES, ids=lambda c: c.name)
+def test_small_shards_and_what_each_adds(ctx, prec, case):
+    """Shards of 1.. paths from the same first path: each record against the fp64 sum of exactly its paths' restated
+    samples, and the difference of two consecutive records against the paths the larger shard adds — the second path
+    of a pair-sum thread, the first lane of a second wavefront, the first thread of a second block.  Tolerance: the
+    per-path one, summed over the paths in question (the records are fp64 sums: their own rounding, some 1e-15 of the
+    sum of magnitudes, is far below it)."""
+    sizes = gc.shard_sizes(case)
+    want, tol, left = gc.wanted(case, prec, max(sizes))
+    assert not left.any()      # a sum leaves no path out (tests/test_greeks_cpu.py: none is near a jump)
+    rec = enqueue_records(ctx, gc.option(case), [gc.sim(case, prec, n_local=m) for m in sizes], case.method)
+    assert np.isfinite(rec).all() and rec[:, 12].tolist() == list(sizes) and not rec[:, 13:].any()
+    sq, sqtol = want * want, square_tolerance(want, tol)
+    lo, before = 0, np.zeros(12)
+    for m, r in zip(sizes, rec[:, :12]):
+        for a, what in ((0, "shard"), (lo, "added")):
+            got, gotsq = (r - (before if a else 0.0))[0::2], (r - (before if a else 0.0))[1::2]
+            err, bound = np.abs(got - want[a:m].sum(axis=0)), tol[a:m].sum(axis=0)
+            print(f"{case.name} prec {prec} paths {a}..{m - 1} ({what}): largest share of the tolerance {(err / np.maximum(bound, 1e-300)).max():.3f}")
+            assert (err <= bound).all(), (m, what, got, want[a:m].sum(axis=0), bound)
+            assert (np.abs(gotsq - sq[a:m].sum(axis=0)) <= sqtol[a:m].sum(axis=0)).all(), (m, what)
+        lo, before = m, r
+
+
+@pytest.mark.parametrize("prec", gc.PRECS)
+@pytest.mark.parametrize("n_steps", [1, 2, 3])
+def test_short_lr_paths_walk_the_grid_stride(ctx, prec, n_steps):
+    """Below 32 steps the LR launch gives each thread ceil(32 / n_sim) paths, walked by grid stride: 20 001 paths of 1, 2
+    and 3 steps run on 3, 5 and 8 workgroups, 27, 16 and 10 paths a thread.  The whole job against its ten shards of
+    2001 and 2000 paths (the same samples in another order of summation: 1e-12 of sqrt(n sum q^2) >= sum |q|), and the
+    first shard against the restatement (per-path tolerance, summed)."""
+    n, shard = 20_001, 2000
+    case = gc.Case(f"lr-{n_steps}-stride", LR, {}, n_steps, gc.SHALLOW)
+    opt, first = gc.option(case), case.where[1]
+    per_thread = -(-32 // n_steps)
+    blocks = -(-(-(-n // per_thread)) // 256)
+    assert per_thread == {1: 32, 2: 16, 3: 11}[n_steps] and 1 <= blocks < 8192    # the cap of one_path_per_thread_grid is far
+    whole = ctx.price_greeks(opt, gc.sim(case, prec, n_local=n), LR)
+    assert whole.n == n and whole.grid == blocks and whole.block == 256
+    assert -(-n // (blocks * 256)) == {1: 27, 2: 16, 3: 10}[n_steps]      # grid-stride trips of a thread
+    cuts = [0, shard + 1] + [shard + 1 + shard * i for i in range(1, 10)]
+    assert cuts[-1] == n and len(cuts) == 11
+    rec = enqueue_records(ctx, opt, [gc.sim(case, prec, first=first + a, n_local=b - a, n_job=first + n)
+                                     for a, b in zip(cuts[:-1], cuts[1:])], LR)
+    assert rec[:, 12].tolist() == [b - a for a, b in zip(cuts[:-1], cuts[1:])] and not rec[:, 13:].any()
+    total = rec[:, :12].sum(axis=0)
+    for k in range(6):
+        scale = math.sqrt(n * whole.sumsq[k])
+        assert abs(total[2 * k] - whole.sum[k]) <= 1e-12 * scale, (k, total[2 * k], whole.sum[k])
+        assert abs(total[2 * k + 1] - whole.sumsq[k]) <= 1e-12 * whole.sumsq[k], (k, total[2 * k + 1], whole.sumsq[k])
+    assert all(whole.sumsq[k] > 0 for k in range(5)) and whole.sumsq[5] == 0.0
+    want, tol, left = gc.wanted(case, prec, shard + 1)
+    assert not left.any()
+    err, bound = np.abs(rec[0, 0:12:2] - want.sum(axis=0)), tol.sum(axis=0)
+    print(f"{case.name} prec {prec}: grid {whole.grid}; first shard, largest share of the tolerance {(err / np.maximum(bound, 1e-300)).max():.3f}")
+    assert (err <= bound).all(), (rec[0, 0:12:2], want.sum(axis=0), bound)
+    assert (np.abs(rec[0, 1:12:2] - (want * want).sum(axis=0)) <= square_tolerance(want, tol).sum(axis=0)).all()

@@ -10,6 +10,10 @@ import os
 import numpy as np
 import pytest
 
+import greeks_cases as gc
+import greeks_restate as gr
+from deep_inputs import check_deep_draws_differ
+
 pkg = importlib.import_module("monte-carlo-project-cuda_amd")
 capi = pkg.capi
 
@@ -125,3 +129,74 @@ def test_greeks_refusals_without_a_device(lib):
     s = capi.make_sim(1000, 12, flags=capi.FLAG_LOG_SPACE)
     assert L.mcamd_price_greeks(None, C.byref(opt), C.byref(s), capi.GREEKS_PATHWISE, C.byref(out)) == capi.ERR_INVALID
     assert b"ctx" in L.mcamd_last_error()
+
+
+# ---- the per-path inputs of tests/test_gpu_greeks.py (tests/greeks_cases.py): what their tolerance and their guards rest on --------
+
+
+def test_restatement_spreads():
+    """prints what the per-path tolerances are made of: per method, precision and estimator, the largest elementwise
+    difference between the two restatements over the method's cases (greeks_cases.spreads)"""
+    for method, name in ((gc.PW, "pathwise"), (gc.LR, "likelihood ratio")):
+        for prec in gc.PRECS:
+            s = gc.spreads(prec, method)
+            print(f"{name} prec {prec}: " + "  ".join(f"{n} {x:.3e}" for n, x in zip(capi.GREEK_NAMES, s)))
+            live = 6 if method == gc.PW else 5     # there is no LR theta
+            assert (s[:live] > 0).all() and (s[live:] == 0).all()
+            # the spread is rounding, not a flipped indicator: far below the estimator's own size in every case
+            mean = np.min([np.abs(gc.wanted(c, prec)[0]).mean(axis=0) for c in gc.CASES if c.method == method], axis=0)
+            assert (s[:5] < (1e-11 if prec == capi.F64 else 1e-4) * mean[:5]).all(), (s, mean)
+
+
+def test_inputs_keep_clear_of_the_jumps():
+    """the conditions under which a path may be left out, on the final case list: in fp32 at most MAX_LEFT_OUT of a case's
+    paths lie within NEAR of a jump, in fp64 (where nothing is left out) every path is 1e-6 or more away — 10^8 times the
+    rounding of an fp64 exponent — and both restatements of a precision agree on which of the compared paths pay.  The
+    shards of the small-shard test are sums and can leave nothing out: none of their paths is near a jump."""
+    for case in gc.CASES + gc.SHARD_CASES:
+        n = gc.N_PATHS if case in gc.CASES else max(gc.shard_sizes(case))
+        opt = gc.option(case)
+        for prec in gc.PRECS:
+            r = gc.restated(case, prec, np.float64, n)
+            out = gc.left_out(case, prec, n).any(axis=1)
+            to_strike = np.abs(r.S_T / opt.K - 1.0).min()
+            to_barrier = np.abs(r.logs - math.log(opt.B / (opt.Sk or opt.S0))).min() if opt.use_window else math.inf
+            print(f"{case.name} prec {prec}: left out {out.sum()} of {n}, closest S_T / K - 1 {to_strike:.2e}, "
+                  f"closest ln(S_t / B) {to_barrier:.2e}, paying {(r.q[:, 0] != 0).mean():.3f}")
+            assert out.sum() <= (gc.MAX_LEFT_OUT if case in gc.CASES else 0), case.name
+            if prec == capi.F64:
+                assert not out.any() and (case.method == gc.LR or to_strike > 1e-6) and to_barrier > 1e-6
+            a, b = gc.restated(case, prec, gc.OWN[prec], n), gc.restated(case, prec, gc.OTHER[prec], n)
+            assert ((a.q[:, 0] != 0) == (b.q[:, 0] != 0))[~out].all(), case.name
+            if case.method == gc.PW:
+                assert ((a.S_T > opt.K) == (b.S_T > opt.K))[~out].all(), case.name
+
+
+def test_window_cases_pay_on_some_paths_and_not_on_others():
+    """not a vacuous window: the restated payoff is non-zero on a fifth of the paths or more and zero on a fifth or more,
+    and the window, not the strike alone, decides on some (but for the restart from 93.5, whose window shuts on no path:
+    the case after it restarts from 110 with a window that shuts at both ends)"""
+    for case in gc.WINDOW_CASES:
+        opt = gc.option(case)
+        for prec in gc.PRECS:
+            r = gc.restated(case, prec, np.float64)
+            paying = (r.q[:, 0] != 0).mean()
+            shut = ((r.S_T > opt.K) & (r.q[:, 0] == 0)).mean()
+            print(f"{case.name} prec {prec}: paying {paying:.3f}, in the money but outside the window {shut:.3f}")
+            assert 0.2 <= paying <= 0.8 and (shut > 0.05 or case is gc.ALWAYS_OPEN), (case.name, prec, paying, shut)
+
+
+@pytest.mark.parametrize("prec", gc.PRECS)
+def test_deep_draws_are_those_of_neither_shallow_word(oracle, prec):
+    """What makes the deep cases worth running: the deep normals share nothing with the streams a dropped high word of
+    the path id or of the seed lands on (tests/deep_inputs.py)."""
+    check_deep_draws_differ(lambda seed, first: gr.normals(oracle, prec, seed, range(first, first + 64), 7))
+
+
+def test_one_path_shards_restate_the_shard(oracle):
+    """restate() of a shard is restate() of its paths one by one: a path's samples depend on its global id alone"""
+    case = gc.WINDOW_CASES[-1]
+    whole = gc.restated(case, capi.F32, np.float64, 5)
+    for i in range(5):
+        one = gr.restate(oracle, gc.option(case), gc.sim(case, capi.F32, first=case.where[1] + i, n_local=1), case.method)
+        assert np.array_equal(one.q[0], whole.q[i]) and one.S_T[0] == whole.S_T[i] and one.count[0] == whole.count[i]
