@@ -860,6 +860,105 @@ int mcamd_price_asian_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mca
 int mcamd_asian_geometric_price_f64(double S0, double K, double T, double r, double v, uint32_t n_steps,
                                     int include_spot, int strike, int payoff, double *price);
 
+/* ---- Worst-of autocallable notes on d = 1..8 correlated assets: early redemption, snowball coupon, knock-in put ----
+ * Additive to ABI version 5: first carried by the build that ships csrc/autocall.hip (no struct of an earlier call
+ * changed, so MCAMD_ABI_VERSION stays 5; a caller finds out with dlsym).
+ * Notional 1; performances are relative to each asset's own spot, so there are no spots and no weights.  r and T come
+ * from opt; opt->S0, opt->v, opt->K and opt->B are ignored.  d = autocall->n_assets; dt = T / n_steps.
+ *   Log-returns.  X_{j,i} and the normals z_{i,k} are exactly those of mcamd_price_basket: the same Cholesky factor,
+ *       drifts and coefficients in the exponent units of the path precision, the same chain of fused multiply-adds in
+ *       ascending k from the drift, the same Philox subsequence (the GLOBAL path id), block and slot order.
+ *       l_i = min_j X_{j,i} is the log of the worst performance after step i, in the path precision.
+ *   Observation dates q = 1..M at the ends of steps s_q = q observe_every, M = n_steps / observe_every; t_q = s_q dt.
+ *   Levels and payments, built on the host in fp64:  L_q = call_level - (q - 1) call_step_down, and ln L_q narrowed
+ *       once to the path precision in exponent units;  pay_q = (1 + q coupon) e^{r (T - t_q)}, the redemption with its
+ *       snowball coupon carried to maturity money, kept as a double.
+ *   Autocall.  The path is called at the first date q >= first_call_date with l_{s_q} >= ln L_q (compared in the path
+ *       precision); date M, maturity, is one of them.  A called path has y = pay_q exactly.
+ *   Knock-in, compared in the path precision as the basket barrier is:
+ *       MCAMD_AUTOCALL_KI_NONE         never;
+ *       MCAMD_AUTOCALL_KI_AT_MATURITY  hit if l_n <= ln ki_level;
+ *       MCAMD_AUTOCALL_KI_EVERY_STEP   hit if l_i <= ln ki_level at any step end i = 1..n.
+ *   A path never called has y = min(A_n, 1) if knocked in and y = 1 otherwise, with A_n = e^{l_n} through the
+ *       exponential that ends a log-space path, formed once in fp64.  At date M the call test comes first: a path
+ *       called there is paid pay_M whatever its knock-in state.
+ *   price = exp(-rT) mean(y), std_err as in mcamd_finalize: y is maturity money, so mcamd_finalize and
+ *       mcamd_finalize_stats serve unchanged although the payment time differs from path to path.
+ * No exponential is taken before maturity.  A wavefront whose lanes have all been called leaves the step loop at the
+ * end of its step group (the steps that consume whole Philox blocks: 1, 2 or 4).
+ * d_samples (nullable, device): n_paths_local values of the path precision; [local path] receives y, (float)pay_q for a
+ * called path in fp32.
+ * res: price / std_err / ci_* / sum / sumsq / n; n_called = the paths called, sum_t_call = the sum of their t_q,
+ * n_knocked_in = the paths not called and knocked in; work_steps = 64 x the steps each wavefront ran, live_steps = the
+ * lane-steps of paths not yet called (s_q of a called path, n_steps of any other); kernel_ms / total_ms / grid / block.
+ * The enqueue form leaves {sum, sumsq, n_called, sum_t_call, n_knocked_in, n} in d_stats (device, >= 6 doubles):
+ * mcamd_finalize_stats with control_variate = 0 and one all-reduce of 6 doubles serve it, and mcamd_enqueued_kernel_ms
+ * covers it.
+ * Requirements (MCAMD_ERR_INVALID before any device work and before the context is looked at): opt, sim, autocall, res
+ * non-NULL; what mcamd_price_basket refuses of n_assets, v and corr, with the same Cholesky pivot rule; reserved[0] ==
+ * reserved[1] == 0; ki_monitoring in range; observe_every >= 1, n_steps % observe_every == 0 and
+ * 1 <= M <= MCAMD_AUTOCALL_MAX_DATES; 1 <= first_call_date <= M; coupon finite and >= 0; call_level finite;
+ * call_step_down finite and >= 0; L_M > 0; with a knock-in 0 < ki_level <= 1 and ki_level < L_M (ki_level is ignored
+ * without one); use_window, P1, P2, Ik, Sk, Tk and opt->dt all 0; sim->flags 0 or MCAMD_FLAG_LOG_SPACE; and what
+ * mcamd_price_paths refuses on sim.  corr entries beyond n_assets are ignored, as is v beyond it.  An empty shard
+ * returns zeros and launches nothing; its enqueue form writes a zero record in stream order.
+ * Out of scope: memory or conditional coupons (the coupon is paid with the redemption only), continuous knock-in
+ * (the minimum of correlated Brownian bridges has no closed-form law), Greeks, a mcamd_group_* form and a shim name
+ * (the reference has no such product).  Multi-GPU: every rank prices its shard (a path's sample depends on its global
+ * id alone); the 6-double records add.  New. */
+#define MCAMD_AUTOCALL_MAX_DATES 64
+#define MCAMD_AUTOCALL_KI_NONE 0
+#define MCAMD_AUTOCALL_KI_AT_MATURITY 1
+#define MCAMD_AUTOCALL_KI_EVERY_STEP 2
+
+typedef struct mcamd_autocall {
+    int32_t n_assets;         /* d, 1..MCAMD_BASKET_MAX_ASSETS */
+    int32_t ki_monitoring;    /* MCAMD_AUTOCALL_KI_* */
+    uint32_t observe_every;   /* steps between observation dates; divides n_steps */
+    uint32_t first_call_date; /* 1..M: the first date the note can be called at */
+    int32_t reserved[2];      /* must be 0 */
+    double call_level;        /* L_1, as a performance (1 = the spots) */
+    double call_step_down;    /* L_q = call_level - (q - 1) call_step_down */
+    double coupon;            /* per date, snowball: a path called at date q receives 1 + q coupon */
+    double ki_level;          /* as a performance, in (0, 1] and below L_M */
+    double v[8];              /* volatilities */
+    double corr[64];          /* correlations, row-major with stride 8 */
+} mcamd_autocall;
+
+typedef struct mcamd_autocall_result {
+    double price;          /* exp(-rT) * sum / n */
+    double std_err;
+    double ci_lo;          /* price -/+ 1.96 std_err */
+    double ci_hi;
+    double sum;            /* sum of the samples (maturity money) */
+    double sumsq;
+    uint64_t n;            /* paths in the shard */
+    uint64_t n_called;     /* of them, called at some date (maturity included) */
+    double sum_t_call;     /* sum of t_q over the called paths: sum_t_call / n_called is the mean call time */
+    uint64_t n_knocked_in; /* paths not called and knocked in */
+    double work_steps;     /* 64 x the steps each wavefront ran */
+    double live_steps;     /* lane-steps of paths not yet called */
+    float kernel_ms;
+    float total_ms;
+    uint32_t grid;
+    uint32_t block;
+} mcamd_autocall_result;
+
+int mcamd_price_autocall(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_autocall *autocall,
+                         void *d_samples, mcamd_autocall_result *res);
+int mcamd_price_autocall_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                                 const mcamd_autocall *autocall, void *d_samples, double *d_stats);
+/* Host closed form of the note on one asset with one date (d = 1, M = 1), for MCAMD_AUTOCALL_KI_NONE and
+ * MCAMD_AUTOCALL_KI_AT_MATURITY.  With d2(x) = (-ln x + (r - v^2/2) T) / (v sqrt T), d1 = d2 + v sqrt T, L = call_level,
+ * B = ki_level, c = coupon:
+ *   price = e^{-rT} [(1 + c) N(d2(L)) + (N(d2(B)) - N(d2(L))) + e^{rT} N(-d1(B))]      (knock-in at maturity)
+ *   price = e^{-rT} [(1 + c) N(d2(L)) + 1 - N(d2(L))]                                   (no knock-in)
+ * N is the erfc form of mcamd_bs_call_f64.  Makes the refusals of mcamd_price_autocall that these arguments can meet:
+ * T and v finite and positive, r finite, coupon finite and >= 0, call_level finite and positive, with a knock-in
+ * 0 < ki_level <= 1 and ki_level < call_level; and refuses MCAMD_AUTOCALL_KI_EVERY_STEP, which has no closed form. */
+int mcamd_autocall_single_date_price_f64(double T, double r, double v, double call_level, double coupon,
+                                         double ki_level, int ki_monitoring, double *price);
+
 /* Host: discount + mean + standard error + 95% CI from (sum, sumsq, n) — after an all-reduce
  * over shards, or directly.  Fills price/std_err/ci_* (and copies sum/sumsq/n) in *res. */
 int mcamd_finalize(double sum, double sumsq, uint64_t n, double r, double T, mcamd_result *res);

@@ -30,6 +30,8 @@ LOOKBACK_FLOATING, LOOKBACK_FIXED = 0, 1
 ASIAN_ARITHMETIC, ASIAN_GEOMETRIC = 0, 1
 ASIAN_FIXED, ASIAN_FLOATING = 0, 1
 ASIAN_CONTROL_NONE, ASIAN_CONTROL_GEOMETRIC = 0, 1
+AUTOCALL_MAX_DATES = 64
+AUTOCALL_KI_NONE, AUTOCALL_KI_AT_MATURITY, AUTOCALL_KI_EVERY_STEP = 0, 1, 2
 BASKET_MAX_ASSETS = 8
 BASKET_ARITHMETIC, BASKET_GEOMETRIC, BASKET_BEST_OF, BASKET_WORST_OF = 0, 1, 2, 3
 BASKET_NO_BARRIER, BASKET_DOWN_OUT, BASKET_DOWN_IN, BASKET_UP_OUT, BASKET_UP_IN = 0, 1, 2, 3, 4
@@ -52,6 +54,7 @@ EXPORTS = [
     "mcamd_price_lookback", "mcamd_price_lookback_enqueue", "mcamd_lookback_price_f64",
     "mcamd_price_basket", "mcamd_price_basket_enqueue", "mcamd_basket_geometric_price_f64", "mcamd_exchange_price_f64",
     "mcamd_price_asian", "mcamd_price_asian_enqueue", "mcamd_asian_geometric_price_f64",
+    "mcamd_price_autocall", "mcamd_price_autocall_enqueue", "mcamd_autocall_single_date_price_f64",
 ]
 
 
@@ -149,6 +152,26 @@ class Asian(C.Structure):
     geometric average serves as control variate."""
     _fields_ = [("average", C.c_int32), ("strike", C.c_int32), ("payoff", C.c_int32), ("include_spot", C.c_int32),
                 ("control", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Autocall(C.Structure):
+    """mcamd_autocall: the terms of the worst-of autocallable note mcamd_price_autocall prices, and its assets."""
+    _fields_ = [("n_assets", C.c_int32), ("ki_monitoring", C.c_int32), ("observe_every", C.c_uint32),
+                ("first_call_date", C.c_uint32), ("reserved", C.c_int32 * 2), ("call_level", C.c_double),
+                ("call_step_down", C.c_double), ("coupon", C.c_double), ("ki_level", C.c_double),
+                ("v", C.c_double * 8), ("corr", C.c_double * 64)]
+
+
+class AutocallResult(C.Structure):
+    """mcamd_autocall_result"""
+    _fields_ = [("price", C.c_double), ("std_err", C.c_double), ("ci_lo", C.c_double), ("ci_hi", C.c_double),
+                ("sum", C.c_double), ("sumsq", C.c_double), ("n", C.c_uint64), ("n_called", C.c_uint64),
+                ("sum_t_call", C.c_double), ("n_knocked_in", C.c_uint64), ("work_steps", C.c_double),
+                ("live_steps", C.c_double), ("kernel_ms", C.c_float), ("total_ms", C.c_float), ("grid", C.c_uint32),
+                ("block", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class DeviceInfo(C.Structure):
@@ -253,6 +276,10 @@ def load() -> C.CDLL:
     L.mcamd_price_asian.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Asian), vp, C.POINTER(Result)]
     L.mcamd_price_asian_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Asian), vp, vp]
     L.mcamd_asian_geometric_price_f64.argtypes = [f64, f64, f64, f64, f64, C.c_uint32, i32, i32, i32, C.POINTER(f64)]
+    L.mcamd_price_autocall.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Autocall), vp,
+                                       C.POINTER(AutocallResult)]
+    L.mcamd_price_autocall_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Autocall), vp, vp]
+    L.mcamd_autocall_single_date_price_f64.argtypes = [f64, f64, f64, f64, f64, f64, i32, C.POINTER(f64)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("mcamd_abi_version",):
@@ -357,6 +384,29 @@ def asian_geometric_price_f64(S0, K, T, r, sigma, n_steps, include_spot=0, strik
     """closed form of the discrete geometric-average option over the n_steps step ends (and t = 0 with include_spot)"""
     p = C.c_double(0)
     _check(load().mcamd_asian_geometric_price_f64(S0, K, T, r, sigma, n_steps, include_spot, strike, payoff, C.byref(p)))
+    return p.value
+
+
+def make_autocall(v, corr, observe_every=1, call_level=1.0, coupon=0.0, ki_level=0.0,
+                  ki_monitoring=AUTOCALL_KI_NONE, call_step_down=0.0, first_call_date=1) -> Autocall:
+    """v: d volatilities (d at most BASKET_MAX_ASSETS); corr: d x d (nested sequences or an array)."""
+    d = len(v)
+    if not 1 <= d <= BASKET_MAX_ASSETS or len(corr) != d or any(len(row) != d for row in corr):
+        raise ValueError(f"an autocallable takes 1..{BASKET_MAX_ASSETS} assets, v of d and corr of d x d values")
+    a = Autocall(d, ki_monitoring, observe_every, first_call_date)
+    a.call_level, a.call_step_down, a.coupon, a.ki_level = call_level, call_step_down, coupon, ki_level
+    for j in range(d):
+        a.v[j] = float(v[j])
+        for k in range(d):
+            a.corr[8 * j + k] = float(corr[j][k])
+    return a
+
+
+def autocall_single_date_price_f64(T, r, sigma, call_level, coupon, ki_level=0.0, ki_monitoring=AUTOCALL_KI_NONE) -> float:
+    """closed form of the autocallable on one asset with one date (no knock-in, or a knock-in at maturity)"""
+    p = C.c_double(0)
+    _check(load().mcamd_autocall_single_date_price_f64(T, r, sigma, call_level, coupon, ki_level, ki_monitoring,
+                                                       C.byref(p)))
     return p.value
 
 
@@ -527,6 +577,20 @@ class Context:
         finalize_stats, with control_variate=True for a controlled job)."""
         _check(self._L.mcamd_price_asian_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(asian), _ptr(samples),
                                                  _ptr(stats)))
+
+    def price_autocall(self, opt: Option, sim: Sim, autocall: Autocall, samples=None) -> AutocallResult:
+        """Worst-of autocallable note (mcamd_price_autocall): r and T come from opt.  samples: optional device tensor of
+        n_paths_local values of the path precision that receives every path's sample, in maturity money."""
+        res = AutocallResult()
+        _check(self._L.mcamd_price_autocall(self._h, C.byref(opt), C.byref(sim), C.byref(autocall), _ptr(samples),
+                                            C.byref(res)))
+        return res
+
+    def price_autocall_enqueue(self, opt: Option, sim: Sim, autocall: Autocall, stats, samples=None) -> None:
+        """Asynchronous: leaves {sum, sumsq, n_called, sum_t_call, n_knocked_in, n} in the device tensor `stats`
+        (>= 6 doubles; finalize_stats without the control variate)."""
+        _check(self._L.mcamd_price_autocall_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(autocall),
+                                                    _ptr(samples), _ptr(stats)))
 
     def price_basket(self, opt: Option, sim: Sim, basket: Basket, samples=None) -> Result:
         """Basket, spread or rainbow option on correlated assets (mcamd_price_basket): r, T, K and the barrier level B

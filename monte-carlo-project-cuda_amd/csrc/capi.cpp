@@ -10,6 +10,7 @@
 #include "lookback.hpp"
 #include "basket.hpp"
 #include "asian.hpp"
+#include "autocall.hpp"
 
 #include "mcamd.h"
 
@@ -33,6 +34,9 @@ static_assert(sizeof(mcamd_barrier) == 16, "C ABI struct layout changed: bump MC
 static_assert(sizeof(mcamd_lookback) == 16, "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
 static_assert(sizeof(mcamd_basket) == 728, "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
 static_assert(sizeof(mcamd_asian) == 24, "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
+static_assert(sizeof(mcamd_autocall) == 632 && sizeof(mcamd_autocall_result) == 112,
+              "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
+static_assert(MCAMD_AUTOCALL_MAX_DATES == mcamd::kAutocallMaxDates, "the kernel's date tables hold MCAMD_AUTOCALL_MAX_DATES");
 
 namespace {
 
@@ -976,6 +980,105 @@ int prepare_basket(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim
                             }});
 }
 
+// The refusals of the autocall calls that depend on the note's terms alone (shared with the closed form); L_last is the
+// autocall level of the last date.
+int check_autocall_terms(double coupon, double call_level, double call_step_down, double L_last, int ki_monitoring,
+                         double ki_level)
+{
+    if (ki_monitoring < MCAMD_AUTOCALL_KI_NONE || ki_monitoring > MCAMD_AUTOCALL_KI_EVERY_STEP)
+        return fail(MCAMD_ERR_INVALID, "ki_monitoring must be MCAMD_AUTOCALL_KI_NONE (0) .. MCAMD_AUTOCALL_KI_EVERY_STEP "
+                                       "(2), got %d", ki_monitoring);
+    if (!std::isfinite(coupon) || !(coupon >= 0.0))
+        return fail(MCAMD_ERR_INVALID, "the coupon must be finite and >= 0, got %g", coupon);
+    if (!std::isfinite(call_level)) return fail(MCAMD_ERR_INVALID, "call_level must be finite, got %g", call_level);
+    if (!std::isfinite(call_step_down) || !(call_step_down >= 0.0))
+        return fail(MCAMD_ERR_INVALID, "call_step_down must be finite and >= 0, got %g", call_step_down);
+    if (!(L_last > 0.0))
+        return fail(MCAMD_ERR_INVALID, "the autocall level of the last date must be positive, got %g", L_last);
+    if (ki_monitoring != MCAMD_AUTOCALL_KI_NONE && (!(ki_level > 0.0) || !(ki_level <= 1.0) || !(ki_level < L_last)))
+        return fail(MCAMD_ERR_INVALID, "ki_level must lie in (0, 1] and below the autocall level of the last date "
+                                       "(ki_level = %g, last level = %g)", ki_level, L_last);
+    return MCAMD_OK;
+}
+
+// The autocall calls.  The kernel always finishes its own sum (one_path_per_thread_grid caps the grid); every refusal
+// that depends on the request alone comes before the context is looked at.
+template <typename Drive>
+int prepare_autocall(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_autocall *ac,
+                     void *d_samples, Drive drive)
+{
+    if (!opt || !sim || !ac) return fail(MCAMD_ERR_INVALID, "opt, sim and autocall must be non-NULL");
+    if (ac->reserved[0] != 0 || ac->reserved[1] != 0)
+        return fail(MCAMD_ERR_INVALID, "autocall->reserved must be 0, got {%d, %d}", ac->reserved[0], ac->reserved[1]);
+    // the assets through the basket's own checks and Cholesky factor: performances have spot 1 and weight 1
+    mcamd_basket assets{};
+    assets.n_assets = ac->n_assets;
+    assets.payoff = MCAMD_PAYOFF_PUT;
+    for (int j = 0; j < MCAMD_BASKET_MAX_ASSETS; ++j) {
+        assets.S0[j] = assets.w[j] = 1.0;
+        assets.v[j] = ac->v[j];
+    }
+    std::memcpy(assets.corr, ac->corr, sizeof assets.corr);
+    double L[64];
+    if (int rc = check_basket_assets(&assets, true, L)) return rc;
+    const int d = ac->n_assets;
+    if (ac->observe_every == 0 || sim->n_steps % ac->observe_every != 0)
+        return fail(MCAMD_ERR_INVALID, "observe_every must be >= 1 and divide n_steps (observe_every = %u, n_steps = %u)",
+                    ac->observe_every, sim->n_steps);
+    const uint32_t M = sim->n_steps / ac->observe_every;
+    if (M > MCAMD_AUTOCALL_MAX_DATES)   // M == 0 is n_steps == 0, which check_request refuses below
+        return fail(MCAMD_ERR_INVALID, "n_steps / observe_every = %u observation dates exceed MCAMD_AUTOCALL_MAX_DATES = %d",
+                    M, MCAMD_AUTOCALL_MAX_DATES);
+    if (M != 0 && (ac->first_call_date < 1 || ac->first_call_date > M))
+        return fail(MCAMD_ERR_INVALID, "first_call_date must be 1..%u (the observation dates), got %u", M,
+                    ac->first_call_date);
+    const double L_last = ac->call_level - (static_cast<double>(M) - 1.0) * ac->call_step_down;
+    if (int rc = check_autocall_terms(ac->coupon, ac->call_level, ac->call_step_down, M ? L_last : ac->call_level,
+                                      ac->ki_monitoring, ac->ki_level))
+        return rc;
+    // what the option itself contributes is r and T: the spot-start rules and those of mcamd_price_paths see a
+    // performance (spot 1) with each asset's volatility in the place of opt->S0 and opt->v; K and B are ignored
+    mcamd_option seen = *opt;
+    seen.S0 = 1.0;
+    seen.v = ac->v[0];
+    seen.K = seen.B = 0.0;
+    if (int rc = check_spot_start("autocallable", false, &seen, sim)) return rc;
+    for (int j = 0; j < d; ++j) {   // the fp64 exponent range, asset by asset, as prepare_basket bounds it
+        seen.v = ac->v[j] * std::sqrt(static_cast<double>(d));
+        if (int rc = check_request(&seen, sim)) return rc;
+        seen.v = ac->v[j];
+        if (int rc = check_request(&seen, sim)) return rc;
+    }
+    if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
+    if (sim->n_paths_local == 0) return drive(empty_call());
+    mcamd::AutocallJob job{};
+    job.path = make_plain_job(&seen, sim, false, true);
+    job.d = d;
+    const double dt = opt->T / static_cast<double>(sim->n_steps), sqdt = std::sqrt(dt);
+    for (int j = 0; j < d; ++j) {
+        job.drift[j] = (opt->r - 0.5 * ac->v[j] * ac->v[j]) * dt;
+        for (int k = 0; k <= j; ++k) job.coef[j * (j + 1) / 2 + k] = ac->v[j] * sqdt * L[8 * j + k];
+    }
+    job.observe_every = ac->observe_every;
+    job.n_dates = M;
+    job.first_call_date = ac->first_call_date;
+    for (uint32_t q = 1; q <= M; ++q) {
+        const double t_q = static_cast<double>(q * ac->observe_every) * dt;
+        job.log_level[q - 1] = std::log(ac->call_level - (static_cast<double>(q) - 1.0) * ac->call_step_down);
+        job.pay[q - 1] = (1.0 + static_cast<double>(q) * ac->coupon) * std::exp(opt->r * (opt->T - t_q));
+    }
+    job.dt = dt;
+    job.ki = ac->ki_monitoring != MCAMD_AUTOCALL_KI_NONE;
+    job.ki_every_step = ac->ki_monitoring == MCAMD_AUTOCALL_KI_EVERY_STEP;
+    job.log_ki = job.ki ? std::log(ac->ki_level) : 0.0;
+    job.d_samples = d_samples;
+    const uint32_t grid = mcamd::one_path_per_thread_grid(job.path.n_local);
+    return drive(DeviceCall{job.path.n_local, grid, mcamd::kAutocallRecord, 6, Finish::kFolded,
+                            [&](const mcamd::FinishSpec &fs) {
+                                return mcamd::launch_autocall(job, ctx->d_partials, grid, fs, ctx->stream);
+                            }});
+}
+
 // h(S0) replaces an estimate it exceeds (exercise at t = 0); returns whether it did
 bool floor_at_immediate(double h0, double *price, double *std_err)
 {
@@ -1904,6 +2007,61 @@ int mcamd_asian_geometric_price_f64(double S0, double K, double T, double r, dou
 {
     if (!price) return fail(MCAMD_ERR_INVALID, "price is NULL");
     return asian_geometric_price(S0, K, T, r, v, n_steps, include_spot, strike, payoff, price);
+}
+
+int mcamd_price_autocall(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_autocall *autocall,
+                         void *d_samples, mcamd_autocall_result *res)
+{
+    if (!res) return fail(MCAMD_ERR_INVALID, "opt, sim, autocall and res must be non-NULL");
+    std::memset(res, 0, sizeof *res);
+    return prepare_autocall(ctx, opt, sim, autocall, d_samples, [&](const auto &call) {
+        return run_sync(ctx, call, res, [&](const double *rec) {
+            // {sum, sumsq, paths called, sum of their call times, paths not called and knocked in, wave-steps, live}
+            const Estimate e = estimate(rec[0], rec[1], sim->n_paths_local, std::exp(-opt->r * opt->T));
+            res->sum = rec[0];
+            res->sumsq = rec[1];
+            res->n = sim->n_paths_local;
+            res->price = e.value;
+            res->std_err = e.std_err;
+            set_ci(res);
+            res->n_called = static_cast<uint64_t>(std::llround(rec[2]));
+            res->sum_t_call = rec[3];
+            res->n_knocked_in = static_cast<uint64_t>(std::llround(rec[4]));
+            res->work_steps = 64.0 * rec[5];   // wave-steps x 64 lanes
+            res->live_steps = rec[6];
+        });
+    });
+}
+
+int mcamd_price_autocall_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                                 const mcamd_autocall *autocall, void *d_samples, double *d_stats)
+{
+    return prepare_autocall(ctx, opt, sim, autocall, d_samples,
+                            [&](const auto &call) { return run_enqueue(ctx, call, d_stats); });
+}
+
+// One asset, one date: S_T / S_0 is lognormal, P[S_T / S_0 >= x] = N(d2(x)) and E[(S_T / S_0) 1{S_T / S_0 <= x}] =
+// e^{rT} N(-d1(x)).  Called above L: 1 + c; between B and L: 1; at or below B: the performance itself (B <= 1).
+int mcamd_autocall_single_date_price_f64(double T, double r, double v, double call_level, double coupon,
+                                         double ki_level, int ki_monitoring, double *price)
+{
+    if (!price) return fail(MCAMD_ERR_INVALID, "price is NULL");
+    *price = 0.0;
+    if (!(T > 0.0) || !(v > 0.0) || !std::isfinite(T) || !std::isfinite(r) || !std::isfinite(v))
+        return fail(MCAMD_ERR_INVALID, "the single-date autocall closed form needs finite T, v > 0 and a finite r");
+    if (int rc = check_autocall_terms(coupon, call_level, 0.0, call_level, ki_monitoring, ki_level)) return rc;
+    if (ki_monitoring == MCAMD_AUTOCALL_KI_EVERY_STEP)
+        return fail(MCAMD_ERR_INVALID, "the closed form covers MCAMD_AUTOCALL_KI_NONE and MCAMD_AUTOCALL_KI_AT_MATURITY: "
+                                       "a knock-in monitored at every step has none");
+    const auto N = [](double x) { return 0.5 * std::erfc(-x / std::sqrt(2.0)); };
+    const double s = v * std::sqrt(T);
+    const auto d2 = [&](double x) { return (-std::log(x) + (r - 0.5 * v * v) * T) / s; };
+    const double pL = N(d2(call_level));
+    double value = (1.0 + coupon) * pL;
+    if (ki_monitoring == MCAMD_AUTOCALL_KI_NONE) value += 1.0 - pL;
+    else value += (N(d2(ki_level)) - pL) + std::exp(r * T) * N(-(d2(ki_level) + s));
+    *price = std::exp(-r * T) * value;
+    return MCAMD_OK;
 }
 
 int mcamd_finalize(double sum, double sumsq, uint64_t n, double r, double T, mcamd_result *res)
