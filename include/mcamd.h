@@ -959,6 +959,96 @@ int mcamd_price_autocall_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const 
 int mcamd_autocall_single_date_price_f64(double T, double r, double v, double call_level, double coupon,
                                          double ki_level, int ki_monitoring, double *price);
 
+/* ---- Local volatility: European and single-barrier options under a surface sigma(t, ln(S / S0)), dividend yield q ----
+ * Additive to ABI version 5: first carried by the build that ships csrc/localvol.hip (no struct of an earlier call
+ * changed, so MCAMD_ABI_VERSION stays 5; a caller finds out with dlsym).  The first model here that is not constant-
+ * volatility geometric Brownian motion: log-Euler with the volatility frozen over each step, one normal per step from
+ * the stream mcamd_price_barrier draws from, nothing else drawn.  All path arithmetic is in the path precision; the
+ * sample is formed once per path in fp64.  opt->v is ignored (and may hold anything).
+ *   Surface.  n_t time slices of n_x nodes; node k lies at x_k = x_min + k dx, dx = (x_max - x_min) / (n_x - 1), in
+ *       x = ln(S / S0) with S0 = opt->S0 of the pricing call.  h_sigma: n_t rows of n_x doubles, [j * n_x + k] =
+ *       sigma_j(x_k), every entry finite and > 0.  The slices divide [0, opt->T] equally and are chosen by step index:
+ *       step i = 0..n-1 (from t_i to t_{i+1}, n = n_steps) uses row(i) = floor(i n_t / n), in 64-bit integers; n_t need
+ *       not divide n and may exceed it (rows are then skipped).
+ *   Interpolation in x (linear; flat outside [x_min, x_max], which is the clamp):
+ *       u = min(max((X - x_min) (1 / dx), 0), n_x - 1),  k = min(floor(u), n_x - 2),  f = u - k,
+ *       sigma = fma(f, slope_k, sigma_k),  slope_k = sigma_{k+1} - sigma_k.
+ *       slope_k and 1 / dx are formed in double on the host and then narrowed to the path precision, as sigma_k and
+ *       x_min are.
+ *   Step.  dt = T / n, X_0 = 0;  s_{i+1} = sigma(row(i), X_i);
+ *       X_{i+1} = X_i + (((r - q) - s_{i+1}^2 / 2) dt + s_{i+1} sqrt(dt) z_{i+1}),
+ *       z the path's normals exactly as mcamd_price_barrier draws them (Philox subsequence = the GLOBAL path id, blocks
+ *       0, 1, ...: 4 normals per block in fp32, 2 in fp64).  S_T = S0 e^{X_n}.
+ *   h(S) = (S - K)+ for MCAMD_PAYOFF_CALL, (K - S)+ for MCAMD_PAYOFF_PUT.
+ *   Barrier.  localvol->barrier is MCAMD_LOCALVOL_NO_BARRIER (y = h(S_T); monitoring is checked but plays no part) or
+ *       MCAMD_BARRIER_DOWN_OUT .. MCAMD_BARRIER_UP_IN at the level opt->B.  With b = ln(B / S0), the hit tests, the
+ *       distances d_i (d_0 = |b|), the survival weight w, the knock-out / knock-in samples and the cut Q (38 in fp64,
+ *       18 in fp32) are exactly those of mcamd_price_barrier, with the step's own frozen volatility in the bridge factor:
+ *           q_i = 2 d_{i-1} d_i / (s_i^2 dt).
+ *       That factor is the exact conditional survival probability where sigma does not depend on x (a surface that
+ *       varies in time only: the continuous sample is then unbiased at every n_steps); where sigma varies in x the
+ *       bridge between two step ends is not Brownian with volatility s_i and the weight carries an O(dt) bias, on top of
+ *       the O(dt) weak error of the Euler step itself.
+ *   price = exp(-rT) mean(y), std_err as in mcamd_finalize.
+ * A flat surface with q = 0 is mcamd_price_barrier sample for sample up to rounding; a surface that varies in time only
+ * prices to Black-Scholes (mcamd_bs_price_f64) at the rms volatility at every n_steps.
+ * A surface is an immutable object: mcamd_localvol_surface_create checks the grid and the table, builds the (sigma_k,
+ * slope_k) pair tables in fp32 and fp64 (the slope of a row's last node is 0 and never read) and uploads both,
+ * synchronously, into device memory the surface owns.  An enqueued call therefore never races a later upload.  Several
+ * surfaces may be alive in one context; a surface serves the context it was created on and no other; destroy it once
+ * the work enqueued with it has finished and before its context is destroyed.  mcamd_localvol_surface_destroy(NULL) is
+ * MCAMD_OK.
+ * d_samples (nullable, device): n_paths_local values of the path precision; [local path] receives y.
+ * res: filled as mcamd_price_barrier fills it; work_steps = 64 x the steps each wavefront ran (a knock-out wavefront
+ * leaves the step loop at the first Philox-block end where every lane is knocked), live_steps = the lane-steps of paths
+ * not yet knocked (every lane-step without a barrier).  The enqueue form leaves {sum, sumsq, 0, 0, 0, n} in d_stats:
+ * mcamd_finalize_stats serves it and mcamd_enqueued_kernel_ms covers it.
+ * Requirements (MCAMD_ERR_INVALID before any device work; for the pricing calls before the context is looked at): no
+ * NULL pointer (d_samples apart); grid: n_t >= 1, n_x >= 2, n_t n_x <= MCAMD_LOCALVOL_MAX_NODES, x_min and x_max finite,
+ * x_min < x_max, every table entry finite and > 0; payoff, barrier, monitoring in range; reserved == 0; q finite; with a
+ * barrier B > 0 and S0 strictly on the live side; use_window, P1, P2, Ik, Sk, Tk and opt->dt all 0; sim->flags 0 or
+ * MCAMD_FLAG_LOG_SPACE; what mcamd_price_paths refuses on sim (its fp64 exponent-range bound taken at r - q and the
+ * surface's largest entry); a surface created on another context.  An empty shard returns zeros and launches nothing.
+ * There is no mcamd_group_* form and no shim name: the reference has no such model.  New. */
+#define MCAMD_LOCALVOL_NO_BARRIER (-1)
+#define MCAMD_LOCALVOL_MAX_NODES 2048   /* n_t n_x: the fp64 pair table is then 32 KiB of LDS per workgroup */
+
+typedef struct mcamd_localvol_grid {
+    uint32_t n_t;        /* time slices, >= 1 */
+    uint32_t n_x;        /* nodes per slice, >= 2 */
+    double x_min;        /* ln(S / S0) of node 0 */
+    double x_max;        /* ln(S / S0) of node n_x - 1 */
+} mcamd_localvol_grid;
+
+typedef struct mcamd_localvol {
+    int32_t payoff;      /* MCAMD_PAYOFF_* */
+    int32_t barrier;     /* MCAMD_LOCALVOL_NO_BARRIER or MCAMD_BARRIER_* */
+    int32_t monitoring;  /* MCAMD_MONITOR_* */
+    int32_t reserved;    /* must be 0 */
+    double q;            /* continuous dividend yield */
+} mcamd_localvol;
+
+typedef struct mcamd_localvol_surface mcamd_localvol_surface;
+
+int mcamd_localvol_surface_create(mcamd_ctx *ctx, const mcamd_localvol_grid *grid, const double *h_sigma,
+                                  mcamd_localvol_surface **surface);
+int mcamd_localvol_surface_destroy(mcamd_localvol_surface *surface);
+int mcamd_price_localvol(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_localvol *localvol,
+                         const mcamd_localvol_surface *surface, void *d_samples, mcamd_result *res);
+int mcamd_price_localvol_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                                 const mcamd_localvol *localvol, const mcamd_localvol_surface *surface, void *d_samples,
+                                 double *d_stats);
+/* Host: the volatility step `step` (0 .. n_steps - 1) of a path standing at x = ln(S / S0) uses, by the definition
+ * above evaluated in double.  Refuses what mcamd_localvol_surface_create refuses of grid and h_sigma, n_steps == 0,
+ * step >= n_steps and a NaN x. */
+int mcamd_localvol_sigma_f64(const mcamd_localvol_grid *grid, const double *h_sigma, uint32_t n_steps, uint32_t step,
+                             double x, double *sigma);
+/* Host closed form: Black-Scholes with a continuous dividend yield q (Merton 1973),
+ *   call = S0 e^{-qT} N(d1) - K e^{-rT} N(d2),  put = K e^{-rT} N(-d2) - S0 e^{-qT} N(-d1),
+ *   d1 = (ln(S0 / K) + (r - q + v^2/2) T) / (v sqrt T),  d2 = d1 - v sqrt T,  N the erfc form of mcamd_bs_call_f64.
+ * Refuses non-finite arguments, S0, K, T or v <= 0 and a bad payoff. */
+int mcamd_bs_price_f64(double S0, double K, double T, double r, double q, double v, int payoff, double *price);
+
 /* Host: discount + mean + standard error + 95% CI from (sum, sumsq, n) — after an all-reduce
  * over shards, or directly.  Fills price/std_err/ci_* (and copies sum/sumsq/n) in *res. */
 int mcamd_finalize(double sum, double sumsq, uint64_t n, double r, double T, mcamd_result *res);

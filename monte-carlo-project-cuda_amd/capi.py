@@ -32,6 +32,8 @@ ASIAN_FIXED, ASIAN_FLOATING = 0, 1
 ASIAN_CONTROL_NONE, ASIAN_CONTROL_GEOMETRIC = 0, 1
 AUTOCALL_MAX_DATES = 64
 AUTOCALL_KI_NONE, AUTOCALL_KI_AT_MATURITY, AUTOCALL_KI_EVERY_STEP = 0, 1, 2
+LOCALVOL_NO_BARRIER = -1
+LOCALVOL_MAX_NODES = 2048
 BASKET_MAX_ASSETS = 8
 BASKET_ARITHMETIC, BASKET_GEOMETRIC, BASKET_BEST_OF, BASKET_WORST_OF = 0, 1, 2, 3
 BASKET_NO_BARRIER, BASKET_DOWN_OUT, BASKET_DOWN_IN, BASKET_UP_OUT, BASKET_UP_IN = 0, 1, 2, 3, 4
@@ -55,6 +57,8 @@ EXPORTS = [
     "mcamd_price_basket", "mcamd_price_basket_enqueue", "mcamd_basket_geometric_price_f64", "mcamd_exchange_price_f64",
     "mcamd_price_asian", "mcamd_price_asian_enqueue", "mcamd_asian_geometric_price_f64",
     "mcamd_price_autocall", "mcamd_price_autocall_enqueue", "mcamd_autocall_single_date_price_f64",
+    "mcamd_localvol_surface_create", "mcamd_localvol_surface_destroy", "mcamd_price_localvol",
+    "mcamd_price_localvol_enqueue", "mcamd_localvol_sigma_f64", "mcamd_bs_price_f64",
 ]
 
 
@@ -174,6 +178,18 @@ class AutocallResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class LocalVolGrid(C.Structure):
+    """mcamd_localvol_grid: n_t time slices of n_x nodes, equally spaced in ln(S / S0) on [x_min, x_max]."""
+    _fields_ = [("n_t", C.c_uint32), ("n_x", C.c_uint32), ("x_min", C.c_double), ("x_max", C.c_double)]
+
+
+class LocalVol(C.Structure):
+    """mcamd_localvol: the payoff, the optional barrier with its monitoring, and the dividend yield
+    mcamd_price_localvol prices under a surface."""
+    _fields_ = [("payoff", C.c_int32), ("barrier", C.c_int32), ("monitoring", C.c_int32), ("reserved", C.c_int32),
+                ("q", C.c_double)]
+
+
 class DeviceInfo(C.Structure):
     _fields_ = [("name", C.c_char * 256), ("arch", C.c_char * 64), ("total_mem", C.c_uint64),
                 ("free_mem", C.c_uint64), ("compute_units", C.c_int32), ("wavefront_size", C.c_int32),
@@ -280,6 +296,14 @@ def load() -> C.CDLL:
                                        C.POINTER(AutocallResult)]
     L.mcamd_price_autocall_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Autocall), vp, vp]
     L.mcamd_autocall_single_date_price_f64.argtypes = [f64, f64, f64, f64, f64, f64, i32, C.POINTER(f64)]
+    L.mcamd_localvol_surface_create.argtypes = [vp, C.POINTER(LocalVolGrid), C.POINTER(f64), C.POINTER(vp)]
+    L.mcamd_localvol_surface_destroy.argtypes = [vp]
+    L.mcamd_price_localvol.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(LocalVol), vp, vp,
+                                       C.POINTER(Result)]
+    L.mcamd_price_localvol_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(LocalVol), vp, vp, vp]
+    L.mcamd_localvol_sigma_f64.argtypes = [C.POINTER(LocalVolGrid), C.POINTER(f64), C.c_uint32, C.c_uint32, f64,
+                                           C.POINTER(f64)]
+    L.mcamd_bs_price_f64.argtypes = [f64, f64, f64, f64, f64, f64, i32, C.POINTER(f64)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("mcamd_abi_version",):
@@ -407,6 +431,38 @@ def autocall_single_date_price_f64(T, r, sigma, call_level, coupon, ki_level=0.0
     p = C.c_double(0)
     _check(load().mcamd_autocall_single_date_price_f64(T, r, sigma, call_level, coupon, ki_level, ki_monitoring,
                                                        C.byref(p)))
+    return p.value
+
+
+def make_localvol(payoff=PAYOFF_CALL, barrier=LOCALVOL_NO_BARRIER, monitoring=MONITOR_DISCRETE, q=0.0) -> LocalVol:
+    return LocalVol(payoff, barrier, monitoring, 0, q)
+
+
+def make_localvol_grid(n_t, n_x, x_min, x_max) -> LocalVolGrid:
+    return LocalVolGrid(n_t, n_x, x_min, x_max)
+
+
+def _sigma_array(grid: LocalVolGrid, sigma):
+    """the table as n_t * n_x C doubles (any nested sequence or numpy array of that many finite-or-not values)"""
+    flat = [float(v) for row in sigma for v in (row if hasattr(row, "__iter__") else (row,))]
+    if len(flat) != grid.n_t * grid.n_x:
+        raise ValueError(f"sigma holds {len(flat)} values; the grid has n_t * n_x = {grid.n_t * grid.n_x} nodes")
+    return (C.c_double * len(flat))(*flat)
+
+
+def localvol_sigma_f64(grid, sigma, n_steps, step, x) -> float:
+    """the volatility step `step` of n_steps uses at x = ln(S / S0) (mcamd_localvol_sigma_f64); grid: a LocalVolGrid
+    or its (n_t, n_x, x_min, x_max)"""
+    g = grid if isinstance(grid, LocalVolGrid) else make_localvol_grid(*grid)
+    out = C.c_double(0)
+    _check(load().mcamd_localvol_sigma_f64(C.byref(g), _sigma_array(g, sigma), n_steps, step, x, C.byref(out)))
+    return out.value
+
+
+def bs_price_f64(S0, K, T, r, q, sigma, payoff=PAYOFF_CALL) -> float:
+    """Black-Scholes with a continuous dividend yield q"""
+    p = C.c_double(0)
+    _check(load().mcamd_bs_price_f64(S0, K, T, r, q, sigma, payoff, C.byref(p)))
     return p.value
 
 
@@ -550,6 +606,27 @@ class Context:
         """Asynchronous: leaves {sum, sumsq, 0, 0, 0, n} in the device tensor `stats` (>= 6 doubles; finalize_stats)."""
         _check(self._L.mcamd_price_barrier_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(barrier),
                                                    _ptr(samples), _ptr(stats)))
+
+    def localvol_surface(self, grid_args, sigma) -> "LocalVolSurface":
+        """An immutable local-volatility surface on this context (mcamd_localvol_surface_create).  grid_args: a
+        LocalVolGrid or its (n_t, n_x, x_min, x_max); sigma: n_t rows of n_x volatilities.  close() it (or use it as a
+        context manager) before the context is closed."""
+        return LocalVolSurface(self, grid_args, sigma)
+
+    def price_localvol(self, opt: Option, sim: Sim, localvol: LocalVol, surface: "LocalVolSurface", samples=None) -> Result:
+        """European or single-barrier option under a local-volatility surface (mcamd_price_localvol); opt.v is
+        ignored, opt.B is the barrier level.  samples: optional device tensor of n_paths_local values of the path
+        precision that receives each path's undiscounted sample."""
+        res = Result()
+        _check(self._L.mcamd_price_localvol(self._h, C.byref(opt), C.byref(sim), C.byref(localvol), surface._h,
+                                            _ptr(samples), C.byref(res)))
+        return res
+
+    def price_localvol_enqueue(self, opt: Option, sim: Sim, localvol: LocalVol, surface: "LocalVolSurface", stats,
+                               samples=None) -> None:
+        """Asynchronous: leaves {sum, sumsq, 0, 0, 0, n} in the device tensor `stats` (>= 6 doubles; finalize_stats)."""
+        _check(self._L.mcamd_price_localvol_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(localvol), surface._h,
+                                                    _ptr(samples), _ptr(stats)))
 
     def price_lookback(self, opt: Option, sim: Sim, lookback: Lookback, samples=None) -> Result:
         """Lookback option (mcamd_price_lookback).  samples: optional device tensor of n_paths_local values of the path
@@ -712,6 +789,35 @@ class Context:
         _check(self._L.mcamd_nmc_fused(self._h, C.byref(opt), C.byref(sim), outer_seed, layout, _ptr(prices),
                                        _ptr(counts), _ptr(point_prices), C.byref(res)))
         return res
+
+
+class LocalVolSurface:
+    """Owns one mcamd_localvol_surface: the pair tables of a local-volatility surface in the memory of one context's
+    device.  Immutable; several may be alive in one context."""
+
+    def __init__(self, ctx: Context, grid_args, sigma):
+        self._L = load()
+        self._h = C.c_void_p()
+        self.grid = grid_args if isinstance(grid_args, LocalVolGrid) else make_localvol_grid(*grid_args)
+        _check(self._L.mcamd_localvol_surface_create(ctx._h, C.byref(self.grid), _sigma_array(self.grid, sigma),
+                                                     C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            self._L.mcamd_localvol_surface_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 class Group:

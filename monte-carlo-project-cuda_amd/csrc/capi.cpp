@@ -11,9 +11,12 @@
 #include "basket.hpp"
 #include "asian.hpp"
 #include "autocall.hpp"
+#include "localvol.hpp"
 
 #include "mcamd.h"
 
+#include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -36,6 +39,9 @@ static_assert(sizeof(mcamd_basket) == 728, "C ABI struct layout changed: bump MC
 static_assert(sizeof(mcamd_asian) == 24, "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
 static_assert(sizeof(mcamd_autocall) == 632 && sizeof(mcamd_autocall_result) == 112,
               "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
+static_assert(sizeof(mcamd_localvol_grid) == 24 && sizeof(mcamd_localvol) == 24,
+              "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
+static_assert(MCAMD_LOCALVOL_MAX_NODES == mcamd::kLocalVolMaxNodes, "the kernel's LDS budget holds MCAMD_LOCALVOL_MAX_NODES");
 static_assert(MCAMD_AUTOCALL_MAX_DATES == mcamd::kAutocallMaxDates, "the kernel's date tables hold MCAMD_AUTOCALL_MAX_DATES");
 
 namespace {
@@ -90,6 +96,18 @@ struct mcamd_ctx {
     static constexpr uint32_t kRing = 64;
     hipEvent_t ring0[kRing] = {}, ring1[kRing] = {};
     uint64_t n_enqueued = 0;
+    uint64_t id = 0;   // unique per context of the process: what a local-volatility surface remembers of its owner
+};
+
+// An immutable local-volatility surface: the grid, the largest entry, and the two pair tables in device memory.
+struct mcamd_localvol_surface {
+    const mcamd_ctx *ctx = nullptr;
+    uint64_t ctx_id = 0;
+    int device = 0;
+    mcamd_localvol_grid grid = {};
+    double sigma_max = 0.0;
+    void *d_tables = nullptr;   // one allocation: n fp64 pairs, then n fp32 pairs
+    void *d_tab64 = nullptr, *d_tab32 = nullptr;
 };
 
 namespace {
@@ -695,6 +713,107 @@ int prepare_barrier(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *si
                             }});
 }
 
+// What mcamd_localvol_surface_create and the host lookup refuse of a grid and its table; *sigma_max (nullable) receives
+// the largest entry.
+int check_localvol_grid(const mcamd_localvol_grid *grid, const double *h_sigma, double *sigma_max)
+{
+    if (!grid || !h_sigma) return fail(MCAMD_ERR_INVALID, "grid and h_sigma must be non-NULL");
+    if (grid->n_t < 1 || grid->n_x < 2)
+        return fail(MCAMD_ERR_INVALID, "a surface needs n_t >= 1 and n_x >= 2, got n_t = %u, n_x = %u", grid->n_t, grid->n_x);
+    if (static_cast<uint64_t>(grid->n_t) * grid->n_x > MCAMD_LOCALVOL_MAX_NODES)
+        return fail(MCAMD_ERR_INVALID, "n_t * n_x = %llu nodes; at most %d fit the kernel's LDS table",
+                    static_cast<unsigned long long>(static_cast<uint64_t>(grid->n_t) * grid->n_x), MCAMD_LOCALVOL_MAX_NODES);
+    if (!std::isfinite(grid->x_min) || !std::isfinite(grid->x_max) || !(grid->x_min < grid->x_max))
+        return fail(MCAMD_ERR_INVALID, "the surface's axis needs finite x_min < x_max, got [%g, %g]", grid->x_min,
+                    grid->x_max);
+    double top = 0.0;
+    const uint32_t n = grid->n_t * grid->n_x;
+    for (uint32_t e = 0; e < n; ++e) {
+        if (!std::isfinite(h_sigma[e]) || !(h_sigma[e] > 0.0))
+            return fail(MCAMD_ERR_INVALID, "every surface entry must be finite and > 0: sigma[%u][%u] = %g", e / grid->n_x,
+                        e % grid->n_x, h_sigma[e]);
+        top = std::fmax(top, h_sigma[e]);
+    }
+    if (sigma_max) *sigma_max = top;
+    return MCAMD_OK;
+}
+
+// The local-volatility calls.  The kernel always finishes its own sum (one_path_per_thread_grid caps the grid); every
+// refusal that depends on the request alone comes before the context is looked at, and all that do not need the
+// surface before the surface is.  opt->v is ignored.
+template <typename Drive>
+int prepare_localvol(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_localvol *lv,
+                     const mcamd_localvol_surface *surface, void *d_samples, Drive drive)
+{
+    if (!opt || !sim || !lv) return fail(MCAMD_ERR_INVALID, "opt, sim, localvol and surface must be non-NULL");
+    if (lv->payoff != MCAMD_PAYOFF_CALL && lv->payoff != MCAMD_PAYOFF_PUT)
+        return fail(MCAMD_ERR_INVALID, "payoff must be MCAMD_PAYOFF_CALL (0) or MCAMD_PAYOFF_PUT (1), got %d", lv->payoff);
+    if (lv->barrier != MCAMD_LOCALVOL_NO_BARRIER && (lv->barrier < MCAMD_BARRIER_DOWN_OUT || lv->barrier > MCAMD_BARRIER_UP_IN))
+        return fail(MCAMD_ERR_INVALID, "localvol->barrier must be MCAMD_LOCALVOL_NO_BARRIER (-1) or MCAMD_BARRIER_DOWN_OUT (0) "
+                                       ".. MCAMD_BARRIER_UP_IN (3), got %d", lv->barrier);
+    if (lv->monitoring != MCAMD_MONITOR_DISCRETE && lv->monitoring != MCAMD_MONITOR_CONTINUOUS)
+        return fail(MCAMD_ERR_INVALID, "monitoring must be MCAMD_MONITOR_DISCRETE (0) or MCAMD_MONITOR_CONTINUOUS (1), "
+                                       "got %d", lv->monitoring);
+    if (lv->reserved != 0) return fail(MCAMD_ERR_INVALID, "localvol->reserved must be 0, got %d", lv->reserved);
+    if (!std::isfinite(lv->q)) return fail(MCAMD_ERR_INVALID, "the dividend yield q must be finite, got %g", lv->q);
+    const bool barrier = lv->barrier != MCAMD_LOCALVOL_NO_BARRIER;
+    if (barrier) {
+        if (int rc = check_barrier_kind(opt->S0, opt->B, lv->barrier, lv->payoff)) return rc;
+    }
+    if (!std::isfinite(opt->r)) return fail(MCAMD_ERR_INVALID, "option parameters must be finite with T > 0");
+    // the checks shared with the other calls, on a copy that carries no volatility of its own: everything they refuse
+    // of the option, the flags and sim, with the drift r - q alone in the fp64 exponent-range bound
+    mcamd_option seen = *opt;
+    seen.r = opt->r - lv->q;
+    seen.v = 1.0;
+    if (int rc = check_spot_start("local-volatility", false, &seen, sim)) return rc;
+    seen.v = 0.0;
+    if (int rc = check_request(&seen, sim)) return rc;
+    if (!(opt->S0 > 0.0)) return fail(MCAMD_ERR_INVALID, "local-volatility options need S0 > 0 (S0 = %g)", opt->S0);
+    if (!surface) return fail(MCAMD_ERR_INVALID, "opt, sim, localvol and surface must be non-NULL");
+    const double dt = opt->T / static_cast<double>(sim->n_steps);
+    if (sim->precision == MCAMD_F64) {
+        // check_request's bound with the largest drift and volatility any node can give
+        const double top = surface->sigma_max;
+        const double per_step = (std::fabs(seen.r) + 0.5 * top * top) * dt + 8.6 * top * std::sqrt(dt);
+        if (!(per_step < 700.0) || !(per_step * static_cast<double>(sim->n_steps) < 20000.0))
+            return fail(MCAMD_ERR_INVALID,
+                        "fp64 path: |drift| + 8.6 vol = %.3g per step over %u steps exceeds the exponent range "
+                        "(per step < 700, per path < 20000)", per_step, sim->n_steps);
+    }
+    if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
+    if (surface->ctx != ctx || surface->ctx_id != ctx->id)
+        return fail(MCAMD_ERR_INVALID, "the surface was created on another context");
+    if (sim->n_paths_local == 0) return drive(empty_call());
+    mcamd::LocalVolJob job;
+    job.seed = sim->seed;
+    job.path_offset = sim->path_offset;
+    job.n_local = sim->n_paths_local;
+    job.n_steps = sim->n_steps;
+    job.precision = sim->precision;
+    job.S0 = opt->S0;
+    job.K = opt->K;
+    job.B = opt->B;
+    job.mu = opt->r - lv->q;
+    job.dt = dt;
+    job.barrier = barrier;
+    job.up = lv->barrier == MCAMD_BARRIER_UP_OUT || lv->barrier == MCAMD_BARRIER_UP_IN;
+    job.out = lv->barrier == MCAMD_BARRIER_DOWN_OUT || lv->barrier == MCAMD_BARRIER_UP_OUT;
+    job.continuous = barrier && lv->monitoring == MCAMD_MONITOR_CONTINUOUS;
+    job.put = lv->payoff == MCAMD_PAYOFF_PUT;
+    job.n_t = surface->grid.n_t;
+    job.n_x = surface->grid.n_x;
+    job.x_min = surface->grid.x_min;
+    job.x_max = surface->grid.x_max;
+    job.d_table = sim->precision == MCAMD_F32 ? surface->d_tab32 : surface->d_tab64;
+    job.d_samples = d_samples;
+    const uint32_t grid = mcamd::one_path_per_thread_grid(job.n_local);
+    return drive(DeviceCall{job.n_local, grid, mcamd::kLocalVolRecord, 6, Finish::kFolded,
+                            [&](const mcamd::FinishSpec &fs) {
+                                return mcamd::launch_localvol(job, ctx->d_partials, grid, fs, ctx->stream);
+                            }});
+}
+
 // The refusals of the lookback calls that depend on the product alone (shared with the closed form).
 int check_lookback_kind(double K, int strike, int payoff)
 {
@@ -1142,6 +1261,8 @@ int mcamd_ctx_create(int device, void *hip_stream, mcamd_ctx **out)
     mcamd_ctx *ctx = new (std::nothrow) mcamd_ctx;
     if (!ctx) return fail(MCAMD_ERR_NOMEM, "out of host memory");
     ctx->device = device;
+    static std::atomic<uint64_t> next_id{0};
+    ctx->id = ++next_id;
     if (hip_stream) {
         ctx->stream = static_cast<hipStream_t>(hip_stream);
     } else {
@@ -2061,6 +2182,113 @@ int mcamd_autocall_single_date_price_f64(double T, double r, double v, double ca
     if (ki_monitoring == MCAMD_AUTOCALL_KI_NONE) value += 1.0 - pL;
     else value += (N(d2(ki_level)) - pL) + std::exp(r * T) * N(-(d2(ki_level) + s));
     *price = std::exp(-r * T) * value;
+    return MCAMD_OK;
+}
+
+int mcamd_localvol_surface_create(mcamd_ctx *ctx, const mcamd_localvol_grid *grid, const double *h_sigma,
+                                  mcamd_localvol_surface **surface)
+{
+    if (!surface) return fail(MCAMD_ERR_INVALID, "surface out-pointer is NULL");
+    *surface = nullptr;
+    double sigma_max = 0.0;
+    if (int rc = check_localvol_grid(grid, h_sigma, &sigma_max)) return rc;
+    if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
+    const uint32_t n_x = grid->n_x, n = grid->n_t * n_x;
+    // the pairs: sigma_k and slope_k = sigma_{k+1} - sigma_k, the slope formed in double, then narrowed
+    std::vector<mcamd::VolPair<double>> t64(n);
+    std::vector<mcamd::VolPair<float>> t32(n);
+    for (uint32_t e = 0; e < n; ++e) {
+        const double slope = (e % n_x == n_x - 1) ? 0.0 : h_sigma[e + 1] - h_sigma[e];
+        t64[e] = {h_sigma[e], slope};
+        t32[e] = {static_cast<float>(h_sigma[e]), static_cast<float>(slope)};
+    }
+    mcamd_localvol_surface *s = new (std::nothrow) mcamd_localvol_surface;
+    if (!s) return fail(MCAMD_ERR_NOMEM, "out of host memory");
+    s->ctx = ctx;
+    s->ctx_id = ctx->id;
+    s->device = ctx->device;
+    s->grid = *grid;
+    s->sigma_max = sigma_max;
+    const size_t bytes64 = n * sizeof(mcamd::VolPair<double>), bytes32 = n * sizeof(mcamd::VolPair<float>);
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e == hipSuccess) e = hipMalloc(&s->d_tables, bytes64 + bytes32);
+    if (e == hipSuccess) {
+        s->d_tab64 = s->d_tables;
+        s->d_tab32 = static_cast<char *>(s->d_tables) + bytes64;   // bytes64 is a multiple of 16
+        e = hipMemcpy(s->d_tab64, t64.data(), bytes64, hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess) e = hipMemcpy(s->d_tab32, t32.data(), bytes32, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        if (s->d_tables) (void)hipFree(s->d_tables);
+        delete s;
+        return fail(e == hipErrorOutOfMemory ? MCAMD_ERR_NOMEM : MCAMD_ERR_HIP, "surface upload: %s", hipGetErrorString(e));
+    }
+    *surface = s;
+    return MCAMD_OK;
+}
+
+int mcamd_localvol_surface_destroy(mcamd_localvol_surface *surface)
+{
+    if (!surface) return MCAMD_OK;
+    (void)hipSetDevice(surface->device);
+    if (surface->d_tables) (void)hipFree(surface->d_tables);
+    delete surface;
+    return MCAMD_OK;
+}
+
+int mcamd_price_localvol(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_localvol *localvol,
+                         const mcamd_localvol_surface *surface, void *d_samples, mcamd_result *res)
+{
+    if (!res) return fail(MCAMD_ERR_INVALID, "opt, sim, localvol, surface and res must be non-NULL");
+    zero_result(res);
+    return prepare_localvol(ctx, opt, sim, localvol, surface, d_samples, [&](const auto &call) {
+        return run_sync(ctx, call, res, [&](const double *rec) {
+            finalize_counted_into(rec, sim->n_paths_local, opt->r, opt->T, res);
+        });
+    });
+}
+
+int mcamd_price_localvol_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                                 const mcamd_localvol *localvol, const mcamd_localvol_surface *surface, void *d_samples,
+                                 double *d_stats)
+{
+    return prepare_localvol(ctx, opt, sim, localvol, surface, d_samples,
+                            [&](const auto &call) { return run_enqueue(ctx, call, d_stats); });
+}
+
+int mcamd_localvol_sigma_f64(const mcamd_localvol_grid *grid, const double *h_sigma, uint32_t n_steps, uint32_t step,
+                             double x, double *sigma)
+{
+    if (!sigma) return fail(MCAMD_ERR_INVALID, "sigma is NULL");
+    *sigma = 0.0;
+    if (int rc = check_localvol_grid(grid, h_sigma, nullptr)) return rc;
+    if (n_steps == 0 || step >= n_steps)
+        return fail(MCAMD_ERR_INVALID, "step = %u must lie in [0, n_steps = %u)", step, n_steps);
+    if (std::isnan(x)) return fail(MCAMD_ERR_INVALID, "x is NaN");
+    const uint64_t row = static_cast<uint64_t>(step) * grid->n_t / n_steps;
+    const double dx = (grid->x_max - grid->x_min) / static_cast<double>(grid->n_x - 1);
+    const double u = std::fmin(std::fmax((x - grid->x_min) * (1.0 / dx), 0.0), static_cast<double>(grid->n_x - 1));
+    const uint32_t k = std::min(static_cast<uint32_t>(u), grid->n_x - 2);
+    const double *s = h_sigma + row * grid->n_x + k;
+    *sigma = std::fma(u - static_cast<double>(k), s[1] - s[0], s[0]);
+    return MCAMD_OK;
+}
+
+int mcamd_bs_price_f64(double S0, double K, double T, double r, double q, double v, int payoff, double *price)
+{
+    if (!price) return fail(MCAMD_ERR_INVALID, "price is NULL");
+    *price = 0.0;
+    if (!(S0 > 0.0) || !(K > 0.0) || !(T > 0.0) || !(v > 0.0) || !std::isfinite(S0) || !std::isfinite(K) ||
+        !std::isfinite(T) || !std::isfinite(v) || !std::isfinite(r) || !std::isfinite(q))
+        return fail(MCAMD_ERR_INVALID, "Black-Scholes needs finite S0, K, T, v > 0 and finite r, q");
+    if (payoff != MCAMD_PAYOFF_CALL && payoff != MCAMD_PAYOFF_PUT)
+        return fail(MCAMD_ERR_INVALID, "payoff must be MCAMD_PAYOFF_CALL (0) or MCAMD_PAYOFF_PUT (1), got %d", payoff);
+    const double sqrtT = std::sqrt(T);
+    const double d1 = (std::log(S0 / K) + (r - q + 0.5 * v * v) * T) / (v * sqrtT), d2 = d1 - v * sqrtT;
+    const auto N = [](double x) { return 0.5 * std::erfc(-x / std::sqrt(2.0)); };
+    const double Sd = S0 * std::exp(-q * T), Kd = K * std::exp(-r * T);
+    *price = payoff == MCAMD_PAYOFF_CALL ? Sd * N(d1) - Kd * N(d2) : Kd * N(-d2) - Sd * N(-d1);
     return MCAMD_OK;
 }
 
