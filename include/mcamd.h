@@ -1048,6 +1048,76 @@ int mcamd_localvol_sigma_f64(const mcamd_localvol_grid *grid, const double *h_si
  *   d1 = (ln(S0 / K) + (r - q + v^2/2) T) / (v sqrt T),  d2 = d1 - v sqrt T,  N the erfc form of mcamd_bs_call_f64.
  * Refuses non-finite arguments, S0, K, T or v <= 0 and a bad payoff. */
 int mcamd_bs_price_f64(double S0, double K, double T, double r, double q, double v, int payoff, double *price);
+/* Host: the inverse of mcamd_bs_price_f64 in v.  With F = S0 e^{(r-q)T} and D = e^{-rT} the price of a vanilla lies
+ * strictly between lower = D max(+-(F - K), 0) (+ call, - put) and upper = S0 e^{-qT} (call) or K D (put), and grows
+ * with v from one to the other.  Returns the v with mcamd_bs_price_f64(S0, K, T, r, q, v, payoff) = price, found by a
+ * bracketed iteration — Newton steps kept inside the bracket, a bisection wherever a step would leave it or shrinks it
+ * too slowly — with a capped iteration count: it terminates for every admissible input, also one ulp inside a bound.
+ * Refuses (MCAMD_ERR_INVALID, *vol = NaN) non-finite arguments, S0, K or T <= 0, a bad payoff and a price that is not
+ * strictly inside (lower, upper).  New. */
+int mcamd_bs_implied_vol_f64(double S0, double K, double T, double r, double q, int payoff, double price, double *vol);
+
+/* ---- Local-volatility smile: n_expiries x n_strikes vanillas priced on ONE set of local-volatility paths ----
+ * Additive to ABI version 5: first carried by the build that ships csrc/localvol_smile.hip (MCAMD_ABI_VERSION stays 5;
+ * a caller finds out with dlsym).  "smile" is the strike-by-expiry set of options; "grid" stays the surface's node grid.
+ *   Paths.  Those of mcamd_price_localvol with MCAMD_LOCALVOL_NO_BARRIER, draw for draw and operation for operation:
+ *       the same surface lookup with row(i) = floor(i n_t / n_steps) over the WHOLE n_steps, the same log-Euler step in
+ *       the path precision with dt = T / n_steps, the same Philox subsequence (the GLOBAL path id).  Nothing else is
+ *       drawn.  opt->v and opt->K are ignored (and may hold anything).
+ *   Expiries.  h_expiry_steps[m], m = 0 .. n_expiries - 1, strictly ascending with 1 <= s_m <= n_steps.  Expiry m is the
+ *       time t_m = s_m (T / n_steps); its spot is S_m = S0 e^{X_{s_m}}, evaluated exactly as mcamd_price_localvol
+ *       evaluates S_T, in the path precision.  The last expiry need not be n_steps: the paths stop after the last
+ *       expiry, but the rows are still chosen against n_steps.
+ *   Nodes.  Node (m, k) pairs expiry m with the strike K_k = h_strikes[k], k = 0 .. n_strikes - 1, and has the
+ *       undiscounted sample h = max(S_m - K_k, 0) (MCAMD_PAYOFF_CALL) or max(K_k - S_m, 0) (MCAMD_PAYOFF_PUT; one
+ *       payoff for every node), formed in the path precision from K_k narrowed to the path precision, then widened
+ *       to double.  sum[m n_strikes + k] = sum of h and sumsq[m n_strikes + k] = sum of h^2 over the shard's paths,
+ *       both accumulated in fp64.
+ *   h_stats: 2 n_expiries n_strikes doubles, all the sums first, then all the sums of squares.
+ *   price[m][k] = e^{-r t_m} sum / n,  std_err[m][k] = e^{-r t_m} sqrt(s^2 / n) with mcamd_finalize's sample variance
+ *       (mcamd_finalize_smile).  NOTE the discount runs to the node's OWN expiry t_m, not over the full T as in every
+ *       other call of this header: node (m, k) is an option that expires at t_m.
+ *   res: n, kernel_ms (the path kernel), total_ms (with the sum of the per-wavefront records), grid, block;
+ *       work_steps = 64 x the steps each wavefront ran (s_last per wavefront that holds a path), live_steps = work_steps;
+ *       sum, sumsq, price, std_err, ci_lo, ci_hi are those of the LAST node (last expiry, last strike), finalized with
+ *       t of the last expiry.  Everything else in res is zero.
+ *   d_spots (nullable, device): n_expiries x n_paths_local values of the path precision, expiry-major:
+ *       [m n_paths_local + local path] receives S_m — for path-by-path tests, or for other European payoffs at those
+ *       dates.
+ *   The enqueue form leaves the same 2 n_expiries n_strikes doubles in d_stats, followed by one more double that holds
+ *   n (the shard's paths): d_stats has room for 2 n_expiries n_strikes + 1 doubles.  Shards add element by element;
+ *   mcamd_finalize_smile then serves the total.  mcamd_enqueued_kernel_ms covers the path kernel.  h_expiry_steps
+ *   and h_strikes are read before the call returns.  Results do not depend on earlier calls, and two runs of one job
+ *   give the same bits.
+ * mcamd_finalize_smile (host): stats as above with n paths, opt->r and opt->T, n_steps and the expiry steps of the job;
+ * h_price and h_std_err receive n_expiries x n_strikes doubles each, [m n_strikes + k].
+ * Requirements (MCAMD_ERR_INVALID before any device work; everything that needs neither the surface nor the context
+ * comes before either is looked at): no NULL pointer (d_spots apart); payoff in range; reserved == 0; n_expiries in
+ * 1 .. MCAMD_SMILE_MAX_EXPIRIES, n_strikes in 1 .. MCAMD_SMILE_MAX_STRIKES; expiry steps strictly ascending in
+ * 1 .. n_steps; every strike finite and > 0; q finite; use_window, P1, P2, Ik, Sk, Tk and opt->dt all 0; sim->flags 0 or
+ * MCAMD_FLAG_LOG_SPACE; what mcamd_price_paths refuses on sim (its fp64 exponent-range bound taken as
+ * mcamd_price_localvol takes it, at r - q and the surface's largest entry); S0 > 0; then the surface, a surface created
+ * on another context included; then the context.  An empty shard returns zeros and launches nothing.  There is no
+ * mcamd_group_* form and no shim name.  Barriers, mixed call / put nodes and Greeks are not offered.  New. */
+#define MCAMD_SMILE_MAX_STRIKES  64
+#define MCAMD_SMILE_MAX_EXPIRIES 32
+
+typedef struct mcamd_smile {
+    int32_t  payoff;       /* MCAMD_PAYOFF_CALL or _PUT, for every node */
+    uint32_t n_expiries;   /* 1 .. MCAMD_SMILE_MAX_EXPIRIES */
+    uint32_t n_strikes;    /* 1 .. MCAMD_SMILE_MAX_STRIKES */
+    int32_t  reserved;     /* must be 0 */
+    double   q;            /* continuous dividend yield */
+} mcamd_smile;
+
+int mcamd_price_localvol_smile(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_smile *smile,
+                               const uint32_t *h_expiry_steps, const double *h_strikes,
+                               const mcamd_localvol_surface *surface, void *d_spots, double *h_stats, mcamd_result *res);
+int mcamd_price_localvol_smile_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                                       const mcamd_smile *smile, const uint32_t *h_expiry_steps, const double *h_strikes,
+                                       const mcamd_localvol_surface *surface, void *d_spots, double *d_stats);
+int mcamd_finalize_smile(const double *stats, uint64_t n, const mcamd_option *opt, uint32_t n_steps,
+                         const mcamd_smile *smile, const uint32_t *h_expiry_steps, double *h_price, double *h_std_err);
 
 /* Host: discount + mean + standard error + 95% CI from (sum, sumsq, n) — after an all-reduce
  * over shards, or directly.  Fills price/std_err/ci_* (and copies sum/sumsq/n) in *res. */

@@ -34,6 +34,7 @@ AUTOCALL_MAX_DATES = 64
 AUTOCALL_KI_NONE, AUTOCALL_KI_AT_MATURITY, AUTOCALL_KI_EVERY_STEP = 0, 1, 2
 LOCALVOL_NO_BARRIER = -1
 LOCALVOL_MAX_NODES = 2048
+SMILE_MAX_STRIKES, SMILE_MAX_EXPIRIES = 64, 32
 BASKET_MAX_ASSETS = 8
 BASKET_ARITHMETIC, BASKET_GEOMETRIC, BASKET_BEST_OF, BASKET_WORST_OF = 0, 1, 2, 3
 BASKET_NO_BARRIER, BASKET_DOWN_OUT, BASKET_DOWN_IN, BASKET_UP_OUT, BASKET_UP_IN = 0, 1, 2, 3, 4
@@ -59,6 +60,7 @@ EXPORTS = [
     "mcamd_price_autocall", "mcamd_price_autocall_enqueue", "mcamd_autocall_single_date_price_f64",
     "mcamd_localvol_surface_create", "mcamd_localvol_surface_destroy", "mcamd_price_localvol",
     "mcamd_price_localvol_enqueue", "mcamd_localvol_sigma_f64", "mcamd_bs_price_f64",
+    "mcamd_bs_implied_vol_f64", "mcamd_price_localvol_smile", "mcamd_price_localvol_smile_enqueue", "mcamd_finalize_smile",
 ]
 
 
@@ -190,6 +192,13 @@ class LocalVol(C.Structure):
                 ("q", C.c_double)]
 
 
+class Smile(C.Structure):
+    """mcamd_smile: the payoff of every node, the numbers of expiries and strikes, and the dividend yield
+    mcamd_price_localvol_smile prices a strike-by-expiry set of vanillas with."""
+    _fields_ = [("payoff", C.c_int32), ("n_expiries", C.c_uint32), ("n_strikes", C.c_uint32), ("reserved", C.c_int32),
+                ("q", C.c_double)]
+
+
 class DeviceInfo(C.Structure):
     _fields_ = [("name", C.c_char * 256), ("arch", C.c_char * 64), ("total_mem", C.c_uint64),
                 ("free_mem", C.c_uint64), ("compute_units", C.c_int32), ("wavefront_size", C.c_int32),
@@ -304,6 +313,14 @@ def load() -> C.CDLL:
     L.mcamd_localvol_sigma_f64.argtypes = [C.POINTER(LocalVolGrid), C.POINTER(f64), C.c_uint32, C.c_uint32, f64,
                                            C.POINTER(f64)]
     L.mcamd_bs_price_f64.argtypes = [f64, f64, f64, f64, f64, f64, i32, C.POINTER(f64)]
+    L.mcamd_bs_implied_vol_f64.argtypes = [f64, f64, f64, f64, f64, i32, f64, C.POINTER(f64)]
+    u32p = C.POINTER(C.c_uint32)
+    L.mcamd_price_localvol_smile.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Smile), u32p,
+                                             C.POINTER(f64), vp, vp, C.POINTER(f64), C.POINTER(Result)]
+    L.mcamd_price_localvol_smile_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Smile), u32p,
+                                                     C.POINTER(f64), vp, vp, vp]
+    L.mcamd_finalize_smile.argtypes = [C.POINTER(f64), u64, C.POINTER(Option), C.c_uint32, C.POINTER(Smile), u32p,
+                                       C.POINTER(f64), C.POINTER(f64)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("mcamd_abi_version",):
@@ -464,6 +481,54 @@ def bs_price_f64(S0, K, T, r, q, sigma, payoff=PAYOFF_CALL) -> float:
     p = C.c_double(0)
     _check(load().mcamd_bs_price_f64(S0, K, T, r, q, sigma, payoff, C.byref(p)))
     return p.value
+
+
+def bs_implied_vol(S0, K, T, r, q, price, payoff=PAYOFF_CALL) -> float:
+    """the volatility at which bs_price_f64 gives `price` (mcamd_bs_implied_vol_f64); raises McamdError for a price
+    that is not strictly inside the no-arbitrage bounds"""
+    v = C.c_double(0)
+    _check(load().mcamd_bs_implied_vol_f64(S0, K, T, r, q, payoff, price, C.byref(v)))
+    return v.value
+
+
+def make_smile(n_expiries, n_strikes, payoff=PAYOFF_CALL, q=0.0) -> Smile:
+    return Smile(payoff, n_expiries, n_strikes, 0, q)
+
+
+def _smile_arrays(smile: Smile, expiry_steps, strikes):
+    """the expiry steps and strikes as C arrays of the lengths the smile states"""
+    steps, ks = [int(s) for s in expiry_steps], [float(k) for k in strikes]
+    if len(steps) != smile.n_expiries or len(ks) != smile.n_strikes:
+        raise ValueError(f"the smile states {smile.n_expiries} expiries and {smile.n_strikes} strikes; got {len(steps)} "
+                         f"and {len(ks)}")
+    return (C.c_uint32 * max(len(steps), 1))(*steps), (C.c_double * max(len(ks), 1))(*ks)
+
+
+def finalize_smile(stats, n, opt: Option, n_steps, smile: Smile, expiry_steps):
+    """(price, std_err) as (n_expiries, n_strikes) numpy arrays from the 2 n_e n_K sums of n paths
+    (mcamd_finalize_smile): every node is discounted to its own expiry"""
+    import numpy as np
+    nodes = smile.n_expiries * smile.n_strikes
+    arr = (C.c_double * (2 * nodes))(*[float(x) for x in list(stats)[:2 * nodes]])
+    steps, _ = _smile_arrays(smile, expiry_steps, [1.0] * smile.n_strikes)
+    price, se = (C.c_double * nodes)(), (C.c_double * nodes)()
+    _check(load().mcamd_finalize_smile(arr, int(n), C.byref(opt), n_steps, C.byref(smile), steps, price, se))
+    shape = (smile.n_expiries, smile.n_strikes)
+    return np.array(price[:]).reshape(shape), np.array(se[:]).reshape(shape)
+
+
+def implied_vols(S0, strikes, times, r, q, prices, payoff=PAYOFF_CALL):
+    """bs_implied_vol over a price array: prices[m][k] is the option at times[m] struck at strikes[k].  NaN where a
+    price lies outside the no-arbitrage bounds; never raises for that."""
+    import numpy as np
+    prices = np.asarray(prices, dtype=np.float64)
+    out = np.full(prices.shape, np.nan)
+    L, v = load(), C.c_double(0)
+    for m, t in enumerate(times):
+        for k, K in enumerate(strikes):
+            if L.mcamd_bs_implied_vol_f64(S0, float(K), float(t), r, q, payoff, float(prices[m, k]), C.byref(v)) == OK:
+                out[m, k] = v.value
+    return out
 
 
 def _ptr(t):
@@ -627,6 +692,30 @@ class Context:
         """Asynchronous: leaves {sum, sumsq, 0, 0, 0, n} in the device tensor `stats` (>= 6 doubles; finalize_stats)."""
         _check(self._L.mcamd_price_localvol_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(localvol), surface._h,
                                                     _ptr(samples), _ptr(stats)))
+
+    def price_localvol_smile(self, opt: Option, sim: Sim, smile: Smile, expiry_steps, strikes,
+                             surface: "LocalVolSurface", spots=None):
+        """n_expiries x n_strikes vanillas on one set of local-volatility paths (mcamd_price_localvol_smile); opt.v and
+        opt.K are ignored.  spots: optional device tensor of n_expiries x n_paths_local values of the path precision
+        that receives every path's spot at every expiry, expiry-major.  Returns (price, std_err, stats, res): price
+        and std_err as (n_expiries, n_strikes) numpy arrays, each node discounted to its own expiry; stats the
+        2 n_e n_K sums (all sums, then all sums of squares) as a numpy array; res as the header describes it."""
+        import numpy as np
+        steps, ks = _smile_arrays(smile, expiry_steps, strikes)
+        nodes = smile.n_expiries * smile.n_strikes
+        stats, res = (C.c_double * max(2 * nodes, 1))(), Result()
+        _check(self._L.mcamd_price_localvol_smile(self._h, C.byref(opt), C.byref(sim), C.byref(smile), steps, ks,
+                                                  surface._h, _ptr(spots), stats, C.byref(res)))
+        price, se = finalize_smile(stats, res.n, opt, sim.n_steps, smile, expiry_steps)
+        return price, se, np.array(stats[:2 * nodes]), res
+
+    def price_localvol_smile_enqueue(self, opt: Option, sim: Sim, smile: Smile, expiry_steps, strikes,
+                                     surface: "LocalVolSurface", stats, spots=None) -> None:
+        """Asynchronous: leaves the 2 n_e n_K sums and then n in the device tensor `stats` (>= 2 n_e n_K + 1 doubles;
+        finalize_smile serves the sums)."""
+        steps, ks = _smile_arrays(smile, expiry_steps, strikes)
+        _check(self._L.mcamd_price_localvol_smile_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(smile), steps, ks,
+                                                          surface._h, _ptr(spots), _ptr(stats)))
 
     def price_lookback(self, opt: Option, sim: Sim, lookback: Lookback, samples=None) -> Result:
         """Lookback option (mcamd_price_lookback).  samples: optional device tensor of n_paths_local values of the path

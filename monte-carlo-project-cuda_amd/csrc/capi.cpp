@@ -12,6 +12,7 @@
 #include "asian.hpp"
 #include "autocall.hpp"
 #include "localvol.hpp"
+#include "localvol_smile.hpp"
 
 #include "mcamd.h"
 
@@ -41,6 +42,9 @@ static_assert(sizeof(mcamd_autocall) == 632 && sizeof(mcamd_autocall_result) == 
               "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
 static_assert(sizeof(mcamd_localvol_grid) == 24 && sizeof(mcamd_localvol) == 24,
               "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
+static_assert(sizeof(mcamd_smile) == 24, "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
+static_assert(MCAMD_SMILE_MAX_STRIKES == mcamd::kSmileMaxStrikes && MCAMD_SMILE_MAX_EXPIRIES == mcamd::kSmileMaxExpiries,
+              "the smile kernel takes one strike per lane and MCAMD_SMILE_MAX_EXPIRIES expiry steps");
 static_assert(MCAMD_LOCALVOL_MAX_NODES == mcamd::kLocalVolMaxNodes, "the kernel's LDS budget holds MCAMD_LOCALVOL_MAX_NODES");
 static_assert(MCAMD_AUTOCALL_MAX_DATES == mcamd::kAutocallMaxDates, "the kernel's date tables hold MCAMD_AUTOCALL_MAX_DATES");
 
@@ -97,6 +101,10 @@ struct mcamd_ctx {
     hipEvent_t ring0[kRing] = {}, ring1[kRing] = {};
     uint64_t n_enqueued = 0;
     uint64_t id = 0;   // unique per context of the process: what a local-volatility surface remembers of its owner
+    // pinned: the node sums of a synchronous smile call (allocated by the first one, at the largest smile's size)
+    static constexpr uint32_t kSmileStats = 2 * MCAMD_SMILE_MAX_EXPIRIES * MCAMD_SMILE_MAX_STRIKES;
+    double *h_smile = nullptr;
+    double *h_smile_dev = nullptr;   // h_smile as the device addresses it
 };
 
 // An immutable local-volatility surface: the grid, the largest entry, and the two pair tables in device memory.
@@ -814,6 +822,109 @@ int prepare_localvol(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *s
                             }});
 }
 
+// The smile calls: mcamd_price_localvol's paths without a barrier, stopped at the expiry steps, every strike priced at
+// every expiry.  The refusals follow prepare_localvol's order: the request alone, then the surface, then the context.
+// drive(job, grid) runs the form's driver; grid == 0 is the empty shard.  opt->v and opt->K are ignored.
+template <typename Drive>
+int prepare_smile(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_smile *sm,
+                  const uint32_t *h_expiry_steps, const double *h_strikes, const mcamd_localvol_surface *surface,
+                  void *d_spots, Drive drive)
+{
+    if (!opt || !sim || !sm || !h_expiry_steps || !h_strikes)
+        return fail(MCAMD_ERR_INVALID, "opt, sim, smile, h_expiry_steps, h_strikes and surface must be non-NULL");
+    if (sm->payoff != MCAMD_PAYOFF_CALL && sm->payoff != MCAMD_PAYOFF_PUT)
+        return fail(MCAMD_ERR_INVALID, "payoff must be MCAMD_PAYOFF_CALL (0) or MCAMD_PAYOFF_PUT (1), got %d", sm->payoff);
+    if (sm->reserved != 0) return fail(MCAMD_ERR_INVALID, "smile->reserved must be 0, got %d", sm->reserved);
+    if (sm->n_expiries < 1 || sm->n_expiries > MCAMD_SMILE_MAX_EXPIRIES)
+        return fail(MCAMD_ERR_INVALID, "n_expiries must lie in 1 .. %d, got %u", MCAMD_SMILE_MAX_EXPIRIES, sm->n_expiries);
+    if (sm->n_strikes < 1 || sm->n_strikes > MCAMD_SMILE_MAX_STRIKES)
+        return fail(MCAMD_ERR_INVALID, "n_strikes must lie in 1 .. %d, got %u", MCAMD_SMILE_MAX_STRIKES, sm->n_strikes);
+    for (uint32_t m = 0; m < sm->n_expiries; ++m) {
+        const uint32_t before = m ? h_expiry_steps[m - 1] : 0;
+        if (h_expiry_steps[m] <= before || h_expiry_steps[m] > sim->n_steps)
+            return fail(MCAMD_ERR_INVALID, "expiry steps must be strictly ascending in 1 .. n_steps = %u: "
+                                           "h_expiry_steps[%u] = %u", sim->n_steps, m, h_expiry_steps[m]);
+    }
+    for (uint32_t k = 0; k < sm->n_strikes; ++k)
+        if (!std::isfinite(h_strikes[k]) || !(h_strikes[k] > 0.0))
+            return fail(MCAMD_ERR_INVALID, "every strike must be finite and > 0: h_strikes[%u] = %g", k, h_strikes[k]);
+    if (!std::isfinite(sm->q)) return fail(MCAMD_ERR_INVALID, "the dividend yield q must be finite, got %g", sm->q);
+    if (!std::isfinite(opt->r)) return fail(MCAMD_ERR_INVALID, "option parameters must be finite with T > 0");
+    // as prepare_localvol: the shared checks on a copy that carries neither a volatility nor a strike of its own
+    mcamd_option seen = *opt;
+    seen.r = opt->r - sm->q;
+    seen.K = 1.0;
+    seen.v = 1.0;
+    if (int rc = check_spot_start("local-volatility smile", false, &seen, sim)) return rc;
+    seen.v = 0.0;
+    if (int rc = check_request(&seen, sim)) return rc;
+    if (!(opt->S0 > 0.0)) return fail(MCAMD_ERR_INVALID, "local-volatility smile options need S0 > 0 (S0 = %g)", opt->S0);
+    if (!surface)
+        return fail(MCAMD_ERR_INVALID, "opt, sim, smile, h_expiry_steps, h_strikes and surface must be non-NULL");
+    const double dt = opt->T / static_cast<double>(sim->n_steps);
+    if (sim->precision == MCAMD_F64) {
+        // check_request's bound with the largest drift and volatility any node can give, as mcamd_price_localvol takes it
+        const double top = surface->sigma_max;
+        const double per_step = (std::fabs(seen.r) + 0.5 * top * top) * dt + 8.6 * top * std::sqrt(dt);
+        if (!(per_step < 700.0) || !(per_step * static_cast<double>(sim->n_steps) < 20000.0))
+            return fail(MCAMD_ERR_INVALID,
+                        "fp64 path: |drift| + 8.6 vol = %.3g per step over %u steps exceeds the exponent range "
+                        "(per step < 700, per path < 20000)", per_step, sim->n_steps);
+    }
+    if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
+    if (surface->ctx != ctx || surface->ctx_id != ctx->id)
+        return fail(MCAMD_ERR_INVALID, "the surface was created on another context");
+    mcamd::SmileJob job = {};
+    job.seed = sim->seed;
+    job.path_offset = sim->path_offset;
+    job.n_local = sim->n_paths_local;
+    job.n_steps = sim->n_steps;
+    job.precision = sim->precision;
+    job.S0 = opt->S0;
+    job.mu = opt->r - sm->q;
+    job.dt = dt;
+    job.put = sm->payoff == MCAMD_PAYOFF_PUT;
+    job.n_t = surface->grid.n_t;
+    job.n_x = surface->grid.n_x;
+    job.x_min = surface->grid.x_min;
+    job.x_max = surface->grid.x_max;
+    job.d_table = sim->precision == MCAMD_F32 ? surface->d_tab32 : surface->d_tab64;
+    job.n_expiries = sm->n_expiries;
+    job.n_strikes = sm->n_strikes;
+    std::copy(h_expiry_steps, h_expiry_steps + sm->n_expiries, job.expiry_steps);
+    std::copy(h_strikes, h_strikes + sm->n_strikes, job.strikes);
+    job.d_spots = d_spots;
+    const uint32_t grid = job.n_local ? mcamd::smile_grid(job.n_local, job.n_expiries, job.n_strikes, ctx->compute_units) : 0;
+    return drive(job, grid);
+}
+
+// price and standard error of every node of a smile from its 2 n_e n_K sums, each discounted to its own expiry
+void finalize_smile_into(const double *stats, uint64_t n, double r, double T, uint32_t n_steps, uint32_t n_e, uint32_t n_K,
+                         const uint32_t *expiry_steps, double *price, double *std_err)
+{
+    const uint32_t nodes = n_e * n_K;
+    const double dt = T / static_cast<double>(n_steps);
+    for (uint32_t m = 0; m < n_e; ++m) {
+        const double disc = std::exp(-r * (static_cast<double>(expiry_steps[m]) * dt));
+        for (uint32_t k = 0; k < n_K; ++k) {
+            const Estimate e = estimate(stats[m * n_K + k], stats[nodes + m * n_K + k], n, disc);
+            if (price) price[m * n_K + k] = e.value;
+            if (std_err) std_err[m * n_K + k] = e.std_err;
+        }
+    }
+}
+
+// Black-Scholes with a dividend yield at volatility v > 0 and its vega; every argument checked by the caller
+double bs_value(double S0, double K, double T, double r, double q, double v, bool call, double *vega)
+{
+    const double sqrtT = std::sqrt(T);
+    const double d1 = (std::log(S0 / K) + (r - q + 0.5 * v * v) * T) / (v * sqrtT), d2 = d1 - v * sqrtT;
+    const auto N = [](double x) { return 0.5 * std::erfc(-x / std::sqrt(2.0)); };
+    const double Sd = S0 * std::exp(-q * T), Kd = K * std::exp(-r * T);
+    if (vega) *vega = Sd * sqrtT * std::exp(-0.5 * d1 * d1) * 0.3989422804014327;
+    return call ? Sd * N(d1) - Kd * N(d2) : Kd * N(-d2) - Sd * N(-d1);
+}
+
 // The refusals of the lookback calls that depend on the product alone (shared with the closed form).
 int check_lookback_kind(double K, int strike, int payoff)
 {
@@ -1308,6 +1419,7 @@ int mcamd_ctx_destroy(mcamd_ctx *ctx)
     if (ctx->d_out) (void)hipFree(ctx->d_out);
     if (ctx->d_queue) (void)hipFree(ctx->d_queue);
     if (ctx->h_rec) (void)hipHostFree(ctx->h_rec);
+    if (ctx->h_smile) (void)hipHostFree(ctx->h_smile);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     if (ctx->ev2) (void)hipEventDestroy(ctx->ev2);
@@ -2257,6 +2369,104 @@ int mcamd_price_localvol_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const 
                             [&](const auto &call) { return run_enqueue(ctx, call, d_stats); });
 }
 
+// The smile's two launches on the context's stream: the walk into the per-wavefront records, then their sum into out.
+static int launch_smile_pair(mcamd_ctx *ctx, const mcamd::SmileJob &job, uint32_t grid, double *out, double n_value,
+                             hipEvent_t before, hipEvent_t after)
+{
+    HIP_TRY(hipEventRecord(before, ctx->stream));
+    HIP_TRY(mcamd::launch_localvol_smile(job, ctx->d_partials, grid, ctx->stream));
+    HIP_TRY(hipEventRecord(after, ctx->stream));
+    HIP_TRY(mcamd::launch_smile_finish(ctx->d_partials, grid * mcamd::kSmileWavesPerBlock, job.n_expiries * job.n_strikes,
+                                       out, n_value, ctx->stream));
+    return MCAMD_OK;
+}
+
+int mcamd_price_localvol_smile(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_smile *smile,
+                               const uint32_t *h_expiry_steps, const double *h_strikes,
+                               const mcamd_localvol_surface *surface, void *d_spots, double *h_stats, mcamd_result *res)
+{
+    if (!res || !h_stats) return fail(MCAMD_ERR_INVALID, "h_stats and res must be non-NULL");
+    zero_result(res);
+    return prepare_smile(ctx, opt, sim, smile, h_expiry_steps, h_strikes, surface, d_spots,
+                         [&](const mcamd::SmileJob &job, uint32_t grid) -> int {
+        const uint32_t nodes = job.n_expiries * job.n_strikes, n_stats = 2 * nodes;
+        std::fill(h_stats, h_stats + n_stats, 0.0);
+        if (job.n_local == 0) return MCAMD_OK;
+        HIP_TRY(hipSetDevice(ctx->device));
+        if (!ctx->h_smile) {
+            HIP_TRY(hipHostMalloc(&ctx->h_smile, mcamd_ctx::kSmileStats * sizeof(double), hipHostMallocDefault));
+            HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&ctx->h_smile_dev), ctx->h_smile, 0));
+        }
+        if (int rc = ensure_partials(ctx, grid * mcamd::kSmileWavesPerBlock, static_cast<int>(n_stats))) return rc;
+        // the finishing kernel writes the pinned buffer itself; all-ones bits there afterwards mean it never ran
+        arm_record(ctx->h_smile, static_cast<int>(n_stats));
+        if (int rc = launch_smile_pair(ctx, job, grid, ctx->h_smile_dev, -1.0, ctx->ev0, ctx->ev1)) return rc;
+        HIP_TRY(hipEventRecord(ctx->ev2, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        float kernel_ms = 0.0f, total_ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&kernel_ms, ctx->ev0, ctx->ev1));
+        HIP_TRY(hipEventElapsedTime(&total_ms, ctx->ev0, ctx->ev2));
+        if (record_unwritten(ctx->h_smile, static_cast<int>(n_stats)))
+            return fail(MCAMD_ERR_HIP, "the smile kernels left no result (the finishing kernel did not write every node)");
+        std::memcpy(h_stats, ctx->h_smile, n_stats * sizeof(double));
+        const uint32_t last = job.expiry_steps[job.n_expiries - 1];
+        finalize_into(h_stats[nodes - 1], h_stats[n_stats - 1], job.n_local, opt->r,
+                      static_cast<double>(last) * job.dt, res);
+        res->work_steps = 64.0 * static_cast<double>((job.n_local + 63) / 64) * static_cast<double>(last);
+        res->live_steps = res->work_steps;
+        res->kernel_ms = kernel_ms;
+        res->total_ms = total_ms;
+        res->grid = grid;
+        res->block = mcamd::kBlockThreads;
+        return MCAMD_OK;
+    });
+}
+
+int mcamd_price_localvol_smile_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                                       const mcamd_smile *smile, const uint32_t *h_expiry_steps, const double *h_strikes,
+                                       const mcamd_localvol_surface *surface, void *d_spots, double *d_stats)
+{
+    if (!d_stats) return fail(MCAMD_ERR_INVALID, "d_stats is NULL");
+    return prepare_smile(ctx, opt, sim, smile, h_expiry_steps, h_strikes, surface, d_spots,
+                         [&](const mcamd::SmileJob &job, uint32_t grid) -> int {
+        const uint32_t n_stats = 2 * job.n_expiries * job.n_strikes;
+        HIP_TRY(hipSetDevice(ctx->device));
+        const uint32_t slot = static_cast<uint32_t>(ctx->n_enqueued % mcamd_ctx::kRing);
+        if (job.n_local == 0) {
+            HIP_TRY(hipMemsetAsync(d_stats, 0, (n_stats + 1) * sizeof(double), ctx->stream));
+            HIP_TRY(hipEventRecord(ctx->ring0[slot], ctx->stream));
+            HIP_TRY(hipEventRecord(ctx->ring1[slot], ctx->stream));
+            ctx->n_enqueued++;
+            return MCAMD_OK;
+        }
+        const uint32_t waves = grid * mcamd::kSmileWavesPerBlock;
+        // growing the scratch buffer frees the old one: wait for work that may still read it
+        if (static_cast<uint64_t>(waves) * n_stats > ctx->partial_capacity) HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if (int rc = ensure_partials(ctx, waves, static_cast<int>(n_stats))) return rc;
+        if (int rc = launch_smile_pair(ctx, job, grid, d_stats, static_cast<double>(job.n_local), ctx->ring0[slot],
+                                       ctx->ring1[slot]))
+            return rc;
+        ctx->n_enqueued++;
+        return MCAMD_OK;
+    });
+}
+
+int mcamd_finalize_smile(const double *stats, uint64_t n, const mcamd_option *opt, uint32_t n_steps,
+                         const mcamd_smile *smile, const uint32_t *h_expiry_steps, double *h_price, double *h_std_err)
+{
+    if (!stats || !opt || !smile || !h_expiry_steps || !h_price || !h_std_err)
+        return fail(MCAMD_ERR_INVALID, "stats, opt, smile, h_expiry_steps, h_price and h_std_err must be non-NULL");
+    if (smile->n_expiries < 1 || smile->n_expiries > MCAMD_SMILE_MAX_EXPIRIES || smile->n_strikes < 1 ||
+        smile->n_strikes > MCAMD_SMILE_MAX_STRIKES)
+        return fail(MCAMD_ERR_INVALID, "n_expiries must lie in 1 .. %d and n_strikes in 1 .. %d", MCAMD_SMILE_MAX_EXPIRIES,
+                    MCAMD_SMILE_MAX_STRIKES);
+    if (n_steps == 0 || !(opt->T > 0.0) || !std::isfinite(opt->T) || !std::isfinite(opt->r))
+        return fail(MCAMD_ERR_INVALID, "a smile needs n_steps >= 1 and finite r and T > 0");
+    finalize_smile_into(stats, n, opt->r, opt->T, n_steps, smile->n_expiries, smile->n_strikes, h_expiry_steps, h_price,
+                        h_std_err);
+    return MCAMD_OK;
+}
+
 int mcamd_localvol_sigma_f64(const mcamd_localvol_grid *grid, const double *h_sigma, uint32_t n_steps, uint32_t step,
                              double x, double *sigma)
 {
@@ -2289,6 +2499,53 @@ int mcamd_bs_price_f64(double S0, double K, double T, double r, double q, double
     const auto N = [](double x) { return 0.5 * std::erfc(-x / std::sqrt(2.0)); };
     const double Sd = S0 * std::exp(-q * T), Kd = K * std::exp(-r * T);
     *price = payoff == MCAMD_PAYOFF_CALL ? Sd * N(d1) - Kd * N(d2) : Kd * N(-d2) - Sd * N(-d1);
+    return MCAMD_OK;
+}
+
+int mcamd_bs_implied_vol_f64(double S0, double K, double T, double r, double q, int payoff, double price, double *vol)
+{
+    if (!vol) return fail(MCAMD_ERR_INVALID, "vol is NULL");
+    *vol = std::nan("");
+    if (!(S0 > 0.0) || !(K > 0.0) || !(T > 0.0) || !std::isfinite(S0) || !std::isfinite(K) || !std::isfinite(T) ||
+        !std::isfinite(r) || !std::isfinite(q) || !std::isfinite(price))
+        return fail(MCAMD_ERR_INVALID, "an implied volatility needs finite S0, K, T > 0 and finite r, q and price");
+    if (payoff != MCAMD_PAYOFF_CALL && payoff != MCAMD_PAYOFF_PUT)
+        return fail(MCAMD_ERR_INVALID, "payoff must be MCAMD_PAYOFF_CALL (0) or MCAMD_PAYOFF_PUT (1), got %d", payoff);
+    const bool call = payoff == MCAMD_PAYOFF_CALL;
+    const double D = std::exp(-r * T), F = S0 * std::exp((r - q) * T);
+    const double lower = D * std::fmax(call ? F - K : K - F, 0.0);
+    const double upper = call ? S0 * std::exp(-q * T) : K * D;
+    if (!(price > lower) || !(price < upper))
+        return fail(MCAMD_ERR_INVALID, "the price %.17g is not strictly inside the no-arbitrage bounds (%.17g, %.17g)", price,
+                    lower, upper);
+    // The price grows with v from lower to upper: bracket the root, then Newton steps kept inside the bracket and
+    // replaced by a bisection whenever they leave it or shrink it too slowly (plain Newton diverges in the wings,
+    // where the vega vanishes).  f is "not above" at lo and "above or equal" at hi throughout; a NaN counts as not above.
+    double lo = 0.0, hi = 1.0 / std::sqrt(T);
+    for (int grow = 0; grow < 64 && !(bs_value(S0, K, T, r, q, hi, call, nullptr) >= price); ++grow) {
+        lo = hi;
+        hi *= 2.0;
+    }
+    double x = 0.5 * (lo + hi), dx_old = hi - lo, dx = dx_old, vega = 0.0;
+    double f = bs_value(S0, K, T, r, q, x, call, &vega) - price;
+    for (int it = 0; it < 400; ++it) {
+        const bool newton_leaves = !(((x - hi) * vega - f) * ((x - lo) * vega - f) < 0.0);
+        const bool newton_slow = !(std::fabs(2.0 * f) <= std::fabs(dx_old * vega));
+        dx_old = dx;
+        if (newton_leaves || newton_slow) {
+            dx = 0.5 * (hi - lo);
+            x = lo + dx;
+        } else {
+            dx = f / vega;
+            x -= dx;
+        }
+        if (!(std::fabs(dx) > 1e-15 * x)) break;
+        f = bs_value(S0, K, T, r, q, x, call, &vega) - price;
+        if (f >= 0.0) hi = x;
+        else lo = x;
+        if (f == 0.0) break;
+    }
+    *vol = x;
     return MCAMD_OK;
 }
 

@@ -1,0 +1,273 @@
+// localvol_smile.hip — a strike-by-expiry set of vanillas on one set of local-volatility paths, for gfx950 (both path
+// precisions).
+//
+// Definitions (include/mcamd.h, mcamd_price_localvol_smile): the paths are mcamd_price_localvol's without a barrier —
+// the walk below restates localvol.hip's step in the same operation order, with the same table in dynamic LDS, the
+// same carried row and the same Philox subsequence — stopped at the expiry steps s_0 < s_1 < ...; the spot of expiry m
+// is S_m = exp_of_logreturn(S0, X_{s_m} exp_scale), as localvol.hip forms S_T.
+//
+// Walk phase: one path per lane.  The next expiry step is wave-uniform and lives in a scalar register; a Philox block
+// that holds no expiry runs the plain unrolled steps, one that holds an expiry (or the end) tests every step.
+// Strike phase: at an expiry the wavefront holds 64 spots, one per lane, and turns the work a quarter-turn: lane k
+// holds strike k and runs over the wavefront's valid paths j (a prefix; its length comes from the ballot), reading S_j
+// by v_readlane into scalar registers, and keeps sum h and sum h^2 of node (m, k) in two fp64 registers.  After the
+// loop lane k adds them to its own 16-byte entry of the wavefront's private record [m][k] in global memory — a plain
+// read-modify-write that only this lane of this wavefront ever touches, in program order; the first trip of a
+// wavefront writes instead of adding (its old value is taken as 0 and the entry is not read), and a wavefront without
+// any path writes zeros, so every entry of every record is written whatever the buffer held.
+// Finish: smile_finish_kernel, one thread per node, sums the entries over the wavefronts in index order.
+#include "localvol_smile.hpp"
+#include "path_consts.hpp"
+
+namespace mcamd {
+
+template <typename T>
+struct SmileArgs {
+    T x_min, inv_dx;          // node 0 and 1 / dx
+    T u_max;                  // n_x - 1
+    uint32_t k_max;           // n_x - 2
+    uint32_t n_x, n_entries;  // n_entries = n_t n_x
+    uint32_t row_whole_nx;    // (n_t / n_steps) n_x: what the row base grows by at every step
+    uint32_t row_rem;         // n_t % n_steps
+    uint32_t row_thr;         // n_steps - row_rem: the remainder counter carries when it reaches this
+    const VolPair<T> *table;  // global memory
+    T mu_dt, half_dt, sqrt_dt;
+    T exp_scale;              // exponent units per natural-log unit (log2 e in fp32, 65536 / ln 2 in fp64)
+    T S0;
+    int put;
+    uint32_t n_expiries, n_strikes;
+    uint32_t last_step;       // expiry_steps[n_expiries - 1]: the walk ends there
+    uint64_t seed;
+    uint64_t path_offset;
+    uint64_t n_local;
+    T *spots;                 // nullable
+    uint32_t expiry_steps[kSmileMaxExpiries];
+    T strikes[kSmileMaxStrikes];
+};
+
+// what a step reads, with the constants of the full-rate fp32 instructions in vector registers (mc_device.hpp
+// vgpr_resident)
+template <typename T>
+struct SmileStep {
+    T x_min, inv_dx, u_max, mu_dt, half_dt, sqrt_dt;
+};
+__device__ __forceinline__ SmileStep<float> sm_resident(const SmileArgs<float> &a)
+{
+    return {vgpr_resident(a.x_min), vgpr_resident(a.inv_dx), vgpr_resident(a.u_max),
+            vgpr_resident(a.mu_dt), vgpr_resident(a.half_dt), vgpr_resident(a.sqrt_dt)};
+}
+__device__ __forceinline__ SmileStep<double> sm_resident(const SmileArgs<double> &a)
+{
+    return {a.x_min, a.inv_dx, a.u_max, a.mu_dt, a.half_dt, a.sqrt_dt};
+}
+
+__device__ __forceinline__ float sm_min(float a, float b) { return __builtin_fminf(a, b); }
+__device__ __forceinline__ double sm_min(double a, double b) { return __builtin_fmin(a, b); }
+__device__ __forceinline__ float sm_max(float a, float b) { return __builtin_fmaxf(a, b); }
+__device__ __forceinline__ double sm_max(double a, double b) { return __builtin_fmax(a, b); }
+
+// lane j's value, j wave-uniform: v_readlane_b32 into scalar registers (a pair for fp64)
+__device__ __forceinline__ float sm_broadcast(float v, uint32_t j)
+{
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), static_cast<int>(j)));
+}
+__device__ __forceinline__ double sm_broadcast(double v, uint32_t j)
+{
+    const uint64_t bits = __builtin_bit_cast(uint64_t, v);
+    const uint32_t lo = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(bits), static_cast<int>(j)));
+    const uint32_t hi = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(bits >> 32), static_cast<int>(j)));
+    return __builtin_bit_cast(double, (static_cast<uint64_t>(hi) << 32) | lo);
+}
+
+struct alignas(16) SmileEntry {
+    double sum, sumsq;
+};
+
+extern __shared__ __attribute__((aligned(16))) unsigned char sm_table_lds[];
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void smile_kernel(SmileArgs<T> args, double *__restrict__ partials)
+{
+    constexpr int NB = Normals<T>::kPerBlock;
+    // every thread of the workgroup copies its share of the table; one barrier, then the table is read-only
+    VolPair<T> *tab = reinterpret_cast<VolPair<T> *>(sm_table_lds);
+    for (uint32_t e = threadIdx.x; e < args.n_entries; e += kBlock) tab[e] = args.table[e];
+    __syncthreads();
+    const MathCtx<T> m = MathCtx<T>::init();
+    const PhiloxKeys key = PhiloxKeys::make(args.seed);
+    const SmileStep<T> a = sm_resident(args);
+    const uint32_t lane = threadIdx.x & (kWave - 1);
+    const uint32_t wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+    const uint32_t wave = blockIdx.x * (kBlock / kWave) + wave_in_block;
+    const uint32_t n_e = args.n_expiries, n_K = args.n_strikes;
+    const bool has_node = lane < n_K;
+    // h = max(+-(S - K), 0) as one fma with the sign in a lane constant: fma(S, sign, -sign K) rounds S - K or K - S
+    // once, as the subtraction does (the product with +-1 is exact)
+    const T sign = args.put ? T(-1) : T(1);
+    T minus_sign_K = -sign * args.strikes[has_node ? lane : 0];
+    asm volatile("" : "+v"(minus_sign_K));   // the strike has arrived before the first strike loop, not inside it
+    // the wavefront's record: n_e rows of n_K entries
+    SmileEntry *rec = reinterpret_cast<SmileEntry *>(partials) + static_cast<uint64_t>(wave) * n_e * n_K;
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
+    const uint32_t last = args.last_step;
+    const uint32_t n_blocks = (last + NB - 1) / NB;
+    bool first = true;   // wave-uniform: this trip writes the record, later ones add to it
+    for (uint64_t i0 = static_cast<uint64_t>(wave) * kWave; first || i0 < args.n_local; i0 += stride) {
+        const uint64_t i = i0 + lane;
+        const bool valid = i < args.n_local;
+        // the valid lanes are a prefix (path ids grow with the lane): their number is the strike loop's trip count
+        const uint32_t count = static_cast<uint32_t>(__builtin_popcountll(__builtin_amdgcn_ballot_w64(valid)));
+        if (count == 0) {
+            // only a wavefront's first trip can be empty: its record is all zeros
+            if (has_node)
+                for (uint32_t mi = 0; mi < n_e; ++mi) rec[mi * n_K + lane] = SmileEntry{0.0, 0.0};
+            first = false;
+            continue;
+        }
+        // lanes past the end walk a path nobody reads: the strike phase needs the whole wavefront
+        const uint64_t subsequence = args.path_offset + i;
+        T X = T(0);               // ln(S / S0), natural units
+        uint32_t row_base = 0;    // row(i) n_x, wave-uniform
+        uint32_t row_phase = 0;   // (i row_rem) mod n_steps, wave-uniform
+        uint32_t mi = 0;          // the next expiry, wave-uniform
+        uint32_t next = args.expiry_steps[0];
+        Normals<T> nz;
+        auto step = [&](T z) {
+            T u = (X - a.x_min) * a.inv_dx;
+            u = sm_min(sm_max(u, T(0)), a.u_max);   // a NaN lands on node 0: the index stays inside the table
+            uint32_t k = static_cast<uint32_t>(u);
+            k = k < args.k_max ? k : args.k_max;
+            const T f = u - static_cast<T>(k);
+            const VolPair<T> p = tab[row_base + k];
+            const T s = fma_t(f, p.slope, p.sigma);
+            // row(i + 1)
+            row_base += args.row_whole_nx;
+            if (row_phase >= args.row_thr) {
+                row_phase -= args.row_thr;
+                row_base += args.n_x;
+            } else {
+                row_phase += args.row_rem;
+            }
+            const T s2 = s * s;
+            X += fma_t(s * a.sqrt_dt, z, fma_t(-s2, a.half_dt, a.mu_dt));
+        };
+        auto expiry = [&]() {
+            const T S = exp_of_logreturn(args.S0, X * args.exp_scale, m);
+            if (args.spots && valid) args.spots[static_cast<uint64_t>(mi) * args.n_local + i] = S;
+            SmileEntry *entry = rec + mi * n_K + lane;
+            // the entry's load is issued before the strike loop, whose length hides its latency
+            SmileEntry old{0.0, 0.0};
+            if (!first && has_node) old = *entry;
+            double sum = 0.0, sumsq = 0.0;
+            for (uint32_t j = 0; j < count; ++j) {
+                const T Sj = sm_broadcast(S, j);
+                T h = fma_t(Sj, sign, minus_sign_K);
+                h = h > T(0) ? h : T(0);
+                const double hd = static_cast<double>(h);
+                sum += hd;
+                sumsq = __builtin_fma(hd, hd, sumsq);
+            }
+            if (has_node) *entry = SmileEntry{old.sum + sum, old.sumsq + sumsq};
+            ++mi;
+            next = mi < n_e ? args.expiry_steps[mi] : 0xFFFFFFFFu;
+        };
+        for (uint32_t kb = 0; kb < n_blocks; ++kb) {
+            nz.fill(m, key, subsequence, kb);
+            const uint32_t base = kb * NB;
+            if (next > base + NB) {   // no expiry inside this block, hence a full one
+#pragma unroll
+                for (int j = 0; j < NB; ++j) step(nz.z[j]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < NB; ++j) {
+                    if (base + j < last) {
+                        step(nz.z[j]);
+                        if (base + j + 1 == next) expiry();
+                    }
+                }
+            }
+        }
+        first = false;
+    }
+}
+
+// One thread per node: the node's entries over the wavefronts, in index order (adjacent threads read adjacent entries).
+__global__ __launch_bounds__(kBlock) void smile_finish_kernel(const SmileEntry *__restrict__ rec, uint32_t n_waves,
+                                                              uint32_t n_nodes, double *__restrict__ out, double n_value)
+{
+    const uint32_t node = blockIdx.x * kBlock + threadIdx.x;
+    if (node >= n_nodes) return;
+    double sum = 0.0, sumsq = 0.0;
+#pragma unroll 8
+    for (uint32_t w = 0; w < n_waves; ++w) {
+        const SmileEntry e = rec[static_cast<uint64_t>(w) * n_nodes + node];
+        sum += e.sum;
+        sumsq += e.sumsq;
+    }
+    out[node] = sum;
+    out[n_nodes + node] = sumsq;
+    if (node == 0 && n_value >= 0.0) out[2 * n_nodes] = n_value;
+}
+
+template <typename T>
+static hipError_t launch_smile_t(const SmileJob &j, double *d_partials, uint32_t grid, hipStream_t stream)
+{
+    const double dx = (j.x_max - j.x_min) / static_cast<double>(j.n_x - 1);
+    SmileArgs<T> a;
+    a.x_min = static_cast<T>(j.x_min);
+    a.inv_dx = static_cast<T>(1.0 / dx);
+    a.u_max = static_cast<T>(j.n_x - 1);
+    a.k_max = j.n_x - 2;
+    a.n_x = j.n_x;
+    a.n_entries = j.n_t * j.n_x;
+    a.row_whole_nx = (j.n_t / j.n_steps) * j.n_x;
+    a.row_rem = j.n_t % j.n_steps;
+    a.row_thr = j.n_steps - a.row_rem;
+    a.table = static_cast<const VolPair<T> *>(j.d_table);
+    a.mu_dt = static_cast<T>(j.mu * j.dt);
+    a.half_dt = static_cast<T>(0.5 * j.dt);
+    a.sqrt_dt = static_cast<T>(std::sqrt(j.dt));
+    a.exp_scale = static_cast<T>(sizeof(T) == 4 ? 1.4426950408889634 : f64::kExpScale);   // make_consts' literals
+    a.S0 = static_cast<T>(j.S0);
+    a.put = j.put ? 1 : 0;
+    a.n_expiries = j.n_expiries;
+    a.n_strikes = j.n_strikes;
+    a.last_step = j.expiry_steps[j.n_expiries - 1];
+    a.seed = j.seed;
+    a.path_offset = j.path_offset;
+    a.n_local = j.n_local;
+    a.spots = static_cast<T *>(j.d_spots);
+    for (uint32_t m = 0; m < kSmileMaxExpiries; ++m) a.expiry_steps[m] = m < j.n_expiries ? j.expiry_steps[m] : 0xFFFFFFFFu;
+    for (uint32_t k = 0; k < kSmileMaxStrikes; ++k) a.strikes[k] = k < j.n_strikes ? static_cast<T>(j.strikes[k]) : T(0);
+    const size_t lds_bytes = static_cast<size_t>(a.n_entries) * sizeof(VolPair<T>);
+    hipLaunchKernelGGL((smile_kernel<T>), dim3(grid), dim3(kBlock), lds_bytes, stream, a, d_partials);
+    return hipGetLastError();
+}
+
+hipError_t launch_localvol_smile(const SmileJob &job, double *d_partials, uint32_t grid, hipStream_t stream)
+{
+    if (!d_partials || grid == 0 || grid > kFoldMaxRecords) return hipErrorInvalidValue;
+    if (!job.d_table || job.n_steps == 0 || job.n_x < 2 || job.n_t < 1 ||
+        static_cast<uint64_t>(job.n_t) * job.n_x > kLocalVolMaxNodes)
+        return hipErrorInvalidValue;
+    if (job.n_expiries < 1 || job.n_expiries > kSmileMaxExpiries || job.n_strikes < 1 || job.n_strikes > kSmileMaxStrikes)
+        return hipErrorInvalidValue;
+    for (uint32_t m = 0; m < job.n_expiries; ++m) {
+        const uint32_t lo = m ? job.expiry_steps[m - 1] : 0;
+        if (job.expiry_steps[m] <= lo || job.expiry_steps[m] > job.n_steps) return hipErrorInvalidValue;
+    }
+    return job.precision == 32 ? launch_smile_t<float>(job, d_partials, grid, stream)
+                               : launch_smile_t<double>(job, d_partials, grid, stream);
+}
+
+hipError_t launch_smile_finish(const double *d_partials, uint32_t n_waves, uint32_t n_nodes, double *out, double n_value,
+                               hipStream_t stream)
+{
+    if (!d_partials || !out || n_waves == 0 || n_nodes == 0) return hipErrorInvalidValue;
+    const uint32_t grid = (n_nodes + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(smile_finish_kernel, dim3(grid), dim3(kBlock), 0, stream,
+                       reinterpret_cast<const SmileEntry *>(d_partials), n_waves, n_nodes, out, n_value);
+    return hipGetLastError();
+}
+
+}  // namespace mcamd
