@@ -46,16 +46,33 @@ __device__ __forceinline__ float vgpr_resident(float s)
     return v;
 }
 
+// Two scalars copied into a vector register pair by one v_mov_b64 (4 cycles whatever its source; a v_mov_b32 from a
+// scalar register costs as much for one: profiles/philox_head_operand_costs.txt).  Not volatile: the scheduler may place it.
+__device__ __forceinline__ void vgpr_resident_pair(uint32_t &a, uint32_t &b)
+{
+    const uint64_t s = (static_cast<uint64_t>(b) << 32) | a;
+    uint64_t v;
+    asm("v_mov_b64 %0, %1" : "=v"(v) : "s"(s));
+    a = static_cast<uint32_t>(v);
+    b = static_cast<uint32_t>(v >> 32);
+}
+
 // The ten round-key pairs of Philox4x32-10 for one seed, in vector registers (20 VGPRs, built once per kernel).
 struct PhiloxKeys {
     uint32_t k0[10], k1[10];
     uint32_t k1_first;   // k1[0] once more, left to the compiler (a scalar register): round 1 folds it into scalar terms
+    // k0[1], k1[1] and k0[2] once more as scalars: the wave-uniform head (PhiloxHead below) folds them into scalar
+    // terms and into lane constants that are computed once per path
+    uint32_t k0_second, k1_second, k0_third;
     __device__ __forceinline__ static PhiloxKeys make(uint64_t seed)
     {
         constexpr uint32_t W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
         PhiloxKeys k;
         uint32_t a = static_cast<uint32_t>(seed), b = static_cast<uint32_t>(seed >> 32);
         k.k1_first = b;
+        k.k0_second = a + W0;
+        k.k1_second = b + W1;
+        k.k0_third = a + 2u * W0;
 #pragma unroll
         for (int i = 0; i < 10; ++i) {
             k.k0[i] = vgpr_resident(a);
@@ -102,6 +119,147 @@ __device__ __forceinline__ U4 philox_block(const PhiloxKeys &key, uint64_t subse
 {
     return philox4x32_10(static_cast<uint32_t>(block), static_cast<uint32_t>(block >> 32),
                          static_cast<uint32_t>(subsequence), static_cast<uint32_t>(subsequence >> 32), key);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The wave-uniform head of Philox in a step loop.  There the counter is (k, 0, sub_lo, sub_hi) with k the loop counter
+// (scalar) and the subsequence a path id that the loop does not change; and sub_hi is the same in every lane of a
+// wavefront, except in the one wavefront per 2^32 paths that straddles a multiple of 2^32.  With sub_hi uniform,
+//   round 1   c0' = hi(M1 sub_lo) ^ k0[0]           lane constant      c1' = lo(M1 sub_lo)     lane constant
+//             c2' = hi(M0 k) ^ k1[0] ^ sub_hi       SCALAR             c3' = lo(M0 k)          scalar
+//   round 2   c0  = hi(M1 c2') ^ (c1' ^ k0[1])      scalar ^ lane constant
+//             c1  = lo(M1 c2')                      SCALAR (the product is two scalar multiplies)
+//             c2  = (hi(M0 c0') ^ k1[1]) ^ c3'      lane constant ^ scalar
+//             c3  = lo(M0 c0')                      lane constant
+//   round 3   c0  = hi(M1 c2) ^ (c1 ^ k0[2])        vector ^ scalar;   the rest of round 3 and rounds 4..10 as ever.
+// So per block a chain pays three two-input xors, each reading a scalar register (4 cycles, see vgpr_resident), where
+// it paid a v_mad_u64_u32 and four xors, two of them reading a scalar register: 12 issue cycles for 16 (17.6 as
+// measured in isolation, 12.7 now); the lane constants (PhiloxLane) are computed once per path and the
+// three scalars (PhiloxHead) once per block on the scalar unit.  Same ten rounds, same four words, bit for bit.
+// ---------------------------------------------------------------------------------------------
+struct PhiloxLane {
+    uint32_t x0;   // lo(M1 sub_lo) ^ k0[1]
+    uint32_t x2;   // hi(M0 c0') ^ k1[1]
+    uint32_t c3;   // lo(M0 c0')
+    __device__ __forceinline__ static PhiloxLane make(const PhiloxKeys &key, uint32_t sub_lo)
+    {
+        constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
+        const uint64_t p1 = static_cast<uint64_t>(M1) * sub_lo;
+        const uint64_t p0 = static_cast<uint64_t>(M0) * (static_cast<uint32_t>(p1 >> 32) ^ key.k0[0]);
+        return PhiloxLane{static_cast<uint32_t>(p1) ^ key.k0_second, static_cast<uint32_t>(p0 >> 32) ^ key.k1_second,
+                          static_cast<uint32_t>(p0)};
+    }
+};
+
+// The three scalars of block k, plain C++: with sub_hi and k wave-uniform the compiler computes them on the scalar unit
+// (two s_mul for the product) and the three xors of philox_block_uniform read them as scalar operands, 4 cycles each.
+// That is what ships.  The alternative — move them to vector registers once per block for the chains of a loop body
+// that share them, so that the xors stay at 2 cycles — counts fewer issue cycles only when two scalars travel in one
+// v_mov_b64 (a v_mov_b32 from a scalar register costs 4.3 cycles, not 2.2) and was SLOWER in every same-box A/B
+// (profiles/philox_head_ab.txt: fp64 10M x 252 0.985 of the parent against 0.969 with scalar operands, fp32 0.991 against
+// 0.971); -DMCAMD_PHILOX_HEAD_MOVES=1 builds it, for that comparison only.
+#ifndef MCAMD_PHILOX_HEAD_MOVES
+#define MCAMD_PHILOX_HEAD_MOVES 0
+#endif
+struct PhiloxHead {
+    uint32_t s0;   // hi(M1 c2')
+    uint32_t s2;   // lo(M0 k)
+    uint32_t s3;   // lo(M1 c2') ^ k0[2]
+    __device__ __forceinline__ static PhiloxHead make(const PhiloxKeys &key, uint32_t sub_hi, uint32_t k)
+    {
+        constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
+        const uint64_t pk = static_cast<uint64_t>(M0) * k;
+        const uint32_t c2 = (static_cast<uint32_t>(pk >> 32) ^ key.k1_first) ^ sub_hi;
+        const uint64_t p1 = static_cast<uint64_t>(M1) * c2;
+        return PhiloxHead{static_cast<uint32_t>(p1 >> 32), static_cast<uint32_t>(pk), static_cast<uint32_t>(p1) ^ key.k0_third};
+    }
+    // The head as the chains of ONE loop body share it.  With MCAMD_PHILOX_HEAD_MOVES the moves read scalar registers,
+    // so sub_hi AND k must then be wave-uniform (a value that differs between lanes would be taken from the first).
+    __device__ __forceinline__ PhiloxHead shared() const
+    {
+        PhiloxHead h = *this;
+#if MCAMD_PHILOX_HEAD_MOVES
+        vgpr_resident_pair(h.s0, h.s2);
+        asm("v_mov_b32 %0, %1" : "=v"(h.s3) : "s"(s3));
+#endif
+        return h;
+    }
+};
+
+// philox_block(key, (sub_hi << 32) | sub_lo, k) from the lane constants of sub_lo and the head of (sub_hi, k)
+__device__ __forceinline__ U4 philox_block_uniform(const PhiloxKeys &key, const PhiloxLane &ln, const PhiloxHead &h)
+{
+    constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
+    // state after round 2: (ln.x0 ^ h.s0, lo(M1 c2'), ln.x2 ^ h.s2, ln.c3); round 3 folds lo(M1 c2') ^ k0[2] = h.s3
+    uint64_t p0 = static_cast<uint64_t>(M0) * (ln.x0 ^ h.s0);
+    uint64_t p1 = static_cast<uint64_t>(M1) * (ln.x2 ^ h.s2);
+    uint32_t c0 = static_cast<uint32_t>(p1 >> 32) ^ h.s3;
+    uint32_t c2 = __builtin_amdgcn_bitop3_b32(static_cast<uint32_t>(p0 >> 32), ln.c3, key.k1[2], 0x96);
+    uint32_t c1 = static_cast<uint32_t>(p1);
+    uint32_t c3 = static_cast<uint32_t>(p0);
+#pragma unroll
+    for (int i = 3; i < 10; ++i) {
+        p0 = static_cast<uint64_t>(M0) * c0;
+        p1 = static_cast<uint64_t>(M1) * c2;
+        const uint32_t n0 = __builtin_amdgcn_bitop3_b32(static_cast<uint32_t>(p1 >> 32), c1, key.k0[i], 0x96);
+        const uint32_t n2 = __builtin_amdgcn_bitop3_b32(static_cast<uint32_t>(p0 >> 32), c3, key.k1[i], 0x96);
+        c1 = static_cast<uint32_t>(p1);
+        c3 = static_cast<uint32_t>(p0);
+        c0 = n0;
+        c2 = n2;
+    }
+    return U4{c0, c1, c2, c3};
+}
+
+// Marker for tools/count_valu_slots.py, placed in the step loops of the wavefront that straddles a multiple of 2^32:
+// one wavefront in 2^26 runs them, and they are left out of the static per-step instruction counts (as the exact
+// barrier test of PathState<double>::below_barrier is).
+__device__ __forceinline__ void philox_rare_route() { asm volatile("; MCAMD_RARE_BLOCK"); }
+
+// Whether the NP consecutive subsequences a thread walks (subsequence0 .. subsequence0 + NP - 1) have ONE high word
+// across all active lanes of the wavefront, returned in hi0 as a value the compiler knows to be uniform.  Asked once
+// per path group, before the step loop; a wavefront for which it fails walks its blocks through philox_block.
+template <int NP>
+__device__ __forceinline__ bool philox_hi_uniform(uint64_t subsequence0, uint32_t &hi0)
+{
+    hi0 = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(subsequence0 >> 32));
+    bool differs = false;
+#pragma unroll
+    for (int p = 0; p < NP; ++p) differs |= static_cast<uint32_t>((subsequence0 + p) >> 32) != hi0;
+    return __builtin_amdgcn_ballot_w64(differs) == 0;
+}
+
+// One path's Philox blocks as a step loop walks them: block(key, k) is philox_block(key, subsequence, k).
+// PhiloxWalk<true> takes the uniform head (sub_hi uniform; k may be anything),
+// PhiloxWalk<false> the ten plain rounds.  philox_walk() asks philox_hi_uniform and hands the body the right one.
+template <bool UNIFORM>
+struct PhiloxWalk;
+template <>
+struct PhiloxWalk<false> {
+    uint64_t subsequence;
+    __device__ __forceinline__ U4 block(const PhiloxKeys &key, uint32_t k) const
+    {
+        philox_rare_route();
+        return philox_block(key, subsequence, k);
+    }
+};
+template <>
+struct PhiloxWalk<true> {
+    PhiloxLane ln;
+    uint32_t hi0;
+    __device__ __forceinline__ U4 block(const PhiloxKeys &key, uint32_t k) const
+    {
+        return philox_block_uniform(key, ln, PhiloxHead::make(key, hi0, k));
+    }
+};
+template <typename F>
+__device__ __forceinline__ void philox_walk(const PhiloxKeys &key, uint64_t subsequence, F &&body)
+{
+    uint32_t hi0;
+    if (philox_hi_uniform<1>(subsequence, hi0))
+        body(PhiloxWalk<true>{PhiloxLane::make(key, static_cast<uint32_t>(subsequence)), hi0});
+    else
+        body(PhiloxWalk<false>{subsequence});
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -194,10 +352,14 @@ template <>
 struct Normals<float> {
     static constexpr int kPerBlock = 4;
     float z[4];
-    __device__ __forceinline__ void fill(const MathCtx<float> &, const PhiloxKeys &key, uint64_t subsequence,
+    __device__ __forceinline__ void fill(const MathCtx<float> &m, const PhiloxKeys &key, uint64_t subsequence,
                                          uint64_t block)
     {
-        const U4 w = philox_block(key, subsequence, block);
+        fill_words(m, philox_block(key, subsequence, block));
+    }
+    // fill() on the block's four Philox words
+    __device__ __forceinline__ void fill_words(const MathCtx<float> &, const U4 &w)
+    {
         box_muller(w.x, w.y, z[0], z[1]);
         box_muller(w.z, w.w, z[2], z[3]);
     }
@@ -210,9 +372,9 @@ struct Normals<double> {
     __device__ __forceinline__ void fill(const MathCtx<double> &m, const PhiloxKeys &key, uint64_t subsequence,
                                          uint64_t block)
     {
-        const U4 w = philox_block(key, subsequence, block);
-        box_muller(w, m, z[0], z[1]);
+        fill_words(m, philox_block(key, subsequence, block));
     }
+    __device__ __forceinline__ void fill_words(const MathCtx<double> &m, const U4 &w) { box_muller(w, m, z[0], z[1]); }
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -319,10 +481,14 @@ struct Exponents<float> {
         x0 = __builtin_fmaf(__builtin_amdgcn_sinf(rev), sv, c.drift);
         x1 = __builtin_fmaf(__builtin_amdgcn_cosf(rev), sv, c.drift);
     }
-    __device__ __forceinline__ void fill(const MathCtx<float> &, const StepConsts<float> &c, const PhiloxKeys &key,
+    __device__ __forceinline__ void fill(const MathCtx<float> &m, const StepConsts<float> &c, const PhiloxKeys &key,
                                          uint64_t subsequence, uint64_t block)
     {
-        const U4 w = philox_block(key, subsequence, block);
+        fill_words(m, c, philox_block(key, subsequence, block));
+    }
+    // fill() on the block's four Philox words
+    __device__ __forceinline__ void fill_words(const MathCtx<float> &, const StepConsts<float> &c, const U4 &w)
+    {
         pair(w.x, w.y, c, x[0], x[1]);
         pair(w.z, w.w, c, x[2], x[3]);
     }
@@ -335,7 +501,10 @@ struct Exponents<double> {
     __device__ __forceinline__ void fill(const MathCtx<double> &m, const StepConsts<double> &c, const PhiloxKeys &key,
                                          uint64_t subsequence, uint64_t block)
     {
-        const U4 w = philox_block(key, subsequence, block);
+        fill_words(m, c, philox_block(key, subsequence, block));
+    }
+    __device__ __forceinline__ void fill_words(const MathCtx<double> &m, const StepConsts<double> &c, const U4 &w)
+    {
         const double u = f64::u53(w.x, w.y, 0x1p-53);
         const double sv = f64::sqrt_scaled(f64::neg2log(u, m.t.log_tab), c.vol_bm);
         double sn, cs;
@@ -377,10 +546,14 @@ struct PairSum<float> {
         return t * __builtin_amdgcn_sinf(rev);
     }
     // acc + the block's sum (two fused multiply-adds)
-    __device__ __forceinline__ static float add_block(float acc, const MathCtx<float> &, const PhiloxKeys &key,
+    __device__ __forceinline__ static float add_block(float acc, const MathCtx<float> &m, const PhiloxKeys &key,
                                                        uint64_t subsequence, uint64_t block)
     {
-        const U4 w = philox_block(key, subsequence, block);
+        return add_words(acc, philox_block(key, subsequence, block), m);
+    }
+    // add_block() on the block's four Philox words
+    __device__ __forceinline__ static float add_words(float acc, const U4 &w, const MathCtx<float> &)
+    {
         float t1, r1, t2, r2;
         polar(w.x, w.y, 0.125f, t1, r1);
         polar(w.z, w.w, 0.125f, t2, r2);
@@ -432,7 +605,7 @@ struct PairSum<double> {
     {
         return head_words(philox_block(key, subsequence, block), m);
     }
-    __device__ __forceinline__ static double head_words(const U4 &w, const MathCtx<double> &m)
+    __device__ __forceinline__ static double head_words(const U4 &w, const MathCtx<double> &m, uint32_t = 1)
     {
         const double u = f64::u53(w.x, w.y, 0x1p-53);
         const double r = f64::sqrt_unclamped(f64::neg2log(u, m.t.log_tab));
@@ -525,7 +698,27 @@ __device__ __forceinline__ void pair_sums_of_paths(const MathCtx<T> &m, const Ph
     const uint32_t rem = n_sim - n_full * NB;
 #pragma unroll
     for (int p = 0; p < NP; ++p) acc[p] = T(0);
+    uint32_t hi0;
+    if (philox_hi_uniform<NP>(subsequence0, hi0)) {
+        // every wavefront but the one per 2^32 paths that straddles a multiple of 2^32: the NP chains share the
+        // uniform head (n_full comes from a kernel argument, so k is wave-uniform)
+        PhiloxLane ln[NP];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) ln[p] = PhiloxLane::make(seed, static_cast<uint32_t>(subsequence0) + p);
+        for (uint32_t k = 0; k < n_full; ++k) {
+            const PhiloxHead h = PhiloxHead::make(seed, hi0, k).shared();
+#pragma unroll
+            for (int p = 0; p < NP; ++p) acc[p] = PairSum<T>::add_words(acc[p], philox_block_uniform(seed, ln[p], h), m);
+        }
+        if (rem) {
+            const PhiloxHead h = PhiloxHead::make(seed, hi0, n_full).shared();
+#pragma unroll
+            for (int p = 0; p < NP; ++p) acc[p] += PairSum<T>::head_words(philox_block_uniform(seed, ln[p], h), m, rem);
+        }
+        return;
+    }
     for (uint32_t k = 0; k < n_full; ++k) {
+        philox_rare_route();
 #pragma unroll
         for (int p = 0; p < NP; ++p) acc[p] = PairSum<T>::add_block(acc[p], m, seed, subsequence0 + p, k);
     }
@@ -587,26 +780,28 @@ __device__ __forceinline__ Sample<T> simulate_sample(const StepConsts<T> &c, con
                 if (WINDOW) count2 += (c.logB > acc2) ? 1 : 0;
             }
         };
-        for (uint32_t k = 0; k < n_full; ++k) {
-            ex.fill(m, c, seed, subsequence, k);
+        philox_walk(seed, subsequence, [&](const auto &walk) {
+            for (uint32_t k = 0; k < n_full; ++k) {
+                ex.fill_words(m, c, walk.block(seed, k));
 #pragma unroll
-            for (int j = 0; j < NB; ++j) step(ex.x[j]);
-            if (WINDOW && EARLY) {
-                live_steps += open_lanes * NB;
-                open_lanes = window_open_lanes<ANTI>(count, count2, c.P2);
-                if (open_lanes == 0) {
-                    steps_run = (k + 1) * NB;
-                    rem_live = false;
-                    break;
+                for (int j = 0; j < NB; ++j) step(ex.x[j]);
+                if (WINDOW && EARLY) {
+                    live_steps += open_lanes * NB;
+                    open_lanes = window_open_lanes<ANTI>(count, count2, c.P2);
+                    if (open_lanes == 0) {
+                        steps_run = (k + 1) * NB;
+                        rem_live = false;
+                        break;
+                    }
                 }
             }
-        }
-        if (rem && rem_live) {
-            ex.fill(m, c, seed, subsequence, n_full);
+            if (rem && rem_live) {
+                ex.fill_words(m, c, walk.block(seed, n_full));
 #pragma unroll
-            for (int j = 0; j < NB - 1; ++j)
-                if (static_cast<uint32_t>(j) < rem) step(ex.x[j]);
-        }
+                for (int j = 0; j < NB - 1; ++j)
+                    if (static_cast<uint32_t>(j) < rem) step(ex.x[j]);
+            }
+        });
     } else {
         // the reference's recurrence: St *= exp(drift + vol G); the twin uses drift - vol G = 2 drift - x.
         // The barrier count needs St at every step (value()); a European path only at the end.
@@ -623,26 +818,28 @@ __device__ __forceinline__ Sample<T> simulate_sample(const StepConsts<T> &c, con
                 if (WINDOW) count2 += ps2.below_barrier(c, m);
             }
         };
-        for (uint32_t k = 0; k < n_full; ++k) {
-            ex.fill(m, c, seed, subsequence, k);
+        philox_walk(seed, subsequence, [&](const auto &walk) {
+            for (uint32_t k = 0; k < n_full; ++k) {
+                ex.fill_words(m, c, walk.block(seed, k));
 #pragma unroll
-            for (int j = 0; j < NB; ++j) step(ex.x[j]);
-            if (WINDOW && EARLY) {
-                live_steps += open_lanes * NB;
-                open_lanes = window_open_lanes<ANTI>(count, count2, c.P2);
-                if (open_lanes == 0) {
-                    steps_run = (k + 1) * NB;
-                    rem_live = false;
-                    break;
+                for (int j = 0; j < NB; ++j) step(ex.x[j]);
+                if (WINDOW && EARLY) {
+                    live_steps += open_lanes * NB;
+                    open_lanes = window_open_lanes<ANTI>(count, count2, c.P2);
+                    if (open_lanes == 0) {
+                        steps_run = (k + 1) * NB;
+                        rem_live = false;
+                        break;
+                    }
                 }
             }
-        }
-        if (rem && rem_live) {
-            ex.fill(m, c, seed, subsequence, n_full);
+            if (rem && rem_live) {
+                ex.fill_words(m, c, walk.block(seed, n_full));
 #pragma unroll
-            for (int j = 0; j < NB - 1; ++j)
-                if (static_cast<uint32_t>(j) < rem) step(ex.x[j]);
-        }
+                for (int j = 0; j < NB - 1; ++j)
+                    if (static_cast<uint32_t>(j) < rem) step(ex.x[j]);
+            }
+        });
         St = ps.value(m);
         if (ANTI) St2 = ps2.value(m);
     }

@@ -15,6 +15,8 @@
 // last row is bit-identical to the in-register path's terminal price.
 // Algorithmic HBM traffic: sizeof(T) bytes per path-step (+4 with counts) + sizeof(T) per path
 // payoff; no reads.  This is the bandwidth-bound configuration (BASELINE config 3).
+#include <type_traits>
+
 #include "path_consts.hpp"
 
 #include "mcamd.h"
@@ -100,21 +102,44 @@ __device__ __forceinline__ void store_group(const StoreArgs<T> &a, const StepCon
                 }
         }
     };
-    for (uint32_t k = 0; k < n_full; ++k) {
-        Exponents<T> nrm[V];
+    // the V chains share the wave-uniform Philox head (mc_device.hpp PhiloxHead; k is wave-uniform: n_full comes from a
+    // kernel argument); the wavefront that straddles a multiple of 2^32 path ids takes the ten plain rounds
+    uint32_t hi0;
+    const bool uniform = philox_hi_uniform<V>(a.path_offset + base, hi0);
+    auto walk = [&](auto uniform_head) {
+        constexpr bool kUniform = decltype(uniform_head)::value;
+        PhiloxLane ln[V];
+        if constexpr (kUniform) {
 #pragma unroll
-        for (int p = 0; p < V; ++p) nrm[p].fill(m, c, key, a.path_offset + base + p, k);
+            for (int p = 0; p < V; ++p) ln[p] = PhiloxLane::make(key, static_cast<uint32_t>(a.path_offset + base) + p);
+        }
+        auto fill = [&](Exponents<T>(&nrm)[V], uint32_t k) {
+            if constexpr (kUniform) {
+                const PhiloxHead h = PhiloxHead::make(key, hi0, k).shared();
 #pragma unroll
-        for (int j = 0; j < NB; ++j) advance(nrm, j, k * NB + j);
-    }
-    if (rem) {
-        Exponents<T> nrm[V];
+                for (int p = 0; p < V; ++p) nrm[p].fill_words(m, c, philox_block_uniform(key, ln[p], h));
+            } else {
+                philox_rare_route();
 #pragma unroll
-        for (int p = 0; p < V; ++p) nrm[p].fill(m, c, key, a.path_offset + base + p, n_full);
+                for (int p = 0; p < V; ++p) nrm[p].fill(m, c, key, a.path_offset + base + p, k);
+            }
+        };
+        for (uint32_t k = 0; k < n_full; ++k) {
+            Exponents<T> nrm[V];
+            fill(nrm, k);
 #pragma unroll
-        for (int j = 0; j < NB - 1; ++j)
-            if (static_cast<uint32_t>(j) < rem) advance(nrm, j, n_full * NB + j);
-    }
+            for (int j = 0; j < NB; ++j) advance(nrm, j, k * NB + j);
+        }
+        if (rem) {
+            Exponents<T> nrm[V];
+            fill(nrm, n_full);
+#pragma unroll
+            for (int j = 0; j < NB - 1; ++j)
+                if (static_cast<uint32_t>(j) < rem) advance(nrm, j, n_full * NB + j);
+        }
+    };
+    if (uniform) walk(std::true_type{});
+    else walk(std::false_type{});
     T pay[V];
 #pragma unroll
     for (int p = 0; p < V; ++p) {

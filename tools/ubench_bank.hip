@@ -2,6 +2,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
+#include <cstring>
 #include <vector>
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e), __LINE__); return 1; } } while (0)
 
@@ -98,6 +99,13 @@ KERNEL(mul64_inl, INITB, "v_mul_f64 v[40:41], 0.5, v[44:45]", CL)
 KERNEL(mul32_inl, INITB, "v_mul_f32 v40, 2.0, v61", CL)
 KERNEL(fma32_inl, INITB, "v_fma_f32 v40, v61, 2.0, v62", CL)
 KERNEL(mov_b32, INITB, "v_mov_b32 v40, v61", CL)
+// a scalar moved to a vector register: does the move pay the scalar-source penalty of the other full-rate ops, and is
+// a 64-bit move of a scalar pair one 4-cycle issue?  Then the two ways a wave-uniform value can reach two xors.
+KERNEL(mov_sgpr, INITB, "v_mov_b32 v40, s8", CL)
+KERNEL(mov64_sgpr, INITB, "v_mov_b64 v[40:41], s[8:9]", CL)
+KERNEL(mov64_vv, INITB, "v_mov_b64 v[40:41], v[44:45]", CL)
+KERNEL(mix_movs_2xor, INITB, "v_mov_b32 v42, s8\n v_xor_b32 v40, v42, v61\n v_xor_b32 v41, v42, v62", CL)
+KERNEL(mix_2xor_sv, INITB, "v_xor_b32 v40, s8, v61\n v_xor_b32 v41, s8, v62", CL)
 KERNEL(ldexp64_vv, INITB, "v_ldexp_f64 v[40:41], v[44:45], v60", CL)
 KERNEL(mix_mad_2bitop, INITB, "v_mad_u64_u32 v[42:43], vcc, v61, v62, v[56:57]\n v_bitop3_b32 v60, v61, v62, v63 bitop3:0x96\n v_bitop3_b32 v58, v61, v62, v63 bitop3:0x96", CL)
 KERNEL(mix_2mad_2bitop, INITB, "v_mad_u64_u32 v[42:43], vcc, v61, v62, v[56:57]\n v_mad_u64_u32 v[40:41], vcc, v61, v62, v[56:57]\n v_bitop3_b32 v60, v61, v62, v63 bitop3:0x96\n v_bitop3_b32 v58, v61, v62, v63 bitop3:0x96", CL)
@@ -105,7 +113,7 @@ KERNEL(mix_4mad_4bitop, INITB, "v_mad_u64_u32 v[42:43], vcc, v61, v62, v[56:57]\
 KERNEL(mix_2fma64_2bitop, INITB, "v_fma_f64 v[40:41], v[44:45], v[46:47], v[50:51]\n v_fma_f64 v[42:43], v[44:45], v[46:47], v[50:51]\n v_bitop3_b32 v60, v61, v62, v63 bitop3:0x96\n v_bitop3_b32 v58, v61, v62, v63 bitop3:0x96", CL)
 
 struct E { const char *n; void (*f)(uint32_t *, int); };
-int main()
+int main(int argc, char **argv)   // optional argument: run only the probes whose name contains it
 {
     const int grid = 256 * 8;
     uint32_t *out; CK(hipMalloc(&out, (size_t)grid * 256 * 4));
@@ -125,8 +133,10 @@ int main()
               {"lshl_or_inl", lshl_or_inl}, {"lshl_add_inl", lshl_add_inl}, {"perm_vvv", perm_vvv}, {"alignbit_vvv", alignbit_vvv}, {"mov_sdwa", mov_sdwa},
               {"lshl_sdwa", lshl_sdwa}, {"cvt_f64_u32", cvt_f64_u32}, {"cvt_f64_i32", cvt_f64_i32}, {"cvt_f32_u32", cvt_f32_u32}, {"cvt_f32_ubyte1", cvt_f32_ubyte},
               {"fma64_inl", fma64_inl}, {"mul64_inl", mul64_inl}, {"mul32_inl", mul32_inl}, {"fma32_inl", fma32_inl}, {"mov_b32", mov_b32}, {"ldexp64_vv", ldexp64_vv},
+              {"mov_sgpr", mov_sgpr}, {"mov64_sgpr", mov64_sgpr}, {"mov64_vv", mov64_vv}, {"mix_movs_2xor(3)", mix_movs_2xor}, {"mix_2xor_sv(2)", mix_2xor_sv},
               {"mix_mad_2bitop(3)", mix_mad_2bitop}, {"mix_2mad_2bitop(4)", mix_2mad_2bitop}, {"mix_4mad_4bitop(8)", mix_4mad_4bitop}, {"mix_2fma64_2bitop(4)", mix_2fma64_2bitop}};
     for (auto &e : es) {
+        if (argc > 1 && !strstr(e.n, argv[1])) continue;
         float ms[2];
         const int it[2] = {500, 1500};
         for (int k = 0; k < 2; ++k) {
