@@ -1119,6 +1119,78 @@ int mcamd_price_localvol_smile_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, 
 int mcamd_finalize_smile(const double *stats, uint64_t n, const mcamd_option *opt, uint32_t n_steps,
                          const mcamd_smile *smile, const uint32_t *h_expiry_steps, double *h_price, double *h_std_err);
 
+/* ---- Worst-of autocallable notes under per-asset local-volatility surfaces, dividend yields q_j ----
+ * Additive to ABI version 5: first carried by the build that ships csrc/autocall_localvol.hip (no struct of an earlier
+ * call changed, so MCAMD_ABI_VERSION stays 5; a caller finds out with dlsym).  The note of mcamd_price_autocall, stepped
+ * on d = autocall->n_assets correlated assets, asset j under surfaces[j] and the dividend yield q[j].  One normal per
+ * asset per step from the stream mcamd_price_basket draws from; nothing else is drawn.  opt supplies r and T only:
+ * opt->S0, opt->v, opt->K and opt->B are ignored.  n = n_steps, dt = T / n.  All path arithmetic is in the path
+ * precision and in NATURAL-log units.
+ *   Surfaces.  surfaces: a host array of d surface pointers (read before the call returns).  Asset j's surface is in
+ *       x = ln(S_j / S_j,0), the asset's own log-performance.  The same surface may be passed for several assets (its
+ *       nodes then count once per asset).  The lookup sigma_j(row, X), the slice rule row_j(i) = floor(i n_t,j / n), the
+ *       clamp, and the narrowing of sigma_k, slope_k, x_min and 1 / dx are exactly those of mcamd_price_localvol, asset by
+ *       asset, each with its own grid.
+ *   Normals.  z_{i,k}, i = 0..n-1, k = 0..d-1, is normal number i d + k of the path's stream: Philox subsequence = the
+ *       GLOBAL path id, block (i d + k) / NB, slot (i d + k) % NB, NB = 4 in fp32 and 2 in fp64 — mcamd_price_basket's
+ *       layout.  The lower Cholesky factor l of corr[:d, :d] is the one mcamd_price_basket forms (same pivot rule),
+ *       narrowed once to the path precision.  w_j = sum_{k <= j} l_jk z_{i,k}, evaluated as a chain of fused
+ *       multiply-adds in ascending k starting from 0:  w <- fma(l_jk, z_{i,k}, w).  At j = 0 (l_00 = 1) this is z_{i,0}
+ *       exactly.
+ *   Step.  X_{j,0} = 0.  s_j = sigma_j(row_j(i), X_{j,i}), then
+ *       X_{j,i+1} = X_{j,i} + fma(s_j sqrt(dt), w_j, fma(-s_j^2, dt / 2, (r - q_j) dt)),
+ *       with (r - q_j) dt, dt / 2 and sqrt(dt) formed in double on the host and narrowed: the operation order of
+ *       mcamd_price_localvol's step with z replaced by w_j, so d = 1 walks that call's path bit for bit.
+ *       l_i = min_j X_{j,i}, the log of the worst performance after step i.
+ *   Dates, levels and payments.  The observation dates q = 1..M at the ends of steps s_q = q observe_every, the levels
+ *       L_q, the payments pay_q (doubles), the call test "first date q >= first_call_date with l_{s_q} >= ln L_q", the
+ *       knock-in modes MCAMD_AUTOCALL_KI_*, the rule that at date M the call test comes first, the sample of a path never
+ *       called (y = min(A_n, 1) if knocked in, 1 otherwise) and the two step counters are exactly those of
+ *       mcamd_price_autocall — but ln L_q and ln ki_level are narrowed once to the path precision in NATURAL-log units,
+ *       where that call narrows them in exponent units.  A_n = e^{l_n} through the exponential that ends a log-space
+ *       path, exp_of_logreturn(1, l_n exp_scale) with exp_scale = log2 e (fp32) or 65536 / ln 2 (fp64) narrowed to the
+ *       path precision, formed once per path and widened to fp64.
+ *   price = exp(-rT) mean(y): mcamd_finalize and mcamd_finalize_stats serve unchanged.
+ * Flat surfaces with q = 0 give the call dates and, up to rounding, the samples of mcamd_price_autocall at v_j = sigma_j.
+ * A wavefront whose lanes have all been called leaves the step loop at the end of its step group, as there.  Two runs of
+ * one job give the same bits.
+ * d_samples, res (mcamd_autocall_result) and the enqueue form's d_stats = {sum, sumsq, n_called, sum_t_call,
+ * n_knocked_in, n}: as mcamd_price_autocall; mcamd_enqueued_kernel_ms covers the enqueue form.
+ * Requirements (MCAMD_ERR_INVALID before any device work).  First, in this order, everything that needs neither a
+ * surface nor the context: opt, sim, autocall, res non-NULL; reserved[0] == reserved[1] == 0; what mcamd_price_basket
+ * refuses of n_assets and corr, with the same Cholesky pivot rule; q[j] finite for j < d; observe_every >= 1,
+ * n_steps % observe_every == 0 and 1 <= M <= MCAMD_AUTOCALL_MAX_DATES; 1 <= first_call_date <= M; the terms as
+ * mcamd_price_autocall checks them (ki_monitoring, coupon, call_level, call_step_down, L_M > 0, ki_level); r finite;
+ * use_window, P1, P2, Ik, Sk, Tk and opt->dt all 0; sim->flags 0 or MCAMD_FLAG_LOG_SPACE; what mcamd_price_paths refuses
+ * on sim (its fp64 exponent-range bound at the drift r - q_j alone, asset by asset).  Then the surfaces: a NULL array or
+ * entry; a surface created on another context; sum_j n_t,j n_x,j > MCAMD_LOCALVOL_MAX_NODES (the d pair tables share the
+ * kernel's LDS); in fp64 the exponent-range bound of mcamd_price_localvol, asset by asset, at |r - q_j| and the largest
+ * entry of surfaces[j].  Then the context.  q and corr beyond n_assets are ignored.  An empty shard returns zeros and
+ * launches nothing; its enqueue form writes a zero record in stream order.
+ * Out of scope: Greeks, continuous knock-in, lane compaction of the called paths, calibration of the surfaces, a
+ * mcamd_group_* form and a shim name (the reference has no such product).  Multi-GPU: every rank prices its shard with
+ * surfaces of its own context; the 6-double records add.  New. */
+typedef struct mcamd_autocall_localvol {   /* 632 bytes: mcamd_autocall with q[] in the place of v[] */
+    int32_t n_assets;         /* d, 1..MCAMD_BASKET_MAX_ASSETS */
+    int32_t ki_monitoring;    /* MCAMD_AUTOCALL_KI_* */
+    uint32_t observe_every;   /* steps between observation dates; divides n_steps */
+    uint32_t first_call_date; /* 1..M: the first date the note can be called at */
+    int32_t reserved[2];      /* must be 0 */
+    double call_level;        /* L_1, as a performance (1 = the spots) */
+    double call_step_down;    /* L_q = call_level - (q - 1) call_step_down */
+    double coupon;            /* per date, snowball: a path called at date q receives 1 + q coupon */
+    double ki_level;          /* as a performance, in (0, 1] and below L_M */
+    double q[8];              /* continuous dividend yields */
+    double corr[64];          /* correlations, row-major with stride 8 */
+} mcamd_autocall_localvol;
+
+int mcamd_price_autocall_localvol(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                                  const mcamd_autocall_localvol *autocall, const mcamd_localvol_surface *const *surfaces,
+                                  void *d_samples, mcamd_autocall_result *res);
+int mcamd_price_autocall_localvol_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                                          const mcamd_autocall_localvol *autocall,
+                                          const mcamd_localvol_surface *const *surfaces, void *d_samples, double *d_stats);
+
 /* Host: discount + mean + standard error + 95% CI from (sum, sumsq, n) — after an all-reduce
  * over shards, or directly.  Fills price/std_err/ci_* (and copies sum/sumsq/n) in *res. */
 int mcamd_finalize(double sum, double sumsq, uint64_t n, double r, double T, mcamd_result *res);

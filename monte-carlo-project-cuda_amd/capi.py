@@ -61,6 +61,7 @@ EXPORTS = [
     "mcamd_localvol_surface_create", "mcamd_localvol_surface_destroy", "mcamd_price_localvol",
     "mcamd_price_localvol_enqueue", "mcamd_localvol_sigma_f64", "mcamd_bs_price_f64",
     "mcamd_bs_implied_vol_f64", "mcamd_price_localvol_smile", "mcamd_price_localvol_smile_enqueue", "mcamd_finalize_smile",
+    "mcamd_price_autocall_localvol", "mcamd_price_autocall_localvol_enqueue",
 ]
 
 
@@ -178,6 +179,15 @@ class AutocallResult(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class AutocallLocalVol(C.Structure):
+    """mcamd_autocall_localvol: the terms of the worst-of autocallable note mcamd_price_autocall_localvol prices, the
+    dividend yields of its assets and their correlations (mcamd_autocall with q in the place of v)."""
+    _fields_ = [("n_assets", C.c_int32), ("ki_monitoring", C.c_int32), ("observe_every", C.c_uint32),
+                ("first_call_date", C.c_uint32), ("reserved", C.c_int32 * 2), ("call_level", C.c_double),
+                ("call_step_down", C.c_double), ("coupon", C.c_double), ("ki_level", C.c_double),
+                ("q", C.c_double * 8), ("corr", C.c_double * 64)]
 
 
 class LocalVolGrid(C.Structure):
@@ -304,6 +314,10 @@ def load() -> C.CDLL:
     L.mcamd_price_autocall.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Autocall), vp,
                                        C.POINTER(AutocallResult)]
     L.mcamd_price_autocall_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Autocall), vp, vp]
+    L.mcamd_price_autocall_localvol.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(AutocallLocalVol),
+                                                C.POINTER(vp), vp, C.POINTER(AutocallResult)]
+    L.mcamd_price_autocall_localvol_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim),
+                                                        C.POINTER(AutocallLocalVol), C.POINTER(vp), vp, vp]
     L.mcamd_autocall_single_date_price_f64.argtypes = [f64, f64, f64, f64, f64, f64, i32, C.POINTER(f64)]
     L.mcamd_localvol_surface_create.argtypes = [vp, C.POINTER(LocalVolGrid), C.POINTER(f64), C.POINTER(vp)]
     L.mcamd_localvol_surface_destroy.argtypes = [vp]
@@ -441,6 +455,29 @@ def make_autocall(v, corr, observe_every=1, call_level=1.0, coupon=0.0, ki_level
         for k in range(d):
             a.corr[8 * j + k] = float(corr[j][k])
     return a
+
+
+def make_autocall_localvol(q, corr, observe_every=1, call_level=1.0, coupon=0.0, ki_level=0.0,
+                           ki_monitoring=AUTOCALL_KI_NONE, call_step_down=0.0, first_call_date=1) -> AutocallLocalVol:
+    """q: d dividend yields (d at most BASKET_MAX_ASSETS); corr: d x d (nested sequences or an array)."""
+    d = len(q)
+    if not 1 <= d <= BASKET_MAX_ASSETS or len(corr) != d or any(len(row) != d for row in corr):
+        raise ValueError(f"an autocallable takes 1..{BASKET_MAX_ASSETS} assets, q of d and corr of d x d values")
+    a = AutocallLocalVol(d, ki_monitoring, observe_every, first_call_date)
+    a.call_level, a.call_step_down, a.coupon, a.ki_level = call_level, call_step_down, coupon, ki_level
+    for j in range(d):
+        a.q[j] = float(q[j])
+        for k in range(d):
+            a.corr[8 * j + k] = float(corr[j][k])
+    return a
+
+
+def surface_array(surfaces):
+    """the host array of surface pointers the autocall calls under local volatility take: None stays NULL, and so does
+    an entry that is None"""
+    if surfaces is None:
+        return None
+    return (C.c_void_p * max(len(surfaces), 1))(*[None if s is None else s._h for s in surfaces])
 
 
 def autocall_single_date_price_f64(T, r, sigma, call_level, coupon, ki_level=0.0, ki_monitoring=AUTOCALL_KI_NONE) -> float:
@@ -757,6 +794,23 @@ class Context:
         (>= 6 doubles; finalize_stats without the control variate)."""
         _check(self._L.mcamd_price_autocall_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(autocall),
                                                     _ptr(samples), _ptr(stats)))
+
+    def price_autocall_localvol(self, opt: Option, sim: Sim, autocall: AutocallLocalVol, surfaces,
+                                samples=None) -> AutocallResult:
+        """Worst-of autocallable note under per-asset local-volatility surfaces (mcamd_price_autocall_localvol): r and T
+        come from opt; surfaces: one LocalVolSurface per asset (the same one may appear several times).  samples:
+        optional device tensor of n_paths_local values of the path precision that receives every path's sample."""
+        res = AutocallResult()
+        _check(self._L.mcamd_price_autocall_localvol(self._h, C.byref(opt), C.byref(sim), C.byref(autocall),
+                                                     surface_array(surfaces), _ptr(samples), C.byref(res)))
+        return res
+
+    def price_autocall_localvol_enqueue(self, opt: Option, sim: Sim, autocall: AutocallLocalVol, surfaces, stats,
+                                        samples=None) -> None:
+        """Asynchronous: leaves {sum, sumsq, n_called, sum_t_call, n_knocked_in, n} in the device tensor `stats`
+        (>= 6 doubles; finalize_stats without the control variate).  The surfaces must outlive the enqueued work."""
+        _check(self._L.mcamd_price_autocall_localvol_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(autocall),
+                                                             surface_array(surfaces), _ptr(samples), _ptr(stats)))
 
     def price_basket(self, opt: Option, sim: Sim, basket: Basket, samples=None) -> Result:
         """Basket, spread or rainbow option on correlated assets (mcamd_price_basket): r, T, K and the barrier level B

@@ -1,0 +1,33 @@
+// autocall_localvol.hip — worst-of autocallable notes under per-asset local-volatility surfaces for gfx950: the
+// launcher's checks and the fp64 kernels (D = 1..8, two knock-in variants).  The fp32 kernels are compiled in
+// autocall_localvol_f32.hip; the kernel itself is in autocall_localvol_impl.hpp.
+#include "autocall_localvol_impl.hpp"
+
+namespace mcamd {
+
+hipError_t launch_autocall_localvol_f64(const AutocallLocalVolJob &job, double *d_partials, uint32_t grid,
+                                        const FinishSpec &finish, hipStream_t stream)
+{
+    return launch_autocall_localvol_t<double>(job, d_partials, grid, finish, stream);
+}
+
+hipError_t launch_autocall_localvol(const AutocallLocalVolJob &job, double *d_partials, uint32_t grid,
+                                    const FinishSpec &finish, hipStream_t stream)
+{
+    if (!finish_ok(finish, grid)) return hipErrorInvalidValue;
+    const uint32_t n_steps = job.n_steps;
+    if (job.observe_every == 0 || job.n_dates == 0 || job.n_dates > static_cast<uint32_t>(kAutocallMaxDates) ||
+        static_cast<uint64_t>(job.n_dates) * job.observe_every != n_steps || job.first_call_date == 0)
+        return hipErrorInvalidValue;   // the date tables are indexed by a counter these rules bound
+    if (job.d < 1 || job.d > kBasketMaxAssets) return hipErrorInvalidValue;
+    uint64_t nodes = 0;                // the D tables share one LDS allocation: no index may leave its own table
+    for (int j = 0; j < job.d; ++j) {
+        if (!job.d_table[j] || job.n_x[j] < 2 || job.n_t[j] < 1) return hipErrorInvalidValue;
+        nodes += static_cast<uint64_t>(job.n_t[j]) * job.n_x[j];
+        if (nodes > kLocalVolMaxNodes) return hipErrorInvalidValue;
+    }
+    return job.precision == 32 ? launch_autocall_localvol_f32(job, d_partials, grid, finish, stream)
+                               : launch_autocall_localvol_f64(job, d_partials, grid, finish, stream);
+}
+
+}  // namespace mcamd

@@ -11,6 +11,7 @@
 #include "basket.hpp"
 #include "asian.hpp"
 #include "autocall.hpp"
+#include "autocall_localvol.hpp"
 #include "localvol.hpp"
 #include "localvol_smile.hpp"
 
@@ -40,6 +41,7 @@ static_assert(sizeof(mcamd_basket) == 728, "C ABI struct layout changed: bump MC
 static_assert(sizeof(mcamd_asian) == 24, "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
 static_assert(sizeof(mcamd_autocall) == 632 && sizeof(mcamd_autocall_result) == 112,
               "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
+static_assert(sizeof(mcamd_autocall_localvol) == 632, "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
 static_assert(sizeof(mcamd_localvol_grid) == 24 && sizeof(mcamd_localvol) == 24,
               "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
 static_assert(sizeof(mcamd_smile) == 24, "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
@@ -1309,6 +1311,118 @@ int prepare_autocall(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *s
                             }});
 }
 
+// The autocall calls under per-asset local-volatility surfaces.  Every refusal that needs neither a surface nor the
+// context comes first, in prepare_autocall's order; then the surfaces; then the context.  opt supplies r and T alone.
+template <typename Drive>
+int prepare_autocall_localvol(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                              const mcamd_autocall_localvol *ac, const mcamd_localvol_surface *const *surfaces,
+                              void *d_samples, Drive drive)
+{
+    if (!opt || !sim || !ac) return fail(MCAMD_ERR_INVALID, "opt, sim, autocall and surfaces must be non-NULL");
+    if (ac->reserved[0] != 0 || ac->reserved[1] != 0)
+        return fail(MCAMD_ERR_INVALID, "autocall->reserved must be 0, got {%d, %d}", ac->reserved[0], ac->reserved[1]);
+    // n_assets and corr through the basket's own checks and Cholesky factor: unit spots, weights and volatilities
+    mcamd_basket assets{};
+    assets.n_assets = ac->n_assets;
+    assets.payoff = MCAMD_PAYOFF_PUT;
+    for (int j = 0; j < MCAMD_BASKET_MAX_ASSETS; ++j) assets.S0[j] = assets.w[j] = assets.v[j] = 1.0;
+    std::memcpy(assets.corr, ac->corr, sizeof assets.corr);
+    double L[64];
+    if (int rc = check_basket_assets(&assets, true, L)) return rc;
+    const int d = ac->n_assets;
+    for (int j = 0; j < d; ++j)
+        if (!std::isfinite(ac->q[j]))
+            return fail(MCAMD_ERR_INVALID, "every dividend yield q must be finite, got q[%d] = %g", j, ac->q[j]);
+    if (ac->observe_every == 0 || sim->n_steps % ac->observe_every != 0)
+        return fail(MCAMD_ERR_INVALID, "observe_every must be >= 1 and divide n_steps (observe_every = %u, n_steps = %u)",
+                    ac->observe_every, sim->n_steps);
+    const uint32_t M = sim->n_steps / ac->observe_every;
+    if (M > MCAMD_AUTOCALL_MAX_DATES)   // M == 0 is n_steps == 0, which check_request refuses below
+        return fail(MCAMD_ERR_INVALID, "n_steps / observe_every = %u observation dates exceed MCAMD_AUTOCALL_MAX_DATES = %d",
+                    M, MCAMD_AUTOCALL_MAX_DATES);
+    if (M != 0 && (ac->first_call_date < 1 || ac->first_call_date > M))
+        return fail(MCAMD_ERR_INVALID, "first_call_date must be 1..%u (the observation dates), got %u", M,
+                    ac->first_call_date);
+    const double L_last = ac->call_level - (static_cast<double>(M) - 1.0) * ac->call_step_down;
+    if (int rc = check_autocall_terms(ac->coupon, ac->call_level, ac->call_step_down, M ? L_last : ac->call_level,
+                                      ac->ki_monitoring, ac->ki_level))
+        return rc;
+    if (!std::isfinite(opt->r)) return fail(MCAMD_ERR_INVALID, "option parameters must be finite with T > 0");
+    // as prepare_localvol: the shared checks on a copy that carries no spot, strike or volatility of its own, with
+    // each asset's drift r - q_j alone in the fp64 exponent-range bound
+    mcamd_option seen = *opt;
+    seen.S0 = 1.0;
+    seen.K = seen.B = 0.0;
+    seen.v = 1.0;
+    if (int rc = check_spot_start("local-volatility autocallable", false, &seen, sim)) return rc;
+    seen.v = 0.0;
+    for (int j = 0; j < d; ++j) {
+        seen.r = opt->r - ac->q[j];
+        if (int rc = check_request(&seen, sim)) return rc;
+    }
+    // the surfaces
+    if (!surfaces) return fail(MCAMD_ERR_INVALID, "opt, sim, autocall and surfaces must be non-NULL");
+    for (int j = 0; j < d; ++j)
+        if (!surfaces[j]) return fail(MCAMD_ERR_INVALID, "surfaces[%d] is NULL: every asset needs a surface", j);
+    for (int j = 0; j < d; ++j)
+        if (surfaces[j]->ctx != ctx || (ctx && surfaces[j]->ctx_id != ctx->id))
+            return fail(MCAMD_ERR_INVALID, "the surface of asset %d was created on another context", j);
+    uint64_t nodes = 0;
+    for (int j = 0; j < d; ++j) nodes += static_cast<uint64_t>(surfaces[j]->grid.n_t) * surfaces[j]->grid.n_x;
+    if (nodes > MCAMD_LOCALVOL_MAX_NODES)
+        return fail(MCAMD_ERR_INVALID, "the %d surfaces hold %llu nodes together; at most %d fit the kernel's LDS tables "
+                                       "(a surface passed for several assets counts once per asset)", d,
+                    static_cast<unsigned long long>(nodes), MCAMD_LOCALVOL_MAX_NODES);
+    const double dt = opt->T / static_cast<double>(sim->n_steps);
+    if (sim->precision == MCAMD_F64) {
+        // check_request's bound asset by asset, with the largest drift and volatility any node of its surface can give
+        for (int j = 0; j < d; ++j) {
+            const double top = surfaces[j]->sigma_max;
+            const double per_step = (std::fabs(opt->r - ac->q[j]) + 0.5 * top * top) * dt + 8.6 * top * std::sqrt(dt);
+            if (!(per_step < 700.0) || !(per_step * static_cast<double>(sim->n_steps) < 20000.0))
+                return fail(MCAMD_ERR_INVALID,
+                            "fp64 path: |drift| + 8.6 vol = %.3g per step over %u steps exceeds the exponent range "
+                            "(per step < 700, per path < 20000; asset %d)", per_step, sim->n_steps, j);
+        }
+    }
+    if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
+    if (sim->n_paths_local == 0) return drive(empty_call());
+    mcamd::AutocallLocalVolJob job{};
+    job.seed = sim->seed;
+    job.path_offset = sim->path_offset;
+    job.n_local = sim->n_paths_local;
+    job.n_steps = sim->n_steps;
+    job.precision = sim->precision;
+    job.d = d;
+    job.dt = dt;
+    for (int j = 0; j < d; ++j) {
+        job.mu[j] = opt->r - ac->q[j];
+        for (int k = 0; k <= j; ++k) job.chol[j * (j + 1) / 2 + k] = L[8 * j + k];
+        job.n_t[j] = surfaces[j]->grid.n_t;
+        job.n_x[j] = surfaces[j]->grid.n_x;
+        job.x_min[j] = surfaces[j]->grid.x_min;
+        job.x_max[j] = surfaces[j]->grid.x_max;
+        job.d_table[j] = sim->precision == MCAMD_F32 ? surfaces[j]->d_tab32 : surfaces[j]->d_tab64;
+    }
+    job.observe_every = ac->observe_every;
+    job.n_dates = M;
+    job.first_call_date = ac->first_call_date;
+    for (uint32_t q = 1; q <= M; ++q) {
+        const double t_q = static_cast<double>(q * ac->observe_every) * dt;
+        job.log_level[q - 1] = std::log(ac->call_level - (static_cast<double>(q) - 1.0) * ac->call_step_down);
+        job.pay[q - 1] = (1.0 + static_cast<double>(q) * ac->coupon) * std::exp(opt->r * (opt->T - t_q));
+    }
+    job.ki = ac->ki_monitoring != MCAMD_AUTOCALL_KI_NONE;
+    job.ki_every_step = ac->ki_monitoring == MCAMD_AUTOCALL_KI_EVERY_STEP;
+    job.log_ki = job.ki ? std::log(ac->ki_level) : 0.0;
+    job.d_samples = d_samples;
+    const uint32_t grid = mcamd::one_path_per_thread_grid(job.n_local);
+    return drive(DeviceCall{job.n_local, grid, mcamd::kAutocallRecord, 6, Finish::kFolded,
+                            [&](const mcamd::FinishSpec &fs) {
+                                return mcamd::launch_autocall_localvol(job, ctx->d_partials, grid, fs, ctx->stream);
+                            }});
+}
+
 // h(S0) replaces an estimate it exceeds (exercise at t = 0); returns whether it did
 bool floor_at_immediate(double h0, double *price, double *std_err)
 {
@@ -2367,6 +2481,45 @@ int mcamd_price_localvol_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const 
 {
     return prepare_localvol(ctx, opt, sim, localvol, surface, d_samples,
                             [&](const auto &call) { return run_enqueue(ctx, call, d_stats); });
+}
+
+// fills *res from an autocall kernel's record: {sum, sumsq, paths called, sum of their call times, paths not called and
+// knocked in, wave-steps, live}
+static void fill_autocall_result(const double *rec, uint64_t n, double r, double T, mcamd_autocall_result *res)
+{
+    const Estimate e = estimate(rec[0], rec[1], n, std::exp(-r * T));
+    res->sum = rec[0];
+    res->sumsq = rec[1];
+    res->n = n;
+    res->price = e.value;
+    res->std_err = e.std_err;
+    set_ci(res);
+    res->n_called = static_cast<uint64_t>(std::llround(rec[2]));
+    res->sum_t_call = rec[3];
+    res->n_knocked_in = static_cast<uint64_t>(std::llround(rec[4]));
+    res->work_steps = 64.0 * rec[5];   // wave-steps x 64 lanes
+    res->live_steps = rec[6];
+}
+
+int mcamd_price_autocall_localvol(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                                  const mcamd_autocall_localvol *autocall, const mcamd_localvol_surface *const *surfaces,
+                                  void *d_samples, mcamd_autocall_result *res)
+{
+    if (!res) return fail(MCAMD_ERR_INVALID, "opt, sim, autocall, surfaces and res must be non-NULL");
+    std::memset(res, 0, sizeof *res);
+    return prepare_autocall_localvol(ctx, opt, sim, autocall, surfaces, d_samples, [&](const auto &call) {
+        return run_sync(ctx, call, res, [&](const double *rec) {
+            fill_autocall_result(rec, sim->n_paths_local, opt->r, opt->T, res);
+        });
+    });
+}
+
+int mcamd_price_autocall_localvol_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                                          const mcamd_autocall_localvol *autocall,
+                                          const mcamd_localvol_surface *const *surfaces, void *d_samples, double *d_stats)
+{
+    return prepare_autocall_localvol(ctx, opt, sim, autocall, surfaces, d_samples,
+                                     [&](const auto &call) { return run_enqueue(ctx, call, d_stats); });
 }
 
 // The smile's two launches on the context's stream: the walk into the per-wavefront records, then their sum into out.
