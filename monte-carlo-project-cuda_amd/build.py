@@ -22,7 +22,8 @@ SOURCES = ["price_f64.hip", "price_f32.hip", "store.hip", "aux.hip", "nmc.hip", 
 HEADERS = ["launch.hpp", "mc_device.hpp", "path_consts.hpp", "fast64.hpp", "tables64.inc", "tables64_consts.inc",
            "price_impl.hpp", "nmc_compact.hpp", "greeks.hpp", "american.hpp", "american_device.hpp",
            "american_dual.hpp", "barrier.hpp", "lookback.hpp", "basket.hpp", "basket_device.hpp", "asian.hpp", "autocall.hpp",
-           "localvol.hpp", "localvol_smile.hpp", "autocall_localvol.hpp", "autocall_localvol_impl.hpp"]
+           "localvol.hpp", "localvol_device.hpp", "localvol_smile.hpp", "autocall_localvol.hpp",
+           "autocall_localvol_impl.hpp"]
 ARCH = "gfx950"
 
 

@@ -22,8 +22,8 @@ hipError_t launch_autocall_localvol(const AutocallLocalVolJob &job, double *d_pa
     if (job.d < 1 || job.d > kBasketMaxAssets) return hipErrorInvalidValue;
     uint64_t nodes = 0;                // the D tables share one LDS allocation: no index may leave its own table
     for (int j = 0; j < job.d; ++j) {
-        if (!job.d_table[j] || job.n_x[j] < 2 || job.n_t[j] < 1) return hipErrorInvalidValue;
-        nodes += static_cast<uint64_t>(job.n_t[j]) * job.n_x[j];
+        if (!lv_grid_ok(job.surface[j], n_steps)) return hipErrorInvalidValue;
+        nodes += static_cast<uint64_t>(job.surface[j].n_t) * job.surface[j].n_x;
         if (nodes > kLocalVolMaxNodes) return hipErrorInvalidValue;
     }
     return job.precision == 32 ? launch_autocall_localvol_f32(job, d_partials, grid, finish, stream)

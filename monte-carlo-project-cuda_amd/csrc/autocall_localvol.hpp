@@ -23,9 +23,7 @@ struct AutocallLocalVolJob {
     double mu[kBasketMaxAssets];           // r - q_j
     double chol[kBasketMaxCoefs];          // the Cholesky factor of corr at [j (j + 1) / 2 + k], k <= j
     double dt;                             // T / n_steps
-    uint32_t n_t[kBasketMaxAssets], n_x[kBasketMaxAssets];   // asset j's grid; sum_j n_t n_x <= kLocalVolMaxNodes
-    double x_min[kBasketMaxAssets], x_max[kBasketMaxAssets];
-    const void *d_table[kBasketMaxAssets]; // asset j's n_t n_x VolPair of the path precision, device memory
+    LocalVolGrid surface[kBasketMaxAssets];   // asset j's; sum_j n_t n_x <= kLocalVolMaxNodes
     uint32_t observe_every;                // steps between observation dates
     uint32_t n_dates;                      // M = n_steps / observe_every, 1..kAutocallMaxDates
     uint32_t first_call_date;              // 1..M

@@ -32,16 +32,6 @@ struct BarrierArgs {
     GridFinish fin;
 };
 
-// 1 - exp(-q), q >= 0 in the units BarrierArgs::kq leaves it in
-__device__ __forceinline__ float bridge_factor(float q, const MathCtx<float> &)
-{
-    return 1.0f - __builtin_amdgcn_exp2f(-q);
-}
-__device__ __forceinline__ double bridge_factor(double q, const MathCtx<double> &m)
-{
-    return 1.0 - f64::mul_exp(1.0, -q, m.t.exp_hi_tab, m.t.exp_lo_tab);
-}
-
 template <typename T, bool UP, bool CONT, bool OUT>
 __global__ __launch_bounds__(kBlock) void barrier_kernel(BarrierArgs<T> a, double *__restrict__ partials)
 {

@@ -748,6 +748,50 @@ int check_localvol_grid(const mcamd_localvol_grid *grid, const double *h_sigma, 
     return MCAMD_OK;
 }
 
+// What the local-volatility calls (name: how the messages call the product) refuse of the option, the flags and sim
+// through the checks shared with the other calls.  seen: the caller's copy of the option with every field it does not
+// read made harmless; it carries no volatility of its own, so check_spot_start sees v = 1 and check_request v = 0,
+// which leaves each drift mu[j] = r - q_j alone in the fp64 exponent-range bound.
+int check_localvol_request(const char *name, mcamd_option seen, const mcamd_sim *sim, const double *mu, int n_mu)
+{
+    seen.v = 1.0;
+    if (int rc = check_spot_start(name, false, &seen, sim)) return rc;
+    seen.v = 0.0;
+    for (int j = 0; j < n_mu; ++j) {
+        seen.r = mu[j];
+        if (int rc = check_request(&seen, sim)) return rc;
+    }
+    return MCAMD_OK;
+}
+
+// check_request's fp64 bound with the largest drift and volatility any node of a surface can give; asset >= 0 names
+// the asset the surface belongs to.
+int check_localvol_exponent_range(double mu, double sigma_max, double dt, uint32_t n_steps, int asset = -1)
+{
+    const double per_step = (std::fabs(mu) + 0.5 * sigma_max * sigma_max) * dt + 8.6 * sigma_max * std::sqrt(dt);
+    if (per_step < 700.0 && per_step * static_cast<double>(n_steps) < 20000.0) return MCAMD_OK;
+    if (asset < 0)
+        return fail(MCAMD_ERR_INVALID,
+                    "fp64 path: |drift| + 8.6 vol = %.3g per step over %u steps exceeds the exponent range "
+                    "(per step < 700, per path < 20000)", per_step, n_steps);
+    return fail(MCAMD_ERR_INVALID,
+                "fp64 path: |drift| + 8.6 vol = %.3g per step over %u steps exceeds the exponent range "
+                "(per step < 700, per path < 20000; asset %d)", per_step, n_steps, asset);
+}
+
+// whether the surface was created on this context (a NULL context owns none)
+bool surface_belongs(const mcamd_localvol_surface *surface, const mcamd_ctx *ctx)
+{
+    return ctx && surface->ctx == ctx && surface->ctx_id == ctx->id;
+}
+
+// the surface as a job of the given path precision carries it
+mcamd::LocalVolGrid job_surface(const mcamd_localvol_surface *surface, int precision)
+{
+    return {surface->grid.n_t, surface->grid.n_x, surface->grid.x_min, surface->grid.x_max,
+            precision == MCAMD_F32 ? surface->d_tab32 : surface->d_tab64};
+}
+
 // The local-volatility calls.  The kernel always finishes its own sum (one_path_per_thread_grid caps the grid); every
 // refusal that depends on the request alone comes before the context is looked at, and all that do not need the
 // surface before the surface is.  opt->v is ignored.
@@ -771,29 +815,15 @@ int prepare_localvol(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *s
         if (int rc = check_barrier_kind(opt->S0, opt->B, lv->barrier, lv->payoff)) return rc;
     }
     if (!std::isfinite(opt->r)) return fail(MCAMD_ERR_INVALID, "option parameters must be finite with T > 0");
-    // the checks shared with the other calls, on a copy that carries no volatility of its own: everything they refuse
-    // of the option, the flags and sim, with the drift r - q alone in the fp64 exponent-range bound
-    mcamd_option seen = *opt;
-    seen.r = opt->r - lv->q;
-    seen.v = 1.0;
-    if (int rc = check_spot_start("local-volatility", false, &seen, sim)) return rc;
-    seen.v = 0.0;
-    if (int rc = check_request(&seen, sim)) return rc;
+    const double mu = opt->r - lv->q;
+    if (int rc = check_localvol_request("local-volatility", *opt, sim, &mu, 1)) return rc;
     if (!(opt->S0 > 0.0)) return fail(MCAMD_ERR_INVALID, "local-volatility options need S0 > 0 (S0 = %g)", opt->S0);
     if (!surface) return fail(MCAMD_ERR_INVALID, "opt, sim, localvol and surface must be non-NULL");
     const double dt = opt->T / static_cast<double>(sim->n_steps);
-    if (sim->precision == MCAMD_F64) {
-        // check_request's bound with the largest drift and volatility any node can give
-        const double top = surface->sigma_max;
-        const double per_step = (std::fabs(seen.r) + 0.5 * top * top) * dt + 8.6 * top * std::sqrt(dt);
-        if (!(per_step < 700.0) || !(per_step * static_cast<double>(sim->n_steps) < 20000.0))
-            return fail(MCAMD_ERR_INVALID,
-                        "fp64 path: |drift| + 8.6 vol = %.3g per step over %u steps exceeds the exponent range "
-                        "(per step < 700, per path < 20000)", per_step, sim->n_steps);
-    }
+    if (sim->precision == MCAMD_F64)
+        if (int rc = check_localvol_exponent_range(mu, surface->sigma_max, dt, sim->n_steps)) return rc;
     if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
-    if (surface->ctx != ctx || surface->ctx_id != ctx->id)
-        return fail(MCAMD_ERR_INVALID, "the surface was created on another context");
+    if (!surface_belongs(surface, ctx)) return fail(MCAMD_ERR_INVALID, "the surface was created on another context");
     if (sim->n_paths_local == 0) return drive(empty_call());
     mcamd::LocalVolJob job;
     job.seed = sim->seed;
@@ -804,18 +834,14 @@ int prepare_localvol(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *s
     job.S0 = opt->S0;
     job.K = opt->K;
     job.B = opt->B;
-    job.mu = opt->r - lv->q;
+    job.mu = mu;
     job.dt = dt;
     job.barrier = barrier;
     job.up = lv->barrier == MCAMD_BARRIER_UP_OUT || lv->barrier == MCAMD_BARRIER_UP_IN;
     job.out = lv->barrier == MCAMD_BARRIER_DOWN_OUT || lv->barrier == MCAMD_BARRIER_UP_OUT;
     job.continuous = barrier && lv->monitoring == MCAMD_MONITOR_CONTINUOUS;
     job.put = lv->payoff == MCAMD_PAYOFF_PUT;
-    job.n_t = surface->grid.n_t;
-    job.n_x = surface->grid.n_x;
-    job.x_min = surface->grid.x_min;
-    job.x_max = surface->grid.x_max;
-    job.d_table = sim->precision == MCAMD_F32 ? surface->d_tab32 : surface->d_tab64;
+    job.surface = job_surface(surface, sim->precision);
     job.d_samples = d_samples;
     const uint32_t grid = mcamd::one_path_per_thread_grid(job.n_local);
     return drive(DeviceCall{job.n_local, grid, mcamd::kLocalVolRecord, 6, Finish::kFolded,
@@ -852,30 +878,19 @@ int prepare_smile(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
             return fail(MCAMD_ERR_INVALID, "every strike must be finite and > 0: h_strikes[%u] = %g", k, h_strikes[k]);
     if (!std::isfinite(sm->q)) return fail(MCAMD_ERR_INVALID, "the dividend yield q must be finite, got %g", sm->q);
     if (!std::isfinite(opt->r)) return fail(MCAMD_ERR_INVALID, "option parameters must be finite with T > 0");
-    // as prepare_localvol: the shared checks on a copy that carries neither a volatility nor a strike of its own
+    // as prepare_localvol, on a copy that carries no strike of its own either
+    const double mu = opt->r - sm->q;
     mcamd_option seen = *opt;
-    seen.r = opt->r - sm->q;
     seen.K = 1.0;
-    seen.v = 1.0;
-    if (int rc = check_spot_start("local-volatility smile", false, &seen, sim)) return rc;
-    seen.v = 0.0;
-    if (int rc = check_request(&seen, sim)) return rc;
+    if (int rc = check_localvol_request("local-volatility smile", seen, sim, &mu, 1)) return rc;
     if (!(opt->S0 > 0.0)) return fail(MCAMD_ERR_INVALID, "local-volatility smile options need S0 > 0 (S0 = %g)", opt->S0);
     if (!surface)
         return fail(MCAMD_ERR_INVALID, "opt, sim, smile, h_expiry_steps, h_strikes and surface must be non-NULL");
     const double dt = opt->T / static_cast<double>(sim->n_steps);
-    if (sim->precision == MCAMD_F64) {
-        // check_request's bound with the largest drift and volatility any node can give, as mcamd_price_localvol takes it
-        const double top = surface->sigma_max;
-        const double per_step = (std::fabs(seen.r) + 0.5 * top * top) * dt + 8.6 * top * std::sqrt(dt);
-        if (!(per_step < 700.0) || !(per_step * static_cast<double>(sim->n_steps) < 20000.0))
-            return fail(MCAMD_ERR_INVALID,
-                        "fp64 path: |drift| + 8.6 vol = %.3g per step over %u steps exceeds the exponent range "
-                        "(per step < 700, per path < 20000)", per_step, sim->n_steps);
-    }
+    if (sim->precision == MCAMD_F64)
+        if (int rc = check_localvol_exponent_range(mu, surface->sigma_max, dt, sim->n_steps)) return rc;
     if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
-    if (surface->ctx != ctx || surface->ctx_id != ctx->id)
-        return fail(MCAMD_ERR_INVALID, "the surface was created on another context");
+    if (!surface_belongs(surface, ctx)) return fail(MCAMD_ERR_INVALID, "the surface was created on another context");
     mcamd::SmileJob job = {};
     job.seed = sim->seed;
     job.path_offset = sim->path_offset;
@@ -883,14 +898,10 @@ int prepare_smile(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
     job.n_steps = sim->n_steps;
     job.precision = sim->precision;
     job.S0 = opt->S0;
-    job.mu = opt->r - sm->q;
+    job.mu = mu;
     job.dt = dt;
     job.put = sm->payoff == MCAMD_PAYOFF_PUT;
-    job.n_t = surface->grid.n_t;
-    job.n_x = surface->grid.n_x;
-    job.x_min = surface->grid.x_min;
-    job.x_max = surface->grid.x_max;
-    job.d_table = sim->precision == MCAMD_F32 ? surface->d_tab32 : surface->d_tab64;
+    job.surface = job_surface(surface, sim->precision);
     job.n_expiries = sm->n_expiries;
     job.n_strikes = sm->n_strikes;
     std::copy(h_expiry_steps, h_expiry_steps + sm->n_expiries, job.expiry_steps);
@@ -1348,24 +1359,19 @@ int prepare_autocall_localvol(mcamd_ctx *ctx, const mcamd_option *opt, const mca
                                       ac->ki_monitoring, ac->ki_level))
         return rc;
     if (!std::isfinite(opt->r)) return fail(MCAMD_ERR_INVALID, "option parameters must be finite with T > 0");
-    // as prepare_localvol: the shared checks on a copy that carries no spot, strike or volatility of its own, with
-    // each asset's drift r - q_j alone in the fp64 exponent-range bound
+    // as prepare_localvol, asset by asset, on a copy that carries no spot, strike or barrier of its own either
+    double mu[MCAMD_BASKET_MAX_ASSETS];
+    for (int j = 0; j < d; ++j) mu[j] = opt->r - ac->q[j];
     mcamd_option seen = *opt;
     seen.S0 = 1.0;
     seen.K = seen.B = 0.0;
-    seen.v = 1.0;
-    if (int rc = check_spot_start("local-volatility autocallable", false, &seen, sim)) return rc;
-    seen.v = 0.0;
-    for (int j = 0; j < d; ++j) {
-        seen.r = opt->r - ac->q[j];
-        if (int rc = check_request(&seen, sim)) return rc;
-    }
+    if (int rc = check_localvol_request("local-volatility autocallable", seen, sim, mu, d)) return rc;
     // the surfaces
     if (!surfaces) return fail(MCAMD_ERR_INVALID, "opt, sim, autocall and surfaces must be non-NULL");
     for (int j = 0; j < d; ++j)
         if (!surfaces[j]) return fail(MCAMD_ERR_INVALID, "surfaces[%d] is NULL: every asset needs a surface", j);
     for (int j = 0; j < d; ++j)
-        if (surfaces[j]->ctx != ctx || (ctx && surfaces[j]->ctx_id != ctx->id))
+        if (!surface_belongs(surfaces[j], ctx))
             return fail(MCAMD_ERR_INVALID, "the surface of asset %d was created on another context", j);
     uint64_t nodes = 0;
     for (int j = 0; j < d; ++j) nodes += static_cast<uint64_t>(surfaces[j]->grid.n_t) * surfaces[j]->grid.n_x;
@@ -1374,17 +1380,9 @@ int prepare_autocall_localvol(mcamd_ctx *ctx, const mcamd_option *opt, const mca
                                        "(a surface passed for several assets counts once per asset)", d,
                     static_cast<unsigned long long>(nodes), MCAMD_LOCALVOL_MAX_NODES);
     const double dt = opt->T / static_cast<double>(sim->n_steps);
-    if (sim->precision == MCAMD_F64) {
-        // check_request's bound asset by asset, with the largest drift and volatility any node of its surface can give
-        for (int j = 0; j < d; ++j) {
-            const double top = surfaces[j]->sigma_max;
-            const double per_step = (std::fabs(opt->r - ac->q[j]) + 0.5 * top * top) * dt + 8.6 * top * std::sqrt(dt);
-            if (!(per_step < 700.0) || !(per_step * static_cast<double>(sim->n_steps) < 20000.0))
-                return fail(MCAMD_ERR_INVALID,
-                            "fp64 path: |drift| + 8.6 vol = %.3g per step over %u steps exceeds the exponent range "
-                            "(per step < 700, per path < 20000; asset %d)", per_step, sim->n_steps, j);
-        }
-    }
+    if (sim->precision == MCAMD_F64)
+        for (int j = 0; j < d; ++j)
+            if (int rc = check_localvol_exponent_range(mu[j], surfaces[j]->sigma_max, dt, sim->n_steps, j)) return rc;
     if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
     if (sim->n_paths_local == 0) return drive(empty_call());
     mcamd::AutocallLocalVolJob job{};
@@ -1396,13 +1394,9 @@ int prepare_autocall_localvol(mcamd_ctx *ctx, const mcamd_option *opt, const mca
     job.d = d;
     job.dt = dt;
     for (int j = 0; j < d; ++j) {
-        job.mu[j] = opt->r - ac->q[j];
+        job.mu[j] = mu[j];
         for (int k = 0; k <= j; ++k) job.chol[j * (j + 1) / 2 + k] = L[8 * j + k];
-        job.n_t[j] = surfaces[j]->grid.n_t;
-        job.n_x[j] = surfaces[j]->grid.n_x;
-        job.x_min[j] = surfaces[j]->grid.x_min;
-        job.x_max[j] = surfaces[j]->grid.x_max;
-        job.d_table[j] = sim->precision == MCAMD_F32 ? surfaces[j]->d_tab32 : surfaces[j]->d_tab64;
+        job.surface[j] = job_surface(surfaces[j], sim->precision);
     }
     job.observe_every = ac->observe_every;
     job.n_dates = M;

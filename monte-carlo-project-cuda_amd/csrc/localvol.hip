@@ -1,36 +1,27 @@
 // localvol.hip — European and single-barrier options under a local-volatility surface, for gfx950 (both path precisions).
 //
 // Definitions (include/mcamd.h, mcamd_price_localvol): X_i = ln(S_i / S0) in NATURAL-log units (the surface's axis);
-// step i looks its volatility up at X_i in row(i) = floor(i n_t / n) of the surface, s = fma(f, slope_k, sigma_k) with
-// u = clamp((X - x_min) / dx, 0, n_x - 1), k = min(floor u, n_x - 2), f = u - k, and moves
-// X += ((r - q) - s^2/2) dt + s sqrt(dt) z.  The barrier tests, distances, survival weight and samples are those of
-// barrier.hip with b = ln(B / S0) in natural units and the step's own s in the bridge factor, q_i = 2 d d' / (s^2 dt).
+// the lookup of the step's volatility s, the row carry and the move X += ((r - q) - s^2/2) dt + s sqrt(dt) z are
+// localvol_device.hpp's, which the smile and the autocallable kernels walk as well.  The barrier tests, distances,
+// survival weight and samples are those of barrier.hip with b = ln(B / S0) in natural units and the step's own s in
+// the bridge factor, q_i = 2 d d' / (s^2 dt).
 //
 // The table — n_t n_x (sigma_k, slope_k) pairs of the path precision — is copied from global memory into dynamic LDS
 // once per workgroup; a step then costs one ds_read_b64 (fp32) / ds_read_b128 (fp64) per lane at a wave-uniform row
 // base plus the lane's k, and FMAs.  The volatility differs per lane and per step, so the exponent cannot be pre-scaled
 // as Exponents<T> does: the loop takes plain normals (Normals<T>) and converts X to the exponential's unit once, at the
-// end of the path.  row(i) is carried, not divided out: row += n_t / n and a remainder counter that carries when it
-// passes n (both wave-uniform, scalar unit).
-#include "localvol.hpp"
-#include "path_consts.hpp"
+// end of the path.
+#include "localvol_device.hpp"
 
 namespace mcamd {
 
 template <typename T>
 struct LocalVolArgs {
-    T x_min, inv_dx;          // node 0 and 1 / dx
-    T u_max;                  // n_x - 1
-    uint32_t k_max;           // n_x - 2
-    uint32_t n_x, n_entries;  // n_entries = n_t n_x
-    uint32_t row_whole_nx;    // (n_t / n_steps) n_x: what the row base grows by at every step
-    uint32_t row_rem;         // n_t % n_steps
-    uint32_t row_thr;         // n_steps - row_rem: the remainder counter carries when it reaches this
-    const VolPair<T> *table;  // global memory
+    LvSurface<T> surf;
     T mu_dt, half_dt, sqrt_dt;
     T exp_scale;              // exponent units per natural-log unit (log2 e in fp32, 65536 / ln 2 in fp64)
     T b;                      // ln(B / S0)
-    T kq;                     // 2 / dt, in the unit lv_bridge_factor's exponential takes (fp32: times log2 e)
+    T kq;                     // 2 / dt, in the unit bridge_factor's exponential takes (fp32: times log2 e)
     T q_cut;                  // Q in the same unit
     T K, S0;
     int put;
@@ -42,49 +33,19 @@ struct LocalVolArgs {
     GridFinish fin;
 };
 
-// 1 - exp(-q), q >= 0 in the unit LocalVolArgs::kq leaves it in
-__device__ __forceinline__ float lv_bridge_factor(float q, const MathCtx<float> &)
-{
-    return 1.0f - __builtin_amdgcn_exp2f(-q);
-}
-__device__ __forceinline__ double lv_bridge_factor(double q, const MathCtx<double> &m)
-{
-    return 1.0 - f64::mul_exp(1.0, -q, m.t.exp_hi_tab, m.t.exp_lo_tab);
-}
-
-__device__ __forceinline__ float lv_min(float a, float b) { return __builtin_fminf(a, b); }
-__device__ __forceinline__ double lv_min(double a, double b) { return __builtin_fmin(a, b); }
-__device__ __forceinline__ float lv_max(float a, float b) { return __builtin_fmaxf(a, b); }
-__device__ __forceinline__ double lv_max(double a, double b) { return __builtin_fmax(a, b); }
-
-// the constants of the full-rate fp32 instructions of the step go to vector registers (mc_device.hpp vgpr_resident)
-__device__ __forceinline__ LocalVolArgs<float> lv_resident(LocalVolArgs<float> a)
-{
-    a.x_min = vgpr_resident(a.x_min);
-    a.inv_dx = vgpr_resident(a.inv_dx);
-    a.u_max = vgpr_resident(a.u_max);
-    a.mu_dt = vgpr_resident(a.mu_dt);
-    a.half_dt = vgpr_resident(a.half_dt);
-    a.sqrt_dt = vgpr_resident(a.sqrt_dt);
-    return a;
-}
-__device__ __forceinline__ const LocalVolArgs<double> &lv_resident(const LocalVolArgs<double> &a) { return a; }
-
-extern __shared__ __attribute__((aligned(16))) unsigned char lv_table_lds[];
-
 // BAR: 0 no barrier, 1 down, 2 up.  CONT and OUT are read with a barrier only.
 template <typename T, int BAR, bool CONT, bool OUT>
-__global__ __launch_bounds__(kBlock) void localvol_kernel(LocalVolArgs<T> args, double *__restrict__ partials)
+__global__ __launch_bounds__(kBlock) void localvol_kernel(LocalVolArgs<T> a, double *__restrict__ partials)
 {
     constexpr int NB = Normals<T>::kPerBlock;
     constexpr bool UP = BAR == 2;
-    // every thread of the workgroup copies its share of the table; one barrier, then the table is read-only
     VolPair<T> *tab = reinterpret_cast<VolPair<T> *>(lv_table_lds);
-    for (uint32_t e = threadIdx.x; e < args.n_entries; e += kBlock) tab[e] = args.table[e];
+    lv_copy_table(tab, 0, a.surf.table, a.surf.rows.n_entries);
     __syncthreads();
     const MathCtx<T> m = MathCtx<T>::init();
-    const PhiloxKeys key = PhiloxKeys::make(args.seed);
-    const LocalVolArgs<T> a = lv_resident(args);
+    const PhiloxKeys key = PhiloxKeys::make(a.seed);
+    const LvAxis<T> axis = lv_resident(a.surf.axis);
+    const T mu_dt = lv_resident(a.mu_dt), half_dt = lv_resident(a.half_dt), sqrt_dt = lv_resident(a.sqrt_dt);
     const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
     const uint32_t n_full = a.n_steps / NB;
     const uint32_t rem = a.n_steps - n_full * NB;
@@ -99,28 +60,12 @@ __global__ __launch_bounds__(kBlock) void localvol_kernel(LocalVolArgs<T> args, 
         uint32_t live = 0;   // steps this path entered not yet knocked
         uint32_t steps_run = a.n_steps;
         bool rem_live = true;
-        uint32_t row_base = 0;    // row(i) n_x, wave-uniform
-        uint32_t row_phase = 0;   // (i row_rem) mod n_steps, wave-uniform
+        LvRow row{0, 0};
         Normals<T> nz;
         auto step = [&](T z) {
             live += alive ? 1u : 0u;
-            T u = (X - a.x_min) * a.inv_dx;
-            u = lv_min(lv_max(u, T(0)), a.u_max);   // a NaN lands on node 0: the index stays inside the table
-            uint32_t k = static_cast<uint32_t>(u);
-            k = k < a.k_max ? k : a.k_max;
-            const T f = u - static_cast<T>(k);
-            const VolPair<T> p = tab[row_base + k];
-            const T s = fma_t(f, p.slope, p.sigma);
-            // row(i + 1)
-            row_base += a.row_whole_nx;
-            if (row_phase >= a.row_thr) {
-                row_phase -= a.row_thr;
-                row_base += a.n_x;
-            } else {
-                row_phase += a.row_rem;
-            }
-            const T s2 = s * s;
-            X += fma_t(s * a.sqrt_dt, z, fma_t(-s2, a.half_dt, a.mu_dt));
+            const T s = lv_sigma(X, axis, a.surf.rows, tab, row);
+            const T s2 = lv_move(X, s, z, sqrt_dt, half_dt, mu_dt);
             if (BAR != 0) {
                 const T d = UP ? a.b - X : X - a.b;
                 const bool hit = UP ? (X > a.b) : (a.b > X);
@@ -129,7 +74,7 @@ __global__ __launch_bounds__(kBlock) void localvol_kernel(LocalVolArgs<T> args, 
                     const T num = a.kq * d_prev * d;   // q s^2
                     const bool close_by = alive && (num < a.q_cut * s2);
                     if (__builtin_amdgcn_ballot_w64(close_by) != 0) {   // wave-uniform: most steps take no exponential
-                        const T fac = lv_bridge_factor(num / s2, m);
+                        const T fac = bridge_factor(num / s2, m);
                         w = close_by ? w * fac : w;
                     }
                     d_prev = d;
@@ -178,7 +123,7 @@ __global__ __launch_bounds__(kBlock) void localvol_kernel(LocalVolArgs<T> args, 
 template <typename T, int BAR, bool CONT, bool OUT>
 static void launch_localvol_k(const LocalVolArgs<T> &a, double *d_partials, uint32_t grid, hipStream_t stream)
 {
-    const size_t lds_bytes = static_cast<size_t>(a.n_entries) * sizeof(VolPair<T>);
+    const size_t lds_bytes = static_cast<size_t>(a.surf.rows.n_entries) * sizeof(VolPair<T>);
     hipLaunchKernelGGL((localvol_kernel<T, BAR, CONT, OUT>), dim3(grid), dim3(kBlock), lds_bytes, stream, a, d_partials);
 }
 
@@ -202,22 +147,12 @@ static hipError_t launch_localvol_t(const LocalVolJob &j, double *d_partials, ui
     // natural log per unit of q: the fp32 bridge factor is 1 - 2^-q
     const double q_unit = sizeof(T) == 4 ? kLn2 : 1.0;
     const double q_cut = sizeof(T) == 4 ? 18.0 : 38.0;
-    const double dx = (j.x_max - j.x_min) / static_cast<double>(j.n_x - 1);
     LocalVolArgs<T> a;
-    a.x_min = static_cast<T>(j.x_min);
-    a.inv_dx = static_cast<T>(1.0 / dx);
-    a.u_max = static_cast<T>(j.n_x - 1);
-    a.k_max = j.n_x - 2;
-    a.n_x = j.n_x;
-    a.n_entries = j.n_t * j.n_x;
-    a.row_whole_nx = (j.n_t / j.n_steps) * j.n_x;
-    a.row_rem = j.n_t % j.n_steps;
-    a.row_thr = j.n_steps - a.row_rem;
-    a.table = static_cast<const VolPair<T> *>(j.d_table);
+    a.surf = lv_surface<T>(j.surface, j.n_steps);
     a.mu_dt = static_cast<T>(j.mu * j.dt);
     a.half_dt = static_cast<T>(0.5 * j.dt);
     a.sqrt_dt = static_cast<T>(std::sqrt(j.dt));
-    a.exp_scale = static_cast<T>(sizeof(T) == 4 ? 1.4426950408889634 : f64::kExpScale);   // make_consts' literals
+    a.exp_scale = lv_exp_scale<T>();
     a.b = j.barrier ? static_cast<T>(std::log(j.B / j.S0)) : T(0);
     a.kq = static_cast<T>(2.0 / (j.dt * q_unit));
     a.q_cut = static_cast<T>(q_cut / q_unit);
@@ -240,9 +175,7 @@ hipError_t launch_localvol(const LocalVolJob &job, double *d_partials, uint32_t 
                            hipStream_t stream)
 {
     if (!finish_ok(finish, grid)) return hipErrorInvalidValue;
-    if (!job.d_table || job.n_steps == 0 || job.n_x < 2 || job.n_t < 1 ||
-        static_cast<uint64_t>(job.n_t) * job.n_x > kLocalVolMaxNodes)
-        return hipErrorInvalidValue;
+    if (!lv_grid_ok(job.surface, job.n_steps)) return hipErrorInvalidValue;
     return job.precision == 32 ? launch_localvol_t<float>(job, d_partials, grid, finish, stream)
                                : launch_localvol_t<double>(job, d_partials, grid, finish, stream);
 }

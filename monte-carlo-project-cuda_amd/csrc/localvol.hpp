@@ -21,6 +21,13 @@ struct alignas(2 * sizeof(T)) VolPair {
     T slope;   // sigma_{k+1} - sigma_k (0 at a row's last node, which is never read)
 };
 
+// A surface as a job carries it: the grid and the pair table of the job's path precision.
+struct LocalVolGrid {
+    uint32_t n_t, n_x;
+    double x_min, x_max;
+    const void *d_table;   // n_t n_x VolPair of the path precision, device memory, 16-byte aligned
+};
+
 struct LocalVolJob {
     uint64_t seed, path_offset, n_local;
     uint32_t n_steps;
@@ -33,9 +40,7 @@ struct LocalVolJob {
     bool out;            // knock-out (else knock-in)
     bool continuous;     // Brownian-bridge survival factors with the step's frozen volatility
     bool put;            // h(S) = (K - S)+ (else (S - K)+)
-    uint32_t n_t, n_x;
-    double x_min, x_max;
-    const void *d_table; // n_t n_x VolPair of the path precision, device memory, 16-byte aligned
+    LocalVolGrid surface;
     void *d_samples;     // nullable: n_local samples of the path precision
 };
 

@@ -2,9 +2,9 @@
 // precisions).
 //
 // Definitions (include/mcamd.h, mcamd_price_localvol_smile): the paths are mcamd_price_localvol's without a barrier —
-// the walk below restates localvol.hip's step in the same operation order, with the same table in dynamic LDS, the
-// same carried row and the same Philox subsequence — stopped at the expiry steps s_0 < s_1 < ...; the spot of expiry m
-// is S_m = exp_of_logreturn(S0, X_{s_m} exp_scale), as localvol.hip forms S_T.
+// the same step (localvol_device.hpp: the table in dynamic LDS, the lookup, the carried row, the move) on the same
+// Philox subsequence — stopped at the expiry steps s_0 < s_1 < ...; the spot of expiry m is
+// S_m = exp_of_logreturn(S0, X_{s_m} exp_scale), as localvol.hip forms S_T.
 //
 // Walk phase: one path per lane.  The next expiry step is wave-uniform and lives in a scalar register; a Philox block
 // that holds no expiry runs the plain unrolled steps, one that holds an expiry (or the end) tests every step.
@@ -17,20 +17,13 @@
 // any path writes zeros, so every entry of every record is written whatever the buffer held.
 // Finish: smile_finish_kernel, one thread per node, sums the entries over the wavefronts in index order.
 #include "localvol_smile.hpp"
-#include "path_consts.hpp"
+#include "localvol_device.hpp"
 
 namespace mcamd {
 
 template <typename T>
 struct SmileArgs {
-    T x_min, inv_dx;          // node 0 and 1 / dx
-    T u_max;                  // n_x - 1
-    uint32_t k_max;           // n_x - 2
-    uint32_t n_x, n_entries;  // n_entries = n_t n_x
-    uint32_t row_whole_nx;    // (n_t / n_steps) n_x: what the row base grows by at every step
-    uint32_t row_rem;         // n_t % n_steps
-    uint32_t row_thr;         // n_steps - row_rem: the remainder counter carries when it reaches this
-    const VolPair<T> *table;  // global memory
+    LvSurface<T> surf;
     T mu_dt, half_dt, sqrt_dt;
     T exp_scale;              // exponent units per natural-log unit (log2 e in fp32, 65536 / ln 2 in fp64)
     T S0;
@@ -44,27 +37,6 @@ struct SmileArgs {
     uint32_t expiry_steps[kSmileMaxExpiries];
     T strikes[kSmileMaxStrikes];
 };
-
-// what a step reads, with the constants of the full-rate fp32 instructions in vector registers (mc_device.hpp
-// vgpr_resident)
-template <typename T>
-struct SmileStep {
-    T x_min, inv_dx, u_max, mu_dt, half_dt, sqrt_dt;
-};
-__device__ __forceinline__ SmileStep<float> sm_resident(const SmileArgs<float> &a)
-{
-    return {vgpr_resident(a.x_min), vgpr_resident(a.inv_dx), vgpr_resident(a.u_max),
-            vgpr_resident(a.mu_dt), vgpr_resident(a.half_dt), vgpr_resident(a.sqrt_dt)};
-}
-__device__ __forceinline__ SmileStep<double> sm_resident(const SmileArgs<double> &a)
-{
-    return {a.x_min, a.inv_dx, a.u_max, a.mu_dt, a.half_dt, a.sqrt_dt};
-}
-
-__device__ __forceinline__ float sm_min(float a, float b) { return __builtin_fminf(a, b); }
-__device__ __forceinline__ double sm_min(double a, double b) { return __builtin_fmin(a, b); }
-__device__ __forceinline__ float sm_max(float a, float b) { return __builtin_fmaxf(a, b); }
-__device__ __forceinline__ double sm_max(double a, double b) { return __builtin_fmax(a, b); }
 
 // lane j's value, j wave-uniform: v_readlane_b32 into scalar registers (a pair for fp64)
 __device__ __forceinline__ float sm_broadcast(float v, uint32_t j)
@@ -83,19 +55,17 @@ struct alignas(16) SmileEntry {
     double sum, sumsq;
 };
 
-extern __shared__ __attribute__((aligned(16))) unsigned char sm_table_lds[];
-
 template <typename T>
 __global__ __launch_bounds__(kBlock) void smile_kernel(SmileArgs<T> args, double *__restrict__ partials)
 {
     constexpr int NB = Normals<T>::kPerBlock;
-    // every thread of the workgroup copies its share of the table; one barrier, then the table is read-only
-    VolPair<T> *tab = reinterpret_cast<VolPair<T> *>(sm_table_lds);
-    for (uint32_t e = threadIdx.x; e < args.n_entries; e += kBlock) tab[e] = args.table[e];
+    VolPair<T> *tab = reinterpret_cast<VolPair<T> *>(lv_table_lds);
+    lv_copy_table(tab, 0, args.surf.table, args.surf.rows.n_entries);
     __syncthreads();
     const MathCtx<T> m = MathCtx<T>::init();
     const PhiloxKeys key = PhiloxKeys::make(args.seed);
-    const SmileStep<T> a = sm_resident(args);
+    const LvAxis<T> axis = lv_resident(args.surf.axis);
+    const T mu_dt = lv_resident(args.mu_dt), half_dt = lv_resident(args.half_dt), sqrt_dt = lv_resident(args.sqrt_dt);
     const uint32_t lane = threadIdx.x & (kWave - 1);
     const uint32_t wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     const uint32_t wave = blockIdx.x * (kBlock / kWave) + wave_in_block;
@@ -127,29 +97,13 @@ __global__ __launch_bounds__(kBlock) void smile_kernel(SmileArgs<T> args, double
         // lanes past the end walk a path nobody reads: the strike phase needs the whole wavefront
         const uint64_t subsequence = args.path_offset + i;
         T X = T(0);               // ln(S / S0), natural units
-        uint32_t row_base = 0;    // row(i) n_x, wave-uniform
-        uint32_t row_phase = 0;   // (i row_rem) mod n_steps, wave-uniform
+        LvRow row{0, 0};
         uint32_t mi = 0;          // the next expiry, wave-uniform
         uint32_t next = args.expiry_steps[0];
         Normals<T> nz;
         auto step = [&](T z) {
-            T u = (X - a.x_min) * a.inv_dx;
-            u = sm_min(sm_max(u, T(0)), a.u_max);   // a NaN lands on node 0: the index stays inside the table
-            uint32_t k = static_cast<uint32_t>(u);
-            k = k < args.k_max ? k : args.k_max;
-            const T f = u - static_cast<T>(k);
-            const VolPair<T> p = tab[row_base + k];
-            const T s = fma_t(f, p.slope, p.sigma);
-            // row(i + 1)
-            row_base += args.row_whole_nx;
-            if (row_phase >= args.row_thr) {
-                row_phase -= args.row_thr;
-                row_base += args.n_x;
-            } else {
-                row_phase += args.row_rem;
-            }
-            const T s2 = s * s;
-            X += fma_t(s * a.sqrt_dt, z, fma_t(-s2, a.half_dt, a.mu_dt));
+            const T s = lv_sigma(X, axis, args.surf.rows, tab, row);
+            lv_move(X, s, z, sqrt_dt, half_dt, mu_dt);
         };
         auto expiry = [&]() {
             const T S = exp_of_logreturn(args.S0, X * args.exp_scale, m);
@@ -212,22 +166,12 @@ __global__ __launch_bounds__(kBlock) void smile_finish_kernel(const SmileEntry *
 template <typename T>
 static hipError_t launch_smile_t(const SmileJob &j, double *d_partials, uint32_t grid, hipStream_t stream)
 {
-    const double dx = (j.x_max - j.x_min) / static_cast<double>(j.n_x - 1);
     SmileArgs<T> a;
-    a.x_min = static_cast<T>(j.x_min);
-    a.inv_dx = static_cast<T>(1.0 / dx);
-    a.u_max = static_cast<T>(j.n_x - 1);
-    a.k_max = j.n_x - 2;
-    a.n_x = j.n_x;
-    a.n_entries = j.n_t * j.n_x;
-    a.row_whole_nx = (j.n_t / j.n_steps) * j.n_x;
-    a.row_rem = j.n_t % j.n_steps;
-    a.row_thr = j.n_steps - a.row_rem;
-    a.table = static_cast<const VolPair<T> *>(j.d_table);
+    a.surf = lv_surface<T>(j.surface, j.n_steps);
     a.mu_dt = static_cast<T>(j.mu * j.dt);
     a.half_dt = static_cast<T>(0.5 * j.dt);
     a.sqrt_dt = static_cast<T>(std::sqrt(j.dt));
-    a.exp_scale = static_cast<T>(sizeof(T) == 4 ? 1.4426950408889634 : f64::kExpScale);   // make_consts' literals
+    a.exp_scale = lv_exp_scale<T>();
     a.S0 = static_cast<T>(j.S0);
     a.put = j.put ? 1 : 0;
     a.n_expiries = j.n_expiries;
@@ -239,7 +183,7 @@ static hipError_t launch_smile_t(const SmileJob &j, double *d_partials, uint32_t
     a.spots = static_cast<T *>(j.d_spots);
     for (uint32_t m = 0; m < kSmileMaxExpiries; ++m) a.expiry_steps[m] = m < j.n_expiries ? j.expiry_steps[m] : 0xFFFFFFFFu;
     for (uint32_t k = 0; k < kSmileMaxStrikes; ++k) a.strikes[k] = k < j.n_strikes ? static_cast<T>(j.strikes[k]) : T(0);
-    const size_t lds_bytes = static_cast<size_t>(a.n_entries) * sizeof(VolPair<T>);
+    const size_t lds_bytes = static_cast<size_t>(a.surf.rows.n_entries) * sizeof(VolPair<T>);
     hipLaunchKernelGGL((smile_kernel<T>), dim3(grid), dim3(kBlock), lds_bytes, stream, a, d_partials);
     return hipGetLastError();
 }
@@ -247,9 +191,7 @@ static hipError_t launch_smile_t(const SmileJob &j, double *d_partials, uint32_t
 hipError_t launch_localvol_smile(const SmileJob &job, double *d_partials, uint32_t grid, hipStream_t stream)
 {
     if (!d_partials || grid == 0 || grid > kFoldMaxRecords) return hipErrorInvalidValue;
-    if (!job.d_table || job.n_steps == 0 || job.n_x < 2 || job.n_t < 1 ||
-        static_cast<uint64_t>(job.n_t) * job.n_x > kLocalVolMaxNodes)
-        return hipErrorInvalidValue;
+    if (!lv_grid_ok(job.surface, job.n_steps)) return hipErrorInvalidValue;
     if (job.n_expiries < 1 || job.n_expiries > kSmileMaxExpiries || job.n_strikes < 1 || job.n_strikes > kSmileMaxStrikes)
         return hipErrorInvalidValue;
     for (uint32_t m = 0; m < job.n_expiries; ++m) {

@@ -1,6 +1,6 @@
 // localvol_smile.hpp — host-side interface of the smile kernels (localvol_smile.hip) for the C ABI (capi.cpp).
 //
-// A smile kernel walks mcamd_price_localvol's paths without a barrier (localvol.hip's walk, restated), stops at up to 32
+// A smile kernel walks mcamd_price_localvol's paths without a barrier (the walk of localvol_device.hpp), stops at up to 32
 // expiry steps and there turns the work a quarter-turn: every lane of a wavefront takes one strike and runs over the
 // wavefront's 64 spots, so a path set serves n_e x n_K vanillas (include/mcamd.h, mcamd_price_localvol_smile).  Every
 // wavefront owns a private record [m][k] of (sum h, sum h^2) pairs in global memory; a second kernel sums the records in
@@ -25,9 +25,7 @@ struct SmileJob {
     double mu;           // r - q
     double dt;           // T / n_steps
     bool put;            // h(S) = (K - S)+ at every node (else (S - K)+)
-    uint32_t n_t, n_x;
-    double x_min, x_max;
-    const void *d_table; // as LocalVolJob::d_table
+    LocalVolGrid surface;
     uint32_t n_expiries, n_strikes;
     uint32_t expiry_steps[kSmileMaxExpiries];   // strictly ascending, 1 .. n_steps
     double strikes[kSmileMaxStrikes];

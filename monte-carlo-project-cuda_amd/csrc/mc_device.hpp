@@ -636,6 +636,17 @@ __device__ __forceinline__ double exp_of_logreturn(double S, double y, const Mat
     return ps.value(m);
 }
 
+// The Brownian-bridge survival factor 1 - exp(-q) of the continuously monitored barrier kernels (barrier.hip,
+// localvol.hip), q >= 0 in the unit the kernel's kq leaves it in: log2 units in fp32, natural-log units in fp64.
+__device__ __forceinline__ float bridge_factor(float q, const MathCtx<float> &)
+{
+    return 1.0f - __builtin_amdgcn_exp2f(-q);
+}
+__device__ __forceinline__ double bridge_factor(double q, const MathCtx<double> &m)
+{
+    return 1.0 - f64::mul_exp(1.0, -q, m.t.exp_hi_tab, m.t.exp_lo_tab);
+}
+
 // Simulates n_sim steps of one path in registers from (St, count) on the Philox stream
 // (seed, subsequence) and returns its undiscounted payoff.  Step loop of
 // inc/trajectories.cuh:144-148 (and the inner loops inc/nmc.cuh:55-59, :335-339).

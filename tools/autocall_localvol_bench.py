@@ -31,6 +31,7 @@ def main():
     ap.add_argument("--observe-every", type=int, default=63)
     ap.add_argument("--assets", type=int, default=3, help="1..8; beyond 3, q_j repeats and v_j keeps growing")
     ap.add_argument("--skew-nx", type=int, default=65, help="nodes per slice of the skewed surfaces (4 slices each)")
+    ap.add_argument("--ki", choices=("every-step", "maturity"), default="every-step", help="the knock-in's monitoring")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -38,7 +39,8 @@ def main():
     stream = torch.cuda.Stream()
     torch.cuda.set_stream(stream)
     ctx = capi.Context(0, stream.cuda_stream)
-    r, T, d, ki_level, ki = 0.05, 5.0, args.assets, 0.6, capi.AUTOCALL_KI_EVERY_STEP
+    r, T, d, ki_level = 0.05, 5.0, args.assets, 0.6
+    ki = capi.AUTOCALL_KI_EVERY_STEP if args.ki == "every-step" else capi.AUTOCALL_KI_AT_MATURITY
     med = lambda xs: sorted(xs)[len(xs) // 2]
     v = [0.15 + 0.05 * j for j in range(d)]
     q = [(0.0, 0.03, 0.01)[j % 3] for j in range(d)]
@@ -52,7 +54,7 @@ def main():
             for j in range(d)]
 
     out = {"tool": "autocall_localvol_bench", "device": ctx.device_info().name.decode(), "paths": args.paths,
-           "steps": args.steps, "observe_every": args.observe_every, "assets": d, "reps": args.reps, "r": r, "T": T,
+           "steps": args.steps, "observe_every": args.observe_every, "assets": d, "ki": args.ki, "reps": args.reps, "r": r, "T": T,
            "skewed_grid": [n_t, n_x, x_min, x_max], "q_skewed": q, "jobs": []}
     for prec in (capi.F64, capi.F32):
         sim = capi.make_sim(args.paths, args.steps, prec, seed=1234)

@@ -1,0 +1,74 @@
+#!/usr/bin/env python3
+"""Compares the gfx950 machine code of two source trees kernel by kernel, without a GPU: for every kernel symbol of the
+given kernel files the multiset of vector, LDS and memory opcodes (v_*, ds_*, global_*, flat_*, buffer_*) and the
+compiler's resource figures (VGPRs, AGPRs, spilled registers, LDS and scratch bytes) must agree; scalar-instruction
+order and the SGPR count may differ, and the SGPR counts are reported.
+    python3 tools/isa_diff.py OTHER_TREE [FILE.hip ...]          # OTHER_TREE: a checkout of the commit to compare with
+Exit status 1 when a kernel differs."""
+import collections, importlib.util, os, re, subprocess, sys, tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = "monte-carlo-project-cuda_amd"
+DEFAULT = ["localvol.hip", "localvol_smile.hip", "autocall_localvol.hip", "autocall_localvol_f32.hip", "barrier.hip"]
+OPCODE = re.compile(r"^\s+((?:v|ds|global|flat|buffer)_[a-z0-9_]+)\b")
+FIGURES = {"vgpr": ".vgpr_count", "agpr": ".agpr_count", "vgpr_spill": ".vgpr_spill_count",
+           "sgpr_spill": ".sgpr_spill_count", "lds": ".group_segment_fixed_size", "scratch": ".private_segment_fixed_size",
+           "sgpr": ".sgpr_count"}
+
+
+def kernels_of(tree, src):
+    """{kernel symbol: (opcode multiset, figures)} of one kernel file of one tree, compiled with that tree's flags"""
+    spec = importlib.util.spec_from_file_location("build_" + str(abs(hash(tree))), os.path.join(tree, PKG, "build.py"))
+    build = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(build)
+    with tempfile.TemporaryDirectory() as td:
+        out = os.path.join(td, "k.s")
+        subprocess.check_call([build.hipcc(), *build._flags(), "-S", "--cuda-device-only", os.path.join(build.CSRC, src),
+                               "-o", out], stderr=subprocess.DEVNULL)
+        with open(out) as f:
+            asm = f.read()
+    ops, cur = {}, None
+    for line in asm.splitlines():
+        m = re.match(r"^(_Z\w+):", line)
+        if m:
+            cur = ops.setdefault(m.group(1), collections.Counter())
+        elif line.startswith("\t.end_amdhsa_kernel") or line.startswith(".Lfunc_end"):
+            cur = None
+        elif cur is not None:
+            m = OPCODE.match(line)
+            if m:
+                cur[m.group(1)] += 1
+    figures = {}
+    for block in asm.split("  - .agpr_count:")[1:]:
+        block = "    .agpr_count:" + block
+        name = re.search(r"^    \.name:\s+(\S+)", block, re.M).group(1)   # the kernel's, not an argument's
+        figures[name] = {k: int(re.search(r"^\s+" + re.escape(v) + r":\s+(\d+)", block, re.M).group(1))
+                         for k, v in FIGURES.items()}
+    return {k: (ops[k], figures[k]) for k in figures}
+
+
+def main():
+    other = os.path.abspath(sys.argv[1])
+    bad = 0
+    for src in sys.argv[2:] or DEFAULT:
+        a, b = kernels_of(other, src), kernels_of(ROOT, src)
+        differ = [k for k in sorted(set(a) | set(b)) if k not in a or k not in b or a[k][0] != b[k][0] or
+                  any(a[k][1][f] != b[k][1][f] for f in FIGURES if f != "sgpr")]
+        sg = sorted(set(a) & set(b))
+        moved = [(a[k][1]["sgpr"], b[k][1]["sgpr"]) for k in sg if a[k][1]["sgpr"] != b[k][1]["sgpr"]]
+        print(f"{src}: {len(b)} kernels, {sum(sum(v[0].values()) for v in b.values())} counted instructions, "
+              f"{len(differ)} differ; SGPRs {min(b[k][1]['sgpr'] for k in sg)}..{max(b[k][1]['sgpr'] for k in sg)}, "
+              f"changed in {len(moved)} kernels {sorted(set(moved))}")
+        for k in differ:
+            bad += 1
+            if k in a and k in b:
+                d = {op: (a[k][0][op], b[k][0][op]) for op in set(a[k][0]) | set(b[k][0]) if a[k][0][op] != b[k][0][op]}
+                f = {f: (a[k][1][f], b[k][1][f]) for f in FIGURES if a[k][1][f] != b[k][1][f]}
+                print(f"  DIFFERS {k}: opcodes (other, this) {d}; figures {f}")
+            else:
+                print(f"  DIFFERS {k}: only in {'the other tree' if k in a else 'this tree'}")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -25,6 +25,8 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--paths", type=int, default=10_000_000)
     ap.add_argument("--steps", type=int, default=252)
+    ap.add_argument("--monitoring", choices=("discrete", "continuous"), default="discrete",
+                    help="of the three DOWN_OUT jobs (continuous: the kernels with the bridge factor)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -39,11 +41,12 @@ def main():
     full = ctx.localvol_surface((16, 128, -1.5, 1.5),
                                 [[(0.15 + 0.01 * j) * (1.0 + 0.5 * math.exp(-x)) / 1.5 for x in xs] for j in range(16)])
     plain = capi.make_localvol(capi.PAYOFF_CALL)
-    knock = capi.make_localvol(capi.PAYOFF_CALL, capi.BARRIER_DOWN_OUT, capi.MONITOR_DISCRETE)
-    bar = capi.make_barrier(capi.BARRIER_DOWN_OUT, capi.PAYOFF_CALL, capi.MONITOR_DISCRETE)
+    mon = capi.MONITOR_CONTINUOUS if args.monitoring == "continuous" else capi.MONITOR_DISCRETE
+    knock = capi.make_localvol(capi.PAYOFF_CALL, capi.BARRIER_DOWN_OUT, mon)
+    bar = capi.make_barrier(capi.BARRIER_DOWN_OUT, capi.PAYOFF_CALL, mon)
     med = lambda xs_: sorted(xs_)[len(xs_) // 2]
     out = {"tool": "localvol_bench", "device": ctx.device_info().name.decode(), "n_paths": args.paths,
-           "n_steps": args.steps, "reps": args.reps, **base, "q": 0.0, "jobs": []}
+           "n_steps": args.steps, "reps": args.reps, "monitoring": args.monitoring, **base, "q": 0.0, "jobs": []}
     for prec in (capi.F64, capi.F32):
         sim = capi.make_sim(args.paths, args.steps, prec, seed=1234)
         calls = {

@@ -1,0 +1,135 @@
+#!/usr/bin/env python3
+"""Do two builds of the library compute the same bits?  One fresh worker process per library (MCAMD_LIB) runs a fixed
+list of small jobs on the kernels that walk a local-volatility surface — mcamd_price_localvol, mcamd_price_localvol_smile,
+mcamd_price_autocall_localvol — and on mcamd_price_barrier's continuous monitoring, and prints a SHA-256 per job over
+the per-path outputs (samples or spots) and the result record without its two timings; this process compares the lines.
+    python3 tools/same_bits.py LIB_A LIB_B          # on an MI355X; exit status 1 on any difference
+Every job is 1000 paths (four workgroups, a partial last wavefront) of a 2^40-path job, from path 5003 and from path
+2^33 + 5003, in both precisions.  Step counts 1, 2, 3, 5, 7 and 13 leave every remainder of a Philox block of 2 and of
+4 normals; the surfaces are a flat 1 x 2, a skewed 3 x 5 (n_t divides no step count but 3), a 16 x 5 (more rows than
+steps), the full 16 x 128 table and an axis so narrow that the paths clamp on both sides."""
+import hashlib, importlib, json, math, os, struct, subprocess, sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+N, OFFSETS, STEPS = 1000, (5003, 2 ** 33 + 5003), (1, 2, 3, 5, 7, 13)
+TIMINGS = ("kernel_ms", "total_ms")
+
+
+def surfaces(ctx):
+    def skew(n_t, n_x, lo, hi, v=0.2):
+        xs = [lo + k * (hi - lo) / (n_x - 1) for k in range(n_x)]
+        return ctx.localvol_surface((n_t, n_x, lo, hi),
+                                    [[v * (0.9 + 0.05 * t) * (1.0 + 0.5 * math.exp(-x)) / 1.5 for x in xs] for t in range(n_t)])
+    return {"flat": ctx.localvol_surface((1, 2, -1.5, 1.5), [[0.2, 0.2]]), "skew3x5": skew(3, 5, -1.0, 1.0),
+            "rows16x5": skew(16, 5, -1.0, 1.0, 0.3), "full16x128": skew(16, 128, -1.5, 1.5),
+            "narrow": skew(2, 4, -0.01, 0.01, 0.4)}
+
+
+def worker():
+    sys.path.insert(0, ROOT)
+    import torch
+    capi = importlib.import_module("monte-carlo-project-cuda_amd").capi
+    stream = torch.cuda.Stream()
+    torch.cuda.set_stream(stream)
+    ctx = capi.Context(0, stream.cuda_stream)
+    surf = surfaces(ctx)
+    dtype = {capi.F32: torch.float32, capi.F64: torch.float64}
+
+    def emit(name, res, *arrays):
+        h = hashlib.sha256()
+        for a in arrays:
+            h.update(a.cpu().numpy().tobytes() if hasattr(a, "cpu") else a.tobytes())
+        for key, value in res.as_dict().items():
+            if key not in TIMINGS:
+                h.update(struct.pack("<d", float(value)))
+        print(json.dumps({"job": name, "sha256": h.hexdigest()}))
+
+    def sim(n_steps, prec, off, n=N):
+        return capi.make_sim(2 ** 40, n_steps, prec, seed=77, path_offset=off, n_paths_local=n)
+
+    for prec in (capi.F32, capi.F64):
+        for off in OFFSETS:
+            tag = f"f{prec} @{off}"
+            out = torch.empty(N, dtype=dtype[prec], device="cuda")
+            # mcamd_price_localvol: no barrier, and every kind x monitoring x payoff, on every surface and step count
+            kinds = [(capi.LOCALVOL_NO_BARRIER, capi.MONITOR_DISCRETE, capi.PAYOFF_CALL)] + [
+                (kind, mon, pay) for kind in range(4) for mon in (capi.MONITOR_DISCRETE, capi.MONITOR_CONTINUOUS)
+                for pay in (capi.PAYOFF_CALL, capi.PAYOFF_PUT)]
+            for sname, s in surf.items():
+                for n_steps in STEPS:
+                    for kind, mon, pay in kinds:
+                        up = kind in (capi.BARRIER_UP_OUT, capi.BARRIER_UP_IN)
+                        opt = capi.make_option(S0=100.0, K=100.0, B=110.0 if up else 90.0, r=0.05, v=0.0, T=1.0)
+                        res = ctx.price_localvol(opt, sim(n_steps, prec, off), capi.make_localvol(pay, kind, mon, q=0.02), s,
+                                                 out.zero_())
+                        emit(f"localvol {tag} {sname} n={n_steps} kind={kind} mon={mon} pay={pay}", res, out)
+            # mcamd_price_localvol_smile: expiries on different slots of a Philox block and in the remainder block
+            opt = capi.make_option(S0=100.0, K=0.0, r=0.05, v=0.0, T=1.0)
+            for sname in ("skew3x5", "full16x128", "narrow"):
+                for n_K in (1, 64):
+                    strikes = [60.0 + 80.0 * k / max(n_K - 1, 1) for k in range(n_K)]
+                    spots = torch.zeros(3 * N, dtype=dtype[prec], device="cuda")
+                    _, _, stats, res = ctx.price_localvol_smile(opt, sim(13, prec, off), capi.make_smile(3, n_K, q=0.02),
+                                                                (5, 6, 13), strikes, surf[sname], spots)
+                    emit(f"smile {tag} {sname} n_K={n_K}", res, spots, stats)
+            # two trips: 32 x 64 nodes cap the grid at 512 workgroups, so 150 000 paths make wavefronts add to their record
+            n2, strikes = 150_000, [60.0 + 80.0 * k / 63 for k in range(64)]
+            spots = torch.zeros(32 * n2, dtype=dtype[prec], device="cuda")
+            _, _, stats, res = ctx.price_localvol_smile(opt, sim(32, prec, off, n2), capi.make_smile(32, 64, capi.PAYOFF_PUT),
+                                                        range(1, 33), strikes, surf["skew3x5"], spots)
+            emit(f"smile {tag} two trips grid={res.grid}", res, spots, stats)
+            # mcamd_price_autocall_localvol: every width and knock-in mode, a surface per asset, and one shared by three
+            opt = capi.make_option(S0=0.0, K=0.0, r=0.03, v=0.0, T=3.0)
+            cycle = ["skew3x5", "flat", "rows16x5", "narrow"]
+            notes = [(d, [cycle[j % 4] for j in range(d)]) for d in range(1, 9)]
+            notes += [(1, ["full16x128"]), (3, ["skew3x5"] * 3)]
+            for d, names in notes:
+                ss = [surf[name] for name in names]
+                corr = [[0.5 ** abs(j - k) for k in range(d)] for j in range(d)]
+                q = [0.01 * (j % 3) for j in range(d)]
+                for ki in (capi.AUTOCALL_KI_NONE, capi.AUTOCALL_KI_AT_MATURITY, capi.AUTOCALL_KI_EVERY_STEP):
+                    ac = capi.make_autocall_localvol(q, corr, 3, 1.0, 0.02, 0.8 if ki else 0.0, ki, call_step_down=0.01)
+                    res = ctx.price_autocall_localvol(opt, sim(12, prec, off), ac, ss, out.zero_())
+                    emit(f"autocall {tag} d={d} on {'+'.join(names)} ki={ki}", res, out)
+            # mcamd_price_barrier, continuous monitoring: the bridge factor
+            for kind in range(4):
+                up = kind in (capi.BARRIER_UP_OUT, capi.BARRIER_UP_IN)
+                opt = capi.make_option(S0=100.0, K=100.0, B=110.0 if up else 90.0, r=0.05, v=0.2, T=1.0)
+                res = ctx.price_barrier(opt, sim(13, prec, off), capi.make_barrier(kind, capi.PAYOFF_CALL), out.zero_())
+                emit(f"barrier {tag} kind={kind}", res, out)
+    print(json.dumps({"build_id": capi.build_id()}))
+    for s in surf.values():
+        s.close()
+    ctx.close()
+
+
+def main():
+    if sys.argv[1:] == ["--worker"]:
+        return worker()
+    if len(sys.argv) != 3:
+        print(__doc__, file=sys.stderr)
+        return 2
+    runs = []
+    n_lines = []
+    for lib in sys.argv[1:]:
+        env = dict(os.environ, MCAMD_LIB=os.path.abspath(lib))
+        o = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker"], env=env, capture_output=True, text=True)
+        lines = [json.loads(l) for l in o.stdout.splitlines() if l.startswith("{")]
+        if o.returncode or not lines or "build_id" not in lines[-1]:
+            print(f"worker failed for {lib} (exit status {o.returncode}):", o.stderr[-2000:], file=sys.stderr)
+            return 1
+        runs.append((lines[-1]["build_id"], {l["job"]: l["sha256"] for l in lines[:-1]}))
+        n_lines.append(len(lines) - 1)
+    (id_a, a), (id_b, b) = runs
+    differ = sorted(job for job in set(a) | set(b) if a.get(job) != b.get(job))
+    for job in differ:
+        print("DIFFERS", job)
+    print(f"same_bits: {len(a)} jobs, {len(differ)} differ; builds {id_a} and {id_b}")
+    if n_lines != [len(a), len(b)]:
+        print("same_bits: two jobs share a name", file=sys.stderr)
+        return 1
+    return 1 if differ or not a else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
