@@ -1191,6 +1191,99 @@ int mcamd_price_autocall_localvol_enqueue(mcamd_ctx *ctx, const mcamd_option *op
                                           const mcamd_autocall_localvol *autocall,
                                           const mcamd_localvol_surface *const *surfaces, void *d_samples, double *d_stats);
 
+/* ---- Local-volatility Greeks: price, delta, gamma, vega, bucketed vega, rho and dividend rho from ONE walk ----
+ * Additive to ABI version 5: first carried by the build that ships csrc/localvol_greeks.hip (no struct of an earlier
+ * call changed, so MCAMD_ABI_VERSION stays 5; a caller finds out with dlsym).  The pathwise derivative of the log-Euler
+ * path is a first-order tangent recurrence, driven by the normal and the table entry the step loads anyway.
+ *   Paths.  Those of mcamd_price_localvol with MCAMD_LOCALVOL_NO_BARRIER, draw for draw and operation for operation:
+ *       X_0 = 0, the same lookup, row rule, step and Philox subsequence (the GLOBAL path id).  opt->v is ignored.
+ *   Lookup and slope at step i = 0 .. n - 1 (n = n_steps):  k, f and s = fma(f, slope_k, sigma_k) exactly as there;
+ *       u_raw = (X_i - x_min) (1 / dx) is the value before the clamp;
+ *       s' = slope_k (1 / dx)  if 0 < u_raw < n_x - 1, strictly;  s' = 0 otherwise (a NaN gives 0).
+ *       The surface is flat outside its range, so a clamped path has no slope.
+ *   Tangents, in the path precision, with one factor per step:
+ *       c_i = sqrt(dt) z_{i+1} - s dt          (two products and their difference: three roundings; dt = T / n narrowed)
+ *       g_i = fma(s', c_i, 1)
+ *       J_{i+1} = J_i g_i,            J_0 = 1   tangent to X_0: the spot moves, the surface stays where it is in
+ *                                               absolute price
+ *       U_{i+1} = fma(U_i, g_i, c_i), U_0 = 0   tangent to sigma -> sigma + theta at every node
+ *       R_{i+1} = fma(R_i, g_i, dt),  R_0 = 0   tangent to r; the tangent to q is -R
+ *       U^b: sigma -> sigma + theta on the steps of time bucket b only, bucket(i) = floor(i B / n) in 64-bit integers
+ *            (the rule the rows use), B = n_vega_buckets in 0 .. 8; B need not divide n and may exceed it:
+ *            U^b_{i+1} = fma(U^b_i, g_i, c_i) if bucket(i) = b,  U^b_i g_i otherwise,  U^b_0 = 0.
+ *            A bucket that is empty or has not started is exactly 0.
+ *       Every fused operation is written as fma above; every other product, sum and difference is one operation.
+ *   Samples, formed once per path in fp64 (each product, quotient and difference one fp64 operation, left to right):
+ *       y = h(S_T) as mcamd_price_localvol forms it; omega = +1 (call) or -1 (put); I = 1{omega (S_T - K) > 0} (= h > 0
+ *       in the path precision); m = omega I S_T.
+ *       price y;  delta m J_n / S0;  vega m U_n;  bucket b: m U^b_n;  rho m R_n - T y;  rho_q -(m R_n).
+ *   Gamma.  The piecewise-linear surface has a slope that jumps at the nodes, and S0 often sits on a node, so a second
+ *       pathwise derivative does not exist.  Gamma is a central common-random-number difference of the pathwise delta:
+ *       with eta = gamma_bump, two more walks start at X_0 = +eta and X_0 = -eta (narrowed to the path precision) on the
+ *       same normals, each with its own lookups and its own J.  With S^+- = S0 e^{+-eta} (fp64), S_T^+- = S0 e^{X_n^+-},
+ *       delta^+- = m^+- J_n^+- / S^+-, the sample is (delta^+ - delta^-) / (S^+ - S^-).  eta = 0 skips the two walks:
+ *       gamma's value and std_err are then NaN and its sums 0.
+ *   On a node.  When X_0 lies exactly on a node, which cell floor(u) picks at step 0 depends on the rounding of 1 / dx in
+ *       the path precision.  Only J_1, hence delta and gamma, sees that (U_1 = c_0 and R_1 = dt do not): delta is then a
+ *       one-sided derivative, and the two path precisions may take different sides.
+ *   value = e^{-rT} mean, std_err as mcamd_finalize computes it.  Vega and the buckets are per unit of volatility, rho
+ *   and rho_q per unit of rate.  Theta is not offered: with the time slices tied to T its convention is ambiguous.
+ *   Statistics record (32 doubles): [0..12) the (sum, sumsq) pairs of price, delta, gamma, vega, rho, rho_q;
+ *   [12..28) the pairs of the eight buckets, unused ones exact zeros; [28] = n; [29..32) = 0.  Shards add element by
+ *   element; mcamd_finalize_localvol_greeks_stats serves the total (gamma_defined = 0 reports gamma as NaN with zero
+ *   sums; buckets from n_vega_buckets on stay 0).  The enqueue form leaves the record in d_stats (device, >= 32 doubles;
+ *   it reads NaN until the kernel has written it); mcamd_enqueued_kernel_ms covers it.  One launch, one fixed order of
+ *   summation: two runs of one job give the same bits.
+ *   d_samples (nullable, device): ALWAYS double, estimator-major, (6 + n_vega_buckets) x n_paths_local values:
+ *   [e * n_paths_local + local path] receives sample e (MCAMD_LOCALVOL_GREEK_* order, then the buckets; the gamma row
+ *   is 0 when eta = 0).
+ * Requirements (MCAMD_ERR_INVALID before any device work; first everything that needs neither the surface nor the
+ * context, then the surface, then the context): everything mcamd_price_localvol refuses for a barrier-less job; payoff in
+ * range; n_vega_buckets <= MCAMD_LOCALVOL_GREEKS_MAX_BUCKETS; gamma_bump finite and in [0, 0.1]; the fp64 exponent-
+ * range bound taken with |eta| added to the path's log-return range.  An empty shard returns zeros and launches nothing.
+ * There is no mcamd_group_* form, no shim name and no barrier; per-node vega and Greeks of the smile and of the
+ * autocallable are not offered.  New. */
+#define MCAMD_LOCALVOL_GREEKS_MAX_BUCKETS 8
+
+#define MCAMD_LOCALVOL_GREEK_PRICE 0
+#define MCAMD_LOCALVOL_GREEK_DELTA 1
+#define MCAMD_LOCALVOL_GREEK_GAMMA 2
+#define MCAMD_LOCALVOL_GREEK_VEGA  3
+#define MCAMD_LOCALVOL_GREEK_RHO   4
+#define MCAMD_LOCALVOL_GREEK_RHO_Q 5
+
+typedef struct mcamd_localvol_greeks_job {   /* 24 bytes */
+    int32_t  payoff;           /* MCAMD_PAYOFF_* */
+    uint32_t n_vega_buckets;   /* 0 .. MCAMD_LOCALVOL_GREEKS_MAX_BUCKETS */
+    double   q;                /* continuous dividend yield */
+    double   gamma_bump;       /* eta in ln(S) units, 0 .. 0.1; 0: no gamma */
+} mcamd_localvol_greeks_job;
+
+typedef struct mcamd_localvol_greeks {       /* 472 bytes */
+    double value[6];           /* D * mean, indexed MCAMD_LOCALVOL_GREEK_*; gamma NaN when gamma_bump = 0 */
+    double std_err[6];         /* D * sqrt(s^2 / n) */
+    double bucket_value[8];    /* bucketed vega; buckets from n_vega_buckets on are 0 */
+    double bucket_std_err[8];
+    double sum[6];             /* the shard's raw fp64 sums of the undiscounted samples */
+    double sumsq[6];
+    double bucket_sum[8];
+    double bucket_sumsq[8];
+    uint64_t n;                /* paths */
+    float kernel_ms;           /* HIP-event time of the kernel (it finishes its own sum: the whole call's device work) */
+    float total_ms;
+    uint32_t grid;             /* launch shape the engine chose */
+    uint32_t block;
+} mcamd_localvol_greeks;
+
+int mcamd_price_localvol_greeks(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                                const mcamd_localvol_greeks_job *job, const mcamd_localvol_surface *surface,
+                                double *d_samples, mcamd_localvol_greeks *out);
+int mcamd_price_localvol_greeks_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                                        const mcamd_localvol_greeks_job *job, const mcamd_localvol_surface *surface,
+                                        double *d_samples, double *d_stats);
+int mcamd_finalize_localvol_greeks_stats(const double stats[32], double r, double T, uint32_t n_vega_buckets,
+                                         int gamma_defined, mcamd_localvol_greeks *out);
+
 /* Host: discount + mean + standard error + 95% CI from (sum, sumsq, n) — after an all-reduce
  * over shards, or directly.  Fills price/std_err/ci_* (and copies sum/sumsq/n) in *res. */
 int mcamd_finalize(double sum, double sumsq, uint64_t n, double r, double T, mcamd_result *res);

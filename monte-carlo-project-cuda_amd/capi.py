@@ -35,6 +35,11 @@ AUTOCALL_KI_NONE, AUTOCALL_KI_AT_MATURITY, AUTOCALL_KI_EVERY_STEP = 0, 1, 2
 LOCALVOL_NO_BARRIER = -1
 LOCALVOL_MAX_NODES = 2048
 SMILE_MAX_STRIKES, SMILE_MAX_EXPIRIES = 64, 32
+LOCALVOL_GREEKS_MAX_BUCKETS = 8
+(LOCALVOL_GREEK_PRICE, LOCALVOL_GREEK_DELTA, LOCALVOL_GREEK_GAMMA, LOCALVOL_GREEK_VEGA, LOCALVOL_GREEK_RHO,
+ LOCALVOL_GREEK_RHO_Q) = range(6)
+LOCALVOL_GREEK_NAMES = ("price", "delta", "gamma", "vega", "rho", "rho_q")
+LOCALVOL_GREEKS_STATS = 32   # doubles of the record: six (sum, sumsq) pairs, eight bucket pairs, n, zeros
 BASKET_MAX_ASSETS = 8
 BASKET_ARITHMETIC, BASKET_GEOMETRIC, BASKET_BEST_OF, BASKET_WORST_OF = 0, 1, 2, 3
 BASKET_NO_BARRIER, BASKET_DOWN_OUT, BASKET_DOWN_IN, BASKET_UP_OUT, BASKET_UP_IN = 0, 1, 2, 3, 4
@@ -62,6 +67,7 @@ EXPORTS = [
     "mcamd_price_localvol_enqueue", "mcamd_localvol_sigma_f64", "mcamd_bs_price_f64",
     "mcamd_bs_implied_vol_f64", "mcamd_price_localvol_smile", "mcamd_price_localvol_smile_enqueue", "mcamd_finalize_smile",
     "mcamd_price_autocall_localvol", "mcamd_price_autocall_localvol_enqueue",
+    "mcamd_price_localvol_greeks", "mcamd_price_localvol_greeks_enqueue", "mcamd_finalize_localvol_greeks_stats",
 ]
 
 
@@ -202,6 +208,25 @@ class LocalVol(C.Structure):
                 ("q", C.c_double)]
 
 
+class LocalVolGreeksJob(C.Structure):
+    """mcamd_localvol_greeks_job: the payoff, the number of vega time buckets, the dividend yield and gamma's bump in
+    ln(S) (0: no gamma) of mcamd_price_localvol_greeks."""
+    _fields_ = [("payoff", C.c_int32), ("n_vega_buckets", C.c_uint32), ("q", C.c_double), ("gamma_bump", C.c_double)]
+
+
+class LocalVolGreeks(C.Structure):
+    """mcamd_localvol_greeks: value / std_err / raw sums of price, delta, gamma, vega, rho, rho_q (indexed
+    LOCALVOL_GREEK_*) and of the vega buckets."""
+    _fields_ = [("value", C.c_double * 6), ("std_err", C.c_double * 6), ("bucket_value", C.c_double * 8),
+                ("bucket_std_err", C.c_double * 8), ("sum", C.c_double * 6), ("sumsq", C.c_double * 6),
+                ("bucket_sum", C.c_double * 8), ("bucket_sumsq", C.c_double * 8), ("n", C.c_uint64),
+                ("kernel_ms", C.c_float), ("total_ms", C.c_float), ("grid", C.c_uint32), ("block", C.c_uint32)]
+
+    def as_dict(self):
+        """{name: (value, std_err)} of the six quantities"""
+        return {name: (self.value[i], self.std_err[i]) for i, name in enumerate(LOCALVOL_GREEK_NAMES)}
+
+
 class Smile(C.Structure):
     """mcamd_smile: the payoff of every node, the numbers of expiries and strikes, and the dividend yield
     mcamd_price_localvol_smile prices a strike-by-expiry set of vanillas with."""
@@ -335,6 +360,12 @@ def load() -> C.CDLL:
                                                      C.POINTER(f64), vp, vp, vp]
     L.mcamd_finalize_smile.argtypes = [C.POINTER(f64), u64, C.POINTER(Option), C.c_uint32, C.POINTER(Smile), u32p,
                                        C.POINTER(f64), C.POINTER(f64)]
+    L.mcamd_price_localvol_greeks.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(LocalVolGreeksJob), vp, vp,
+                                              C.POINTER(LocalVolGreeks)]
+    L.mcamd_price_localvol_greeks_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(LocalVolGreeksJob),
+                                                      vp, vp, vp]
+    L.mcamd_finalize_localvol_greeks_stats.argtypes = [C.POINTER(f64), f64, f64, C.c_uint32, i32,
+                                                       C.POINTER(LocalVolGreeks)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("mcamd_abi_version",):
@@ -492,6 +523,10 @@ def make_localvol(payoff=PAYOFF_CALL, barrier=LOCALVOL_NO_BARRIER, monitoring=MO
     return LocalVol(payoff, barrier, monitoring, 0, q)
 
 
+def make_localvol_greeks_job(payoff=PAYOFF_CALL, n_vega_buckets=0, q=0.0, gamma_bump=0.0) -> LocalVolGreeksJob:
+    return LocalVolGreeksJob(payoff, n_vega_buckets, q, gamma_bump)
+
+
 def make_localvol_grid(n_t, n_x, x_min, x_max) -> LocalVolGrid:
     return LocalVolGrid(n_t, n_x, x_min, x_max)
 
@@ -612,6 +647,14 @@ def finalize_greeks_stats(stats16, r, T, theta_defined=True) -> Greeks:
     return out
 
 
+def finalize_localvol_greeks_stats(stats32, r, T, n_vega_buckets=0, gamma_defined=True) -> LocalVolGreeks:
+    """Greeks of a (possibly all-reduced) 32-double record left by Context.price_localvol_greeks_enqueue."""
+    out = LocalVolGreeks()
+    arr = (C.c_double * LOCALVOL_GREEKS_STATS)(*[float(x) for x in stats32])
+    _check(load().mcamd_finalize_localvol_greeks_stats(arr, r, T, n_vega_buckets, int(gamma_defined), C.byref(out)))
+    return out
+
+
 def bs_greeks_f64(S0, K, T, r, sigma):
     """closed-form (price, delta, gamma, vega, rho, theta) of the call"""
     arr = (C.c_double * 6)()
@@ -729,6 +772,23 @@ class Context:
         """Asynchronous: leaves {sum, sumsq, 0, 0, 0, n} in the device tensor `stats` (>= 6 doubles; finalize_stats)."""
         _check(self._L.mcamd_price_localvol_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(localvol), surface._h,
                                                     _ptr(samples), _ptr(stats)))
+
+    def price_localvol_greeks(self, opt: Option, sim: Sim, job: LocalVolGreeksJob, surface: "LocalVolSurface",
+                              samples=None) -> LocalVolGreeks:
+        """Price, delta, gamma, vega, bucketed vega, rho and dividend rho of a European option under a local-volatility
+        surface from one walk of the paths (mcamd_price_localvol_greeks); opt.v is ignored.  samples: optional device
+        tensor of (6 + n_vega_buckets) x n_paths_local doubles, estimator-major, that receives every path's
+        undiscounted samples."""
+        out = LocalVolGreeks()
+        _check(self._L.mcamd_price_localvol_greeks(self._h, C.byref(opt), C.byref(sim), C.byref(job), surface._h,
+                                                   _ptr(samples), C.byref(out)))
+        return out
+
+    def price_localvol_greeks_enqueue(self, opt: Option, sim: Sim, job: LocalVolGreeksJob, surface: "LocalVolSurface",
+                                      stats, samples=None) -> None:
+        """Asynchronous: leaves the 32-double record in the device tensor `stats` (finalize_localvol_greeks_stats)."""
+        _check(self._L.mcamd_price_localvol_greeks_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(job), surface._h,
+                                                           _ptr(samples), _ptr(stats)))
 
     def price_localvol_smile(self, opt: Option, sim: Sim, smile: Smile, expiry_steps, strikes,
                              surface: "LocalVolSurface", spots=None):

@@ -13,6 +13,7 @@
 #include "autocall.hpp"
 #include "autocall_localvol.hpp"
 #include "localvol.hpp"
+#include "localvol_greeks.hpp"
 #include "localvol_smile.hpp"
 
 #include "mcamd.h"
@@ -47,6 +48,10 @@ static_assert(sizeof(mcamd_localvol_grid) == 24 && sizeof(mcamd_localvol) == 24,
 static_assert(sizeof(mcamd_smile) == 24, "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
 static_assert(MCAMD_SMILE_MAX_STRIKES == mcamd::kSmileMaxStrikes && MCAMD_SMILE_MAX_EXPIRIES == mcamd::kSmileMaxExpiries,
               "the smile kernel takes one strike per lane and MCAMD_SMILE_MAX_EXPIRIES expiry steps");
+static_assert(sizeof(mcamd_localvol_greeks_job) == 24 && sizeof(mcamd_localvol_greeks) == 472,
+              "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
+static_assert(MCAMD_LOCALVOL_GREEKS_MAX_BUCKETS == mcamd::kLvGreeksMaxBuckets && MCAMD_LOCALVOL_GREEK_RHO_Q + 1 == mcamd::kLvGreeks,
+              "the kernel's record holds six estimators and MCAMD_LOCALVOL_GREEKS_MAX_BUCKETS buckets");
 static_assert(MCAMD_LOCALVOL_MAX_NODES == mcamd::kLocalVolMaxNodes, "the kernel's LDS budget holds MCAMD_LOCALVOL_MAX_NODES");
 static_assert(MCAMD_AUTOCALL_MAX_DATES == mcamd::kAutocallMaxDates, "the kernel's date tables hold MCAMD_AUTOCALL_MAX_DATES");
 
@@ -95,7 +100,7 @@ struct mcamd_ctx {
     unsigned long long *d_queue = nullptr;  // task counter of the wave-per-point nested-MC kernel
     unsigned int *d_ticket = nullptr;       // arrival counter of kernels that finish their own sum (in d_queue's allocation)
     uint32_t compute_units = 0;
-    static constexpr int kRecord = 16;      // doubles of h_rec: the widest final record (Greeks' statistics layout)
+    static constexpr int kRecord = 32;      // doubles of h_rec: the widest final record (the local-volatility Greeks' statistics layout)
     double *h_rec = nullptr;                // pinned: the final record of a synchronous call
     double *h_rec_dev = nullptr;            // h_rec as the device addresses it (a self-finishing kernel writes there)
     // asynchronous calls: a ring of event pairs around the simulation kernel of the last kRing enqueues
@@ -276,7 +281,8 @@ struct DeviceCall {
     uint64_t n;      // paths (nested MC: points) of the shard, the statistics layout's n; 0: empty shard, nothing runs
     uint32_t grid;   // block records the kernel writes
     int rec;         // doubles per block record
-    int stats;       // doubles of the statistics layout an enqueue leaves in d_stats: 6, or 16 for Greeks
+    int stats;       // doubles of the statistics layout an enqueue leaves in d_stats: 6, 16 for Greeks, 32 for the
+                     // local-volatility Greeks
     Finish how;
     Launch launch;
 };
@@ -765,11 +771,12 @@ int check_localvol_request(const char *name, mcamd_option seen, const mcamd_sim 
 }
 
 // check_request's fp64 bound with the largest drift and volatility any node of a surface can give; asset >= 0 names
-// the asset the surface belongs to.
-int check_localvol_exponent_range(double mu, double sigma_max, double dt, uint32_t n_steps, int asset = -1)
+// the asset the surface belongs to; start: the largest |X_0| of the call's walks.
+int check_localvol_exponent_range(double mu, double sigma_max, double dt, uint32_t n_steps, int asset = -1,
+                                  double start = 0.0)
 {
     const double per_step = (std::fabs(mu) + 0.5 * sigma_max * sigma_max) * dt + 8.6 * sigma_max * std::sqrt(dt);
-    if (per_step < 700.0 && per_step * static_cast<double>(n_steps) < 20000.0) return MCAMD_OK;
+    if (per_step < 700.0 && per_step * static_cast<double>(n_steps) + start < 20000.0) return MCAMD_OK;
     if (asset < 0)
         return fail(MCAMD_ERR_INVALID,
                     "fp64 path: |drift| + 8.6 vol = %.3g per step over %u steps exceeds the exponent range "
@@ -847,6 +854,85 @@ int prepare_localvol(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *s
     return drive(DeviceCall{job.n_local, grid, mcamd::kLocalVolRecord, 6, Finish::kFolded,
                             [&](const mcamd::FinishSpec &fs) {
                                 return mcamd::launch_localvol(job, ctx->d_partials, grid, fs, ctx->stream);
+                            }});
+}
+
+// value / std_err / sums of a (possibly all-reduced) 32-double local-volatility Greeks record
+void finalize_localvol_greeks_into(const double stats[32], double r, double T, uint32_t n_buckets, int gamma_defined,
+                                   mcamd_localvol_greeks *out)
+{
+    const double disc = std::exp(-r * T);
+    const uint64_t n = static_cast<uint64_t>(std::llround(stats[mcamd::kLvGreeksRecord]));
+    out->n = n;
+    for (int k = 0; k < mcamd::kLvGreeks; ++k) {
+        const Estimate e = estimate(stats[2 * k], stats[2 * k + 1], n, disc);
+        out->sum[k] = stats[2 * k];
+        out->sumsq[k] = stats[2 * k + 1];
+        out->value[k] = e.value;
+        out->std_err[k] = e.std_err;
+    }
+    if (!gamma_defined) {
+        out->value[MCAMD_LOCALVOL_GREEK_GAMMA] = out->std_err[MCAMD_LOCALVOL_GREEK_GAMMA] = std::nan("");
+        out->sum[MCAMD_LOCALVOL_GREEK_GAMMA] = out->sumsq[MCAMD_LOCALVOL_GREEK_GAMMA] = 0.0;
+    }
+    for (uint32_t b = 0; b < n_buckets; ++b) {
+        const double *pair = stats + 2 * (mcamd::kLvGreeks + b);
+        const Estimate e = estimate(pair[0], pair[1], n, disc);
+        out->bucket_sum[b] = pair[0];
+        out->bucket_sumsq[b] = pair[1];
+        out->bucket_value[b] = e.value;
+        out->bucket_std_err[b] = e.std_err;
+    }
+}
+
+// The local-volatility Greeks calls: prepare_localvol's refusals for a barrier-less job, in its order, with the
+// job's own in between.  The kernel finishes its own sum into the 32-double statistics record.  opt->v is ignored.
+template <typename Drive>
+int prepare_localvol_greeks(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                            const mcamd_localvol_greeks_job *gj, const mcamd_localvol_surface *surface, double *d_samples,
+                            Drive drive)
+{
+    if (!opt || !sim || !gj) return fail(MCAMD_ERR_INVALID, "opt, sim, job and surface must be non-NULL");
+    if (gj->payoff != MCAMD_PAYOFF_CALL && gj->payoff != MCAMD_PAYOFF_PUT)
+        return fail(MCAMD_ERR_INVALID, "payoff must be MCAMD_PAYOFF_CALL (0) or MCAMD_PAYOFF_PUT (1), got %d", gj->payoff);
+    if (gj->n_vega_buckets > MCAMD_LOCALVOL_GREEKS_MAX_BUCKETS)
+        return fail(MCAMD_ERR_INVALID, "n_vega_buckets must lie in 0 .. %d, got %u", MCAMD_LOCALVOL_GREEKS_MAX_BUCKETS,
+                    gj->n_vega_buckets);
+    if (!std::isfinite(gj->gamma_bump) || gj->gamma_bump < 0.0 || gj->gamma_bump > 0.1)
+        return fail(MCAMD_ERR_INVALID, "gamma_bump must be finite and lie in 0 .. 0.1, got %g", gj->gamma_bump);
+    if (!std::isfinite(gj->q)) return fail(MCAMD_ERR_INVALID, "the dividend yield q must be finite, got %g", gj->q);
+    if (!std::isfinite(opt->r)) return fail(MCAMD_ERR_INVALID, "option parameters must be finite with T > 0");
+    const double mu = opt->r - gj->q;
+    if (int rc = check_localvol_request("local-volatility Greeks", *opt, sim, &mu, 1)) return rc;
+    if (!(opt->S0 > 0.0)) return fail(MCAMD_ERR_INVALID, "local-volatility Greeks need S0 > 0 (S0 = %g)", opt->S0);
+    if (!surface) return fail(MCAMD_ERR_INVALID, "opt, sim, job and surface must be non-NULL");
+    const double dt = opt->T / static_cast<double>(sim->n_steps);
+    if (sim->precision == MCAMD_F64)
+        if (int rc = check_localvol_exponent_range(mu, surface->sigma_max, dt, sim->n_steps, -1, gj->gamma_bump)) return rc;
+    if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
+    if (!surface_belongs(surface, ctx)) return fail(MCAMD_ERR_INVALID, "the surface was created on another context");
+    if (sim->n_paths_local == 0) return drive(empty_call(mcamd::kLvGreeksStats));
+    mcamd::LocalVolGreeksJob job;
+    job.seed = sim->seed;
+    job.path_offset = sim->path_offset;
+    job.n_local = sim->n_paths_local;
+    job.n_steps = sim->n_steps;
+    job.precision = sim->precision;
+    job.S0 = opt->S0;
+    job.K = opt->K;
+    job.mu = mu;
+    job.dt = dt;
+    job.T = opt->T;
+    job.put = gj->payoff == MCAMD_PAYOFF_PUT;
+    job.n_buckets = gj->n_vega_buckets;
+    job.gamma_bump = gj->gamma_bump;
+    job.surface = job_surface(surface, sim->precision);
+    job.d_samples = d_samples;
+    const uint32_t grid = mcamd::one_path_per_thread_grid(job.n_local);
+    return drive(DeviceCall{job.n_local, grid, mcamd::kLvGreeksRecord, mcamd::kLvGreeksStats, Finish::kFolded,
+                            [&](const mcamd::FinishSpec &fs) {
+                                return mcamd::launch_localvol_greeks(job, ctx->d_partials, grid, fs.out, fs.ticket,
+                                                                     ctx->stream);
                             }});
 }
 
@@ -2475,6 +2561,44 @@ int mcamd_price_localvol_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const 
 {
     return prepare_localvol(ctx, opt, sim, localvol, surface, d_samples,
                             [&](const auto &call) { return run_enqueue(ctx, call, d_stats); });
+}
+
+int mcamd_price_localvol_greeks(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                                const mcamd_localvol_greeks_job *job, const mcamd_localvol_surface *surface,
+                                double *d_samples, mcamd_localvol_greeks *out)
+{
+    if (!out) return fail(MCAMD_ERR_INVALID, "opt, sim, job, surface and out must be non-NULL");
+    std::memset(out, 0, sizeof *out);
+    return prepare_localvol_greeks(ctx, opt, sim, job, surface, d_samples, [&](const auto &call) {
+        return run_sync(ctx, call, out, [&](const double *stats) {
+            finalize_localvol_greeks_into(stats, opt->r, opt->T, job->n_vega_buckets, job->gamma_bump > 0.0, out);
+        });
+    });
+}
+
+int mcamd_price_localvol_greeks_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                                        const mcamd_localvol_greeks_job *job, const mcamd_localvol_surface *surface,
+                                        double *d_samples, double *d_stats)
+{
+    return prepare_localvol_greeks(ctx, opt, sim, job, surface, d_samples, [&](const auto &call) {
+        if (call.n && d_stats) {   // NaN (all-ones bytes) until the kernel has written the record
+            HIP_TRY(hipSetDevice(ctx->device));
+            HIP_TRY(hipMemsetAsync(d_stats, 0xFF, mcamd::kLvGreeksStats * sizeof(double), ctx->stream));
+        }
+        return run_enqueue(ctx, call, d_stats);
+    });
+}
+
+int mcamd_finalize_localvol_greeks_stats(const double stats[32], double r, double T, uint32_t n_vega_buckets,
+                                         int gamma_defined, mcamd_localvol_greeks *out)
+{
+    if (!stats || !out) return fail(MCAMD_ERR_INVALID, "stats and out must be non-NULL");
+    if (n_vega_buckets > MCAMD_LOCALVOL_GREEKS_MAX_BUCKETS)
+        return fail(MCAMD_ERR_INVALID, "n_vega_buckets must lie in 0 .. %d, got %u", MCAMD_LOCALVOL_GREEKS_MAX_BUCKETS,
+                    n_vega_buckets);
+    std::memset(out, 0, sizeof *out);
+    finalize_localvol_greeks_into(stats, r, T, n_vega_buckets, gamma_defined, out);
+    return MCAMD_OK;
 }
 
 // fills *res from an autocall kernel's record: {sum, sumsq, paths called, sum of their call times, paths not called and

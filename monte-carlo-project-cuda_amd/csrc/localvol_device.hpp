@@ -1,6 +1,7 @@
 // localvol_device.hpp — everything a kernel needs to walk one local-volatility surface, shared by localvol.hip,
-// localvol_smile.hip and autocall_localvol_impl.hpp: the surface's constants and the host function that builds them,
-// the table's copy into dynamic LDS, the lookup with its row carry, and the log-Euler move.
+// localvol_smile.hip, autocall_localvol_impl.hpp and localvol_greeks.hip: the surface's constants and the host function
+// that builds them, the table's copy into dynamic LDS, the lookup with its row carry (and, for the Greeks, the lookup
+// that hands back the cell's slope as well), and the log-Euler move.
 //
 // Definitions (include/mcamd.h, mcamd_price_localvol): X = ln(S / S0) in NATURAL-log units (the surface's axis).  Step
 // i looks its volatility up at X in row(i) = floor(i n_t / n) of the surface, s = fma(f, slope_k, sigma_k) with
@@ -127,6 +128,41 @@ __device__ __forceinline__ T lv_sigma(T X, const LvAxis<T> &ax, const LvRows &r,
         row.phase += r.row_rem;
     }
     return s;
+}
+
+// lv_sigma for a kernel that differentiates the walk (localvol_greeks.hip): the same u, k, f and s at the row a caller
+// holds, with the cell's slope and whether X lies strictly inside the axis (before the clamp: outside it the surface
+// is flat and the walk has no slope; a NaN is outside).  The row is not advanced, so several walks can look the same
+// step up; lv_next_row then carries it exactly as lv_sigma does.
+template <typename T>
+struct LvLookup {
+    T s;           // fma(f, slope_k, sigma_k)
+    T slope;       // slope_k
+    bool inside;   // 0 < (X - x_min) (1 / dx) < n_x - 1
+};
+
+template <typename T>
+__device__ __forceinline__ LvLookup<T> lv_sigma_slope(T X, const LvAxis<T> &ax, const LvRows &r, const VolPair<T> *tab,
+                                                      const LvRow &row)
+{
+    const T u_raw = (X - ax.x_min) * ax.inv_dx;
+    const T u = lv_min(lv_max(u_raw, T(0)), ax.u_max);
+    uint32_t k = static_cast<uint32_t>(u);
+    k = k < r.k_max ? k : r.k_max;
+    const T f = u - static_cast<T>(k);
+    const VolPair<T> p = tab[row.base + k];
+    return {fma_t(f, p.slope, p.sigma), p.slope, u_raw > T(0) && u_raw < ax.u_max};
+}
+
+__device__ __forceinline__ void lv_next_row(const LvRows &r, LvRow &row)
+{
+    row.base += r.row_whole_nx;
+    if (row.phase >= r.row_thr) {
+        row.phase -= r.row_thr;
+        row.base += r.n_x;
+    } else {
+        row.phase += r.row_rem;
+    }
 }
 
 // The log-Euler move of one step at volatility s with the normal z (the correlated w_j of a multi-asset kernel).

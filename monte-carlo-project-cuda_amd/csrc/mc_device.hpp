@@ -967,10 +967,11 @@ static_assert(MCAMD_FINISH_ACC == 1 || MCAMD_FINISH_ACC == 2 || MCAMD_FINISH_ACC
 // Sums n_records records of N doubles with the BLOCK threads of one workgroup in a fixed order: thread t takes records
 // t, t + BLOCK, ... round-robin into kAcc = 4 independent accumulator sets (more would push the pricing kernels past 80 vector registers, i.e. below six wavefronts per SIMD; four loads in flight per lane hide most of the L2
 // latency of the lone workgroup), the sets are added pairwise, block_sumN finishes.  Result valid in thread 0.
-template <int BLOCK, int N>
+// ACC: the number of sets; a kernel with a wide record that always finishes itself may take fewer (its own fixed order).
+template <int BLOCK, int N, int ACC = MCAMD_FINISH_ACC>
 __device__ __forceinline__ void small_final_sum(const double *__restrict__ partials, uint32_t n_records, double (&v)[N])
 {
-    constexpr int kAcc = MCAMD_FINISH_ACC;
+    constexpr int kAcc = ACC;
     double s[kAcc][N];
 #pragma unroll
     for (int u = 0; u < kAcc; ++u)
@@ -1025,7 +1026,7 @@ struct GridFinish {
 // relaxed agent-scope atomic add; consumer = the lane whose add came last, agent-scope acquire fence, s_waitcnt,
 // workgroup barrier, plain loads.  Per-XCD L2s are not coherent: the release writes the record back, the acquire
 // drops what the reading CU may hold of the array from an earlier launch.
-template <int BLOCK, int N>
+template <int BLOCK, int N, int ACC = MCAMD_FINISH_ACC>
 __device__ __forceinline__ void grid_finish(double (&v)[N], double *__restrict__ partials, const GridFinish &f)
 {
     __shared__ unsigned int s_last;
@@ -1053,7 +1054,7 @@ __device__ __forceinline__ void grid_finish(double (&v)[N], double *__restrict__
     __syncthreads();
     if (s_last == 0) return;   // workgroup-uniform
     double t[N];
-    small_final_sum<BLOCK, N>(partials, gridDim.x, t);
+    small_final_sum<BLOCK, N, ACC>(partials, gridDim.x, t);
     if (threadIdx.x == 0) {
         write_final(f.out, t, N, f.n_value);
         __hip_atomic_store(f.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
