@@ -1284,6 +1284,107 @@ int mcamd_price_localvol_greeks_enqueue(mcamd_ctx *ctx, const mcamd_option *opt,
 int mcamd_finalize_localvol_greeks_stats(const double stats[32], double r, double T, uint32_t n_vega_buckets,
                                          int gamma_defined, mcamd_localvol_greeks *out);
 
+/* ---- Cliquets, forward-start options and realized-variance swaps under a local-volatility surface ----
+ * Additive to ABI version 5: first carried by the build that ships csrc/cliquet.hip (no struct of an earlier call
+ * changed, so MCAMD_ABI_VERSION stays 5; a caller finds out with dlsym).  Payoffs built from the returns between reset
+ * dates, where every other surface call reads the path at maturity or against a level fixed today: what they are worth
+ * rests on the forward smile, which a local-volatility surface flattens.
+ *   Paths.  Those of mcamd_price_localvol with MCAMD_LOCALVOL_NO_BARRIER, draw for draw and operation for operation:
+ *       X_0 = 0, the same surface object, lookup, row rule, step and Philox subsequence (the GLOBAL path id), one normal
+ *       per step and nothing else drawn.  r, T and S0 come from opt; the notional is 1, so S0 only says which spot the
+ *       surface's axis x = ln(S / S0) is measured from and no arithmetic reads it.  opt->v, opt->K and opt->B are
+ *       ignored.  q = cliquet->q is the dividend yield, n = n_steps, dt = T / n.
+ *   Reset dates.  p = 1..M at the ends of steps s_p = p reset_every, M = n / reset_every, s_0 = 0; tau = reset_every dt.
+ *       The period log-return is D_p = X_{s_p} - X_{s_{p-1}}, one subtraction in the path precision.  Periods
+ *       p < first_period are walked but do not count (the forward-start forms); P = M - first_period + 1 periods count.
+ *   MCAMD_CLIQUET_SUM (additive cliquet).  R_p = e^{D_p} - 1 through the exponential that ends a log-space path with
+ *       multiplier 1, exp_of_logreturn(1, D_p exp_scale) with exp_scale = log2 e (fp32) or 65536 / ln 2 (fp64) narrowed
+ *       to the path precision, then minus 1;  c_p = min(max(R_p, local_floor), local_cap), the bounds narrowed once;
+ *       A = sum_{p >= first_period} c_p, added in date order in the path precision.
+ *   MCAMD_CLIQUET_COMPOUND (compounding ratchet).  l_p = min(max(D_p, ln(1 + local_floor)), ln(1 + local_cap)), the two
+ *       logarithms formed in double on the host (log(1.0 + bound): ln 0 = -inf and ln inf = +inf are legitimate
+ *       operands) and narrowed once;  L = sum_{p >= first_period} l_p in date order in the path precision;
+ *       A = e^L - 1: ONE exponential per path, exp_of_logreturn(1, L exp_scale) in the path precision, widened, and the
+ *       subtraction in fp64.  No exponential is taken before maturity.
+ *   MCAMD_CLIQUET_VARIANCE (realized variance, annualised).  V = sum_{p >= first_period} D_p^2 in date order, as
+ *       V <- fma(D_p, D_p, V) in the path precision;  A = V (1 / (P tau)), the factor formed in double on the host as
+ *       1.0 / (P * (reset_every * dt)) and the product taken in fp64.  No exponential at all.
+ *   Sample, formed once per path in fp64:  y = min(max(A, global_floor), global_cap); an infinite bound never binds.
+ *       price = exp(-rT) mean(y), std_err as in mcamd_finalize.  A forward-start call struck at k times the spot of
+ *       the date t_1 the last period starts at is caller arithmetic on the SUM form with first_period = M,
+ *       local_floor = k - 1 and no other bound:  (S_T / S_{t_1} - k)+ = y - (k - 1).
+ *   Counters.  n_floored = paths with A <= global_floor, n_capped = paths with A >= global_cap, the comparisons in
+ *       fp64 on the value that is clipped; 0 for an infinite bound.
+ * A is kept in the path precision because it is path arithmetic (it is what an fp32 job is asked to do cheaply); y is
+ * formed in fp64 so that the clip, the counters and the sums see one value whatever the path precision.
+ * d_samples (nullable, device): n_paths_local values of the path precision; [local path] receives y.
+ * res: price .. n as mcamd_result; work_steps = 64 x the steps each wavefront ran, always the full count (there is no
+ * early exit).  The enqueue form leaves {sum, sumsq, n_floored, n_capped, 0, n} in d_stats: mcamd_finalize_stats serves
+ * it and mcamd_enqueued_kernel_ms covers it.  A sample depends on its global path id alone, so one all-reduce of the 6
+ * doubles serves multi-GPU use.  One launch, one fixed order of summation: two runs of one job give the same bits.
+ * Requirements (MCAMD_ERR_INVALID before any device work).  First everything that does not need the surface: opt, sim,
+ * cliquet, res non-NULL; kind in range; reserved == 0; reset_every >= 1 and n_steps % reset_every == 0;
+ * 1 <= first_period <= M; no bound NaN; local_floor < local_cap and global_floor < global_cap; COMPOUND:
+ * local_floor >= -1 and local_cap > -1; VARIANCE: local_floor == -inf and local_cap == +inf (they have no meaning
+ * there); q finite; r finite; use_window, P1, P2, Ik, Sk, Tk and opt->dt all 0; sim->flags 0 or MCAMD_FLAG_LOG_SPACE;
+ * what mcamd_price_paths refuses on sim (its fp64 exponent-range bound at the drift r - q alone).  Then the surface: NULL;
+ * in fp64 the exponent-range bound of mcamd_price_localvol at |r - q| and the surface's largest entry.  Then the
+ * context, and a surface created on another context.  An empty shard returns zeros and launches nothing; its enqueue
+ * form writes a zero record in stream order.
+ * Out of scope: an early exit once a floored sum has passed the global cap, Greeks, reverse cliquets, Napoleons and
+ * memory coupons, several assets, non-uniform reset schedules, corridor, gamma and volatility (square-root) swaps, a
+ * mcamd_group_* form and a shim name (the reference has no such product).  New. */
+#define MCAMD_CLIQUET_SUM 0
+#define MCAMD_CLIQUET_COMPOUND 1
+#define MCAMD_CLIQUET_VARIANCE 2
+
+typedef struct mcamd_cliquet {   /* 56 bytes */
+    int32_t kind;            /* MCAMD_CLIQUET_* */
+    uint32_t reset_every;    /* steps per period; divides n_steps */
+    uint32_t first_period;   /* 1..M: the first period that counts */
+    int32_t reserved;        /* must be 0 */
+    double local_floor;      /* of the period return R_p (-inf: none); VARIANCE: must be -inf */
+    double local_cap;        /* of the period return R_p (+inf: none); VARIANCE: must be +inf */
+    double global_floor;     /* of A (-inf: none) */
+    double global_cap;       /* of A (+inf: none) */
+    double q;                /* continuous dividend yield */
+} mcamd_cliquet;
+
+typedef struct mcamd_cliquet_result {   /* 96 bytes */
+    double price;            /* exp(-rT) * mean(y) */
+    double std_err;
+    double ci_lo, ci_hi;     /* 95 % confidence interval */
+    double sum, sumsq;       /* the shard's raw fp64 sums of the undiscounted samples */
+    uint64_t n;              /* paths */
+    uint64_t n_floored;      /* paths with A <= global_floor (0 without one) */
+    uint64_t n_capped;       /* paths with A >= global_cap (0 without one) */
+    double work_steps;       /* 64 x the steps each wavefront ran: always the full count */
+    float kernel_ms;         /* HIP-event time of the kernel (it finishes its own sum: the whole call's device work) */
+    float total_ms;
+    uint32_t grid;           /* launch shape the engine chose */
+    uint32_t block;
+} mcamd_cliquet_result;
+
+int mcamd_price_cliquet(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_cliquet *cliquet,
+                        const mcamd_localvol_surface *surface, void *d_samples, mcamd_cliquet_result *res);
+int mcamd_price_cliquet_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                                const mcamd_cliquet *cliquet, const mcamd_localvol_surface *surface, void *d_samples,
+                                double *d_stats);
+/* Host closed form, exact when the volatility varies in time only: there D_p ~ N((r - q - v_p^2 / 2) tau, v_p^2 tau),
+ * independently across periods, at every step count (the log-Euler walk is exact there).  tau = T / n_periods;
+ * period_vol[p - 1] = v_p, the rms volatility of period p; there is no global clip.
+ *   c_p(k) = E[(e^{D_p} - k)+] = e^{(r-q) tau} N(d1) - k N(d2),  d1 = ((r - q + v_p^2 / 2) tau - ln k) / (v_p sqrt tau),
+ *       d2 = d1 - v_p sqrt tau;  for k <= 0 it is e^{(r-q) tau} - k, for k = +inf it is 0.  N: the erfc form of
+ *       mcamd_bs_call_f64.
+ *   F = max(local_floor, -1) (a floor at or below -1 never binds);  E_p = (1 + F) + c_p(1 + F) - c_p(1 + local_cap),
+ *       the mean of the clipped gross return.
+ *   SUM: e^{-rT} sum_{p >= first_period} (E_p - 1).   COMPOUND: e^{-rT} (prod_{p >= first_period} E_p - 1).
+ *   VARIANCE: e^{-rT} (1 / (P tau)) sum_{p >= first_period} [v_p^2 tau + ((r - q - v_p^2 / 2) tau)^2].
+ * Refuses a NULL pointer, kind out of range, T <= 0, non-finite T, r or q, n_periods == 0, first_period outside
+ * 1..n_periods, a volatility that is not finite and > 0, and what mcamd_price_cliquet refuses of the local bounds. */
+int mcamd_cliquet_price_f64(int kind, double T, double r, double q, uint32_t n_periods, uint32_t first_period,
+                            const double *period_vol, double local_floor, double local_cap, double *price);
+
 /* Host: discount + mean + standard error + 95% CI from (sum, sumsq, n) — after an all-reduce
  * over shards, or directly.  Fills price/std_err/ci_* (and copies sum/sumsq/n) in *res. */
 int mcamd_finalize(double sum, double sumsq, uint64_t n, double r, double T, mcamd_result *res);

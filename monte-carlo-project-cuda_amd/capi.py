@@ -7,6 +7,7 @@ every call goes to the HIP library, and loading fails loudly if the library is m
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 
 PKG = os.path.dirname(os.path.abspath(__file__))
@@ -40,6 +41,7 @@ LOCALVOL_GREEKS_MAX_BUCKETS = 8
  LOCALVOL_GREEK_RHO_Q) = range(6)
 LOCALVOL_GREEK_NAMES = ("price", "delta", "gamma", "vega", "rho", "rho_q")
 LOCALVOL_GREEKS_STATS = 32   # doubles of the record: six (sum, sumsq) pairs, eight bucket pairs, n, zeros
+CLIQUET_SUM, CLIQUET_COMPOUND, CLIQUET_VARIANCE = 0, 1, 2
 BASKET_MAX_ASSETS = 8
 BASKET_ARITHMETIC, BASKET_GEOMETRIC, BASKET_BEST_OF, BASKET_WORST_OF = 0, 1, 2, 3
 BASKET_NO_BARRIER, BASKET_DOWN_OUT, BASKET_DOWN_IN, BASKET_UP_OUT, BASKET_UP_IN = 0, 1, 2, 3, 4
@@ -68,6 +70,7 @@ EXPORTS = [
     "mcamd_bs_implied_vol_f64", "mcamd_price_localvol_smile", "mcamd_price_localvol_smile_enqueue", "mcamd_finalize_smile",
     "mcamd_price_autocall_localvol", "mcamd_price_autocall_localvol_enqueue",
     "mcamd_price_localvol_greeks", "mcamd_price_localvol_greeks_enqueue", "mcamd_finalize_localvol_greeks_stats",
+    "mcamd_price_cliquet", "mcamd_price_cliquet_enqueue", "mcamd_cliquet_price_f64",
 ]
 
 
@@ -227,6 +230,25 @@ class LocalVolGreeks(C.Structure):
         return {name: (self.value[i], self.std_err[i]) for i, name in enumerate(LOCALVOL_GREEK_NAMES)}
 
 
+class Cliquet(C.Structure):
+    """mcamd_cliquet: the kind (CLIQUET_*), the reset schedule, the local bounds of a period's return, the global bounds
+    of the accumulated payoff (-inf / +inf: none) and the dividend yield mcamd_price_cliquet prices with."""
+    _fields_ = [("kind", C.c_int32), ("reset_every", C.c_uint32), ("first_period", C.c_uint32), ("reserved", C.c_int32),
+                ("local_floor", C.c_double), ("local_cap", C.c_double), ("global_floor", C.c_double),
+                ("global_cap", C.c_double), ("q", C.c_double)]
+
+
+class CliquetResult(C.Structure):
+    """mcamd_cliquet_result"""
+    _fields_ = [("price", C.c_double), ("std_err", C.c_double), ("ci_lo", C.c_double), ("ci_hi", C.c_double),
+                ("sum", C.c_double), ("sumsq", C.c_double), ("n", C.c_uint64), ("n_floored", C.c_uint64),
+                ("n_capped", C.c_uint64), ("work_steps", C.c_double), ("kernel_ms", C.c_float), ("total_ms", C.c_float),
+                ("grid", C.c_uint32), ("block", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class Smile(C.Structure):
     """mcamd_smile: the payoff of every node, the numbers of expiries and strikes, and the dividend yield
     mcamd_price_localvol_smile prices a strike-by-expiry set of vanillas with."""
@@ -349,6 +371,11 @@ def load() -> C.CDLL:
     L.mcamd_price_localvol.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(LocalVol), vp, vp,
                                        C.POINTER(Result)]
     L.mcamd_price_localvol_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(LocalVol), vp, vp, vp]
+    L.mcamd_price_cliquet.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Cliquet), vp, vp,
+                                      C.POINTER(CliquetResult)]
+    L.mcamd_price_cliquet_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Cliquet), vp, vp, vp]
+    L.mcamd_cliquet_price_f64.argtypes = [i32, f64, f64, f64, C.c_uint32, C.c_uint32, C.POINTER(f64), f64, f64,
+                                          C.POINTER(f64)]
     L.mcamd_localvol_sigma_f64.argtypes = [C.POINTER(LocalVolGrid), C.POINTER(f64), C.c_uint32, C.c_uint32, f64,
                                            C.POINTER(f64)]
     L.mcamd_bs_price_f64.argtypes = [f64, f64, f64, f64, f64, f64, i32, C.POINTER(f64)]
@@ -521,6 +548,21 @@ def autocall_single_date_price_f64(T, r, sigma, call_level, coupon, ki_level=0.0
 
 def make_localvol(payoff=PAYOFF_CALL, barrier=LOCALVOL_NO_BARRIER, monitoring=MONITOR_DISCRETE, q=0.0) -> LocalVol:
     return LocalVol(payoff, barrier, monitoring, 0, q)
+
+
+def make_cliquet(kind=CLIQUET_SUM, reset_every=1, first_period=1, local_floor=-math.inf, local_cap=math.inf,
+                 global_floor=-math.inf, global_cap=math.inf, q=0.0) -> Cliquet:
+    return Cliquet(kind, reset_every, first_period, 0, local_floor, local_cap, global_floor, global_cap, q)
+
+
+def cliquet_price(kind, T, r, q, period_vol, first_period=1, local_floor=-math.inf, local_cap=math.inf) -> float:
+    """Closed form of a cliquet without a global clip where the volatility varies in time only
+    (mcamd_cliquet_price_f64); period_vol: the rms volatility of each of the n_periods = len(period_vol) periods."""
+    vols = (C.c_double * len(period_vol))(*[float(v) for v in period_vol])
+    out = C.c_double()
+    _check(load().mcamd_cliquet_price_f64(kind, T, r, q, len(period_vol), first_period, vols, local_floor, local_cap,
+                                          C.byref(out)))
+    return out.value
 
 
 def make_localvol_greeks_job(payoff=PAYOFF_CALL, n_vega_buckets=0, q=0.0, gamma_bump=0.0) -> LocalVolGreeksJob:
@@ -772,6 +814,23 @@ class Context:
         """Asynchronous: leaves {sum, sumsq, 0, 0, 0, n} in the device tensor `stats` (>= 6 doubles; finalize_stats)."""
         _check(self._L.mcamd_price_localvol_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(localvol), surface._h,
                                                     _ptr(samples), _ptr(stats)))
+
+    def price_cliquet(self, opt: Option, sim: Sim, cliquet: Cliquet, surface: "LocalVolSurface",
+                      samples=None) -> CliquetResult:
+        """Cliquet, forward-start option or realized-variance swap on the paths of price_localvol
+        (mcamd_price_cliquet); r, T and S0 come from opt, opt.v, opt.K and opt.B are ignored.  samples: optional device
+        tensor of n_paths_local values of the path precision that receives each path's undiscounted sample."""
+        res = CliquetResult()
+        _check(self._L.mcamd_price_cliquet(self._h, C.byref(opt), C.byref(sim), C.byref(cliquet), surface._h,
+                                           _ptr(samples), C.byref(res)))
+        return res
+
+    def price_cliquet_enqueue(self, opt: Option, sim: Sim, cliquet: Cliquet, surface: "LocalVolSurface", stats,
+                              samples=None) -> None:
+        """Asynchronous: leaves {sum, sumsq, n_floored, n_capped, 0, n} in the device tensor `stats` (>= 6 doubles;
+        finalize_stats)."""
+        _check(self._L.mcamd_price_cliquet_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(cliquet), surface._h,
+                                                   _ptr(samples), _ptr(stats)))
 
     def price_localvol_greeks(self, opt: Option, sim: Sim, job: LocalVolGreeksJob, surface: "LocalVolSurface",
                               samples=None) -> LocalVolGreeks:

@@ -12,6 +12,7 @@
 #include "asian.hpp"
 #include "autocall.hpp"
 #include "autocall_localvol.hpp"
+#include "cliquet.hpp"
 #include "localvol.hpp"
 #include "localvol_greeks.hpp"
 #include "localvol_smile.hpp"
@@ -52,6 +53,11 @@ static_assert(sizeof(mcamd_localvol_greeks_job) == 24 && sizeof(mcamd_localvol_g
               "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
 static_assert(MCAMD_LOCALVOL_GREEKS_MAX_BUCKETS == mcamd::kLvGreeksMaxBuckets && MCAMD_LOCALVOL_GREEK_RHO_Q + 1 == mcamd::kLvGreeks,
               "the kernel's record holds six estimators and MCAMD_LOCALVOL_GREEKS_MAX_BUCKETS buckets");
+static_assert(sizeof(mcamd_cliquet) == 56 && sizeof(mcamd_cliquet_result) == 96,
+              "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
+static_assert(MCAMD_CLIQUET_SUM == mcamd::kCliquetSum && MCAMD_CLIQUET_COMPOUND == mcamd::kCliquetCompound &&
+                  MCAMD_CLIQUET_VARIANCE == mcamd::kCliquetVariance,
+              "the kernels' kinds are MCAMD_CLIQUET_*");
 static_assert(MCAMD_LOCALVOL_MAX_NODES == mcamd::kLocalVolMaxNodes, "the kernel's LDS budget holds MCAMD_LOCALVOL_MAX_NODES");
 static_assert(MCAMD_AUTOCALL_MAX_DATES == mcamd::kAutocallMaxDates, "the kernel's date tables hold MCAMD_AUTOCALL_MAX_DATES");
 
@@ -854,6 +860,103 @@ int prepare_localvol(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *s
     return drive(DeviceCall{job.n_local, grid, mcamd::kLocalVolRecord, 6, Finish::kFolded,
                             [&](const mcamd::FinishSpec &fs) {
                                 return mcamd::launch_localvol(job, ctx->d_partials, grid, fs, ctx->stream);
+                            }});
+}
+
+// What the cliquet call and its closed form refuse of the kind ...
+int check_cliquet_kind(int kind)
+{
+    if (kind < MCAMD_CLIQUET_SUM || kind > MCAMD_CLIQUET_VARIANCE)
+        return fail(MCAMD_ERR_INVALID, "kind must be MCAMD_CLIQUET_SUM (0), MCAMD_CLIQUET_COMPOUND (1) or "
+                                       "MCAMD_CLIQUET_VARIANCE (2), got %d", kind);
+    return MCAMD_OK;
+}
+
+// ... of the local bounds whatever the kind ...
+int check_cliquet_local(double local_floor, double local_cap)
+{
+    if (std::isnan(local_floor) || std::isnan(local_cap))
+        return fail(MCAMD_ERR_INVALID, "a bound must not be NaN (-inf / +inf: none): local_floor = %g, local_cap = %g",
+                    local_floor, local_cap);
+    if (!(local_floor < local_cap))
+        return fail(MCAMD_ERR_INVALID, "local_floor must lie below local_cap, got %g and %g", local_floor, local_cap);
+    return MCAMD_OK;
+}
+
+// ... and of the local bounds what depends on the kind.
+int check_cliquet_kind_bounds(int kind, double local_floor, double local_cap)
+{
+    if (kind == MCAMD_CLIQUET_COMPOUND && (local_floor < -1.0 || !(local_cap > -1.0)))
+        return fail(MCAMD_ERR_INVALID, "a compounding cliquet needs local_floor >= -1 and local_cap > -1 (a gross return "
+                                       "is positive), got %g and %g", local_floor, local_cap);
+    if (kind == MCAMD_CLIQUET_VARIANCE && (local_floor != -HUGE_VAL || local_cap != HUGE_VAL))
+        return fail(MCAMD_ERR_INVALID, "realized variance takes no local bounds: local_floor must be -inf and local_cap "
+                                       "+inf, got %g and %g", local_floor, local_cap);
+    return MCAMD_OK;
+}
+
+// The cliquet calls: mcamd_price_localvol's paths without a barrier.  The refusals follow prepare_localvol's order: the
+// request alone, then the surface, then the context.  opt->v, opt->K and opt->B are ignored, and S0 is read by nothing.
+template <typename Drive>
+int prepare_cliquet(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_cliquet *cq,
+                    const mcamd_localvol_surface *surface, void *d_samples, Drive drive)
+{
+    if (!opt || !sim || !cq) return fail(MCAMD_ERR_INVALID, "opt, sim, cliquet and surface must be non-NULL");
+    if (int rc = check_cliquet_kind(cq->kind)) return rc;
+    if (cq->reserved != 0) return fail(MCAMD_ERR_INVALID, "cliquet->reserved must be 0, got %d", cq->reserved);
+    if (cq->reset_every == 0 || sim->n_steps % cq->reset_every != 0)
+        return fail(MCAMD_ERR_INVALID, "reset_every must be >= 1 and divide n_steps (reset_every = %u, n_steps = %u)",
+                    cq->reset_every, sim->n_steps);
+    const uint32_t M = sim->n_steps / cq->reset_every;
+    if (M != 0 && (cq->first_period < 1 || cq->first_period > M))   // M == 0 is n_steps == 0, refused below
+        return fail(MCAMD_ERR_INVALID, "first_period must be 1..%u (the periods), got %u", M, cq->first_period);
+    if (std::isnan(cq->global_floor) || std::isnan(cq->global_cap))
+        return fail(MCAMD_ERR_INVALID, "a bound must not be NaN (-inf / +inf: none): global_floor = %g, global_cap = %g",
+                    cq->global_floor, cq->global_cap);
+    if (int rc = check_cliquet_local(cq->local_floor, cq->local_cap)) return rc;
+    if (!(cq->global_floor < cq->global_cap))
+        return fail(MCAMD_ERR_INVALID, "global_floor must lie below global_cap, got %g and %g", cq->global_floor,
+                    cq->global_cap);
+    if (int rc = check_cliquet_kind_bounds(cq->kind, cq->local_floor, cq->local_cap)) return rc;
+    if (!std::isfinite(cq->q)) return fail(MCAMD_ERR_INVALID, "the dividend yield q must be finite, got %g", cq->q);
+    if (!std::isfinite(opt->r)) return fail(MCAMD_ERR_INVALID, "option parameters must be finite with T > 0");
+    const double mu = opt->r - cq->q;
+    // as prepare_localvol, on a copy that carries no spot, strike or barrier of its own either
+    mcamd_option seen = *opt;
+    seen.S0 = 1.0;
+    seen.K = seen.B = 0.0;
+    if (int rc = check_localvol_request("cliquet", seen, sim, &mu, 1)) return rc;
+    if (!surface) return fail(MCAMD_ERR_INVALID, "opt, sim, cliquet and surface must be non-NULL");
+    const double dt = opt->T / static_cast<double>(sim->n_steps);
+    if (sim->precision == MCAMD_F64)
+        if (int rc = check_localvol_exponent_range(mu, surface->sigma_max, dt, sim->n_steps)) return rc;
+    if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
+    if (!surface_belongs(surface, ctx)) return fail(MCAMD_ERR_INVALID, "the surface was created on another context");
+    if (sim->n_paths_local == 0) return drive(empty_call());
+    mcamd::CliquetJob job;
+    job.seed = sim->seed;
+    job.path_offset = sim->path_offset;
+    job.n_local = sim->n_paths_local;
+    job.n_steps = sim->n_steps;
+    job.precision = sim->precision;
+    job.kind = cq->kind;
+    job.reset_every = cq->reset_every;
+    job.first_period = cq->first_period;
+    job.mu = mu;
+    job.dt = dt;
+    const bool compound = cq->kind == MCAMD_CLIQUET_COMPOUND;
+    job.local_lo = compound ? std::log(1.0 + cq->local_floor) : cq->local_floor;
+    job.local_hi = compound ? std::log(1.0 + cq->local_cap) : cq->local_cap;
+    job.global_lo = cq->global_floor;
+    job.global_hi = cq->global_cap;
+    const double P = static_cast<double>(M - cq->first_period + 1);
+    job.scale = 1.0 / (P * (static_cast<double>(cq->reset_every) * dt));
+    job.surface = job_surface(surface, sim->precision);
+    job.d_samples = d_samples;
+    const uint32_t grid = mcamd::one_path_per_thread_grid(job.n_local);
+    return drive(DeviceCall{job.n_local, grid, mcamd::kCliquetRecord, 6, Finish::kFolded,
+                            [&](const mcamd::FinishSpec &fs) {
+                                return mcamd::launch_cliquet(job, ctx->d_partials, grid, fs, ctx->stream);
                             }});
 }
 
@@ -2561,6 +2664,84 @@ int mcamd_price_localvol_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const 
 {
     return prepare_localvol(ctx, opt, sim, localvol, surface, d_samples,
                             [&](const auto &call) { return run_enqueue(ctx, call, d_stats); });
+}
+
+int mcamd_price_cliquet(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_cliquet *cliquet,
+                        const mcamd_localvol_surface *surface, void *d_samples, mcamd_cliquet_result *res)
+{
+    if (!res) return fail(MCAMD_ERR_INVALID, "opt, sim, cliquet, surface and res must be non-NULL");
+    std::memset(res, 0, sizeof *res);
+    return prepare_cliquet(ctx, opt, sim, cliquet, surface, d_samples, [&](const auto &call) {
+        return run_sync(ctx, call, res, [&](const double *rec) {
+            // {sum, sumsq, paths on the global floor, paths on the global cap, wave-steps}
+            const Estimate e = estimate(rec[0], rec[1], sim->n_paths_local, std::exp(-opt->r * opt->T));
+            res->sum = rec[0];
+            res->sumsq = rec[1];
+            res->n = sim->n_paths_local;
+            res->price = e.value;
+            res->std_err = e.std_err;
+            set_ci(res);
+            res->n_floored = static_cast<uint64_t>(std::llround(rec[2]));
+            res->n_capped = static_cast<uint64_t>(std::llround(rec[3]));
+            res->work_steps = 64.0 * rec[4];   // wave-steps x 64 lanes
+        });
+    });
+}
+
+int mcamd_price_cliquet_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                                const mcamd_cliquet *cliquet, const mcamd_localvol_surface *surface, void *d_samples,
+                                double *d_stats)
+{
+    return prepare_cliquet(ctx, opt, sim, cliquet, surface, d_samples,
+                           [&](const auto &call) { return run_enqueue(ctx, call, d_stats); });
+}
+
+// Volatility in time only: the period log-returns D_p ~ N((r - q - v_p^2 / 2) tau, v_p^2 tau) are independent, so the
+// mean of a sum of clipped returns is the sum of the means and that of their product the product.  A return clipped to
+// [F, C] is (1 + F) + (e^D - (1 + F))+ - (e^D - (1 + C))+ gross: two calls on e^D.
+int mcamd_cliquet_price_f64(int kind, double T, double r, double q, uint32_t n_periods, uint32_t first_period,
+                            const double *period_vol, double local_floor, double local_cap, double *price)
+{
+    if (!price) return fail(MCAMD_ERR_INVALID, "price is NULL");
+    *price = 0.0;
+    if (!period_vol) return fail(MCAMD_ERR_INVALID, "period_vol is NULL");
+    if (int rc = check_cliquet_kind(kind)) return rc;
+    if (int rc = check_cliquet_local(local_floor, local_cap)) return rc;
+    if (int rc = check_cliquet_kind_bounds(kind, local_floor, local_cap)) return rc;
+    if (!(T > 0.0) || !std::isfinite(T) || !std::isfinite(r) || !std::isfinite(q))
+        return fail(MCAMD_ERR_INVALID, "the cliquet closed form needs a finite T > 0 and finite r and q");
+    if (n_periods == 0 || first_period < 1 || first_period > n_periods)
+        return fail(MCAMD_ERR_INVALID, "n_periods must be >= 1 and first_period 1..n_periods, got %u and %u", n_periods,
+                    first_period);
+    for (uint32_t p = 0; p < n_periods; ++p)
+        if (!std::isfinite(period_vol[p]) || !(period_vol[p] > 0.0))
+            return fail(MCAMD_ERR_INVALID, "every period volatility must be finite and > 0: period_vol[%u] = %g", p,
+                        period_vol[p]);
+    const auto N = [](double x) { return 0.5 * std::erfc(-x / std::sqrt(2.0)); };
+    const double tau = T / static_cast<double>(n_periods), fwd = std::exp((r - q) * tau);
+    const double F = std::fmax(local_floor, -1.0);   // a floor at or below -1 never binds
+    double sum = 0.0, prod = 1.0;
+    for (uint32_t p = first_period; p <= n_periods; ++p) {
+        const double v = period_vol[p - 1], s = v * std::sqrt(tau);
+        const auto call = [&](double k) {   // E[(e^D - k)+]
+            if (k <= 0.0) return fwd - k;
+            if (k == HUGE_VAL) return 0.0;
+            const double d1 = ((r - q + 0.5 * v * v) * tau - std::log(k)) / s;
+            return fwd * N(d1) - k * N(d1 - s);
+        };
+        if (kind == MCAMD_CLIQUET_VARIANCE) {
+            const double mean = (r - q - 0.5 * v * v) * tau;
+            sum += v * v * tau + mean * mean;
+        } else {
+            const double E = (1.0 + F) + call(1.0 + F) - call(1.0 + local_cap);
+            sum += E - 1.0;
+            prod *= E;
+        }
+    }
+    const double P = static_cast<double>(n_periods - first_period + 1);
+    const double value = kind == MCAMD_CLIQUET_SUM ? sum : kind == MCAMD_CLIQUET_COMPOUND ? prod - 1.0 : sum / (P * tau);
+    *price = std::exp(-r * T) * value;
+    return MCAMD_OK;
 }
 
 int mcamd_price_localvol_greeks(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,

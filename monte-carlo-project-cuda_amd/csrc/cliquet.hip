@@ -1,0 +1,164 @@
+// cliquet.hip — cliquets, forward-start options and realized-variance swaps under a local-volatility surface, for gfx950
+// (both path precisions).
+//
+// Definitions (include/mcamd.h, mcamd_price_cliquet): the path is mcamd_price_localvol's, X_i = ln(S_i / S0) in
+// NATURAL-log units, walked by localvol_device.hpp's lookup, row carry and move on the normals of localvol.hip (one per
+// step, whole Philox blocks, the remainder block as there).  Reset date p = 1..M falls on the end of step p reset_every;
+// D_p = X at date p minus X at date p - 1.  What a counted period (p >= first_period) adds depends on KIND:
+//   SUM       c_p = min(max(e^{D_p} - 1, lo), hi), A = sum c_p: one exponential per counted period;
+//   COMPOUND  l_p = min(max(D_p, ln(1 + lo)), ln(1 + hi)), L = sum l_p, A = e^L - 1: one exponential per path, at the end;
+//   VARIANCE  V = fma(D_p, D_p, V), A = V / (P tau): no exponential at all.
+// y = min(max(A, global floor), global cap) in fp64.
+//
+// KIND is a template parameter, so the exponential exists in the SUM loop only.  The step index is wave-uniform: the
+// reset test is a scalar compare of the step with the step of the next reset, the period counter and "does this period
+// count" are scalars, and no lane divides or takes a remainder (autocall.hip's date counter).  A reset may fall on any
+// step of a Philox block (reset_every may be 1, odd, or larger than a block), so the test sits in the step, not at the
+// block ends.  There is no early exit: every wavefront runs every step.
+#include "cliquet.hpp"
+#include "localvol_device.hpp"
+
+namespace mcamd {
+
+template <typename T>
+struct CliquetArgs {
+    LvSurface<T> surf;
+    T mu_dt, half_dt, sqrt_dt;
+    T exp_scale;              // exponent units per natural-log unit (log2 e in fp32, 65536 / ln 2 in fp64)
+    T lo, hi;                 // the local bounds: of R_p (SUM), of D_p (COMPOUND: ln(1 + bound)); unread by VARIANCE
+    double g_lo, g_hi;        // the global bounds of A; -inf / +inf: none
+    double scale;             // VARIANCE: 1 / (P tau)
+    uint32_t n_steps, reset_every, first_period;
+    uint64_t seed;
+    uint64_t path_offset;
+    uint64_t n_local;
+    T *samples;               // nullable
+    GridFinish fin;
+};
+
+template <typename T, int KIND>
+__global__ __launch_bounds__(kBlock) void cliquet_kernel(CliquetArgs<T> a, double *__restrict__ partials)
+{
+    constexpr int NB = Normals<T>::kPerBlock;
+    VolPair<T> *tab = reinterpret_cast<VolPair<T> *>(lv_table_lds);
+    lv_copy_table(tab, 0, a.surf.table, a.surf.rows.n_entries);
+    __syncthreads();
+    const MathCtx<T> m = MathCtx<T>::init();
+    const PhiloxKeys key = PhiloxKeys::make(a.seed);
+    const LvAxis<T> axis = lv_resident(a.surf.axis);
+    const T mu_dt = lv_resident(a.mu_dt), half_dt = lv_resident(a.half_dt), sqrt_dt = lv_resident(a.sqrt_dt);
+    const T lo = lv_resident(a.lo), hi = lv_resident(a.hi), exp_scale = lv_resident(a.exp_scale);
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
+    const uint32_t n_full = a.n_steps / NB;
+    const uint32_t rem = a.n_steps - n_full * NB;
+    // an infinite bound never binds and counts nothing, whatever the arithmetic made of A
+    const bool has_floor = a.g_lo > -__builtin_huge_val(), has_cap = a.g_hi < __builtin_huge_val();
+    double acc5[kCliquetRecord] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < a.n_local; i += stride) {
+        const uint64_t subsequence = a.path_offset + i;
+        T X = T(0);          // ln(S / S0), natural units
+        T X_reset = T(0);    // X at the last reset date
+        T sum = T(0);        // sum c_p (SUM), sum l_p (COMPOUND), sum D_p^2 (VARIANCE)
+        uint32_t p = 0;                         // reset dates behind the wavefront
+        uint32_t next_reset = a.reset_every;    // the step that ends on date p + 1
+        LvRow row{0, 0};
+        Normals<T> nz;
+        // step `index` (wave-uniform) with the normal z
+        auto step = [&](T z, uint32_t index) {
+            const T s = lv_sigma(X, axis, a.surf.rows, tab, row);
+            lv_move(X, s, z, sqrt_dt, half_dt, mu_dt);
+            if (index + 1 == next_reset) {   // a scalar compare
+                const T D = X - X_reset;
+                X_reset = X;
+                if (p + 1 >= a.first_period) {
+                    if (KIND == kCliquetSum) {
+                        const T R = exp_of_logreturn(T(1), D * exp_scale, m) - T(1);
+                        sum += lv_min(lv_max(R, lo), hi);
+                    } else if (KIND == kCliquetCompound) {
+                        sum += lv_min(lv_max(D, lo), hi);
+                    } else {
+                        sum = fma_t(D, D, sum);
+                    }
+                }
+                ++p;
+                next_reset += a.reset_every;
+            }
+        };
+        for (uint32_t kb = 0; kb < n_full; ++kb) {
+            nz.fill(m, key, subsequence, kb);
+#pragma unroll
+            for (int j = 0; j < NB; ++j) step(nz.z[j], kb * NB + j);
+        }
+        if (rem) {
+            nz.fill(m, key, subsequence, n_full);
+#pragma unroll
+            for (int j = 0; j < NB - 1; ++j)
+                if (static_cast<uint32_t>(j) < rem) step(nz.z[j], n_full * NB + j);
+        }
+        double A;
+        if (KIND == kCliquetSum) A = static_cast<double>(sum);
+        else if (KIND == kCliquetCompound) A = static_cast<double>(exp_of_logreturn(T(1), sum * exp_scale, m)) - 1.0;
+        else A = static_cast<double>(sum) * a.scale;
+        const double y = __builtin_fmin(__builtin_fmax(A, a.g_lo), a.g_hi);
+        if (a.samples) a.samples[i] = static_cast<T>(y);
+        acc5[0] += y;
+        acc5[1] = __builtin_fma(y, y, acc5[1]);
+        acc5[2] += (has_floor && A <= a.g_lo) ? 1.0 : 0.0;
+        acc5[3] += (has_cap && A >= a.g_hi) ? 1.0 : 0.0;
+        // a wavefront's active lanes are a prefix (path ids grow with the lane): lane 0 counts the wavefront's steps
+        if ((threadIdx.x & (kWave - 1)) == 0) acc5[4] += static_cast<double>(a.n_steps);
+    }
+    if (a.fin.n_value >= 0.0) acc5[4] = 0.0;   // the 6-double statistics layout has no slot for the step counter
+    block_sumN<kBlock, kCliquetRecord>(acc5);
+    grid_finish<kBlock, kCliquetRecord>(acc5, partials, a.fin);
+}
+
+template <typename T, int KIND>
+static void launch_cliquet_k(const CliquetArgs<T> &a, double *d_partials, uint32_t grid, hipStream_t stream)
+{
+    const size_t lds_bytes = static_cast<size_t>(a.surf.rows.n_entries) * sizeof(VolPair<T>);
+    hipLaunchKernelGGL((cliquet_kernel<T, KIND>), dim3(grid), dim3(kBlock), lds_bytes, stream, a, d_partials);
+}
+
+template <typename T>
+static hipError_t launch_cliquet_t(const CliquetJob &j, double *d_partials, uint32_t grid, const FinishSpec &fs,
+                                   hipStream_t stream)
+{
+    CliquetArgs<T> a;
+    a.surf = lv_surface<T>(j.surface, j.n_steps);
+    a.mu_dt = static_cast<T>(j.mu * j.dt);
+    a.half_dt = static_cast<T>(0.5 * j.dt);
+    a.sqrt_dt = static_cast<T>(std::sqrt(j.dt));
+    a.exp_scale = lv_exp_scale<T>();
+    a.lo = static_cast<T>(j.local_lo);
+    a.hi = static_cast<T>(j.local_hi);
+    a.g_lo = j.global_lo;
+    a.g_hi = j.global_hi;
+    a.scale = j.scale;
+    a.n_steps = j.n_steps;
+    a.reset_every = j.reset_every;
+    a.first_period = j.first_period;
+    a.seed = j.seed;
+    a.path_offset = j.path_offset;
+    a.n_local = j.n_local;
+    a.samples = static_cast<T *>(j.d_samples);
+    a.fin = GridFinish{fs.out, fs.ticket, fs.n_value};
+    if (j.kind == kCliquetSum) launch_cliquet_k<T, kCliquetSum>(a, d_partials, grid, stream);
+    else if (j.kind == kCliquetCompound) launch_cliquet_k<T, kCliquetCompound>(a, d_partials, grid, stream);
+    else launch_cliquet_k<T, kCliquetVariance>(a, d_partials, grid, stream);
+    return hipGetLastError();
+}
+
+hipError_t launch_cliquet(const CliquetJob &job, double *d_partials, uint32_t grid, const FinishSpec &finish,
+                          hipStream_t stream)
+{
+    if (!finish_ok(finish, grid)) return hipErrorInvalidValue;
+    if (!lv_grid_ok(job.surface, job.n_steps)) return hipErrorInvalidValue;
+    if (job.kind < kCliquetSum || job.kind > kCliquetVariance || job.reset_every == 0 ||
+        job.n_steps % job.reset_every != 0 || job.first_period == 0 || job.first_period > job.n_steps / job.reset_every)
+        return hipErrorInvalidValue;
+    return job.precision == 32 ? launch_cliquet_t<float>(job, d_partials, grid, finish, stream)
+                               : launch_cliquet_t<double>(job, d_partials, grid, finish, stream);
+}
+
+}  // namespace mcamd
