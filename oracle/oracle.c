@@ -107,6 +107,20 @@ void oracle_generate_normals_f64(uint64_t seed, uint64_t n, double *out)
     }
 }
 
+/* The per-path streams of the engine in bulk: row s holds blocks 0 .. n_blocks - 1 of subsequence first + s, each by
+ * the per-block call above (tests/window_restate.py draws a few hundred thousand blocks per nested-MC case). */
+void oracle_normals_of_subsequences_f32(uint64_t seed, uint64_t first, uint64_t n_subsequences, uint64_t n_blocks, float *out)
+{
+    for (uint64_t s = 0; s < n_subsequences; ++s)
+        for (uint64_t b = 0; b < n_blocks; ++b) oracle_normal4_f32(seed, first + s, b, out + 4 * (s * n_blocks + b));
+}
+
+void oracle_normals_of_subsequences_f64(uint64_t seed, uint64_t first, uint64_t n_subsequences, uint64_t n_blocks, double *out)
+{
+    for (uint64_t s = 0; s < n_subsequences; ++s)
+        for (uint64_t b = 0; b < n_blocks; ++b) oracle_normal2_f64(seed, first + s, b, out + 2 * (s * n_blocks + b));
+}
+
 /* ------------------------------------------------------------------ */
 /* Closed form                                                         */
 /* ------------------------------------------------------------------ */

@@ -58,6 +58,10 @@ void oracle_normal2_f64(uint64_t seed, uint64_t subsequence, uint64_t block, dou
 /* bulk fill: out[i] = i-th normal of the stream (subsequence = i / per_block... see .c) */
 void oracle_generate_normals_f32(uint64_t seed, uint64_t n, float *out);
 void oracle_generate_normals_f64(uint64_t seed, uint64_t n, double *out);
+/* blocks 0 .. n_blocks - 1 of n_subsequences consecutive subsequences, row-major:
+ * out[s * n_blocks * per_block + b * per_block + j] = normal j of block b of subsequence first + s (per_block = 4 / 2) */
+void oracle_normals_of_subsequences_f32(uint64_t seed, uint64_t first, uint64_t n_subsequences, uint64_t n_blocks, float *out);
+void oracle_normals_of_subsequences_f64(uint64_t seed, uint64_t first, uint64_t n_subsequences, uint64_t n_blocks, double *out);
 
 /* ---- closed form (inc/BlackandScholes.hpp) ---- */
 float oracle_cnd_f32(float x);                                        /* :8-30  */

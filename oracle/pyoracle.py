@@ -73,6 +73,10 @@ def lib() -> C.CDLL:
         L.oracle_normal2_f64.argtypes = [u64, u64, u64, pf64]
         L.oracle_generate_normals_f32.argtypes = [u64, u64, pf32]
         L.oracle_generate_normals_f64.argtypes = [u64, u64, pf64]
+        L.oracle_normals_of_subsequences_f32.argtypes = [u64, u64, u64, u64, pf32]
+        L.oracle_normals_of_subsequences_f32.restype = None
+        L.oracle_normals_of_subsequences_f64.argtypes = [u64, u64, u64, u64, pf64]
+        L.oracle_normals_of_subsequences_f64.restype = None
         L.oracle_cnd_f32.argtypes = [f32]
         L.oracle_cnd_f32.restype = f32
         L.oracle_bs_call_f32.argtypes = [f32] * 5
@@ -130,6 +134,18 @@ def generate_normals(seed: int, n: int, precision: int = 32) -> np.ndarray:
     else:
         out = np.zeros(n, dtype=np.float64)
         lib().oracle_generate_normals_f64(seed, n, _p(out, C.c_double))
+    return out
+
+
+def normals_of_subsequences(seed: int, first: int, n_subsequences: int, n_blocks: int, precision: int = 32) -> np.ndarray:
+    """[n_subsequences, n_blocks * per_block]: blocks 0 .. n_blocks - 1 of the subsequences first, first + 1, ..,
+    each as normal4_f32 / normal2_f64 returns it (float32 / float64)."""
+    if precision == 32:
+        out = np.zeros((n_subsequences, 4 * n_blocks), dtype=np.float32)
+        lib().oracle_normals_of_subsequences_f32(seed, first, n_subsequences, n_blocks, _p(out, C.c_float))
+    else:
+        out = np.zeros((n_subsequences, 2 * n_blocks), dtype=np.float64)
+        lib().oracle_normals_of_subsequences_f64(seed, first, n_subsequences, n_blocks, _p(out, C.c_double))
     return out
 
 
