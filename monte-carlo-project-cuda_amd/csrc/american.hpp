@@ -1,4 +1,4 @@
-// american.hpp — host-side interface of the least-squares Monte Carlo kernels (american.hip) for the C ABI (capi.cpp).
+// american.hpp — host-side interface of the least-squares Monte Carlo kernels (american.hip) for the C ABI (capi_american.cpp).
 //
 // Training: the trajectory store (launch_store, step-major) and then M launches of the backward sweep on the context's
 // stream, with no host synchronisation in between.  Launch j (j = M-1 .. 0) solves date j+1's normal equations from

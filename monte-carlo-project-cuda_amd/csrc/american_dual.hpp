@@ -1,5 +1,5 @@
 // american_dual.hpp — host-side interface of the Andersen-Broadie dual (upper) bound kernels (american_dual.hip) for the
-// C ABI (capi.cpp).
+// C ABI (capi_american.cpp).
 //
 // The shard's outer paths are stored by launch_store (step-major, product form).  The continuation kernel then prices
 // every point (p, j), j = 0..M-1, by n_inner paths that follow the fitted rule from S_{p,j} on, and the scan kernel

@@ -1,4 +1,4 @@
-// asian.hpp — host-side interface of the Asian (average-rate) kernels (asian.hip) for the C ABI (capi.cpp).
+// asian.hpp — host-side interface of the Asian (average-rate) kernels (asian.hip) for the C ABI (capi_pathdep.cpp).
 //
 // An Asian kernel walks the paths of mcamd_price_paths (same Philox stream = global path id, same Exponents) and keeps
 // what the average needs (include/mcamd.h, mcamd_price_asian): for the arithmetic average the running price in the

@@ -1,4 +1,4 @@
-// autocall.hpp — host-side interface of the worst-of autocallable kernels (autocall.hip) for the C ABI (capi.cpp).
+// autocall.hpp — host-side interface of the worst-of autocallable kernels (autocall.hip) for the C ABI (capi_multi.cpp).
 //
 // An autocall kernel steps d correlated log-performances per path exactly as a basket kernel does (include/mcamd.h,
 // mcamd_price_autocall: same Philox subsequence = the GLOBAL path id, same blocks and slots, same chain of fused

@@ -1,5 +1,5 @@
 // autocall_localvol.hpp — host-side interface of the worst-of autocallable kernels under per-asset local-volatility
-// surfaces (autocall_localvol.hip, autocall_localvol_f32.hip) for the C ABI (capi.cpp).
+// surfaces (autocall_localvol.hip, autocall_localvol_f32.hip) for the C ABI (capi_localvol.cpp).
 //
 // A kernel steps d correlated log-performances per path (include/mcamd.h, mcamd_price_autocall_localvol): asset j looks
 // its volatility up at its own X_j in its own surface table, exactly as a local-volatility kernel does, and moves by the

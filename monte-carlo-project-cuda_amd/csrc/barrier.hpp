@@ -1,4 +1,4 @@
-// barrier.hpp — host-side interface of the single-barrier kernels (barrier.hip) for the C ABI (capi.cpp).
+// barrier.hpp — host-side interface of the single-barrier kernels (barrier.hip) for the C ABI (capi_pathdep.cpp).
 //
 // A barrier kernel walks the log-space paths of mcamd_price_paths (same Philox stream = global path id, same
 // Exponents), keeps each path's survival weight w (include/mcamd.h, mcamd_price_barrier) and forms one undiscounted

@@ -1,4 +1,4 @@
-// basket.hpp — host-side interface of the multi-asset kernels (basket.hip) for the C ABI (capi.cpp).
+// basket.hpp — host-side interface of the multi-asset kernels (basket.hip) for the C ABI (capi_multi.cpp).
 //
 // A basket kernel steps d correlated log-prices per path (include/mcamd.h, mcamd_price_basket): step i of asset j is
 // x_j = drift_j + sum_{k <= j} coef_jk z_{i,k}, a chain of fused multiply-adds in ascending k that starts from the

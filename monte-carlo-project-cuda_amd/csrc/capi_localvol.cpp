@@ -1,0 +1,747 @@
+// capi_localvol.cpp — the calls of the C ABI that walk a local-volatility surface: the surface itself, European and
+// barrier options, cliquets and variance swaps, Greeks by tangent paths, the strike-by-expiry smile and the worst-of
+// autocallable on per-asset surfaces.  Each call is a prepare_* step (the refusals and the job) and its synchronous
+// and enqueue forms; the refusals keep one order: the request alone, then the surface, then the context.
+#include "capi_internal.hpp"
+#include "autocall_localvol.hpp"
+#include "cliquet.hpp"
+#include "localvol.hpp"
+#include "localvol_greeks.hpp"
+#include "localvol_smile.hpp"
+
+#include <algorithm>
+#include <vector>
+
+static_assert(sizeof(mcamd_localvol_grid) == 24 && sizeof(mcamd_localvol) == 24,
+              "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
+static_assert(MCAMD_LOCALVOL_MAX_NODES == mcamd::kLocalVolMaxNodes, "the kernel's LDS budget holds MCAMD_LOCALVOL_MAX_NODES");
+static_assert(sizeof(mcamd_cliquet) == 56 && sizeof(mcamd_cliquet_result) == 96,
+              "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
+static_assert(MCAMD_CLIQUET_SUM == mcamd::kCliquetSum && MCAMD_CLIQUET_COMPOUND == mcamd::kCliquetCompound &&
+                  MCAMD_CLIQUET_VARIANCE == mcamd::kCliquetVariance,
+              "the kernels' kinds are MCAMD_CLIQUET_*");
+static_assert(sizeof(mcamd_localvol_greeks_job) == 24 && sizeof(mcamd_localvol_greeks) == 472,
+              "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
+static_assert(MCAMD_LOCALVOL_GREEKS_MAX_BUCKETS == mcamd::kLvGreeksMaxBuckets && MCAMD_LOCALVOL_GREEK_RHO_Q + 1 == mcamd::kLvGreeks,
+              "the kernel's record holds six estimators and MCAMD_LOCALVOL_GREEKS_MAX_BUCKETS buckets");
+static_assert(sizeof(mcamd_smile) == 24, "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
+static_assert(MCAMD_SMILE_MAX_STRIKES == mcamd::kSmileMaxStrikes && MCAMD_SMILE_MAX_EXPIRIES == mcamd::kSmileMaxExpiries,
+              "the smile kernel takes one strike per lane and MCAMD_SMILE_MAX_EXPIRIES expiry steps");
+static_assert(sizeof(mcamd_autocall_localvol) == 632, "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
+
+using namespace mcamd::capi;
+
+namespace mcamd::capi {
+
+// What mcamd_localvol_surface_create and the host lookup refuse of a grid and its table; *sigma_max (nullable) receives
+// the largest entry.
+int check_localvol_grid(const mcamd_localvol_grid *grid, const double *h_sigma, double *sigma_max)
+{
+    if (!grid || !h_sigma) return fail(MCAMD_ERR_INVALID, "grid and h_sigma must be non-NULL");
+    if (grid->n_t < 1 || grid->n_x < 2)
+        return fail(MCAMD_ERR_INVALID, "a surface needs n_t >= 1 and n_x >= 2, got n_t = %u, n_x = %u", grid->n_t, grid->n_x);
+    if (static_cast<uint64_t>(grid->n_t) * grid->n_x > MCAMD_LOCALVOL_MAX_NODES)
+        return fail(MCAMD_ERR_INVALID, "n_t * n_x = %llu nodes; at most %d fit the kernel's LDS table",
+                    static_cast<unsigned long long>(static_cast<uint64_t>(grid->n_t) * grid->n_x), MCAMD_LOCALVOL_MAX_NODES);
+    if (!std::isfinite(grid->x_min) || !std::isfinite(grid->x_max) || !(grid->x_min < grid->x_max))
+        return fail(MCAMD_ERR_INVALID, "the surface's axis needs finite x_min < x_max, got [%g, %g]", grid->x_min,
+                    grid->x_max);
+    double top = 0.0;
+    const uint32_t n = grid->n_t * grid->n_x;
+    for (uint32_t e = 0; e < n; ++e) {
+        if (!std::isfinite(h_sigma[e]) || !(h_sigma[e] > 0.0))
+            return fail(MCAMD_ERR_INVALID, "every surface entry must be finite and > 0: sigma[%u][%u] = %g", e / grid->n_x,
+                        e % grid->n_x, h_sigma[e]);
+        top = std::fmax(top, h_sigma[e]);
+    }
+    if (sigma_max) *sigma_max = top;
+    return MCAMD_OK;
+}
+
+// What the cliquet call and its closed form refuse of the kind ...
+int check_cliquet_kind(int kind)
+{
+    if (kind < MCAMD_CLIQUET_SUM || kind > MCAMD_CLIQUET_VARIANCE)
+        return fail(MCAMD_ERR_INVALID, "kind must be MCAMD_CLIQUET_SUM (0), MCAMD_CLIQUET_COMPOUND (1) or "
+                                       "MCAMD_CLIQUET_VARIANCE (2), got %d", kind);
+    return MCAMD_OK;
+}
+
+// ... of the local bounds whatever the kind ...
+int check_cliquet_local(double local_floor, double local_cap)
+{
+    if (std::isnan(local_floor) || std::isnan(local_cap))
+        return fail(MCAMD_ERR_INVALID, "a bound must not be NaN (-inf / +inf: none): local_floor = %g, local_cap = %g",
+                    local_floor, local_cap);
+    if (!(local_floor < local_cap))
+        return fail(MCAMD_ERR_INVALID, "local_floor must lie below local_cap, got %g and %g", local_floor, local_cap);
+    return MCAMD_OK;
+}
+
+// ... and of the local bounds what depends on the kind.
+int check_cliquet_kind_bounds(int kind, double local_floor, double local_cap)
+{
+    if (kind == MCAMD_CLIQUET_COMPOUND && (local_floor < -1.0 || !(local_cap > -1.0)))
+        return fail(MCAMD_ERR_INVALID, "a compounding cliquet needs local_floor >= -1 and local_cap > -1 (a gross return "
+                                       "is positive), got %g and %g", local_floor, local_cap);
+    if (kind == MCAMD_CLIQUET_VARIANCE && (local_floor != -HUGE_VAL || local_cap != HUGE_VAL))
+        return fail(MCAMD_ERR_INVALID, "realized variance takes no local bounds: local_floor must be -inf and local_cap "
+                                       "+inf, got %g and %g", local_floor, local_cap);
+    return MCAMD_OK;
+}
+
+void finalize_localvol_greeks_into(const double stats[32], double r, double T, uint32_t n_buckets, int gamma_defined,
+                                   mcamd_localvol_greeks *out)
+{
+    const double disc = std::exp(-r * T);
+    const uint64_t n = static_cast<uint64_t>(std::llround(stats[kLvGreeksRecord]));
+    out->n = n;
+    for (int k = 0; k < kLvGreeks; ++k) {
+        const Estimate e = estimate(stats[2 * k], stats[2 * k + 1], n, disc);
+        out->sum[k] = stats[2 * k];
+        out->sumsq[k] = stats[2 * k + 1];
+        out->value[k] = e.value;
+        out->std_err[k] = e.std_err;
+    }
+    if (!gamma_defined) {
+        out->value[MCAMD_LOCALVOL_GREEK_GAMMA] = out->std_err[MCAMD_LOCALVOL_GREEK_GAMMA] = std::nan("");
+        out->sum[MCAMD_LOCALVOL_GREEK_GAMMA] = out->sumsq[MCAMD_LOCALVOL_GREEK_GAMMA] = 0.0;
+    }
+    for (uint32_t b = 0; b < n_buckets; ++b) {
+        const double *pair = stats + 2 * (kLvGreeks + b);
+        const Estimate e = estimate(pair[0], pair[1], n, disc);
+        out->bucket_sum[b] = pair[0];
+        out->bucket_sumsq[b] = pair[1];
+        out->bucket_value[b] = e.value;
+        out->bucket_std_err[b] = e.std_err;
+    }
+}
+
+void finalize_smile_into(const double *stats, uint64_t n, double r, double T, uint32_t n_steps, uint32_t n_e, uint32_t n_K,
+                         const uint32_t *expiry_steps, double *price, double *std_err)
+{
+    const uint32_t nodes = n_e * n_K;
+    const double dt = T / static_cast<double>(n_steps);
+    for (uint32_t m = 0; m < n_e; ++m) {
+        const double disc = std::exp(-r * (static_cast<double>(expiry_steps[m]) * dt));
+        for (uint32_t k = 0; k < n_K; ++k) {
+            const Estimate e = estimate(stats[m * n_K + k], stats[nodes + m * n_K + k], n, disc);
+            if (price) price[m * n_K + k] = e.value;
+            if (std_err) std_err[m * n_K + k] = e.std_err;
+        }
+    }
+}
+
+}  // namespace mcamd::capi
+
+namespace {
+
+// What the local-volatility calls (name: how the messages call the product) refuse of the option, the flags and sim
+// through the checks shared with the other calls.  seen: the caller's copy of the option with every field it does not
+// read made harmless; it carries no volatility of its own, so check_spot_start sees v = 1 and check_request v = 0,
+// which leaves each drift mu[j] = r - q_j alone in the fp64 exponent-range bound.
+int check_localvol_request(const char *name, mcamd_option seen, const mcamd_sim *sim, const double *mu, int n_mu)
+{
+    seen.v = 1.0;
+    if (int rc = check_spot_start(name, false, &seen, sim)) return rc;
+    seen.v = 0.0;
+    for (int j = 0; j < n_mu; ++j) {
+        seen.r = mu[j];
+        if (int rc = check_request(&seen, sim)) return rc;
+    }
+    return MCAMD_OK;
+}
+
+// check_request's fp64 bound with the largest drift and volatility any node of a surface can give; asset >= 0 names
+// the asset the surface belongs to; start: the largest |X_0| of the call's walks.
+int check_localvol_exponent_range(double mu, double sigma_max, double dt, uint32_t n_steps, int asset = -1,
+                                  double start = 0.0)
+{
+    const double per_step = (std::fabs(mu) + 0.5 * sigma_max * sigma_max) * dt + 8.6 * sigma_max * std::sqrt(dt);
+    if (per_step < 700.0 && per_step * static_cast<double>(n_steps) + start < 20000.0) return MCAMD_OK;
+    if (asset < 0)
+        return fail(MCAMD_ERR_INVALID,
+                    "fp64 path: |drift| + 8.6 vol = %.3g per step over %u steps exceeds the exponent range "
+                    "(per step < 700, per path < 20000)", per_step, n_steps);
+    return fail(MCAMD_ERR_INVALID,
+                "fp64 path: |drift| + 8.6 vol = %.3g per step over %u steps exceeds the exponent range "
+                "(per step < 700, per path < 20000; asset %d)", per_step, n_steps, asset);
+}
+
+// whether the surface was created on this context (a NULL context owns none)
+bool surface_belongs(const mcamd_localvol_surface *surface, const mcamd_ctx *ctx)
+{
+    return ctx && surface->ctx == ctx && surface->ctx_id == ctx->id;
+}
+
+// the surface as a job of the given path precision carries it
+mcamd::LocalVolGrid job_surface(const mcamd_localvol_surface *surface, int precision)
+{
+    return {surface->grid.n_t, surface->grid.n_x, surface->grid.x_min, surface->grid.x_max,
+            precision == MCAMD_F32 ? surface->d_tab32 : surface->d_tab64};
+}
+
+// The local-volatility calls.  The kernel always finishes its own sum (one_path_per_thread_grid caps the grid); every
+// refusal that depends on the request alone comes before the context is looked at, and all that do not need the
+// surface before the surface is.  opt->v is ignored.
+template <typename Drive>
+int prepare_localvol(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_localvol *lv,
+                     const mcamd_localvol_surface *surface, void *d_samples, Drive drive)
+{
+    if (!opt || !sim || !lv) return fail(MCAMD_ERR_INVALID, "opt, sim, localvol and surface must be non-NULL");
+    if (int rc = check_payoff(lv->payoff)) return rc;
+    if (lv->barrier != MCAMD_LOCALVOL_NO_BARRIER && (lv->barrier < MCAMD_BARRIER_DOWN_OUT || lv->barrier > MCAMD_BARRIER_UP_IN))
+        return fail(MCAMD_ERR_INVALID, "localvol->barrier must be MCAMD_LOCALVOL_NO_BARRIER (-1) or MCAMD_BARRIER_DOWN_OUT (0) "
+                                       ".. MCAMD_BARRIER_UP_IN (3), got %d", lv->barrier);
+    if (lv->monitoring != MCAMD_MONITOR_DISCRETE && lv->monitoring != MCAMD_MONITOR_CONTINUOUS)
+        return fail(MCAMD_ERR_INVALID, "monitoring must be MCAMD_MONITOR_DISCRETE (0) or MCAMD_MONITOR_CONTINUOUS (1), "
+                                       "got %d", lv->monitoring);
+    if (lv->reserved != 0) return fail(MCAMD_ERR_INVALID, "localvol->reserved must be 0, got %d", lv->reserved);
+    if (!std::isfinite(lv->q)) return fail(MCAMD_ERR_INVALID, "the dividend yield q must be finite, got %g", lv->q);
+    const bool barrier = lv->barrier != MCAMD_LOCALVOL_NO_BARRIER;
+    if (barrier) {
+        if (int rc = check_barrier_kind(opt->S0, opt->B, lv->barrier, lv->payoff)) return rc;
+    }
+    if (!std::isfinite(opt->r)) return fail(MCAMD_ERR_INVALID, "option parameters must be finite with T > 0");
+    const double mu = opt->r - lv->q;
+    if (int rc = check_localvol_request("local-volatility", *opt, sim, &mu, 1)) return rc;
+    if (!(opt->S0 > 0.0)) return fail(MCAMD_ERR_INVALID, "local-volatility options need S0 > 0 (S0 = %g)", opt->S0);
+    if (!surface) return fail(MCAMD_ERR_INVALID, "opt, sim, localvol and surface must be non-NULL");
+    const double dt = even_dt(opt, sim);
+    if (sim->precision == MCAMD_F64)
+        if (int rc = check_localvol_exponent_range(mu, surface->sigma_max, dt, sim->n_steps)) return rc;
+    if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
+    if (!surface_belongs(surface, ctx)) return fail(MCAMD_ERR_INVALID, "the surface was created on another context");
+    if (sim->n_paths_local == 0) return drive(empty_call());
+    mcamd::LocalVolJob job;
+    job.seed = sim->seed;
+    job.path_offset = sim->path_offset;
+    job.n_local = sim->n_paths_local;
+    job.n_steps = sim->n_steps;
+    job.precision = sim->precision;
+    job.S0 = opt->S0;
+    job.K = opt->K;
+    job.B = opt->B;
+    job.mu = mu;
+    job.dt = dt;
+    job.barrier = barrier;
+    const BarrierSides sides = barrier_sides(lv->barrier);   // MCAMD_LOCALVOL_NO_BARRIER: neither up nor out
+    job.up = sides.up;
+    job.out = sides.out;
+    job.continuous = barrier && lv->monitoring == MCAMD_MONITOR_CONTINUOUS;
+    job.put = lv->payoff == MCAMD_PAYOFF_PUT;
+    job.surface = job_surface(surface, sim->precision);
+    job.d_samples = d_samples;
+    const uint32_t grid = mcamd::one_path_per_thread_grid(job.n_local);
+    return drive(DeviceCall{job.n_local, grid, mcamd::kLocalVolRecord, 6, Finish::kFolded,
+                            [&](const mcamd::FinishSpec &fs) {
+                                return mcamd::launch_localvol(job, ctx->d_partials, grid, fs, ctx->stream);
+                            }});
+}
+
+// The cliquet calls: mcamd_price_localvol's paths without a barrier.  The refusals follow prepare_localvol's order: the
+// request alone, then the surface, then the context.  opt->v, opt->K and opt->B are ignored, and S0 is read by nothing.
+template <typename Drive>
+int prepare_cliquet(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_cliquet *cq,
+                    const mcamd_localvol_surface *surface, void *d_samples, Drive drive)
+{
+    if (!opt || !sim || !cq) return fail(MCAMD_ERR_INVALID, "opt, sim, cliquet and surface must be non-NULL");
+    if (int rc = check_cliquet_kind(cq->kind)) return rc;
+    if (cq->reserved != 0) return fail(MCAMD_ERR_INVALID, "cliquet->reserved must be 0, got %d", cq->reserved);
+    if (cq->reset_every == 0 || sim->n_steps % cq->reset_every != 0)
+        return fail(MCAMD_ERR_INVALID, "reset_every must be >= 1 and divide n_steps (reset_every = %u, n_steps = %u)",
+                    cq->reset_every, sim->n_steps);
+    const uint32_t M = sim->n_steps / cq->reset_every;
+    if (M != 0 && (cq->first_period < 1 || cq->first_period > M))   // M == 0 is n_steps == 0, refused below
+        return fail(MCAMD_ERR_INVALID, "first_period must be 1..%u (the periods), got %u", M, cq->first_period);
+    if (std::isnan(cq->global_floor) || std::isnan(cq->global_cap))
+        return fail(MCAMD_ERR_INVALID, "a bound must not be NaN (-inf / +inf: none): global_floor = %g, global_cap = %g",
+                    cq->global_floor, cq->global_cap);
+    if (int rc = check_cliquet_local(cq->local_floor, cq->local_cap)) return rc;
+    if (!(cq->global_floor < cq->global_cap))
+        return fail(MCAMD_ERR_INVALID, "global_floor must lie below global_cap, got %g and %g", cq->global_floor,
+                    cq->global_cap);
+    if (int rc = check_cliquet_kind_bounds(cq->kind, cq->local_floor, cq->local_cap)) return rc;
+    if (!std::isfinite(cq->q)) return fail(MCAMD_ERR_INVALID, "the dividend yield q must be finite, got %g", cq->q);
+    if (!std::isfinite(opt->r)) return fail(MCAMD_ERR_INVALID, "option parameters must be finite with T > 0");
+    const double mu = opt->r - cq->q;
+    // as prepare_localvol, on a copy that carries no spot, strike or barrier of its own either
+    mcamd_option seen = *opt;
+    seen.S0 = 1.0;
+    seen.K = seen.B = 0.0;
+    if (int rc = check_localvol_request("cliquet", seen, sim, &mu, 1)) return rc;
+    if (!surface) return fail(MCAMD_ERR_INVALID, "opt, sim, cliquet and surface must be non-NULL");
+    const double dt = even_dt(opt, sim);
+    if (sim->precision == MCAMD_F64)
+        if (int rc = check_localvol_exponent_range(mu, surface->sigma_max, dt, sim->n_steps)) return rc;
+    if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
+    if (!surface_belongs(surface, ctx)) return fail(MCAMD_ERR_INVALID, "the surface was created on another context");
+    if (sim->n_paths_local == 0) return drive(empty_call());
+    mcamd::CliquetJob job;
+    job.seed = sim->seed;
+    job.path_offset = sim->path_offset;
+    job.n_local = sim->n_paths_local;
+    job.n_steps = sim->n_steps;
+    job.precision = sim->precision;
+    job.kind = cq->kind;
+    job.reset_every = cq->reset_every;
+    job.first_period = cq->first_period;
+    job.mu = mu;
+    job.dt = dt;
+    const bool compound = cq->kind == MCAMD_CLIQUET_COMPOUND;
+    job.local_lo = compound ? std::log(1.0 + cq->local_floor) : cq->local_floor;
+    job.local_hi = compound ? std::log(1.0 + cq->local_cap) : cq->local_cap;
+    job.global_lo = cq->global_floor;
+    job.global_hi = cq->global_cap;
+    const double P = static_cast<double>(M - cq->first_period + 1);
+    job.scale = 1.0 / (P * (static_cast<double>(cq->reset_every) * dt));
+    job.surface = job_surface(surface, sim->precision);
+    job.d_samples = d_samples;
+    const uint32_t grid = mcamd::one_path_per_thread_grid(job.n_local);
+    return drive(DeviceCall{job.n_local, grid, mcamd::kCliquetRecord, 6, Finish::kFolded,
+                            [&](const mcamd::FinishSpec &fs) {
+                                return mcamd::launch_cliquet(job, ctx->d_partials, grid, fs, ctx->stream);
+                            }});
+}
+
+// The local-volatility Greeks calls: prepare_localvol's refusals for a barrier-less job, in its order, with the
+// job's own in between.  The kernel finishes its own sum into the 32-double statistics record.  opt->v is ignored.
+template <typename Drive>
+int prepare_localvol_greeks(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                            const mcamd_localvol_greeks_job *gj, const mcamd_localvol_surface *surface, double *d_samples,
+                            Drive drive)
+{
+    if (!opt || !sim || !gj) return fail(MCAMD_ERR_INVALID, "opt, sim, job and surface must be non-NULL");
+    if (int rc = check_payoff(gj->payoff)) return rc;
+    if (gj->n_vega_buckets > MCAMD_LOCALVOL_GREEKS_MAX_BUCKETS)
+        return fail(MCAMD_ERR_INVALID, "n_vega_buckets must lie in 0 .. %d, got %u", MCAMD_LOCALVOL_GREEKS_MAX_BUCKETS,
+                    gj->n_vega_buckets);
+    if (!std::isfinite(gj->gamma_bump) || gj->gamma_bump < 0.0 || gj->gamma_bump > 0.1)
+        return fail(MCAMD_ERR_INVALID, "gamma_bump must be finite and lie in 0 .. 0.1, got %g", gj->gamma_bump);
+    if (!std::isfinite(gj->q)) return fail(MCAMD_ERR_INVALID, "the dividend yield q must be finite, got %g", gj->q);
+    if (!std::isfinite(opt->r)) return fail(MCAMD_ERR_INVALID, "option parameters must be finite with T > 0");
+    const double mu = opt->r - gj->q;
+    if (int rc = check_localvol_request("local-volatility Greeks", *opt, sim, &mu, 1)) return rc;
+    if (!(opt->S0 > 0.0)) return fail(MCAMD_ERR_INVALID, "local-volatility Greeks need S0 > 0 (S0 = %g)", opt->S0);
+    if (!surface) return fail(MCAMD_ERR_INVALID, "opt, sim, job and surface must be non-NULL");
+    const double dt = even_dt(opt, sim);
+    if (sim->precision == MCAMD_F64)
+        if (int rc = check_localvol_exponent_range(mu, surface->sigma_max, dt, sim->n_steps, -1, gj->gamma_bump)) return rc;
+    if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
+    if (!surface_belongs(surface, ctx)) return fail(MCAMD_ERR_INVALID, "the surface was created on another context");
+    if (sim->n_paths_local == 0) return drive(empty_call(mcamd::kLvGreeksStats));
+    mcamd::LocalVolGreeksJob job;
+    job.seed = sim->seed;
+    job.path_offset = sim->path_offset;
+    job.n_local = sim->n_paths_local;
+    job.n_steps = sim->n_steps;
+    job.precision = sim->precision;
+    job.S0 = opt->S0;
+    job.K = opt->K;
+    job.mu = mu;
+    job.dt = dt;
+    job.T = opt->T;
+    job.put = gj->payoff == MCAMD_PAYOFF_PUT;
+    job.n_buckets = gj->n_vega_buckets;
+    job.gamma_bump = gj->gamma_bump;
+    job.surface = job_surface(surface, sim->precision);
+    job.d_samples = d_samples;
+    const uint32_t grid = mcamd::one_path_per_thread_grid(job.n_local);
+    return drive(DeviceCall{job.n_local, grid, mcamd::kLvGreeksRecord, mcamd::kLvGreeksStats, Finish::kFolded,
+                            [&](const mcamd::FinishSpec &fs) {
+                                return mcamd::launch_localvol_greeks(job, ctx->d_partials, grid, fs.out, fs.ticket,
+                                                                     ctx->stream);
+                            }});
+}
+
+// The smile calls: mcamd_price_localvol's paths without a barrier, stopped at the expiry steps, every strike priced at
+// every expiry.  The refusals follow prepare_localvol's order: the request alone, then the surface, then the context.
+// drive(job, grid) runs the form's driver; grid == 0 is the empty shard.  opt->v and opt->K are ignored.
+template <typename Drive>
+int prepare_smile(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_smile *sm,
+                  const uint32_t *h_expiry_steps, const double *h_strikes, const mcamd_localvol_surface *surface,
+                  void *d_spots, Drive drive)
+{
+    if (!opt || !sim || !sm || !h_expiry_steps || !h_strikes)
+        return fail(MCAMD_ERR_INVALID, "opt, sim, smile, h_expiry_steps, h_strikes and surface must be non-NULL");
+    if (int rc = check_payoff(sm->payoff)) return rc;
+    if (sm->reserved != 0) return fail(MCAMD_ERR_INVALID, "smile->reserved must be 0, got %d", sm->reserved);
+    if (sm->n_expiries < 1 || sm->n_expiries > MCAMD_SMILE_MAX_EXPIRIES)
+        return fail(MCAMD_ERR_INVALID, "n_expiries must lie in 1 .. %d, got %u", MCAMD_SMILE_MAX_EXPIRIES, sm->n_expiries);
+    if (sm->n_strikes < 1 || sm->n_strikes > MCAMD_SMILE_MAX_STRIKES)
+        return fail(MCAMD_ERR_INVALID, "n_strikes must lie in 1 .. %d, got %u", MCAMD_SMILE_MAX_STRIKES, sm->n_strikes);
+    for (uint32_t m = 0; m < sm->n_expiries; ++m) {
+        const uint32_t before = m ? h_expiry_steps[m - 1] : 0;
+        if (h_expiry_steps[m] <= before || h_expiry_steps[m] > sim->n_steps)
+            return fail(MCAMD_ERR_INVALID, "expiry steps must be strictly ascending in 1 .. n_steps = %u: "
+                                           "h_expiry_steps[%u] = %u", sim->n_steps, m, h_expiry_steps[m]);
+    }
+    for (uint32_t k = 0; k < sm->n_strikes; ++k)
+        if (!std::isfinite(h_strikes[k]) || !(h_strikes[k] > 0.0))
+            return fail(MCAMD_ERR_INVALID, "every strike must be finite and > 0: h_strikes[%u] = %g", k, h_strikes[k]);
+    if (!std::isfinite(sm->q)) return fail(MCAMD_ERR_INVALID, "the dividend yield q must be finite, got %g", sm->q);
+    if (!std::isfinite(opt->r)) return fail(MCAMD_ERR_INVALID, "option parameters must be finite with T > 0");
+    // as prepare_localvol, on a copy that carries no strike of its own either
+    const double mu = opt->r - sm->q;
+    mcamd_option seen = *opt;
+    seen.K = 1.0;
+    if (int rc = check_localvol_request("local-volatility smile", seen, sim, &mu, 1)) return rc;
+    if (!(opt->S0 > 0.0)) return fail(MCAMD_ERR_INVALID, "local-volatility smile options need S0 > 0 (S0 = %g)", opt->S0);
+    if (!surface)
+        return fail(MCAMD_ERR_INVALID, "opt, sim, smile, h_expiry_steps, h_strikes and surface must be non-NULL");
+    const double dt = even_dt(opt, sim);
+    if (sim->precision == MCAMD_F64)
+        if (int rc = check_localvol_exponent_range(mu, surface->sigma_max, dt, sim->n_steps)) return rc;
+    if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
+    if (!surface_belongs(surface, ctx)) return fail(MCAMD_ERR_INVALID, "the surface was created on another context");
+    mcamd::SmileJob job = {};
+    job.seed = sim->seed;
+    job.path_offset = sim->path_offset;
+    job.n_local = sim->n_paths_local;
+    job.n_steps = sim->n_steps;
+    job.precision = sim->precision;
+    job.S0 = opt->S0;
+    job.mu = mu;
+    job.dt = dt;
+    job.put = sm->payoff == MCAMD_PAYOFF_PUT;
+    job.surface = job_surface(surface, sim->precision);
+    job.n_expiries = sm->n_expiries;
+    job.n_strikes = sm->n_strikes;
+    std::copy(h_expiry_steps, h_expiry_steps + sm->n_expiries, job.expiry_steps);
+    std::copy(h_strikes, h_strikes + sm->n_strikes, job.strikes);
+    job.d_spots = d_spots;
+    const uint32_t grid = job.n_local ? mcamd::smile_grid(job.n_local, job.n_expiries, job.n_strikes, ctx->compute_units) : 0;
+    return drive(job, grid);
+}
+
+// The autocall calls under per-asset local-volatility surfaces.  Every refusal that needs neither a surface nor the
+// context comes first, in prepare_autocall's order; then the surfaces; then the context.  opt supplies r and T alone.
+template <typename Drive>
+int prepare_autocall_localvol(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                              const mcamd_autocall_localvol *ac, const mcamd_localvol_surface *const *surfaces,
+                              void *d_samples, Drive drive)
+{
+    if (!opt || !sim || !ac) return fail(MCAMD_ERR_INVALID, "opt, sim, autocall and surfaces must be non-NULL");
+    if (ac->reserved[0] != 0 || ac->reserved[1] != 0)
+        return fail(MCAMD_ERR_INVALID, "autocall->reserved must be 0, got {%d, %d}", ac->reserved[0], ac->reserved[1]);
+    // n_assets and corr through the basket's own checks and Cholesky factor: unit spots, weights and volatilities
+    mcamd_basket assets{};
+    assets.n_assets = ac->n_assets;
+    assets.payoff = MCAMD_PAYOFF_PUT;
+    for (int j = 0; j < MCAMD_BASKET_MAX_ASSETS; ++j) assets.S0[j] = assets.w[j] = assets.v[j] = 1.0;
+    std::memcpy(assets.corr, ac->corr, sizeof assets.corr);
+    double L[64];
+    if (int rc = check_basket_assets(&assets, true, L)) return rc;
+    const int d = ac->n_assets;
+    for (int j = 0; j < d; ++j)
+        if (!std::isfinite(ac->q[j]))
+            return fail(MCAMD_ERR_INVALID, "every dividend yield q must be finite, got q[%d] = %g", j, ac->q[j]);
+    if (ac->observe_every == 0 || sim->n_steps % ac->observe_every != 0)
+        return fail(MCAMD_ERR_INVALID, "observe_every must be >= 1 and divide n_steps (observe_every = %u, n_steps = %u)",
+                    ac->observe_every, sim->n_steps);
+    const uint32_t M = sim->n_steps / ac->observe_every;
+    if (M > MCAMD_AUTOCALL_MAX_DATES)   // M == 0 is n_steps == 0, which check_request refuses below
+        return fail(MCAMD_ERR_INVALID, "n_steps / observe_every = %u observation dates exceed MCAMD_AUTOCALL_MAX_DATES = %d",
+                    M, MCAMD_AUTOCALL_MAX_DATES);
+    if (M != 0 && (ac->first_call_date < 1 || ac->first_call_date > M))
+        return fail(MCAMD_ERR_INVALID, "first_call_date must be 1..%u (the observation dates), got %u", M,
+                    ac->first_call_date);
+    const double L_last = ac->call_level - (static_cast<double>(M) - 1.0) * ac->call_step_down;
+    if (int rc = check_autocall_terms(ac->coupon, ac->call_level, ac->call_step_down, M ? L_last : ac->call_level,
+                                      ac->ki_monitoring, ac->ki_level))
+        return rc;
+    if (!std::isfinite(opt->r)) return fail(MCAMD_ERR_INVALID, "option parameters must be finite with T > 0");
+    // as prepare_localvol, asset by asset, on a copy that carries no spot, strike or barrier of its own either
+    double mu[MCAMD_BASKET_MAX_ASSETS];
+    for (int j = 0; j < d; ++j) mu[j] = opt->r - ac->q[j];
+    mcamd_option seen = *opt;
+    seen.S0 = 1.0;
+    seen.K = seen.B = 0.0;
+    if (int rc = check_localvol_request("local-volatility autocallable", seen, sim, mu, d)) return rc;
+    // the surfaces
+    if (!surfaces) return fail(MCAMD_ERR_INVALID, "opt, sim, autocall and surfaces must be non-NULL");
+    for (int j = 0; j < d; ++j)
+        if (!surfaces[j]) return fail(MCAMD_ERR_INVALID, "surfaces[%d] is NULL: every asset needs a surface", j);
+    for (int j = 0; j < d; ++j)
+        if (!surface_belongs(surfaces[j], ctx))
+            return fail(MCAMD_ERR_INVALID, "the surface of asset %d was created on another context", j);
+    uint64_t nodes = 0;
+    for (int j = 0; j < d; ++j) nodes += static_cast<uint64_t>(surfaces[j]->grid.n_t) * surfaces[j]->grid.n_x;
+    if (nodes > MCAMD_LOCALVOL_MAX_NODES)
+        return fail(MCAMD_ERR_INVALID, "the %d surfaces hold %llu nodes together; at most %d fit the kernel's LDS tables "
+                                       "(a surface passed for several assets counts once per asset)", d,
+                    static_cast<unsigned long long>(nodes), MCAMD_LOCALVOL_MAX_NODES);
+    const double dt = even_dt(opt, sim);
+    if (sim->precision == MCAMD_F64)
+        for (int j = 0; j < d; ++j)
+            if (int rc = check_localvol_exponent_range(mu[j], surfaces[j]->sigma_max, dt, sim->n_steps, j)) return rc;
+    if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
+    if (sim->n_paths_local == 0) return drive(empty_call());
+    mcamd::AutocallLocalVolJob job{};
+    job.seed = sim->seed;
+    job.path_offset = sim->path_offset;
+    job.n_local = sim->n_paths_local;
+    job.n_steps = sim->n_steps;
+    job.precision = sim->precision;
+    job.d = d;
+    job.dt = dt;
+    for (int j = 0; j < d; ++j) {
+        job.mu[j] = mu[j];
+        for (int k = 0; k <= j; ++k) job.chol[j * (j + 1) / 2 + k] = L[8 * j + k];
+        job.surface[j] = job_surface(surfaces[j], sim->precision);
+    }
+    job.observe_every = ac->observe_every;
+    job.n_dates = M;
+    job.first_call_date = ac->first_call_date;
+    for (uint32_t q = 1; q <= M; ++q) {
+        const double t_q = static_cast<double>(q * ac->observe_every) * dt;
+        job.log_level[q - 1] = std::log(ac->call_level - (static_cast<double>(q) - 1.0) * ac->call_step_down);
+        job.pay[q - 1] = (1.0 + static_cast<double>(q) * ac->coupon) * std::exp(opt->r * (opt->T - t_q));
+    }
+    job.ki = ac->ki_monitoring != MCAMD_AUTOCALL_KI_NONE;
+    job.ki_every_step = ac->ki_monitoring == MCAMD_AUTOCALL_KI_EVERY_STEP;
+    job.log_ki = job.ki ? std::log(ac->ki_level) : 0.0;
+    job.d_samples = d_samples;
+    const uint32_t grid = mcamd::one_path_per_thread_grid(job.n_local);
+    return drive(DeviceCall{job.n_local, grid, mcamd::kAutocallRecord, 6, Finish::kFolded,
+                            [&](const mcamd::FinishSpec &fs) {
+                                return mcamd::launch_autocall_localvol(job, ctx->d_partials, grid, fs, ctx->stream);
+                            }});
+}
+
+// The smile's two launches on the context's stream: the walk into the per-wavefront records, then their sum into out.
+int launch_smile_pair(mcamd_ctx *ctx, const mcamd::SmileJob &job, uint32_t grid, double *out, double n_value,
+                      hipEvent_t before, hipEvent_t after)
+{
+    HIP_TRY(hipEventRecord(before, ctx->stream));
+    HIP_TRY(mcamd::launch_localvol_smile(job, ctx->d_partials, grid, ctx->stream));
+    HIP_TRY(hipEventRecord(after, ctx->stream));
+    HIP_TRY(mcamd::launch_smile_finish(ctx->d_partials, grid * mcamd::kSmileWavesPerBlock, job.n_expiries * job.n_strikes,
+                                       out, n_value, ctx->stream));
+    return MCAMD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mcamd_localvol_surface_create(mcamd_ctx *ctx, const mcamd_localvol_grid *grid, const double *h_sigma,
+                                  mcamd_localvol_surface **surface)
+{
+    if (!surface) return fail(MCAMD_ERR_INVALID, "surface out-pointer is NULL");
+    *surface = nullptr;
+    double sigma_max = 0.0;
+    if (int rc = check_localvol_grid(grid, h_sigma, &sigma_max)) return rc;
+    if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
+    const uint32_t n_x = grid->n_x, n = grid->n_t * n_x;
+    // the pairs: sigma_k and slope_k = sigma_{k+1} - sigma_k, the slope formed in double, then narrowed
+    std::vector<mcamd::VolPair<double>> t64(n);
+    std::vector<mcamd::VolPair<float>> t32(n);
+    for (uint32_t e = 0; e < n; ++e) {
+        const double slope = (e % n_x == n_x - 1) ? 0.0 : h_sigma[e + 1] - h_sigma[e];
+        t64[e] = {h_sigma[e], slope};
+        t32[e] = {static_cast<float>(h_sigma[e]), static_cast<float>(slope)};
+    }
+    mcamd_localvol_surface *s = new (std::nothrow) mcamd_localvol_surface;
+    if (!s) return fail(MCAMD_ERR_NOMEM, "out of host memory");
+    s->ctx = ctx;
+    s->ctx_id = ctx->id;
+    s->device = ctx->device;
+    s->grid = *grid;
+    s->sigma_max = sigma_max;
+    const size_t bytes64 = n * sizeof(mcamd::VolPair<double>), bytes32 = n * sizeof(mcamd::VolPair<float>);
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e == hipSuccess) e = hipMalloc(&s->d_tables, bytes64 + bytes32);
+    if (e == hipSuccess) {
+        s->d_tab64 = s->d_tables;
+        s->d_tab32 = static_cast<char *>(s->d_tables) + bytes64;   // bytes64 is a multiple of 16
+        e = hipMemcpy(s->d_tab64, t64.data(), bytes64, hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess) e = hipMemcpy(s->d_tab32, t32.data(), bytes32, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        if (s->d_tables) (void)hipFree(s->d_tables);
+        delete s;
+        return fail(e == hipErrorOutOfMemory ? MCAMD_ERR_NOMEM : MCAMD_ERR_HIP, "surface upload: %s", hipGetErrorString(e));
+    }
+    *surface = s;
+    return MCAMD_OK;
+}
+
+int mcamd_localvol_surface_destroy(mcamd_localvol_surface *surface)
+{
+    if (!surface) return MCAMD_OK;
+    (void)hipSetDevice(surface->device);
+    if (surface->d_tables) (void)hipFree(surface->d_tables);
+    delete surface;
+    return MCAMD_OK;
+}
+
+int mcamd_price_localvol(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_localvol *localvol,
+                         const mcamd_localvol_surface *surface, void *d_samples, mcamd_result *res)
+{
+    if (!res) return fail(MCAMD_ERR_INVALID, "opt, sim, localvol, surface and res must be non-NULL");
+    zero_result(res);
+    return prepare_localvol(ctx, opt, sim, localvol, surface, d_samples, [&](const auto &call) {
+        return run_sync(ctx, call, res, [&](const double *rec) {
+            finalize_counted_into(rec, sim->n_paths_local, opt->r, opt->T, res);
+        });
+    });
+}
+
+int mcamd_price_localvol_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                                 const mcamd_localvol *localvol, const mcamd_localvol_surface *surface, void *d_samples,
+                                 double *d_stats)
+{
+    return prepare_localvol(ctx, opt, sim, localvol, surface, d_samples,
+                            [&](const auto &call) { return run_enqueue(ctx, call, d_stats); });
+}
+
+int mcamd_price_cliquet(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_cliquet *cliquet,
+                        const mcamd_localvol_surface *surface, void *d_samples, mcamd_cliquet_result *res)
+{
+    if (!res) return fail(MCAMD_ERR_INVALID, "opt, sim, cliquet, surface and res must be non-NULL");
+    std::memset(res, 0, sizeof *res);
+    return prepare_cliquet(ctx, opt, sim, cliquet, surface, d_samples, [&](const auto &call) {
+        return run_sync(ctx, call, res, [&](const double *rec) {
+            // {sum, sumsq, paths on the global floor, paths on the global cap, wave-steps}
+            const Estimate e = estimate(rec[0], rec[1], sim->n_paths_local, std::exp(-opt->r * opt->T));
+            res->sum = rec[0];
+            res->sumsq = rec[1];
+            res->n = sim->n_paths_local;
+            res->price = e.value;
+            res->std_err = e.std_err;
+            set_ci(res);
+            res->n_floored = static_cast<uint64_t>(std::llround(rec[2]));
+            res->n_capped = static_cast<uint64_t>(std::llround(rec[3]));
+            res->work_steps = 64.0 * rec[4];   // wave-steps x 64 lanes
+        });
+    });
+}
+
+int mcamd_price_cliquet_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                                const mcamd_cliquet *cliquet, const mcamd_localvol_surface *surface, void *d_samples,
+                                double *d_stats)
+{
+    return prepare_cliquet(ctx, opt, sim, cliquet, surface, d_samples,
+                           [&](const auto &call) { return run_enqueue(ctx, call, d_stats); });
+}
+
+int mcamd_price_localvol_greeks(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                                const mcamd_localvol_greeks_job *job, const mcamd_localvol_surface *surface,
+                                double *d_samples, mcamd_localvol_greeks *out)
+{
+    if (!out) return fail(MCAMD_ERR_INVALID, "opt, sim, job, surface and out must be non-NULL");
+    std::memset(out, 0, sizeof *out);
+    return prepare_localvol_greeks(ctx, opt, sim, job, surface, d_samples, [&](const auto &call) {
+        return run_sync(ctx, call, out, [&](const double *stats) {
+            finalize_localvol_greeks_into(stats, opt->r, opt->T, job->n_vega_buckets, job->gamma_bump > 0.0, out);
+        });
+    });
+}
+
+int mcamd_price_localvol_greeks_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                                        const mcamd_localvol_greeks_job *job, const mcamd_localvol_surface *surface,
+                                        double *d_samples, double *d_stats)
+{
+    return prepare_localvol_greeks(ctx, opt, sim, job, surface, d_samples, [&](const auto &call) {
+        if (call.n && d_stats) {   // NaN (all-ones bytes) until the kernel has written the record
+            HIP_TRY(hipSetDevice(ctx->device));
+            HIP_TRY(hipMemsetAsync(d_stats, 0xFF, mcamd::kLvGreeksStats * sizeof(double), ctx->stream));
+        }
+        return run_enqueue(ctx, call, d_stats);
+    });
+}
+
+int mcamd_price_autocall_localvol(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                                  const mcamd_autocall_localvol *autocall, const mcamd_localvol_surface *const *surfaces,
+                                  void *d_samples, mcamd_autocall_result *res)
+{
+    if (!res) return fail(MCAMD_ERR_INVALID, "opt, sim, autocall, surfaces and res must be non-NULL");
+    std::memset(res, 0, sizeof *res);
+    return prepare_autocall_localvol(ctx, opt, sim, autocall, surfaces, d_samples, [&](const auto &call) {
+        return run_sync(ctx, call, res, [&](const double *rec) {
+            fill_autocall_result(rec, sim->n_paths_local, opt->r, opt->T, res);
+        });
+    });
+}
+
+int mcamd_price_autocall_localvol_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                                          const mcamd_autocall_localvol *autocall,
+                                          const mcamd_localvol_surface *const *surfaces, void *d_samples, double *d_stats)
+{
+    return prepare_autocall_localvol(ctx, opt, sim, autocall, surfaces, d_samples,
+                                     [&](const auto &call) { return run_enqueue(ctx, call, d_stats); });
+}
+
+int mcamd_price_localvol_smile(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_smile *smile,
+                               const uint32_t *h_expiry_steps, const double *h_strikes,
+                               const mcamd_localvol_surface *surface, void *d_spots, double *h_stats, mcamd_result *res)
+{
+    if (!res || !h_stats) return fail(MCAMD_ERR_INVALID, "h_stats and res must be non-NULL");
+    zero_result(res);
+    return prepare_smile(ctx, opt, sim, smile, h_expiry_steps, h_strikes, surface, d_spots,
+                         [&](const mcamd::SmileJob &job, uint32_t grid) -> int {
+        const uint32_t nodes = job.n_expiries * job.n_strikes, n_stats = 2 * nodes;
+        std::fill(h_stats, h_stats + n_stats, 0.0);
+        if (job.n_local == 0) return MCAMD_OK;
+        HIP_TRY(hipSetDevice(ctx->device));
+        if (!ctx->h_smile) {
+            HIP_TRY(hipHostMalloc(&ctx->h_smile, mcamd_ctx::kSmileStats * sizeof(double), hipHostMallocDefault));
+            HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&ctx->h_smile_dev), ctx->h_smile, 0));
+        }
+        if (int rc = ensure_partials(ctx, grid * mcamd::kSmileWavesPerBlock, static_cast<int>(n_stats))) return rc;
+        // the finishing kernel writes the pinned buffer itself; all-ones bits there afterwards mean it never ran
+        arm_record(ctx->h_smile, static_cast<int>(n_stats));
+        if (int rc = launch_smile_pair(ctx, job, grid, ctx->h_smile_dev, -1.0, ctx->ev0, ctx->ev1)) return rc;
+        HIP_TRY(hipEventRecord(ctx->ev2, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        float kernel_ms = 0.0f, total_ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&kernel_ms, ctx->ev0, ctx->ev1));
+        HIP_TRY(hipEventElapsedTime(&total_ms, ctx->ev0, ctx->ev2));
+        if (record_unwritten(ctx->h_smile, static_cast<int>(n_stats)))
+            return fail(MCAMD_ERR_HIP, "the smile kernels left no result (the finishing kernel did not write every node)");
+        std::memcpy(h_stats, ctx->h_smile, n_stats * sizeof(double));
+        const uint32_t last = job.expiry_steps[job.n_expiries - 1];
+        finalize_into(h_stats[nodes - 1], h_stats[n_stats - 1], job.n_local, opt->r,
+                      static_cast<double>(last) * job.dt, res);
+        res->work_steps = 64.0 * static_cast<double>((job.n_local + 63) / 64) * static_cast<double>(last);
+        res->live_steps = res->work_steps;
+        res->kernel_ms = kernel_ms;
+        res->total_ms = total_ms;
+        res->grid = grid;
+        res->block = mcamd::kBlockThreads;
+        return MCAMD_OK;
+    });
+}
+
+int mcamd_price_localvol_smile_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                                       const mcamd_smile *smile, const uint32_t *h_expiry_steps, const double *h_strikes,
+                                       const mcamd_localvol_surface *surface, void *d_spots, double *d_stats)
+{
+    if (!d_stats) return fail(MCAMD_ERR_INVALID, "d_stats is NULL");
+    return prepare_smile(ctx, opt, sim, smile, h_expiry_steps, h_strikes, surface, d_spots,
+                         [&](const mcamd::SmileJob &job, uint32_t grid) -> int {
+        const uint32_t n_stats = 2 * job.n_expiries * job.n_strikes;
+        HIP_TRY(hipSetDevice(ctx->device));
+        const uint32_t slot = static_cast<uint32_t>(ctx->n_enqueued % mcamd_ctx::kRing);
+        if (job.n_local == 0) {
+            HIP_TRY(hipMemsetAsync(d_stats, 0, (n_stats + 1) * sizeof(double), ctx->stream));
+            HIP_TRY(hipEventRecord(ctx->ring0[slot], ctx->stream));
+            HIP_TRY(hipEventRecord(ctx->ring1[slot], ctx->stream));
+            ctx->n_enqueued++;
+            return MCAMD_OK;
+        }
+        const uint32_t waves = grid * mcamd::kSmileWavesPerBlock;
+        // growing the scratch buffer frees the old one: wait for work that may still read it
+        if (static_cast<uint64_t>(waves) * n_stats > ctx->partial_capacity) HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if (int rc = ensure_partials(ctx, waves, static_cast<int>(n_stats))) return rc;
+        if (int rc = launch_smile_pair(ctx, job, grid, d_stats, static_cast<double>(job.n_local), ctx->ring0[slot],
+                                       ctx->ring1[slot]))
+            return rc;
+        ctx->n_enqueued++;
+        return MCAMD_OK;
+    });
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-// cliquet.hpp — host-side interface of the cliquet kernels (cliquet.hip) for the C ABI (capi.cpp).
+// cliquet.hpp — host-side interface of the cliquet kernels (cliquet.hip) for the C ABI (capi_localvol.cpp).
 //
 // A cliquet kernel walks mcamd_price_localvol's paths (localvol_device.hpp: the same surface, lookup, row carry,
 // log-Euler move and normals) and accumulates a payoff from the log-returns between equally spaced reset dates

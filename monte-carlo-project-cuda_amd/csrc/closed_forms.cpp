@@ -1,0 +1,390 @@
+// closed_forms.cpp — every host formula of the C ABI that touches no device: the Black-Scholes family, the closed
+// forms the product tests price against, and the host lookup of a local-volatility table.  Compiled with the flags of
+// the other C ABI files (no contraction), so a formula a prepare_* step shares gives the bits it gives here.
+#define MCAMD_CAPI_HOST_ONLY
+#include "capi_internal.hpp"
+
+#include <algorithm>
+
+using namespace mcamd::capi;
+
+namespace mcamd::capi {
+
+// Black-Scholes with a dividend yield at volatility v > 0 and its vega; every argument checked by the caller
+double bs_value(double S0, double K, double T, double r, double q, double v, bool call, double *vega)
+{
+    const double sqrtT = std::sqrt(T);
+    const double d1 = (std::log(S0 / K) + (r - q + 0.5 * v * v) * T) / (v * sqrtT), d2 = d1 - v * sqrtT;
+    const double Sd = S0 * std::exp(-q * T), Kd = K * std::exp(-r * T);
+    if (vega) *vega = Sd * sqrtT * std::exp(-0.5 * d1 * d1) * 0.3989422804014327;
+    return call ? Sd * norm_cdf(d1) - Kd * norm_cdf(d2) : Kd * norm_cdf(-d2) - Sd * norm_cdf(-d1);
+}
+
+// The discrete geometric average of geometric Brownian motion over the step ends i = 1..n (and t = 0 with
+// include_spot; m dates in all) is lognormal: ln G ~ N(M, s^2) with M = ln S0 + mu dt n(n+1) / (2m) and
+// s^2 = v^2 dt n(n+1)(2n+1) / (6 m^2), mu = r - v^2/2.  The floating strike exchanges G for S_T, two lognormals with
+// covariance v^2 dt n(n+1) / (2m) of their logarithms (Margrabe's form on the forwards).
+int asian_geometric_price(double S0, double K, double T, double r, double v, uint32_t n_steps, int include_spot,
+                          int strike, int payoff, double *price)
+{
+    *price = 0.0;
+    if (!(S0 > 0.0) || !(T > 0.0) || !(v > 0.0) || !std::isfinite(S0) || !std::isfinite(T) || !std::isfinite(r) ||
+        !std::isfinite(v))
+        return fail(MCAMD_ERR_INVALID, "the geometric Asian closed form needs finite S0, T, v > 0 and a finite r");
+    if (n_steps == 0) return fail(MCAMD_ERR_INVALID, "n_steps must be >= 1");
+    if (int rc = check_asian_kind(K, strike, payoff, include_spot)) return rc;
+    const double n = static_cast<double>(n_steps), m = n + include_spot, dt = T / n;
+    const double mu = r - 0.5 * v * v, D = std::exp(-r * T);
+    const double M = std::log(S0) + mu * dt * n * (n + 1.0) / (2.0 * m);
+    const double s2 = v * v * dt * n * (n + 1.0) * (2.0 * n + 1.0) / (6.0 * m * m);
+    const double F = std::exp(M + 0.5 * s2);   // E[G]
+    const bool put = payoff == MCAMD_PAYOFF_PUT;
+    if (strike == MCAMD_ASIAN_FIXED) {
+        const double s = std::sqrt(s2);
+        const double d1 = (M - std::log(K)) / s + s;
+        const double call = D * (F * norm_cdf(d1) - K * norm_cdf(d1 - s));
+        *price = put ? call - D * (F - K) : call;
+        return MCAMD_OK;
+    }
+    const double sf2 = v * v * T + s2 - v * v * dt * n * (n + 1.0) / m;
+    // one step without the spot: the average IS S_T, and the option pays nothing
+    if ((n_steps == 1 && !include_spot) || !(sf2 > 0.0)) return MCAMD_OK;
+    const double F1 = S0 * std::exp(r * T), sf = std::sqrt(sf2);
+    const double d1 = (std::log(F1 / F) + 0.5 * sf2) / sf;
+    const double call = D * (F1 * norm_cdf(d1) - F * norm_cdf(d1 - sf));
+    *price = put ? call - D * (F1 - F) : call;
+    return MCAMD_OK;
+}
+
+}  // namespace mcamd::capi
+
+extern "C" {
+
+int mcamd_bs_greeks_f64(double S0, double K, double T, double r, double v, double out[6])
+{
+    if (!out) return fail(MCAMD_ERR_INVALID, "out is NULL");
+    if (!(S0 > 0.0) || !(K > 0.0) || !(T > 0.0) || !(v > 0.0) || !std::isfinite(S0) || !std::isfinite(K) ||
+        !std::isfinite(T) || !std::isfinite(r) || !std::isfinite(v))
+        return fail(MCAMD_ERR_INVALID, "closed-form Greeks need finite S0, K, T, v > 0 and a finite r");
+    const double sqrtT = std::sqrt(T);
+    const double d1 = (std::log(S0 / K) + (r + 0.5 * v * v) * T) / (v * sqrtT);
+    const double d2 = d1 - v * sqrtT;
+    const double Nd1 = norm_cdf(d1), Nd2 = norm_cdf(d2);
+    const double phi = std::exp(-0.5 * d1 * d1) / std::sqrt(2.0 * M_PI);
+    const double Kdisc = K * std::exp(-r * T);
+    out[MCAMD_GREEK_PRICE] = mcamd_bs_call_f64(S0, K, T, r, v);
+    out[MCAMD_GREEK_DELTA] = Nd1;
+    out[MCAMD_GREEK_GAMMA] = phi / (S0 * v * sqrtT);
+    out[MCAMD_GREEK_VEGA] = S0 * phi * sqrtT;
+    out[MCAMD_GREEK_RHO] = Kdisc * T * Nd2;
+    out[MCAMD_GREEK_THETA] = -S0 * phi * v / (2.0 * sqrtT) - r * Kdisc * Nd2;
+    return MCAMD_OK;
+}
+
+// Reiner and Rubinstein (1991) / Merton (1973): the continuously monitored single barrier without rebate or dividends,
+// from the four terms A..D of the standard presentation (phi = 1 call / -1 put, eta = 1 down / -1 up).
+int mcamd_barrier_price_f64(double S0, double K, double B, double T, double r, double v, int kind, int payoff,
+                            double *price)
+{
+    if (!price) return fail(MCAMD_ERR_INVALID, "price is NULL");
+    *price = 0.0;
+    if (!(K > 0.0) || !(T > 0.0) || !(v > 0.0) || !std::isfinite(K) || !std::isfinite(T) || !std::isfinite(r) ||
+        !std::isfinite(v))
+        return fail(MCAMD_ERR_INVALID, "the barrier closed form needs finite K, T, v > 0 and a finite r");
+    if (int rc = check_barrier_kind(S0, B, kind, payoff)) return rc;
+    const auto [up, out] = barrier_sides(kind);
+    const double phi = payoff == MCAMD_PAYOFF_PUT ? -1.0 : 1.0, eta = up ? -1.0 : 1.0;
+    const double s = v * std::sqrt(T), mu = (r - 0.5 * v * v) / (v * v), Kd = K * std::exp(-r * T);
+    const auto N = norm_cdf;
+    const double x1 = std::log(S0 / K) / s + (1.0 + mu) * s, x2 = std::log(S0 / B) / s + (1.0 + mu) * s;
+    const double y1 = std::log(B * B / (S0 * K)) / s + (1.0 + mu) * s, y2 = std::log(B / S0) / s + (1.0 + mu) * s;
+    const double p0 = std::pow(B / S0, 2.0 * mu), p1 = p0 * (B / S0) * (B / S0);
+    const double tA = phi * S0 * N(phi * x1) - phi * Kd * N(phi * x1 - phi * s);
+    const double tB = phi * S0 * N(phi * x2) - phi * Kd * N(phi * x2 - phi * s);
+    const double tC = phi * S0 * p1 * N(eta * y1) - phi * Kd * p0 * N(eta * y1 - eta * s);
+    const double tD = phi * S0 * p1 * N(eta * y2) - phi * Kd * p0 * N(eta * y2 - eta * s);
+    // the knock-in; the knock-out is the vanilla price (term A) less it.  Which combination depends on whether the
+    // strike lies on the live side of the barrier for this payoff.
+    const bool call = phi > 0.0;
+    double in;
+    if (call != up) in = (call ? K >= B : K <= B) ? tC : tA - tB + tD;          // down call, up put
+    else in = (call ? K >= B : K <= B) ? tA : tB - tC + tD;                     // up call, down put
+    *price = out ? tA - in : in;
+    return MCAMD_OK;
+}
+
+// Goldman, Sosin and Gatto (1979) for the floating strike, Conze and Viswanathan (1991) for the fixed one: the
+// continuously monitored, newly issued lookback without dividends.  A fixed strike on the side of the spot the extremum
+// has already passed (call: K <= S0, put: K >= S0) is the opposite floating lookback plus a forward.
+int mcamd_lookback_price_f64(double S0, double K, double T, double r, double v, int strike, int payoff, double *price)
+{
+    if (!price) return fail(MCAMD_ERR_INVALID, "price is NULL");
+    *price = 0.0;
+    if (!(S0 > 0.0) || !(T > 0.0) || !(v > 0.0) || !std::isfinite(S0) || !std::isfinite(T) || !std::isfinite(r) ||
+        !std::isfinite(v))
+        return fail(MCAMD_ERR_INVALID, "the lookback closed form needs finite S0, T, v > 0 and a finite r");
+    if (r == 0.0)
+        return fail(MCAMD_ERR_INVALID, "the lookback closed form carries v^2 / (2r): r == 0 is not covered");
+    if (int rc = check_lookback_kind(K, strike, payoff)) return rc;
+    const bool put = payoff == MCAMD_PAYOFF_PUT;
+    const double sq = std::sqrt(T), s = v * sq, D = std::exp(-r * T), G = std::exp(r * T);
+    const double lam = v * v / (2.0 * r), shift = 2.0 * r * sq / v;
+    const auto N = norm_cdf;
+    const double a = (r + 0.5 * v * v) * T / s;
+    const auto floating = [&](bool is_put) {
+        if (is_put) return S0 * D * N(-a + s) - S0 * N(-a) + S0 * D * lam * (-N(a - shift) + G * N(a));
+        return S0 * N(a) - S0 * D * N(a - s) + S0 * D * lam * (N(-a + shift) - G * N(-a));
+    };
+    if (strike == MCAMD_LOOKBACK_FLOATING) {
+        *price = floating(put);
+        return MCAMD_OK;
+    }
+    const double d = (std::log(S0 / K) + (r + 0.5 * v * v) * T) / s;
+    const double pw = std::pow(S0 / K, -2.0 * r / (v * v));
+    if (!put) {
+        if (K > S0) *price = S0 * N(d) - K * D * N(d - s) + S0 * D * lam * (-pw * N(d - shift) + G * N(d));
+        else *price = floating(true) + S0 - K * D;
+    } else {
+        if (K < S0) *price = K * D * N(-d + s) - S0 * N(-d) + S0 * D * lam * (pw * N(-d + shift) - G * N(-d));
+        else *price = floating(false) + K * D - S0;
+    }
+    return MCAMD_OK;
+}
+
+// The geometric basket is a lognormal: ln A_T ~ N(m, s^2), m = sum_j w_j (ln S0_j + (r - v_j^2/2) T),
+// s^2 = T w'(v o corr o v) w.
+int mcamd_basket_geometric_price_f64(const mcamd_basket *basket, double K, double T, double r, double *price)
+{
+    if (!price) return fail(MCAMD_ERR_INVALID, "price is NULL");
+    *price = 0.0;
+    if (!basket) return fail(MCAMD_ERR_INVALID, "basket is NULL");
+    double L[64];
+    if (int rc = check_basket_assets(basket, false, L)) return rc;
+    if (!std::isfinite(K) || !(K >= 0.0)) return fail(MCAMD_ERR_INVALID, "a basket option needs a finite K >= 0, got %g", K);
+    if (!(T > 0.0) || !std::isfinite(T) || !std::isfinite(r))
+        return fail(MCAMD_ERR_INVALID, "the geometric closed form needs a finite T > 0 and a finite r");
+    const int d = basket->n_assets;
+    double mean = 0.0, var = 0.0;
+    for (int j = 0; j < d; ++j) {
+        mean += basket->w[j] * (std::log(basket->S0[j]) + (r - 0.5 * basket->v[j] * basket->v[j]) * T);
+        for (int k = 0; k < d; ++k)
+            var += basket->w[j] * basket->v[j] * basket->corr[8 * j + k] * basket->v[k] * basket->w[k];
+    }
+    var *= T;
+    const double s = std::sqrt(var > 0.0 ? var : 0.0), D = std::exp(-r * T), F = std::exp(mean + 0.5 * var);
+    const bool put = basket->payoff == MCAMD_PAYOFF_PUT;
+    if (K == 0.0 || !(s > 0.0)) {   // a forward: A_T > 0 = K always, or A_T is not random (weights that cancel)
+        const double fwd = K == 0.0 ? F : std::exp(mean);
+        *price = D * std::fmax(put ? K - fwd : fwd - K, 0.0);
+        return MCAMD_OK;
+    }
+    const double d1 = (mean - std::log(K)) / s + s, d2 = d1 - s;
+    *price = put ? D * (K * norm_cdf(-d2) - F * norm_cdf(-d1)) : D * (F * norm_cdf(d1) - K * norm_cdf(d2));
+    return MCAMD_OK;
+}
+
+// Margrabe (1978): the option to exchange b S2 for a S1.
+int mcamd_exchange_price_f64(double a_S1, double b_S2, double T, double v1, double v2, double rho, double *price)
+{
+    if (!price) return fail(MCAMD_ERR_INVALID, "price is NULL");
+    *price = 0.0;
+    if (!(a_S1 > 0.0) || !(b_S2 > 0.0) || !(T > 0.0) || !(v1 > 0.0) || !(v2 > 0.0) || !std::isfinite(a_S1) ||
+        !std::isfinite(b_S2) || !std::isfinite(T) || !std::isfinite(v1) || !std::isfinite(v2))
+        return fail(MCAMD_ERR_INVALID, "the exchange closed form needs finite a S1, b S2, T, v1, v2 > 0");
+    if (!(rho > -1.0 && rho < 1.0))
+        return fail(MCAMD_ERR_INVALID, "the exchange closed form needs -1 < rho < 1, got %g", rho);
+    const double s = std::sqrt((v1 * v1 + v2 * v2 - 2.0 * rho * v1 * v2) * T);
+    const double d1 = std::log(a_S1 / b_S2) / s + 0.5 * s;
+    *price = a_S1 * norm_cdf(d1) - b_S2 * norm_cdf(d1 - s);
+    return MCAMD_OK;
+}
+
+int mcamd_asian_geometric_price_f64(double S0, double K, double T, double r, double v, uint32_t n_steps,
+                                    int include_spot, int strike, int payoff, double *price)
+{
+    if (!price) return fail(MCAMD_ERR_INVALID, "price is NULL");
+    return asian_geometric_price(S0, K, T, r, v, n_steps, include_spot, strike, payoff, price);
+}
+
+// One asset, one date: S_T / S_0 is lognormal, P[S_T / S_0 >= x] = N(d2(x)) and E[(S_T / S_0) 1{S_T / S_0 <= x}] =
+// e^{rT} N(-d1(x)).  Called above L: 1 + c; between B and L: 1; at or below B: the performance itself (B <= 1).
+int mcamd_autocall_single_date_price_f64(double T, double r, double v, double call_level, double coupon,
+                                         double ki_level, int ki_monitoring, double *price)
+{
+    if (!price) return fail(MCAMD_ERR_INVALID, "price is NULL");
+    *price = 0.0;
+    if (!(T > 0.0) || !(v > 0.0) || !std::isfinite(T) || !std::isfinite(r) || !std::isfinite(v))
+        return fail(MCAMD_ERR_INVALID, "the single-date autocall closed form needs finite T, v > 0 and a finite r");
+    if (int rc = check_autocall_terms(coupon, call_level, 0.0, call_level, ki_monitoring, ki_level)) return rc;
+    if (ki_monitoring == MCAMD_AUTOCALL_KI_EVERY_STEP)
+        return fail(MCAMD_ERR_INVALID, "the closed form covers MCAMD_AUTOCALL_KI_NONE and MCAMD_AUTOCALL_KI_AT_MATURITY: "
+                                       "a knock-in monitored at every step has none");
+    const double s = v * std::sqrt(T);
+    const auto d2 = [&](double x) { return (-std::log(x) + (r - 0.5 * v * v) * T) / s; };
+    const double pL = norm_cdf(d2(call_level));
+    double value = (1.0 + coupon) * pL;
+    if (ki_monitoring == MCAMD_AUTOCALL_KI_NONE) value += 1.0 - pL;
+    else value += (norm_cdf(d2(ki_level)) - pL) + std::exp(r * T) * norm_cdf(-(d2(ki_level) + s));
+    *price = std::exp(-r * T) * value;
+    return MCAMD_OK;
+}
+
+// Volatility in time only: the period log-returns D_p ~ N((r - q - v_p^2 / 2) tau, v_p^2 tau) are independent, so the
+// mean of a sum of clipped returns is the sum of the means and that of their product the product.  A return clipped to
+// [F, C] is (1 + F) + (e^D - (1 + F))+ - (e^D - (1 + C))+ gross: two calls on e^D.
+int mcamd_cliquet_price_f64(int kind, double T, double r, double q, uint32_t n_periods, uint32_t first_period,
+                            const double *period_vol, double local_floor, double local_cap, double *price)
+{
+    if (!price) return fail(MCAMD_ERR_INVALID, "price is NULL");
+    *price = 0.0;
+    if (!period_vol) return fail(MCAMD_ERR_INVALID, "period_vol is NULL");
+    if (int rc = check_cliquet_kind(kind)) return rc;
+    if (int rc = check_cliquet_local(local_floor, local_cap)) return rc;
+    if (int rc = check_cliquet_kind_bounds(kind, local_floor, local_cap)) return rc;
+    if (!(T > 0.0) || !std::isfinite(T) || !std::isfinite(r) || !std::isfinite(q))
+        return fail(MCAMD_ERR_INVALID, "the cliquet closed form needs a finite T > 0 and finite r and q");
+    if (n_periods == 0 || first_period < 1 || first_period > n_periods)
+        return fail(MCAMD_ERR_INVALID, "n_periods must be >= 1 and first_period 1..n_periods, got %u and %u", n_periods,
+                    first_period);
+    for (uint32_t p = 0; p < n_periods; ++p)
+        if (!std::isfinite(period_vol[p]) || !(period_vol[p] > 0.0))
+            return fail(MCAMD_ERR_INVALID, "every period volatility must be finite and > 0: period_vol[%u] = %g", p,
+                        period_vol[p]);
+    const double tau = T / static_cast<double>(n_periods), fwd = std::exp((r - q) * tau);
+    const double F = std::fmax(local_floor, -1.0);   // a floor at or below -1 never binds
+    double sum = 0.0, prod = 1.0;
+    for (uint32_t p = first_period; p <= n_periods; ++p) {
+        const double v = period_vol[p - 1], s = v * std::sqrt(tau);
+        const auto call = [&](double k) {   // E[(e^D - k)+]
+            if (k <= 0.0) return fwd - k;
+            if (k == HUGE_VAL) return 0.0;
+            const double d1 = ((r - q + 0.5 * v * v) * tau - std::log(k)) / s;
+            return fwd * norm_cdf(d1) - k * norm_cdf(d1 - s);
+        };
+        if (kind == MCAMD_CLIQUET_VARIANCE) {
+            const double mean = (r - q - 0.5 * v * v) * tau;
+            sum += v * v * tau + mean * mean;
+        } else {
+            const double E = (1.0 + F) + call(1.0 + F) - call(1.0 + local_cap);
+            sum += E - 1.0;
+            prod *= E;
+        }
+    }
+    const double P = static_cast<double>(n_periods - first_period + 1);
+    const double value = kind == MCAMD_CLIQUET_SUM ? sum : kind == MCAMD_CLIQUET_COMPOUND ? prod - 1.0 : sum / (P * tau);
+    *price = std::exp(-r * T) * value;
+    return MCAMD_OK;
+}
+
+int mcamd_localvol_sigma_f64(const mcamd_localvol_grid *grid, const double *h_sigma, uint32_t n_steps, uint32_t step,
+                             double x, double *sigma)
+{
+    if (!sigma) return fail(MCAMD_ERR_INVALID, "sigma is NULL");
+    *sigma = 0.0;
+    if (int rc = check_localvol_grid(grid, h_sigma, nullptr)) return rc;
+    if (n_steps == 0 || step >= n_steps)
+        return fail(MCAMD_ERR_INVALID, "step = %u must lie in [0, n_steps = %u)", step, n_steps);
+    if (std::isnan(x)) return fail(MCAMD_ERR_INVALID, "x is NaN");
+    const uint64_t row = static_cast<uint64_t>(step) * grid->n_t / n_steps;
+    const double dx = (grid->x_max - grid->x_min) / static_cast<double>(grid->n_x - 1);
+    const double u = std::fmin(std::fmax((x - grid->x_min) * (1.0 / dx), 0.0), static_cast<double>(grid->n_x - 1));
+    const uint32_t k = std::min(static_cast<uint32_t>(u), grid->n_x - 2);
+    const double *s = h_sigma + row * grid->n_x + k;
+    *sigma = std::fma(u - static_cast<double>(k), s[1] - s[0], s[0]);
+    return MCAMD_OK;
+}
+
+int mcamd_bs_price_f64(double S0, double K, double T, double r, double q, double v, int payoff, double *price)
+{
+    if (!price) return fail(MCAMD_ERR_INVALID, "price is NULL");
+    *price = 0.0;
+    if (!(S0 > 0.0) || !(K > 0.0) || !(T > 0.0) || !(v > 0.0) || !std::isfinite(S0) || !std::isfinite(K) ||
+        !std::isfinite(T) || !std::isfinite(v) || !std::isfinite(r) || !std::isfinite(q))
+        return fail(MCAMD_ERR_INVALID, "Black-Scholes needs finite S0, K, T, v > 0 and finite r, q");
+    if (int rc = check_payoff(payoff)) return rc;
+    const double sqrtT = std::sqrt(T);
+    const double d1 = (std::log(S0 / K) + (r - q + 0.5 * v * v) * T) / (v * sqrtT), d2 = d1 - v * sqrtT;
+    const double Sd = S0 * std::exp(-q * T), Kd = K * std::exp(-r * T);
+    *price = payoff == MCAMD_PAYOFF_CALL ? Sd * norm_cdf(d1) - Kd * norm_cdf(d2) : Kd * norm_cdf(-d2) - Sd * norm_cdf(-d1);
+    return MCAMD_OK;
+}
+
+int mcamd_bs_implied_vol_f64(double S0, double K, double T, double r, double q, int payoff, double price, double *vol)
+{
+    if (!vol) return fail(MCAMD_ERR_INVALID, "vol is NULL");
+    *vol = std::nan("");
+    if (!(S0 > 0.0) || !(K > 0.0) || !(T > 0.0) || !std::isfinite(S0) || !std::isfinite(K) || !std::isfinite(T) ||
+        !std::isfinite(r) || !std::isfinite(q) || !std::isfinite(price))
+        return fail(MCAMD_ERR_INVALID, "an implied volatility needs finite S0, K, T > 0 and finite r, q and price");
+    if (int rc = check_payoff(payoff)) return rc;
+    const bool call = payoff == MCAMD_PAYOFF_CALL;
+    const double D = std::exp(-r * T), F = S0 * std::exp((r - q) * T);
+    const double lower = D * std::fmax(call ? F - K : K - F, 0.0);
+    const double upper = call ? S0 * std::exp(-q * T) : K * D;
+    if (!(price > lower) || !(price < upper))
+        return fail(MCAMD_ERR_INVALID, "the price %.17g is not strictly inside the no-arbitrage bounds (%.17g, %.17g)", price,
+                    lower, upper);
+    // The price grows with v from lower to upper: bracket the root, then Newton steps kept inside the bracket and
+    // replaced by a bisection whenever they leave it or shrink it too slowly (plain Newton diverges in the wings,
+    // where the vega vanishes).  f is "not above" at lo and "above or equal" at hi throughout; a NaN counts as not above.
+    double lo = 0.0, hi = 1.0 / std::sqrt(T);
+    for (int grow = 0; grow < 64 && !(bs_value(S0, K, T, r, q, hi, call, nullptr) >= price); ++grow) {
+        lo = hi;
+        hi *= 2.0;
+    }
+    double x = 0.5 * (lo + hi), dx_old = hi - lo, dx = dx_old, vega = 0.0;
+    double f = bs_value(S0, K, T, r, q, x, call, &vega) - price;
+    for (int it = 0; it < 400; ++it) {
+        const bool newton_leaves = !(((x - hi) * vega - f) * ((x - lo) * vega - f) < 0.0);
+        const bool newton_slow = !(std::fabs(2.0 * f) <= std::fabs(dx_old * vega));
+        dx_old = dx;
+        if (newton_leaves || newton_slow) {
+            dx = 0.5 * (hi - lo);
+            x = lo + dx;
+        } else {
+            dx = f / vega;
+            x -= dx;
+        }
+        if (!(std::fabs(dx) > 1e-15 * x)) break;
+        f = bs_value(S0, K, T, r, q, x, call, &vega) - price;
+        if (f >= 0.0) hi = x;
+        else lo = x;
+        if (f == 0.0) break;
+    }
+    *vol = x;
+    return MCAMD_OK;
+}
+
+// Closed form, host.  Same operation order and the same mixed precision as the reference:
+// `0.5 * v * v` and `exp(-r * T)` are evaluated in double and narrowed (inc/BlackandScholes.hpp:37,42).
+float mcamd_cnd_f32(float x)
+{
+    const float p = 0.2316419f;
+    const float b1 = 0.31938153f, b2 = -0.356563782f, b3 = 1.781477937f, b4 = -1.821255978f, b5 = 1.330274429f;
+    const float one_over_sqrt_twopi = 0.39894228f;
+    const float t = 1.0f / (1.0f + p * std::fabs(x));
+    const float tail = one_over_sqrt_twopi * expf(-x * x / 2.0f) * t * (t * (t * (t * (t * b5 + b4) + b3) + b2) + b1);
+    return x >= 0.0f ? 1.0f - tail : tail;
+}
+
+float mcamd_bs_call_f32(float x0, float strike, float T, float r, float sigma)
+{
+    const float sqrtT = sqrtf(T);
+    const float d1 = static_cast<float>(
+        (static_cast<double>(logf(x0 / strike)) + (static_cast<double>(r) + 0.5 * sigma * sigma) * T) /
+        static_cast<double>(sigma * sqrtT));
+    const float d2 = d1 - sigma * sqrtT;
+    const float n1 = mcamd_cnd_f32(d1), n2 = mcamd_cnd_f32(d2);
+    return static_cast<float>(static_cast<double>(x0 * n1) -
+                              static_cast<double>(strike) * std::exp(static_cast<double>(-r * T)) * n2);
+}
+
+double mcamd_bs_call_f64(double x0, double strike, double T, double r, double sigma)
+{
+    const double sqrtT = std::sqrt(T);
+    const double d1 = (std::log(x0 / strike) + (r + 0.5 * sigma * sigma) * T) / (sigma * sqrtT);
+    const double d2 = d1 - sigma * sqrtT;
+    return x0 * norm_cdf(d1) - strike * std::exp(-r * T) * norm_cdf(d2);
+}
+
+}  // extern "C"

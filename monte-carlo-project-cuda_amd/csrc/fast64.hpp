@@ -301,7 +301,7 @@ MC_HD double sin_bits_rotated(uint32_t z, uint32_t w, const D2 *rot_tab, double 
 // terminal price (European payoff) does six fp64 operations per step and looks nothing up until the end; a
 // path that needs St at every step (barrier count, trajectory store) evaluates the value each step — the
 // same expression, so the last stored price and the in-register terminal price are the same bits.
-// Range: |k| < 2^31 over the whole path (the host checks n_steps * max|y|, capi.cpp); ldexp saturates to
+// Range: |k| < 2^31 over the whole path (the host checks n_steps * max|y|, check_request in capi.cpp); ldexp saturates to
 // inf / 0 like exp does.
 // ---------------------------------------------------------------------------------------------
 constexpr int kExpBits = 16;

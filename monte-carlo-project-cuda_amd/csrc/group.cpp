@@ -7,7 +7,7 @@
 // Philox subsequence of a path is its global id, so the result equals the single-GPU result up to fp64
 // summation order.  RCCL is loaded with dlopen when the first group is created: libmcamd.so keeps no link-time
 // dependency on it, and a process that already carries an RCCL (PyTorch ships its own) reuses that one.
-#include "mcamd.h"
+#include "capi_internal.hpp"   // mcamd_set_error_
 #include "greeks.hpp"
 
 #include <hip/hip_runtime_api.h>
@@ -20,8 +20,6 @@
 #include <mutex>
 #include <string>
 #include <vector>
-
-int mcamd_set_error_(int code, const char *msg);  // capi.cpp: records the thread's last error string
 
 namespace {
 

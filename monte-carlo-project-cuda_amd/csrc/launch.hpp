@@ -1,4 +1,4 @@
-// launch.hpp — host-side launcher interface between the C ABI (capi.cpp) and the kernel
+// launch.hpp — host-side launcher interface between the C ABI (capi.cpp, capi_*.cpp) and the kernel
 // translation units.  Launchers only enqueue work on `stream`; they never synchronise or allocate.
 #pragma once
 

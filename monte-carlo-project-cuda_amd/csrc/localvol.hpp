@@ -1,4 +1,4 @@
-// localvol.hpp — host-side interface of the local-volatility kernels (localvol.hip) for the C ABI (capi.cpp).
+// localvol.hpp — host-side interface of the local-volatility kernels (localvol.hip) for the C ABI (capi_localvol.cpp).
 //
 // A local-volatility kernel walks log-Euler paths whose volatility is looked up per step, per lane, in a surface table
 // held in LDS (include/mcamd.h, mcamd_price_localvol), draws the normals of mcamd_price_barrier (same Philox stream =

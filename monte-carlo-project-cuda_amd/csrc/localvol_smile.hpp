@@ -1,4 +1,4 @@
-// localvol_smile.hpp — host-side interface of the smile kernels (localvol_smile.hip) for the C ABI (capi.cpp).
+// localvol_smile.hpp — host-side interface of the smile kernels (localvol_smile.hip) for the C ABI (capi_localvol.cpp).
 //
 // A smile kernel walks mcamd_price_localvol's paths without a barrier (the walk of localvol_device.hpp), stops at up to 32
 // expiry steps and there turns the work a quarter-turn: every lane of a wavefront takes one strike and runs over the

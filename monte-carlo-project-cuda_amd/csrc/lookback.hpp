@@ -1,4 +1,4 @@
-// lookback.hpp — host-side interface of the lookback kernels (lookback.hip) for the C ABI (capi.cpp).
+// lookback.hpp — host-side interface of the lookback kernels (lookback.hip) for the C ABI (capi_pathdep.cpp).
 //
 // A lookback kernel walks the log-space paths of mcamd_price_paths (same Philox stream = global path id, same
 // Exponents), keeps the one running extremum E of X = ln(S / S0) the product needs (include/mcamd.h,

@@ -19,7 +19,7 @@ def lib():
 
 
 def test_american_structs_match_the_header(lib):
-    # static_assert(sizeof(mcamd_american) == 32 && sizeof(mcamd_american_result) == 152) in csrc/capi.cpp
+    # static_assert(sizeof(mcamd_american) == 32 && sizeof(mcamd_american_result) == 152) in csrc/capi_american.cpp
     A, R = capi.American, capi.AmericanResult
     assert C.sizeof(A) == 32 and C.sizeof(R) == 152
     assert (A.exercise_every.offset, A.n_basis.offset, A.reserved.offset, A.n_train.offset, A.train_seed.offset) == \

@@ -37,7 +37,7 @@ def test_header_declares_the_calls_and_structs(lib):
 
 
 def test_structs_match_the_header(lib):
-    # static_assert(sizeof(mcamd_american_dual) == 16 && sizeof(mcamd_american_dual_result) == 104) in csrc/capi.cpp
+    # static_assert(sizeof(mcamd_american_dual) == 16 && sizeof(mcamd_american_dual_result) == 104) in csrc/capi_american.cpp
     D, R = capi.AmericanDual, capi.AmericanDualResult
     assert C.sizeof(D) == 16 and C.sizeof(R) == 104
     assert (D.n_inner.offset, D.reserved.offset, D.inner_seed.offset) == (0, 4, 8)

@@ -50,7 +50,7 @@ def test_header_declares_the_calls_and_the_struct(lib):
 
 
 def test_struct_matches_the_header():
-    # static_assert(sizeof(mcamd_asian) == 24) in csrc/capi.cpp
+    # static_assert(sizeof(mcamd_asian) == 24) in csrc/capi_pathdep.cpp
     A = capi.Asian
     assert C.sizeof(A) == 24
     assert (A.average.offset, A.strike.offset, A.payoff.offset, A.include_spot.offset, A.control.offset,

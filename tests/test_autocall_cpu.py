@@ -51,7 +51,7 @@ def test_header_declares_the_calls_and_the_structs(lib):
 
 
 def test_structs_match_the_header():
-    # static_assert(sizeof(mcamd_autocall) == 632 && sizeof(mcamd_autocall_result) == 112) in csrc/capi.cpp
+    # static_assert(sizeof(mcamd_autocall) == 632 && sizeof(mcamd_autocall_result) == 112) in csrc/capi_multi.cpp
     A, R = capi.Autocall, capi.AutocallResult
     assert C.sizeof(A) == 632 and C.sizeof(R) == 112
     assert (A.n_assets.offset, A.ki_monitoring.offset, A.observe_every.offset, A.first_call_date.offset,

@@ -47,7 +47,7 @@ def test_header_declares_the_calls_and_the_struct(lib):
 
 
 def test_struct_matches_the_header():
-    # static_assert(sizeof(mcamd_autocall_localvol) == 632) in csrc/capi.cpp
+    # static_assert(sizeof(mcamd_autocall_localvol) == 632) in csrc/capi_localvol.cpp
     A, B = capi.AutocallLocalVol, capi.Autocall
     assert C.sizeof(A) == 632 == C.sizeof(B)
     assert [(k if k != "q" else "v", getattr(A, k).offset) for k, _ in A._fields_] == \

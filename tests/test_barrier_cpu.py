@@ -45,7 +45,7 @@ def test_header_declares_the_calls_and_the_struct(lib):
 
 
 def test_struct_matches_the_header():
-    # static_assert(sizeof(mcamd_barrier) == 16) in csrc/capi.cpp
+    # static_assert(sizeof(mcamd_barrier) == 16) in csrc/capi_pathdep.cpp
     Bq = capi.Barrier
     assert C.sizeof(Bq) == 16
     assert (Bq.kind.offset, Bq.payoff.offset, Bq.monitoring.offset, Bq.reserved.offset) == (0, 4, 8, 12)

@@ -47,7 +47,7 @@ def test_header_declares_the_calls_and_the_struct(lib):
 
 
 def test_struct_matches_the_header():
-    # static_assert(sizeof(mcamd_basket) == 728) in csrc/capi.cpp
+    # static_assert(sizeof(mcamd_basket) == 728) in csrc/capi_multi.cpp
     Bk = capi.Basket
     assert C.sizeof(Bk) == 728
     assert (Bk.n_assets.offset, Bk.kind.offset, Bk.payoff.offset, Bk.barrier.offset, Bk.reserved.offset, Bk.S0.offset,

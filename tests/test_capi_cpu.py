@@ -32,6 +32,21 @@ def test_exports_every_declared_symbol(lib):
     assert lib.mcamd_abi_version() == 5
 
 
+def test_every_declared_function_is_a_defined_dynamic_symbol(lib):
+    # the C ABI is split over several sources (csrc/capi*.cpp, closed_forms.cpp, group.cpp): a shared library links with
+    # one of them left out of build.SOURCES, and only its dynamic symbol table shows the functions that went with it
+    import shutil
+    import subprocess
+    nm = shutil.which("nm") or shutil.which("llvm-nm") or "/opt/rocm/llvm/bin/llvm-nm"
+    out = subprocess.check_output([nm, "-D", "--defined-only", capi.LIB_PATH], text=True)
+    defined = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    header = open(os.path.join(ROOT, "include", "mcamd.h")).read()
+    declared = set(re.findall(r"mcamd_[a-z0-9_]+\(", header))
+    assert len(declared) > 80, len(declared)
+    missing = sorted(name[:-1] for name in declared if name[:-1] not in defined)
+    assert not missing, missing
+
+
 def test_slot_counts_describe_the_built_library(lib):
     # bench.py prices the VALU roofline with ISA slot counts (profiles/valu_slots.json); they carry the id of the
     # sources they were counted from, and build() refreshes them: library, sources and counts must agree

@@ -49,7 +49,7 @@ def test_header_declares_the_calls_and_the_structs(lib):
 
 
 def test_structs_match_the_header():
-    # static_assert(sizeof(mcamd_cliquet) == 56 && sizeof(mcamd_cliquet_result) == 96) in csrc/capi.cpp
+    # static_assert(sizeof(mcamd_cliquet) == 56 && sizeof(mcamd_cliquet_result) == 96) in csrc/capi_localvol.cpp
     Q, R = capi.Cliquet, capi.CliquetResult
     assert C.sizeof(Q) == 56 and C.sizeof(R) == 96
     assert [(k, getattr(Q, k).offset) for k, _ in Q._fields_] == [

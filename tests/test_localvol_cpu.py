@@ -54,7 +54,7 @@ def test_header_declares_the_calls_and_the_structs(lib):
 
 
 def test_structs_match_the_header():
-    # static_assert(sizeof(mcamd_localvol_grid) == 24 && sizeof(mcamd_localvol) == 24) in csrc/capi.cpp
+    # static_assert(sizeof(mcamd_localvol_grid) == 24 && sizeof(mcamd_localvol) == 24) in csrc/capi_localvol.cpp
     G, J = capi.LocalVolGrid, capi.LocalVol
     assert C.sizeof(G) == 24 and (G.n_t.offset, G.n_x.offset, G.x_min.offset, G.x_max.offset) == (0, 4, 8, 16)
     assert C.sizeof(J) == 24

@@ -53,7 +53,7 @@ def test_header_declares_the_calls_and_the_structs(lib):
 
 
 def test_structs_match_the_header():
-    # static_assert(sizeof(mcamd_localvol_greeks_job) == 24 && sizeof(mcamd_localvol_greeks) == 472) in csrc/capi.cpp
+    # static_assert(sizeof(mcamd_localvol_greeks_job) == 24 && sizeof(mcamd_localvol_greeks) == 472) in csrc/capi_localvol.cpp
     J, G = capi.LocalVolGreeksJob, capi.LocalVolGreeks
     assert C.sizeof(J) == 24
     assert (J.payoff.offset, J.n_vega_buckets.offset, J.q.offset, J.gamma_bump.offset) == (0, 4, 8, 16)

@@ -46,7 +46,7 @@ def test_header_declares_the_calls_and_the_struct(lib):
 
 
 def test_struct_matches_the_header():
-    # static_assert(sizeof(mcamd_lookback) == 16) in csrc/capi.cpp
+    # static_assert(sizeof(mcamd_lookback) == 16) in csrc/capi_pathdep.cpp
     Lb = capi.Lookback
     assert C.sizeof(Lb) == 16
     assert (Lb.strike.offset, Lb.payoff.offset, Lb.monitoring.offset, Lb.reserved.offset) == (0, 4, 8, 12)
