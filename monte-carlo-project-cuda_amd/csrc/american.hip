@@ -119,8 +119,7 @@ __global__ __launch_bounds__(kBlock) void am_price_kernel(AmPriceArgs<T> a, doub
     const PhiloxKeys key = PhiloxKeys::make(a.seed);
     const StepConsts<T> c = resident(a.c);
     const bool put = a.put != 0;
-    const uint32_t n_full = c.n_sim / NB;         // Philox blocks whose NB steps are all simulated
-    const uint32_t rem = c.n_sim - n_full * NB;   // steps of the last, partial block
+    const StepBlocks blocks = step_blocks<NB>(c.n_sim);
     const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
     double acc[kAmPriceRecord];
 #pragma unroll
@@ -153,24 +152,10 @@ __global__ __launch_bounds__(kBlock) void am_price_kernel(AmPriceArgs<T> a, doub
                 }
             }
         };
-        bool running = true;
-        for (uint32_t b = 0; b < n_full; ++b) {
-            Exponents<T> ex;
-            ex.fill(m, c, key, subsequence, b);
-#pragma unroll
-            for (int j = 0; j < NB; ++j) step(ex.x[j]);
-            if (__builtin_amdgcn_ballot_w64(live) == 0) {   // every lane's path has stopped
-                running = false;
-                break;
-            }
-        }
-        if (rem && running) {
-            Exponents<T> ex;
-            ex.fill(m, c, key, subsequence, n_full);
-#pragma unroll
-            for (int j = 0; j < NB - 1; ++j)
-                if (static_cast<uint32_t>(j) < rem) step(ex.x[j]);
-        }
+        Exponents<T> ex;
+        walk_steps<NB>(
+            blocks, [&](uint32_t b) { ex.fill(m, c, key, subsequence, b); }, [&](uint32_t, int j) { step(ex.x[j]); },
+            [&] { return __builtin_amdgcn_ballot_w64(live) == 0; });   // every lane's path has stopped
         acc[0] += y;
         acc[1] = __builtin_fma(y, y, acc[1]);
         if (ex_date != 0) {

@@ -7,7 +7,7 @@
 // summed in fp64 in ascending i; A = sum / m, S_T = P_n.  Geometric: L = sum_i X_i in the path precision,
 // G = exp_of_logreturn(S0, L / m), S_T = exp_of_logreturn(S0, X_n): no exponential inside the step loop.
 //
-// The loop restates that of lookback_kernel: per Philox block one Exponents<T>::fill; per step, geometric: two adds;
+// The loop is walk_steps (mc_device.hpp): per Philox block one Exponents<T>::fill; per step, geometric: two adds;
 // arithmetic: one PathState<T> step (the exponential of the step is what the product costs), in fp32 one widening, and
 // one fp64 add.  The controlled job (ARITH and GEO) does both on the same exponents.  Strike type, payoff and
 // include_spot are wave-uniform selects outside the step loop.
@@ -40,8 +40,7 @@ __global__ __launch_bounds__(kBlock) void asian_kernel(AsianArgs<T> a, double *_
     const PhiloxKeys key = PhiloxKeys::make(a.seed);
     const StepConsts<T> c = resident(a.c);
     const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
-    const uint32_t n_full = c.n_sim / NB;
-    const uint32_t rem = c.n_sim - n_full * NB;
+    const StepBlocks blocks = step_blocks<NB>(c.n_sim);
     // one sample from an average and a terminal price, both already fp64
     auto sample = [&](double avg, double St) {
         const double d = a.floating ? (a.put ? avg - St : St - avg) : (a.put ? a.K - avg : avg - a.K);
@@ -65,17 +64,8 @@ __global__ __launch_bounds__(kBlock) void asian_kernel(AsianArgs<T> a, double *_
                 L += X;
             }
         };
-        for (uint32_t k = 0; k < n_full; ++k) {
-            ex.fill(m, c, key, subsequence, k);
-#pragma unroll
-            for (int j = 0; j < NB; ++j) step(ex.x[j]);
-        }
-        if (rem) {
-            ex.fill(m, c, key, subsequence, n_full);
-#pragma unroll
-            for (int j = 0; j < NB - 1; ++j)
-                if (static_cast<uint32_t>(j) < rem) step(ex.x[j]);
-        }
+        walk_steps<NB>(
+            blocks, [&](uint32_t k) { ex.fill(m, c, key, subsequence, k); }, [&](uint32_t, int j) { step(ex.x[j]); });
         double y, g = 0.0;
         if (GEO) {
             // the same routine for both prices: one step without the spot has L / m == X bit for bit, so G == S_T

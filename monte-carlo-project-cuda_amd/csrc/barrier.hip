@@ -8,11 +8,11 @@
 // exp(-q) < 2^-54 / 2^-25 and 1 - exp(-q) rounds to 1 anyway).  The sample is w h(S_T) (knock-out) or (1 - w) h(S_T)
 // (knock-in), formed once per path in fp64.
 //
-// The loop is the log-space window form of simulate_sample: per Philox block one Exponents<T>::fill, per step
-// acc += x, one subtract for d, the strict compare.  The bridge factor costs one multiply-multiply-compare per step
-// and an exponential only where a live lane has q < Q; that skip is decided per wavefront (one ballot), and paths
-// spend most of their steps far from the barrier.  A knock-out wavefront leaves the step loop at the first block end
-// where every lane is knocked; a knock-in runs to maturity, because it needs S_T.
+// The loop is walk_steps (mc_device.hpp) on the log-space window step of simulate_sample: per Philox block one
+// Exponents<T>::fill, per step acc += x, one subtract for d, the strict compare.  The bridge factor costs one
+// multiply-multiply-compare per step and an exponential only where a live lane has q < Q; that skip is decided per
+// wavefront (one ballot), and paths spend most of their steps far from the barrier.  A knock-out wavefront leaves the
+// step loop at the first block end where every lane is knocked; a knock-in runs to maturity, because it needs S_T.
 #include "barrier.hpp"
 #include "path_consts.hpp"
 
@@ -40,8 +40,7 @@ __global__ __launch_bounds__(kBlock) void barrier_kernel(BarrierArgs<T> a, doubl
     const PhiloxKeys key = PhiloxKeys::make(a.seed);
     const StepConsts<T> c = resident(a.c);
     const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
-    const uint32_t n_full = c.n_sim / NB;
-    const uint32_t rem = c.n_sim - n_full * NB;
+    const StepBlocks blocks = step_blocks<NB>(c.n_sim);
     const T d0 = UP ? c.logB : -c.logB;   // |b|: the spot is strictly on the live side (checked on the host)
     double acc4[kBarrierRecord] = {0.0, 0.0, 0.0, 0.0};
     for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < a.n_local; i += stride) {
@@ -51,8 +50,6 @@ __global__ __launch_bounds__(kBlock) void barrier_kernel(BarrierArgs<T> a, doubl
         T w = T(1);          // the bridge factors so far (CONT); the hits are in `alive`
         bool alive = true;
         uint32_t live = 0;   // steps this path entered not yet knocked
-        uint32_t steps_run = c.n_sim;
-        bool rem_live = true;
         Exponents<T> ex;
         auto step = [&](T x) {
             live += alive ? 1u : 0u;
@@ -70,22 +67,9 @@ __global__ __launch_bounds__(kBlock) void barrier_kernel(BarrierArgs<T> a, doubl
                 d_prev = d;
             }
         };
-        for (uint32_t k = 0; k < n_full; ++k) {
-            ex.fill(m, c, key, subsequence, k);
-#pragma unroll
-            for (int j = 0; j < NB; ++j) step(ex.x[j]);
-            if (OUT && __builtin_amdgcn_ballot_w64(alive) == 0) {
-                steps_run = (k + 1) * NB;
-                rem_live = false;
-                break;
-            }
-        }
-        if (rem && rem_live) {
-            ex.fill(m, c, key, subsequence, n_full);
-#pragma unroll
-            for (int j = 0; j < NB - 1; ++j)
-                if (static_cast<uint32_t>(j) < rem) step(ex.x[j]);
-        }
+        const uint32_t steps_run = walk_steps<NB>(
+            blocks, [&](uint32_t k) { ex.fill(m, c, key, subsequence, k); }, [&](uint32_t, int j) { step(ex.x[j]); },
+            [&] { return OUT && __builtin_amdgcn_ballot_w64(alive) == 0; });
         const T St = exp_of_logreturn(c.S_start, acc, m);
         T h = a.put ? c.K - St : St - c.K;
         h = h > T(0) ? h : T(0);

@@ -49,8 +49,7 @@ __global__ __launch_bounds__(kBlock) void cliquet_kernel(CliquetArgs<T> a, doubl
     const T mu_dt = lv_resident(a.mu_dt), half_dt = lv_resident(a.half_dt), sqrt_dt = lv_resident(a.sqrt_dt);
     const T lo = lv_resident(a.lo), hi = lv_resident(a.hi), exp_scale = lv_resident(a.exp_scale);
     const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
-    const uint32_t n_full = a.n_steps / NB;
-    const uint32_t rem = a.n_steps - n_full * NB;
+    const StepBlocks blocks = step_blocks<NB>(a.n_steps);
     // an infinite bound never binds and counts nothing, whatever the arithmetic made of A
     const bool has_floor = a.g_lo > -__builtin_huge_val(), has_cap = a.g_hi < __builtin_huge_val();
     double acc5[kCliquetRecord] = {0.0, 0.0, 0.0, 0.0, 0.0};
@@ -84,17 +83,9 @@ __global__ __launch_bounds__(kBlock) void cliquet_kernel(CliquetArgs<T> a, doubl
                 next_reset += a.reset_every;
             }
         };
-        for (uint32_t kb = 0; kb < n_full; ++kb) {
-            nz.fill(m, key, subsequence, kb);
-#pragma unroll
-            for (int j = 0; j < NB; ++j) step(nz.z[j], kb * NB + j);
-        }
-        if (rem) {
-            nz.fill(m, key, subsequence, n_full);
-#pragma unroll
-            for (int j = 0; j < NB - 1; ++j)
-                if (static_cast<uint32_t>(j) < rem) step(nz.z[j], n_full * NB + j);
-        }
+        walk_steps<NB>(
+            blocks, [&](uint32_t kb) { nz.fill(m, key, subsequence, kb); },
+            [&](uint32_t kb, int j) { step(nz.z[j], kb * NB + j); });
         double A;
         if (KIND == kCliquetSum) A = static_cast<double>(sum);
         else if (KIND == kCliquetCompound) A = static_cast<double>(exp_of_logreturn(T(1), sum * exp_scale, m)) - 1.0;

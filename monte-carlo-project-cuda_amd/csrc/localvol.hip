@@ -47,8 +47,7 @@ __global__ __launch_bounds__(kBlock) void localvol_kernel(LocalVolArgs<T> a, dou
     const LvAxis<T> axis = lv_resident(a.surf.axis);
     const T mu_dt = lv_resident(a.mu_dt), half_dt = lv_resident(a.half_dt), sqrt_dt = lv_resident(a.sqrt_dt);
     const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
-    const uint32_t n_full = a.n_steps / NB;
-    const uint32_t rem = a.n_steps - n_full * NB;
+    const StepBlocks blocks = step_blocks<NB>(a.n_steps);
     const T d0 = UP ? a.b : -a.b;   // |b|: the spot is strictly on the live side (checked on the host)
     double acc4[kLocalVolRecord] = {0.0, 0.0, 0.0, 0.0};
     for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < a.n_local; i += stride) {
@@ -58,8 +57,6 @@ __global__ __launch_bounds__(kBlock) void localvol_kernel(LocalVolArgs<T> a, dou
         T w = T(1);          // the bridge factors so far (CONT); the hits are in `alive`
         bool alive = true;
         uint32_t live = 0;   // steps this path entered not yet knocked
-        uint32_t steps_run = a.n_steps;
-        bool rem_live = true;
         LvRow row{0, 0};
         Normals<T> nz;
         auto step = [&](T z) {
@@ -81,22 +78,9 @@ __global__ __launch_bounds__(kBlock) void localvol_kernel(LocalVolArgs<T> a, dou
                 }
             }
         };
-        for (uint32_t kb = 0; kb < n_full; ++kb) {
-            nz.fill(m, key, subsequence, kb);
-#pragma unroll
-            for (int j = 0; j < NB; ++j) step(nz.z[j]);
-            if (BAR != 0 && OUT && __builtin_amdgcn_ballot_w64(alive) == 0) {
-                steps_run = (kb + 1) * NB;
-                rem_live = false;
-                break;
-            }
-        }
-        if (rem && rem_live) {
-            nz.fill(m, key, subsequence, n_full);
-#pragma unroll
-            for (int j = 0; j < NB - 1; ++j)
-                if (static_cast<uint32_t>(j) < rem) step(nz.z[j]);
-        }
+        const uint32_t steps_run = walk_steps<NB>(
+            blocks, [&](uint32_t kb) { nz.fill(m, key, subsequence, kb); }, [&](uint32_t, int j) { step(nz.z[j]); },
+            [&] { return BAR != 0 && OUT && __builtin_amdgcn_ballot_w64(alive) == 0; });
         const T St = exp_of_logreturn(a.S0, X * a.exp_scale, m);
         T h = a.put ? a.K - St : St - a.K;
         h = h > T(0) ? h : T(0);

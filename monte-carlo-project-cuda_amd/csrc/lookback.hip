@@ -9,7 +9,7 @@
 // The minimum is the mirror image.  The sample is formed once per path in fp64 from S_T = S0 e^{X_n} and
 // S_E = S0 e^{E_n}, both through exp_of_logreturn, so a path whose extremum is its last point has S_E == S_T.
 //
-// The loop restates the log-space loop of simulate_sample: per Philox block one Exponents<T>::fill and — continuous —
+// The loop is walk_steps (mc_device.hpp) in log space: per Philox block one Exponents<T>::fill and — continuous —
 // one more Philox block at 2^63 + k for the step uniforms; per step acc += x, one max / min, and for the bridge two
 // subtracts, two multiplies and a compare for q, a logarithm, a fused multiply-add, a root, two adds, a multiply, one
 // max / min and a select.  The bridge is predicated per lane, not skipped per wavefront: at 50 steps a half to three
@@ -92,8 +92,7 @@ __global__ __launch_bounds__(kBlock) void lookback_kernel(LookbackArgs<T> a, dou
     const StepConsts<T> c = resident(a.c);
     const T kq = resident_t(a.kq), kb = resident_t(a.kb), q_cut = resident_t(a.q_cut);
     const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
-    const uint32_t n_full = c.n_sim / NB;
-    const uint32_t rem = c.n_sim - n_full * NB;
+    const StepBlocks blocks = step_blocks<NB>(c.n_sim);
     double acc4[kLookbackRecord] = {0.0, 0.0, 0.0, 0.0};
     for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < a.n_local; i += stride) {
         const uint64_t subsequence = a.path_offset + i;
@@ -119,19 +118,13 @@ __global__ __launch_bounds__(kBlock) void lookback_kernel(LookbackArgs<T> a, dou
                 live += close_by ? 1u : 0u;
             }
         };
-        for (uint32_t k = 0; k < n_full; ++k) {
-            ex.fill(m, c, key, subsequence, k);
-            if (CONT) bl.fill(m, key, subsequence, k);
-#pragma unroll
-            for (int j = 0; j < NB; ++j) step(ex.x[j], CONT ? bl.l[j] : T(0));
-        }
-        if (rem) {
-            ex.fill(m, c, key, subsequence, n_full);
-            if (CONT) bl.fill(m, key, subsequence, n_full);
-#pragma unroll
-            for (int j = 0; j < NB - 1; ++j)
-                if (static_cast<uint32_t>(j) < rem) step(ex.x[j], CONT ? bl.l[j] : T(0));
-        }
+        walk_steps<NB>(
+            blocks,
+            [&](uint32_t k) {
+                ex.fill(m, c, key, subsequence, k);
+                if (CONT) bl.fill(m, key, subsequence, k);
+            },
+            [&](uint32_t, int j) { step(ex.x[j], CONT ? bl.l[j] : T(0)); });
         // the same routine for both prices: E == acc bit for bit gives S_E == S_T, and a floating sample of exactly 0
         const double St = static_cast<double>(exp_of_logreturn(c.S_start, acc, m));
         const double Se = static_cast<double>(exp_of_logreturn(c.S_start, E, m));

@@ -514,6 +514,52 @@ struct Exponents<double> {
     }
 };
 
+// The walk of a one-path-per-thread kernel over its path's steps, one Philox block of NB steps (Exponents<T> or
+// Normals<T>::kPerBlock) at a time: n_full whole blocks, then the first rem steps of block n_full.
+struct StepBlocks {
+    uint32_t n_steps, n_full, rem;
+};
+template <int NB>
+__device__ __forceinline__ StepBlocks step_blocks(uint32_t n_steps)
+{
+    const uint32_t n_full = n_steps / NB;
+    return StepBlocks{n_steps, n_full, n_steps - n_full * NB};
+}
+
+struct NeverLeave {
+    __device__ __forceinline__ bool operator()() const { return false; }
+};
+
+// fill(k) draws block k, step(k, j) takes its step j (step k NB + j of the path), and leave() — asked after every whole
+// block, wave-uniform — says that nothing is left for the wavefront to do; a kernel whose wavefronts run every step
+// passes none.  Returns the steps the wavefront ran: n_steps, or (k + 1) NB when it left after block k.
+// The counts are copied into locals: read through `b` at every use, the partial block of several fp32 kernels compiles
+// to other selects and compares than the loop written out in the kernel does (tools/isa_diff.py).
+template <int NB, typename Fill, typename Step, typename Leave = NeverLeave>
+__device__ __forceinline__ uint32_t walk_steps(const StepBlocks &b, Fill fill, Step step, Leave leave = Leave{})
+{
+    const uint32_t n_full = b.n_full, rem = b.rem;
+    uint32_t steps_run = b.n_steps;
+    bool rem_live = true;
+    for (uint32_t k = 0; k < n_full; ++k) {
+        fill(k);
+#pragma unroll
+        for (int j = 0; j < NB; ++j) step(k, j);
+        if (leave()) {
+            steps_run = (k + 1) * NB;
+            rem_live = false;
+            break;
+        }
+    }
+    if (rem && rem_live) {
+        fill(n_full);
+#pragma unroll
+        for (int j = 0; j < NB - 1; ++j)
+            if (static_cast<uint32_t>(j) < rem) step(n_full, j);
+    }
+    return steps_run;
+}
+
 // Sum of the normals of one Philox block, for the paths that need nothing else of them (a window-less path in log
 // space: ln(S_T / S_0) = n drift + vol (z_1 + ... + z_n)).  A Box-Muller pair is (r sin a, r cos a), so its sum is
 //     r (sin a + cos a) = sqrt(2) r sin(a + pi/4):

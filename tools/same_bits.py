@@ -1,18 +1,29 @@
 #!/usr/bin/env python3
 """Do two builds of the library compute the same bits?  One fresh worker process per library (MCAMD_LIB) runs a fixed
 list of small jobs on the kernels that walk a local-volatility surface — mcamd_price_localvol, mcamd_price_localvol_smile,
-mcamd_price_autocall_localvol — and on mcamd_price_barrier's continuous monitoring, and prints a SHA-256 per job over
-the per-path outputs (samples or spots) and the result record without its two timings; this process compares the lines.
+mcamd_price_autocall_localvol, mcamd_price_cliquet, mcamd_price_localvol_greeks — and on the one-path-per-thread kernels
+of constant volatility — mcamd_price_barrier, mcamd_price_lookback, mcamd_price_asian, the likelihood-ratio and pathwise
+mcamd_price_greeks, mcamd_price_american, mcamd_american_upper_bound — and prints a SHA-256 per job over the per-path
+outputs where the call has them (samples, spots, continuation values, coefficients) and the result record without its
+timings; this process compares the lines.
     python3 tools/same_bits.py LIB_A LIB_B          # on an MI355X; exit status 1 on any difference
 Every job is 1000 paths (four workgroups, a partial last wavefront) of a 2^40-path job, from path 5003 and from path
 2^33 + 5003, in both precisions.  Step counts 1, 2, 3, 5, 7 and 13 leave every remainder of a Philox block of 2 and of
-4 normals; the surfaces are a flat 1 x 2, a skewed 3 x 5 (n_t divides no step count but 3), a 16 x 5 (more rows than
-steps), the full 16 x 128 table and an axis so narrow that the paths clamp on both sides."""
+4 normals; the one-path-per-thread kernels also take 4 and 8, a path of whole blocks only in fp32 too; where a product
+ties the count to a period (reset_every, exercise_every) the counts still leave no whole block, no remainder and a
+remainder.  The surfaces are a
+flat 1 x 2, a skewed 3 x 5 (n_t divides no step count but 3), a 16 x 5 (more rows than steps), the full 16 x 128 table
+and an axis so narrow that the paths clamp on both sides.  Two jobs make whole wavefronts leave the step loop after a
+whole block: a knock-out barrier beside the spot on 100 000 paths (its work_steps fall short of the full count), and an
+American put so deep in the money (K = 10 S0) that every priced path is exercised at the first date, step 4 of 48 —
+the worker refuses to go on otherwise — so that every wavefront of the pricing kernel leaves 44 steps early."""
 import hashlib, importlib, json, math, os, struct, subprocess, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N, OFFSETS, STEPS = 1000, (5003, 2 ** 33 + 5003), (1, 2, 3, 5, 7, 13)
-TIMINGS = ("kernel_ms", "total_ms")
+STEPS_WALK = (1, 2, 3, 4, 5, 7, 8, 13)   # of the one-path-per-thread kernels: 4 and 8 are whole blocks in fp32 as well
+# (n_steps, period): reset_every of a cliquet, exercise_every of an American option
+PERIODS = ((1, 1), (2, 1), (2, 2), (3, 1), (3, 3), (4, 2), (5, 1), (7, 7), (8, 1), (8, 4), (13, 1), (13, 13))
 
 
 def surfaces(ctx):
@@ -39,9 +50,11 @@ def worker():
         h = hashlib.sha256()
         for a in arrays:
             h.update(a.cpu().numpy().tobytes() if hasattr(a, "cpu") else a.tobytes())
-        for key, value in res.as_dict().items():
-            if key not in TIMINGS:
-                h.update(struct.pack("<d", float(value)))
+        for key, _ in res._fields_:   # the record without its timings; an array field value by value
+            if not key.endswith("_ms"):
+                value = getattr(res, key)
+                for v in (value if hasattr(value, "__len__") else (value,)):
+                    h.update(struct.pack("<d", float(v)))
         print(json.dumps({"job": name, "sha256": h.hexdigest()}))
 
     def sim(n_steps, prec, off, n=N):
@@ -56,7 +69,7 @@ def worker():
                 (kind, mon, pay) for kind in range(4) for mon in (capi.MONITOR_DISCRETE, capi.MONITOR_CONTINUOUS)
                 for pay in (capi.PAYOFF_CALL, capi.PAYOFF_PUT)]
             for sname, s in surf.items():
-                for n_steps in STEPS:
+                for n_steps in STEPS_WALK:
                     for kind, mon, pay in kinds:
                         up = kind in (capi.BARRIER_UP_OUT, capi.BARRIER_UP_IN)
                         opt = capi.make_option(S0=100.0, K=100.0, B=110.0 if up else 90.0, r=0.05, v=0.0, T=1.0)
@@ -91,12 +104,90 @@ def worker():
                     ac = capi.make_autocall_localvol(q, corr, 3, 1.0, 0.02, 0.8 if ki else 0.0, ki, call_step_down=0.01)
                     res = ctx.price_autocall_localvol(opt, sim(12, prec, off), ac, ss, out.zero_())
                     emit(f"autocall {tag} d={d} on {'+'.join(names)} ki={ki}", res, out)
-            # mcamd_price_barrier, continuous monitoring: the bridge factor
-            for kind in range(4):
-                up = kind in (capi.BARRIER_UP_OUT, capi.BARRIER_UP_IN)
-                opt = capi.make_option(S0=100.0, K=100.0, B=110.0 if up else 90.0, r=0.05, v=0.2, T=1.0)
-                res = ctx.price_barrier(opt, sim(13, prec, off), capi.make_barrier(kind, capi.PAYOFF_CALL), out.zero_())
-                emit(f"barrier {tag} kind={kind}", res, out)
+            # mcamd_price_cliquet: every kind, resets inside a block, at its end and at the path's end only
+            opt = capi.make_option(S0=100.0, K=0.0, r=0.05, v=0.0, T=1.0)
+            for sname in ("skew3x5", "full16x128"):
+                for n_steps, every in PERIODS:
+                    for kind in (capi.CLIQUET_SUM, capi.CLIQUET_COMPOUND, capi.CLIQUET_VARIANCE):
+                        local = {} if kind == capi.CLIQUET_VARIANCE else dict(local_floor=-0.03, local_cap=0.05)
+                        cq = capi.make_cliquet(kind, every, 1 + (n_steps // every) // 3, global_floor=0.0, global_cap=0.2,
+                                               q=0.02, **local)
+                        res = ctx.price_cliquet(opt, sim(n_steps, prec, off), cq, surf[sname], out.zero_())
+                        emit(f"cliquet {tag} {sname} n={n_steps} every={every} kind={kind}", res, out)
+            # mcamd_price_localvol_greeks: with and without gamma's two bumped walks and the vega buckets
+            opt = capi.make_option(S0=100.0, K=100.0, r=0.05, v=0.0, T=1.0)
+            for sname in ("skew3x5", "full16x128"):
+                for n_steps in STEPS_WALK:
+                    for n_b, bump in ((0, 0.0), (0, 0.01), (3, 0.0), (8, 0.01)):
+                        each = torch.zeros((6 + n_b) * N, dtype=torch.float64, device="cuda")
+                        job = capi.make_localvol_greeks_job(capi.PAYOFF_PUT if n_b == 3 else capi.PAYOFF_CALL, n_b, 0.02, bump)
+                        res = ctx.price_localvol_greeks(opt, sim(n_steps, prec, off), job, surf[sname], each)
+                        emit(f"localvol greeks {tag} {sname} n={n_steps} buckets={n_b} bump={bump}", res, each)
+            # mcamd_price_barrier: every kind, monitoring and payoff
+            for n_steps in STEPS_WALK:
+                for kind in range(4):
+                    up = kind in (capi.BARRIER_UP_OUT, capi.BARRIER_UP_IN)
+                    opt = capi.make_option(S0=100.0, K=100.0, B=110.0 if up else 90.0, r=0.05, v=0.2, T=1.0)
+                    for mon in (capi.MONITOR_DISCRETE, capi.MONITOR_CONTINUOUS):
+                        for pay in (capi.PAYOFF_CALL, capi.PAYOFF_PUT):
+                            res = ctx.price_barrier(opt, sim(n_steps, prec, off), capi.make_barrier(kind, pay, mon), out.zero_())
+                            emit(f"barrier {tag} n={n_steps} kind={kind} mon={mon} pay={pay}", res, out)
+            # ... and a knock-out with the barrier beside the spot: whole wavefronts leave after a whole block
+            n_ko = 100_000
+            opt = capi.make_option(S0=100.0, K=100.0, B=99.9, r=0.0, v=0.4, T=1.0)
+            many = torch.empty(n_ko, dtype=dtype[prec], device="cuda")
+            for mon in (capi.MONITOR_DISCRETE, capi.MONITOR_CONTINUOUS):
+                res = ctx.price_barrier(opt, sim(51, prec, off, n_ko), capi.make_barrier(capi.BARRIER_DOWN_OUT, capi.PAYOFF_CALL, mon),
+                                        many.zero_())
+                emit(f"barrier {tag} early exit mon={mon} work={res.work_steps:.0f} of {64.0 * 51 * ((n_ko + 63) // 64):.0f}",
+                     res, many)
+            # mcamd_price_lookback: both monitorings, strikes and payoffs
+            opt = capi.make_option(S0=100.0, K=105.0, r=0.05, v=0.25, T=1.0)
+            for n_steps in STEPS_WALK:
+                for mon in (capi.MONITOR_DISCRETE, capi.MONITOR_CONTINUOUS):
+                    for strike in (capi.LOOKBACK_FLOATING, capi.LOOKBACK_FIXED):
+                        for pay in (capi.PAYOFF_CALL, capi.PAYOFF_PUT):
+                            res = ctx.price_lookback(opt, sim(n_steps, prec, off), capi.make_lookback(strike, pay, mon), out.zero_())
+                            emit(f"lookback {tag} n={n_steps} mon={mon} strike={strike} pay={pay}", res, out)
+            # mcamd_price_asian: arithmetic, geometric, and arithmetic with the geometric control
+            for n_steps in STEPS_WALK:
+                for avg, control in ((capi.ASIAN_ARITHMETIC, capi.ASIAN_CONTROL_NONE), (capi.ASIAN_GEOMETRIC, capi.ASIAN_CONTROL_NONE),
+                                     (capi.ASIAN_ARITHMETIC, capi.ASIAN_CONTROL_GEOMETRIC)):
+                    for strike in (capi.ASIAN_FIXED, capi.ASIAN_FLOATING):
+                        for pay in (capi.PAYOFF_CALL, capi.PAYOFF_PUT):
+                            asian = capi.make_asian(avg, strike, pay, include_spot=(n_steps + pay) % 2, control=control)
+                            res = ctx.price_asian(opt, sim(n_steps, prec, off), asian, out.zero_())
+                            emit(f"asian {tag} n={n_steps} avg={avg} control={control} strike={strike} pay={pay}", res, out)
+            # mcamd_price_greeks: likelihood ratio without and with the bullet window (it closes: P2 = 1), and pathwise
+            for n_steps in STEPS_WALK:
+                plain = capi.make_option(S0=100.0, K=100.0, r=0.05, v=0.2, T=1.0)
+                window = capi.make_option(S0=100.0, K=100.0, B=101.0, P1=0, P2=1, use_window=1, r=0.05, v=0.2, T=1.0)
+                for name, opt, method in (("lr", plain, capi.GREEKS_LIKELIHOOD_RATIO), ("lr window", window, capi.GREEKS_LIKELIHOOD_RATIO),
+                                          ("pathwise", plain, capi.GREEKS_PATHWISE)):
+                    emit(f"greeks {tag} {name} n={n_steps}", ctx.price_greeks(opt, sim(n_steps, prec, off), method))
+            # mcamd_price_american and mcamd_american_upper_bound on its rule; K = 1000 at 48 steps: so deep in the money
+            # that every path is exercised at the first date, so every wavefront leaves after the block that holds step 4
+            for n_steps, every in PERIODS + ((48, 4),):
+                for K in (100.0, 1000.0):
+                    if K == 1000.0 and n_steps != 48:
+                        continue
+                    opt = capi.make_option(S0=100.0, K=K, r=0.06, v=0.3, T=1.0)
+                    s, am = sim(n_steps, prec, off), capi.make_american(capi.PAYOFF_PUT, every, n_train=4096, train_seed=99)
+                    work = torch.empty(capi.american_workspace_bytes(am, s), dtype=torch.uint8, device="cuda")
+                    res, rule = ctx.price_american(opt, s, am, work, coeffs=True)
+                    note = ""
+                    if K == 1000.0:
+                        t_first = every * opt.T / n_steps
+                        if res.n_early != N or abs(res.sum_t_exercise - N * t_first) > 1e-9 * N:
+                            raise SystemExit(f"american {tag}: {res.n_early} of {N} paths exercised early, mean date "
+                                             f"{res.sum_t_exercise / max(res.n_early, 1)}: not all at the first, {t_first}")
+                        note = f" early exit: all {res.n_early} paths exercised at step {every}"
+                    emit(f"american {tag} n={n_steps} every={every} K={K}{note}", res, rule)
+                    dual = capi.make_american_dual(n_inner=96, inner_seed=55)
+                    work = torch.empty(capi.american_dual_workspace_bytes(am, s, dual), dtype=torch.uint8, device="cuda")
+                    cont = torch.zeros((n_steps // every) * N, dtype=torch.float64, device="cuda")
+                    res = ctx.american_upper_bound(opt, s, am, dual, rule, work, cont)
+                    emit(f"american dual {tag} n={n_steps} every={every} K={K} work={res.work_steps:.0f}", res, cont)
     print(json.dumps({"build_id": capi.build_id()}))
     for s in surf.values():
         s.close()
@@ -124,6 +215,9 @@ def main():
     differ = sorted(job for job in set(a) | set(b) if a.get(job) != b.get(job))
     for job in differ:
         print("DIFFERS", job)
+    for job in sorted(a):   # the jobs whose names carry what shows that wavefronts did leave early
+        if "early exit" in job:
+            print("ran", job)
     print(f"same_bits: {len(a)} jobs, {len(differ)} differ; builds {id_a} and {id_b}")
     if n_lines != [len(a), len(b)]:
         print("same_bits: two jobs share a name", file=sys.stderr)
