@@ -1385,6 +1385,111 @@ int mcamd_price_cliquet_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const m
 int mcamd_cliquet_price_f64(int kind, double T, double r, double q, uint32_t n_periods, uint32_t first_period,
                             const double *period_vol, double local_floor, double local_cap, double *price);
 
+/* ---- European options under Heston stochastic volatility ----
+ * Additive to ABI version 5: first carried by the build that ships csrc/heston.hip (no struct of an earlier call
+ * changed, so MCAMD_ABI_VERSION stays 5; a caller finds out with dlsym).  The one model here whose volatility has a
+ * random driver of its own: it keeps the forward smile that a local-volatility surface flattens.
+ *   Model.  dS / S = (r - q) dt + sqrt(v) dW1,  dv = kappa (theta - v) dt + xi sqrt(v) dW2,  d<W1, W2> = rho dt.
+ *   Scheme.  MCAMD_HESTON_FULL_TRUNCATION: the full-truncation Euler scheme in the log-price (Lord, Koekkoek, van Dijk
+ *       2010).  The raw variance v may go below zero; the drift, the diffusion and the mean reversion read
+ *       v+ = max(v, 0).  The step map is continuous in every input (max, sqrt and fused multiply-adds: no branch on a
+ *       moment ratio, no inverse distribution function), so two precisions of one path never take different formulas.
+ *       The scheme is weakly first order in dt.  scheme is a field so that another one can arrive without an ABI change.
+ *   Per path.  X_0 = 0 (X = ln(S / S0) in natural units), v_0 = v0, n = n_steps, dt = T / n.  r, T, S0 and K come from
+ *       opt, the rest from the job; opt->v and opt->B are ignored.
+ *   Draws.  z = normal i of Philox blocks 0, 1, .. of the path's subsequence (the GLOBAL path id): exactly the normal
+ *       mcamd_price_barrier and mcamd_price_localvol draw for step i (4 per block in fp32, 2 per block in fp64, whole
+ *       blocks, the remainder block as there).  z' = normal i of blocks 2^63, 2^63 + 1, .. of the same key and
+ *       subsequence, by the same Box-Muller: where mcamd_price_lookback keeps its step uniforms.  Nothing else is drawn.
+ *   Per step i = 0 .. n - 1, in one precision (the path precision) throughout:
+ *       v+ = max(v_i, 0),  s = sqrt(v+)            fp32: the hardware square root (1 ulp); fp64: correctly rounded
+ *       w  = fma(rho, z, sqrt(1 - rho^2) z')        sqrt(1 - rho^2) formed in double on the host and narrowed once:
+ *                                                   0 at rho = +-1, where w = rho z exactly
+ *       X_{i+1} = X_i + fma(s sqrt(dt), z, fma(-v+, dt / 2, (r - q) dt))
+ *       v_{i+1} = v_i + fma(s (xi sqrt(dt)), w, fma(-v+, kappa dt, kappa theta dt))
+ *       These are the contractions the kernels use, written as explicit fused operations (the X line is
+ *       mcamd_price_localvol's move with s^2 replaced by v+).  The constants (r - q) dt, dt / 2, sqrt(dt), kappa dt,
+ *       kappa theta dt, xi sqrt(dt), rho and sqrt(1 - rho^2) are formed in double on the host and narrowed once.
+ *       xi = 0 (v deterministic), kappa = 0 and rho = +-1 are legal.  With xi = 0 and kappa = 0 the path is that of
+ *       mcamd_price_localvol on a flat surface at sqrt(v0), normal for normal.
+ *   Per path, after the loop.  S_T = S0 e^{X_n} through the exponential that ends a local-volatility path;
+ *       h = max(+-(S_T - K), 0) in the path precision;  y = h widened to double.
+ *       trunc = the number of steps entered with v_i < 0 (a 32-bit counter);  rv = (1 / n) sum_i v+_i, the path's
+ *       average variance, summed in the path precision in step order, the factor 1 / n applied in fp64.
+ *   price = exp(-rT) mean(y), std_err as in mcamd_finalize.
+ * d_samples (nullable, device): n_paths_local values of the path precision; [local path] receives y.
+ * d_state (nullable, device): 2 n_paths_local values of the path precision; [local path] receives S_T and
+ * [n_paths_local + local path] the raw v_n, which may be negative.
+ * res: price .. n as mcamd_result; truncated_steps = sum of trunc over the shard (a double: it adds over shards);
+ * mean_variance = mean of rv over the shard; work_steps = 64 x the steps each wavefront ran, always the full count
+ * (there is no early exit).  The enqueue form leaves {sum, sumsq, truncated_steps, sum of rv, 0, n} in d_stats:
+ * mcamd_finalize_stats serves it and mcamd_enqueued_kernel_ms covers it.  A sample depends on its global path id alone,
+ * so shards add element by element and one all-reduce of the 6 doubles serves multi-GPU use.  One launch, one fixed
+ * order of summation: two runs of one job give the same bits.
+ * Requirements (MCAMD_ERR_INVALID before any device work, in this order): opt, sim, heston, res non-NULL; payoff and
+ * scheme in range; reserved == 0; q, v0, kappa, theta, xi, rho finite; v0, kappa, theta, xi >= 0; |rho| <= 1; r finite;
+ * use_window, P1, P2, Ik, Sk, Tk and opt->dt all 0; sim->flags 0 or MCAMD_FLAG_LOG_SPACE; what mcamd_price_paths refuses
+ * on sim (its fp64 exponent-range bound at the drift r - q alone: the variance is random, and no bound on the request
+ * covers it); S0 > 0 and K > 0; then the context.  An empty shard returns zeros and launches nothing; its enqueue form
+ * writes a zero record in stream order.
+ * Left out on purpose: the QE scheme and exact simulation, barriers and path-dependent payoffs, Greeks, a term
+ * structure of the parameters, a smile call, a mcamd_group_* form and a shim name (the reference has no such model).
+ * New. */
+#define MCAMD_HESTON_FULL_TRUNCATION 0
+
+typedef struct mcamd_heston {   /* 64 bytes */
+    int32_t payoff;          /* MCAMD_PAYOFF_* */
+    int32_t scheme;          /* MCAMD_HESTON_FULL_TRUNCATION */
+    double q;                /* continuous dividend yield */
+    double v0;               /* the variance at t = 0, >= 0 */
+    double kappa;            /* speed of mean reversion, >= 0 */
+    double theta;            /* long-run variance, >= 0 */
+    double xi;               /* volatility of the variance, >= 0 */
+    double rho;              /* correlation of the two drivers, in [-1, 1] */
+    double reserved;         /* must be 0 */
+} mcamd_heston;
+
+typedef struct mcamd_heston_result {   /* 96 bytes */
+    double price;            /* exp(-rT) * mean(y) */
+    double std_err;
+    double ci_lo, ci_hi;     /* 95 % confidence interval */
+    double sum, sumsq;       /* the shard's raw fp64 sums of the undiscounted samples */
+    uint64_t n;              /* paths */
+    double truncated_steps;  /* lane-steps entered with v < 0 */
+    double mean_variance;    /* mean over the shard of the paths' average variance (1 / n_steps) sum v+ */
+    double work_steps;       /* 64 x the steps each wavefront ran: always the full count */
+    float kernel_ms;         /* HIP-event time of the kernel (it finishes its own sum: the whole call's device work) */
+    float total_ms;
+    uint32_t grid;           /* launch shape the engine chose */
+    uint32_t block;
+} mcamd_heston_result;
+
+int mcamd_price_heston(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_heston *heston,
+                       void *d_samples, void *d_state, mcamd_heston_result *res);
+int mcamd_price_heston_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_heston *heston,
+                               void *d_samples, void *d_state, double *d_stats);
+/* Host closed form of the model itself (not of the scheme, whose bias is first order in dt).  With F = S0 e^{(r-q)T},
+ * D = e^{-rT}, k = ln(F / K) and phi the characteristic function of ln(S_T / F) in the branch-cut-safe form (Albrecher,
+ * Mayer, Schoutens, Tistaert 2007, "the little Heston trap"), rearranged so that nothing is divided by xi^2:
+ *   call = D (F - sqrt(F K) / pi  int_0^U Re[e^{iuk} phi(u - i/2)] / (u^2 + 1/4) du)   (Lewis 2000);  put by parity.
+ * The rule: composite Gauss-Legendre, 16 nodes on each panel of width 1/2, over [0, U] with U the first of 32, 64, ..,
+ * 4096 at which the envelope |phi(U - i/2)| / (U^2 + 1/4) is below 1e-15: 1024 nodes at U = 32, 131072 at most.
+ * |phi(u - i/2)| <= E[e^{x/2}] <= 1, so whatever the parameters the dropped tail is at most D sqrt(F K) / (pi U); it
+ * is that large only where the envelope has not fallen by U = 4096: a total variance near 0, or rho = +-1 (at
+ * xi = 2 kappa rho the characteristic function does not decay at all).  Halving the panel or doubling U moves the
+ * inputs of tests/test_heston_cpu.py by less than 1e-9 of S0, and an adaptive quadrature of the textbook form agrees
+ * with them to 3e-13.
+ * Below xi = MCAMD_HESTON_XI_MIN the variance is taken as deterministic: Black-Scholes (mcamd_bs_price_f64) at the
+ * average variance theta + (v0 - theta)(1 - e^{-kappa T}) / (kappa T) (v0 at kappa = 0; the discounted intrinsic value
+ * of the forward where that is 0).  The model's price has a slope in xi at 0 (the skew rho buys: up to 5 per unit
+ * of xi at a spot of 100 on the tests' inputs), so the step across the threshold is that slope times 1e-8: below
+ * 1e-9 S0.
+ * Refuses a NULL price, payoff out of range, what mcamd_price_heston refuses of q, v0, kappa, theta, xi and rho,
+ * S0 <= 0, K <= 0, T <= 0 and a non-finite S0, K, T or r. */
+#define MCAMD_HESTON_XI_MIN 1e-8
+int mcamd_heston_price_f64(double S0, double K, double T, double r, double q, double v0, double kappa, double theta,
+                           double xi, double rho, int payoff, double *price);
+
 /* Host: discount + mean + standard error + 95% CI from (sum, sumsq, n) — after an all-reduce
  * over shards, or directly.  Fills price/std_err/ci_* (and copies sum/sumsq/n) in *res. */
 int mcamd_finalize(double sum, double sumsq, uint64_t n, double r, double T, mcamd_result *res);

@@ -42,6 +42,8 @@ LOCALVOL_GREEKS_MAX_BUCKETS = 8
 LOCALVOL_GREEK_NAMES = ("price", "delta", "gamma", "vega", "rho", "rho_q")
 LOCALVOL_GREEKS_STATS = 32   # doubles of the record: six (sum, sumsq) pairs, eight bucket pairs, n, zeros
 CLIQUET_SUM, CLIQUET_COMPOUND, CLIQUET_VARIANCE = 0, 1, 2
+HESTON_FULL_TRUNCATION = 0
+HESTON_XI_MIN = 1e-8   # below it heston_price takes the variance as deterministic
 BASKET_MAX_ASSETS = 8
 BASKET_ARITHMETIC, BASKET_GEOMETRIC, BASKET_BEST_OF, BASKET_WORST_OF = 0, 1, 2, 3
 BASKET_NO_BARRIER, BASKET_DOWN_OUT, BASKET_DOWN_IN, BASKET_UP_OUT, BASKET_UP_IN = 0, 1, 2, 3, 4
@@ -71,6 +73,7 @@ EXPORTS = [
     "mcamd_price_autocall_localvol", "mcamd_price_autocall_localvol_enqueue",
     "mcamd_price_localvol_greeks", "mcamd_price_localvol_greeks_enqueue", "mcamd_finalize_localvol_greeks_stats",
     "mcamd_price_cliquet", "mcamd_price_cliquet_enqueue", "mcamd_cliquet_price_f64",
+    "mcamd_price_heston", "mcamd_price_heston_enqueue", "mcamd_heston_price_f64",
 ]
 
 
@@ -249,6 +252,25 @@ class CliquetResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class Heston(C.Structure):
+    """mcamd_heston: the payoff, the scheme (HESTON_FULL_TRUNCATION), the dividend yield and the model's parameters
+    mcamd_price_heston prices a European option with."""
+    _fields_ = [("payoff", C.c_int32), ("scheme", C.c_int32), ("q", C.c_double), ("v0", C.c_double),
+                ("kappa", C.c_double), ("theta", C.c_double), ("xi", C.c_double), ("rho", C.c_double),
+                ("reserved", C.c_double)]
+
+
+class HestonResult(C.Structure):
+    """mcamd_heston_result"""
+    _fields_ = [("price", C.c_double), ("std_err", C.c_double), ("ci_lo", C.c_double), ("ci_hi", C.c_double),
+                ("sum", C.c_double), ("sumsq", C.c_double), ("n", C.c_uint64), ("truncated_steps", C.c_double),
+                ("mean_variance", C.c_double), ("work_steps", C.c_double), ("kernel_ms", C.c_float),
+                ("total_ms", C.c_float), ("grid", C.c_uint32), ("block", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class Smile(C.Structure):
     """mcamd_smile: the payoff of every node, the numbers of expiries and strikes, and the dividend yield
     mcamd_price_localvol_smile prices a strike-by-expiry set of vanillas with."""
@@ -376,6 +398,10 @@ def load() -> C.CDLL:
     L.mcamd_price_cliquet_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Cliquet), vp, vp, vp]
     L.mcamd_cliquet_price_f64.argtypes = [i32, f64, f64, f64, C.c_uint32, C.c_uint32, C.POINTER(f64), f64, f64,
                                           C.POINTER(f64)]
+    L.mcamd_price_heston.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Heston), vp, vp,
+                                     C.POINTER(HestonResult)]
+    L.mcamd_price_heston_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Heston), vp, vp, vp]
+    L.mcamd_heston_price_f64.argtypes = [f64] * 10 + [i32, C.POINTER(f64)]
     L.mcamd_localvol_sigma_f64.argtypes = [C.POINTER(LocalVolGrid), C.POINTER(f64), C.c_uint32, C.c_uint32, f64,
                                            C.POINTER(f64)]
     L.mcamd_bs_price_f64.argtypes = [f64, f64, f64, f64, f64, f64, i32, C.POINTER(f64)]
@@ -562,6 +588,19 @@ def cliquet_price(kind, T, r, q, period_vol, first_period=1, local_floor=-math.i
     out = C.c_double()
     _check(load().mcamd_cliquet_price_f64(kind, T, r, q, len(period_vol), first_period, vols, local_floor, local_cap,
                                           C.byref(out)))
+    return out.value
+
+
+def make_heston(payoff=PAYOFF_CALL, q=0.0, v0=0.04, kappa=2.0, theta=0.04, xi=0.3, rho=-0.7,
+                scheme=HESTON_FULL_TRUNCATION) -> Heston:
+    return Heston(payoff, scheme, q, v0, kappa, theta, xi, rho, 0.0)
+
+
+def heston_price(S0, K, T, r, q, v0, kappa, theta, xi, rho, payoff=PAYOFF_CALL) -> float:
+    """Closed form of a European option under Heston (mcamd_heston_price_f64): the model's price, which the
+    full-truncation scheme of price_heston approaches at first order in the step."""
+    out = C.c_double()
+    _check(load().mcamd_heston_price_f64(S0, K, T, r, q, v0, kappa, theta, xi, rho, payoff, C.byref(out)))
     return out.value
 
 
@@ -831,6 +870,22 @@ class Context:
         finalize_stats)."""
         _check(self._L.mcamd_price_cliquet_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(cliquet), surface._h,
                                                    _ptr(samples), _ptr(stats)))
+
+    def price_heston(self, opt: Option, sim: Sim, heston: Heston, samples=None, state=None) -> HestonResult:
+        """European option under Heston stochastic volatility, full-truncation Euler in the log-price
+        (mcamd_price_heston); r, T, S0 and K come from opt, opt.v and opt.B are ignored.  samples: optional device
+        tensor of n_paths_local values of the path precision that receives each path's undiscounted sample; state:
+        optional device tensor of 2 x n_paths_local such values that receives S_T, then the raw final variance."""
+        res = HestonResult()
+        _check(self._L.mcamd_price_heston(self._h, C.byref(opt), C.byref(sim), C.byref(heston), _ptr(samples),
+                                          _ptr(state), C.byref(res)))
+        return res
+
+    def price_heston_enqueue(self, opt: Option, sim: Sim, heston: Heston, stats, samples=None, state=None) -> None:
+        """Asynchronous: leaves {sum, sumsq, truncated_steps, sum of the paths' average variance, 0, n} in the device
+        tensor `stats` (>= 6 doubles; finalize_stats)."""
+        _check(self._L.mcamd_price_heston_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(heston), _ptr(samples),
+                                                  _ptr(state), _ptr(stats)))
 
     def price_localvol_greeks(self, opt: Option, sim: Sim, job: LocalVolGreeksJob, surface: "LocalVolSurface",
                               samples=None) -> LocalVolGreeks:

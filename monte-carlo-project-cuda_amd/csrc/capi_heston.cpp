@@ -1,0 +1,122 @@
+// capi_heston.cpp — the calls of the C ABI that walk Heston stochastic-volatility paths: European options under the
+// full-truncation Euler scheme.  One prepare step (the refusals and the job) and its synchronous and enqueue forms; the
+// refusals keep the order of the other families: the request alone, then the context.
+#include "capi_internal.hpp"
+#include "heston.hpp"
+
+static_assert(sizeof(mcamd_heston) == 64 && sizeof(mcamd_heston_result) == 96,
+              "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
+static_assert(MCAMD_HESTON_FULL_TRUNCATION == mcamd::kHestonFullTruncation, "the kernels' scheme is MCAMD_HESTON_*");
+
+using namespace mcamd::capi;
+
+namespace mcamd::capi {
+
+// What the Heston call and its closed form refuse of the model's parameters.
+int check_heston_model(double q, double v0, double kappa, double theta, double xi, double rho)
+{
+    if (!std::isfinite(q) || !std::isfinite(v0) || !std::isfinite(kappa) || !std::isfinite(theta) || !std::isfinite(xi) ||
+        !std::isfinite(rho))
+        return fail(MCAMD_ERR_INVALID, "the Heston parameters must be finite: q = %g, v0 = %g, kappa = %g, theta = %g, "
+                                       "xi = %g, rho = %g", q, v0, kappa, theta, xi, rho);
+    if (v0 < 0.0 || kappa < 0.0 || theta < 0.0 || xi < 0.0)
+        return fail(MCAMD_ERR_INVALID, "Heston needs v0, kappa, theta and xi >= 0, got v0 = %g, kappa = %g, theta = %g, "
+                                       "xi = %g", v0, kappa, theta, xi);
+    if (std::fabs(rho) > 1.0) return fail(MCAMD_ERR_INVALID, "the correlation rho must lie in [-1, 1], got %g", rho);
+    return MCAMD_OK;
+}
+
+}  // namespace mcamd::capi
+
+namespace {
+
+// The Heston calls.  The kernel always finishes its own sum (one_path_per_thread_grid caps the grid); every refusal
+// depends on the request alone and comes before the context is looked at.  opt->v and opt->B are ignored.
+template <typename Drive>
+int prepare_heston(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_heston *hs, void *d_samples,
+                   void *d_state, Drive drive)
+{
+    if (!opt || !sim || !hs) return fail(MCAMD_ERR_INVALID, "opt, sim and heston must be non-NULL");
+    if (int rc = check_payoff(hs->payoff)) return rc;
+    if (hs->scheme != MCAMD_HESTON_FULL_TRUNCATION)
+        return fail(MCAMD_ERR_INVALID, "heston->scheme must be MCAMD_HESTON_FULL_TRUNCATION (0), got %d", hs->scheme);
+    if (hs->reserved != 0.0) return fail(MCAMD_ERR_INVALID, "heston->reserved must be 0, got %g", hs->reserved);
+    if (int rc = check_heston_model(hs->q, hs->v0, hs->kappa, hs->theta, hs->xi, hs->rho)) return rc;
+    if (!std::isfinite(opt->r)) return fail(MCAMD_ERR_INVALID, "option parameters must be finite with T > 0");
+    const double mu = opt->r - hs->q;
+    // as the local-volatility calls: on a copy whose ignored fields are harmless.  It carries no volatility of its
+    // own, so check_spot_start sees v = 1 and check_request v = 0, which leaves the drift r - q alone in the fp64
+    // exponent-range bound (the variance is random: no bound on the request can cover it)
+    mcamd_option seen = *opt;
+    seen.B = 0.0;
+    seen.v = 1.0;
+    if (int rc = check_spot_start("Heston", false, &seen, sim)) return rc;
+    seen.v = 0.0;
+    seen.r = mu;
+    if (int rc = check_request(&seen, sim)) return rc;
+    if (!(opt->S0 > 0.0) || !(opt->K > 0.0))
+        return fail(MCAMD_ERR_INVALID, "Heston options need S0 > 0 and K > 0 (S0 = %g, K = %g)", opt->S0, opt->K);
+    if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
+    if (sim->n_paths_local == 0) return drive(empty_call());
+    mcamd::HestonJob job;
+    job.seed = sim->seed;
+    job.path_offset = sim->path_offset;
+    job.n_local = sim->n_paths_local;
+    job.n_steps = sim->n_steps;
+    job.precision = sim->precision;
+    job.scheme = hs->scheme;
+    job.S0 = opt->S0;
+    job.K = opt->K;
+    job.mu = mu;
+    job.dt = even_dt(opt, sim);
+    job.v0 = hs->v0;
+    job.kappa = hs->kappa;
+    job.theta = hs->theta;
+    job.xi = hs->xi;
+    job.rho = hs->rho;
+    job.put = hs->payoff == MCAMD_PAYOFF_PUT;
+    job.d_samples = d_samples;
+    job.d_state = d_state;
+    const uint32_t grid = mcamd::one_path_per_thread_grid(job.n_local);
+    return drive(DeviceCall{job.n_local, grid, mcamd::kHestonRecord, 6, Finish::kFolded,
+                            [&](const mcamd::FinishSpec &fs) {
+                                return mcamd::launch_heston(job, ctx->d_partials, grid, fs, ctx->stream);
+                            }});
+}
+
+}  // namespace
+
+extern "C" {
+
+int mcamd_price_heston(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_heston *heston,
+                       void *d_samples, void *d_state, mcamd_heston_result *res)
+{
+    if (!res) return fail(MCAMD_ERR_INVALID, "opt, sim, heston and res must be non-NULL");
+    std::memset(res, 0, sizeof *res);
+    return prepare_heston(ctx, opt, sim, heston, d_samples, d_state, [&](const auto &call) {
+        return run_sync(ctx, call, res, [&](const double *rec) {
+            // {sum, sumsq, lane-steps entered with v < 0, sum of the paths' average variance}
+            const uint64_t n = sim->n_paths_local;
+            const Estimate e = estimate(rec[0], rec[1], n, std::exp(-opt->r * opt->T));
+            res->sum = rec[0];
+            res->sumsq = rec[1];
+            res->n = n;
+            res->price = e.value;
+            res->std_err = e.std_err;
+            set_ci(res);
+            res->truncated_steps = rec[2];
+            res->mean_variance = rec[3] / static_cast<double>(n);
+            // there is no early exit: every wavefront runs every step
+            res->work_steps = 64.0 * static_cast<double>((n + 63) / 64) * static_cast<double>(sim->n_steps);
+        });
+    });
+}
+
+int mcamd_price_heston_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_heston *heston,
+                               void *d_samples, void *d_state, double *d_stats)
+{
+    return prepare_heston(ctx, opt, sim, heston, d_samples, d_state,
+                          [&](const auto &call) { return run_enqueue(ctx, call, d_stats); });
+}
+
+}  // extern "C"

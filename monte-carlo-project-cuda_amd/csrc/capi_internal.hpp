@@ -73,6 +73,8 @@ int check_localvol_grid(const mcamd_localvol_grid *grid, const double *h_sigma, 
 int check_cliquet_kind(int kind);
 int check_cliquet_local(double local_floor, double local_cap);
 int check_cliquet_kind_bounds(int kind, double local_floor, double local_cap);
+// capi_heston.cpp
+int check_heston_model(double q, double v0, double kappa, double theta, double xi, double rho);
 // closed_forms.cpp
 int asian_geometric_price(double S0, double K, double T, double r, double v, uint32_t n_steps, int include_spot,
                           int strike, int payoff, double *price);
@@ -204,7 +206,8 @@ struct Estimate {
 };
 Estimate estimate(double sum, double sumsq, uint64_t n, double disc);
 
-template <typename Result>   // mcamd_result, mcamd_american_result, mcamd_autocall_result, mcamd_cliquet_result
+template <typename Result>   // mcamd_result, mcamd_american_result, mcamd_autocall_result, mcamd_cliquet_result,
+                             // mcamd_heston_result
 void set_ci(Result *res)
 {
     res->ci_lo = res->price - kZ95 * res->std_err;

@@ -5,6 +5,7 @@
 #include "capi_internal.hpp"
 
 #include <algorithm>
+#include <complex>
 
 using namespace mcamd::capi;
 
@@ -57,6 +58,72 @@ int asian_geometric_price(double S0, double K, double T, double r, double v, uin
 }
 
 }  // namespace mcamd::capi
+
+namespace {
+
+using cplx = std::complex<double>;
+
+// e^x - 1 for a complex x without the cancellation at small |x|
+cplx c_expm1(cplx x)
+{
+    const double a = x.real(), b = x.imag(), sh = std::sin(0.5 * b);
+    return {std::expm1(a) * std::cos(b) - 2.0 * sh * sh, std::exp(a) * std::sin(b)};
+}
+
+// ln(1 + z) / z for a complex z, 1 at z = 0 (Kahan's quotient: the rounding of 1 + z cancels)
+cplx c_log1p_over(cplx z)
+{
+    const cplx w = 1.0 + z;
+    if (w == cplx(1.0, 0.0)) return 1.0 - 0.5 * z;
+    return std::log(w) / (w - 1.0);
+}
+
+// ln E[e^{iu x}] of x = ln(S_T / F) under Heston in the branch-cut-safe form (Albrecher, Mayer, Schoutens, Tistaert
+// 2007), rearranged so that nothing is divided by xi^2.  With A = u^2 + iu, b = kappa - rho xi iu, d = sqrt(b^2 + xi^2 A)
+// (principal root, Re d >= 0), the textbook (b - d) / xi^2 is -A / (b + d) (b^2 - d^2 = -xi^2 A: no cancellation),
+// g = (b - d) / (b + d) = -xi^2 A / (b + d)^2, E = e^{-dT}, and
+//     ln phi = kappa theta [ -A T / (b + d) - 2 ln(1 + z) / xi^2 ] - v0 A (1 - E) / ((b + d)(1 - g E)),
+//     z = g (1 - E) / (1 - g),   ln(1 + z) / xi^2 = [ln(1 + z) / z] [-A (1 - E) / ((b + d)^2 (1 - g))].
+// It stays finite down to xi = 0 unless kappa is 0 as well (b + d = 0), which the caller's limit serves.
+cplx heston_log_cf(cplx u, double T, double v0, double kappa, double theta, double xi, double rho)
+{
+    const cplx iu = cplx(0.0, 1.0) * u, A = u * u + iu;
+    const cplx b = kappa - rho * xi * iu, d = std::sqrt(b * b + xi * xi * A), bd = b + d;
+    const cplx q = -A / bd, g = xi * xi * q / bd;
+    const cplx one_minus_E = -c_expm1(-d * T), E = 1.0 - one_minus_E;
+    const cplx z = g * one_minus_E / (1.0 - g);
+    const cplx log_over_xi2 = c_log1p_over(z) * (q * one_minus_E / (bd * (1.0 - g)));
+    return kappa * theta * (q * T - 2.0 * log_over_xi2) + v0 * q * one_minus_E / (1.0 - g * E);
+}
+
+constexpr int kGlNodes = 16;          // Gauss-Legendre nodes per panel
+constexpr double kHestonPanel = 0.5;  // panel width in u
+constexpr double kHestonRangeMin = 32.0, kHestonRangeMax = 4096.0;
+constexpr double kHestonEnvelope = 1e-15;
+
+// nodes and weights of the 16-point Gauss-Legendre rule on [-1, 1]: Newton steps on P_16 from the Chebyshev guess
+void gauss_legendre(double x[kGlNodes], double w[kGlNodes])
+{
+    for (int i = 0; i < kGlNodes; ++i) {
+        double t = std::cos(M_PI * (i + 0.75) / (kGlNodes + 0.5)), dp = 1.0;
+        for (int it = 0; it < 100; ++it) {
+            double p0 = 1.0, p1 = t;
+            for (int k = 2; k <= kGlNodes; ++k) {
+                const double p2 = ((2.0 * k - 1.0) * t * p1 - (k - 1.0) * p0) / k;
+                p0 = p1;
+                p1 = p2;
+            }
+            dp = kGlNodes * (t * p1 - p0) / (t * t - 1.0);
+            const double step = p1 / dp;
+            t -= step;
+            if (std::fabs(step) < 1e-16) break;
+        }
+        x[i] = t;
+        w[i] = 2.0 / ((1.0 - t * t) * dp * dp);
+    }
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -306,6 +373,54 @@ int mcamd_bs_price_f64(double S0, double K, double T, double r, double q, double
     const double d1 = (std::log(S0 / K) + (r - q + 0.5 * v * v) * T) / (v * sqrtT), d2 = d1 - v * sqrtT;
     const double Sd = S0 * std::exp(-q * T), Kd = K * std::exp(-r * T);
     *price = payoff == MCAMD_PAYOFF_CALL ? Sd * norm_cdf(d1) - Kd * norm_cdf(d2) : Kd * norm_cdf(-d2) - Sd * norm_cdf(-d1);
+    return MCAMD_OK;
+}
+
+// Lewis's single integral on the line Im u = -1/2, where the integrand has no pole and decays fastest:
+//     call = D (F - sqrt(F K) / pi  int_0^inf Re[e^{iuk} phi(u - i/2)] / (u^2 + 1/4) du),  k = ln(F / K).
+int mcamd_heston_price_f64(double S0, double K, double T, double r, double q, double v0, double kappa, double theta,
+                           double xi, double rho, int payoff, double *price)
+{
+    if (!price) return fail(MCAMD_ERR_INVALID, "price is NULL");
+    *price = 0.0;
+    if (int rc = check_payoff(payoff)) return rc;
+    if (int rc = check_heston_model(q, v0, kappa, theta, xi, rho)) return rc;
+    if (!(S0 > 0.0) || !(K > 0.0) || !(T > 0.0) || !std::isfinite(S0) || !std::isfinite(K) || !std::isfinite(T) ||
+        !std::isfinite(r))
+        return fail(MCAMD_ERR_INVALID, "the Heston closed form needs finite S0, K, T > 0 and a finite r");
+    const bool call = payoff == MCAMD_PAYOFF_CALL;
+    const double D = std::exp(-r * T), F = S0 * std::exp((r - q) * T);
+    if (xi < MCAMD_HESTON_XI_MIN) {
+        // v is deterministic: Black-Scholes at the average variance theta + (v0 - theta)(1 - e^{-kappa T}) / (kappa T)
+        const double kT = kappa * T;
+        const double mean_v = theta + (v0 - theta) * (kT > 0.0 ? -std::expm1(-kT) / kT : 1.0);
+        *price = mean_v > 0.0 ? bs_value(S0, K, T, r, q, std::sqrt(mean_v), call, nullptr)
+                              : D * std::fmax(call ? F - K : K - F, 0.0);
+        return MCAMD_OK;
+    }
+    const double k = std::log(F / K);
+    const auto integrand = [&](double u) {
+        const cplx lnphi = heston_log_cf(cplx(u, -0.5), T, v0, kappa, theta, xi, rho);
+        return (std::exp(lnphi + cplx(0.0, u * k))).real() / (u * u + 0.25);
+    };
+    // the range: the first of 32, 64, .. 4096 at which the integrand's envelope |phi(u - i/2)| / (u^2 + 1/4) is below 1e-15
+    double U = kHestonRangeMin;
+    while (U < kHestonRangeMax &&
+           std::exp(heston_log_cf(cplx(U, -0.5), T, v0, kappa, theta, xi, rho).real()) / (U * U + 0.25) >= kHestonEnvelope)
+        U *= 2.0;
+    double x[kGlNodes], w[kGlNodes];
+    gauss_legendre(x, w);
+    const int panels = static_cast<int>(U / kHestonPanel);
+    double integral = 0.0;
+    for (int p = 0; p < panels; ++p) {
+        const double mid = (p + 0.5) * kHestonPanel;
+        double s = 0.0;
+        for (int i = 0; i < kGlNodes; ++i) s += w[i] * integrand(mid + 0.5 * kHestonPanel * x[i]);
+        integral += 0.5 * kHestonPanel * s;
+    }
+    const double c = D * (F - std::sqrt(F * K) / M_PI * integral);
+    if (!std::isfinite(c)) return fail(MCAMD_ERR_INVALID, "the Heston integral is not finite at these parameters");
+    *price = call ? c : c - D * (F - K);
     return MCAMD_OK;
 }
 

@@ -1,0 +1,125 @@
+// heston.hip — European options under Heston stochastic volatility, full-truncation Euler in the log-price, for gfx950
+// (both path precisions).
+//
+// Definitions (include/mcamd.h, mcamd_price_heston): X_i = ln(S_i / S0) in NATURAL-log units and the raw variance v_i,
+// moved by heston_device.hpp's heston_move.  Step i takes the normal z of the constant- and local-volatility kernels
+// (normal i of Philox blocks 0, 1, .. of the path's subsequence) for the log-price and a second one, z' = normal i of
+// blocks 2^63, 2^63 + 1, .. of the same subsequence (where lookback.hip keeps its step uniforms), for the variance:
+// a block of the walk is two Philox blocks and two Box-Muller fills.  The path ends as localvol.hip's does, with one
+// exponential.
+//
+// Beside the sample a path leaves two diagnostics of the scheme: how many steps it entered with v < 0 (a 32-bit
+// counter, widened at the end) and its average variance (1 / n) sum v+_i (summed in the path precision in step order,
+// scaled in fp64).  There is no table in LDS beyond what MathCtx<T> needs and no early exit.
+#include "heston.hpp"
+#include "heston_device.hpp"
+
+namespace mcamd {
+
+// The variance normals' block of a step block: same key and subsequence, 2^63 beyond (n_steps is 32-bit: the
+// log-price normals never get there).
+constexpr uint64_t kHestonVarianceBlocks = 1ull << 63;
+
+template <typename T>
+struct HestonArgs {
+    HestonConsts<T> c;
+    T exp_scale;              // exponent units per natural-log unit (log2 e in fp32, 65536 / ln 2 in fp64)
+    T v0;
+    T K, S0;
+    double inv_n;             // 1 / n_steps
+    int put;
+    uint32_t n_steps;
+    uint64_t seed;
+    uint64_t path_offset;
+    uint64_t n_local;
+    T *samples;               // nullable
+    T *state;                 // nullable: S_T at [i], v_n at [n_local + i]
+    GridFinish fin;
+};
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void heston_kernel(HestonArgs<T> a, double *__restrict__ partials)
+{
+    constexpr int NB = Normals<T>::kPerBlock;
+    const MathCtx<T> m = MathCtx<T>::init();
+    const PhiloxKeys key = PhiloxKeys::make(a.seed);
+    const HestonConsts<T> c = heston_resident(a.c);
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
+    const StepBlocks blocks = step_blocks<NB>(a.n_steps);
+    double acc4[kHestonRecord] = {0.0, 0.0, 0.0, 0.0};
+    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < a.n_local; i += stride) {
+        const uint64_t subsequence = a.path_offset + i;
+        T X = T(0);           // ln(S / S0), natural units
+        T v = a.v0;           // the raw variance
+        T v_sum = T(0);       // sum of v+ over the steps
+        uint32_t trunc = 0;   // steps entered with v < 0
+        Normals<T> nz, nv;
+        walk_steps<NB>(
+            blocks,
+            [&](uint32_t kb) {
+                nz.fill(m, key, subsequence, kb);
+                nv.fill(m, key, subsequence, kHestonVarianceBlocks + kb);
+            },
+            [&](uint32_t, int j) {
+                trunc += v < T(0) ? 1u : 0u;
+                v_sum += heston_move(X, v, nz.z[j], nv.z[j], c);
+            });
+        const T St = exp_of_logreturn(a.S0, X * a.exp_scale, m);
+        T h = a.put ? a.K - St : St - a.K;
+        h = h > T(0) ? h : T(0);
+        const double y = static_cast<double>(h);
+        if (a.samples) a.samples[i] = h;
+        if (a.state) {
+            a.state[i] = St;
+            a.state[a.n_local + i] = v;
+        }
+        acc4[0] += y;
+        acc4[1] = __builtin_fma(y, y, acc4[1]);
+        acc4[2] += static_cast<double>(trunc);
+        acc4[3] += static_cast<double>(v_sum) * a.inv_n;
+    }
+    block_sumN<kBlock, kHestonRecord>(acc4);
+    grid_finish<kBlock, kHestonRecord>(acc4, partials, a.fin);
+}
+
+template <typename T>
+static hipError_t launch_heston_t(const HestonJob &j, double *d_partials, uint32_t grid, const FinishSpec &fs,
+                                  hipStream_t stream)
+{
+    const double sqrt_dt = std::sqrt(j.dt);
+    HestonArgs<T> a;
+    a.c.mu_dt = static_cast<T>(j.mu * j.dt);
+    a.c.half_dt = static_cast<T>(0.5 * j.dt);
+    a.c.sqrt_dt = static_cast<T>(sqrt_dt);
+    a.c.kappa_dt = static_cast<T>(j.kappa * j.dt);
+    a.c.kappa_theta_dt = static_cast<T>(j.kappa * j.theta * j.dt);
+    a.c.xi_sqrt_dt = static_cast<T>(j.xi * sqrt_dt);
+    a.c.rho = static_cast<T>(j.rho);
+    a.c.rho_c = static_cast<T>(std::sqrt(1.0 - j.rho * j.rho));
+    a.exp_scale = static_cast<T>(sizeof(T) == 4 ? 1.4426950408889634 : f64::kExpScale);
+    a.v0 = static_cast<T>(j.v0);
+    a.K = static_cast<T>(j.K);
+    a.S0 = static_cast<T>(j.S0);
+    a.inv_n = 1.0 / static_cast<double>(j.n_steps);
+    a.put = j.put ? 1 : 0;
+    a.n_steps = j.n_steps;
+    a.seed = j.seed;
+    a.path_offset = j.path_offset;
+    a.n_local = j.n_local;
+    a.samples = static_cast<T *>(j.d_samples);
+    a.state = static_cast<T *>(j.d_state);
+    a.fin = GridFinish{fs.out, fs.ticket, fs.n_value};
+    hipLaunchKernelGGL((heston_kernel<T>), dim3(grid), dim3(kBlock), 0, stream, a, d_partials);
+    return hipGetLastError();
+}
+
+hipError_t launch_heston(const HestonJob &job, double *d_partials, uint32_t grid, const FinishSpec &finish,
+                         hipStream_t stream)
+{
+    if (!finish_ok(finish, grid)) return hipErrorInvalidValue;
+    if (job.scheme != kHestonFullTruncation || job.n_steps == 0 || job.n_local == 0) return hipErrorInvalidValue;
+    return job.precision == 32 ? launch_heston_t<float>(job, d_partials, grid, finish, stream)
+                               : launch_heston_t<double>(job, d_partials, grid, finish, stream);
+}
+
+}  // namespace mcamd

@@ -1,0 +1,67 @@
+// heston_device.hpp — the step of a Heston path under the full-truncation Euler scheme in the log-price, for any kernel
+// that walks such paths (heston.hip today; barriers, Asians and cliquets under Heston can reuse it): the step constants
+// and the move of one step.
+//
+// Definitions (include/mcamd.h, mcamd_price_heston): X = ln(S / S0) in NATURAL-log units, v the raw variance, which may
+// go below zero; v+ = max(v, 0) is what the drift, the diffusion and the mean reversion read.  With the step's two
+// independent normals z (the log-price's) and z' (the variance's own),
+//     w = fma(rho, z, sqrt(1 - rho^2) z')
+//     X += fma(s sqrt(dt), z, fma(-v+, dt / 2, (r - q) dt))                        s = sqrt(v+)
+//     v += fma(s (xi sqrt(dt)), w, fma(-v+, kappa dt, kappa theta dt)).
+// The X line is localvol_device.hpp's lv_move with s^2 replaced by v+ itself, so with xi = 0 and kappa = 0 a Heston path
+// is the constant-volatility path of the surface kernels up to the rounding of s s against v+.  Every fused operation
+// is an explicit fma_t and nothing else here is of the form a * b + c, so the compiler contracts nothing on its own and
+// every kernel that includes this header computes the same bits.
+//
+// The map is continuous in every input — max, sqrt and fused multiply-adds, no branch on a moment ratio, no inverse
+// distribution function — so two precisions of one path never take different formulas.
+#pragma once
+
+#include "mc_device.hpp"
+
+namespace mcamd {
+
+// The floating-point constants of a step, formed in double on the host and narrowed once.
+template <typename T>
+struct HestonConsts {
+    T mu_dt;            // (r - q) dt
+    T half_dt;          // dt / 2
+    T sqrt_dt;          // sqrt(dt)
+    T kappa_dt;         // kappa dt
+    T kappa_theta_dt;   // kappa theta dt
+    T xi_sqrt_dt;       // xi sqrt(dt)
+    T rho;
+    T rho_c;            // sqrt(1 - rho^2): 0 at rho = +-1
+};
+
+// Where they live.  fp32: in vector registers, because a scalar operand doubles the issue time of the full-rate fp32
+// instructions (mc_device.hpp vgpr_resident).  fp64: an operation issues in 4 cycles with or without a scalar operand.
+__device__ __forceinline__ HestonConsts<float> heston_resident(const HestonConsts<float> &c)
+{
+    return {vgpr_resident(c.mu_dt),    vgpr_resident(c.half_dt),        vgpr_resident(c.sqrt_dt),
+            vgpr_resident(c.kappa_dt), vgpr_resident(c.kappa_theta_dt), vgpr_resident(c.xi_sqrt_dt),
+            vgpr_resident(c.rho),      vgpr_resident(c.rho_c)};
+}
+__device__ __forceinline__ HestonConsts<double> heston_resident(const HestonConsts<double> &c) { return c; }
+
+__device__ __forceinline__ float heston_positive(float v) { return __builtin_fmaxf(v, 0.0f); }
+__device__ __forceinline__ double heston_positive(double v) { return __builtin_fmax(v, 0.0); }
+// fp32: v_sqrt_f32 (1 ulp; 0 gives 0).  fp64: the correctly rounded square root, exact at 0 and on subnormal arguments,
+// which f64::sqrt_pos (clamped to 1e-300, so sqrt 0 = 1e-150) is not; v+ = 0 is an everyday argument here.
+__device__ __forceinline__ float heston_root(float a) { return __builtin_amdgcn_sqrtf(a); }
+__device__ __forceinline__ double heston_root(double a) { return __builtin_sqrt(a); }
+
+// One step from (X, v) with the log-price normal z and the variance's own normal zv.  Returns v+, the variance the step
+// was taken at.
+template <typename T>
+__device__ __forceinline__ T heston_move(T &X, T &v, T z, T zv, const HestonConsts<T> &c)
+{
+    const T vp = heston_positive(v);
+    const T s = heston_root(vp);
+    const T w = fma_t(c.rho, z, c.rho_c * zv);
+    X += fma_t(s * c.sqrt_dt, z, fma_t(-vp, c.half_dt, c.mu_dt));
+    v += fma_t(s * c.xi_sqrt_dt, w, fma_t(-vp, c.kappa_dt, c.kappa_theta_dt));
+    return vp;
+}
+
+}  // namespace mcamd
