@@ -246,8 +246,10 @@ int mcamd_simulate_trajectories(mcamd_ctx *ctx, const mcamd_option *opt, const m
 int mcamd_diag_store_pattern(mcamd_ctx *ctx, uint64_t n_paths_local, uint32_t n_steps, int precision, void *d_traj,
                              void *d_payoffs, float *kernel_ms);
 
-/* Array-driven pricer: normals are an input, d_normals[path * n_steps + step] (the reference's
- * layout), precision per sim->precision; d_payoffs (nullable): n_paths_local payoffs.
+/* Array-driven pricer: normals are an input, d_normals[path * n_sim_steps + step] (the reference's
+ * layout; a row holds the n_sim_steps = n_steps - Tk simulated steps, so the buffer has
+ * n_paths_local * n_sim_steps elements), precision per sim->precision; d_payoffs (nullable):
+ * n_paths_local payoffs.
  * Replaces simulateOptionPriceGPU / simulateOptionPriceMultipleBlockGPU (array overloads)
  * inc/trajectories.cuh:14-52; CPU twin inc/testing.cuh:75-91. */
 int mcamd_price_from_normals(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const void *d_normals,

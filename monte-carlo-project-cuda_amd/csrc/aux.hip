@@ -7,8 +7,8 @@
 namespace mcamd {
 
 // ---------------------------------------------------------------------------------------------
-// Array-driven European pricer: normals are an input, d_normals[path * n_steps + step] (the
-// reference's layout).  Replaces simulateOptionPriceGPU / simulateOptionPriceMultipleBlockGPU
+// Array-driven European pricer: normals are an input, d_normals[path * n_sim + step] (the
+// reference's layout; n_sim = n_steps - Tk).  Replaces simulateOptionPriceGPU / simulateOptionPriceMultipleBlockGPU
 // (array overloads), inc/trajectories.cuh:14-52; this is the deterministic parity path (its CPU
 // twin is inc/testing.cuh:75-91).  A wavefront stages a 64-path x 128-byte tile through LDS:
 // global reads are row-contiguous (one full 128 B line per path row), LDS reads are column-wise
