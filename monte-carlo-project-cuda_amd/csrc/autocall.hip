@@ -161,26 +161,27 @@ static hipError_t launch_autocall_d(const AutocallJob &j, double *d_partials, ui
                                     hipStream_t stream)
 {
     const double u = exponent_unit<T>();   // natural log per exponent unit
+    const AutocallSchedule &sc = j.schedule;
     AutocallArgs<T, D> a{};
     for (int q = 0; q < D; ++q) a.drift[q] = static_cast<T>(j.drift[q] / u);
     for (int c = 0; c < D * (D + 1) / 2; ++c) a.coef[c] = static_cast<T>(j.coef[c] / u);
-    for (uint32_t q = 0; q < j.n_dates; ++q) {
-        a.log_level[q] = static_cast<T>(j.log_level[q] / u);
-        a.pay[q] = j.pay[q];
+    for (uint32_t q = 0; q < sc.n_dates; ++q) {
+        a.log_level[q] = static_cast<T>(sc.log_level[q] / u);
+        a.pay[q] = sc.pay[q];
     }
-    a.log_ki = j.ki ? static_cast<T>(j.log_ki / u) : T(0);
-    a.dt = j.dt;
-    a.ki = j.ki ? 1 : 0;
+    a.log_ki = sc.ki ? static_cast<T>(sc.log_ki / u) : T(0);
+    a.dt = sc.dt;
+    a.ki = sc.ki ? 1 : 0;
     a.n_steps = j.path.n_sim;
-    a.observe_every = j.observe_every;
-    a.first_call_date = j.first_call_date;
+    a.observe_every = sc.observe_every;
+    a.first_call_date = sc.first_call_date;
     a.seed = j.path.seed;
     a.path_offset = j.path.path_offset;
     a.n_local = j.path.n_local;
     a.samples = static_cast<T *>(j.d_samples);
     a.fin = GridFinish{fs.out, fs.ticket, fs.n_value};
     const dim3 g(grid), b(kBlock);
-    if (j.ki && j.ki_every_step) hipLaunchKernelGGL((autocall_kernel<T, D, true>), g, b, 0, stream, a, d_partials);
+    if (sc.ki && sc.ki_every_step) hipLaunchKernelGGL((autocall_kernel<T, D, true>), g, b, 0, stream, a, d_partials);
     else hipLaunchKernelGGL((autocall_kernel<T, D, false>), g, b, 0, stream, a, d_partials);
     return hipGetLastError();
 }
@@ -189,27 +190,16 @@ template <typename T>
 static hipError_t launch_autocall_t(const AutocallJob &j, double *d_partials, uint32_t grid, const FinishSpec &fs,
                                     hipStream_t stream)
 {
-    switch (j.d) {
-    case 1: return launch_autocall_d<T, 1>(j, d_partials, grid, fs, stream);
-    case 2: return launch_autocall_d<T, 2>(j, d_partials, grid, fs, stream);
-    case 3: return launch_autocall_d<T, 3>(j, d_partials, grid, fs, stream);
-    case 4: return launch_autocall_d<T, 4>(j, d_partials, grid, fs, stream);
-    case 5: return launch_autocall_d<T, 5>(j, d_partials, grid, fs, stream);
-    case 6: return launch_autocall_d<T, 6>(j, d_partials, grid, fs, stream);
-    case 7: return launch_autocall_d<T, 7>(j, d_partials, grid, fs, stream);
-    case 8: return launch_autocall_d<T, 8>(j, d_partials, grid, fs, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_assets(j.d, [&](auto d) {
+        return launch_autocall_d<T, decltype(d)::value>(j, d_partials, grid, fs, stream);
+    });
 }
 
 hipError_t launch_autocall(const AutocallJob &job, double *d_partials, uint32_t grid, const FinishSpec &finish,
                            hipStream_t stream)
 {
     if (!finish_ok(finish, grid)) return hipErrorInvalidValue;
-    const uint32_t n_steps = job.path.n_sim;
-    if (job.observe_every == 0 || job.n_dates == 0 || job.n_dates > static_cast<uint32_t>(kAutocallMaxDates) ||
-        static_cast<uint64_t>(job.n_dates) * job.observe_every != n_steps || job.first_call_date == 0)
-        return hipErrorInvalidValue;   // the date tables are indexed by a counter these rules bound
+    if (!autocall_schedule_ok(job.schedule, job.path.n_sim)) return hipErrorInvalidValue;
     return job.path.precision == 32 ? launch_autocall_t<float>(job, d_partials, grid, finish, stream)
                                     : launch_autocall_t<double>(job, d_partials, grid, finish, stream);
 }

@@ -17,12 +17,8 @@ namespace mcamd {
 constexpr int kAutocallRecord = 7;
 constexpr int kAutocallMaxDates = 64;
 
-// Everything in double and in natural-log units; the launcher narrows to the path precision and its exponent units.
-struct AutocallJob {
-    PathJob path;                          // n_sim = n_steps, seed, shard, precision (the single-asset fields are unused)
-    int d;                                 // assets, 1..kBasketMaxAssets
-    double drift[kBasketMaxAssets];        // (r - v_j^2 / 2) dt
-    double coef[kBasketMaxCoefs];          // v_j sqrt(dt) L_jk at [j (j + 1) / 2 + k], k <= j
+// The note's terms as both autocall kernels (here and autocall_localvol.hpp) take them, in double and natural-log units.
+struct AutocallSchedule {
     uint32_t observe_every;                // steps between observation dates
     uint32_t n_dates;                      // M = n_steps / observe_every, 1..kAutocallMaxDates
     uint32_t first_call_date;              // 1..M: dates before it are not tested
@@ -31,6 +27,22 @@ struct AutocallJob {
     double dt;                             // T / n_steps: t_q = (q observe_every) dt
     bool ki, ki_every_step;                // a knock-in, and whether every step end is monitored (else maturity alone)
     double log_ki;                         // ln ki_level (with a knock-in)
+};
+
+// What the launchers refuse: the kernels index the date tables by a counter that these rules bound.
+inline bool autocall_schedule_ok(const AutocallSchedule &s, uint32_t n_steps)
+{
+    return s.observe_every != 0 && s.n_dates != 0 && s.n_dates <= static_cast<uint32_t>(kAutocallMaxDates) &&
+           static_cast<uint64_t>(s.n_dates) * s.observe_every == n_steps && s.first_call_date != 0;
+}
+
+// Everything in double and in natural-log units; the launcher narrows to the path precision and its exponent units.
+struct AutocallJob {
+    PathJob path;                          // n_sim = n_steps, seed, shard, precision (the single-asset fields are unused)
+    int d;                                 // assets, 1..kBasketMaxAssets
+    double drift[kBasketMaxAssets];        // (r - v_j^2 / 2) dt
+    double coef[kBasketMaxCoefs];          // v_j sqrt(dt) L_jk at [j (j + 1) / 2 + k], k <= j
+    AutocallSchedule schedule;
     void *d_samples;                       // nullable: n_local samples of the path precision
 };
 

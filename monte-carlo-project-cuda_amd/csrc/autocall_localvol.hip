@@ -16,9 +16,7 @@ hipError_t launch_autocall_localvol(const AutocallLocalVolJob &job, double *d_pa
 {
     if (!finish_ok(finish, grid)) return hipErrorInvalidValue;
     const uint32_t n_steps = job.n_steps;
-    if (job.observe_every == 0 || job.n_dates == 0 || job.n_dates > static_cast<uint32_t>(kAutocallMaxDates) ||
-        static_cast<uint64_t>(job.n_dates) * job.observe_every != n_steps || job.first_call_date == 0)
-        return hipErrorInvalidValue;   // the date tables are indexed by a counter these rules bound
+    if (!autocall_schedule_ok(job.schedule, n_steps)) return hipErrorInvalidValue;
     if (job.d < 1 || job.d > kBasketMaxAssets) return hipErrorInvalidValue;
     uint64_t nodes = 0;                // the D tables share one LDS allocation: no index may leave its own table
     for (int j = 0; j < job.d; ++j) {

@@ -22,15 +22,8 @@ struct AutocallLocalVolJob {
     int d;                                 // assets, 1..kBasketMaxAssets
     double mu[kBasketMaxAssets];           // r - q_j
     double chol[kBasketMaxCoefs];          // the Cholesky factor of corr at [j (j + 1) / 2 + k], k <= j
-    double dt;                             // T / n_steps
     LocalVolGrid surface[kBasketMaxAssets];   // asset j's; sum_j n_t n_x <= kLocalVolMaxNodes
-    uint32_t observe_every;                // steps between observation dates
-    uint32_t n_dates;                      // M = n_steps / observe_every, 1..kAutocallMaxDates
-    uint32_t first_call_date;              // 1..M
-    double log_level[kAutocallMaxDates];   // ln L_q at [q - 1]
-    double pay[kAutocallMaxDates];         // pay_q at [q - 1]
-    bool ki, ki_every_step;
-    double log_ki;                         // ln ki_level (with a knock-in)
+    AutocallSchedule schedule;             // its dt = T / n_steps is the step's as well
     void *d_samples;                       // nullable: n_local samples of the path precision
 };
 

@@ -10,13 +10,17 @@
 // l_i = min_j X_{j,i}.  Dates, levels, payments, the call test, the knock-in modes, the sample and the block record are
 // those of autocall.hip, with ln L_q and ln ki_level in natural-log units; A_n = exp_of_logreturn(1, l_n exp_scale).
 //
-// The loop restates autocall.hip's (groups of G = NB / gcd(D, NB) steps on whole Philox blocks, unrolled with the block
-// boundaries at compile-time positions; a wave-uniform observation test and date counter; a wavefront leaves at the
-// first group end where no lane is uncalled): a constant-volatility walk, whose a * b + c shapes the compiler may
-// contract differently once the code moves, stays with its kernel.  The lookup, the row carry and the move are the
-// shared ones, one per asset.  The D pair tables lie back to back in dynamic LDS, copied once per workgroup; a step
-// costs D reads (ds_read_b64 in fp32, ds_read_b128 in fp64) at asset j's row base — which starts at the table's own
-// base — plus the lane's k_j.  The per-asset grid constants and the row carries are wave-uniform (scalar unit).
+// The loop is written as autocall.hip's is (groups of G = NB / gcd(D, NB) steps on whole Philox blocks, unrolled with
+// the block boundaries at compile-time positions; a wave-uniform observation test and date counter; a wavefront leaves
+// at the first group end where no lane is uncalled) and keeps the note's state as that kernel does.  Each was tried in
+// one place for both kernels: with one group walk or one note, kernels of this file compiled to other vector
+// instructions or crossed an occupancy step, and with one function for the chain of fused multiply-adds the fp64
+// kernel of D = 8 without a step-wise knock-in spilled 11 more scalars and ran 2.8 % slower (profiles/README.md, "One
+// schedule for two autocall calls; one walk for three kernels, tried").  The lookup, the row carry and the move are
+// localvol_device.hpp's, one per asset.  The D pair tables lie back to back in dynamic LDS, copied once per workgroup;
+// a step costs D reads (ds_read_b64 in fp32, ds_read_b128 in fp64) at asset j's row base — which starts at the
+// table's own base — plus the lane's k_j.  The per-asset grid constants and the row carries are wave-uniform (scalar
+// unit).
 #pragma once
 
 #include "autocall_localvol.hpp"
@@ -201,6 +205,7 @@ template <typename T, int D>
 static hipError_t launch_autocall_localvol_d(const AutocallLocalVolJob &j, double *d_partials, uint32_t grid,
                                              const FinishSpec &fs, hipStream_t stream)
 {
+    const AutocallSchedule &sc = j.schedule;
     AutocallLocalVolArgs<T, D> a{};
     uint32_t total = 0;
     for (int q = 0; q < D; ++q) {
@@ -216,23 +221,23 @@ static hipError_t launch_autocall_localvol_d(const AutocallLocalVolJob &j, doubl
         a.row_thr[q] = s.rows.row_thr;
         a.table[q] = s.table;
         a.base[q] = total;
-        a.mu_dt[q] = static_cast<T>(j.mu[q] * j.dt);
+        a.mu_dt[q] = static_cast<T>(j.mu[q] * sc.dt);
         total += s.rows.n_entries;
     }
     for (int c = 0; c < D * (D + 1) / 2; ++c) a.chol[c] = static_cast<T>(j.chol[c]);
-    a.half_dt = static_cast<T>(0.5 * j.dt);
-    a.sqrt_dt = static_cast<T>(std::sqrt(j.dt));
+    a.half_dt = static_cast<T>(0.5 * sc.dt);
+    a.sqrt_dt = static_cast<T>(std::sqrt(sc.dt));
     a.exp_scale = lv_exp_scale<T>();
-    for (uint32_t q = 0; q < j.n_dates; ++q) {
-        a.log_level[q] = static_cast<T>(j.log_level[q]);
-        a.pay[q] = j.pay[q];
+    for (uint32_t q = 0; q < sc.n_dates; ++q) {
+        a.log_level[q] = static_cast<T>(sc.log_level[q]);
+        a.pay[q] = sc.pay[q];
     }
-    a.log_ki = j.ki ? static_cast<T>(j.log_ki) : T(0);
-    a.dt = j.dt;
-    a.ki = j.ki ? 1 : 0;
+    a.log_ki = sc.ki ? static_cast<T>(sc.log_ki) : T(0);
+    a.dt = sc.dt;
+    a.ki = sc.ki ? 1 : 0;
     a.n_steps = j.n_steps;
-    a.observe_every = j.observe_every;
-    a.first_call_date = j.first_call_date;
+    a.observe_every = sc.observe_every;
+    a.first_call_date = sc.first_call_date;
     a.seed = j.seed;
     a.path_offset = j.path_offset;
     a.n_local = j.n_local;
@@ -240,7 +245,7 @@ static hipError_t launch_autocall_localvol_d(const AutocallLocalVolJob &j, doubl
     a.fin = GridFinish{fs.out, fs.ticket, fs.n_value};
     const dim3 g(grid), b(kBlock);
     const size_t lds_bytes = static_cast<size_t>(total) * sizeof(VolPair<T>);
-    if (j.ki && j.ki_every_step)
+    if (sc.ki && sc.ki_every_step)
         hipLaunchKernelGGL((autocall_localvol_kernel<T, D, true>), g, b, lds_bytes, stream, a, d_partials);
     else
         hipLaunchKernelGGL((autocall_localvol_kernel<T, D, false>), g, b, lds_bytes, stream, a, d_partials);
@@ -251,17 +256,9 @@ template <typename T>
 static hipError_t launch_autocall_localvol_t(const AutocallLocalVolJob &j, double *d_partials, uint32_t grid,
                                              const FinishSpec &fs, hipStream_t stream)
 {
-    switch (j.d) {
-    case 1: return launch_autocall_localvol_d<T, 1>(j, d_partials, grid, fs, stream);
-    case 2: return launch_autocall_localvol_d<T, 2>(j, d_partials, grid, fs, stream);
-    case 3: return launch_autocall_localvol_d<T, 3>(j, d_partials, grid, fs, stream);
-    case 4: return launch_autocall_localvol_d<T, 4>(j, d_partials, grid, fs, stream);
-    case 5: return launch_autocall_localvol_d<T, 5>(j, d_partials, grid, fs, stream);
-    case 6: return launch_autocall_localvol_d<T, 6>(j, d_partials, grid, fs, stream);
-    case 7: return launch_autocall_localvol_d<T, 7>(j, d_partials, grid, fs, stream);
-    case 8: return launch_autocall_localvol_d<T, 8>(j, d_partials, grid, fs, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_assets(j.d, [&](auto d) {
+        return launch_autocall_localvol_d<T, decltype(d)::value>(j, d_partials, grid, fs, stream);
+    });
 }
 
 }  // namespace mcamd

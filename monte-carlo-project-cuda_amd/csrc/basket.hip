@@ -186,17 +186,9 @@ template <typename T>
 static hipError_t launch_basket_t(const BasketJob &j, double *d_partials, uint32_t grid, const FinishSpec &fs,
                                   hipStream_t stream)
 {
-    switch (j.d) {
-    case 1: return launch_basket_d<T, 1>(j, d_partials, grid, fs, stream);
-    case 2: return launch_basket_d<T, 2>(j, d_partials, grid, fs, stream);
-    case 3: return launch_basket_d<T, 3>(j, d_partials, grid, fs, stream);
-    case 4: return launch_basket_d<T, 4>(j, d_partials, grid, fs, stream);
-    case 5: return launch_basket_d<T, 5>(j, d_partials, grid, fs, stream);
-    case 6: return launch_basket_d<T, 6>(j, d_partials, grid, fs, stream);
-    case 7: return launch_basket_d<T, 7>(j, d_partials, grid, fs, stream);
-    case 8: return launch_basket_d<T, 8>(j, d_partials, grid, fs, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_assets(j.d, [&](auto d) {
+        return launch_basket_d<T, decltype(d)::value>(j, d_partials, grid, fs, stream);
+    });
 }
 
 hipError_t launch_basket(const BasketJob &job, double *d_partials, uint32_t grid, const FinishSpec &finish,

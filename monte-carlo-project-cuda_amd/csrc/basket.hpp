@@ -8,6 +8,8 @@
 // Its block record is {sum y, sum y^2, wave-steps executed, lane-steps of paths not yet hit}: 4 doubles.
 #pragma once
 
+#include <type_traits>
+
 #include "launch.hpp"
 
 namespace mcamd {
@@ -15,6 +17,24 @@ namespace mcamd {
 constexpr int kBasketRecord = 4;
 constexpr int kBasketMaxAssets = 8;
 constexpr int kBasketMaxCoefs = kBasketMaxAssets * (kBasketMaxAssets + 1) / 2;
+
+// The kernels of d correlated assets take d as a template argument: f(std::integral_constant<int, D>{}) with D = d.
+template <typename F>
+hipError_t dispatch_assets(int d, F f)
+{
+    switch (d) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    case 6: return f(std::integral_constant<int, 6>{});
+    case 7: return f(std::integral_constant<int, 7>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    default: return hipErrorInvalidValue;
+    }
+}
+static_assert(kBasketMaxAssets == 8, "dispatch_assets lists the asset counts");
 
 enum BasketKind { kBasketArithmetic = 0, kBasketGeometric = 1, kBasketBestOf = 2, kBasketWorstOf = 3 };
 

@@ -1,5 +1,8 @@
 // basket_device.hpp — device helpers shared by the kernels that step d correlated assets in registers (basket.hip,
-// autocall.hip): the step group's arithmetic, the extremum and where the loop's constants live.
+// autocall.hip, autocall_localvol_impl.hpp): the step group's arithmetic, the extremum and where the loop's constants
+// live.  The group walk and the chain of fused multiply-adds are written out in each kernel: one walk_groups and one
+// bk_correlate for the three were tried, and each changed the kernels' vector instructions or their speed
+// (profiles/README.md, "One schedule for two autocall calls; one walk for three kernels, tried").
 #pragma once
 
 #include "mc_device.hpp"

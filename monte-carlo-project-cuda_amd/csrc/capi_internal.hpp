@@ -18,6 +18,10 @@
 // capi.cpp: records the calling thread's last error message (for callers that have the text already)
 int mcamd_set_error_(int code, const char *msg);
 
+namespace mcamd {
+struct AutocallSchedule;   // autocall.hpp
+}
+
 #pragma GCC visibility push(hidden)
 
 namespace mcamd::capi {
@@ -68,6 +72,27 @@ int check_asian_kind(double K, int strike, int payoff, int include_spot);
 int check_basket_assets(const mcamd_basket *b, bool positive_weights, double L[64]);
 int check_autocall_terms(double coupon, double call_level, double call_step_down, double L_last, int ki_monitoring,
                          double ki_level);
+// ... and what mcamd_price_autocall and mcamd_price_autocall_localvol share, whose structs differ in v / q alone.
+// The assets of a note through check_basket_assets (performances: spot 1 and weight 1), with the volatilities v or,
+// with v NULL, ones:
+int check_autocall_assets(int n_assets, const double *v, const double corr[64], double L[64]);
+// the fields the two structs have in common
+struct AutocallTerms {
+    uint32_t observe_every, first_call_date;
+    int ki_monitoring;
+    double call_level, call_step_down, coupon, ki_level;
+};
+template <typename Autocall>
+AutocallTerms autocall_terms(const Autocall *ac)
+{
+    return {ac->observe_every, ac->first_call_date, ac->ki_monitoring, ac->call_level, ac->call_step_down, ac->coupon,
+            ac->ki_level};
+}
+// the refusals from "observe_every must be >= 1" through check_autocall_terms; *M = n_steps / observe_every
+int check_autocall_schedule(const AutocallTerms &t, uint32_t n_steps, uint32_t *M);
+// the M dates' levels and payments (maturity money at rate r) and the knock-in, for steps of dt
+void make_autocall_schedule(const AutocallTerms &t, uint32_t M, double r, double T, double dt,
+                            mcamd::AutocallSchedule *schedule);
 // capi_localvol.cpp
 int check_localvol_grid(const mcamd_localvol_grid *grid, const double *h_sigma, double *sigma_max);
 int check_cliquet_kind(int kind);

@@ -424,32 +424,16 @@ int prepare_autocall_localvol(mcamd_ctx *ctx, const mcamd_option *opt, const mca
     if (!opt || !sim || !ac) return fail(MCAMD_ERR_INVALID, "opt, sim, autocall and surfaces must be non-NULL");
     if (ac->reserved[0] != 0 || ac->reserved[1] != 0)
         return fail(MCAMD_ERR_INVALID, "autocall->reserved must be 0, got {%d, %d}", ac->reserved[0], ac->reserved[1]);
-    // n_assets and corr through the basket's own checks and Cholesky factor: unit spots, weights and volatilities
-    mcamd_basket assets{};
-    assets.n_assets = ac->n_assets;
-    assets.payoff = MCAMD_PAYOFF_PUT;
-    for (int j = 0; j < MCAMD_BASKET_MAX_ASSETS; ++j) assets.S0[j] = assets.w[j] = assets.v[j] = 1.0;
-    std::memcpy(assets.corr, ac->corr, sizeof assets.corr);
+    // n_assets and corr through the basket's own checks and Cholesky factor, with unit volatilities
     double L[64];
-    if (int rc = check_basket_assets(&assets, true, L)) return rc;
+    if (int rc = check_autocall_assets(ac->n_assets, nullptr, ac->corr, L)) return rc;
     const int d = ac->n_assets;
     for (int j = 0; j < d; ++j)
         if (!std::isfinite(ac->q[j]))
             return fail(MCAMD_ERR_INVALID, "every dividend yield q must be finite, got q[%d] = %g", j, ac->q[j]);
-    if (ac->observe_every == 0 || sim->n_steps % ac->observe_every != 0)
-        return fail(MCAMD_ERR_INVALID, "observe_every must be >= 1 and divide n_steps (observe_every = %u, n_steps = %u)",
-                    ac->observe_every, sim->n_steps);
-    const uint32_t M = sim->n_steps / ac->observe_every;
-    if (M > MCAMD_AUTOCALL_MAX_DATES)   // M == 0 is n_steps == 0, which check_request refuses below
-        return fail(MCAMD_ERR_INVALID, "n_steps / observe_every = %u observation dates exceed MCAMD_AUTOCALL_MAX_DATES = %d",
-                    M, MCAMD_AUTOCALL_MAX_DATES);
-    if (M != 0 && (ac->first_call_date < 1 || ac->first_call_date > M))
-        return fail(MCAMD_ERR_INVALID, "first_call_date must be 1..%u (the observation dates), got %u", M,
-                    ac->first_call_date);
-    const double L_last = ac->call_level - (static_cast<double>(M) - 1.0) * ac->call_step_down;
-    if (int rc = check_autocall_terms(ac->coupon, ac->call_level, ac->call_step_down, M ? L_last : ac->call_level,
-                                      ac->ki_monitoring, ac->ki_level))
-        return rc;
+    const AutocallTerms terms = autocall_terms(ac);
+    uint32_t M;
+    if (int rc = check_autocall_schedule(terms, sim->n_steps, &M)) return rc;
     if (!std::isfinite(opt->r)) return fail(MCAMD_ERR_INVALID, "option parameters must be finite with T > 0");
     // as prepare_localvol, asset by asset, on a copy that carries no spot, strike or barrier of its own either
     double mu[MCAMD_BASKET_MAX_ASSETS];
@@ -484,23 +468,12 @@ int prepare_autocall_localvol(mcamd_ctx *ctx, const mcamd_option *opt, const mca
     job.n_steps = sim->n_steps;
     job.precision = sim->precision;
     job.d = d;
-    job.dt = dt;
     for (int j = 0; j < d; ++j) {
         job.mu[j] = mu[j];
         for (int k = 0; k <= j; ++k) job.chol[j * (j + 1) / 2 + k] = L[8 * j + k];
         job.surface[j] = job_surface(surfaces[j], sim->precision);
     }
-    job.observe_every = ac->observe_every;
-    job.n_dates = M;
-    job.first_call_date = ac->first_call_date;
-    for (uint32_t q = 1; q <= M; ++q) {
-        const double t_q = static_cast<double>(q * ac->observe_every) * dt;
-        job.log_level[q - 1] = std::log(ac->call_level - (static_cast<double>(q) - 1.0) * ac->call_step_down);
-        job.pay[q - 1] = (1.0 + static_cast<double>(q) * ac->coupon) * std::exp(opt->r * (opt->T - t_q));
-    }
-    job.ki = ac->ki_monitoring != MCAMD_AUTOCALL_KI_NONE;
-    job.ki_every_step = ac->ki_monitoring == MCAMD_AUTOCALL_KI_EVERY_STEP;
-    job.log_ki = job.ki ? std::log(ac->ki_level) : 0.0;
+    make_autocall_schedule(terms, M, opt->r, opt->T, dt, &job.schedule);
     job.d_samples = d_samples;
     const uint32_t grid = mcamd::one_path_per_thread_grid(job.n_local);
     return drive(DeviceCall{job.n_local, grid, mcamd::kAutocallRecord, 6, Finish::kFolded,

@@ -85,6 +85,54 @@ int check_autocall_terms(double coupon, double call_level, double call_step_down
     return MCAMD_OK;
 }
 
+int check_autocall_assets(int n_assets, const double *v, const double corr[64], double L[64])
+{
+    mcamd_basket assets{};
+    assets.n_assets = n_assets;
+    assets.payoff = MCAMD_PAYOFF_PUT;
+    for (int j = 0; j < MCAMD_BASKET_MAX_ASSETS; ++j) {
+        assets.S0[j] = assets.w[j] = 1.0;
+        assets.v[j] = v ? v[j] : 1.0;
+    }
+    std::memcpy(assets.corr, corr, sizeof assets.corr);
+    return check_basket_assets(&assets, true, L);
+}
+
+int check_autocall_schedule(const AutocallTerms &t, uint32_t n_steps, uint32_t *M_out)
+{
+    if (t.observe_every == 0 || n_steps % t.observe_every != 0)
+        return fail(MCAMD_ERR_INVALID, "observe_every must be >= 1 and divide n_steps (observe_every = %u, n_steps = %u)",
+                    t.observe_every, n_steps);
+    const uint32_t M = *M_out = n_steps / t.observe_every;
+    if (M > MCAMD_AUTOCALL_MAX_DATES)   // M == 0 is n_steps == 0, which check_request refuses later
+        return fail(MCAMD_ERR_INVALID, "n_steps / observe_every = %u observation dates exceed MCAMD_AUTOCALL_MAX_DATES = %d",
+                    M, MCAMD_AUTOCALL_MAX_DATES);
+    if (M != 0 && (t.first_call_date < 1 || t.first_call_date > M))
+        return fail(MCAMD_ERR_INVALID, "first_call_date must be 1..%u (the observation dates), got %u", M,
+                    t.first_call_date);
+    const double L_last = t.call_level - (static_cast<double>(M) - 1.0) * t.call_step_down;
+    return check_autocall_terms(t.coupon, t.call_level, t.call_step_down, M ? L_last : t.call_level, t.ki_monitoring,
+                                t.ki_level);
+}
+
+void make_autocall_schedule(const AutocallTerms &t, uint32_t M, double r, double T, double dt,
+                            mcamd::AutocallSchedule *schedule)
+{
+    mcamd::AutocallSchedule &s = *schedule;
+    s.observe_every = t.observe_every;
+    s.n_dates = M;
+    s.first_call_date = t.first_call_date;
+    for (uint32_t q = 1; q <= M; ++q) {
+        const double t_q = static_cast<double>(q * t.observe_every) * dt;
+        s.log_level[q - 1] = std::log(t.call_level - (static_cast<double>(q) - 1.0) * t.call_step_down);
+        s.pay[q - 1] = (1.0 + static_cast<double>(q) * t.coupon) * std::exp(r * (T - t_q));
+    }
+    s.dt = dt;
+    s.ki = t.ki_monitoring != MCAMD_AUTOCALL_KI_NONE;
+    s.ki_every_step = t.ki_monitoring == MCAMD_AUTOCALL_KI_EVERY_STEP;
+    s.log_ki = s.ki ? std::log(t.ki_level) : 0.0;
+}
+
 void fill_autocall_result(const double *rec, uint64_t n, double r, double T, mcamd_autocall_result *res)
 {
     const Estimate e = estimate(rec[0], rec[1], n, std::exp(-r * T));
@@ -196,32 +244,13 @@ int prepare_autocall(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *s
     if (!opt || !sim || !ac) return fail(MCAMD_ERR_INVALID, "opt, sim and autocall must be non-NULL");
     if (ac->reserved[0] != 0 || ac->reserved[1] != 0)
         return fail(MCAMD_ERR_INVALID, "autocall->reserved must be 0, got {%d, %d}", ac->reserved[0], ac->reserved[1]);
-    // the assets through the basket's own checks and Cholesky factor: performances have spot 1 and weight 1
-    mcamd_basket assets{};
-    assets.n_assets = ac->n_assets;
-    assets.payoff = MCAMD_PAYOFF_PUT;
-    for (int j = 0; j < MCAMD_BASKET_MAX_ASSETS; ++j) {
-        assets.S0[j] = assets.w[j] = 1.0;
-        assets.v[j] = ac->v[j];
-    }
-    std::memcpy(assets.corr, ac->corr, sizeof assets.corr);
+    // the assets through the basket's own checks and Cholesky factor
     double L[64];
-    if (int rc = check_basket_assets(&assets, true, L)) return rc;
+    if (int rc = check_autocall_assets(ac->n_assets, ac->v, ac->corr, L)) return rc;
     const int d = ac->n_assets;
-    if (ac->observe_every == 0 || sim->n_steps % ac->observe_every != 0)
-        return fail(MCAMD_ERR_INVALID, "observe_every must be >= 1 and divide n_steps (observe_every = %u, n_steps = %u)",
-                    ac->observe_every, sim->n_steps);
-    const uint32_t M = sim->n_steps / ac->observe_every;
-    if (M > MCAMD_AUTOCALL_MAX_DATES)   // M == 0 is n_steps == 0, which check_request refuses below
-        return fail(MCAMD_ERR_INVALID, "n_steps / observe_every = %u observation dates exceed MCAMD_AUTOCALL_MAX_DATES = %d",
-                    M, MCAMD_AUTOCALL_MAX_DATES);
-    if (M != 0 && (ac->first_call_date < 1 || ac->first_call_date > M))
-        return fail(MCAMD_ERR_INVALID, "first_call_date must be 1..%u (the observation dates), got %u", M,
-                    ac->first_call_date);
-    const double L_last = ac->call_level - (static_cast<double>(M) - 1.0) * ac->call_step_down;
-    if (int rc = check_autocall_terms(ac->coupon, ac->call_level, ac->call_step_down, M ? L_last : ac->call_level,
-                                      ac->ki_monitoring, ac->ki_level))
-        return rc;
+    const AutocallTerms terms = autocall_terms(ac);
+    uint32_t M;
+    if (int rc = check_autocall_schedule(terms, sim->n_steps, &M)) return rc;
     // what the option itself contributes is r and T: the spot-start rules and those of mcamd_price_paths see a
     // performance (spot 1) with each asset's volatility in the place of opt->S0 and opt->v; K and B are ignored
     mcamd_option seen = *opt;
@@ -245,18 +274,7 @@ int prepare_autocall(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *s
         job.drift[j] = (opt->r - 0.5 * ac->v[j] * ac->v[j]) * dt;
         for (int k = 0; k <= j; ++k) job.coef[j * (j + 1) / 2 + k] = ac->v[j] * sqdt * L[8 * j + k];
     }
-    job.observe_every = ac->observe_every;
-    job.n_dates = M;
-    job.first_call_date = ac->first_call_date;
-    for (uint32_t q = 1; q <= M; ++q) {
-        const double t_q = static_cast<double>(q * ac->observe_every) * dt;
-        job.log_level[q - 1] = std::log(ac->call_level - (static_cast<double>(q) - 1.0) * ac->call_step_down);
-        job.pay[q - 1] = (1.0 + static_cast<double>(q) * ac->coupon) * std::exp(opt->r * (opt->T - t_q));
-    }
-    job.dt = dt;
-    job.ki = ac->ki_monitoring != MCAMD_AUTOCALL_KI_NONE;
-    job.ki_every_step = ac->ki_monitoring == MCAMD_AUTOCALL_KI_EVERY_STEP;
-    job.log_ki = job.ki ? std::log(ac->ki_level) : 0.0;
+    make_autocall_schedule(terms, M, opt->r, opt->T, dt, &job.schedule);
     job.d_samples = d_samples;
     const uint32_t grid = mcamd::one_path_per_thread_grid(job.path.n_local);
     return drive(DeviceCall{job.path.n_local, grid, mcamd::kAutocallRecord, 6, Finish::kFolded,

@@ -217,6 +217,36 @@ def test_refusals_come_in_the_stated_order(lib):
     assert rc == capi.ERR_INVALID and "surfaces" in msg and "ctx" not in msg, msg
 
 
+def test_both_autocall_calls_refuse_a_schedule_in_the_same_words(lib):
+    """Each defect of the schedule — the run from "observe_every must be >= 1" through the refusals of the terms — on a
+    note of 2 assets and 12 steps (65 steps where 65 dates are the defect), without a context: mcamd_price_autocall and
+    mcamd_price_autocall_localvol return the same code and leave the same text."""
+    KI_M, KI_S = capi.AUTOCALL_KI_AT_MATURITY, capi.AUTOCALL_KI_EVERY_STEP
+    defects = [(12, dict(observe_every=0), "observe_every"), (12, dict(observe_every=5), "observe_every"),
+               (65, dict(observe_every=1), "MCAMD_AUTOCALL_MAX_DATES"),
+               (12, dict(first_call_date=0), "first_call_date"), (12, dict(first_call_date=5), "first_call_date"),
+               (12, dict(call_level=0.75, call_step_down=0.25, ki_monitoring=0), "last date"),
+               (12, dict(call_level=-1.0, ki_monitoring=0), "last date"),
+               (12, dict(ki_monitoring=-1), "ki_monitoring"), (12, dict(ki_monitoring=3), "ki_monitoring"),
+               (12, dict(coupon=-0.01), "coupon"), (12, dict(coupon=NAN), "coupon"),
+               (12, dict(call_level=INF), "call_level"), (12, dict(call_level=NAN), "call_level"),
+               (12, dict(call_step_down=-0.01), "call_step_down"), (12, dict(call_step_down=NAN), "call_step_down")]
+    defects += [(12, dict(ki_monitoring=ki, **kw), "ki_level") for ki in (KI_M, KI_S)
+                for kw in (dict(ki_level=0.0), dict(ki_level=1.01), dict(ki_level=NAN), dict(call_level=0.6),
+                           dict(call_level=1.0, call_step_down=0.125, ki_level=0.625))]
+    args = dict(observe_every=3, call_level=1.0, coupon=0.02, ki_level=0.7, ki_monitoring=KI_S)
+    opt, corr = capi.make_option(**dict(BASE, v=0.2)), alr.corr(2)
+    for n_steps, kw, words in defects:
+        sim, kw = capi.make_sim(1000, n_steps), dict(args, **kw)
+        out = capi.AutocallResult()
+        plain = capi.make_autocall([0.2, 0.25], corr, **kw)
+        rc_a = lib.mcamd_price_autocall(None, C.byref(opt), C.byref(sim), C.byref(plain), None, C.byref(out))
+        msg_a = lib.mcamd_last_error().decode()
+        rc_b, msg_b = price(lib, opt, sim, capi.make_autocall_localvol(alr.Q[:2], corr, **kw), surfaces=NULL_ENTRY)
+        assert rc_a == rc_b == capi.ERR_INVALID and words in msg_a, (kw, msg_a)
+        assert msg_a == msg_b, (kw, msg_a, msg_b)
+
+
 @pytest.mark.parametrize("d", alr.DS)
 @pytest.mark.parametrize("ki", (alr.KI_NONE,) + alr.KI_MODES)
 @pytest.mark.parametrize("flags,prec", [(0, capi.F64), (capi.FLAG_LOG_SPACE, capi.F32)])

@@ -3,7 +3,8 @@
 list of small jobs on the kernels that walk a local-volatility surface — mcamd_price_localvol, mcamd_price_localvol_smile,
 mcamd_price_autocall_localvol, mcamd_price_cliquet, mcamd_price_localvol_greeks — and on the one-path-per-thread kernels
 of constant volatility — mcamd_price_barrier, mcamd_price_lookback, mcamd_price_asian, the likelihood-ratio and pathwise
-mcamd_price_greeks, mcamd_price_american, mcamd_american_upper_bound — and prints a SHA-256 per job over the per-path
+mcamd_price_greeks, mcamd_price_american, mcamd_american_upper_bound, and on d = 1..8 correlated assets
+mcamd_price_basket and mcamd_price_autocall — and prints a SHA-256 per job over the per-path
 outputs where the call has them (samples, spots, continuation values, coefficients) and the result record without its
 timings; this process compares the lines.
     python3 tools/same_bits.py LIB_A LIB_B          # on an MI355X; exit status 1 on any difference
@@ -13,10 +14,17 @@ Every job is 1000 paths (four workgroups, a partial last wavefront) of a 2^40-pa
 ties the count to a period (reset_every, exercise_every) the counts still leave no whole block, no remainder and a
 remainder.  The surfaces are a
 flat 1 x 2, a skewed 3 x 5 (n_t divides no step count but 3), a 16 x 5 (more rows than steps), the full 16 x 128 table
-and an axis so narrow that the paths clamp on both sides.  Two jobs make whole wavefronts leave the step loop after a
-whole block: a knock-out barrier beside the spot on 100 000 paths (its work_steps fall short of the full count), and an
-American put so deep in the money (K = 10 S0) that every priced path is exercised at the first date, step 4 of 48 —
-the worker refuses to go on otherwise — so that every wavefront of the pricing kernel leaves 44 steps early."""
+and an axis so narrow that the paths clamp on both sides.  The baskets take every kind x payoff, and best-of / worst-of
+with every barrier, at d = 1..8 over the step counts of the one-path-per-thread kernels: a group of G = NB / gcd(d, NB)
+steps is 1, 2 or 4 steps, so they leave every remainder, no whole group, and whole groups only; the constant-volatility
+autocallable takes d = 1..8 and the three knock-in modes over the (n_steps, period) pairs.  Some jobs make whole
+wavefronts leave the step loop after a whole block or group, and their names carry the proof: a knock-out barrier beside
+the spot on 100 000 paths and a worst-of knock-out basket with the barrier beside the aggregate (d = 3 and 8; their
+work_steps fall short of the full count — the worker refuses to go on otherwise); an American put so deep in the money
+(K = 10 S0) that every priced path is exercised at the first date, step 4 of 48, so that every wavefront of the
+pricing kernel leaves 44 steps early; and a 3-asset note with a call level of 0.01 under mcamd_price_autocall and under
+mcamd_price_autocall_localvol, every path called at the first date, step 4 of 48, after 4 wave-steps per wavefront —
+the worker refuses to go on otherwise there too."""
 import hashlib, importlib, json, math, os, struct, subprocess, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -188,6 +196,59 @@ def worker():
                     cont = torch.zeros((n_steps // every) * N, dtype=torch.float64, device="cuda")
                     res = ctx.american_upper_bound(opt, s, am, dual, rule, work, cont)
                     emit(f"american dual {tag} n={n_steps} every={every} K={K} work={res.work_steps:.0f}", res, cont)
+            # mcamd_price_basket: every width, kind and payoff, and best-of / worst-of with every barrier
+            extreme = (capi.BASKET_BEST_OF, capi.BASKET_WORST_OF)
+            for d in range(1, 9):
+                corr = [[0.5 ** abs(j - k) for k in range(d)] for j in range(d)]
+                S0, v = [100.0 + j for j in range(d)], [0.2 + 0.02 * j for j in range(d)]
+                for n_steps in STEPS_WALK:
+                    for kind in range(4):
+                        w = [1.0] * d if kind in extreme else [1.0 / d] * d
+                        for barrier in range(5 if kind in extreme else 1):
+                            up = barrier in (capi.BASKET_UP_OUT, capi.BASKET_UP_IN)
+                            opt = capi.make_option(S0=0.0, K=100.0, B=115.0 if up else 90.0, r=0.05, v=0.0, T=1.0)
+                            for pay in (capi.PAYOFF_CALL, capi.PAYOFF_PUT):
+                                res = ctx.price_basket(opt, sim(n_steps, prec, off), capi.make_basket(S0, v, w, corr, kind, pay, barrier),
+                                                       out.zero_())
+                                emit(f"basket {tag} d={d} n={n_steps} kind={kind} barrier={barrier} pay={pay}", res, out)
+            # ... and a worst-of knock-out with the barrier beside the aggregate: whole wavefronts leave after a whole group
+            opt = capi.make_option(S0=0.0, K=100.0, B=99.9, r=0.0, v=0.0, T=1.0)
+            for d in (3, 8):
+                corr = [[0.5 ** abs(j - k) for k in range(d)] for j in range(d)]
+                bk = capi.make_basket([100.0] * d, [0.4] * d, [1.0] * d, corr, capi.BASKET_WORST_OF, capi.PAYOFF_CALL,
+                                      capi.BASKET_DOWN_OUT)
+                res = ctx.price_basket(opt, sim(51, prec, off, n_ko), bk, many.zero_())
+                full = 64.0 * 51 * ((n_ko + 63) // 64)
+                if not res.work_steps < full:
+                    raise SystemExit(f"basket {tag} d={d}: no wavefront left the loop early ({res.work_steps} of {full})")
+                emit(f"basket {tag} d={d} early exit work={res.work_steps:.0f} of {full:.0f}", res, many)
+            # mcamd_price_autocall: every width, the three knock-in modes, dates inside a group, at its end and at maturity only
+            opt = capi.make_option(S0=0.0, K=0.0, r=0.03, v=0.0, T=3.0)
+            for d in range(1, 9):
+                corr = [[0.5 ** abs(j - k) for k in range(d)] for j in range(d)]
+                v = [0.2 + 0.02 * j for j in range(d)]
+                for n_steps, every in PERIODS:
+                    for ki in (capi.AUTOCALL_KI_NONE, capi.AUTOCALL_KI_AT_MATURITY, capi.AUTOCALL_KI_EVERY_STEP):
+                        ac = capi.make_autocall(v, corr, every, 1.0, 0.02, 0.8 if ki else 0.0, ki, call_step_down=0.01)
+                        res = ctx.price_autocall(opt, sim(n_steps, prec, off), ac, out.zero_())
+                        emit(f"autocall const {tag} d={d} n={n_steps} every={every} ki={ki}", res, out)
+            # ... and, under constant volatilities and under surfaces, a note with a call level so low (0.01) that every path
+            # is called at the first date, step 4 of 48: every wavefront leaves after the group that holds step 4
+            d, every, n_steps = 3, 4, 48
+            corr = [[0.5 ** abs(j - k) for k in range(d)] for j in range(d)]
+            t_first, early = every * opt.T / n_steps, 64.0 * every * ((N + 63) // 64)
+            for name, run in (("autocall const", lambda: ctx.price_autocall(
+                                  opt, sim(n_steps, prec, off), capi.make_autocall([0.2, 0.22, 0.24], corr, every, 0.01, 0.02), out.zero_())),
+                              ("autocall", lambda: ctx.price_autocall_localvol(
+                                  opt, sim(n_steps, prec, off), capi.make_autocall_localvol([0.0, 0.01, 0.02], corr, every, 0.01, 0.02),
+                                  [surf["skew3x5"], surf["flat"], surf["rows16x5"]], out.zero_()))):
+                res = run()
+                if res.n_called != N or abs(res.sum_t_call - N * t_first) > 1e-9 * N or res.work_steps != early:
+                    raise SystemExit(f"{name} {tag}: {res.n_called} of {N} paths called, mean date "
+                                     f"{res.sum_t_call / max(res.n_called, 1)}, {res.work_steps} wave-steps: not all called at "
+                                     f"the first date, {t_first}, after {early} wave-steps")
+                emit(f"{name} {tag} d={d} early exit: all {res.n_called} paths called at step {every}, work={res.work_steps:.0f}",
+                     res, out)
     print(json.dumps({"build_id": capi.build_id()}))
     for s in surf.values():
         s.close()
