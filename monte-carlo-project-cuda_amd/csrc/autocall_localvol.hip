@@ -15,7 +15,7 @@ hipError_t launch_autocall_localvol(const AutocallLocalVolJob &job, double *d_pa
                                     const FinishSpec &finish, hipStream_t stream)
 {
     if (!finish_ok(finish, grid)) return hipErrorInvalidValue;
-    const uint32_t n_steps = job.n_steps;
+    const uint32_t n_steps = job.paths.n_steps;
     if (!autocall_schedule_ok(job.schedule, n_steps)) return hipErrorInvalidValue;
     if (job.d < 1 || job.d > kBasketMaxAssets) return hipErrorInvalidValue;
     uint64_t nodes = 0;                // the D tables share one LDS allocation: no index may leave its own table
@@ -24,7 +24,7 @@ hipError_t launch_autocall_localvol(const AutocallLocalVolJob &job, double *d_pa
         nodes += static_cast<uint64_t>(job.surface[j].n_t) * job.surface[j].n_x;
         if (nodes > kLocalVolMaxNodes) return hipErrorInvalidValue;
     }
-    return job.precision == 32 ? launch_autocall_localvol_f32(job, d_partials, grid, finish, stream)
+    return job.paths.precision == 32 ? launch_autocall_localvol_f32(job, d_partials, grid, finish, stream)
                                : launch_autocall_localvol_f64(job, d_partials, grid, finish, stream);
 }
 

@@ -16,9 +16,7 @@ namespace mcamd {
 
 // Everything in double and in natural-log units; the launcher narrows to the path precision.
 struct AutocallLocalVolJob {
-    uint64_t seed, path_offset, n_local;
-    uint32_t n_steps;
-    int precision;                         // 32 / 64
+    PathRange paths;
     int d;                                 // assets, 1..kBasketMaxAssets
     double mu[kBasketMaxAssets];           // r - q_j
     double chol[kBasketMaxCoefs];          // the Cholesky factor of corr at [j (j + 1) / 2 + k], k <= j

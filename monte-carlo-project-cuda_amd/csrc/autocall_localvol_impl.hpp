@@ -209,7 +209,7 @@ static hipError_t launch_autocall_localvol_d(const AutocallLocalVolJob &j, doubl
     AutocallLocalVolArgs<T, D> a{};
     uint32_t total = 0;
     for (int q = 0; q < D; ++q) {
-        const LvSurface<T> s = lv_surface<T>(j.surface[q], j.n_steps);
+        const LvSurface<T> s = lv_surface<T>(j.surface[q], j.paths.n_steps);
         a.x_min[q] = s.axis.x_min;
         a.inv_dx[q] = s.axis.inv_dx;
         a.u_max[q] = s.axis.u_max;
@@ -235,12 +235,12 @@ static hipError_t launch_autocall_localvol_d(const AutocallLocalVolJob &j, doubl
     a.log_ki = sc.ki ? static_cast<T>(sc.log_ki) : T(0);
     a.dt = sc.dt;
     a.ki = sc.ki ? 1 : 0;
-    a.n_steps = j.n_steps;
+    a.n_steps = j.paths.n_steps;
     a.observe_every = sc.observe_every;
     a.first_call_date = sc.first_call_date;
-    a.seed = j.seed;
-    a.path_offset = j.path_offset;
-    a.n_local = j.n_local;
+    a.seed = j.paths.seed;
+    a.path_offset = j.paths.path_offset;
+    a.n_local = j.paths.n_local;
     a.samples = static_cast<T *>(j.d_samples);
     a.fin = GridFinish{fs.out, fs.ticket, fs.n_value};
     const dim3 g(grid), b(kBlock);

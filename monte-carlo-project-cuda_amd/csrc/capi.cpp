@@ -72,6 +72,23 @@ int ensure_partials(mcamd_ctx *ctx, uint32_t records, int record_doubles)
     return MCAMD_OK;
 }
 
+int enqueue_empty_shard(mcamd_ctx *ctx, double *d_stats, uint32_t n)
+{
+    const uint32_t slot = static_cast<uint32_t>(ctx->n_enqueued % mcamd_ctx::kRing);
+    HIP_TRY(hipMemsetAsync(d_stats, 0, n * sizeof(double), ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ring0[slot], ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ring1[slot], ctx->stream));
+    ctx->n_enqueued++;
+    return MCAMD_OK;
+}
+
+int ensure_partials_enqueued(mcamd_ctx *ctx, uint32_t records, int record_doubles)
+{
+    // wait for work that may still read the old buffer
+    if (static_cast<uint64_t>(records) * record_doubles > ctx->partial_capacity) HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ensure_partials(ctx, records, record_doubles);
+}
+
 int check_request(const mcamd_option *opt, const mcamd_sim *sim)
 {
     if (int rc = check_precision_steps(sim)) return rc;
@@ -182,6 +199,18 @@ int check_spot_start(const char *name, bool american, const mcamd_option *opt, c
                                                   "MCAMD_FLAG_PRODUCT_FORM, got %d"
                                                 : "%s options take flags 0 or MCAMD_FLAG_LOG_SPACE only, got %d",
                     name, sim->flags);
+    return MCAMD_OK;
+}
+
+int check_drift_request(const char *name, mcamd_option seen, const mcamd_sim *sim, const double *mu, int n_mu)
+{
+    seen.v = 1.0;
+    if (int rc = check_spot_start(name, false, &seen, sim)) return rc;
+    seen.v = 0.0;
+    for (int j = 0; j < n_mu; ++j) {
+        seen.r = mu[j];
+        if (int rc = check_request(&seen, sim)) return rc;
+    }
     return MCAMD_OK;
 }
 

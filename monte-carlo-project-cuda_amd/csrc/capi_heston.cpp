@@ -44,26 +44,17 @@ int prepare_heston(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim
     if (int rc = check_heston_model(hs->q, hs->v0, hs->kappa, hs->theta, hs->xi, hs->rho)) return rc;
     if (!std::isfinite(opt->r)) return fail(MCAMD_ERR_INVALID, "option parameters must be finite with T > 0");
     const double mu = opt->r - hs->q;
-    // as the local-volatility calls: on a copy whose ignored fields are harmless.  It carries no volatility of its
-    // own, so check_spot_start sees v = 1 and check_request v = 0, which leaves the drift r - q alone in the fp64
-    // exponent-range bound (the variance is random: no bound on the request can cover it)
+    // as the local-volatility calls: on a copy whose ignored fields are harmless (the variance is random: no bound on
+    // the request can cover it, so the drift r - q stands alone in the fp64 exponent-range bound)
     mcamd_option seen = *opt;
     seen.B = 0.0;
-    seen.v = 1.0;
-    if (int rc = check_spot_start("Heston", false, &seen, sim)) return rc;
-    seen.v = 0.0;
-    seen.r = mu;
-    if (int rc = check_request(&seen, sim)) return rc;
+    if (int rc = check_drift_request("Heston", seen, sim, &mu, 1)) return rc;
     if (!(opt->S0 > 0.0) || !(opt->K > 0.0))
         return fail(MCAMD_ERR_INVALID, "Heston options need S0 > 0 and K > 0 (S0 = %g, K = %g)", opt->S0, opt->K);
     if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
     if (sim->n_paths_local == 0) return drive(empty_call());
     mcamd::HestonJob job;
-    job.seed = sim->seed;
-    job.path_offset = sim->path_offset;
-    job.n_local = sim->n_paths_local;
-    job.n_steps = sim->n_steps;
-    job.precision = sim->precision;
+    job.paths = path_range(sim);
     job.scheme = hs->scheme;
     job.S0 = opt->S0;
     job.K = opt->K;
@@ -77,8 +68,8 @@ int prepare_heston(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim
     job.put = hs->payoff == MCAMD_PAYOFF_PUT;
     job.d_samples = d_samples;
     job.d_state = d_state;
-    const uint32_t grid = mcamd::one_path_per_thread_grid(job.n_local);
-    return drive(DeviceCall{job.n_local, grid, mcamd::kHestonRecord, 6, Finish::kFolded,
+    const uint32_t grid = mcamd::one_path_per_thread_grid(sim->n_paths_local);
+    return drive(DeviceCall{sim->n_paths_local, grid, mcamd::kHestonRecord, 6, Finish::kFolded,
                             [&](const mcamd::FinishSpec &fs) {
                                 return mcamd::launch_heston(job, ctx->d_partials, grid, fs, ctx->stream);
                             }});

@@ -175,10 +175,20 @@ int check_plain(const mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *
 // the flags.  american: the rules of the two American calls, which read only use_window of the window fields, price
 // off S0 and K as well, and take the product form; the others allow MCAMD_FLAG_LOG_SPACE alone.
 int check_spot_start(const char *name, bool american, const mcamd_option *opt, const mcamd_sim *sim);
+// What a call whose volatility is not the option's (the local-volatility calls, Heston; name: how the messages call
+// the product) refuses of the option, the flags and sim through the two checks above.  seen: the caller's copy of the
+// option with every field it does not read made harmless; it carries no volatility of its own, so check_spot_start
+// sees v = 1 and check_request v = 0, which leaves each drift mu[j] = r - q_j alone in the fp64 exponent-range bound.
+int check_drift_request(const char *name, mcamd_option seen, const mcamd_sim *sim, const double *mu, int n_mu);
 
 PathJob make_job(const mcamd_option *opt, const mcamd_sim *sim);
 // The job of a call that runs plain paths whatever the flags say: no variance reduction, the given window and form.
 PathJob make_plain_job(const mcamd_option *opt, const mcamd_sim *sim, bool window, bool logspace);
+// the shard's paths as the local-volatility and Heston jobs carry them
+inline PathRange path_range(const mcamd_sim *sim)
+{
+    return {sim->seed, sim->path_offset, sim->n_paths_local, sim->n_steps, sim->precision};
+}
 
 void zero_result(mcamd_result *res);
 
@@ -305,6 +315,13 @@ int run_sync(mcamd_ctx *ctx, const DeviceCall<Launch> &call, Result *res, Fill f
     return MCAMD_OK;
 }
 
+// capi.cpp: what every enqueue form (run_enqueue and the smile's own) does to the ring and the scratch buffer, after
+// hipSetDevice.  The slot of the call being enqueued is n_enqueued % kRing; a call counts once its kernels are enqueued.
+// The empty shard: n all-zero doubles in d_stats, ordered on the stream, between both events of the slot; counted.
+int enqueue_empty_shard(mcamd_ctx *ctx, double *d_stats, uint32_t n);
+// ensure_partials under an enqueue: growing the scratch buffer frees the old one, so the stream is waited for first
+int ensure_partials_enqueued(mcamd_ctx *ctx, uint32_t records, int record_doubles);
+
 // Asynchronous driver: the kernel runs between a pair of ring events, and its record reaches d_stats in the statistics
 // layout with n_value = n, from the kernel itself (kFolded) or from the separate sum.  Nothing waits on the host but the
 // growth of the scratch buffer.  An empty shard leaves all-zero statistics, still ordered on the stream.
@@ -313,18 +330,10 @@ int run_enqueue(mcamd_ctx *ctx, const DeviceCall<Launch> &call, double *d_stats)
 {
     if (!d_stats) return fail(MCAMD_ERR_INVALID, "d_stats is NULL");
     HIP_TRY(hipSetDevice(ctx->device));
+    if (call.n == 0) return enqueue_empty_shard(ctx, d_stats, static_cast<uint32_t>(call.stats));
     const uint32_t slot = static_cast<uint32_t>(ctx->n_enqueued % mcamd_ctx::kRing);
-    if (call.n == 0) {
-        HIP_TRY(hipMemsetAsync(d_stats, 0, call.stats * sizeof(double), ctx->stream));
-        HIP_TRY(hipEventRecord(ctx->ring0[slot], ctx->stream));
-        HIP_TRY(hipEventRecord(ctx->ring1[slot], ctx->stream));
-        ctx->n_enqueued++;
-        return MCAMD_OK;
-    }
     const double n_value = static_cast<double>(call.n);
-    // growing the scratch buffer frees the old one: wait for work that may still read it
-    if (static_cast<uint64_t>(call.grid) * call.rec > ctx->partial_capacity) HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (int rc = ensure_partials(ctx, call.grid, call.rec)) return rc;
+    if (int rc = ensure_partials_enqueued(ctx, call.grid, call.rec)) return rc;
     FinishSpec fs;
     if (call.how == Finish::kFolded) {
         fs.out = d_stats;

@@ -136,22 +136,6 @@ void finalize_smile_into(const double *stats, uint64_t n, double r, double T, ui
 
 namespace {
 
-// What the local-volatility calls (name: how the messages call the product) refuse of the option, the flags and sim
-// through the checks shared with the other calls.  seen: the caller's copy of the option with every field it does not
-// read made harmless; it carries no volatility of its own, so check_spot_start sees v = 1 and check_request v = 0,
-// which leaves each drift mu[j] = r - q_j alone in the fp64 exponent-range bound.
-int check_localvol_request(const char *name, mcamd_option seen, const mcamd_sim *sim, const double *mu, int n_mu)
-{
-    seen.v = 1.0;
-    if (int rc = check_spot_start(name, false, &seen, sim)) return rc;
-    seen.v = 0.0;
-    for (int j = 0; j < n_mu; ++j) {
-        seen.r = mu[j];
-        if (int rc = check_request(&seen, sim)) return rc;
-    }
-    return MCAMD_OK;
-}
-
 // check_request's fp64 bound with the largest drift and volatility any node of a surface can give; asset >= 0 names
 // the asset the surface belongs to; start: the largest |X_0| of the call's walks.
 int check_localvol_exponent_range(double mu, double sigma_max, double dt, uint32_t n_steps, int asset = -1,
@@ -181,6 +165,32 @@ mcamd::LocalVolGrid job_surface(const mcamd_localvol_surface *surface, int preci
             precision == MCAMD_F32 ? surface->d_tab32 : surface->d_tab64};
 }
 
+// The two refusal stages the four single-surface calls share; a call's own checks stand between them.
+// The drift stage (name: how the messages call the product): the dividend yield q, the rate, then the option (seen: the
+// caller's copy with every field it does not read made harmless), the flags and sim.  *mu receives r - q.
+int check_walk_drift(const char *name, const mcamd_option &seen, const mcamd_sim *sim, double q, double *mu)
+{
+    if (!std::isfinite(q)) return fail(MCAMD_ERR_INVALID, "the dividend yield q must be finite, got %g", q);
+    if (!std::isfinite(seen.r)) return fail(MCAMD_ERR_INVALID, "option parameters must be finite with T > 0");
+    *mu = seen.r - q;
+    return check_drift_request(name, seen, sim, mu, 1);
+}
+
+// The surface stage: the surface (null_message: the call's own words for a NULL one), its fp64 exponent range (start:
+// the largest |X_0| of the call's walks), then the context and whether it owns the surface.  Fills *walk.
+int make_walk(const char *null_message, const mcamd_ctx *ctx, const mcamd_localvol_surface *surface, double mu,
+              const mcamd_option *opt, const mcamd_sim *sim, double start, mcamd::LocalVolWalk *walk)
+{
+    if (!surface) return fail(MCAMD_ERR_INVALID, "%s", null_message);
+    const double dt = even_dt(opt, sim);
+    if (sim->precision == MCAMD_F64)
+        if (int rc = check_localvol_exponent_range(mu, surface->sigma_max, dt, sim->n_steps, -1, start)) return rc;
+    if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
+    if (!surface_belongs(surface, ctx)) return fail(MCAMD_ERR_INVALID, "the surface was created on another context");
+    *walk = {path_range(sim), mu, dt, job_surface(surface, sim->precision)};
+    return MCAMD_OK;
+}
+
 // The local-volatility calls.  The kernel always finishes its own sum (one_path_per_thread_grid caps the grid); every
 // refusal that depends on the request alone comes before the context is looked at, and all that do not need the
 // surface before the surface is.  opt->v is ignored.
@@ -197,43 +207,31 @@ int prepare_localvol(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *s
         return fail(MCAMD_ERR_INVALID, "monitoring must be MCAMD_MONITOR_DISCRETE (0) or MCAMD_MONITOR_CONTINUOUS (1), "
                                        "got %d", lv->monitoring);
     if (lv->reserved != 0) return fail(MCAMD_ERR_INVALID, "localvol->reserved must be 0, got %d", lv->reserved);
+    // a non-finite q is refused ahead of the barrier, which the drift stage comes after
     if (!std::isfinite(lv->q)) return fail(MCAMD_ERR_INVALID, "the dividend yield q must be finite, got %g", lv->q);
     const bool barrier = lv->barrier != MCAMD_LOCALVOL_NO_BARRIER;
     if (barrier) {
         if (int rc = check_barrier_kind(opt->S0, opt->B, lv->barrier, lv->payoff)) return rc;
     }
-    if (!std::isfinite(opt->r)) return fail(MCAMD_ERR_INVALID, "option parameters must be finite with T > 0");
-    const double mu = opt->r - lv->q;
-    if (int rc = check_localvol_request("local-volatility", *opt, sim, &mu, 1)) return rc;
+    double mu;
+    if (int rc = check_walk_drift("local-volatility", *opt, sim, lv->q, &mu)) return rc;
     if (!(opt->S0 > 0.0)) return fail(MCAMD_ERR_INVALID, "local-volatility options need S0 > 0 (S0 = %g)", opt->S0);
-    if (!surface) return fail(MCAMD_ERR_INVALID, "opt, sim, localvol and surface must be non-NULL");
-    const double dt = even_dt(opt, sim);
-    if (sim->precision == MCAMD_F64)
-        if (int rc = check_localvol_exponent_range(mu, surface->sigma_max, dt, sim->n_steps)) return rc;
-    if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
-    if (!surface_belongs(surface, ctx)) return fail(MCAMD_ERR_INVALID, "the surface was created on another context");
-    if (sim->n_paths_local == 0) return drive(empty_call());
     mcamd::LocalVolJob job;
-    job.seed = sim->seed;
-    job.path_offset = sim->path_offset;
-    job.n_local = sim->n_paths_local;
-    job.n_steps = sim->n_steps;
-    job.precision = sim->precision;
+    if (int rc = make_walk("opt, sim, localvol and surface must be non-NULL", ctx, surface, mu, opt, sim, 0.0, &job.walk))
+        return rc;
+    if (sim->n_paths_local == 0) return drive(empty_call());
     job.S0 = opt->S0;
     job.K = opt->K;
     job.B = opt->B;
-    job.mu = mu;
-    job.dt = dt;
     job.barrier = barrier;
     const BarrierSides sides = barrier_sides(lv->barrier);   // MCAMD_LOCALVOL_NO_BARRIER: neither up nor out
     job.up = sides.up;
     job.out = sides.out;
     job.continuous = barrier && lv->monitoring == MCAMD_MONITOR_CONTINUOUS;
     job.put = lv->payoff == MCAMD_PAYOFF_PUT;
-    job.surface = job_surface(surface, sim->precision);
     job.d_samples = d_samples;
-    const uint32_t grid = mcamd::one_path_per_thread_grid(job.n_local);
-    return drive(DeviceCall{job.n_local, grid, mcamd::kLocalVolRecord, 6, Finish::kFolded,
+    const uint32_t grid = mcamd::one_path_per_thread_grid(sim->n_paths_local);
+    return drive(DeviceCall{sim->n_paths_local, grid, mcamd::kLocalVolRecord, 6, Finish::kFolded,
                             [&](const mcamd::FinishSpec &fs) {
                                 return mcamd::launch_localvol(job, ctx->d_partials, grid, fs, ctx->stream);
                             }});
@@ -262,43 +260,29 @@ int prepare_cliquet(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *si
         return fail(MCAMD_ERR_INVALID, "global_floor must lie below global_cap, got %g and %g", cq->global_floor,
                     cq->global_cap);
     if (int rc = check_cliquet_kind_bounds(cq->kind, cq->local_floor, cq->local_cap)) return rc;
-    if (!std::isfinite(cq->q)) return fail(MCAMD_ERR_INVALID, "the dividend yield q must be finite, got %g", cq->q);
-    if (!std::isfinite(opt->r)) return fail(MCAMD_ERR_INVALID, "option parameters must be finite with T > 0");
-    const double mu = opt->r - cq->q;
     // as prepare_localvol, on a copy that carries no spot, strike or barrier of its own either
     mcamd_option seen = *opt;
     seen.S0 = 1.0;
     seen.K = seen.B = 0.0;
-    if (int rc = check_localvol_request("cliquet", seen, sim, &mu, 1)) return rc;
-    if (!surface) return fail(MCAMD_ERR_INVALID, "opt, sim, cliquet and surface must be non-NULL");
-    const double dt = even_dt(opt, sim);
-    if (sim->precision == MCAMD_F64)
-        if (int rc = check_localvol_exponent_range(mu, surface->sigma_max, dt, sim->n_steps)) return rc;
-    if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
-    if (!surface_belongs(surface, ctx)) return fail(MCAMD_ERR_INVALID, "the surface was created on another context");
-    if (sim->n_paths_local == 0) return drive(empty_call());
+    double mu;
+    if (int rc = check_walk_drift("cliquet", seen, sim, cq->q, &mu)) return rc;
     mcamd::CliquetJob job;
-    job.seed = sim->seed;
-    job.path_offset = sim->path_offset;
-    job.n_local = sim->n_paths_local;
-    job.n_steps = sim->n_steps;
-    job.precision = sim->precision;
+    if (int rc = make_walk("opt, sim, cliquet and surface must be non-NULL", ctx, surface, mu, opt, sim, 0.0, &job.walk))
+        return rc;
+    if (sim->n_paths_local == 0) return drive(empty_call());
     job.kind = cq->kind;
     job.reset_every = cq->reset_every;
     job.first_period = cq->first_period;
-    job.mu = mu;
-    job.dt = dt;
     const bool compound = cq->kind == MCAMD_CLIQUET_COMPOUND;
     job.local_lo = compound ? std::log(1.0 + cq->local_floor) : cq->local_floor;
     job.local_hi = compound ? std::log(1.0 + cq->local_cap) : cq->local_cap;
     job.global_lo = cq->global_floor;
     job.global_hi = cq->global_cap;
     const double P = static_cast<double>(M - cq->first_period + 1);
-    job.scale = 1.0 / (P * (static_cast<double>(cq->reset_every) * dt));
-    job.surface = job_surface(surface, sim->precision);
+    job.scale = 1.0 / (P * (static_cast<double>(cq->reset_every) * job.walk.dt));
     job.d_samples = d_samples;
-    const uint32_t grid = mcamd::one_path_per_thread_grid(job.n_local);
-    return drive(DeviceCall{job.n_local, grid, mcamd::kCliquetRecord, 6, Finish::kFolded,
+    const uint32_t grid = mcamd::one_path_per_thread_grid(sim->n_paths_local);
+    return drive(DeviceCall{sim->n_paths_local, grid, mcamd::kCliquetRecord, 6, Finish::kFolded,
                             [&](const mcamd::FinishSpec &fs) {
                                 return mcamd::launch_cliquet(job, ctx->d_partials, grid, fs, ctx->stream);
                             }});
@@ -318,45 +302,35 @@ int prepare_localvol_greeks(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd
                     gj->n_vega_buckets);
     if (!std::isfinite(gj->gamma_bump) || gj->gamma_bump < 0.0 || gj->gamma_bump > 0.1)
         return fail(MCAMD_ERR_INVALID, "gamma_bump must be finite and lie in 0 .. 0.1, got %g", gj->gamma_bump);
-    if (!std::isfinite(gj->q)) return fail(MCAMD_ERR_INVALID, "the dividend yield q must be finite, got %g", gj->q);
-    if (!std::isfinite(opt->r)) return fail(MCAMD_ERR_INVALID, "option parameters must be finite with T > 0");
-    const double mu = opt->r - gj->q;
-    if (int rc = check_localvol_request("local-volatility Greeks", *opt, sim, &mu, 1)) return rc;
+    double mu;
+    if (int rc = check_walk_drift("local-volatility Greeks", *opt, sim, gj->q, &mu)) return rc;
     if (!(opt->S0 > 0.0)) return fail(MCAMD_ERR_INVALID, "local-volatility Greeks need S0 > 0 (S0 = %g)", opt->S0);
-    if (!surface) return fail(MCAMD_ERR_INVALID, "opt, sim, job and surface must be non-NULL");
-    const double dt = even_dt(opt, sim);
-    if (sim->precision == MCAMD_F64)
-        if (int rc = check_localvol_exponent_range(mu, surface->sigma_max, dt, sim->n_steps, -1, gj->gamma_bump)) return rc;
-    if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
-    if (!surface_belongs(surface, ctx)) return fail(MCAMD_ERR_INVALID, "the surface was created on another context");
-    if (sim->n_paths_local == 0) return drive(empty_call(mcamd::kLvGreeksStats));
     mcamd::LocalVolGreeksJob job;
-    job.seed = sim->seed;
-    job.path_offset = sim->path_offset;
-    job.n_local = sim->n_paths_local;
-    job.n_steps = sim->n_steps;
-    job.precision = sim->precision;
+    if (int rc = make_walk("opt, sim, job and surface must be non-NULL", ctx, surface, mu, opt, sim, gj->gamma_bump,
+                           &job.walk))
+        return rc;
+    if (sim->n_paths_local == 0) return drive(empty_call(mcamd::kLvGreeksStats));
     job.S0 = opt->S0;
     job.K = opt->K;
-    job.mu = mu;
-    job.dt = dt;
     job.T = opt->T;
     job.put = gj->payoff == MCAMD_PAYOFF_PUT;
     job.n_buckets = gj->n_vega_buckets;
     job.gamma_bump = gj->gamma_bump;
-    job.surface = job_surface(surface, sim->precision);
     job.d_samples = d_samples;
-    const uint32_t grid = mcamd::one_path_per_thread_grid(job.n_local);
-    return drive(DeviceCall{job.n_local, grid, mcamd::kLvGreeksRecord, mcamd::kLvGreeksStats, Finish::kFolded,
+    const uint32_t grid = mcamd::one_path_per_thread_grid(sim->n_paths_local);
+    return drive(DeviceCall{sim->n_paths_local, grid, mcamd::kLvGreeksRecord, mcamd::kLvGreeksStats, Finish::kFolded,
                             [&](const mcamd::FinishSpec &fs) {
-                                return mcamd::launch_localvol_greeks(job, ctx->d_partials, grid, fs.out, fs.ticket,
-                                                                     ctx->stream);
+                                return mcamd::launch_localvol_greeks(job, ctx->d_partials, grid, fs, ctx->stream);
                             }});
 }
 
 // The smile calls: mcamd_price_localvol's paths without a barrier, stopped at the expiry steps, every strike priced at
 // every expiry.  The refusals follow prepare_localvol's order: the request alone, then the surface, then the context.
 // drive(job, grid) runs the form's driver; grid == 0 is the empty shard.  opt->v and opt->K are ignored.
+// The forms keep drivers of their own, not run_sync / run_enqueue: a smile is two kernels, its per-wavefront records
+// are not the reported grid, and a record holds up to 4096 doubles where DeviceCall's fit the 32 of h_rec.  Hosting
+// that in DeviceCall and Finish would widen both drivers three ways for this one caller; what the enqueue form does
+// share with run_enqueue, the ring and the scratch buffer's growth, it calls (capi_internal.hpp).
 template <typename Drive>
 int prepare_smile(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_smile *sm,
                   const uint32_t *h_expiry_steps, const double *h_strikes, const mcamd_localvol_surface *surface,
@@ -379,39 +353,25 @@ int prepare_smile(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
     for (uint32_t k = 0; k < sm->n_strikes; ++k)
         if (!std::isfinite(h_strikes[k]) || !(h_strikes[k] > 0.0))
             return fail(MCAMD_ERR_INVALID, "every strike must be finite and > 0: h_strikes[%u] = %g", k, h_strikes[k]);
-    if (!std::isfinite(sm->q)) return fail(MCAMD_ERR_INVALID, "the dividend yield q must be finite, got %g", sm->q);
-    if (!std::isfinite(opt->r)) return fail(MCAMD_ERR_INVALID, "option parameters must be finite with T > 0");
     // as prepare_localvol, on a copy that carries no strike of its own either
-    const double mu = opt->r - sm->q;
     mcamd_option seen = *opt;
     seen.K = 1.0;
-    if (int rc = check_localvol_request("local-volatility smile", seen, sim, &mu, 1)) return rc;
+    double mu;
+    if (int rc = check_walk_drift("local-volatility smile", seen, sim, sm->q, &mu)) return rc;
     if (!(opt->S0 > 0.0)) return fail(MCAMD_ERR_INVALID, "local-volatility smile options need S0 > 0 (S0 = %g)", opt->S0);
-    if (!surface)
-        return fail(MCAMD_ERR_INVALID, "opt, sim, smile, h_expiry_steps, h_strikes and surface must be non-NULL");
-    const double dt = even_dt(opt, sim);
-    if (sim->precision == MCAMD_F64)
-        if (int rc = check_localvol_exponent_range(mu, surface->sigma_max, dt, sim->n_steps)) return rc;
-    if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
-    if (!surface_belongs(surface, ctx)) return fail(MCAMD_ERR_INVALID, "the surface was created on another context");
     mcamd::SmileJob job = {};
-    job.seed = sim->seed;
-    job.path_offset = sim->path_offset;
-    job.n_local = sim->n_paths_local;
-    job.n_steps = sim->n_steps;
-    job.precision = sim->precision;
+    if (int rc = make_walk("opt, sim, smile, h_expiry_steps, h_strikes and surface must be non-NULL", ctx, surface, mu, opt,
+                           sim, 0.0, &job.walk))
+        return rc;
     job.S0 = opt->S0;
-    job.mu = mu;
-    job.dt = dt;
     job.put = sm->payoff == MCAMD_PAYOFF_PUT;
-    job.surface = job_surface(surface, sim->precision);
     job.n_expiries = sm->n_expiries;
     job.n_strikes = sm->n_strikes;
     std::copy(h_expiry_steps, h_expiry_steps + sm->n_expiries, job.expiry_steps);
     std::copy(h_strikes, h_strikes + sm->n_strikes, job.strikes);
     job.d_spots = d_spots;
-    const uint32_t grid = job.n_local ? mcamd::smile_grid(job.n_local, job.n_expiries, job.n_strikes, ctx->compute_units) : 0;
-    return drive(job, grid);
+    const uint64_t n = sim->n_paths_local;
+    return drive(job, n ? mcamd::smile_grid(n, job.n_expiries, job.n_strikes, ctx->compute_units) : 0);
 }
 
 // The autocall calls under per-asset local-volatility surfaces.  Every refusal that needs neither a surface nor the
@@ -441,7 +401,7 @@ int prepare_autocall_localvol(mcamd_ctx *ctx, const mcamd_option *opt, const mca
     mcamd_option seen = *opt;
     seen.S0 = 1.0;
     seen.K = seen.B = 0.0;
-    if (int rc = check_localvol_request("local-volatility autocallable", seen, sim, mu, d)) return rc;
+    if (int rc = check_drift_request("local-volatility autocallable", seen, sim, mu, d)) return rc;
     // the surfaces
     if (!surfaces) return fail(MCAMD_ERR_INVALID, "opt, sim, autocall and surfaces must be non-NULL");
     for (int j = 0; j < d; ++j)
@@ -462,11 +422,7 @@ int prepare_autocall_localvol(mcamd_ctx *ctx, const mcamd_option *opt, const mca
     if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
     if (sim->n_paths_local == 0) return drive(empty_call());
     mcamd::AutocallLocalVolJob job{};
-    job.seed = sim->seed;
-    job.path_offset = sim->path_offset;
-    job.n_local = sim->n_paths_local;
-    job.n_steps = sim->n_steps;
-    job.precision = sim->precision;
+    job.paths = path_range(sim);
     job.d = d;
     for (int j = 0; j < d; ++j) {
         job.mu[j] = mu[j];
@@ -475,8 +431,8 @@ int prepare_autocall_localvol(mcamd_ctx *ctx, const mcamd_option *opt, const mca
     }
     make_autocall_schedule(terms, M, opt->r, opt->T, dt, &job.schedule);
     job.d_samples = d_samples;
-    const uint32_t grid = mcamd::one_path_per_thread_grid(job.n_local);
-    return drive(DeviceCall{job.n_local, grid, mcamd::kAutocallRecord, 6, Finish::kFolded,
+    const uint32_t grid = mcamd::one_path_per_thread_grid(sim->n_paths_local);
+    return drive(DeviceCall{sim->n_paths_local, grid, mcamd::kAutocallRecord, 6, Finish::kFolded,
                             [&](const mcamd::FinishSpec &fs) {
                                 return mcamd::launch_autocall_localvol(job, ctx->d_partials, grid, fs, ctx->stream);
                             }});
@@ -657,7 +613,7 @@ int mcamd_price_localvol_smile(mcamd_ctx *ctx, const mcamd_option *opt, const mc
                          [&](const mcamd::SmileJob &job, uint32_t grid) -> int {
         const uint32_t nodes = job.n_expiries * job.n_strikes, n_stats = 2 * nodes;
         std::fill(h_stats, h_stats + n_stats, 0.0);
-        if (job.n_local == 0) return MCAMD_OK;
+        if (grid == 0) return MCAMD_OK;
         HIP_TRY(hipSetDevice(ctx->device));
         if (!ctx->h_smile) {
             HIP_TRY(hipHostMalloc(&ctx->h_smile, mcamd_ctx::kSmileStats * sizeof(double), hipHostMallocDefault));
@@ -676,9 +632,9 @@ int mcamd_price_localvol_smile(mcamd_ctx *ctx, const mcamd_option *opt, const mc
             return fail(MCAMD_ERR_HIP, "the smile kernels left no result (the finishing kernel did not write every node)");
         std::memcpy(h_stats, ctx->h_smile, n_stats * sizeof(double));
         const uint32_t last = job.expiry_steps[job.n_expiries - 1];
-        finalize_into(h_stats[nodes - 1], h_stats[n_stats - 1], job.n_local, opt->r,
-                      static_cast<double>(last) * job.dt, res);
-        res->work_steps = 64.0 * static_cast<double>((job.n_local + 63) / 64) * static_cast<double>(last);
+        finalize_into(h_stats[nodes - 1], h_stats[n_stats - 1], sim->n_paths_local, opt->r,
+                      static_cast<double>(last) * job.walk.dt, res);
+        res->work_steps = 64.0 * static_cast<double>((sim->n_paths_local + 63) / 64) * static_cast<double>(last);
         res->live_steps = res->work_steps;
         res->kernel_ms = kernel_ms;
         res->total_ms = total_ms;
@@ -697,19 +653,10 @@ int mcamd_price_localvol_smile_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, 
                          [&](const mcamd::SmileJob &job, uint32_t grid) -> int {
         const uint32_t n_stats = 2 * job.n_expiries * job.n_strikes;
         HIP_TRY(hipSetDevice(ctx->device));
+        if (grid == 0) return enqueue_empty_shard(ctx, d_stats, n_stats + 1);
         const uint32_t slot = static_cast<uint32_t>(ctx->n_enqueued % mcamd_ctx::kRing);
-        if (job.n_local == 0) {
-            HIP_TRY(hipMemsetAsync(d_stats, 0, (n_stats + 1) * sizeof(double), ctx->stream));
-            HIP_TRY(hipEventRecord(ctx->ring0[slot], ctx->stream));
-            HIP_TRY(hipEventRecord(ctx->ring1[slot], ctx->stream));
-            ctx->n_enqueued++;
-            return MCAMD_OK;
-        }
-        const uint32_t waves = grid * mcamd::kSmileWavesPerBlock;
-        // growing the scratch buffer frees the old one: wait for work that may still read it
-        if (static_cast<uint64_t>(waves) * n_stats > ctx->partial_capacity) HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (int rc = ensure_partials(ctx, waves, static_cast<int>(n_stats))) return rc;
-        if (int rc = launch_smile_pair(ctx, job, grid, d_stats, static_cast<double>(job.n_local), ctx->ring0[slot],
+        if (int rc = ensure_partials_enqueued(ctx, grid * mcamd::kSmileWavesPerBlock, static_cast<int>(n_stats))) return rc;
+        if (int rc = launch_smile_pair(ctx, job, grid, d_stats, static_cast<double>(sim->n_paths_local), ctx->ring0[slot],
                                        ctx->ring1[slot]))
             return rc;
         ctx->n_enqueued++;

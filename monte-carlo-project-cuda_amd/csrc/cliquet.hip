@@ -116,22 +116,15 @@ static hipError_t launch_cliquet_t(const CliquetJob &j, double *d_partials, uint
                                    hipStream_t stream)
 {
     CliquetArgs<T> a;
-    a.surf = lv_surface<T>(j.surface, j.n_steps);
-    a.mu_dt = static_cast<T>(j.mu * j.dt);
-    a.half_dt = static_cast<T>(0.5 * j.dt);
-    a.sqrt_dt = static_cast<T>(std::sqrt(j.dt));
-    a.exp_scale = lv_exp_scale<T>();
+    lv_walk_args<T>(a, j.walk);
     a.lo = static_cast<T>(j.local_lo);
     a.hi = static_cast<T>(j.local_hi);
     a.g_lo = j.global_lo;
     a.g_hi = j.global_hi;
     a.scale = j.scale;
-    a.n_steps = j.n_steps;
+    a.n_steps = j.walk.paths.n_steps;
     a.reset_every = j.reset_every;
     a.first_period = j.first_period;
-    a.seed = j.seed;
-    a.path_offset = j.path_offset;
-    a.n_local = j.n_local;
     a.samples = static_cast<T *>(j.d_samples);
     a.fin = GridFinish{fs.out, fs.ticket, fs.n_value};
     if (j.kind == kCliquetSum) launch_cliquet_k<T, kCliquetSum>(a, d_partials, grid, stream);
@@ -144,11 +137,12 @@ hipError_t launch_cliquet(const CliquetJob &job, double *d_partials, uint32_t gr
                           hipStream_t stream)
 {
     if (!finish_ok(finish, grid)) return hipErrorInvalidValue;
-    if (!lv_grid_ok(job.surface, job.n_steps)) return hipErrorInvalidValue;
+    const uint32_t n_steps = job.walk.paths.n_steps;
+    if (!lv_grid_ok(job.walk.surface, n_steps)) return hipErrorInvalidValue;
     if (job.kind < kCliquetSum || job.kind > kCliquetVariance || job.reset_every == 0 ||
-        job.n_steps % job.reset_every != 0 || job.first_period == 0 || job.first_period > job.n_steps / job.reset_every)
+        n_steps % job.reset_every != 0 || job.first_period == 0 || job.first_period > n_steps / job.reset_every)
         return hipErrorInvalidValue;
-    return job.precision == 32 ? launch_cliquet_t<float>(job, d_partials, grid, finish, stream)
+    return job.walk.paths.precision == 32 ? launch_cliquet_t<float>(job, d_partials, grid, finish, stream)
                                : launch_cliquet_t<double>(job, d_partials, grid, finish, stream);
 }
 

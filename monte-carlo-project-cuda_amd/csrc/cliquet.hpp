@@ -15,18 +15,13 @@ constexpr int kCliquetRecord = 5;
 constexpr int kCliquetSum = 0, kCliquetCompound = 1, kCliquetVariance = 2;   // MCAMD_CLIQUET_*
 
 struct CliquetJob {
-    uint64_t seed, path_offset, n_local;
-    uint32_t n_steps;
-    int precision;           // 32 / 64
+    LocalVolWalk walk;
     int kind;                // kCliquet*
     uint32_t reset_every;    // steps per period; divides n_steps
     uint32_t first_period;   // 1 .. n_steps / reset_every: the first period that counts
-    double mu;               // r - q
-    double dt;               // T / n_steps
     double local_lo, local_hi;     // SUM: the bounds of R_p; COMPOUND: ln(1 + bound), -inf / +inf included; VARIANCE: unread
     double global_lo, global_hi;   // the bounds of A, -inf / +inf: none
     double scale;            // VARIANCE: 1 / (P tau); unread otherwise
-    LocalVolGrid surface;
     void *d_samples;         // nullable: n_local samples of the path precision
 };
 

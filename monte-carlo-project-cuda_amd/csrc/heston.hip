@@ -100,12 +100,12 @@ static hipError_t launch_heston_t(const HestonJob &j, double *d_partials, uint32
     a.v0 = static_cast<T>(j.v0);
     a.K = static_cast<T>(j.K);
     a.S0 = static_cast<T>(j.S0);
-    a.inv_n = 1.0 / static_cast<double>(j.n_steps);
+    a.inv_n = 1.0 / static_cast<double>(j.paths.n_steps);
     a.put = j.put ? 1 : 0;
-    a.n_steps = j.n_steps;
-    a.seed = j.seed;
-    a.path_offset = j.path_offset;
-    a.n_local = j.n_local;
+    a.n_steps = j.paths.n_steps;
+    a.seed = j.paths.seed;
+    a.path_offset = j.paths.path_offset;
+    a.n_local = j.paths.n_local;
     a.samples = static_cast<T *>(j.d_samples);
     a.state = static_cast<T *>(j.d_state);
     a.fin = GridFinish{fs.out, fs.ticket, fs.n_value};
@@ -117,8 +117,8 @@ hipError_t launch_heston(const HestonJob &job, double *d_partials, uint32_t grid
                          hipStream_t stream)
 {
     if (!finish_ok(finish, grid)) return hipErrorInvalidValue;
-    if (job.scheme != kHestonFullTruncation || job.n_steps == 0 || job.n_local == 0) return hipErrorInvalidValue;
-    return job.precision == 32 ? launch_heston_t<float>(job, d_partials, grid, finish, stream)
+    if (job.scheme != kHestonFullTruncation || job.paths.n_steps == 0 || job.paths.n_local == 0) return hipErrorInvalidValue;
+    return job.paths.precision == 32 ? launch_heston_t<float>(job, d_partials, grid, finish, stream)
                                : launch_heston_t<double>(job, d_partials, grid, finish, stream);
 }
 

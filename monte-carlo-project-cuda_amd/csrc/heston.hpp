@@ -15,9 +15,7 @@ constexpr int kHestonRecord = 4;
 constexpr int kHestonFullTruncation = 0;   // MCAMD_HESTON_FULL_TRUNCATION
 
 struct HestonJob {
-    uint64_t seed, path_offset, n_local;
-    uint32_t n_steps;
-    int precision;       // 32 / 64
+    PathRange paths;
     int scheme;          // kHestonFullTruncation
     double S0, K;
     double mu;           // r - q

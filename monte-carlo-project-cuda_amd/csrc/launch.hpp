@@ -24,6 +24,13 @@ struct PathJob {
     int precision;       // 32 / 64
 };
 
+// The paths of a shard as the jobs of the local-volatility and Heston kernels carry them.
+struct PathRange {
+    uint64_t seed, path_offset, n_local;
+    uint32_t n_steps;
+    int precision;   // 32 / 64
+};
+
 constexpr uint32_t kMaxGrid = 1u << 20;  // blocks; beyond this the kernels grid-stride
 constexpr uint32_t kBlockThreads = 256;  // threads per workgroup of every kernel (mc_device.hpp kBlock; reported as block)
 

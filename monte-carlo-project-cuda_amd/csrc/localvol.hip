@@ -132,21 +132,14 @@ static hipError_t launch_localvol_t(const LocalVolJob &j, double *d_partials, ui
     const double q_unit = sizeof(T) == 4 ? kLn2 : 1.0;
     const double q_cut = sizeof(T) == 4 ? 18.0 : 38.0;
     LocalVolArgs<T> a;
-    a.surf = lv_surface<T>(j.surface, j.n_steps);
-    a.mu_dt = static_cast<T>(j.mu * j.dt);
-    a.half_dt = static_cast<T>(0.5 * j.dt);
-    a.sqrt_dt = static_cast<T>(std::sqrt(j.dt));
-    a.exp_scale = lv_exp_scale<T>();
+    lv_walk_args<T>(a, j.walk);
     a.b = j.barrier ? static_cast<T>(std::log(j.B / j.S0)) : T(0);
-    a.kq = static_cast<T>(2.0 / (j.dt * q_unit));
+    a.kq = static_cast<T>(2.0 / (j.walk.dt * q_unit));
     a.q_cut = static_cast<T>(q_cut / q_unit);
     a.K = static_cast<T>(j.K);
     a.S0 = static_cast<T>(j.S0);
     a.put = j.put ? 1 : 0;
-    a.n_steps = j.n_steps;
-    a.seed = j.seed;
-    a.path_offset = j.path_offset;
-    a.n_local = j.n_local;
+    a.n_steps = j.walk.paths.n_steps;
     a.samples = static_cast<T *>(j.d_samples);
     a.fin = GridFinish{fs.out, fs.ticket, fs.n_value};
     if (!j.barrier) launch_localvol_k<T, 0, false, false>(a, d_partials, grid, stream);
@@ -159,8 +152,8 @@ hipError_t launch_localvol(const LocalVolJob &job, double *d_partials, uint32_t 
                            hipStream_t stream)
 {
     if (!finish_ok(finish, grid)) return hipErrorInvalidValue;
-    if (!lv_grid_ok(job.surface, job.n_steps)) return hipErrorInvalidValue;
-    return job.precision == 32 ? launch_localvol_t<float>(job, d_partials, grid, finish, stream)
+    if (!lv_grid_ok(job.walk.surface, job.walk.paths.n_steps)) return hipErrorInvalidValue;
+    return job.walk.paths.precision == 32 ? launch_localvol_t<float>(job, d_partials, grid, finish, stream)
                                : launch_localvol_t<double>(job, d_partials, grid, finish, stream);
 }
 

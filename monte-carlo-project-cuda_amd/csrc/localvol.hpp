@@ -28,19 +28,22 @@ struct LocalVolGrid {
     const void *d_table;   // n_t n_x VolPair of the path precision, device memory, 16-byte aligned
 };
 
-struct LocalVolJob {
-    uint64_t seed, path_offset, n_local;
-    uint32_t n_steps;
-    int precision;       // 32 / 64
-    double S0, K, B;     // B read with a barrier only
+// What every job that walks one surface carries: the paths, the drift, the step and the surface.
+struct LocalVolWalk {
+    PathRange paths;
     double mu;           // r - q
     double dt;           // T / n_steps
+    LocalVolGrid surface;
+};
+
+struct LocalVolJob {
+    LocalVolWalk walk;
+    double S0, K, B;     // B read with a barrier only
     bool barrier;        // knock-out / knock-in at B (else European)
     bool up;             // the barrier lies above the spot (else below)
     bool out;            // knock-out (else knock-in)
     bool continuous;     // Brownian-bridge survival factors with the step's frozen volatility
     bool put;            // h(S) = (K - S)+ (else (S - K)+)
-    LocalVolGrid surface;
     void *d_samples;     // nullable: n_local samples of the path precision
 };
 

@@ -74,6 +74,22 @@ inline T lv_exp_scale()
     return static_cast<T>(sizeof(T) == 4 ? 1.4426950408889634 : f64::kExpScale);
 }
 
+// What the argument structs of the single-surface kernels (LocalVolArgs, CliquetArgs, LvGreeksArgs, SmileArgs) have in
+// common, from the walk of their job.  The structs share no sub-struct: each kernel's scalar loads are compiled against
+// its own layout.
+template <typename T, typename Args>
+inline void lv_walk_args(Args &a, const LocalVolWalk &w)
+{
+    a.surf = lv_surface<T>(w.surface, w.paths.n_steps);
+    a.mu_dt = static_cast<T>(w.mu * w.dt);
+    a.half_dt = static_cast<T>(0.5 * w.dt);
+    a.sqrt_dt = static_cast<T>(std::sqrt(w.dt));
+    a.exp_scale = lv_exp_scale<T>();
+    a.seed = w.paths.seed;
+    a.path_offset = w.paths.path_offset;
+    a.n_local = w.paths.n_local;
+}
+
 __device__ __forceinline__ float lv_min(float a, float b) { return __builtin_fminf(a, b); }
 __device__ __forceinline__ double lv_min(double a, double b) { return __builtin_fmin(a, b); }
 __device__ __forceinline__ float lv_max(float a, float b) { return __builtin_fmaxf(a, b); }

@@ -193,35 +193,29 @@ static void launch_lv_greeks_k(const LvGreeksArgs<T> &a, double *d_partials, uin
 }
 
 template <typename T>
-static hipError_t launch_lv_greeks_t(const LocalVolGreeksJob &j, double *d_partials, uint32_t grid, double *out,
-                                     unsigned int *ticket, hipStream_t stream)
+static hipError_t launch_lv_greeks_t(const LocalVolGreeksJob &j, double *d_partials, uint32_t grid, const FinishSpec &fs,
+                                     hipStream_t stream)
 {
+    const uint32_t n_steps = j.walk.paths.n_steps;
     LvGreeksArgs<T> a;
-    a.surf = lv_surface<T>(j.surface, j.n_steps);
-    a.mu_dt = static_cast<T>(j.mu * j.dt);
-    a.half_dt = static_cast<T>(0.5 * j.dt);
-    a.sqrt_dt = static_cast<T>(std::sqrt(j.dt));
-    a.dt = static_cast<T>(j.dt);
-    a.exp_scale = lv_exp_scale<T>();
+    lv_walk_args<T>(a, j.walk);
+    a.dt = static_cast<T>(j.walk.dt);
     a.K = static_cast<T>(j.K);
     a.S0 = static_cast<T>(j.S0);
     a.eta = static_cast<T>(j.gamma_bump);
     a.put = j.put ? 1 : 0;
-    a.n_steps = j.n_steps;
+    a.n_steps = n_steps;
     a.n_buckets = j.n_buckets;
-    a.bkt_whole = j.n_buckets / j.n_steps;
-    a.bkt_rem = j.n_buckets % j.n_steps;
-    a.bkt_thr = j.n_steps - a.bkt_rem;
-    a.seed = j.seed;
-    a.path_offset = j.path_offset;
-    a.n_local = j.n_local;
+    a.bkt_whole = j.n_buckets / n_steps;
+    a.bkt_rem = j.n_buckets % n_steps;
+    a.bkt_thr = n_steps - a.bkt_rem;
     a.S0d = j.S0;
     a.T_mat = j.T;
     a.S_up = j.S0 * std::exp(j.gamma_bump);
     a.S_dn = j.S0 * std::exp(-j.gamma_bump);
     a.dS = a.S_up - a.S_dn;
     a.samples = j.d_samples;
-    a.fin = GridFinish{out, ticket, -1.0};
+    a.fin = GridFinish{fs.out, fs.ticket, -1.0};   // the kernel writes its own 32-double layout, n included
     const bool gamma = j.gamma_bump > 0.0, buckets = j.n_buckets != 0;
     if (gamma) {
         if (buckets) launch_lv_greeks_k<T, true, true>(a, d_partials, grid, stream);
@@ -233,13 +227,14 @@ static hipError_t launch_lv_greeks_t(const LocalVolGreeksJob &j, double *d_parti
     return hipGetLastError();
 }
 
-hipError_t launch_localvol_greeks(const LocalVolGreeksJob &job, double *d_partials, uint32_t grid, double *out,
-                                  unsigned int *ticket, hipStream_t stream)
+hipError_t launch_localvol_greeks(const LocalVolGreeksJob &job, double *d_partials, uint32_t grid, const FinishSpec &finish,
+                                  hipStream_t stream)
 {
-    if (!out || !ticket || grid == 0 || grid > kFoldMaxRecords) return hipErrorInvalidValue;
-    if (!lv_grid_ok(job.surface, job.n_steps) || job.n_buckets > kLvGreeksMaxBuckets) return hipErrorInvalidValue;
-    return job.precision == 32 ? launch_lv_greeks_t<float>(job, d_partials, grid, out, ticket, stream)
-                               : launch_lv_greeks_t<double>(job, d_partials, grid, out, ticket, stream);
+    if (!finish_ok(finish, grid)) return hipErrorInvalidValue;
+    if (!lv_grid_ok(job.walk.surface, job.walk.paths.n_steps) || job.n_buckets > kLvGreeksMaxBuckets)
+        return hipErrorInvalidValue;
+    return job.walk.paths.precision == 32 ? launch_lv_greeks_t<float>(job, d_partials, grid, finish, stream)
+                                          : launch_lv_greeks_t<double>(job, d_partials, grid, finish, stream);
 }
 
 }  // namespace mcamd

@@ -16,24 +16,19 @@ constexpr int kLvGreeksRecord = 2 * (kLvGreeks + kLvGreeksMaxBuckets);   // 28
 constexpr int kLvGreeksStats = 32;        // the record, n, zeros
 
 struct LocalVolGreeksJob {
-    uint64_t seed, path_offset, n_local;
-    uint32_t n_steps;
-    int precision;        // 32 / 64
+    LocalVolWalk walk;
     double S0, K;
-    double mu;            // r - q
-    double dt;            // T / n_steps
     double T;
     bool put;
     uint32_t n_buckets;   // 0 .. kLvGreeksMaxBuckets
     double gamma_bump;    // eta; 0: no gamma
-    LocalVolGrid surface;
     double *d_samples;    // nullable: (6 + n_buckets) x n_local doubles, estimator-major
 };
 
 // Enqueues the kernel on a grid of one_path_per_thread_grid(n_local) workgroups with n_t n_x sizeof(VolPair) bytes of
-// dynamic LDS.  out: the 32-double statistics record ([28] = n_local, [29..32) = 0), written by the kernel itself;
-// d_partials: grid x kLvGreeksRecord doubles; *ticket zero at launch.
-hipError_t launch_localvol_greeks(const LocalVolGreeksJob &job, double *d_partials, uint32_t grid, double *out,
-                                  unsigned int *ticket, hipStream_t stream);
+// dynamic LDS.  finish.out: the 32-double statistics record ([28] = n_local, [29..32) = 0), which the kernel writes
+// itself whatever finish.n_value says; d_partials: grid x kLvGreeksRecord doubles.
+hipError_t launch_localvol_greeks(const LocalVolGreeksJob &job, double *d_partials, uint32_t grid, const FinishSpec &finish,
+                                  hipStream_t stream);
 
 }  // namespace mcamd

@@ -167,19 +167,12 @@ template <typename T>
 static hipError_t launch_smile_t(const SmileJob &j, double *d_partials, uint32_t grid, hipStream_t stream)
 {
     SmileArgs<T> a;
-    a.surf = lv_surface<T>(j.surface, j.n_steps);
-    a.mu_dt = static_cast<T>(j.mu * j.dt);
-    a.half_dt = static_cast<T>(0.5 * j.dt);
-    a.sqrt_dt = static_cast<T>(std::sqrt(j.dt));
-    a.exp_scale = lv_exp_scale<T>();
+    lv_walk_args<T>(a, j.walk);
     a.S0 = static_cast<T>(j.S0);
     a.put = j.put ? 1 : 0;
     a.n_expiries = j.n_expiries;
     a.n_strikes = j.n_strikes;
     a.last_step = j.expiry_steps[j.n_expiries - 1];
-    a.seed = j.seed;
-    a.path_offset = j.path_offset;
-    a.n_local = j.n_local;
     a.spots = static_cast<T *>(j.d_spots);
     for (uint32_t m = 0; m < kSmileMaxExpiries; ++m) a.expiry_steps[m] = m < j.n_expiries ? j.expiry_steps[m] : 0xFFFFFFFFu;
     for (uint32_t k = 0; k < kSmileMaxStrikes; ++k) a.strikes[k] = k < j.n_strikes ? static_cast<T>(j.strikes[k]) : T(0);
@@ -191,14 +184,14 @@ static hipError_t launch_smile_t(const SmileJob &j, double *d_partials, uint32_t
 hipError_t launch_localvol_smile(const SmileJob &job, double *d_partials, uint32_t grid, hipStream_t stream)
 {
     if (!d_partials || grid == 0 || grid > kFoldMaxRecords) return hipErrorInvalidValue;
-    if (!lv_grid_ok(job.surface, job.n_steps)) return hipErrorInvalidValue;
+    if (!lv_grid_ok(job.walk.surface, job.walk.paths.n_steps)) return hipErrorInvalidValue;
     if (job.n_expiries < 1 || job.n_expiries > kSmileMaxExpiries || job.n_strikes < 1 || job.n_strikes > kSmileMaxStrikes)
         return hipErrorInvalidValue;
     for (uint32_t m = 0; m < job.n_expiries; ++m) {
         const uint32_t lo = m ? job.expiry_steps[m - 1] : 0;
-        if (job.expiry_steps[m] <= lo || job.expiry_steps[m] > job.n_steps) return hipErrorInvalidValue;
+        if (job.expiry_steps[m] <= lo || job.expiry_steps[m] > job.walk.paths.n_steps) return hipErrorInvalidValue;
     }
-    return job.precision == 32 ? launch_smile_t<float>(job, d_partials, grid, stream)
+    return job.walk.paths.precision == 32 ? launch_smile_t<float>(job, d_partials, grid, stream)
                                : launch_smile_t<double>(job, d_partials, grid, stream);
 }
 

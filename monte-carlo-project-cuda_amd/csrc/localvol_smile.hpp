@@ -18,14 +18,9 @@ constexpr uint32_t kSmileWavesPerBlock = kBlockThreads / 64;
 constexpr uint64_t kSmilePartialsBudget = 64ull << 20;
 
 struct SmileJob {
-    uint64_t seed, path_offset, n_local;
-    uint32_t n_steps;
-    int precision;       // 32 / 64
+    LocalVolWalk walk;
     double S0;
-    double mu;           // r - q
-    double dt;           // T / n_steps
     bool put;            // h(S) = (K - S)+ at every node (else (S - K)+)
-    LocalVolGrid surface;
     uint32_t n_expiries, n_strikes;
     uint32_t expiry_steps[kSmileMaxExpiries];   // strictly ascending, 1 .. n_steps
     double strikes[kSmileMaxStrikes];

@@ -125,6 +125,104 @@ def test_both_forms_refuse_alike_and_a_refused_enqueue_is_not_counted(ctx, name,
     assert torch.all(stats == 0), "a refused enqueue wrote its statistics buffer"
 
 
+# ---- the surface stage of the four calls that walk one local-volatility surface -------------------------------------------
+# After everything a call refuses of the request alone: the surface NULL, its fp64 exponent range, the context, and
+# whether the context owns the surface, in this order and in the same words for every call.  No CPU test reaches the
+# last three, because a surface needs a live context.  Every request here is refused, so no kernel runs.
+
+class _NoSurface:
+    _h = None   # what the wrappers pass to the library: a NULL surface
+
+
+LV_OPT = dict(S0=100.0, K=100.0, T=100.0, r=0.1, v=0.0)   # dt = 2 over 50 steps: a volatility of 100 leaves the range
+LV_STEPS, LV_STRIKES = (25, 50), (90.0, 110.0)
+
+
+def _lv(c, o, s, surface, stats):
+    job = capi.make_localvol()
+    return c.price_localvol(o, s, job, surface) if stats is None else c.price_localvol_enqueue(o, s, job, surface, stats)
+
+
+def _lv_smile(c, o, s, surface, stats):
+    sm = capi.make_smile(len(LV_STEPS), len(LV_STRIKES))
+    if stats is None:
+        return c.price_localvol_smile(o, s, sm, LV_STEPS, LV_STRIKES, surface)
+    return c.price_localvol_smile_enqueue(o, s, sm, LV_STEPS, LV_STRIKES, surface, stats)
+
+
+def _lv_greeks(c, o, s, surface, stats):
+    job = capi.make_localvol_greeks_job(n_vega_buckets=2, gamma_bump=0.01)
+    if stats is None:
+        return c.price_localvol_greeks(o, s, job, surface)
+    return c.price_localvol_greeks_enqueue(o, s, job, surface, stats)
+
+
+def _cliquet(c, o, s, surface, stats):
+    cq = capi.make_cliquet(capi.CLIQUET_SUM, reset_every=10)
+    return c.price_cliquet(o, s, cq, surface) if stats is None else c.price_cliquet_enqueue(o, s, cq, surface, stats)
+
+
+# (call, its own words for a NULL surface)
+LV_CALLS = {
+    "localvol": (_lv, "opt, sim, localvol and surface must be non-NULL"),
+    "smile": (_lv_smile, "opt, sim, smile, h_expiry_steps, h_strikes and surface must be non-NULL"),
+    "greeks": (_lv_greeks, "opt, sim, job and surface must be non-NULL"),
+    "cliquet": (_cliquet, "opt, sim, cliquet and surface must be non-NULL"),
+}
+LV_FORMS = [(name, form) for name in LV_CALLS for form in ("sync", "enqueue")]
+# (case, what every call's message holds whatever the product)
+LV_STAGES = [("no surface", "and surface must be non-NULL"), ("wild on its own context", "exponent range"),
+             ("wild on the other context", "exponent range"), ("flat of the other context", "another context")]
+
+
+@pytest.fixture(scope="module")
+def two(ctx):
+    """two contexts on device 0, a flat 1 x 2 surface on each, and on the first one whose volatility of 100 an fp64
+    job of 50 steps over T = 100 cannot carry in its exponent"""
+    other = capi.Context(0, torch.cuda.current_stream().cuda_stream)
+    made = []
+    try:
+        for c, sigma in ((ctx, [[0.2, 0.2]]), (other, [[0.2, 0.2]]), (ctx, [[0.2, 100.0]])):
+            made.append(c.localvol_surface((1, 2, -1.0, 1.0), sigma))
+        yield dict(a=ctx, b=other, flat_a=made[0], flat_b=made[1], wild_a=made[2])
+    finally:
+        for s in made:
+            s.close()
+        other.close()
+
+
+def _lv_refusal(two, name, form, case):
+    """(code, message) of the refusal of one case by one form of one call"""
+    c, surface = {"no surface": (two["a"], _NoSurface), "wild on its own context": (two["a"], two["wild_a"]),
+                  "wild on the other context": (two["b"], two["wild_a"]),
+                  "flat of the other context": (two["a"], two["flat_b"])}[case]
+    with pytest.raises(capi.McamdError) as e:
+        LV_CALLS[name][0](c, opt(**LV_OPT), capi.make_sim(1000, 50, F64, n_paths_local=256), surface,
+                          None if form == "sync" else dev(64))
+    return e.value.code, str(e.value)
+
+
+@pytest.mark.parametrize("name,form", LV_FORMS, ids=[f"{n}-{f}" for n, f in LV_FORMS])
+def test_the_surface_stage_refuses_in_one_order(two, name, form):
+    for case, fixed in LV_STAGES:
+        code, msg = _lv_refusal(two, name, form, case)
+        assert code == capi.ERR_INVALID and fixed in msg, (case, msg)
+        if case == "no surface":
+            assert LV_CALLS[name][1] in msg, msg
+    # the flat surface on its own context passes every refusal of the request: an empty shard is accepted
+    empty = capi.make_sim(1000, 50, F64, n_paths_local=0)
+    for c, surface in ((two["a"], two["flat_a"]), (two["b"], two["flat_b"])):
+        LV_CALLS[name][0](c, opt(**LV_OPT), empty, surface, None if form == "sync" else dev(64))
+
+
+@pytest.mark.parametrize("case,fixed", LV_STAGES, ids=[c for c, _ in LV_STAGES])
+def test_the_surface_stage_speaks_alike_in_every_call(two, case, fixed):
+    said = {(name, form): _lv_refusal(two, name, form, case) for name, form in LV_FORMS}
+    # from the fixed words on for the NULL surface, whose message names the call's arguments before them; whole otherwise
+    tails = {(code, msg[msg.index(fixed):] if case == "no surface" else msg) for code, msg in said.values()}
+    assert len(tails) == 1, said
+
+
 def test_a_refused_enqueue_leaves_the_ring_count(ctx):
     fresh = capi.Context(0, torch.cuda.current_stream().cuda_stream)
     try:

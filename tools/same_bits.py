@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Do two builds of the library compute the same bits?  One fresh worker process per library (MCAMD_LIB) runs a fixed
 list of small jobs on the kernels that walk a local-volatility surface — mcamd_price_localvol, mcamd_price_localvol_smile,
-mcamd_price_autocall_localvol, mcamd_price_cliquet, mcamd_price_localvol_greeks — and on the one-path-per-thread kernels
-of constant volatility — mcamd_price_barrier, mcamd_price_lookback, mcamd_price_asian, the likelihood-ratio and pathwise
+mcamd_price_autocall_localvol, mcamd_price_cliquet, mcamd_price_localvol_greeks — on mcamd_price_heston (a put and a
+call, with the samples and the final state), and on the one-path-per-thread kernels of constant volatility — mcamd_price_barrier, mcamd_price_lookback, mcamd_price_asian, the likelihood-ratio and pathwise
 mcamd_price_greeks, mcamd_price_american, mcamd_american_upper_bound, and on d = 1..8 correlated assets
 mcamd_price_basket and mcamd_price_autocall — and prints a SHA-256 per job over the per-path
 outputs where the call has them (samples, spots, continuation values, coefficients) and the result record without its
@@ -131,6 +131,14 @@ def worker():
                         job = capi.make_localvol_greeks_job(capi.PAYOFF_PUT if n_b == 3 else capi.PAYOFF_CALL, n_b, 0.02, bump)
                         res = ctx.price_localvol_greeks(opt, sim(n_steps, prec, off), job, surf[sname], each)
                         emit(f"localvol greeks {tag} {sname} n={n_steps} buckets={n_b} bump={bump}", res, each)
+            # mcamd_price_heston: a put and a call; xi = 1 against kappa theta = 0.08 sends variances below zero
+            opt = capi.make_option(S0=100.0, K=100.0, r=0.05, v=0.0, T=1.0)
+            state = torch.empty(2 * N, dtype=dtype[prec], device="cuda")
+            for n_steps in STEPS_WALK:
+                for pay in (capi.PAYOFF_CALL, capi.PAYOFF_PUT):
+                    hs = capi.make_heston(pay, q=0.02, v0=0.04, kappa=2.0, theta=0.04, xi=1.0, rho=-0.7)
+                    res = ctx.price_heston(opt, sim(n_steps, prec, off), hs, out.zero_(), state.zero_())
+                    emit(f"heston {tag} n={n_steps} pay={pay}", res, out, state)
             # mcamd_price_barrier: every kind, monitoring and payoff
             for n_steps in STEPS_WALK:
                 for kind in range(4):
