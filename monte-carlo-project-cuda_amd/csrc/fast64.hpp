@@ -8,6 +8,7 @@
 // three 512-entry tables (20 KB per workgroup) keep every polynomial at degree <= 4.
 //
 //   neg2log(u)        -2 ln u          u in [2^-53, 1]                 10 fp64 ops
+//   neg2log_1k(u)     -2 ln u          the same on a 1024-entry table of its own (pair-sum kernels only): 6 fp64 ops
 //   sqrt_pos(a)       sqrt(a)          a >= 0 (clamped to >= 1e-300)   v_rsq_f64 + 8 fp64 ops
 //   sincos_bits(z,w)  sin, cos(pi t)   t = (v2 + 1) 2^-52 from two Philox words: 11 fp64 ops, no int->fp convert
 //   ExpAcc            running product of e^x_i kept as 2^(k/65536) * P: 6 fp64 ops per factor, no table
@@ -41,7 +42,7 @@ struct alignas(16) D2 {
 
 // Pointers to the three tables: LDS copies inside a kernel, the static arrays on the host.
 struct Tables {
-    const D2 *log_tab;        // {-2/c_i, -2 ln c_i}
+    const D2 *log_tab;        // {-2/c_i, -2 ln c_i}: 512 chunks for neg2log; the 1024 of neg2log_1k in a pair-sum kernel
     const D2 *sincos_tab;     // {sin, cos}(2 pi (j + 1/2) / 512): nodes at the MIDDLE of each of the 512 arcs
     const double *exp_hi_tab; // 2^(i/256),   i in [0, 256)
     const double *exp_lo_tab; // 2^(i/65536), i in [0, 256)
@@ -187,6 +188,28 @@ MC_HD double neg2log(double u, const D2 *tab)
     q = fma_vvv(t, q, 1.0 / 12.0);
     q = fma_vvv(t, q, 0.25);
     return w + __builtin_fma(t * t, q, t);
+}
+
+// -2 ln(u) for the pair-sum loops (mc_device.hpp PairSum<double>), on a table of 1024 chunks (kLogTab1k): same
+// reduction as neg2log with ten index bits, so |t| < 2^-10 and the series can stop at t^4/32 — the dropped t^5/80 is
+// below 1.1e-17 absolute — and the whole value is ONE fma chain, six fp64 operations where neg2log has eight:
+//   w + t (1 + t/4 + t^2/12 + t^3/32).
+// <= 2 ulp for u <= 1 - 2^-9; above that the result is below 2e-3 and the truncation shows as up to ~100 ulp of it,
+// < 2e-17 absolute, which is what the radius feeds into a path's sum.  Strictly positive for every u in (0, 1]: the
+// row that serves u = 1 is biased by 1.55e-17 (tools/gen_tables64.py), so sqrt_unclamped needs no clamp.
+MC_HD double neg2log_1k(double u, const D2 *tab1k)
+{
+    const uint32_t hx = hi32(u);
+    const uint32_t tmp = hx - 0x3fe60000u;
+    const int32_t k = static_cast<int32_t>(tmp) >> 20;
+    const double z = make_double(lo32(u), hx - (tmp & 0xfff00000u));
+    const D2 e = *reinterpret_cast<const D2 *>(reinterpret_cast<const char *>(tab1k) + ((tmp >> 6) & 0x3ff0u));
+    const double t = __builtin_fma(z, e.a, 2.0);
+    const double w = __builtin_fma(static_cast<double>(k), kM2Ln2, e.b);
+    double q = fma_usv(t, 1.0 / 32.0, 1.0 / 12.0);
+    q = fma_vvv(t, q, 0.25);
+    const double h = __builtin_fma(t, q, 1.0);
+    return __builtin_fma(t, h, w);
 }
 
 // sqrt(a), a >= 0: hardware reciprocal-sqrt seed, one coupled Newton step, one correction.

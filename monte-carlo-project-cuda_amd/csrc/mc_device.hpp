@@ -264,8 +264,9 @@ __device__ __forceinline__ void philox_walk(const PhiloxKeys &key, uint64_t subs
 
 // ---------------------------------------------------------------------------------------------
 // Per-workgroup math context.  The fp64 path uses the table-driven functions of fast64.hpp; their
-// three 512-entry tables (20 KB) are copied into LDS once per workgroup, so the per-lane lookups
-// run on the LDS pipe beside the VALU.  The fp32 path needs nothing (hardware transcendentals).
+// three 512-entry tables (20 KB; 28 KB in a pair-sum kernel, whose log table has 1024 entries) are copied into LDS
+// once per workgroup, so the per-lane lookups run on the LDS pipe beside the VALU.  The fp32 path needs nothing
+// (hardware transcendentals).
 // ---------------------------------------------------------------------------------------------
 template <typename T>
 struct MathCtx {
@@ -282,12 +283,14 @@ struct MathCtx<double> {
     // saturated a newly launched wave otherwise needs ~58 us for these thirty instructions (tools/init_probe.hip:
     // 1.4 us on an idle CU) — during which its workgroup holds LDS and registers without computing.
     // ROTATED: the sin/cos table is copied rotated by an eighth of a turn (entry j = arc j + N/8), which is what the
-    // pair-sum loop (PairSum below) looks up; a kernel uses one form or the other, never both.
+    // pair-sum loop (PairSum below) looks up; a kernel uses one form or the other, never both.  That loop also takes
+    // its logarithm from the 1024-entry table (f64::neg2log_1k), so ROTATED copies kLogTab1k where the plain form
+    // copies kLogTab: 28 840 bytes of LDS per workgroup instead of 20 648.
     template <bool ROTATED = false>
     __device__ __forceinline__ static MathCtx init()
     {
         __builtin_amdgcn_s_setprio(3);
-        __shared__ f64::D2 s_log[MCAMD_TAB_N];
+        __shared__ f64::D2 s_log[ROTATED ? MCAMD_LOG1K_N : MCAMD_TAB_N];
         __shared__ f64::D2 s_sincos[MCAMD_TAB_N];
         __shared__ double s_exp_hi[256];
         __shared__ double s_exp_lo[256];
@@ -295,15 +298,19 @@ struct MathCtx<double> {
         for (int i = threadIdx.x; i < MCAMD_TAB_N; i += blockDim.x) {
             const int j = ROTATED ? ((i + MCAMD_TAB_N / 8) & (MCAMD_TAB_N - 1)) : i;
 #if defined(MCAMD_LDS_PLANES)   // experiment: two 8-byte planes per table (fast64.hpp table_entry)
-            reinterpret_cast<double *>(s_log)[i] = kLogTab[i][0];
-            reinterpret_cast<double *>(s_log)[MCAMD_TAB_N + i] = kLogTab[i][1];
+            if (!ROTATED) {
+                reinterpret_cast<double *>(s_log)[i] = kLogTab[i][0];
+                reinterpret_cast<double *>(s_log)[MCAMD_TAB_N + i] = kLogTab[i][1];
+            }
             reinterpret_cast<double *>(s_sincos)[i] = kSinCosTab[j][0];
             reinterpret_cast<double *>(s_sincos)[MCAMD_TAB_N + i] = kSinCosTab[j][1];
 #else
-            s_log[i] = f64::D2{kLogTab[i][0], kLogTab[i][1]};
+            if (!ROTATED) s_log[i] = f64::D2{kLogTab[i][0], kLogTab[i][1]};
             s_sincos[i] = f64::D2{kSinCosTab[j][0], kSinCosTab[j][1]};
 #endif
         }
+        if (ROTATED)
+            for (int i = threadIdx.x; i < MCAMD_LOG1K_N; i += blockDim.x) s_log[i] = f64::D2{kLogTab1k[i][0], kLogTab1k[i][1]};
         for (int i = threadIdx.x; i < 256; i += blockDim.x) {
             s_exp_hi[i] = kExpHiTab[i];
             s_exp_lo[i] = kExpLoTab[i];
@@ -642,7 +649,7 @@ struct PairSum<double> {
     __device__ __forceinline__ static double add_words(double acc, const U4 &w, const MathCtx<double> &m)
     {
         const double u = f64::u53(w.x, w.y, 0x1p-53);
-        const double r = f64::sqrt_unclamped(f64::neg2log(u, m.t.log_tab));   // strictly positive argument (fast64.hpp)
+        const double r = f64::sqrt_unclamped(f64::neg2log_1k(u, m.t.log_tab));   // strictly positive argument (fast64.hpp)
         return __builtin_fma(r, f64::sin_bits_rotated<false>(w.z, w.w, m.t.sincos_tab, nullptr), acc);
     }
     // n == 1: z0 = r sin a = r (sin a' - cos a') / sqrt 2 with a' = a + pi/4 the rotated angle
@@ -654,7 +661,7 @@ struct PairSum<double> {
     __device__ __forceinline__ static double head_words(const U4 &w, const MathCtx<double> &m, uint32_t = 1)
     {
         const double u = f64::u53(w.x, w.y, 0x1p-53);
-        const double r = f64::sqrt_unclamped(f64::neg2log(u, m.t.log_tab));
+        const double r = f64::sqrt_unclamped(f64::neg2log_1k(u, m.t.log_tab));
         double cs;
         const double sn = f64::sin_bits_rotated<true>(w.z, w.w, m.t.sincos_tab, &cs);
         return r * (0.5 * (sn - cs));

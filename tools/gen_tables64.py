@@ -5,6 +5,7 @@ committed, so neither the library nor the tests depend on mpmath.
 
   LOG    512 x (-2/c_i, -2 ln c_i)      -2 ln(z) = -2 ln c_i + g(t), t = fma(z, -2/c_i, 2), |t| < 2^-9
   SINCOS 512 x (sin, cos)(2 pi (j + 1/2)/512)   nodes at the arc midpoints (fast64.hpp sincos_bits)
+  LOG1K  1024 x (-2/c_i, -2 ln c_i)     the same with |t| < 2^-10, for the pair-sum kernels (fast64.hpp neg2log_1k)
   EXP_HI 256 x 2^(i/256),  EXP_LO 256 x 2^(i/65536)   two-level table of 2^(k/65536) (fast64.hpp ExpAcc)
 (20 KB in all: 512 entries keep the log / sin / cos polynomials at degree <= 4)
 Table layout follows the standard "reduce with a small table, finish with a short polynomial" scheme
@@ -58,6 +59,56 @@ def log_table():
     return rows
 
 
+N1K = 1024
+LOGB1K = 10
+# What neg2log_1k returns at u = 1 without a bias is its truncation: the chain stops at t^4/32, and the dropped
+# t^5/80 (t = 2 - 2/c of the chunk [1, 1 + 2^-10), 9.76e-4) leaves -1.108e-17 there.  log_table_1k() evaluates the
+# chain operation by operation, as the device does (every step is one fma, so the bits are the device's), and asserts
+# what the bias has to give: a result at u = 1 that is strictly positive, and small enough that the largest pair sum
+# there, sqrt(2 a), stays within the 3e-9 the device tests allow at u = 1.  1.55e-17 leaves a = 4.4e-18 (radius
+# 2.1e-9; the 512-entry table's 4e-18 leaves 3.6e-18).  Everywhere else in that chunk the result is >= 1.38, where
+# the bias is 1/14 ulp.
+BIAS_1K = 1.55e-17
+
+
+def fma(a: float, b: float, c: float) -> float:
+    return dbl(mp.mpf(a) * mp.mpf(b) + mp.mpf(c))  # the 60-digit sum is exact, so this rounds once
+
+
+def neg2log_1k_of_one(row) -> float:
+    """fast64.hpp neg2log_1k at u = 1 (z = 1, k = 0) on the table row that serves it, operation by operation."""
+    a, b = row
+    t = fma(1.0, a, 2.0)
+    q = fma(t, 1.0 / 32.0, 1.0 / 12.0)
+    q = fma(t, q, 0.25)
+    h = fma(t, q, 1.0)
+    return fma(t, h, b)
+
+
+def log_table_1k():
+    """The 1024-entry table of the pair-sum kernels (fast64.hpp neg2log_1k): built as log_table() builds the
+    512-entry one, |t| < 2^-10, so that -2 ln(1 - t/2) can stop at t^4/32 (t^5/80 < 1.1e-17 absolute)."""
+    rows = []
+    for i in range(N1K):
+        lo = as_double(OFF + (i << (52 - LOGB1K)))
+        hi = as_double(OFF + ((i + 1) << (52 - LOGB1K)))
+        if hi == 1.0:
+            invc = 1.0  # chunk [1 - 2^-11, 1): c = 1 exactly
+        else:
+            c = (mp.mpf(lo) + mp.mpf(hi)) / 2
+            invc = dbl(1 / c)
+        logc = mp.log(1 / mp.mpf(invc)) if invc != 1.0 else mp.mpf(0)
+        rows.append((-2.0 * invc, dbl(-2 * logc)))
+    i_one = (0x3FF0000000000000 - OFF) >> (52 - LOGB1K)
+    cancel = neg2log_1k_of_one(rows[i_one])
+    assert abs(cancel) < BIAS_1K <= 5e-17, cancel
+    a, b = rows[i_one]
+    rows[i_one] = (a, b + BIAS_1K)
+    at_one = neg2log_1k_of_one(rows[i_one])
+    assert 0.0 < at_one <= BIAS_1K and (2 * at_one) ** 0.5 <= 3e-9, at_one
+    return rows
+
+
 def main():
     out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "monte-carlo-project-cuda_amd",
                        "csrc", "tables64.inc")
@@ -82,6 +133,11 @@ def main():
         f.write("};\nMCAMD_TAB_DECL double kExpLoTab[256] = {  // 2^(i/65536)\n")
         for a in EXL:
             f.write(f"    {hexf(a)},\n")
+        f.write("};\n")
+        f.write(f"#define MCAMD_LOG1K_N {N1K}\n")
+        f.write("MCAMD_TAB_DECL double kLogTab1k[MCAMD_LOG1K_N][2] = {  // {-2/c_i, -2 ln c_i}, 1024 chunks\n")
+        for a, b in log_table_1k():
+            f.write(f"    {{{hexf(a)}, {hexf(b)}}},\n")
         f.write("};\n")
         f.write("// clang-format on\n")
     c1 = mp.log(2) / 65536
