@@ -5,12 +5,12 @@
 // h the exercise value, u = S / K - 1, phi = (1, u, .., u^(m-1)), d_j = exp(-r t_j).  Regression arithmetic is fp64 on
 // (double) S whatever the path precision.
 //
-// Sweep, launch j (j = M-1 .. 0), one grid-stride pass over the n_train training paths:
+// Sweep, launch j (j = M-1 .. 0), one pass over the n_train training paths (path_frame.hpp's ThreadPaths):
 //   1. every workgroup reads the record launch j+1 finished and solves date j+1's 2..4-unknown normal equations —
 //      uniform and redundant, so every workgroup holds identical bits; workgroup 0 writes the table row of date j+1;
 //   2. each path applies date j+1's decision to V (launch M-1 sets V = d_M h(S_M) instead);
 //   3. each path adds to date j's record: the power sums P_0..P_6 of u, sum V u^q (q < 4) and |I_j| over the paths in
-//      the money at date j (launch 0: sum V and sum V^2, the in-sample estimate).  block_sumN + grid_finish sum the
+//      the money at date j (launch 0: sum V and sum V^2, the in-sample estimate).  finish_paths sums the
 //      record in a fixed order and the last workgroup writes it to the workspace: no host round trip between dates.
 // Pricing: one path per thread, the product-form loop of the store kernel (same Philox blocks, same PathState), the
 // price evaluated at exercise dates only; a wavefront leaves the step loop once every lane's path has stopped.
@@ -20,6 +20,7 @@
 #include "american.hpp"
 #include "american_device.hpp"
 #include "path_consts.hpp"
+#include "path_frame.hpp"
 
 #include <algorithm>
 
@@ -64,8 +65,7 @@ __global__ __launch_bounds__(kBlock) void am_sweep_kernel(AmSweepArgs<T> a, doub
     for (int q = 0; q < kAmRecord; ++q) acc[q] = 0.0;
     const T *__restrict__ next = a.traj + a.row_next * a.n;
     const T *__restrict__ cur = a.traj + a.row_j * a.n;
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
-    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < a.n; i += stride) {
+    for (const uint64_t i : ThreadPaths{a.n}) {
         const double Sn = static_cast<double>(next[i]);
         double v;
         if (first) {
@@ -90,21 +90,17 @@ __global__ __launch_bounds__(kBlock) void am_sweep_kernel(AmSweepArgs<T> a, doub
             }
             a.V[i] = v;
         } else {
-            acc[0] += v;
-            acc[1] = __builtin_fma(v, v, acc[1]);
+            add_sample(acc, v);
         }
     }
-    block_sumN<kBlock, kAmRecord>(acc);
-    grid_finish<kBlock, kAmRecord>(acc, partials, a.fin);
+    finish_paths(acc, partials, a.fin);
 }
 
 template <typename T>
 struct AmPriceArgs {
     StepConsts<T> c;
     const double *table;
-    uint64_t seed;
-    uint64_t path_offset;
-    uint64_t n_local;
+    PathShard shard;
     double K;
     uint32_t k, M;
     int put;
@@ -116,16 +112,15 @@ __global__ __launch_bounds__(kBlock) void am_price_kernel(AmPriceArgs<T> a, doub
 {
     constexpr int NB = Normals<T>::kPerBlock;
     const MathCtx<T> m = MathCtx<T>::init();
-    const PhiloxKeys key = PhiloxKeys::make(a.seed);
+    const PhiloxKeys key = PhiloxKeys::make(a.shard.seed);
     const StepConsts<T> c = resident(a.c);
     const bool put = a.put != 0;
     const StepBlocks blocks = step_blocks<NB>(c.n_sim);
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
     double acc[kAmPriceRecord];
 #pragma unroll
     for (int q = 0; q < kAmPriceRecord; ++q) acc[q] = 0.0;
-    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < a.n_local; i += stride) {
-        const uint64_t subsequence = a.path_offset + i;
+    for (const uint64_t i : ThreadPaths{a.shard.n_local}) {
+        const uint64_t subsequence = a.shard.path_offset + i;
         PathState<T> ps = PathState<T>::start(c.S_start);
         bool live = true;
         double y = 0.0;
@@ -156,16 +151,14 @@ __global__ __launch_bounds__(kBlock) void am_price_kernel(AmPriceArgs<T> a, doub
         walk_steps<NB>(
             blocks, [&](uint32_t b) { ex.fill(m, c, key, subsequence, b); }, [&](uint32_t, int j) { step(ex.x[j]); },
             [&] { return __builtin_amdgcn_ballot_w64(live) == 0; });   // every lane's path has stopped
-        acc[0] += y;
-        acc[1] = __builtin_fma(y, y, acc[1]);
+        add_sample(acc, y);
         if (ex_date != 0) {
             acc[2] += 1.0;
             acc[3] += a.table[static_cast<uint64_t>(ex_date) * kAmRow + 6];
         }
         acc[4] += 1.0;
     }
-    block_sumN<kBlock, kAmPriceRecord>(acc);
-    grid_finish<kBlock, kAmPriceRecord>(acc, partials, a.fin);
+    finish_paths(acc, partials, a.fin);
 }
 
 static uint64_t align256(uint64_t x) { return (x + 255) & ~static_cast<uint64_t>(255); }
@@ -221,9 +214,7 @@ static hipError_t price_t(const AmJob &job, const double *table, double *d_parti
     AmPriceArgs<T> a;
     a.c = make_consts<T>(job.path);
     a.table = table;
-    a.seed = job.path.seed;
-    a.path_offset = job.path.path_offset;
-    a.n_local = job.path.n_local;
+    a.shard = shard_of(job.path);
     a.K = job.path.K;
     a.k = job.k;
     a.M = job.M;

@@ -16,6 +16,7 @@
 #include "american_dual.hpp"
 #include "american_device.hpp"
 #include "path_consts.hpp"
+#include "path_frame.hpp"
 
 #include <algorithm>
 
@@ -27,9 +28,7 @@ struct AmContArgs {
     const T *traj;           // step-major rows of the shard's n_local outer paths
     const double *table;
     double *Q;
-    uint64_t seed;           // inner seed
-    uint64_t path_offset;
-    uint64_t n_local;
+    PathShard shard;         // the outer paths, with the inner seed
     uint64_t n_points;       // M n_local
     double K;
     uint32_t k, M, n_inner;
@@ -42,16 +41,16 @@ __global__ __launch_bounds__(kBlock) void am_cont_kernel(AmContArgs<T> a, double
 {
     constexpr int NB = Normals<T>::kPerBlock;
     const MathCtx<T> m = MathCtx<T>::init();
-    const PhiloxKeys key = PhiloxKeys::make(a.seed);
+    const PhiloxKeys key = PhiloxKeys::make(a.shard.seed);
     const StepConsts<T> c = resident(a.c);
     const bool put = a.put != 0;
     const bool first_lane = (threadIdx.x & (kWave - 1)) == 0;
     double rec[kAmContRecord] = {0.0, 0.0};   // thread 0: this workgroup's wave-steps and live lane-steps
     for (uint64_t task = blockIdx.x; task < a.n_points; task += gridDim.x) {
-        const uint32_t j0 = static_cast<uint32_t>(task / a.n_local);   // date-major: a workgroup's tasks span the dates
-        const uint64_t p = task - static_cast<uint64_t>(j0) * a.n_local;
-        const T S_in = j0 == 0 ? c.S_start : a.traj[(static_cast<uint64_t>(j0) * a.k - 1) * a.n_local + p];
-        const uint64_t sub0 = ((a.path_offset + p) * a.M + j0) * a.n_inner;
+        const uint32_t j0 = static_cast<uint32_t>(task / a.shard.n_local);   // date-major: a workgroup's tasks span the dates
+        const uint64_t p = task - static_cast<uint64_t>(j0) * a.shard.n_local;
+        const T S_in = j0 == 0 ? c.S_start : a.traj[(static_cast<uint64_t>(j0) * a.k - 1) * a.shard.n_local + p];
+        const uint64_t sub0 = ((a.shard.path_offset + p) * a.M + j0) * a.n_inner;
         const uint32_t n_sim = (a.M - j0) * a.k;
         const uint32_t n_full = n_sim / NB;
         const uint32_t rem = n_sim - n_full * NB;
@@ -140,8 +139,7 @@ __global__ __launch_bounds__(kBlock) void am_dual_scan_kernel(AmScanArgs<T> a, d
     double acc[kAmDualRecord];
 #pragma unroll
     for (int q = 0; q < kAmDualRecord; ++q) acc[q] = 0.0;
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
-    for (uint64_t p = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; p < a.n_local; p += stride) {
+    for (const uint64_t p : ThreadPaths{a.n_local}) {
         const double q0 = a.Q[p];
         double q_prev = q0, pi = 0.0, u = -__builtin_inf();
         for (uint32_t j = 1; j <= a.M; ++j) {
@@ -171,13 +169,11 @@ __global__ __launch_bounds__(kBlock) void am_dual_scan_kernel(AmScanArgs<T> a, d
             u = cand > u ? cand : u;
             q_prev = q_j;
         }
-        acc[0] += u;
-        acc[1] = __builtin_fma(u, u, acc[1]);
+        add_sample(acc, u);
         acc[2] += q0;
         acc[3] += 1.0;
     }
-    block_sumN<kBlock, kAmDualRecord>(acc);
-    grid_finish<kBlock, kAmDualRecord>(acc, partials, a.fin);
+    finish_paths(acc, partials, a.fin);
 }
 
 static uint64_t align256(uint64_t x) { return (x + 255) & ~static_cast<uint64_t>(255); }
@@ -212,9 +208,7 @@ static hipError_t cont_t(const AmDualJob &job, const void *traj, const double *t
     a.traj = static_cast<const T *>(traj);
     a.table = table;
     a.Q = Q;
-    a.seed = job.inner_seed;
-    a.path_offset = job.path.path_offset;
-    a.n_local = job.path.n_local;
+    a.shard = PathShard{job.inner_seed, job.path.path_offset, job.path.n_local};
     a.n_points = static_cast<uint64_t>(job.M) * job.path.n_local;
     a.K = job.path.K;
     a.k = job.k;

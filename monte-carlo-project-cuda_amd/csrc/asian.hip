@@ -13,6 +13,7 @@
 // include_spot are wave-uniform selects outside the step loop.
 #include "asian.hpp"
 #include "path_consts.hpp"
+#include "path_frame.hpp"
 
 namespace mcamd {
 
@@ -24,9 +25,7 @@ struct AsianArgs {
     double K;            // fixed strike
     double control_mean; // E[g] (ARITH and GEO)
     int floating, put, include_spot;
-    uint64_t seed;
-    uint64_t path_offset;
-    uint64_t n_local;
+    PathShard shard;
     T *samples;          // nullable
     GridFinish fin;
 };
@@ -37,9 +36,8 @@ __global__ __launch_bounds__(kBlock) void asian_kernel(AsianArgs<T> a, double *_
     static_assert(ARITH || GEO, "an Asian kernel averages something");
     constexpr int NB = Exponents<T>::kPerBlock;
     const MathCtx<T> m = MathCtx<T>::init();
-    const PhiloxKeys key = PhiloxKeys::make(a.seed);
+    const PhiloxKeys key = PhiloxKeys::make(a.shard.seed);
     const StepConsts<T> c = resident(a.c);
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
     const StepBlocks blocks = step_blocks<NB>(c.n_sim);
     // one sample from an average and a terminal price, both already fp64
     auto sample = [&](double avg, double St) {
@@ -47,8 +45,8 @@ __global__ __launch_bounds__(kBlock) void asian_kernel(AsianArgs<T> a, double *_
         return d > 0.0 ? d : 0.0;
     };
     double acc6[kAsianRecord] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < a.n_local; i += stride) {
-        const uint64_t subsequence = a.path_offset + i;
+    for (const uint64_t i : ThreadPaths{a.shard.n_local}) {
+        const uint64_t subsequence = a.shard.path_offset + i;
         PathState<T> ps = PathState<T>::start(c.S_start);                               // ARITH: P_i
         double sum_p = a.include_spot ? static_cast<double>(c.S_start) : 0.0;           // ARITH: P_0 + .. + P_i
         T X = T(0);                                                                     // GEO: X_i, exponent units
@@ -76,19 +74,16 @@ __global__ __launch_bounds__(kBlock) void asian_kernel(AsianArgs<T> a, double *_
         if (ARITH) y = sample(sum_p / a.m, static_cast<double>(ps.value(m)));
         else y = g;
         if (a.samples) a.samples[i] = static_cast<T>(y);
-        acc6[0] += y;
-        acc6[1] = __builtin_fma(y, y, acc6[1]);
+        add_sample(acc6, y);
         if (ARITH && GEO) {
             const double ctl = g - a.control_mean;
             acc6[2] += ctl;
             acc6[3] = __builtin_fma(ctl, ctl, acc6[3]);
             acc6[4] = __builtin_fma(y, ctl, acc6[4]);
         }
-        // a wavefront's active lanes are a prefix (path ids grow with the lane): lane 0 counts the wavefront's steps
-        if ((threadIdx.x & (kWave - 1)) == 0) acc6[5] += static_cast<double>(c.n_sim);
+        add_wave_steps(acc6[5], c.n_sim);
     }
-    block_sumN<kBlock, kAsianRecord>(acc6);
-    grid_finish<kBlock, kAsianRecord>(acc6, partials, a.fin);   // the statistics layout puts n where the counter is
+    finish_paths(acc6, partials, a.fin);   // the statistics layout puts n where the counter is
 }
 
 template <typename T>
@@ -97,8 +92,8 @@ static hipError_t launch_asian_t(const AsianJob &j, double *d_partials, uint32_t
 {
     const double dates = static_cast<double>(j.path.n_sim) + (j.include_spot ? 1.0 : 0.0);
     const AsianArgs<T> a{make_consts<T>(j.path), static_cast<T>(1.0 / dates), dates, j.K, j.control_mean,
-                         j.floating ? 1 : 0, j.put ? 1 : 0, j.include_spot ? 1 : 0, j.path.seed, j.path.path_offset,
-                         j.path.n_local, static_cast<T *>(j.d_samples), GridFinish{fs.out, fs.ticket, fs.n_value}};
+                         j.floating ? 1 : 0, j.put ? 1 : 0, j.include_spot ? 1 : 0, shard_of(j.path),
+                         static_cast<T *>(j.d_samples), grid_finish_of(fs)};
     const dim3 g(grid), b(kBlock);
     if (!j.arithmetic) hipLaunchKernelGGL((asian_kernel<T, false, true>), g, b, 0, stream, a, d_partials);
     else if (j.control) hipLaunchKernelGGL((asian_kernel<T, true, true>), g, b, 0, stream, a, d_partials);
@@ -110,8 +105,9 @@ hipError_t launch_asian(const AsianJob &job, double *d_partials, uint32_t grid, 
                         hipStream_t stream)
 {
     if (!finish_ok(finish, grid)) return hipErrorInvalidValue;
-    return job.path.precision == 32 ? launch_asian_t<float>(job, d_partials, grid, finish, stream)
-                                    : launch_asian_t<double>(job, d_partials, grid, finish, stream);
+    return dispatch_precision(job.path.precision, [&](auto p) {
+        return launch_asian_t<typename decltype(p)::type>(job, d_partials, grid, finish, stream);
+    });
 }
 
 }  // namespace mcamd

@@ -18,6 +18,7 @@
 // at all by a wavefront whose lanes have all been called: it leaves the loop at the first group end where that is so.
 #include "autocall.hpp"
 #include "path_consts.hpp"
+#include "path_frame.hpp"
 #include "basket_device.hpp"
 
 namespace mcamd {
@@ -32,9 +33,7 @@ struct AutocallArgs {
     double dt;
     int ki;                          // a knock-in applies (always, with KI_EVERY_STEP)
     uint32_t n_steps, observe_every, first_call_date;
-    uint64_t seed;
-    uint64_t path_offset;
-    uint64_t n_local;
+    PathShard shard;
     T *samples;                      // nullable
     GridFinish fin;
 };
@@ -47,18 +46,17 @@ __global__ __launch_bounds__(kBlock) void autocall_kernel(AutocallArgs<T, D> a, 
     constexpr int BPG = G * D / NB;        // the blocks they consume
     constexpr int NC = D * (D + 1) / 2;
     const MathCtx<T> m = MathCtx<T>::init();
-    const PhiloxKeys key = PhiloxKeys::make(a.seed);
+    const PhiloxKeys key = PhiloxKeys::make(a.shard.seed);
     T drift[D], coef[NC];
 #pragma unroll
     for (int j = 0; j < D; ++j) drift[j] = bk_resident<D>(a.drift[j]);
 #pragma unroll
     for (int c = 0; c < NC; ++c) coef[c] = bk_resident<D>(a.coef[c]);
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
     const uint32_t n_groups = a.n_steps / G;
     const uint32_t rem = a.n_steps - n_groups * G;
     double acc[kAutocallRecord] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < a.n_local; i += stride) {
-        const uint64_t subsequence = a.path_offset + i;
+    for (const uint64_t i : ThreadPaths{a.shard.n_local}) {
+        const uint64_t subsequence = a.shard.path_offset + i;
         T X[D];                  // ln(S_j / S_{j,0}) so far, in exponent units
 #pragma unroll
         for (int j = 0; j < D; ++j) X[j] = T(0);
@@ -136,13 +134,11 @@ __global__ __launch_bounds__(kBlock) void autocall_kernel(AutocallArgs<T, D> a, 
         y = called ? y_call : y;
         if (a.samples) a.samples[i] = static_cast<T>(y);
         const uint32_t s_call = q_call * a.observe_every;   // the step the path was called at
-        acc[0] += y;
-        acc[1] = __builtin_fma(y, y, acc[1]);
+        add_sample(acc, y);
         acc[2] += called ? 1.0 : 0.0;
         acc[3] += called ? static_cast<double>(s_call) * a.dt : 0.0;
         acc[4] += (!called && knocked) ? 1.0 : 0.0;
-        // a wavefront's active lanes are a prefix (path ids grow with the lane): lane 0 counts the wavefront's steps
-        if ((threadIdx.x & (kWave - 1)) == 0) acc[5] += static_cast<double>(steps_run);
+        add_wave_steps(acc[5], steps_run);
         // the steps this path entered not yet called: all of them, or those up to its call
         acc[6] += static_cast<double>(called ? s_call : a.n_steps);
     }
@@ -175,11 +171,9 @@ static hipError_t launch_autocall_d(const AutocallJob &j, double *d_partials, ui
     a.n_steps = j.path.n_sim;
     a.observe_every = sc.observe_every;
     a.first_call_date = sc.first_call_date;
-    a.seed = j.path.seed;
-    a.path_offset = j.path.path_offset;
-    a.n_local = j.path.n_local;
+    a.shard = shard_of(j.path);
     a.samples = static_cast<T *>(j.d_samples);
-    a.fin = GridFinish{fs.out, fs.ticket, fs.n_value};
+    a.fin = grid_finish_of(fs);
     const dim3 g(grid), b(kBlock);
     if (sc.ki && sc.ki_every_step) hipLaunchKernelGGL((autocall_kernel<T, D, true>), g, b, 0, stream, a, d_partials);
     else hipLaunchKernelGGL((autocall_kernel<T, D, false>), g, b, 0, stream, a, d_partials);
@@ -200,8 +194,9 @@ hipError_t launch_autocall(const AutocallJob &job, double *d_partials, uint32_t 
 {
     if (!finish_ok(finish, grid)) return hipErrorInvalidValue;
     if (!autocall_schedule_ok(job.schedule, job.path.n_sim)) return hipErrorInvalidValue;
-    return job.path.precision == 32 ? launch_autocall_t<float>(job, d_partials, grid, finish, stream)
-                                    : launch_autocall_t<double>(job, d_partials, grid, finish, stream);
+    return dispatch_precision(job.path.precision, [&](auto p) {
+        return launch_autocall_t<typename decltype(p)::type>(job, d_partials, grid, finish, stream);
+    });
 }
 
 }  // namespace mcamd

@@ -26,6 +26,7 @@
 #include "autocall_localvol.hpp"
 #include "localvol_device.hpp"
 #include "basket_device.hpp"
+#include "path_frame.hpp"
 
 namespace mcamd {
 
@@ -54,9 +55,7 @@ struct AutocallLocalVolArgs {
     double dt;
     int ki;                          // a knock-in applies (always, with KI_EVERY_STEP)
     uint32_t n_steps, observe_every, first_call_date;
-    uint64_t seed;
-    uint64_t path_offset;
-    uint64_t n_local;
+    PathShard shard;
     T *samples;                      // nullable
     GridFinish fin;
 };
@@ -79,7 +78,7 @@ __global__ __launch_bounds__(kBlock) void autocall_localvol_kernel(AutocallLocal
     for (int j = 0; j < D; ++j) lv_copy_table(tab, a.base[j], a.table[j], a.n_entries[j]);
     __syncthreads();
     const MathCtx<T> m = MathCtx<T>::init();
-    const PhiloxKeys key = PhiloxKeys::make(a.seed);
+    const PhiloxKeys key = PhiloxKeys::make(a.shard.seed);
     LvAxis<T> axis[D];
     T mu_dt[D], chol[NC];
 #pragma unroll
@@ -90,12 +89,11 @@ __global__ __launch_bounds__(kBlock) void autocall_localvol_kernel(AutocallLocal
 #pragma unroll
     for (int c = 0; c < NC; ++c) chol[c] = bk_resident<D>(a.chol[c]);
     const T half_dt = lv_resident(a.half_dt), sqrt_dt = lv_resident(a.sqrt_dt);
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
     const uint32_t n_groups = a.n_steps / G;
     const uint32_t rem = a.n_steps - n_groups * G;
     double acc[kAutocallRecord] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < a.n_local; i += stride) {
-        const uint64_t subsequence = a.path_offset + i;
+    for (const uint64_t i : ThreadPaths{a.shard.n_local}) {
+        const uint64_t subsequence = a.shard.path_offset + i;
         T X[D];                  // ln(S_j / S_{j,0}) so far, natural units
         LvRow row[D];            // asset j's starts at its table's own base
 #pragma unroll
@@ -181,13 +179,11 @@ __global__ __launch_bounds__(kBlock) void autocall_localvol_kernel(AutocallLocal
         y = called ? y_call : y;
         if (a.samples) a.samples[i] = static_cast<T>(y);
         const uint32_t s_call = q_call * a.observe_every;   // the step the path was called at
-        acc[0] += y;
-        acc[1] = __builtin_fma(y, y, acc[1]);
+        add_sample(acc, y);
         acc[2] += called ? 1.0 : 0.0;
         acc[3] += called ? static_cast<double>(s_call) * a.dt : 0.0;
         acc[4] += (!called && knocked) ? 1.0 : 0.0;
-        // a wavefront's active lanes are a prefix (path ids grow with the lane): lane 0 counts the wavefront's steps
-        if ((threadIdx.x & (kWave - 1)) == 0) acc[5] += static_cast<double>(steps_run);
+        add_wave_steps(acc[5], steps_run);
         // the steps this path entered not yet called: all of them, or those up to its call
         acc[6] += static_cast<double>(called ? s_call : a.n_steps);
     }
@@ -238,11 +234,9 @@ static hipError_t launch_autocall_localvol_d(const AutocallLocalVolJob &j, doubl
     a.n_steps = j.paths.n_steps;
     a.observe_every = sc.observe_every;
     a.first_call_date = sc.first_call_date;
-    a.seed = j.paths.seed;
-    a.path_offset = j.paths.path_offset;
-    a.n_local = j.paths.n_local;
+    a.shard = shard_of(j.paths);
     a.samples = static_cast<T *>(j.d_samples);
-    a.fin = GridFinish{fs.out, fs.ticket, fs.n_value};
+    a.fin = grid_finish_of(fs);
     const dim3 g(grid), b(kBlock);
     const size_t lds_bytes = static_cast<size_t>(total) * sizeof(VolPair<T>);
     if (sc.ki && sc.ki_every_step)

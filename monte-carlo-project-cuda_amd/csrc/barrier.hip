@@ -15,6 +15,7 @@
 // step loop at the first block end where every lane is knocked; a knock-in runs to maturity, because it needs S_T.
 #include "barrier.hpp"
 #include "path_consts.hpp"
+#include "path_frame.hpp"
 
 namespace mcamd {
 
@@ -25,9 +26,7 @@ struct BarrierArgs {
                        // fp32: 2 ln 2 / (v^2 dt): q = kq d d' in log2 units (v_exp_f32's)
     T q_cut;           // Q in the units of q
     int put;
-    uint64_t seed;
-    uint64_t path_offset;
-    uint64_t n_local;
+    PathShard shard;
     T *samples;        // nullable
     GridFinish fin;
 };
@@ -37,14 +36,13 @@ __global__ __launch_bounds__(kBlock) void barrier_kernel(BarrierArgs<T> a, doubl
 {
     constexpr int NB = Exponents<T>::kPerBlock;
     const MathCtx<T> m = MathCtx<T>::init();
-    const PhiloxKeys key = PhiloxKeys::make(a.seed);
+    const PhiloxKeys key = PhiloxKeys::make(a.shard.seed);
     const StepConsts<T> c = resident(a.c);
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
     const StepBlocks blocks = step_blocks<NB>(c.n_sim);
     const T d0 = UP ? c.logB : -c.logB;   // |b|: the spot is strictly on the live side (checked on the host)
     double acc4[kBarrierRecord] = {0.0, 0.0, 0.0, 0.0};
-    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < a.n_local; i += stride) {
-        const uint64_t subsequence = a.path_offset + i;
+    for (const uint64_t i : ThreadPaths{a.shard.n_local}) {
+        const uint64_t subsequence = a.shard.path_offset + i;
         T acc = T(0);        // X so far, in exponent units
         T d_prev = d0;
         T w = T(1);          // the bridge factors so far (CONT); the hits are in `alive`
@@ -77,15 +75,11 @@ __global__ __launch_bounds__(kBlock) void barrier_kernel(BarrierArgs<T> a, doubl
         // a knocked path of a knock-out pays 0 whatever its (possibly unfinished) price is
         const double y = OUT ? (alive ? wd * static_cast<double>(h) : 0.0) : (1.0 - wd) * static_cast<double>(h);
         if (a.samples) a.samples[i] = static_cast<T>(y);
-        acc4[0] += y;
-        acc4[1] = __builtin_fma(y, y, acc4[1]);
-        // a wavefront's active lanes are a prefix (path ids grow with the lane): lane 0 counts the wavefront's steps
-        if ((threadIdx.x & (kWave - 1)) == 0) acc4[2] += static_cast<double>(steps_run);
-        acc4[3] += static_cast<double>(live);
+        add_sample(acc4, y);
+        add_counters(acc4, steps_run, live);
     }
     if (a.fin.n_value >= 0.0) acc4[2] = acc4[3] = 0.0;   // the 6-double statistics layout has no slot for the counters
-    block_sumN<kBlock, kBarrierRecord>(acc4);
-    grid_finish<kBlock, kBarrierRecord>(acc4, partials, a.fin);
+    finish_paths(acc4, partials, a.fin);
 }
 
 template <typename T, bool UP, bool CONT>
@@ -105,8 +99,7 @@ static hipError_t launch_barrier_t(const BarrierJob &j, double *d_partials, uint
     const double q_unit = sizeof(T) == 4 ? kLn2 : 1.0;
     const double q_cut = sizeof(T) == 4 ? 18.0 : 38.0;
     const BarrierArgs<T> a{make_consts<T>(j.path), static_cast<T>(j.kq * u * u / q_unit), static_cast<T>(q_cut / q_unit),
-                           j.put ? 1 : 0, j.path.seed, j.path.path_offset, j.path.n_local,
-                           static_cast<T *>(j.d_samples), GridFinish{fs.out, fs.ticket, fs.n_value}};
+                           j.put ? 1 : 0, shard_of(j.path), static_cast<T *>(j.d_samples), grid_finish_of(fs)};
     if (j.up) {
         if (j.continuous) launch_barrier_k<T, true, true>(j, a, d_partials, grid, stream);
         else launch_barrier_k<T, true, false>(j, a, d_partials, grid, stream);
@@ -121,8 +114,9 @@ hipError_t launch_barrier(const BarrierJob &job, double *d_partials, uint32_t gr
                           hipStream_t stream)
 {
     if (!finish_ok(finish, grid)) return hipErrorInvalidValue;
-    return job.path.precision == 32 ? launch_barrier_t<float>(job, d_partials, grid, finish, stream)
-                                    : launch_barrier_t<double>(job, d_partials, grid, finish, stream);
+    return dispatch_precision(job.path.precision, [&](auto p) {
+        return launch_barrier_t<typename decltype(p)::type>(job, d_partials, grid, finish, stream);
+    });
 }
 
 }  // namespace mcamd

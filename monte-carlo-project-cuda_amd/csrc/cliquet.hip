@@ -17,6 +17,7 @@
 // block ends.  There is no early exit: every wavefront runs every step.
 #include "cliquet.hpp"
 #include "localvol_device.hpp"
+#include "path_frame.hpp"
 
 namespace mcamd {
 
@@ -29,9 +30,7 @@ struct CliquetArgs {
     double g_lo, g_hi;        // the global bounds of A; -inf / +inf: none
     double scale;             // VARIANCE: 1 / (P tau)
     uint32_t n_steps, reset_every, first_period;
-    uint64_t seed;
-    uint64_t path_offset;
-    uint64_t n_local;
+    PathShard shard;
     T *samples;               // nullable
     GridFinish fin;
 };
@@ -44,17 +43,16 @@ __global__ __launch_bounds__(kBlock) void cliquet_kernel(CliquetArgs<T> a, doubl
     lv_copy_table(tab, 0, a.surf.table, a.surf.rows.n_entries);
     __syncthreads();
     const MathCtx<T> m = MathCtx<T>::init();
-    const PhiloxKeys key = PhiloxKeys::make(a.seed);
+    const PhiloxKeys key = PhiloxKeys::make(a.shard.seed);
     const LvAxis<T> axis = lv_resident(a.surf.axis);
     const T mu_dt = lv_resident(a.mu_dt), half_dt = lv_resident(a.half_dt), sqrt_dt = lv_resident(a.sqrt_dt);
     const T lo = lv_resident(a.lo), hi = lv_resident(a.hi), exp_scale = lv_resident(a.exp_scale);
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
     const StepBlocks blocks = step_blocks<NB>(a.n_steps);
     // an infinite bound never binds and counts nothing, whatever the arithmetic made of A
     const bool has_floor = a.g_lo > -__builtin_huge_val(), has_cap = a.g_hi < __builtin_huge_val();
     double acc5[kCliquetRecord] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < a.n_local; i += stride) {
-        const uint64_t subsequence = a.path_offset + i;
+    for (const uint64_t i : ThreadPaths{a.shard.n_local}) {
+        const uint64_t subsequence = a.shard.path_offset + i;
         T X = T(0);          // ln(S / S0), natural units
         T X_reset = T(0);    // X at the last reset date
         T sum = T(0);        // sum c_p (SUM), sum l_p (COMPOUND), sum D_p^2 (VARIANCE)
@@ -92,16 +90,13 @@ __global__ __launch_bounds__(kBlock) void cliquet_kernel(CliquetArgs<T> a, doubl
         else A = static_cast<double>(sum) * a.scale;
         const double y = __builtin_fmin(__builtin_fmax(A, a.g_lo), a.g_hi);
         if (a.samples) a.samples[i] = static_cast<T>(y);
-        acc5[0] += y;
-        acc5[1] = __builtin_fma(y, y, acc5[1]);
+        add_sample(acc5, y);
         acc5[2] += (has_floor && A <= a.g_lo) ? 1.0 : 0.0;
         acc5[3] += (has_cap && A >= a.g_hi) ? 1.0 : 0.0;
-        // a wavefront's active lanes are a prefix (path ids grow with the lane): lane 0 counts the wavefront's steps
-        if ((threadIdx.x & (kWave - 1)) == 0) acc5[4] += static_cast<double>(a.n_steps);
+        add_wave_steps(acc5[4], a.n_steps);
     }
     if (a.fin.n_value >= 0.0) acc5[4] = 0.0;   // the 6-double statistics layout has no slot for the step counter
-    block_sumN<kBlock, kCliquetRecord>(acc5);
-    grid_finish<kBlock, kCliquetRecord>(acc5, partials, a.fin);
+    finish_paths(acc5, partials, a.fin);
 }
 
 template <typename T, int KIND>
@@ -116,7 +111,8 @@ static hipError_t launch_cliquet_t(const CliquetJob &j, double *d_partials, uint
                                    hipStream_t stream)
 {
     CliquetArgs<T> a;
-    lv_walk_args<T>(a, j.walk);
+    lv_step_args<T>(a, j.walk);
+    a.shard = shard_of(j.walk.paths);
     a.lo = static_cast<T>(j.local_lo);
     a.hi = static_cast<T>(j.local_hi);
     a.g_lo = j.global_lo;
@@ -126,7 +122,7 @@ static hipError_t launch_cliquet_t(const CliquetJob &j, double *d_partials, uint
     a.reset_every = j.reset_every;
     a.first_period = j.first_period;
     a.samples = static_cast<T *>(j.d_samples);
-    a.fin = GridFinish{fs.out, fs.ticket, fs.n_value};
+    a.fin = grid_finish_of(fs);
     if (j.kind == kCliquetSum) launch_cliquet_k<T, kCliquetSum>(a, d_partials, grid, stream);
     else if (j.kind == kCliquetCompound) launch_cliquet_k<T, kCliquetCompound>(a, d_partials, grid, stream);
     else launch_cliquet_k<T, kCliquetVariance>(a, d_partials, grid, stream);
@@ -142,8 +138,9 @@ hipError_t launch_cliquet(const CliquetJob &job, double *d_partials, uint32_t gr
     if (job.kind < kCliquetSum || job.kind > kCliquetVariance || job.reset_every == 0 ||
         n_steps % job.reset_every != 0 || job.first_period == 0 || job.first_period > n_steps / job.reset_every)
         return hipErrorInvalidValue;
-    return job.walk.paths.precision == 32 ? launch_cliquet_t<float>(job, d_partials, grid, finish, stream)
-                               : launch_cliquet_t<double>(job, d_partials, grid, finish, stream);
+    return dispatch_precision(job.walk.paths.precision, [&](auto p) {
+        return launch_cliquet_t<typename decltype(p)::type>(job, d_partials, grid, finish, stream);
+    });
 }
 
 }  // namespace mcamd

@@ -18,6 +18,7 @@
 // x - drift = vol z (one subtract and one fma per step); z_1 and sum z_i come from the first step and the log price.
 #include "greeks.hpp"
 #include "path_consts.hpp"
+#include "path_frame.hpp"
 
 namespace mcamd {
 
@@ -25,9 +26,7 @@ template <typename T>
 struct GreeksArgs {
     StepConsts<T> c;
     GreeksConsts g;
-    uint64_t seed;
-    uint64_t path_offset;
-    uint64_t n_local;
+    PathShard shard;
     GridFinish fin;   // fin.out: the 16-double statistics record
 };
 
@@ -46,7 +45,7 @@ template <typename T>
 __device__ __forceinline__ void write_stats_tail(const GreeksArgs<T> &a)
 {
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        a.fin.out[kGreeksRecord] = static_cast<double>(a.n_local);
+        a.fin.out[kGreeksRecord] = static_cast<double>(a.shard.n_local);
         for (int k = kGreeksRecord + 1; k < kGreeksStats; ++k) a.fin.out[k] = 0.0;
     }
 }
@@ -87,19 +86,20 @@ __global__ __launch_bounds__(kBlock) void greeks_pathwise_kernel(GreeksArgs<T> a
 {
     constexpr int NP = kPairSumPaths;
     const MathCtx<T> m = MathCtx<T>::template init<true>();
-    const PhiloxKeys key = PhiloxKeys::make(a.seed);
+    const PhiloxKeys key = PhiloxKeys::make(a.shard.seed);
     const StepConsts<T> c = resident(a.c);
     const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
     write_stats_tail(a);
     double acc[kGreeksRecord];
 #pragma unroll
     for (int k = 0; k < kGreeksRecord; ++k) acc[k] = 0.0;
-    for (uint64_t g = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; g * NP < a.n_local; g += stride) {
+    // path groups, not paths: the bound g NP < n_local stays a multiplication (ThreadPaths would need the division)
+    for (uint64_t g = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; g * NP < a.shard.n_local; g += stride) {
         T sums[NP];
-        pair_sums_of_paths<T, NP>(m, key, a.path_offset + g * NP, c.n_sim, sums);
+        pair_sums_of_paths<T, NP>(m, key, a.shard.path_offset + g * NP, c.n_sim, sums);
 #pragma unroll
         for (int p = 0; p < NP; ++p)
-            if (g * NP + p < a.n_local) {
+            if (g * NP + p < a.shard.n_local) {
                 const Sample<T> s = sample_from_pair_sum<T, false>(c, m, sums[p], c.S_start, c.n_sim);
                 // the exponent sample_from_pair_sum exponentiated: ln(S_T / S_s) in exponent units
                 const T x = fma_t(sums[p], c.vol * PairSum<T>::kUnit, c.drift * static_cast<T>(c.n_sim));
@@ -108,8 +108,7 @@ __global__ __launch_bounds__(kBlock) void greeks_pathwise_kernel(GreeksArgs<T> a
                 add_greeks(acc, q);
             }
     }
-    block_sumN<kBlock, kGreeksRecord>(acc);
-    grid_finish<kBlock, kGreeksRecord>(acc, partials, a.fin);
+    finish_paths(acc, partials, a.fin);
 }
 
 // The log-space stepping loop of simulate_sample (LOGSPACE, no antithetic twin), one path per thread, with the same
@@ -120,9 +119,9 @@ __global__ __launch_bounds__(kBlock) void greeks_lr_kernel(GreeksArgs<T> a, doub
 {
     constexpr int NB = Normals<T>::kPerBlock;
     const MathCtx<T> m = MathCtx<T>::init();
-    const PhiloxKeys key = PhiloxKeys::make(a.seed);
+    const PhiloxKeys key = PhiloxKeys::make(a.shard.seed);
     const StepConsts<T> c = resident(a.c);
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
+    const ThreadPaths paths(a.shard.n_local);   // made at the loop, the fp64 kernels compile to other instructions
     const uint32_t n_full = c.n_sim / NB;
     const uint32_t rem = c.n_sim - n_full * NB;
     const double inv_vol = 1.0 / static_cast<double>(c.vol);   // exponent units per normal
@@ -131,8 +130,8 @@ __global__ __launch_bounds__(kBlock) void greeks_lr_kernel(GreeksArgs<T> a, doub
     double acc[kGreeksRecord];
 #pragma unroll
     for (int k = 0; k < kGreeksRecord; ++k) acc[k] = 0.0;
-    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < a.n_local; i += stride) {
-        const uint64_t subsequence = a.path_offset + i;
+    for (const uint64_t i : paths) {
+        const uint64_t subsequence = a.shard.path_offset + i;
         int32_t count = c.Ik;
         T lg = T(0);    // ln(S_t / S_s) in exponent units
         T sq = T(0);    // sum of (x - drift)^2 = vol^2 sum z^2
@@ -171,8 +170,7 @@ __global__ __launch_bounds__(kBlock) void greeks_lr_kernel(GreeksArgs<T> a, doub
         lr_samples(a.g, y, z1, sz, szz, static_cast<double>(c.n_sim), q);
         add_greeks(acc, q);
     }
-    block_sumN<kBlock, kGreeksRecord>(acc);
-    grid_finish<kBlock, kGreeksRecord>(acc, partials, a.fin);
+    finish_paths(acc, partials, a.fin);
 }
 
 uint32_t greeks_grid(const GreeksJob &job)
@@ -192,8 +190,7 @@ static hipError_t launch_greeks_t(const GreeksJob &j, double *d_partials, uint32
 {
     GreeksConsts gc = j.g;
     gc.inv_scale = exponent_unit<T>();
-    const GreeksArgs<T> a{make_consts<T>(j.path), gc, j.path.seed, j.path.path_offset, j.path.n_local,
-                          GridFinish{out, ticket, -1.0}};
+    const GreeksArgs<T> a{make_consts<T>(j.path), gc, shard_of(j.path), GridFinish{out, ticket, -1.0}};
     const dim3 g(grid), b(kBlock);
     if (!j.lr) hipLaunchKernelGGL((greeks_pathwise_kernel<T>), g, b, 0, stream, a, d_partials);
     else if (j.path.window) hipLaunchKernelGGL((greeks_lr_kernel<T, true>), g, b, 0, stream, a, d_partials);
@@ -205,8 +202,9 @@ hipError_t launch_greeks(const GreeksJob &job, double *d_partials, uint32_t grid
                          hipStream_t stream)
 {
     if (!out || !ticket || grid > kFoldMaxRecords) return hipErrorInvalidValue;
-    return job.path.precision == 32 ? launch_greeks_t<float>(job, d_partials, grid, out, ticket, stream)
-                                    : launch_greeks_t<double>(job, d_partials, grid, out, ticket, stream);
+    return dispatch_precision(job.path.precision, [&](auto p) {
+        return launch_greeks_t<typename decltype(p)::type>(job, d_partials, grid, out, ticket, stream);
+    });
 }
 
 }  // namespace mcamd

@@ -13,6 +13,7 @@
 // scaled in fp64).  There is no table in LDS beyond what MathCtx<T> needs and no early exit.
 #include "heston.hpp"
 #include "heston_device.hpp"
+#include "path_frame.hpp"
 
 namespace mcamd {
 
@@ -29,9 +30,7 @@ struct HestonArgs {
     double inv_n;             // 1 / n_steps
     int put;
     uint32_t n_steps;
-    uint64_t seed;
-    uint64_t path_offset;
-    uint64_t n_local;
+    PathShard shard;
     T *samples;               // nullable
     T *state;                 // nullable: S_T at [i], v_n at [n_local + i]
     GridFinish fin;
@@ -42,13 +41,12 @@ __global__ __launch_bounds__(kBlock) void heston_kernel(HestonArgs<T> a, double 
 {
     constexpr int NB = Normals<T>::kPerBlock;
     const MathCtx<T> m = MathCtx<T>::init();
-    const PhiloxKeys key = PhiloxKeys::make(a.seed);
+    const PhiloxKeys key = PhiloxKeys::make(a.shard.seed);
     const HestonConsts<T> c = heston_resident(a.c);
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
     const StepBlocks blocks = step_blocks<NB>(a.n_steps);
     double acc4[kHestonRecord] = {0.0, 0.0, 0.0, 0.0};
-    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < a.n_local; i += stride) {
-        const uint64_t subsequence = a.path_offset + i;
+    for (const uint64_t i : ThreadPaths{a.shard.n_local}) {
+        const uint64_t subsequence = a.shard.path_offset + i;
         T X = T(0);           // ln(S / S0), natural units
         T v = a.v0;           // the raw variance
         T v_sum = T(0);       // sum of v+ over the steps
@@ -71,15 +69,13 @@ __global__ __launch_bounds__(kBlock) void heston_kernel(HestonArgs<T> a, double 
         if (a.samples) a.samples[i] = h;
         if (a.state) {
             a.state[i] = St;
-            a.state[a.n_local + i] = v;
+            a.state[a.shard.n_local + i] = v;
         }
-        acc4[0] += y;
-        acc4[1] = __builtin_fma(y, y, acc4[1]);
+        add_sample(acc4, y);
         acc4[2] += static_cast<double>(trunc);
         acc4[3] += static_cast<double>(v_sum) * a.inv_n;
     }
-    block_sumN<kBlock, kHestonRecord>(acc4);
-    grid_finish<kBlock, kHestonRecord>(acc4, partials, a.fin);
+    finish_paths(acc4, partials, a.fin);
 }
 
 template <typename T>
@@ -103,12 +99,10 @@ static hipError_t launch_heston_t(const HestonJob &j, double *d_partials, uint32
     a.inv_n = 1.0 / static_cast<double>(j.paths.n_steps);
     a.put = j.put ? 1 : 0;
     a.n_steps = j.paths.n_steps;
-    a.seed = j.paths.seed;
-    a.path_offset = j.paths.path_offset;
-    a.n_local = j.paths.n_local;
+    a.shard = shard_of(j.paths);
     a.samples = static_cast<T *>(j.d_samples);
     a.state = static_cast<T *>(j.d_state);
-    a.fin = GridFinish{fs.out, fs.ticket, fs.n_value};
+    a.fin = grid_finish_of(fs);
     hipLaunchKernelGGL((heston_kernel<T>), dim3(grid), dim3(kBlock), 0, stream, a, d_partials);
     return hipGetLastError();
 }
@@ -118,8 +112,9 @@ hipError_t launch_heston(const HestonJob &job, double *d_partials, uint32_t grid
 {
     if (!finish_ok(finish, grid)) return hipErrorInvalidValue;
     if (job.scheme != kHestonFullTruncation || job.paths.n_steps == 0 || job.paths.n_local == 0) return hipErrorInvalidValue;
-    return job.paths.precision == 32 ? launch_heston_t<float>(job, d_partials, grid, finish, stream)
-                               : launch_heston_t<double>(job, d_partials, grid, finish, stream);
+    return dispatch_precision(job.paths.precision, [&](auto p) {
+        return launch_heston_t<typename decltype(p)::type>(job, d_partials, grid, finish, stream);
+    });
 }
 
 }  // namespace mcamd

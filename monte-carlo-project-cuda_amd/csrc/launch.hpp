@@ -31,6 +31,19 @@ struct PathRange {
     int precision;   // 32 / 64
 };
 
+// The shard as the Args of the one-path-per-thread kernels carry it: local path i is subsequence path_offset + i.
+struct PathShard {
+    uint64_t seed, path_offset, n_local;
+};
+inline PathShard shard_of(const PathJob &j) { return PathShard{j.seed, j.path_offset, j.n_local}; }
+inline PathShard shard_of(const PathRange &p) { return PathShard{p.seed, p.path_offset, p.n_local}; }
+
+// The launchers take the path precision as a template argument: f(Precision<T>{}) with T = float for 32, else double.
+template <typename T>
+struct Precision { using type = T; };
+template <typename F>
+hipError_t dispatch_precision(int precision, F f) { return precision == 32 ? f(Precision<float>{}) : f(Precision<double>{}); }
+
 constexpr uint32_t kMaxGrid = 1u << 20;  // blocks; beyond this the kernels grid-stride
 constexpr uint32_t kBlockThreads = 256;  // threads per workgroup of every kernel (mc_device.hpp kBlock; reported as block)
 

@@ -12,6 +12,7 @@
 // as Exponents<T> does: the loop takes plain normals (Normals<T>) and converts X to the exponential's unit once, at the
 // end of the path.
 #include "localvol_device.hpp"
+#include "path_frame.hpp"
 
 namespace mcamd {
 
@@ -26,9 +27,7 @@ struct LocalVolArgs {
     T K, S0;
     int put;
     uint32_t n_steps;
-    uint64_t seed;
-    uint64_t path_offset;
-    uint64_t n_local;
+    PathShard shard;
     T *samples;               // nullable
     GridFinish fin;
 };
@@ -43,15 +42,15 @@ __global__ __launch_bounds__(kBlock) void localvol_kernel(LocalVolArgs<T> a, dou
     lv_copy_table(tab, 0, a.surf.table, a.surf.rows.n_entries);
     __syncthreads();
     const MathCtx<T> m = MathCtx<T>::init();
-    const PhiloxKeys key = PhiloxKeys::make(a.seed);
+    const PhiloxKeys key = PhiloxKeys::make(a.shard.seed);
     const LvAxis<T> axis = lv_resident(a.surf.axis);
     const T mu_dt = lv_resident(a.mu_dt), half_dt = lv_resident(a.half_dt), sqrt_dt = lv_resident(a.sqrt_dt);
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
+    const ThreadPaths paths(a.shard.n_local);   // made at the loop, one fp64 kernel spills 8 scalars for 4
     const StepBlocks blocks = step_blocks<NB>(a.n_steps);
     const T d0 = UP ? a.b : -a.b;   // |b|: the spot is strictly on the live side (checked on the host)
     double acc4[kLocalVolRecord] = {0.0, 0.0, 0.0, 0.0};
-    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < a.n_local; i += stride) {
-        const uint64_t subsequence = a.path_offset + i;
+    for (const uint64_t i : paths) {
+        const uint64_t subsequence = a.shard.path_offset + i;
         T X = T(0);          // ln(S / S0), natural units
         T d_prev = d0;
         T w = T(1);          // the bridge factors so far (CONT); the hits are in `alive`
@@ -93,15 +92,11 @@ __global__ __launch_bounds__(kBlock) void localvol_kernel(LocalVolArgs<T> a, dou
             y = OUT ? (alive ? wd * static_cast<double>(h) : 0.0) : (1.0 - wd) * static_cast<double>(h);
         }
         if (a.samples) a.samples[i] = static_cast<T>(y);
-        acc4[0] += y;
-        acc4[1] = __builtin_fma(y, y, acc4[1]);
-        // a wavefront's active lanes are a prefix (path ids grow with the lane): lane 0 counts the wavefront's steps
-        if ((threadIdx.x & (kWave - 1)) == 0) acc4[2] += static_cast<double>(steps_run);
-        acc4[3] += static_cast<double>(live);
+        add_sample(acc4, y);
+        add_counters(acc4, steps_run, live);
     }
     if (a.fin.n_value >= 0.0) acc4[2] = acc4[3] = 0.0;   // the 6-double statistics layout has no slot for the counters
-    block_sumN<kBlock, kLocalVolRecord>(acc4);
-    grid_finish<kBlock, kLocalVolRecord>(acc4, partials, a.fin);
+    finish_paths(acc4, partials, a.fin);
 }
 
 template <typename T, int BAR, bool CONT, bool OUT>
@@ -132,8 +127,9 @@ static hipError_t launch_localvol_t(const LocalVolJob &j, double *d_partials, ui
     const double q_unit = sizeof(T) == 4 ? kLn2 : 1.0;
     const double q_cut = sizeof(T) == 4 ? 18.0 : 38.0;
     LocalVolArgs<T> a;
-    lv_walk_args<T>(a, j.walk);
-    a.b = j.barrier ? static_cast<T>(std::log(j.B / j.S0)) : T(0);
+    lv_step_args<T>(a, j.walk);
+    a.shard = shard_of(j.walk.paths);
+    a.b =j.barrier ? static_cast<T>(std::log(j.B / j.S0)) : T(0);
     a.kq = static_cast<T>(2.0 / (j.walk.dt * q_unit));
     a.q_cut = static_cast<T>(q_cut / q_unit);
     a.K = static_cast<T>(j.K);
@@ -141,7 +137,7 @@ static hipError_t launch_localvol_t(const LocalVolJob &j, double *d_partials, ui
     a.put = j.put ? 1 : 0;
     a.n_steps = j.walk.paths.n_steps;
     a.samples = static_cast<T *>(j.d_samples);
-    a.fin = GridFinish{fs.out, fs.ticket, fs.n_value};
+    a.fin = grid_finish_of(fs);
     if (!j.barrier) launch_localvol_k<T, 0, false, false>(a, d_partials, grid, stream);
     else if (j.up) launch_localvol_b<T, 2>(j, a, d_partials, grid, stream);
     else launch_localvol_b<T, 1>(j, a, d_partials, grid, stream);
@@ -153,8 +149,9 @@ hipError_t launch_localvol(const LocalVolJob &job, double *d_partials, uint32_t 
 {
     if (!finish_ok(finish, grid)) return hipErrorInvalidValue;
     if (!lv_grid_ok(job.walk.surface, job.walk.paths.n_steps)) return hipErrorInvalidValue;
-    return job.walk.paths.precision == 32 ? launch_localvol_t<float>(job, d_partials, grid, finish, stream)
-                               : launch_localvol_t<double>(job, d_partials, grid, finish, stream);
+    return dispatch_precision(job.walk.paths.precision, [&](auto p) {
+        return launch_localvol_t<typename decltype(p)::type>(job, d_partials, grid, finish, stream);
+    });
 }
 
 }  // namespace mcamd

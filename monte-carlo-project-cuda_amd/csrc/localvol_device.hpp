@@ -75,16 +75,22 @@ inline T lv_exp_scale()
 }
 
 // What the argument structs of the single-surface kernels (LocalVolArgs, CliquetArgs, LvGreeksArgs, SmileArgs) have in
-// common, from the walk of their job.  The structs share no sub-struct: each kernel's scalar loads are compiled against
-// its own layout.
+// common, from the walk of their job.  The structs share no sub-struct for these: each kernel's scalar loads are
+// compiled against its own layout.  The one-path-per-thread kernels add their PathShard; lv_walk_args adds the three
+// shard fields as the smile kernel carries them.
 template <typename T, typename Args>
-inline void lv_walk_args(Args &a, const LocalVolWalk &w)
+inline void lv_step_args(Args &a, const LocalVolWalk &w)
 {
     a.surf = lv_surface<T>(w.surface, w.paths.n_steps);
     a.mu_dt = static_cast<T>(w.mu * w.dt);
     a.half_dt = static_cast<T>(0.5 * w.dt);
     a.sqrt_dt = static_cast<T>(std::sqrt(w.dt));
     a.exp_scale = lv_exp_scale<T>();
+}
+template <typename T, typename Args>
+inline void lv_walk_args(Args &a, const LocalVolWalk &w)
+{
+    lv_step_args<T>(a, w);
     a.seed = w.paths.seed;
     a.path_offset = w.paths.path_offset;
     a.n_local = w.paths.n_local;

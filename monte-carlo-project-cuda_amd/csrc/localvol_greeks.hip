@@ -16,6 +16,7 @@
 // array index, which would send them to scratch.  BUCKETS = false and GAMMA = false drop their state altogether.
 #include "localvol_device.hpp"
 #include "localvol_greeks.hpp"
+#include "path_frame.hpp"
 
 namespace mcamd {
 
@@ -30,9 +31,7 @@ struct LvGreeksArgs {
     uint32_t n_steps;
     uint32_t n_buckets;
     uint32_t bkt_whole, bkt_rem, bkt_thr;   // B / n, B % n, n - B % n: the rows' carry on the bucket index
-    uint64_t seed;
-    uint64_t path_offset;
-    uint64_t n_local;
+    PathShard shard;
     double S0d, T_mat;        // the sample's fp64 constants
     double S_up, S_dn, dS;    // S0 e^{+-eta} and their difference
     double *samples;          // nullable
@@ -75,22 +74,22 @@ __global__ __launch_bounds__(kBlock) void localvol_greeks_kernel(LvGreeksArgs<T>
     lv_copy_table(tab, 0, a.surf.table, a.surf.rows.n_entries);
     __syncthreads();
     const MathCtx<T> m = MathCtx<T>::init();
-    const PhiloxKeys key = PhiloxKeys::make(a.seed);
+    const PhiloxKeys key = PhiloxKeys::make(a.shard.seed);
     const LvAxis<T> axis = lv_resident(a.surf.axis);
     const T mu_dt = lv_resident(a.mu_dt), half_dt = lv_resident(a.half_dt), sqrt_dt = lv_resident(a.sqrt_dt);
     const T dt = lv_resident(a.dt);
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
+    const ThreadPaths paths(a.shard.n_local);   // made at the loop, seven of the eight kernels spill otherwise
     const uint32_t n_full = a.n_steps / NB;
     const uint32_t rem = a.n_steps - n_full * NB;
     if (blockIdx.x == 0 && threadIdx.x == 0) {   // n and the zero tail of the statistics record
-        a.fin.out[kLvGreeksRecord] = static_cast<double>(a.n_local);
+        a.fin.out[kLvGreeksRecord] = static_cast<double>(a.shard.n_local);
         for (int k = kLvGreeksRecord + 1; k < kLvGreeksStats; ++k) a.fin.out[k] = 0.0;
     }
     double acc[kLvGreeksRecord];
 #pragma unroll
     for (int k = 0; k < kLvGreeksRecord; ++k) acc[k] = 0.0;
-    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < a.n_local; i += stride) {
-        const uint64_t subsequence = a.path_offset + i;
+    for (const uint64_t i : paths) {
+        const uint64_t subsequence = a.shard.path_offset + i;
         T X = T(0), J = T(1), U = T(0), R = T(0);
         T Xp = a.eta, Xm = -a.eta, Jp = T(1), Jm = T(1);   // GAMMA
         T Ub[NBK];                                          // BUCKETS
@@ -175,13 +174,12 @@ __global__ __launch_bounds__(kBlock) void localvol_greeks_kernel(LvGreeksArgs<T>
         if (a.samples) {
 #pragma unroll
             for (int k = 0; k < kLvGreeks + NBK; ++k)
-                if (static_cast<uint32_t>(k) < kLvGreeks + a.n_buckets) a.samples[static_cast<uint64_t>(k) * a.n_local + i] = q[k];
+                if (static_cast<uint32_t>(k) < kLvGreeks + a.n_buckets) a.samples[static_cast<uint64_t>(k) * a.shard.n_local + i] = q[k];
         }
     }
-    block_sumN<kBlock, kLvGreeksRecord>(acc);
     // one accumulator set in the last workgroup's sum: four sets of 28 doubles are 224 vector registers, which would
     // set the whole kernel's allocation (one wavefront per SIMD); a record's 28 loads are independent as it is
-    grid_finish<kBlock, kLvGreeksRecord, 1>(acc, partials, a.fin);
+    finish_paths<kLvGreeksRecord, 1>(acc, partials, a.fin);
 }
 
 template <typename T, bool GAMMA, bool BUCKETS>
@@ -198,7 +196,8 @@ static hipError_t launch_lv_greeks_t(const LocalVolGreeksJob &j, double *d_parti
 {
     const uint32_t n_steps = j.walk.paths.n_steps;
     LvGreeksArgs<T> a;
-    lv_walk_args<T>(a, j.walk);
+    lv_step_args<T>(a, j.walk);
+    a.shard = shard_of(j.walk.paths);
     a.dt = static_cast<T>(j.walk.dt);
     a.K = static_cast<T>(j.K);
     a.S0 = static_cast<T>(j.S0);
@@ -233,8 +232,9 @@ hipError_t launch_localvol_greeks(const LocalVolGreeksJob &job, double *d_partia
     if (!finish_ok(finish, grid)) return hipErrorInvalidValue;
     if (!lv_grid_ok(job.walk.surface, job.walk.paths.n_steps) || job.n_buckets > kLvGreeksMaxBuckets)
         return hipErrorInvalidValue;
-    return job.walk.paths.precision == 32 ? launch_lv_greeks_t<float>(job, d_partials, grid, finish, stream)
-                                          : launch_lv_greeks_t<double>(job, d_partials, grid, finish, stream);
+    return dispatch_precision(job.walk.paths.precision, [&](auto p) {
+        return launch_lv_greeks_t<typename decltype(p)::type>(job, d_partials, grid, finish, stream);
+    });
 }
 
 }  // namespace mcamd

@@ -17,6 +17,7 @@
 // lane does not occur, and without the branch the compiler is free to interleave the transcendentals of a block's steps.
 #include "lookback.hpp"
 #include "path_consts.hpp"
+#include "path_frame.hpp"
 
 namespace mcamd {
 
@@ -28,9 +29,7 @@ struct LookbackArgs {
     T q_cut;           // Q, natural-log units
     double K;          // fixed strike
     int fixed, put;
-    uint64_t seed;
-    uint64_t path_offset;
-    uint64_t n_local;
+    PathShard shard;
     T *samples;        // nullable
     GridFinish fin;
 };
@@ -88,14 +87,13 @@ __global__ __launch_bounds__(kBlock) void lookback_kernel(LookbackArgs<T> a, dou
 {
     constexpr int NB = Exponents<T>::kPerBlock;
     const MathCtx<T> m = MathCtx<T>::init();
-    const PhiloxKeys key = PhiloxKeys::make(a.seed);
+    const PhiloxKeys key = PhiloxKeys::make(a.shard.seed);
     const StepConsts<T> c = resident(a.c);
     const T kq = resident_t(a.kq), kb = resident_t(a.kb), q_cut = resident_t(a.q_cut);
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
     const StepBlocks blocks = step_blocks<NB>(c.n_sim);
     double acc4[kLookbackRecord] = {0.0, 0.0, 0.0, 0.0};
-    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < a.n_local; i += stride) {
-        const uint64_t subsequence = a.path_offset + i;
+    for (const uint64_t i : ThreadPaths{a.shard.n_local}) {
+        const uint64_t subsequence = a.shard.path_offset + i;
         T acc = T(0);        // X so far, in exponent units
         T E = T(0);          // its running extremum: the option is newly issued, so S0 counts
         uint32_t live = 0;   // steps whose bridge extremum was formed (q < Q)
@@ -136,15 +134,11 @@ __global__ __launch_bounds__(kBlock) void lookback_kernel(LookbackArgs<T> a, dou
             y = a.put ? Se - St : St - Se;
         }
         if (a.samples) a.samples[i] = static_cast<T>(y);
-        acc4[0] += y;
-        acc4[1] = __builtin_fma(y, y, acc4[1]);
-        // a wavefront's active lanes are a prefix (path ids grow with the lane): lane 0 counts the wavefront's steps
-        if ((threadIdx.x & (kWave - 1)) == 0) acc4[2] += static_cast<double>(c.n_sim);
-        acc4[3] += static_cast<double>(live);
+        add_sample(acc4, y);
+        add_counters(acc4, c.n_sim, live);
     }
     if (a.fin.n_value >= 0.0) acc4[2] = acc4[3] = 0.0;   // the 6-double statistics layout has no slot for the counters
-    block_sumN<kBlock, kLookbackRecord>(acc4);
-    grid_finish<kBlock, kLookbackRecord>(acc4, partials, a.fin);
+    finish_paths(acc4, partials, a.fin);
 }
 
 template <typename T, bool MAXIMUM>
@@ -167,8 +161,7 @@ static hipError_t launch_lookback_t(const LookbackJob &j, double *d_partials, ui
     const double q_cut = sizeof(T) == 4 ? 22.25 : 36.75;
     const LookbackArgs<T> a{make_consts<T>(j.path), static_cast<T>(2.0 * u * u / j.v2dt),
                             static_cast<T>(j.v2dt * log_unit / (u * u)), static_cast<T>(q_cut), j.K, j.fixed ? 1 : 0,
-                            j.put ? 1 : 0, j.path.seed, j.path.path_offset, j.path.n_local,
-                            static_cast<T *>(j.d_samples), GridFinish{fs.out, fs.ticket, fs.n_value}};
+                            j.put ? 1 : 0, shard_of(j.path), static_cast<T *>(j.d_samples), grid_finish_of(fs)};
     if (j.maximum) launch_lookback_k<T, true>(j, a, d_partials, grid, stream);
     else launch_lookback_k<T, false>(j, a, d_partials, grid, stream);
     return hipGetLastError();
@@ -178,8 +171,9 @@ hipError_t launch_lookback(const LookbackJob &job, double *d_partials, uint32_t 
                            hipStream_t stream)
 {
     if (!finish_ok(finish, grid)) return hipErrorInvalidValue;
-    return job.path.precision == 32 ? launch_lookback_t<float>(job, d_partials, grid, finish, stream)
-                                    : launch_lookback_t<double>(job, d_partials, grid, finish, stream);
+    return dispatch_precision(job.path.precision, [&](auto p) {
+        return launch_lookback_t<typename decltype(p)::type>(job, d_partials, grid, finish, stream);
+    });
 }
 
 }  // namespace mcamd
