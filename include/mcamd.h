@@ -1092,7 +1092,8 @@ int mcamd_bs_implied_vol_f64(double S0, double K, double T, double r, double q, 
  *   and h_strikes are read before the call returns.  Results do not depend on earlier calls, and two runs of one job
  *   give the same bits.
  * mcamd_finalize_smile (host): stats as above with n paths, opt->r and opt->T, n_steps and the expiry steps of the job;
- * h_price and h_std_err receive n_expiries x n_strikes doubles each, [m n_strikes + k].
+ * h_price and h_std_err receive n_expiries x n_strikes doubles each, [m n_strikes + k].  Of *smile it reads n_expiries
+ * and n_strikes alone (payoff, reserved and q may hold anything), so it serves mcamd_price_heston_smile's sums as well.
  * Requirements (MCAMD_ERR_INVALID before any device work; everything that needs neither the surface nor the context
  * comes before either is looked at): no NULL pointer (d_spots apart); payoff in range; reserved == 0; n_expiries in
  * 1 .. MCAMD_SMILE_MAX_EXPIRIES, n_strikes in 1 .. MCAMD_SMILE_MAX_STRIKES; expiry steps strictly ascending in
@@ -1435,7 +1436,8 @@ int mcamd_cliquet_price_f64(int kind, double T, double r, double q, uint32_t n_p
  * covers it); S0 > 0 and K > 0; then the context.  An empty shard returns zeros and launches nothing; its enqueue form
  * writes a zero record in stream order.
  * Left out on purpose: the QE scheme and exact simulation, barriers and path-dependent payoffs, Greeks, a term
- * structure of the parameters, a smile call, a mcamd_group_* form and a shim name (the reference has no such model).
+ * structure of the parameters, a mcamd_group_* form and a shim name (the reference has no such model).  The smile of
+ * the model is mcamd_price_heston_smile, below.
  * New. */
 #define MCAMD_HESTON_FULL_TRUNCATION 0
 
@@ -1470,6 +1472,52 @@ int mcamd_price_heston(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim 
                        void *d_samples, void *d_state, mcamd_heston_result *res);
 int mcamd_price_heston_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_heston *heston,
                                void *d_samples, void *d_state, double *d_stats);
+/* ---- Heston smile: n_expiries x n_strikes vanillas priced on ONE set of Heston paths ----
+ * Additive to ABI version 5: first carried by the build that ships csrc/heston_smile.hip (MCAMD_ABI_VERSION stays 5; a
+ * caller finds out with dlsym).  mcamd_price_localvol_smile's shape on mcamd_price_heston's paths: the paths are walked
+ * once and read at every expiry step, where 252 calls of mcamd_price_heston would walk nearly the same paths 252 times.
+ *   Paths.  Those of mcamd_price_heston, draw for draw and operation for operation: X_0 = 0 and v_0 = v0, the same step
+ *       in the path precision with dt = T / n_steps over the WHOLE n_steps, z from Philox blocks 0, 1, .. and z' from
+ *       blocks 2^63, 2^63 + 1, .. of the path's subsequence (the GLOBAL path id).  Nothing else is drawn.  The walk ends
+ *       after the last expiry step.  r, T and S0 come from opt, the model and q from heston; heston->payoff holds for
+ *       every node; opt->K, opt->v and opt->B are ignored (and may hold anything).
+ *   Expiries.  h_expiry_steps[m], m = 0 .. n_expiries - 1, strictly ascending with 1 <= s_m <= n_steps.  Expiry m is the
+ *       time t_m = s_m (T / n_steps); its spot is S_m = S0 e^{X_{s_m}}, evaluated exactly as mcamd_price_heston evaluates
+ *       S_T, in the path precision.  With s_m = n_steps, S_m and v_{s_m} are mcamd_price_heston's S_T and v_n, bit for
+ *       bit.
+ *   Nodes, h_stats, price and std_err: as mcamd_price_localvol_smile defines them.  Node (m, k) has the undiscounted
+ *       sample h = max(+-(S_m - K_k), 0), formed in the path precision from K_k narrowed to it, then widened to double;
+ *       h_stats is 2 n_expiries n_strikes doubles, the sums [m n_strikes + k] first, then the sums of squares, both
+ *       accumulated in fp64; every node is discounted to its OWN expiry t_m.  mcamd_finalize_smile serves the sums: it
+ *       reads only n_expiries and n_strikes of its mcamd_smile.
+ *   res: as mcamd_price_localvol_smile fills it.  n, kernel_ms (the path kernel), total_ms (with the sum of the
+ *       per-wavefront records), grid, block; work_steps = 64 x the steps each wavefront ran (s_last per wavefront that
+ *       holds a path), live_steps = work_steps; sum, sumsq, price, std_err, ci_lo, ci_hi are those of the LAST node,
+ *       finalized with t of the last expiry.  Everything else in res is zero.
+ *   Diagnostics.  truncated_steps and mean_variance are NOT reported: a wavefront's record holds node sums only, and
+ *       mcamd_price_heston on the same sim gives both for the same paths.
+ *   d_state (nullable, device): 2 n_expiries x n_paths_local values of the path precision:
+ *       [m n_paths_local + local path] receives S_m and [(n_expiries + m) n_paths_local + local path] the raw variance
+ *       v_{s_m}, which may be negative.
+ *   The enqueue form leaves the same 2 n_expiries n_strikes doubles in d_stats, followed by one more double that holds
+ *   n (the shard's paths): d_stats has room for 2 n_expiries n_strikes + 1 doubles.  Shards add element by element.
+ *   mcamd_enqueued_kernel_ms covers the path kernel.  h_expiry_steps and h_strikes are read before the call returns.
+ *   Results do not depend on earlier calls, and two runs of one job give the same bits.
+ * Requirements (MCAMD_ERR_INVALID before any device work, in this order): no NULL pointer (d_state apart); what
+ * mcamd_price_heston refuses of payoff, scheme, reserved, the model's parameters and r; n_expiries in
+ * 1 .. MCAMD_SMILE_MAX_EXPIRIES, n_strikes in 1 .. MCAMD_SMILE_MAX_STRIKES; expiry steps strictly ascending in
+ * 1 .. n_steps; every strike finite and > 0; what mcamd_price_heston refuses of opt's other fields, sim->flags and sim;
+ * S0 > 0; then the context.  An empty shard returns zeros and launches nothing; its enqueue form writes a zero record in
+ * stream order.  There is no mcamd_group_* form and no shim name.  Barriers, mixed call / put nodes and Greeks are not
+ * offered.  New. */
+int mcamd_price_heston_smile(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_heston *heston,
+                             uint32_t n_expiries, uint32_t n_strikes, const uint32_t *h_expiry_steps,
+                             const double *h_strikes, void *d_state, double *h_stats, mcamd_result *res);
+int mcamd_price_heston_smile_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                                     const mcamd_heston *heston, uint32_t n_expiries, uint32_t n_strikes,
+                                     const uint32_t *h_expiry_steps, const double *h_strikes, void *d_state,
+                                     double *d_stats);
+
 /* Host closed form of the model itself (not of the scheme, whose bias is first order in dt).  With F = S0 e^{(r-q)T},
  * D = e^{-rT}, k = ln(F / K) and phi the characteristic function of ln(S_T / F) in the branch-cut-safe form (Albrecher,
  * Mayer, Schoutens, Tistaert 2007, "the little Heston trap"), rearranged so that nothing is divided by xi^2:

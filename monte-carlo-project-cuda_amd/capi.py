@@ -74,6 +74,7 @@ EXPORTS = [
     "mcamd_price_localvol_greeks", "mcamd_price_localvol_greeks_enqueue", "mcamd_finalize_localvol_greeks_stats",
     "mcamd_price_cliquet", "mcamd_price_cliquet_enqueue", "mcamd_cliquet_price_f64",
     "mcamd_price_heston", "mcamd_price_heston_enqueue", "mcamd_heston_price_f64",
+    "mcamd_price_heston_smile", "mcamd_price_heston_smile_enqueue",
 ]
 
 
@@ -413,6 +414,10 @@ def load() -> C.CDLL:
                                                      C.POINTER(f64), vp, vp, vp]
     L.mcamd_finalize_smile.argtypes = [C.POINTER(f64), u64, C.POINTER(Option), C.c_uint32, C.POINTER(Smile), u32p,
                                        C.POINTER(f64), C.POINTER(f64)]
+    L.mcamd_price_heston_smile.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Heston), C.c_uint32, C.c_uint32,
+                                           u32p, C.POINTER(f64), vp, C.POINTER(f64), C.POINTER(Result)]
+    L.mcamd_price_heston_smile_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Heston), C.c_uint32,
+                                                   C.c_uint32, u32p, C.POINTER(f64), vp, vp]
     L.mcamd_price_localvol_greeks.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(LocalVolGreeksJob), vp, vp,
                                               C.POINTER(LocalVolGreeks)]
     L.mcamd_price_localvol_greeks_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(LocalVolGreeksJob),
@@ -602,6 +607,14 @@ def heston_price(S0, K, T, r, q, v0, kappa, theta, xi, rho, payoff=PAYOFF_CALL) 
     out = C.c_double()
     _check(load().mcamd_heston_price_f64(S0, K, T, r, q, v0, kappa, theta, xi, rho, payoff, C.byref(out)))
     return out.value
+
+
+def heston_smile_prices(S0, strikes, times, r, q, v0, kappa, theta, xi, rho, payoff=PAYOFF_CALL):
+    """The closed-form grid of a Heston smile: heston_price (mcamd_heston_price_f64) at every node, as a
+    (len(times), len(strikes)) numpy array; times[m] is the expiry of row m in years."""
+    import numpy as np
+    return np.array([[heston_price(S0, float(K), float(t), r, q, v0, kappa, theta, xi, rho, payoff) for K in strikes]
+                     for t in times])
 
 
 def make_localvol_greeks_job(payoff=PAYOFF_CALL, n_vega_buckets=0, q=0.0, gamma_bump=0.0) -> LocalVolGreeksJob:
@@ -886,6 +899,32 @@ class Context:
         tensor `stats` (>= 6 doubles; finalize_stats)."""
         _check(self._L.mcamd_price_heston_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(heston), _ptr(samples),
                                                   _ptr(state), _ptr(stats)))
+
+    def price_heston_smile(self, opt: Option, sim: Sim, heston: Heston, expiry_steps, strikes, state=None):
+        """len(expiry_steps) x len(strikes) vanillas on one set of price_heston's paths (mcamd_price_heston_smile);
+        heston.payoff holds for every node, opt.K, opt.v and opt.B are ignored.  state: optional device tensor of
+        2 x n_expiries x n_paths_local values of the path precision that receives every path's spot at every expiry,
+        expiry-major, then its raw variance there, expiry-major.  Returns (price, std_err, stats, res) as
+        price_localvol_smile does: each node discounted to its own expiry, stats the 2 n_e n_K sums."""
+        import numpy as np
+        smile = make_smile(len(expiry_steps), len(strikes), heston.payoff, heston.q)
+        steps, ks = _smile_arrays(smile, expiry_steps, strikes)
+        nodes = smile.n_expiries * smile.n_strikes
+        stats, res = (C.c_double * max(2 * nodes, 1))(), Result()
+        _check(self._L.mcamd_price_heston_smile(self._h, C.byref(opt), C.byref(sim), C.byref(heston), smile.n_expiries,
+                                                smile.n_strikes, steps, ks, _ptr(state), stats, C.byref(res)))
+        price, se = finalize_smile(stats, res.n, opt, sim.n_steps, smile, expiry_steps)
+        return price, se, np.array(stats[:2 * nodes]), res
+
+    def price_heston_smile_enqueue(self, opt: Option, sim: Sim, heston: Heston, expiry_steps, strikes, stats,
+                                   state=None) -> None:
+        """Asynchronous: leaves the 2 n_e n_K sums and then n in the device tensor `stats` (>= 2 n_e n_K + 1 doubles;
+        finalize_smile serves the sums)."""
+        smile = make_smile(len(expiry_steps), len(strikes), heston.payoff, heston.q)
+        steps, ks = _smile_arrays(smile, expiry_steps, strikes)
+        _check(self._L.mcamd_price_heston_smile_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(heston),
+                                                        smile.n_expiries, smile.n_strikes, steps, ks, _ptr(state),
+                                                        _ptr(stats)))
 
     def price_localvol_greeks(self, opt: Option, sim: Sim, job: LocalVolGreeksJob, surface: "LocalVolSurface",
                               samples=None) -> LocalVolGreeks:

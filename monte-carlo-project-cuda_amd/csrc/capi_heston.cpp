@@ -1,8 +1,12 @@
-// capi_heston.cpp — the calls of the C ABI that walk Heston stochastic-volatility paths: European options under the
-// full-truncation Euler scheme.  One prepare step (the refusals and the job) and its synchronous and enqueue forms; the
-// refusals keep the order of the other families: the request alone, then the context.
+// capi_heston.cpp — the calls of the C ABI that walk Heston stochastic-volatility paths under the full-truncation Euler
+// scheme: European options, and the strike-by-expiry smile.  Each call is a prepare step (the refusals and the job) and
+// its synchronous and enqueue forms; the refusals keep the order of the other families: the request alone, then the
+// context.
 #include "capi_internal.hpp"
 #include "heston.hpp"
+#include "heston_smile.hpp"
+
+#include <algorithm>
 
 static_assert(sizeof(mcamd_heston) == 64 && sizeof(mcamd_heston_result) == 96,
               "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
@@ -30,6 +34,19 @@ int check_heston_model(double q, double v0, double kappa, double theta, double x
 
 namespace {
 
+// What both Heston calls refuse of the job and of the rate, after the NULL pointers: payoff, scheme, reserved, the
+// model, r.
+int check_heston_job(const mcamd_option *opt, const mcamd_heston *hs)
+{
+    if (int rc = check_payoff(hs->payoff)) return rc;
+    if (hs->scheme != MCAMD_HESTON_FULL_TRUNCATION)
+        return fail(MCAMD_ERR_INVALID, "heston->scheme must be MCAMD_HESTON_FULL_TRUNCATION (0), got %d", hs->scheme);
+    if (hs->reserved != 0.0) return fail(MCAMD_ERR_INVALID, "heston->reserved must be 0, got %g", hs->reserved);
+    if (int rc = check_heston_model(hs->q, hs->v0, hs->kappa, hs->theta, hs->xi, hs->rho)) return rc;
+    if (!std::isfinite(opt->r)) return fail(MCAMD_ERR_INVALID, "option parameters must be finite with T > 0");
+    return MCAMD_OK;
+}
+
 // The Heston calls.  The kernel always finishes its own sum (one_path_per_thread_grid caps the grid); every refusal
 // depends on the request alone and comes before the context is looked at.  opt->v and opt->B are ignored.
 template <typename Drive>
@@ -37,12 +54,7 @@ int prepare_heston(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim
                    void *d_state, Drive drive)
 {
     if (!opt || !sim || !hs) return fail(MCAMD_ERR_INVALID, "opt, sim and heston must be non-NULL");
-    if (int rc = check_payoff(hs->payoff)) return rc;
-    if (hs->scheme != MCAMD_HESTON_FULL_TRUNCATION)
-        return fail(MCAMD_ERR_INVALID, "heston->scheme must be MCAMD_HESTON_FULL_TRUNCATION (0), got %d", hs->scheme);
-    if (hs->reserved != 0.0) return fail(MCAMD_ERR_INVALID, "heston->reserved must be 0, got %g", hs->reserved);
-    if (int rc = check_heston_model(hs->q, hs->v0, hs->kappa, hs->theta, hs->xi, hs->rho)) return rc;
-    if (!std::isfinite(opt->r)) return fail(MCAMD_ERR_INVALID, "option parameters must be finite with T > 0");
+    if (int rc = check_heston_job(opt, hs)) return rc;
     const double mu = opt->r - hs->q;
     // as the local-volatility calls: on a copy whose ignored fields are harmless (the variance is random: no bound on
     // the request can cover it, so the drift r - q stands alone in the fp64 exponent-range bound)
@@ -73,6 +85,54 @@ int prepare_heston(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim
                             [&](const mcamd::FinishSpec &fs) {
                                 return mcamd::launch_heston(job, ctx->d_partials, grid, fs, ctx->stream);
                             }});
+}
+
+// The Heston smile calls: mcamd_price_heston's paths, stopped at the expiry steps, every strike priced at every expiry.
+// The refusals: prepare_heston's of the job, the nodes as the local-volatility smile refuses them, prepare_heston's of
+// sim and opt, S0, then the context.  drive(call) runs the form's driver (run_smile_sync, run_smile_enqueue); call.n == 0
+// is the empty shard.  opt->K, opt->v and opt->B are ignored.
+template <typename Drive>
+int prepare_heston_smile(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_heston *hs,
+                         uint32_t n_expiries, uint32_t n_strikes, const uint32_t *h_expiry_steps, const double *h_strikes,
+                         void *d_state, Drive drive)
+{
+    if (!opt || !sim || !hs || !h_expiry_steps || !h_strikes)
+        return fail(MCAMD_ERR_INVALID, "opt, sim, heston, h_expiry_steps and h_strikes must be non-NULL");
+    if (int rc = check_heston_job(opt, hs)) return rc;
+    if (int rc = check_smile_nodes(n_expiries, n_strikes, h_expiry_steps, sim->n_steps, h_strikes)) return rc;
+    const double mu = opt->r - hs->q;
+    // as prepare_heston, on a copy that carries no strike of its own either
+    mcamd_option seen = *opt;
+    seen.B = 0.0;
+    seen.K = 1.0;
+    if (int rc = check_drift_request("Heston smile", seen, sim, &mu, 1)) return rc;
+    if (!(opt->S0 > 0.0)) return fail(MCAMD_ERR_INVALID, "Heston smile options need S0 > 0 (S0 = %g)", opt->S0);
+    if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
+    mcamd::HestonSmileJob job = {};
+    job.paths = path_range(sim);
+    job.S0 = opt->S0;
+    job.mu = mu;
+    job.dt = even_dt(opt, sim);
+    job.v0 = hs->v0;
+    job.kappa = hs->kappa;
+    job.theta = hs->theta;
+    job.xi = hs->xi;
+    job.rho = hs->rho;
+    job.put = hs->payoff == MCAMD_PAYOFF_PUT;
+    job.n_expiries = n_expiries;
+    job.n_strikes = n_strikes;
+    std::copy(h_expiry_steps, h_expiry_steps + n_expiries, job.expiry_steps);
+    std::copy(h_strikes, h_strikes + n_strikes, job.strikes);
+    job.d_state = d_state;
+    const uint64_t n = sim->n_paths_local;
+    const uint32_t last = job.expiry_steps[n_expiries - 1];
+    return drive(SmileCall{n, n ? mcamd::smile_grid(n, n_expiries, n_strikes, ctx->compute_units) : 0, n_expiries,
+                           n_strikes, opt->r, static_cast<double>(last) * job.dt, last,
+                           [](const void *j, double *d_partials, uint32_t grid, hipStream_t stream) {
+                               return mcamd::launch_heston_smile(*static_cast<const mcamd::HestonSmileJob *>(j),
+                                                                 d_partials, grid, stream);
+                           },
+                           &job});
 }
 
 }  // namespace
@@ -108,6 +168,26 @@ int mcamd_price_heston_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mc
 {
     return prepare_heston(ctx, opt, sim, heston, d_samples, d_state,
                           [&](const auto &call) { return run_enqueue(ctx, call, d_stats); });
+}
+
+int mcamd_price_heston_smile(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_heston *heston,
+                             uint32_t n_expiries, uint32_t n_strikes, const uint32_t *h_expiry_steps,
+                             const double *h_strikes, void *d_state, double *h_stats, mcamd_result *res)
+{
+    if (!res || !h_stats) return fail(MCAMD_ERR_INVALID, "h_stats and res must be non-NULL");
+    zero_result(res);
+    return prepare_heston_smile(ctx, opt, sim, heston, n_expiries, n_strikes, h_expiry_steps, h_strikes, d_state,
+                                [&](const SmileCall &call) { return run_smile_sync(ctx, call, h_stats, res); });
+}
+
+int mcamd_price_heston_smile_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                                     const mcamd_heston *heston, uint32_t n_expiries, uint32_t n_strikes,
+                                     const uint32_t *h_expiry_steps, const double *h_strikes, void *d_state,
+                                     double *d_stats)
+{
+    if (!d_stats) return fail(MCAMD_ERR_INVALID, "d_stats is NULL");
+    return prepare_heston_smile(ctx, opt, sim, heston, n_expiries, n_strikes, h_expiry_steps, h_strikes, d_state,
+                                [&](const SmileCall &call) { return run_smile_enqueue(ctx, call, d_stats); });
 }
 
 }  // extern "C"

@@ -98,6 +98,10 @@ int check_localvol_grid(const mcamd_localvol_grid *grid, const double *h_sigma, 
 int check_cliquet_kind(int kind);
 int check_cliquet_local(double local_floor, double local_cap);
 int check_cliquet_kind_bounds(int kind, double local_floor, double local_cap);
+// what both smile families refuse of the nodes, in this order: n_expiries and n_strikes out of range, expiry steps that
+// are not strictly ascending in 1 .. n_steps, a strike that is not finite and > 0
+int check_smile_nodes(uint32_t n_expiries, uint32_t n_strikes, const uint32_t *h_expiry_steps, uint32_t n_steps,
+                      const double *h_strikes);
 // capi_heston.cpp
 int check_heston_model(double q, double v0, double kappa, double theta, double xi, double rho);
 // closed_forms.cpp
@@ -315,7 +319,7 @@ int run_sync(mcamd_ctx *ctx, const DeviceCall<Launch> &call, Result *res, Fill f
     return MCAMD_OK;
 }
 
-// capi.cpp: what every enqueue form (run_enqueue and the smile's own) does to the ring and the scratch buffer, after
+// capi.cpp: what every enqueue form (run_enqueue and run_smile_enqueue) does to the ring and the scratch buffer, after
 // hipSetDevice.  The slot of the call being enqueued is n_enqueued % kRing; a call counts once its kernels are enqueued.
 // The empty shard: n all-zero doubles in d_stats, ordered on the stream, between both events of the slot; counted.
 int enqueue_empty_shard(mcamd_ctx *ctx, double *d_stats, uint32_t n);
@@ -350,6 +354,29 @@ int run_enqueue(mcamd_ctx *ctx, const DeviceCall<Launch> &call, double *d_stats)
     ctx->n_enqueued++;
     return MCAMD_OK;
 }
+
+// ---- capi_localvol.cpp: the two drivers of the smile families -----------------------------------------------------------
+
+// One smile call (mcamd_price_localvol_smile, mcamd_price_heston_smile) as its two drivers see it.  They are not
+// run_sync / run_enqueue: a smile is two kernels, its per-wavefront records are not the reported grid of sums, and a
+// record holds up to 4096 doubles where DeviceCall's fit the 32 of h_rec.  launch(job, d_partials, grid, stream) enqueues
+// the family's walk, which leaves grid x kSmileWavesPerBlock records; launch_smile_finish sums them for either family.
+struct SmileCall {
+    uint64_t n;          // paths of the shard; 0: empty shard, nothing runs
+    uint32_t grid;       // workgroups of the walk (smile_grid)
+    uint32_t n_expiries, n_strikes;
+    double r, t_last;    // what the last node is finalized with: the rate, and the time of the last expiry
+    uint32_t last_step;  // the step of the last expiry: every wavefront that holds a path runs that many
+    hipError_t (*launch)(const void *job, double *d_partials, uint32_t grid, hipStream_t stream);
+    const void *job;
+};
+// Synchronous: h_stats receives the 2 n_e n_K sums (zeros for an empty shard, which launches nothing) through the
+// context's pinned smile record, and *res (zeroed by the caller) the last node, the work and the timings: the walk runs
+// between ev0 and ev1, the sum of the records up to ev2.
+int run_smile_sync(mcamd_ctx *ctx, const SmileCall &call, double *h_stats, mcamd_result *res);
+// Asynchronous: the walk runs between the ring events of the call's slot and the sum leaves the 2 n_e n_K sums and then n
+// in d_stats; an empty shard leaves 2 n_e n_K + 1 zeros, still ordered on the stream.
+int run_smile_enqueue(mcamd_ctx *ctx, const SmileCall &call, double *d_stats);
 
 }  // namespace mcamd::capi
 

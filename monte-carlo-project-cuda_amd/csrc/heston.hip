@@ -17,10 +17,6 @@
 
 namespace mcamd {
 
-// The variance normals' block of a step block: same key and subsequence, 2^63 beyond (n_steps is 32-bit: the
-// log-price normals never get there).
-constexpr uint64_t kHestonVarianceBlocks = 1ull << 63;
-
 template <typename T>
 struct HestonArgs {
     HestonConsts<T> c;
@@ -82,17 +78,9 @@ template <typename T>
 static hipError_t launch_heston_t(const HestonJob &j, double *d_partials, uint32_t grid, const FinishSpec &fs,
                                   hipStream_t stream)
 {
-    const double sqrt_dt = std::sqrt(j.dt);
     HestonArgs<T> a;
-    a.c.mu_dt = static_cast<T>(j.mu * j.dt);
-    a.c.half_dt = static_cast<T>(0.5 * j.dt);
-    a.c.sqrt_dt = static_cast<T>(sqrt_dt);
-    a.c.kappa_dt = static_cast<T>(j.kappa * j.dt);
-    a.c.kappa_theta_dt = static_cast<T>(j.kappa * j.theta * j.dt);
-    a.c.xi_sqrt_dt = static_cast<T>(j.xi * sqrt_dt);
-    a.c.rho = static_cast<T>(j.rho);
-    a.c.rho_c = static_cast<T>(std::sqrt(1.0 - j.rho * j.rho));
-    a.exp_scale = static_cast<T>(sizeof(T) == 4 ? 1.4426950408889634 : f64::kExpScale);
+    a.c = heston_consts<T>(j.mu, j.dt, j.kappa, j.theta, j.xi, j.rho);
+    a.exp_scale = heston_exp_scale<T>();
     a.v0 = static_cast<T>(j.v0);
     a.K = static_cast<T>(j.K);
     a.S0 = static_cast<T>(j.S0);

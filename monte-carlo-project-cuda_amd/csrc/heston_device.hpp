@@ -1,6 +1,6 @@
 // heston_device.hpp — the step of a Heston path under the full-truncation Euler scheme in the log-price, for any kernel
-// that walks such paths (heston.hip today; barriers, Asians and cliquets under Heston can reuse it): the step constants
-// and the move of one step.
+// that walks such paths (heston.hip, heston_smile.hip; barriers, Asians and cliquets under Heston can reuse it): the step
+// constants, where the variance's normals come from, and the move of one step.
 //
 // Definitions (include/mcamd.h, mcamd_price_heston): X = ln(S / S0) in NATURAL-log units, v the raw variance, which may
 // go below zero; v+ = max(v, 0) is what the drift, the diffusion and the mean reversion read.  With the step's two
@@ -21,6 +21,10 @@
 
 namespace mcamd {
 
+// The variance normals' block of a step block: same key and subsequence, 2^63 beyond (n_steps is 32-bit: the
+// log-price normals never get there).
+constexpr uint64_t kHestonVarianceBlocks = 1ull << 63;
+
 // The floating-point constants of a step, formed in double on the host and narrowed once.
 template <typename T>
 struct HestonConsts {
@@ -33,6 +37,30 @@ struct HestonConsts {
     T rho;
     T rho_c;            // sqrt(1 - rho^2): 0 at rho = +-1
 };
+
+// Host: the constants of a step of dt at the drift mu = r - q, as every launcher of these paths forms them ...
+template <typename T>
+inline HestonConsts<T> heston_consts(double mu, double dt, double kappa, double theta, double xi, double rho)
+{
+    const double sqrt_dt = std::sqrt(dt);
+    HestonConsts<T> c;
+    c.mu_dt = static_cast<T>(mu * dt);
+    c.half_dt = static_cast<T>(0.5 * dt);
+    c.sqrt_dt = static_cast<T>(sqrt_dt);
+    c.kappa_dt = static_cast<T>(kappa * dt);
+    c.kappa_theta_dt = static_cast<T>(kappa * theta * dt);
+    c.xi_sqrt_dt = static_cast<T>(xi * sqrt_dt);
+    c.rho = static_cast<T>(rho);
+    c.rho_c = static_cast<T>(std::sqrt(1.0 - rho * rho));
+    return c;
+}
+// ... and the exponent units per natural-log unit of the exponential that ends a path (exp_of_logreturn): log2 e in
+// fp32, 65536 / ln 2 in fp64
+template <typename T>
+inline T heston_exp_scale()
+{
+    return static_cast<T>(sizeof(T) == 4 ? 1.4426950408889634 : f64::kExpScale);
+}
 
 // Where they live.  fp32: in vector registers, because a scalar operand doubles the issue time of the full-rate fp32
 // instructions (mc_device.hpp vgpr_resident).  fp64: an operation issues in 4 cycles with or without a scalar operand.

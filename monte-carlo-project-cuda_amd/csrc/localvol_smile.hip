@@ -8,16 +8,13 @@
 //
 // Walk phase: one path per lane.  The next expiry step is wave-uniform and lives in a scalar register; a Philox block
 // that holds no expiry runs the plain unrolled steps, one that holds an expiry (or the end) tests every step.
-// Strike phase: at an expiry the wavefront holds 64 spots, one per lane, and turns the work a quarter-turn: lane k
-// holds strike k and runs over the wavefront's valid paths j (a prefix; its length comes from the ballot), reading S_j
-// by v_readlane into scalar registers, and keeps sum h and sum h^2 of node (m, k) in two fp64 registers.  After the
-// loop lane k adds them to its own 16-byte entry of the wavefront's private record [m][k] in global memory — a plain
-// read-modify-write that only this lane of this wavefront ever touches, in program order; the first trip of a
-// wavefront writes instead of adding (its old value is taken as 0 and the entry is not read), and a wavefront without
-// any path writes zeros, so every entry of every record is written whatever the buffer held.
+// Strike phase (smile_device.hpp, shared with heston_smile.hip): at an expiry the wavefront holds 64 spots, one per lane;
+// lane k holds strike k, runs over the wavefront's valid paths and adds sum h and sum h^2 of node (m, k) to its own
+// 16-byte entry of the wavefront's private record [m][k] in global memory.
 // Finish: smile_finish_kernel, one thread per node, sums the entries over the wavefronts in index order.
 #include "localvol_smile.hpp"
 #include "localvol_device.hpp"
+#include "smile_device.hpp"
 
 namespace mcamd {
 
@@ -38,23 +35,6 @@ struct SmileArgs {
     T strikes[kSmileMaxStrikes];
 };
 
-// lane j's value, j wave-uniform: v_readlane_b32 into scalar registers (a pair for fp64)
-__device__ __forceinline__ float sm_broadcast(float v, uint32_t j)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), static_cast<int>(j)));
-}
-__device__ __forceinline__ double sm_broadcast(double v, uint32_t j)
-{
-    const uint64_t bits = __builtin_bit_cast(uint64_t, v);
-    const uint32_t lo = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(bits), static_cast<int>(j)));
-    const uint32_t hi = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(bits >> 32), static_cast<int>(j)));
-    return __builtin_bit_cast(double, (static_cast<uint64_t>(hi) << 32) | lo);
-}
-
-struct alignas(16) SmileEntry {
-    double sum, sumsq;
-};
-
 template <typename T>
 __global__ __launch_bounds__(kBlock) void smile_kernel(SmileArgs<T> args, double *__restrict__ partials)
 {
@@ -71,11 +51,7 @@ __global__ __launch_bounds__(kBlock) void smile_kernel(SmileArgs<T> args, double
     const uint32_t wave = blockIdx.x * (kBlock / kWave) + wave_in_block;
     const uint32_t n_e = args.n_expiries, n_K = args.n_strikes;
     const bool has_node = lane < n_K;
-    // h = max(+-(S - K), 0) as one fma with the sign in a lane constant: fma(S, sign, -sign K) rounds S - K or K - S
-    // once, as the subtraction does (the product with +-1 is exact)
-    const T sign = args.put ? T(-1) : T(1);
-    T minus_sign_K = -sign * args.strikes[has_node ? lane : 0];
-    asm volatile("" : "+v"(minus_sign_K));   // the strike has arrived before the first strike loop, not inside it
+    const SmileLane<T> ln = smile_lane(args.strikes, args.put, lane, has_node);
     // the wavefront's record: n_e rows of n_K entries
     SmileEntry *rec = reinterpret_cast<SmileEntry *>(partials) + static_cast<uint64_t>(wave) * n_e * n_K;
     const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
@@ -88,7 +64,7 @@ __global__ __launch_bounds__(kBlock) void smile_kernel(SmileArgs<T> args, double
         // the valid lanes are a prefix (path ids grow with the lane): their number is the strike loop's trip count
         const uint32_t count = static_cast<uint32_t>(__builtin_popcountll(__builtin_amdgcn_ballot_w64(valid)));
         if (count == 0) {
-            // only a wavefront's first trip can be empty: its record is all zeros
+            // only a wavefront's first trip can be empty: its record is all zeros (smile_device.hpp)
             if (has_node)
                 for (uint32_t mi = 0; mi < n_e; ++mi) rec[mi * n_K + lane] = SmileEntry{0.0, 0.0};
             first = false;
@@ -108,20 +84,7 @@ __global__ __launch_bounds__(kBlock) void smile_kernel(SmileArgs<T> args, double
         auto expiry = [&]() {
             const T S = exp_of_logreturn(args.S0, X * args.exp_scale, m);
             if (args.spots && valid) args.spots[static_cast<uint64_t>(mi) * args.n_local + i] = S;
-            SmileEntry *entry = rec + mi * n_K + lane;
-            // the entry's load is issued before the strike loop, whose length hides its latency
-            SmileEntry old{0.0, 0.0};
-            if (!first && has_node) old = *entry;
-            double sum = 0.0, sumsq = 0.0;
-            for (uint32_t j = 0; j < count; ++j) {
-                const T Sj = sm_broadcast(S, j);
-                T h = fma_t(Sj, sign, minus_sign_K);
-                h = h > T(0) ? h : T(0);
-                const double hd = static_cast<double>(h);
-                sum += hd;
-                sumsq = __builtin_fma(hd, hd, sumsq);
-            }
-            if (has_node) *entry = SmileEntry{old.sum + sum, old.sumsq + sumsq};
+            smile_strike_phase(S, count, ln, has_node, first, rec + mi * n_K + lane);
             ++mi;
             next = mi < n_e ? args.expiry_steps[mi] : 0xFFFFFFFFu;
         };
