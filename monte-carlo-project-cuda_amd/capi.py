@@ -683,6 +683,17 @@ def finalize_smile(stats, n, opt: Option, n_steps, smile: Smile, expiry_steps):
     return np.array(price[:]).reshape(shape), np.array(se[:]).reshape(shape)
 
 
+def _smile_sync(opt: Option, sim: Sim, smile: Smile, expiry_steps, call):
+    """the tail of both synchronous smile methods: call(stats, res) runs the C call on the host sums' buffer and the
+    result's reference; returns (price, std_err, stats, res)"""
+    import numpy as np
+    nodes = smile.n_expiries * smile.n_strikes
+    stats, res = (C.c_double * max(2 * nodes, 1))(), Result()
+    _check(call(stats, C.byref(res)))
+    price, se = finalize_smile(stats, res.n, opt, sim.n_steps, smile, expiry_steps)
+    return price, se, np.array(stats[:2 * nodes]), res
+
+
 def implied_vols(S0, strikes, times, r, q, prices, payoff=PAYOFF_CALL):
     """bs_implied_vol over a price array: prices[m][k] is the option at times[m] struck at strikes[k].  NaN where a
     price lies outside the no-arbitrage bounds; never raises for that."""
@@ -906,15 +917,11 @@ class Context:
         2 x n_expiries x n_paths_local values of the path precision that receives every path's spot at every expiry,
         expiry-major, then its raw variance there, expiry-major.  Returns (price, std_err, stats, res) as
         price_localvol_smile does: each node discounted to its own expiry, stats the 2 n_e n_K sums."""
-        import numpy as np
         smile = make_smile(len(expiry_steps), len(strikes), heston.payoff, heston.q)
         steps, ks = _smile_arrays(smile, expiry_steps, strikes)
-        nodes = smile.n_expiries * smile.n_strikes
-        stats, res = (C.c_double * max(2 * nodes, 1))(), Result()
-        _check(self._L.mcamd_price_heston_smile(self._h, C.byref(opt), C.byref(sim), C.byref(heston), smile.n_expiries,
-                                                smile.n_strikes, steps, ks, _ptr(state), stats, C.byref(res)))
-        price, se = finalize_smile(stats, res.n, opt, sim.n_steps, smile, expiry_steps)
-        return price, se, np.array(stats[:2 * nodes]), res
+        return _smile_sync(opt, sim, smile, expiry_steps, lambda stats, res: self._L.mcamd_price_heston_smile(
+            self._h, C.byref(opt), C.byref(sim), C.byref(heston), smile.n_expiries, smile.n_strikes, steps, ks, _ptr(state),
+            stats, res))
 
     def price_heston_smile_enqueue(self, opt: Option, sim: Sim, heston: Heston, expiry_steps, strikes, stats,
                                    state=None) -> None:
@@ -950,14 +957,9 @@ class Context:
         that receives every path's spot at every expiry, expiry-major.  Returns (price, std_err, stats, res): price
         and std_err as (n_expiries, n_strikes) numpy arrays, each node discounted to its own expiry; stats the
         2 n_e n_K sums (all sums, then all sums of squares) as a numpy array; res as the header describes it."""
-        import numpy as np
         steps, ks = _smile_arrays(smile, expiry_steps, strikes)
-        nodes = smile.n_expiries * smile.n_strikes
-        stats, res = (C.c_double * max(2 * nodes, 1))(), Result()
-        _check(self._L.mcamd_price_localvol_smile(self._h, C.byref(opt), C.byref(sim), C.byref(smile), steps, ks,
-                                                  surface._h, _ptr(spots), stats, C.byref(res)))
-        price, se = finalize_smile(stats, res.n, opt, sim.n_steps, smile, expiry_steps)
-        return price, se, np.array(stats[:2 * nodes]), res
+        return _smile_sync(opt, sim, smile, expiry_steps, lambda stats, res: self._L.mcamd_price_localvol_smile(
+            self._h, C.byref(opt), C.byref(sim), C.byref(smile), steps, ks, surface._h, _ptr(spots), stats, res))
 
     def price_localvol_smile_enqueue(self, opt: Option, sim: Sim, smile: Smile, expiry_steps, strikes,
                                      surface: "LocalVolSurface", stats, spots=None) -> None:

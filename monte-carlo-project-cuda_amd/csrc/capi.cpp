@@ -926,22 +926,6 @@ int mcamd_finalize_localvol_greeks_stats(const double stats[32], double r, doubl
     return MCAMD_OK;
 }
 
-int mcamd_finalize_smile(const double *stats, uint64_t n, const mcamd_option *opt, uint32_t n_steps,
-                         const mcamd_smile *smile, const uint32_t *h_expiry_steps, double *h_price, double *h_std_err)
-{
-    if (!stats || !opt || !smile || !h_expiry_steps || !h_price || !h_std_err)
-        return fail(MCAMD_ERR_INVALID, "stats, opt, smile, h_expiry_steps, h_price and h_std_err must be non-NULL");
-    if (smile->n_expiries < 1 || smile->n_expiries > MCAMD_SMILE_MAX_EXPIRIES || smile->n_strikes < 1 ||
-        smile->n_strikes > MCAMD_SMILE_MAX_STRIKES)
-        return fail(MCAMD_ERR_INVALID, "n_expiries must lie in 1 .. %d and n_strikes in 1 .. %d", MCAMD_SMILE_MAX_EXPIRIES,
-                    MCAMD_SMILE_MAX_STRIKES);
-    if (n_steps == 0 || !(opt->T > 0.0) || !std::isfinite(opt->T) || !std::isfinite(opt->r))
-        return fail(MCAMD_ERR_INVALID, "a smile needs n_steps >= 1 and finite r and T > 0");
-    finalize_smile_into(stats, n, opt->r, opt->T, n_steps, smile->n_expiries, smile->n_strikes, h_expiry_steps, h_price,
-                        h_std_err);
-    return MCAMD_OK;
-}
-
 int mcamd_finalize(double sum, double sumsq, uint64_t n, double r, double T, mcamd_result *res)
 {
     if (!res) return fail(MCAMD_ERR_INVALID, "res is NULL");

@@ -6,8 +6,6 @@
 #include "heston.hpp"
 #include "heston_smile.hpp"
 
-#include <algorithm>
-
 static_assert(sizeof(mcamd_heston) == 64 && sizeof(mcamd_heston_result) == 96,
               "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
 static_assert(MCAMD_HESTON_FULL_TRUNCATION == mcamd::kHestonFullTruncation, "the kernels' scheme is MCAMD_HESTON_*");
@@ -47,6 +45,13 @@ int check_heston_job(const mcamd_option *opt, const mcamd_heston *hs)
     return MCAMD_OK;
 }
 
+// The walk of both jobs, read once check_heston_job has passed.  The refusals of sim and opt come after it: until then
+// dt may be anything (n_steps == 0 divides by zero, in floating point) and nothing reads it.
+mcamd::HestonWalk heston_walk(const mcamd_option *opt, const mcamd_sim *sim, const mcamd_heston *hs)
+{
+    return {path_range(sim), opt->r - hs->q, even_dt(opt, sim), hs->v0, hs->kappa, hs->theta, hs->xi, hs->rho};
+}
+
 // The Heston calls.  The kernel always finishes its own sum (one_path_per_thread_grid caps the grid); every refusal
 // depends on the request alone and comes before the context is looked at.  opt->v and opt->B are ignored.
 template <typename Drive>
@@ -55,28 +60,20 @@ int prepare_heston(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim
 {
     if (!opt || !sim || !hs) return fail(MCAMD_ERR_INVALID, "opt, sim and heston must be non-NULL");
     if (int rc = check_heston_job(opt, hs)) return rc;
-    const double mu = opt->r - hs->q;
+    mcamd::HestonJob job;
+    job.walk = heston_walk(opt, sim, hs);
     // as the local-volatility calls: on a copy whose ignored fields are harmless (the variance is random: no bound on
     // the request can cover it, so the drift r - q stands alone in the fp64 exponent-range bound)
     mcamd_option seen = *opt;
     seen.B = 0.0;
-    if (int rc = check_drift_request("Heston", seen, sim, &mu, 1)) return rc;
+    if (int rc = check_drift_request("Heston", seen, sim, &job.walk.mu, 1)) return rc;
     if (!(opt->S0 > 0.0) || !(opt->K > 0.0))
         return fail(MCAMD_ERR_INVALID, "Heston options need S0 > 0 and K > 0 (S0 = %g, K = %g)", opt->S0, opt->K);
     if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
     if (sim->n_paths_local == 0) return drive(empty_call());
-    mcamd::HestonJob job;
-    job.paths = path_range(sim);
     job.scheme = hs->scheme;
     job.S0 = opt->S0;
     job.K = opt->K;
-    job.mu = mu;
-    job.dt = even_dt(opt, sim);
-    job.v0 = hs->v0;
-    job.kappa = hs->kappa;
-    job.theta = hs->theta;
-    job.xi = hs->xi;
-    job.rho = hs->rho;
     job.put = hs->payoff == MCAMD_PAYOFF_PUT;
     job.d_samples = d_samples;
     job.d_state = d_state;
@@ -88,9 +85,9 @@ int prepare_heston(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim
 }
 
 // The Heston smile calls: mcamd_price_heston's paths, stopped at the expiry steps, every strike priced at every expiry.
-// The refusals: prepare_heston's of the job, the nodes as the local-volatility smile refuses them, prepare_heston's of
-// sim and opt, S0, then the context.  drive(call) runs the form's driver (run_smile_sync, run_smile_enqueue); call.n == 0
-// is the empty shard.  opt->K, opt->v and opt->B are ignored.
+// The refusals: prepare_heston's of the job, the nodes as every smile call refuses them (check_smile_nodes),
+// prepare_heston's of sim and opt, S0, then the context.  drive(call) runs the form's driver (run_smile_sync,
+// run_smile_enqueue of capi_smile.cpp); call.n == 0 is the empty shard.  opt->K, opt->v and opt->B are ignored.
 template <typename Drive>
 int prepare_heston_smile(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_heston *hs,
                          uint32_t n_expiries, uint32_t n_strikes, const uint32_t *h_expiry_steps, const double *h_strikes,
@@ -99,40 +96,21 @@ int prepare_heston_smile(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_si
     if (!opt || !sim || !hs || !h_expiry_steps || !h_strikes)
         return fail(MCAMD_ERR_INVALID, "opt, sim, heston, h_expiry_steps and h_strikes must be non-NULL");
     if (int rc = check_heston_job(opt, hs)) return rc;
-    if (int rc = check_smile_nodes(n_expiries, n_strikes, h_expiry_steps, sim->n_steps, h_strikes)) return rc;
-    const double mu = opt->r - hs->q;
+    mcamd::HestonSmileJob job;
+    if (int rc = check_smile_nodes(n_expiries, n_strikes, h_expiry_steps, sim->n_steps, h_strikes, hs->payoff, &job.nodes))
+        return rc;
+    job.walk = heston_walk(opt, sim, hs);
     // as prepare_heston, on a copy that carries no strike of its own either
     mcamd_option seen = *opt;
     seen.B = 0.0;
     seen.K = 1.0;
-    if (int rc = check_drift_request("Heston smile", seen, sim, &mu, 1)) return rc;
+    if (int rc = check_drift_request("Heston smile", seen, sim, &job.walk.mu, 1)) return rc;
     if (!(opt->S0 > 0.0)) return fail(MCAMD_ERR_INVALID, "Heston smile options need S0 > 0 (S0 = %g)", opt->S0);
     if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
-    mcamd::HestonSmileJob job = {};
-    job.paths = path_range(sim);
     job.S0 = opt->S0;
-    job.mu = mu;
-    job.dt = even_dt(opt, sim);
-    job.v0 = hs->v0;
-    job.kappa = hs->kappa;
-    job.theta = hs->theta;
-    job.xi = hs->xi;
-    job.rho = hs->rho;
-    job.put = hs->payoff == MCAMD_PAYOFF_PUT;
-    job.n_expiries = n_expiries;
-    job.n_strikes = n_strikes;
-    std::copy(h_expiry_steps, h_expiry_steps + n_expiries, job.expiry_steps);
-    std::copy(h_strikes, h_strikes + n_strikes, job.strikes);
     job.d_state = d_state;
-    const uint64_t n = sim->n_paths_local;
-    const uint32_t last = job.expiry_steps[n_expiries - 1];
-    return drive(SmileCall{n, n ? mcamd::smile_grid(n, n_expiries, n_strikes, ctx->compute_units) : 0, n_expiries,
-                           n_strikes, opt->r, static_cast<double>(last) * job.dt, last,
-                           [](const void *j, double *d_partials, uint32_t grid, hipStream_t stream) {
-                               return mcamd::launch_heston_smile(*static_cast<const mcamd::HestonSmileJob *>(j),
-                                                                 d_partials, grid, stream);
-                           },
-                           &job});
+    return drive(make_smile_call(ctx, sim, job.nodes, opt->r, job.walk.dt,
+                                 smile_launch<mcamd::HestonSmileJob, mcamd::launch_heston_smile>, &job));
 }
 
 }  // namespace

@@ -20,6 +20,7 @@ int mcamd_set_error_(int code, const char *msg);
 
 namespace mcamd {
 struct AutocallSchedule;   // autocall.hpp
+struct SmileNodes;         // smile.hpp
 }
 
 #pragma GCC visibility push(hidden)
@@ -98,10 +99,11 @@ int check_localvol_grid(const mcamd_localvol_grid *grid, const double *h_sigma, 
 int check_cliquet_kind(int kind);
 int check_cliquet_local(double local_floor, double local_cap);
 int check_cliquet_kind_bounds(int kind, double local_floor, double local_cap);
-// what both smile families refuse of the nodes, in this order: n_expiries and n_strikes out of range, expiry steps that
-// are not strictly ascending in 1 .. n_steps, a strike that is not finite and > 0
+// capi_smile.cpp: what every smile call refuses of the nodes, in this order: n_expiries and n_strikes out of range,
+// expiry steps that are not strictly ascending in 1 .. n_steps, a strike that is not finite and > 0.  Nodes that pass
+// are left in *nodes, as a job carries them, with the payoff (checked by the caller) that holds for all of them.
 int check_smile_nodes(uint32_t n_expiries, uint32_t n_strikes, const uint32_t *h_expiry_steps, uint32_t n_steps,
-                      const double *h_strikes);
+                      const double *h_strikes, int payoff, mcamd::SmileNodes *nodes);
 // capi_heston.cpp
 int check_heston_model(double q, double v0, double kappa, double theta, double xi, double rho);
 // closed_forms.cpp
@@ -262,12 +264,9 @@ void finalize_record(const double *rec, bool control_variate, uint64_t n, double
 // a nested-MC record over n points: the mean point price is the scalar diagnostic of the wrappers
 void finalize_nmc_into(const double rec[kNmcRecord], uint64_t n, mcamd_result *res);
 void finalize_greeks_into(const double stats[16], double r, double T, int theta_defined, mcamd_greeks *out);
-// capi_localvol.cpp: value / std_err / sums of a (possibly all-reduced) 32-double local-volatility Greeks record ...
+// capi_localvol.cpp: value / std_err / sums of a (possibly all-reduced) 32-double local-volatility Greeks record
 void finalize_localvol_greeks_into(const double stats[32], double r, double T, uint32_t n_buckets, int gamma_defined,
                                    mcamd_localvol_greeks *out);
-// ... and price and standard error of every node of a smile from its 2 n_e n_K sums, each discounted to its own expiry
-void finalize_smile_into(const double *stats, uint64_t n, double r, double T, uint32_t n_steps, uint32_t n_e, uint32_t n_K,
-                         const uint32_t *expiry_steps, double *price, double *std_err);
 // capi_multi.cpp: fills *res from an autocall kernel's record: {sum, sumsq, paths called, sum of their call times,
 // paths not called and knocked in, wave-steps, live}
 void fill_autocall_result(const double *rec, uint64_t n, double r, double T, mcamd_autocall_result *res);
@@ -355,21 +354,32 @@ int run_enqueue(mcamd_ctx *ctx, const DeviceCall<Launch> &call, double *d_stats)
     return MCAMD_OK;
 }
 
-// ---- capi_localvol.cpp: the two drivers of the smile families -----------------------------------------------------------
+// ---- capi_smile.cpp: the smile layer, whatever model walks the paths ----------------------------------------------------
 
 // One smile call (mcamd_price_localvol_smile, mcamd_price_heston_smile) as its two drivers see it.  They are not
 // run_sync / run_enqueue: a smile is two kernels, its per-wavefront records are not the reported grid of sums, and a
 // record holds up to 4096 doubles where DeviceCall's fit the 32 of h_rec.  launch(job, d_partials, grid, stream) enqueues
-// the family's walk, which leaves grid x kSmileWavesPerBlock records; launch_smile_finish sums them for either family.
+// the model's walk, which leaves grid x kSmileWavesPerBlock records; launch_smile_finish sums them for every model.
+using SmileLaunch = hipError_t (*)(const void *job, double *d_partials, uint32_t grid, hipStream_t stream);
 struct SmileCall {
     uint64_t n;          // paths of the shard; 0: empty shard, nothing runs
     uint32_t grid;       // workgroups of the walk (smile_grid)
     uint32_t n_expiries, n_strikes;
     double r, t_last;    // what the last node is finalized with: the rate, and the time of the last expiry
     uint32_t last_step;  // the step of the last expiry: every wavefront that holds a path runs that many
-    hipError_t (*launch)(const void *job, double *d_partials, uint32_t grid, hipStream_t stream);
+    SmileLaunch launch;
     const void *job;
 };
+// a model's launcher of its own job type as a SmileLaunch
+template <typename Job, hipError_t (*Launch)(const Job &, double *, uint32_t, hipStream_t)>
+hipError_t smile_launch(const void *job, double *d_partials, uint32_t grid, hipStream_t stream)
+{
+    return Launch(*static_cast<const Job *>(job), d_partials, grid, stream);
+}
+// The call of a shard of sim->n_paths_local paths that stop at `nodes`, with steps of dt at the rate r: the grid is
+// smile_grid's, and an empty shard has n == 0 and grid == 0.  `job` must outlive the call.
+SmileCall make_smile_call(const mcamd_ctx *ctx, const mcamd_sim *sim, const mcamd::SmileNodes &nodes, double r, double dt,
+                          SmileLaunch launch, const void *job);
 // Synchronous: h_stats receives the 2 n_e n_K sums (zeros for an empty shard, which launches nothing) through the
 // context's pinned smile record, and *res (zeroed by the caller) the last node, the work and the timings: the walk runs
 // between ev0 and ev1, the sum of the records up to ev2.

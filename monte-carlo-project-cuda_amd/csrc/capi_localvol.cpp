@@ -1,7 +1,8 @@
 // capi_localvol.cpp — the calls of the C ABI that walk a local-volatility surface: the surface itself, European and
 // barrier options, cliquets and variance swaps, Greeks by tangent paths, the strike-by-expiry smile and the worst-of
 // autocallable on per-asset surfaces.  Each call is a prepare_* step (the refusals and the job) and its synchronous
-// and enqueue forms; the refusals keep one order: the request alone, then the surface, then the context.
+// and enqueue forms; the refusals keep one order: the request alone, then the surface, then the context.  What a smile
+// call is whatever the model (its nodes, its call, its two drivers) is capi_smile.cpp's.
 #include "capi_internal.hpp"
 #include "autocall_localvol.hpp"
 #include "cliquet.hpp"
@@ -9,7 +10,6 @@
 #include "localvol_greeks.hpp"
 #include "localvol_smile.hpp"
 
-#include <algorithm>
 #include <vector>
 
 static_assert(sizeof(mcamd_localvol_grid) == 24 && sizeof(mcamd_localvol) == 24,
@@ -24,9 +24,6 @@ static_assert(sizeof(mcamd_localvol_greeks_job) == 24 && sizeof(mcamd_localvol_g
               "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
 static_assert(MCAMD_LOCALVOL_GREEKS_MAX_BUCKETS == mcamd::kLvGreeksMaxBuckets && MCAMD_LOCALVOL_GREEK_RHO_Q + 1 == mcamd::kLvGreeks,
               "the kernel's record holds six estimators and MCAMD_LOCALVOL_GREEKS_MAX_BUCKETS buckets");
-static_assert(sizeof(mcamd_smile) == 24, "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
-static_assert(MCAMD_SMILE_MAX_STRIKES == mcamd::kSmileMaxStrikes && MCAMD_SMILE_MAX_EXPIRIES == mcamd::kSmileMaxExpiries,
-              "the smile kernel takes one strike per lane and MCAMD_SMILE_MAX_EXPIRIES expiry steps");
 static_assert(sizeof(mcamd_autocall_localvol) == 632, "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
 
 using namespace mcamd::capi;
@@ -115,101 +112,6 @@ void finalize_localvol_greeks_into(const double stats[32], double r, double T, u
         out->bucket_value[b] = e.value;
         out->bucket_std_err[b] = e.std_err;
     }
-}
-
-int check_smile_nodes(uint32_t n_expiries, uint32_t n_strikes, const uint32_t *h_expiry_steps, uint32_t n_steps,
-                      const double *h_strikes)
-{
-    if (n_expiries < 1 || n_expiries > MCAMD_SMILE_MAX_EXPIRIES)
-        return fail(MCAMD_ERR_INVALID, "n_expiries must lie in 1 .. %d, got %u", MCAMD_SMILE_MAX_EXPIRIES, n_expiries);
-    if (n_strikes < 1 || n_strikes > MCAMD_SMILE_MAX_STRIKES)
-        return fail(MCAMD_ERR_INVALID, "n_strikes must lie in 1 .. %d, got %u", MCAMD_SMILE_MAX_STRIKES, n_strikes);
-    for (uint32_t m = 0; m < n_expiries; ++m) {
-        const uint32_t before = m ? h_expiry_steps[m - 1] : 0;
-        if (h_expiry_steps[m] <= before || h_expiry_steps[m] > n_steps)
-            return fail(MCAMD_ERR_INVALID, "expiry steps must be strictly ascending in 1 .. n_steps = %u: "
-                                           "h_expiry_steps[%u] = %u", n_steps, m, h_expiry_steps[m]);
-    }
-    for (uint32_t k = 0; k < n_strikes; ++k)
-        if (!std::isfinite(h_strikes[k]) || !(h_strikes[k] > 0.0))
-            return fail(MCAMD_ERR_INVALID, "every strike must be finite and > 0: h_strikes[%u] = %g", k, h_strikes[k]);
-    return MCAMD_OK;
-}
-
-void finalize_smile_into(const double *stats, uint64_t n, double r, double T, uint32_t n_steps, uint32_t n_e, uint32_t n_K,
-                         const uint32_t *expiry_steps, double *price, double *std_err)
-{
-    const uint32_t nodes = n_e * n_K;
-    const double dt = T / static_cast<double>(n_steps);
-    for (uint32_t m = 0; m < n_e; ++m) {
-        const double disc = std::exp(-r * (static_cast<double>(expiry_steps[m]) * dt));
-        for (uint32_t k = 0; k < n_K; ++k) {
-            const Estimate e = estimate(stats[m * n_K + k], stats[nodes + m * n_K + k], n, disc);
-            if (price) price[m * n_K + k] = e.value;
-            if (std_err) std_err[m * n_K + k] = e.std_err;
-        }
-    }
-}
-
-namespace {
-
-// A smile's two launches on the context's stream: the walk into the per-wavefront records, then their sum into out.
-int launch_smile_pair(mcamd_ctx *ctx, const SmileCall &call, double *out, double n_value, hipEvent_t before,
-                      hipEvent_t after)
-{
-    HIP_TRY(hipEventRecord(before, ctx->stream));
-    HIP_TRY(call.launch(call.job, ctx->d_partials, call.grid, ctx->stream));
-    HIP_TRY(hipEventRecord(after, ctx->stream));
-    HIP_TRY(mcamd::launch_smile_finish(ctx->d_partials, call.grid * mcamd::kSmileWavesPerBlock,
-                                       call.n_expiries * call.n_strikes, out, n_value, ctx->stream));
-    return MCAMD_OK;
-}
-
-}  // namespace
-
-int run_smile_sync(mcamd_ctx *ctx, const SmileCall &call, double *h_stats, mcamd_result *res)
-{
-    const uint32_t nodes = call.n_expiries * call.n_strikes, n_stats = 2 * nodes;
-    std::fill(h_stats, h_stats + n_stats, 0.0);
-    if (call.n == 0) return MCAMD_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (!ctx->h_smile) {
-        HIP_TRY(hipHostMalloc(&ctx->h_smile, mcamd_ctx::kSmileStats * sizeof(double), hipHostMallocDefault));
-        HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&ctx->h_smile_dev), ctx->h_smile, 0));
-    }
-    if (int rc = ensure_partials(ctx, call.grid * mcamd::kSmileWavesPerBlock, static_cast<int>(n_stats))) return rc;
-    // the finishing kernel writes the pinned buffer itself; all-ones bits there afterwards mean it never ran
-    arm_record(ctx->h_smile, static_cast<int>(n_stats));
-    if (int rc = launch_smile_pair(ctx, call, ctx->h_smile_dev, -1.0, ctx->ev0, ctx->ev1)) return rc;
-    HIP_TRY(hipEventRecord(ctx->ev2, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    float kernel_ms = 0.0f, total_ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&kernel_ms, ctx->ev0, ctx->ev1));
-    HIP_TRY(hipEventElapsedTime(&total_ms, ctx->ev0, ctx->ev2));
-    if (record_unwritten(ctx->h_smile, static_cast<int>(n_stats)))
-        return fail(MCAMD_ERR_HIP, "the smile kernels left no result (the finishing kernel did not write every node)");
-    std::memcpy(h_stats, ctx->h_smile, n_stats * sizeof(double));
-    finalize_into(h_stats[nodes - 1], h_stats[n_stats - 1], call.n, call.r, call.t_last, res);
-    res->work_steps = 64.0 * static_cast<double>((call.n + 63) / 64) * static_cast<double>(call.last_step);
-    res->live_steps = res->work_steps;
-    res->kernel_ms = kernel_ms;
-    res->total_ms = total_ms;
-    res->grid = call.grid;
-    res->block = mcamd::kBlockThreads;
-    return MCAMD_OK;
-}
-
-int run_smile_enqueue(mcamd_ctx *ctx, const SmileCall &call, double *d_stats)
-{
-    const uint32_t n_stats = 2 * call.n_expiries * call.n_strikes;
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (call.n == 0) return enqueue_empty_shard(ctx, d_stats, n_stats + 1);
-    const uint32_t slot = static_cast<uint32_t>(ctx->n_enqueued % mcamd_ctx::kRing);
-    if (int rc = ensure_partials_enqueued(ctx, call.grid * mcamd::kSmileWavesPerBlock, static_cast<int>(n_stats))) return rc;
-    if (int rc = launch_smile_pair(ctx, call, d_stats, static_cast<double>(call.n), ctx->ring0[slot], ctx->ring1[slot]))
-        return rc;
-    ctx->n_enqueued++;
-    return MCAMD_OK;
 }
 
 }  // namespace mcamd::capi
@@ -406,8 +308,8 @@ int prepare_localvol_greeks(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd
 
 // The smile calls: mcamd_price_localvol's paths without a barrier, stopped at the expiry steps, every strike priced at
 // every expiry.  The refusals follow prepare_localvol's order: the request alone, then the surface, then the context.
-// drive(call) runs the form's driver (run_smile_sync, run_smile_enqueue: capi_internal.hpp explains why a smile has
-// drivers of its own); call.n == 0 is the empty shard.  opt->v and opt->K are ignored.
+// drive(call) runs the form's driver (run_smile_sync, run_smile_enqueue of capi_smile.cpp: capi_internal.hpp explains why
+// a smile has drivers of its own); call.n == 0 is the empty shard.  opt->v and opt->K are ignored.
 template <typename Drive>
 int prepare_smile(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_smile *sm,
                   const uint32_t *h_expiry_steps, const double *h_strikes, const mcamd_localvol_surface *surface,
@@ -417,33 +319,23 @@ int prepare_smile(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
         return fail(MCAMD_ERR_INVALID, "opt, sim, smile, h_expiry_steps, h_strikes and surface must be non-NULL");
     if (int rc = check_payoff(sm->payoff)) return rc;
     if (sm->reserved != 0) return fail(MCAMD_ERR_INVALID, "smile->reserved must be 0, got %d", sm->reserved);
-    if (int rc = check_smile_nodes(sm->n_expiries, sm->n_strikes, h_expiry_steps, sim->n_steps, h_strikes)) return rc;
+    mcamd::SmileJob job;
+    if (int rc = check_smile_nodes(sm->n_expiries, sm->n_strikes, h_expiry_steps, sim->n_steps, h_strikes, sm->payoff,
+                                   &job.nodes))
+        return rc;
     // as prepare_localvol, on a copy that carries no strike of its own either
     mcamd_option seen = *opt;
     seen.K = 1.0;
     double mu;
     if (int rc = check_walk_drift("local-volatility smile", seen, sim, sm->q, &mu)) return rc;
     if (!(opt->S0 > 0.0)) return fail(MCAMD_ERR_INVALID, "local-volatility smile options need S0 > 0 (S0 = %g)", opt->S0);
-    mcamd::SmileJob job = {};
     if (int rc = make_walk("opt, sim, smile, h_expiry_steps, h_strikes and surface must be non-NULL", ctx, surface, mu, opt,
                            sim, 0.0, &job.walk))
         return rc;
     job.S0 = opt->S0;
-    job.put = sm->payoff == MCAMD_PAYOFF_PUT;
-    job.n_expiries = sm->n_expiries;
-    job.n_strikes = sm->n_strikes;
-    std::copy(h_expiry_steps, h_expiry_steps + sm->n_expiries, job.expiry_steps);
-    std::copy(h_strikes, h_strikes + sm->n_strikes, job.strikes);
     job.d_spots = d_spots;
-    const uint64_t n = sim->n_paths_local;
-    const uint32_t last = job.expiry_steps[job.n_expiries - 1];
-    return drive(SmileCall{n, n ? mcamd::smile_grid(n, job.n_expiries, job.n_strikes, ctx->compute_units) : 0,
-                           job.n_expiries, job.n_strikes, opt->r, static_cast<double>(last) * job.walk.dt, last,
-                           [](const void *j, double *d_partials, uint32_t grid, hipStream_t stream) {
-                               return mcamd::launch_localvol_smile(*static_cast<const mcamd::SmileJob *>(j), d_partials,
-                                                                   grid, stream);
-                           },
-                           &job});
+    return drive(make_smile_call(ctx, sim, job.nodes, opt->r, job.walk.dt,
+                                 smile_launch<mcamd::SmileJob, mcamd::launch_localvol_smile>, &job));
 }
 
 // The autocall calls under per-asset local-volatility surfaces.  Every refusal that needs neither a surface nor the

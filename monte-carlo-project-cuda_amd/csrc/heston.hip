@@ -79,15 +79,15 @@ static hipError_t launch_heston_t(const HestonJob &j, double *d_partials, uint32
                                   hipStream_t stream)
 {
     HestonArgs<T> a;
-    a.c = heston_consts<T>(j.mu, j.dt, j.kappa, j.theta, j.xi, j.rho);
+    a.c = heston_consts<T>(j.walk);
     a.exp_scale = heston_exp_scale<T>();
-    a.v0 = static_cast<T>(j.v0);
+    a.v0 = static_cast<T>(j.walk.v0);
     a.K = static_cast<T>(j.K);
     a.S0 = static_cast<T>(j.S0);
-    a.inv_n = 1.0 / static_cast<double>(j.paths.n_steps);
+    a.inv_n = 1.0 / static_cast<double>(j.walk.paths.n_steps);
     a.put = j.put ? 1 : 0;
-    a.n_steps = j.paths.n_steps;
-    a.shard = shard_of(j.paths);
+    a.n_steps = j.walk.paths.n_steps;
+    a.shard = shard_of(j.walk.paths);
     a.samples = static_cast<T *>(j.d_samples);
     a.state = static_cast<T *>(j.d_state);
     a.fin = grid_finish_of(fs);
@@ -99,8 +99,9 @@ hipError_t launch_heston(const HestonJob &job, double *d_partials, uint32_t grid
                          hipStream_t stream)
 {
     if (!finish_ok(finish, grid)) return hipErrorInvalidValue;
-    if (job.scheme != kHestonFullTruncation || job.paths.n_steps == 0 || job.paths.n_local == 0) return hipErrorInvalidValue;
-    return dispatch_precision(job.paths.precision, [&](auto p) {
+    const PathRange &paths = job.walk.paths;
+    if (job.scheme != kHestonFullTruncation || paths.n_steps == 0 || paths.n_local == 0) return hipErrorInvalidValue;
+    return dispatch_precision(paths.precision, [&](auto p) {
         return launch_heston_t<typename decltype(p)::type>(job, d_partials, grid, finish, stream);
     });
 }

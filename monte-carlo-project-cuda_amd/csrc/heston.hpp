@@ -14,13 +14,18 @@ namespace mcamd {
 constexpr int kHestonRecord = 4;
 constexpr int kHestonFullTruncation = 0;   // MCAMD_HESTON_FULL_TRUNCATION
 
-struct HestonJob {
+// What every job that walks Heston paths carries: the paths, the drift, the step and the model.
+struct HestonWalk {
     PathRange paths;
-    int scheme;          // kHestonFullTruncation
-    double S0, K;
     double mu;           // r - q
     double dt;           // T / n_steps
     double v0, kappa, theta, xi, rho;
+};
+
+struct HestonJob {
+    HestonWalk walk;
+    int scheme;          // kHestonFullTruncation
+    double S0, K;
     bool put;            // h(S) = (K - S)+ (else (S - K)+)
     void *d_samples;     // nullable: n_local samples of the path precision
     void *d_state;       // nullable: 2 n_local values of the path precision, S_T then the raw v_n

@@ -17,6 +17,7 @@
 // distribution function — so two precisions of one path never take different formulas.
 #pragma once
 
+#include "heston.hpp"
 #include "mc_device.hpp"
 
 namespace mcamd {
@@ -38,20 +39,20 @@ struct HestonConsts {
     T rho_c;            // sqrt(1 - rho^2): 0 at rho = +-1
 };
 
-// Host: the constants of a step of dt at the drift mu = r - q, as every launcher of these paths forms them ...
+// Host: the constants of a walk's step, as every launcher of these paths forms them ...
 template <typename T>
-inline HestonConsts<T> heston_consts(double mu, double dt, double kappa, double theta, double xi, double rho)
+inline HestonConsts<T> heston_consts(const HestonWalk &w)
 {
-    const double sqrt_dt = std::sqrt(dt);
+    const double sqrt_dt = std::sqrt(w.dt);
     HestonConsts<T> c;
-    c.mu_dt = static_cast<T>(mu * dt);
-    c.half_dt = static_cast<T>(0.5 * dt);
+    c.mu_dt = static_cast<T>(w.mu * w.dt);
+    c.half_dt = static_cast<T>(0.5 * w.dt);
     c.sqrt_dt = static_cast<T>(sqrt_dt);
-    c.kappa_dt = static_cast<T>(kappa * dt);
-    c.kappa_theta_dt = static_cast<T>(kappa * theta * dt);
-    c.xi_sqrt_dt = static_cast<T>(xi * sqrt_dt);
-    c.rho = static_cast<T>(rho);
-    c.rho_c = static_cast<T>(std::sqrt(1.0 - rho * rho));
+    c.kappa_dt = static_cast<T>(w.kappa * w.dt);
+    c.kappa_theta_dt = static_cast<T>(w.kappa * w.theta * w.dt);
+    c.xi_sqrt_dt = static_cast<T>(w.xi * sqrt_dt);
+    c.rho = static_cast<T>(w.rho);
+    c.rho_c = static_cast<T>(std::sqrt(1.0 - w.rho * w.rho));
     return c;
 }
 // ... and the exponent units per natural-log unit of the exponential that ends a path (exp_of_logreturn): log2 e in

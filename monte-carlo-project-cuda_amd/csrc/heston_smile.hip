@@ -6,13 +6,13 @@
 // is S_m = exp_of_logreturn(S0, X_{s_m} exp_scale), as heston.hip forms S_T, and the variance of expiry m is the raw
 // v_{s_m}.
 //
-// Walk phase, as localvol_smile.hip's: one path per lane.  The next expiry step is wave-uniform and lives in a scalar
+// Walk phase: one path per lane.  The next expiry step is wave-uniform and lives in a scalar
 // register; a block of the walk (two Philox blocks, two Box-Muller fills, as in heston.hip) that holds no expiry runs the
 // plain unrolled steps, one that holds an expiry (or the end) tests every step.
-// Strike phase (smile_device.hpp, shared with localvol_smile.hip): at an expiry the wavefront holds 64 spots, one per
-// lane; lane k holds strike k, runs over the wavefront's valid paths and adds sum h and sum h^2 of node (m, k) to its
-// own 16-byte entry of the wavefront's private record [m][k] in global memory.
-// Finish: localvol_smile.hip's smile_finish_kernel.  The record holds node sums only: the truncated steps and the
+// Strike phase (smile_device.hpp, shared by every model's smile kernel): at an expiry the wavefront holds 64 spots, one
+// per lane; lane k holds strike k, runs over the wavefront's valid paths and adds sum h and sum h^2 of node (m, k) to
+// its own 16-byte entry of the wavefront's private record [m][k] in global memory.
+// Finish: smile.hip's smile_finish_kernel.  The record holds node sums only: the truncated steps and the
 // average variance of these paths are mcamd_price_heston's to report.
 #include "heston_smile.hpp"
 #include "heston_device.hpp"
@@ -109,18 +109,13 @@ template <typename T>
 static hipError_t launch_heston_smile_t(const HestonSmileJob &j, double *d_partials, uint32_t grid, hipStream_t stream)
 {
     HestonSmileArgs<T> a;
-    a.c = heston_consts<T>(j.mu, j.dt, j.kappa, j.theta, j.xi, j.rho);
+    a.c = heston_consts<T>(j.walk);
     a.exp_scale = heston_exp_scale<T>();
-    a.v0 = static_cast<T>(j.v0);
+    a.v0 = static_cast<T>(j.walk.v0);
     a.S0 = static_cast<T>(j.S0);
-    a.put = j.put ? 1 : 0;
-    a.n_expiries = j.n_expiries;
-    a.n_strikes = j.n_strikes;
-    a.last_step = j.expiry_steps[j.n_expiries - 1];
-    a.shard = shard_of(j.paths);
+    smile_node_args<T>(a, j.nodes);
+    a.shard = shard_of(j.walk.paths);
     a.state = static_cast<T *>(j.d_state);
-    for (uint32_t m = 0; m < kSmileMaxExpiries; ++m) a.expiry_steps[m] = m < j.n_expiries ? j.expiry_steps[m] : 0xFFFFFFFFu;
-    for (uint32_t k = 0; k < kSmileMaxStrikes; ++k) a.strikes[k] = k < j.n_strikes ? static_cast<T>(j.strikes[k]) : T(0);
     hipLaunchKernelGGL((heston_smile_kernel<T>), dim3(grid), dim3(kBlock), 0, stream, a, d_partials);
     return hipGetLastError();
 }
@@ -128,14 +123,9 @@ static hipError_t launch_heston_smile_t(const HestonSmileJob &j, double *d_parti
 hipError_t launch_heston_smile(const HestonSmileJob &job, double *d_partials, uint32_t grid, hipStream_t stream)
 {
     if (!d_partials || grid == 0 || grid > kFoldMaxRecords) return hipErrorInvalidValue;
-    if (job.paths.n_steps == 0 || job.paths.n_local == 0) return hipErrorInvalidValue;
-    if (job.n_expiries < 1 || job.n_expiries > kSmileMaxExpiries || job.n_strikes < 1 || job.n_strikes > kSmileMaxStrikes)
-        return hipErrorInvalidValue;
-    for (uint32_t m = 0; m < job.n_expiries; ++m) {
-        const uint32_t lo = m ? job.expiry_steps[m - 1] : 0;
-        if (job.expiry_steps[m] <= lo || job.expiry_steps[m] > job.paths.n_steps) return hipErrorInvalidValue;
-    }
-    return dispatch_precision(job.paths.precision, [&](auto p) {
+    if (job.walk.paths.n_steps == 0 || job.walk.paths.n_local == 0) return hipErrorInvalidValue;
+    if (!smile_nodes_ok(job.nodes, job.walk.paths.n_steps)) return hipErrorInvalidValue;
+    return dispatch_precision(job.walk.paths.precision, [&](auto p) {
         return launch_heston_smile_t<typename decltype(p)::type>(job, d_partials, grid, stream);
     });
 }

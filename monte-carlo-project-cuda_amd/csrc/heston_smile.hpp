@@ -1,28 +1,21 @@
 // heston_smile.hpp — host-side interface of the Heston smile kernels (heston_smile.hip) for the C ABI (capi_heston.cpp).
 //
 // A Heston smile kernel walks mcamd_price_heston's paths (the step of heston_device.hpp on the same two Philox streams),
-// stops at up to 32 expiry steps and there runs the strike phase of the local-volatility smile (smile_device.hpp): every
-// lane of a wavefront takes one strike and runs over the wavefront's 64 spots, so a path set serves n_e x n_K vanillas
-// (include/mcamd.h, mcamd_price_heston_smile).  The per-wavefront records, their sum (launch_smile_finish), the limits
-// and the launch shape (smile_grid) are those of localvol_smile.hpp.  A record holds node sums only: the scheme's
-// diagnostics (truncated steps, average variance) are mcamd_price_heston's, on the same paths.
+// stops at the expiry steps and there runs the strike phase of smile_device.hpp, so a path set serves n_e x n_K
+// vanillas (include/mcamd.h, mcamd_price_heston_smile).  The nodes, the per-wavefront records, their sum
+// (launch_smile_finish), the limits and the launch shape (smile_grid) are smile.hpp's.  A record holds node sums only:
+// the scheme's diagnostics (truncated steps, average variance) are mcamd_price_heston's, on the same paths.
 #pragma once
 
 #include "heston.hpp"
-#include "localvol_smile.hpp"
+#include "smile.hpp"
 
 namespace mcamd {
 
 struct HestonSmileJob {
-    PathRange paths;
+    HestonWalk walk;     // dt = T / n_steps, over the WHOLE n_steps
     double S0;
-    double mu;           // r - q
-    double dt;           // T / n_steps, over the WHOLE n_steps
-    double v0, kappa, theta, xi, rho;
-    bool put;            // h(S) = (K - S)+ at every node (else (S - K)+)
-    uint32_t n_expiries, n_strikes;
-    uint32_t expiry_steps[kSmileMaxExpiries];   // strictly ascending, 1 .. n_steps
-    double strikes[kSmileMaxStrikes];
+    SmileNodes nodes;
     void *d_state;       // nullable: 2 n_expiries x n_local values of the path precision: the spots expiry-major, then
                          // the raw variances expiry-major
 };

@@ -11,7 +11,7 @@
 // Strike phase (smile_device.hpp, shared with heston_smile.hip): at an expiry the wavefront holds 64 spots, one per lane;
 // lane k holds strike k, runs over the wavefront's valid paths and adds sum h and sum h^2 of node (m, k) to its own
 // 16-byte entry of the wavefront's private record [m][k] in global memory.
-// Finish: smile_finish_kernel, one thread per node, sums the entries over the wavefronts in index order.
+// Finish: smile.hip's smile_finish_kernel, one thread per node, sums the entries over the wavefronts in index order.
 #include "localvol_smile.hpp"
 #include "localvol_device.hpp"
 #include "smile_device.hpp"
@@ -108,37 +108,14 @@ __global__ __launch_bounds__(kBlock) void smile_kernel(SmileArgs<T> args, double
     }
 }
 
-// One thread per node: the node's entries over the wavefronts, in index order (adjacent threads read adjacent entries).
-__global__ __launch_bounds__(kBlock) void smile_finish_kernel(const SmileEntry *__restrict__ rec, uint32_t n_waves,
-                                                              uint32_t n_nodes, double *__restrict__ out, double n_value)
-{
-    const uint32_t node = blockIdx.x * kBlock + threadIdx.x;
-    if (node >= n_nodes) return;
-    double sum = 0.0, sumsq = 0.0;
-#pragma unroll 8
-    for (uint32_t w = 0; w < n_waves; ++w) {
-        const SmileEntry e = rec[static_cast<uint64_t>(w) * n_nodes + node];
-        sum += e.sum;
-        sumsq += e.sumsq;
-    }
-    out[node] = sum;
-    out[n_nodes + node] = sumsq;
-    if (node == 0 && n_value >= 0.0) out[2 * n_nodes] = n_value;
-}
-
 template <typename T>
 static hipError_t launch_smile_t(const SmileJob &j, double *d_partials, uint32_t grid, hipStream_t stream)
 {
     SmileArgs<T> a;
     lv_walk_args<T>(a, j.walk);
     a.S0 = static_cast<T>(j.S0);
-    a.put = j.put ? 1 : 0;
-    a.n_expiries = j.n_expiries;
-    a.n_strikes = j.n_strikes;
-    a.last_step = j.expiry_steps[j.n_expiries - 1];
+    smile_node_args<T>(a, j.nodes);
     a.spots = static_cast<T *>(j.d_spots);
-    for (uint32_t m = 0; m < kSmileMaxExpiries; ++m) a.expiry_steps[m] = m < j.n_expiries ? j.expiry_steps[m] : 0xFFFFFFFFu;
-    for (uint32_t k = 0; k < kSmileMaxStrikes; ++k) a.strikes[k] = k < j.n_strikes ? static_cast<T>(j.strikes[k]) : T(0);
     const size_t lds_bytes = static_cast<size_t>(a.surf.rows.n_entries) * sizeof(VolPair<T>);
     hipLaunchKernelGGL((smile_kernel<T>), dim3(grid), dim3(kBlock), lds_bytes, stream, a, d_partials);
     return hipGetLastError();
@@ -148,24 +125,9 @@ hipError_t launch_localvol_smile(const SmileJob &job, double *d_partials, uint32
 {
     if (!d_partials || grid == 0 || grid > kFoldMaxRecords) return hipErrorInvalidValue;
     if (!lv_grid_ok(job.walk.surface, job.walk.paths.n_steps)) return hipErrorInvalidValue;
-    if (job.n_expiries < 1 || job.n_expiries > kSmileMaxExpiries || job.n_strikes < 1 || job.n_strikes > kSmileMaxStrikes)
-        return hipErrorInvalidValue;
-    for (uint32_t m = 0; m < job.n_expiries; ++m) {
-        const uint32_t lo = m ? job.expiry_steps[m - 1] : 0;
-        if (job.expiry_steps[m] <= lo || job.expiry_steps[m] > job.walk.paths.n_steps) return hipErrorInvalidValue;
-    }
+    if (!smile_nodes_ok(job.nodes, job.walk.paths.n_steps)) return hipErrorInvalidValue;
     return job.walk.paths.precision == 32 ? launch_smile_t<float>(job, d_partials, grid, stream)
                                : launch_smile_t<double>(job, d_partials, grid, stream);
-}
-
-hipError_t launch_smile_finish(const double *d_partials, uint32_t n_waves, uint32_t n_nodes, double *out, double n_value,
-                               hipStream_t stream)
-{
-    if (!d_partials || !out || n_waves == 0 || n_nodes == 0) return hipErrorInvalidValue;
-    const uint32_t grid = (n_nodes + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(smile_finish_kernel, dim3(grid), dim3(kBlock), 0, stream,
-                       reinterpret_cast<const SmileEntry *>(d_partials), n_waves, n_nodes, out, n_value);
-    return hipGetLastError();
 }
 
 }  // namespace mcamd

@@ -8,8 +8,8 @@
 // to its own 16-byte entry of the wavefront's private record [m][k] in global memory — a plain read-modify-write that
 // only this lane of this wavefront ever touches, in program order; the first trip of a wavefront writes instead of
 // adding (its old value is taken as 0 and the entry is not read), and a wavefront without any path writes zeros, so
-// every entry of every record is written whatever the buffer held.  smile_finish_kernel (localvol_smile.hip), one
-// thread per node, sums the entries over the wavefronts in index order.
+// every entry of every record is written whatever the buffer held.  smile_finish_kernel (smile.hip), one thread per
+// node, sums the entries over the wavefronts in index order.  The host side of a smile is smile.hpp.
 #pragma once
 
 #include "mc_device.hpp"

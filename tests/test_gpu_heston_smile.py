@@ -48,6 +48,7 @@ import heston_restate as hr
 import heston_smile_restate as hs
 import localvol_smile_restate as sm
 from deep_inputs import DEEP, SHALLOW
+from smile_cases import SUM_RTOL, check_result_fields, check_sums_from_spots, full_work, strikes_for
 
 pytestmark = pytest.mark.gpu
 
@@ -58,7 +59,6 @@ S0, T_, R, Q = hr.S0, hr.T_, hr.R, hr.Q_DIV
 NP_T = {capi.F64: np.float64, capi.F32: np.float32}
 WIDER = {capi.F64: np.longdouble, capi.F32: np.float64}
 FLOOR = {capi.F64: {"S": 1e-11 * S0, "v": 1e-11}, capi.F32: {"S": 2e-3, "v": 2e-5}}
-SUM_RTOL = {capi.F64: 1e-11, capi.F32: 2e-5}
 SHARD_RTOL = 1e-13
 PRECS = [capi.F64, capi.F32]
 PAYOFFS = [capi.PAYOFF_CALL, capi.PAYOFF_PUT]
@@ -77,11 +77,6 @@ def option():
 def model(name, payoff=capi.PAYOFF_CALL, **changes):
     q, v0, kappa, theta, xi, rho = hr.params(name, **changes)
     return capi.make_heston(payoff, q, v0, kappa, theta, xi, rho)
-
-
-def strikes_for(n_K):
-    """from deep in to deep out of the money: a call at 2000 and a put at 5 never pay, the other end always does"""
-    return [100.0] if n_K == 1 else list(np.geomspace(5.0, 2000.0, n_K))
 
 
 _restated = {}
@@ -190,34 +185,6 @@ def shard(prec, case, n=N_LOCAL):
     return capi.make_sim(n_job, n_steps, prec, seed=seed, path_offset=first, n_paths_local=n)
 
 
-def full_work(n, last):
-    return 64 * -(-n // 64) * last
-
-
-def check_result_fields(res, stats, n, steps, n_K, n_steps):
-    nodes = len(steps) * n_K
-    assert res.n == n and res.block == 256 and res.work_steps == res.live_steps == full_work(n, steps[-1])
-    assert (res.sum, res.sumsq) == (stats[nodes - 1], stats[2 * nodes - 1])
-    fin = capi.finalize(res.sum, res.sumsq, n, R, steps[-1] * (T_ / n_steps))
-    assert (res.price, res.std_err, res.ci_lo, res.ci_hi) == (fin.price, fin.std_err, fin.ci_lo, fin.ci_hi)
-    assert res.sum_c == res.sum_cc == res.sum_yc == res.cv_beta == res.cv_rho == 0.0
-    assert 0.0 < res.kernel_ms < 1e4 and 0.0 < res.total_ms < 1e4
-
-
-def check_sums_from_spots(prec, spots, strikes, payoff, stats, tag="", threads=1):
-    """the strike phase alone: node sums against sums formed in numpy from the returned spots"""
-    nodes = spots.shape[0] * len(strikes)
-    want, wantsq, paying = sm.node_sums(spots, strikes, payoff, threads=threads)
-    got, gotsq = stats[:nodes].reshape(want.shape), stats[nodes:].reshape(want.shape)
-    rt = SUM_RTOL[prec]
-    worst = float(np.max(np.abs(got - want) / np.where(want > 0, want, 1.0)))
-    print(f"{tag}: worst relative deviation of a node sum {worst:.3e}, nodes that never pay {(want == 0).sum()}, "
-          f"nodes where every path pays {(paying == spots.shape[1]).sum()}")
-    assert (np.abs(got - want) <= rt * want).all() and (np.abs(gotsq - wantsq) <= rt * wantsq).all()
-    assert (got[want == 0] == 0).all() and (gotsq[want == 0] == 0).all()
-    return want, paying
-
-
 # ---- 1. spots and variances against the restatement -----------------------------------------------------------------------
 
 @pytest.mark.parametrize("case", list(CASES))
@@ -240,7 +207,7 @@ def test_spots_and_variances_against_the_restatement(ctx, name, prec, case):
         assert (got_v < 0).any()   # the raw variance
     if case == "C":
         assert (got_v != hr.MODELS[name][0]).all()
-    check_result_fields(res, stats, N_LOCAL, steps, len(strikes), n_steps)
+    check_result_fields(res, stats, N_LOCAL, steps, len(strikes), n_steps, R, T_)
     check_sums_from_spots(prec, S, strikes, capi.PAYOFF_CALL, stats, f"{name} fp{prec} case {case}")
     want_price, want_se = sm.finalize(stats, N_LOCAL, R, T_, n_steps, steps, len(strikes))
     assert np.allclose(price, want_price, rtol=1e-13, atol=0) and np.allclose(se, want_se, rtol=1e-9, atol=0)
@@ -278,7 +245,7 @@ def test_node_sums_from_the_returned_spots(ctx, prec, payoff, n_e, n_K):
                                              f"({n_e}, {n_K}) payoff {payoff} fp{prec} n {n}")
         if n_K > 1:
             assert (want == 0).any() and (paying == n).any()
-        check_result_fields(res, stats, n, steps, n_K, STRIKE_STEPS)
+        check_result_fields(res, stats, n, steps, n_K, STRIKE_STEPS, R, T_)
         # what the scratch buffer held before plays no part
         pollute(ctx, sim, payoff, steps, strikes)
         _, _, again, _, S_again, v_again = run(ctx, sim, model("F", payoff), steps, strikes)
@@ -297,7 +264,7 @@ def test_wavefronts_that_make_several_trips(ctx, prec):
     _, _, stats, res, S, _ = run(ctx, sim, model("F"), steps, strikes)
     assert res.grid == first.grid and np.isfinite(S).all()
     check_sums_from_spots(prec, S, strikes, payoff, stats, f"several trips fp{prec} grid {res.grid} n {n}", threads=8)
-    check_result_fields(res, stats, n, steps, 64, STRIKE_STEPS)
+    check_result_fields(res, stats, n, steps, 64, STRIKE_STEPS, R, T_)
     pollute(ctx, sim, payoff, steps, strikes)
     again = run(ctx, sim, model("F"), steps, strikes, False)[2]
     assert np.array_equal(again, stats)

@@ -40,6 +40,7 @@ import pytest
 
 import localvol_smile_restate as sm
 from deep_inputs import DEEP, DEEP_SEED, OFFSET, SHALLOW, check_deep_draws_differ
+from smile_cases import SUM_RTOL, check_result_fields, check_sums_from_spots, strikes_for
 
 pytestmark = pytest.mark.gpu
 
@@ -48,7 +49,6 @@ capi = pkg.capi
 
 NP_T = {capi.F64: np.float64, capi.F32: np.float32}
 WIDER = {capi.F64: np.longdouble, capi.F32: np.float64}
-SUM_RTOL = {capi.F64: 1e-11, capi.F32: 2e-5}
 FLAT_INNER_RTOL = {capi.F64: 1e-9, capi.F32: 2e-5}
 BASE = dict(S0=100.0, r=0.1, T=1.0)
 Q_DIV = 0.03
@@ -81,11 +81,6 @@ SPOT_CASES = [("skew", SHALLOW, 50, EVERY_SLOT), ("skew", DEEP, 7, (3, 6)), ("sk
 def option():
     # v and K are ignored by the call: leave something in them that any use would show
     return capi.make_option(**dict(BASE, v=float("nan"), K=float("nan")))
-
-
-def strikes_for(n_K):
-    """from deep in to deep out of the money: a call at 2000 and a put at 5 never pay, the other end always does"""
-    return [100.0] if n_K == 1 else list(np.geomspace(5.0, 2000.0, n_K))
 
 
 _normals = {}
@@ -223,34 +218,6 @@ def run(ctx, sim, payoff, steps, strikes, surface, want_spots=True, opt=None):
     return price, se, stats, res, spots
 
 
-def full_work(n, last):
-    return 64 * -(-n // 64) * last
-
-
-def check_result_fields(res, stats, n, steps, n_K, n_steps):
-    nodes = len(steps) * n_K
-    assert res.n == n and res.block == 256 and res.work_steps == res.live_steps == full_work(n, steps[-1])
-    assert (res.sum, res.sumsq) == (stats[nodes - 1], stats[2 * nodes - 1])
-    fin = capi.finalize(res.sum, res.sumsq, n, BASE["r"], steps[-1] * (BASE["T"] / n_steps))
-    assert (res.price, res.std_err, res.ci_lo, res.ci_hi) == (fin.price, fin.std_err, fin.ci_lo, fin.ci_hi)
-    assert res.sum_c == res.sum_cc == res.sum_yc == res.cv_beta == res.cv_rho == 0.0
-    assert 0.0 < res.kernel_ms < 1e4 and 0.0 < res.total_ms < 1e4
-
-
-def check_sums_from_spots(prec, spots, strikes, payoff, stats, tag="", threads=1):
-    """the strike phase alone: node sums against sums formed in numpy from the returned spots"""
-    nodes = spots.shape[0] * len(strikes)
-    want, wantsq, paying = sm.node_sums(spots, strikes, payoff, threads=threads)
-    got, gotsq = stats[:nodes].reshape(want.shape), stats[nodes:].reshape(want.shape)
-    rt = SUM_RTOL[prec]
-    worst = float(np.max(np.abs(got - want) / np.where(want > 0, want, 1.0)))
-    print(f"{tag}: worst relative deviation of a node sum {worst:.3e}, nodes that never pay {(want == 0).sum()}, "
-          f"nodes where every path pays {(paying == spots.shape[1]).sum()}")
-    assert (np.abs(got - want) <= rt * want).all() and (np.abs(gotsq - wantsq) <= rt * wantsq).all()
-    assert (got[want == 0] == 0).all() and (gotsq[want == 0] == 0).all()
-    return want, paying
-
-
 # ---- 1. spots against the restatement --------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("prec", PRECS)
@@ -269,7 +236,7 @@ def test_spots_against_the_restatement(ctx, surfaces, prec, case):
     print(f"{surface} prec {prec} n_steps {n_steps} first path {first} expiries {steps}: restatement spread "
           f"{measured_spread(prec):.3e}, tolerance {tol.min():.3e}..{tol.max():.3e}, worst deviation {err.max():.3e}")
     assert (err <= tol).all(), (k, got[k], want[k], tol[k])
-    check_result_fields(res, stats, N_LOCAL, steps, len(strikes), n_steps)
+    check_result_fields(res, stats, N_LOCAL, steps, len(strikes), n_steps, BASE["r"], BASE["T"])
     check_sums_from_spots(prec, spots, strikes, capi.PAYOFF_CALL, stats, f"{surface} prec {prec}")
     want_price, want_se = sm.finalize(stats, N_LOCAL, BASE["r"], BASE["T"], n_steps, steps, len(strikes))
     assert np.allclose(price, want_price, rtol=1e-13, atol=0) and np.allclose(se, want_se, rtol=1e-9, atol=0)
@@ -306,7 +273,7 @@ def test_node_sums_from_the_returned_spots(ctx, surfaces, prec, payoff, n_e, n_K
                                              f"({n_e}, {n_K}) payoff {payoff} prec {prec} n {n}")
         if n_K > 1:
             assert (want == 0).any() and (paying == n).any()
-        check_result_fields(res, stats, n, steps, n_K, STRIKE_STEPS)
+        check_result_fields(res, stats, n, steps, n_K, STRIKE_STEPS, BASE["r"], BASE["T"])
         # what the scratch buffer held before plays no part
         pollute(ctx, surfaces, sim, payoff, steps, strikes)
         _, _, again, _, spots_again = run(ctx, sim, payoff, steps, strikes, surfaces["skew"])
@@ -325,7 +292,7 @@ def test_wavefronts_that_make_several_trips(ctx, surfaces, prec):
     _, _, stats, res, spots = run(ctx, sim, payoff, steps, strikes, surfaces["skew"])
     assert res.grid == first.grid and n > res.grid * 256 and np.isfinite(spots).all()
     check_sums_from_spots(prec, spots, strikes, payoff, stats, f"several trips prec {prec} grid {res.grid} n {n}", threads=8)
-    check_result_fields(res, stats, n, steps, 64, 32)
+    check_result_fields(res, stats, n, steps, 64, 32, BASE["r"], BASE["T"])
     pollute(ctx, surfaces, sim, payoff, steps, strikes)
     again = run(ctx, sim, payoff, steps, strikes, surfaces["skew"], False)[2]
     assert np.array_equal(again, stats)

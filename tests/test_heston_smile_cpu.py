@@ -51,8 +51,8 @@ def test_header_declares_the_calls(lib):
     assert "a smile call" not in text
     assert "reads only n_expiries and n_strikes" in text and "truncated_steps and mean_variance are NOT reported" in text
     build = importlib.import_module("monte-carlo-project-cuda_amd.build")
-    assert "heston_smile.hip" in build.SOURCES
-    assert "heston_smile.hpp" in build.HEADERS and "smile_device.hpp" in build.HEADERS
+    assert "heston_smile.hip" in build.SOURCES and "smile.hip" in build.SOURCES
+    assert "heston_smile.hpp" in build.HEADERS and "smile_device.hpp" in build.HEADERS and "smile.hpp" in build.HEADERS
     assert hasattr(capi.Context, "price_heston_smile") and hasattr(capi.Context, "price_heston_smile_enqueue")
 
 
@@ -329,9 +329,13 @@ def test_the_two_kernels_use_no_scratch():
 
 
 def test_the_localvol_smile_kernels_still_use_no_scratch():
-    kernels = isa_tool().kernels_of(ROOT, "localvol_smile.hip")
+    isa = isa_tool()
+    kernels = isa.kernels_of(ROOT, "localvol_smile.hip")
     walks = [k for k in kernels if "smile_kernelI" in k]
-    assert len(walks) == 2 and any("smile_finish_kernel" in k for k in kernels)
+    assert len(walks) == 2 and len(kernels) == 2, sorted(kernels)
+    finish = isa.kernels_of(ROOT, "smile.hip")
+    assert len(finish) == 1 and all("smile_finish_kernel" in k for k in finish), sorted(finish)
+    kernels.update(finish)
     for k, (ops, fig) in kernels.items():
         print(k, fig, "waves/SIMD", waves_per_simd(fig))
         assert fig["scratch"] == 0 and fig["vgpr_spill"] == 0 and fig["sgpr_spill"] == 0, (k, fig)

@@ -53,7 +53,7 @@ def test_header_declares_the_calls_and_the_struct(lib):
 
 
 def test_struct_matches_the_header():
-    # static_assert(sizeof(mcamd_smile) == 24) in csrc/capi_localvol.cpp
+    # static_assert(sizeof(mcamd_smile) == 24) in csrc/capi_smile.cpp
     S = capi.Smile
     assert C.sizeof(S) == 24
     assert (S.payoff.offset, S.n_expiries.offset, S.n_strikes.offset, S.reserved.offset, S.q.offset) == (0, 4, 8, 12, 16)

@@ -13,8 +13,8 @@ import collections, importlib.util, os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = "monte-carlo-project-cuda_amd"
 DEFAULT = ["localvol.hip", "localvol_smile.hip", "autocall_localvol.hip", "autocall_localvol_f32.hip", "barrier.hip",
-           "basket.hip", "autocall.hip", "heston.hip", "cliquet.hip", "localvol_greeks.hip", "lookback.hip", "asian.hip",
-           "american.hip", "american_dual.hip", "greeks.hip"]
+           "basket.hip", "autocall.hip", "heston.hip", "heston_smile.hip", "smile.hip", "cliquet.hip", "localvol_greeks.hip",
+           "lookback.hip", "asian.hip", "american.hip", "american_dual.hip", "greeks.hip"]
 OPCODE = re.compile(r"^\s+((?:v|ds|global|flat|buffer)_[a-z0-9_]+)\b")
 FIGURES = {"vgpr": ".vgpr_count", "agpr": ".agpr_count", "vgpr_spill": ".vgpr_spill_count",
            "sgpr_spill": ".sgpr_spill_count", "lds": ".group_segment_fixed_size", "scratch": ".private_segment_fixed_size",
@@ -42,7 +42,9 @@ def text_of(tree, src):
 
 
 def kernels_of(tree, src):
-    """{kernel symbol: (opcode multiset, figures)} of one kernel file of one tree"""
+    """{kernel symbol: (opcode multiset, figures)} of one kernel file of one tree; none where the tree has no such file"""
+    if not os.path.exists(os.path.join(tree, PKG, "csrc", src)):
+        return {}
     asm = device_asm(tree, src)
     ops, cur = {}, None
     for line in asm.splitlines():
@@ -79,8 +81,9 @@ def main():
         a, b = kernels_of(other, src), kernels_of(ROOT, src)
         differ = [k for k in sorted(set(a) | set(b)) if k not in a or k not in b or a[k][0] != b[k][0] or
                   any(a[k][1][f] != b[k][1][f] for f in FIGURES if f != "sgpr")]
-        sg = sorted(set(a) & set(b))
-        moved = [(a[k][1]["sgpr"], b[k][1]["sgpr"]) for k in sg if a[k][1]["sgpr"] != b[k][1]["sgpr"]]
+        both = sorted(set(a) & set(b))
+        moved = [(a[k][1]["sgpr"], b[k][1]["sgpr"]) for k in both if a[k][1]["sgpr"] != b[k][1]["sgpr"]]
+        sg = both or sorted(b)   # a file of this tree alone: its own range
         print(f"{src}: {len(b)} kernels, {sum(sum(v[0].values()) for v in b.values())} counted instructions, "
               f"{len(differ)} differ; SGPRs {min(b[k][1]['sgpr'] for k in sg)}..{max(b[k][1]['sgpr'] for k in sg)}, "
               f"changed in {len(moved)} kernels {sorted(set(moved))}")

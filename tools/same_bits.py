@@ -2,7 +2,8 @@
 """Do two builds of the library compute the same bits?  One fresh worker process per library (MCAMD_LIB) runs a fixed
 list of small jobs on the kernels that walk a local-volatility surface — mcamd_price_localvol, mcamd_price_localvol_smile,
 mcamd_price_autocall_localvol, mcamd_price_cliquet, mcamd_price_localvol_greeks — on mcamd_price_heston (a put and a
-call, with the samples and the final state), and on the one-path-per-thread kernels of constant volatility — mcamd_price_barrier, mcamd_price_lookback, mcamd_price_asian, the likelihood-ratio and pathwise
+call, with the samples and the final state) and mcamd_price_heston_smile (1 x 1 and 3 x 63 nodes, expiries at step 1 and
+at the last step, with the spots and variances at every expiry), and on the one-path-per-thread kernels of constant volatility — mcamd_price_barrier, mcamd_price_lookback, mcamd_price_asian, the likelihood-ratio and pathwise
 mcamd_price_greeks, mcamd_price_american, mcamd_american_upper_bound, and on d = 1..8 correlated assets
 mcamd_price_basket and mcamd_price_autocall — and prints a SHA-256 per job over the per-path
 outputs where the call has them (samples, spots, continuation values, coefficients) and the result record without its
@@ -139,6 +140,17 @@ def worker():
                     hs = capi.make_heston(pay, q=0.02, v0=0.04, kappa=2.0, theta=0.04, xi=1.0, rho=-0.7)
                     res = ctx.price_heston(opt, sim(n_steps, prec, off), hs, out.zero_(), state.zero_())
                     emit(f"heston {tag} n={n_steps} pay={pay}", res, out, state)
+            # mcamd_price_heston_smile on the same model: one node at step 1 and one at the last step, and 3 x 63 nodes
+            # with expiries at step 1, half way and at the last step (1 or 2 expiries where n_steps < 3 holds no more);
+            # the spots and raw variances are hashed with the sums
+            for n_steps in STEPS_WALK:
+                ends = sorted({1, (n_steps + 1) // 2, n_steps})
+                for pay, steps, n_K in [(capi.PAYOFF_CALL, (s,), 1) for s in sorted({1, n_steps})] + [(capi.PAYOFF_PUT, ends, 63)]:
+                    strikes = [60.0 + 80.0 * k / max(n_K - 1, 1) for k in range(n_K)]
+                    hs = capi.make_heston(pay, q=0.02, v0=0.04, kappa=2.0, theta=0.04, xi=1.0, rho=-0.7)
+                    state = torch.zeros(2 * len(steps) * N, dtype=dtype[prec], device="cuda")
+                    _, _, stats, res = ctx.price_heston_smile(opt, sim(n_steps, prec, off), hs, steps, strikes, state)
+                    emit(f"heston smile {tag} n={n_steps} expiries={list(steps)} n_K={n_K}", res, state, stats)
             # mcamd_price_barrier: every kind, monitoring and payoff
             for n_steps in STEPS_WALK:
                 for kind in range(4):
