@@ -1518,6 +1518,68 @@ int mcamd_price_heston_smile_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, co
                                      const uint32_t *h_expiry_steps, const double *h_strikes, void *d_state,
                                      double *d_stats);
 
+/* ---- Cliquets, forward-start options and realized-variance swaps under Heston ----
+ * Additive to ABI version 5: first carried by the build that ships csrc/heston_cliquet.hip (no struct of an earlier call
+ * changed, so MCAMD_ABI_VERSION stays 5; a caller finds out with dlsym).  mcamd_price_cliquet's payoffs on the one model
+ * here that keeps the forward smile they are worth.  Both job structs are the earlier calls', unchanged.
+ *   Paths.  Those of mcamd_price_heston, draw for draw and operation for operation: X_0 = 0 and v_0 = v0, the same
+ *       full-truncation step in the path precision with dt = T / n_steps, z from Philox blocks 0, 1, .. and z' from
+ *       blocks 2^63, 2^63 + 1, .. of the path's subsequence (the GLOBAL path id).  Nothing else is drawn.  r, T and S0
+ *       come from opt, the model, the scheme and q from heston; the notional is 1 and no arithmetic reads S0.  opt->v,
+ *       opt->K and opt->B are ignored.  heston->payoff must be in range but is not read.  cliquet->q states the same
+ *       dividend yield a second time and must equal heston->q bit for bit.
+ *   Reset dates, kinds, sample, counters.  Those of mcamd_price_cliquet, operation for operation, with X the Heston
+ *       log-price: dates p = 1..M at the ends of steps p reset_every, D_p = X_{s_p} - X_{s_{p-1}}, periods
+ *       p >= first_period count; MCAMD_CLIQUET_SUM, _COMPOUND and _VARIANCE accumulate A as defined there, in the path
+ *       precision; y = min(max(A, global_floor), global_cap) in fp64; n_floored and n_capped count A <= global_floor
+ *       and A >= global_cap.  price = exp(-rT) mean(y), std_err as in mcamd_finalize.
+ *   Caller arithmetic.  A forward-start call struck at k times the spot of the date the last period starts at is the SUM
+ *       form with first_period = M, local_floor = k - 1 and no other bound: (S_T / S_{t_1} - k)+ = y - (k - 1).  A call
+ *       on realized variance struck at K is the VARIANCE form with global_floor = K: max(A, K) = K + (A - K)+.
+ *   Diagnostics.  trunc and rv per path as mcamd_price_heston defines them, over all n steps.
+ * d_samples (nullable, device): n_paths_local values of the path precision; [local path] receives y.
+ * res: price .. block as mcamd_cliquet_result, work_steps = 64 x the steps each wavefront ran (always the full count,
+ * computed on the host); truncated_steps and mean_variance as mcamd_heston_result: on one job they are
+ * mcamd_price_heston's.  The enqueue form leaves {sum, sumsq, n_floored, n_capped, sum of rv, n} in d_stats:
+ * mcamd_finalize_stats serves it with control_variate = 0 and mcamd_enqueued_kernel_ms covers it; truncated_steps is
+ * reported by the synchronous call only (the statistics layout keeps n where the kernel's record keeps it).  A sample
+ * depends on its global path id alone, so shards add element by element.  One launch, one fixed order of summation:
+ * two runs of one job give the same bits.
+ * Requirements (MCAMD_ERR_INVALID before any device work, in this order).  opt, sim, heston, cliquet, res non-NULL.
+ * Then everything mcamd_price_cliquet refuses before its surface: kind in range; cliquet->reserved == 0;
+ * reset_every >= 1 and n_steps % reset_every == 0; 1 <= first_period <= M; no bound NaN; local_floor < local_cap and
+ * global_floor < global_cap; COMPOUND: local_floor >= -1 and local_cap > -1; VARIANCE: local_floor == -inf and
+ * local_cap == +inf; cliquet->q finite; r finite; use_window, P1, P2, Ik, Sk, Tk and opt->dt all 0; sim->flags 0 or
+ * MCAMD_FLAG_LOG_SPACE; what mcamd_price_paths refuses on sim (its fp64 exponent-range bound at the drift r - q alone).
+ * Then what mcamd_price_heston refuses of the model: payoff and scheme in range; heston->reserved == 0; q, v0, kappa,
+ * theta, xi, rho finite; v0, kappa, theta, xi >= 0; |rho| <= 1; then cliquet->q != heston->q; with equal yields
+ * mcamd_price_heston's refusals of sim are those already made, and S0 and K are not looked at.  Then the context.  An
+ * empty shard returns zeros and launches nothing; its enqueue form writes a zero record in stream order.
+ * Out of scope: the QE scheme, barriers and Asians under Heston, Greeks, volatility (square-root) swaps, non-uniform
+ * reset schedules, a mcamd_group_* form and a shim name (the reference has no such product).  New. */
+typedef struct mcamd_heston_cliquet_result {   /* 112 bytes */
+    double price;            /* exp(-rT) * mean(y) */
+    double std_err;
+    double ci_lo, ci_hi;     /* 95 % confidence interval */
+    double sum, sumsq;       /* the shard's raw fp64 sums of the undiscounted samples */
+    uint64_t n;              /* paths */
+    uint64_t n_floored;      /* paths with A <= global_floor (0 without one) */
+    uint64_t n_capped;       /* paths with A >= global_cap (0 without one) */
+    double work_steps;       /* 64 x the steps each wavefront ran: always the full count */
+    float kernel_ms;         /* HIP-event time of the kernel (it finishes its own sum: the whole call's device work) */
+    float total_ms;
+    uint32_t grid;           /* launch shape the engine chose */
+    uint32_t block;
+    double truncated_steps;  /* lane-steps entered with v < 0 */
+    double mean_variance;    /* mean over the shard of the paths' average variance (1 / n_steps) sum v+ */
+} mcamd_heston_cliquet_result;
+
+int mcamd_price_heston_cliquet(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_heston *heston,
+                               const mcamd_cliquet *cliquet, void *d_samples, mcamd_heston_cliquet_result *res);
+int mcamd_price_heston_cliquet_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                                       const mcamd_heston *heston, const mcamd_cliquet *cliquet, void *d_samples,
+                                       double *d_stats);
+
 /* Host closed form of the model itself (not of the scheme, whose bias is first order in dt).  With F = S0 e^{(r-q)T},
  * D = e^{-rT}, k = ln(F / K) and phi the characteristic function of ln(S_T / F) in the branch-cut-safe form (Albrecher,
  * Mayer, Schoutens, Tistaert 2007, "the little Heston trap"), rearranged so that nothing is divided by xi^2:
@@ -1539,6 +1601,40 @@ int mcamd_price_heston_smile_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, co
 #define MCAMD_HESTON_XI_MIN 1e-8
 int mcamd_heston_price_f64(double S0, double K, double T, double r, double q, double v0, double kappa, double theta,
                            double xi, double rho, int payoff, double *price);
+
+/* Host closed form of mcamd_price_heston_cliquet's payoffs under the model itself (not the scheme), without a global
+ * clip.  tau = T / n_periods; period p = 1..n_periods starts at t = (p - 1) tau; P = n_periods - first_period + 1.
+ * The period's log-return D_p has the forward characteristic function
+ *   E[e^{iu D_p}] = exp(iu (r - q) tau + C(tau, u)) M_t(D(tau, u)),
+ * with C and D the coefficients of mcamd_heston_price_f64's branch-cut-safe form (ln phi = C + D v0) and
+ *   M_t(w) = E[e^{w v_t}] = (1 - 2cw)^{-2 kappa theta / xi^2} exp(w v0 e^{-kappa t} / (1 - 2cw)),
+ *   c = xi^2 (1 - e^{-kappa t}) / (4 kappa),
+ * (1 - e^{-kappa t}) / kappa through expm1 (t at kappa = 0, where the power is 1), the power through a complex logarithm
+ * arranged so that nothing is divided by xi^2; M_0(w) = e^{w v0}.
+ *   SUM: c_p(k) = E[(e^{D_p} - k)+] by the Lewis integral and the quadrature rule of mcamd_heston_price_f64 with
+ *       F = e^{(r-q) tau}; F - k for k <= 0, 0 for k = +inf.  Where kappa theta = 0 zero absorbs the variance: a path
+ *       enters the period at v_t = 0 with probability P0 = lim_{w -> -inf} M_t(w) = exp(-v0 e^{-kappa t} / (2c)) and then
+ *       earns the forward exactly, a mass that keeps the characteristic function from decaying; its call P0 (F - k)+ is
+ *       added in closed form and the integral takes phi - P0.  F_lo = max(local_floor, -1),
+ *       E_p = (1 + F_lo) + c_p(1 + F_lo) - c_p(1 + local_cap), price = e^{-rT} sum_{p >= first_period} (E_p - 1): exact
+ *       whatever the number of periods, because expectations add although the periods depend on each other.
+ *   VARIANCE: price = e^{-rT} (1 / (P tau)) sum_{p >= first_period} E[D_p^2], the exact mean of the DISCRETELY sampled
+ *       realized variance (its continuous-sampling limit theta + (v0 - theta)(e^{-kappa t_1} - e^{-kappa T}) /
+ *       (kappa (T - t_1)) is not what is returned).  E[D_p^2] = k2 + k1^2 from the first two cumulants of D_p, each a
+ *       central difference of ln phi_p at h = 1/32 and 2h combined as (4 g(h) - g(2h)) / 3 (error of order h^4 times
+ *       the fifth and sixth cumulants): within 1e-8 relative of -phi_p''(0) evaluated at 30 digits on the inputs of
+ *       tests/test_heston_cliquet_cpu.py.
+ *   COMPOUND: the periods depend on each other through v, so there is no product form.  Served where one period counts
+ *       (first_period == n_periods: it is the SUM form) and below MCAMD_HESTON_XI_MIN; refused otherwise.
+ * Below xi = MCAMD_HESTON_XI_MIN the variance is taken as deterministic: mcamd_cliquet_price_f64 at the period
+ * volatilities v_p^2 = the average of theta + (v0 - theta) e^{-kappa s} over period p (and its refusal of a volatility
+ * that is 0).
+ * Refuses a NULL price, kind out of range, what mcamd_price_cliquet refuses of the local bounds, what mcamd_price_heston
+ * refuses of q, v0, kappa, theta, xi and rho, T <= 0, a non-finite T or r, n_periods == 0, first_period outside
+ * 1..n_periods, and the COMPOUND form described above. */
+int mcamd_heston_cliquet_price_f64(int kind, double T, double r, double q, double v0, double kappa, double theta,
+                                   double xi, double rho, uint32_t n_periods, uint32_t first_period,
+                                   double local_floor, double local_cap, double *price);
 
 /* Host: discount + mean + standard error + 95% CI from (sum, sumsq, n) — after an all-reduce
  * over shards, or directly.  Fills price/std_err/ci_* (and copies sum/sumsq/n) in *res. */

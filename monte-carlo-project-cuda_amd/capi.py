@@ -75,6 +75,7 @@ EXPORTS = [
     "mcamd_price_cliquet", "mcamd_price_cliquet_enqueue", "mcamd_cliquet_price_f64",
     "mcamd_price_heston", "mcamd_price_heston_enqueue", "mcamd_heston_price_f64",
     "mcamd_price_heston_smile", "mcamd_price_heston_smile_enqueue",
+    "mcamd_price_heston_cliquet", "mcamd_price_heston_cliquet_enqueue", "mcamd_heston_cliquet_price_f64",
 ]
 
 
@@ -272,6 +273,17 @@ class HestonResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class HestonCliquetResult(C.Structure):
+    """mcamd_heston_cliquet_result: mcamd_cliquet_result's fields, then mcamd_heston_result's two diagnostics"""
+    _fields_ = CliquetResult._fields_ + [("truncated_steps", C.c_double), ("mean_variance", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+assert C.sizeof(HestonCliquetResult) == 112   # pinned in include/mcamd.h
+
+
 class Smile(C.Structure):
     """mcamd_smile: the payoff of every node, the numbers of expiries and strikes, and the dividend yield
     mcamd_price_localvol_smile prices a strike-by-expiry set of vanillas with."""
@@ -403,6 +415,11 @@ def load() -> C.CDLL:
                                      C.POINTER(HestonResult)]
     L.mcamd_price_heston_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Heston), vp, vp, vp]
     L.mcamd_heston_price_f64.argtypes = [f64] * 10 + [i32, C.POINTER(f64)]
+    L.mcamd_price_heston_cliquet.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Heston), C.POINTER(Cliquet),
+                                             vp, C.POINTER(HestonCliquetResult)]
+    L.mcamd_price_heston_cliquet_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Heston),
+                                                     C.POINTER(Cliquet), vp, vp]
+    L.mcamd_heston_cliquet_price_f64.argtypes = [i32] + [f64] * 8 + [C.c_uint32, C.c_uint32, f64, f64, C.POINTER(f64)]
     L.mcamd_localvol_sigma_f64.argtypes = [C.POINTER(LocalVolGrid), C.POINTER(f64), C.c_uint32, C.c_uint32, f64,
                                            C.POINTER(f64)]
     L.mcamd_bs_price_f64.argtypes = [f64, f64, f64, f64, f64, f64, i32, C.POINTER(f64)]
@@ -606,6 +623,17 @@ def heston_price(S0, K, T, r, q, v0, kappa, theta, xi, rho, payoff=PAYOFF_CALL) 
     full-truncation scheme of price_heston approaches at first order in the step."""
     out = C.c_double()
     _check(load().mcamd_heston_price_f64(S0, K, T, r, q, v0, kappa, theta, xi, rho, payoff, C.byref(out)))
+    return out.value
+
+
+def heston_cliquet_price(kind, T, r, q, v0, kappa, theta, xi, rho, n_periods, first_period=1, local_floor=-math.inf,
+                         local_cap=math.inf) -> float:
+    """Closed form of an additive cliquet, a one-period compounding one or a discretely sampled variance swap under
+    Heston, without a global clip (mcamd_heston_cliquet_price_f64): the model's price, through the forward
+    characteristic function of the period returns."""
+    out = C.c_double()
+    _check(load().mcamd_heston_cliquet_price_f64(kind, T, r, q, v0, kappa, theta, xi, rho, n_periods, first_period,
+                                                 local_floor, local_cap, C.byref(out)))
     return out.value
 
 
@@ -910,6 +938,24 @@ class Context:
         tensor `stats` (>= 6 doubles; finalize_stats)."""
         _check(self._L.mcamd_price_heston_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(heston), _ptr(samples),
                                                   _ptr(state), _ptr(stats)))
+
+    def price_heston_cliquet(self, opt: Option, sim: Sim, heston: Heston, cliquet: Cliquet,
+                             samples=None) -> HestonCliquetResult:
+        """Cliquet, forward-start option or realized-variance swap on the paths of price_heston
+        (mcamd_price_heston_cliquet); r, T and S0 come from opt, opt.v, opt.K and opt.B are ignored, heston.payoff is
+        not read and cliquet.q must equal heston.q.  samples: optional device tensor of n_paths_local values of the
+        path precision that receives each path's undiscounted sample."""
+        res = HestonCliquetResult()
+        _check(self._L.mcamd_price_heston_cliquet(self._h, C.byref(opt), C.byref(sim), C.byref(heston), C.byref(cliquet),
+                                                  _ptr(samples), C.byref(res)))
+        return res
+
+    def price_heston_cliquet_enqueue(self, opt: Option, sim: Sim, heston: Heston, cliquet: Cliquet, stats,
+                                     samples=None) -> None:
+        """Asynchronous: leaves {sum, sumsq, n_floored, n_capped, sum of the paths' average variance, n} in the device
+        tensor `stats` (>= 6 doubles; finalize_stats)."""
+        _check(self._L.mcamd_price_heston_cliquet_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(heston),
+                                                          C.byref(cliquet), _ptr(samples), _ptr(stats)))
 
     def price_heston_smile(self, opt: Option, sim: Sim, heston: Heston, expiry_steps, strikes, state=None):
         """len(expiry_steps) x len(strikes) vanillas on one set of price_heston's paths (mcamd_price_heston_smile);

@@ -1,13 +1,15 @@
 // capi_heston.cpp — the calls of the C ABI that walk Heston stochastic-volatility paths under the full-truncation Euler
-// scheme: European options, and the strike-by-expiry smile.  Each call is a prepare step (the refusals and the job) and
+// scheme: European options, the strike-by-expiry smile, and cliquets.  Each call is a prepare step (the refusals and the job) and
 // its synchronous and enqueue forms; the refusals keep the order of the other families: the request alone, then the
 // context.
 #include "capi_internal.hpp"
 #include "heston.hpp"
+#include "heston_cliquet.hpp"
 #include "heston_smile.hpp"
 
 static_assert(sizeof(mcamd_heston) == 64 && sizeof(mcamd_heston_result) == 96,
               "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
+static_assert(sizeof(mcamd_heston_cliquet_result) == 112, "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
 static_assert(MCAMD_HESTON_FULL_TRUNCATION == mcamd::kHestonFullTruncation, "the kernels' scheme is MCAMD_HESTON_*");
 
 using namespace mcamd::capi;
@@ -113,6 +115,52 @@ int prepare_heston_smile(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_si
                                  smile_launch<mcamd::HestonSmileJob, mcamd::launch_heston_smile>, &job));
 }
 
+// The Heston cliquet calls: mcamd_price_heston's paths with mcamd_price_cliquet's payoff.  The refusals: what
+// prepare_cliquet refuses before the surface (the job, then q, r, opt and sim at the drift r - cliquet->q), what
+// prepare_heston refuses of the job and the model, the two dividend yields that must be one, then the context.  Once
+// the yields agree prepare_heston's refusals of sim are the ones already made.  opt->v, opt->K and opt->B are ignored,
+// S0 is read by nothing, and heston->payoff must be in range but is not read.
+template <typename Drive>
+int prepare_heston_cliquet(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_heston *hs,
+                           const mcamd_cliquet *cq, void *d_samples, Drive drive)
+{
+    if (!opt || !sim || !hs || !cq) return fail(MCAMD_ERR_INVALID, "opt, sim, heston and cliquet must be non-NULL");
+    if (int rc = check_cliquet_job(cq, sim->n_steps)) return rc;
+    if (!std::isfinite(cq->q)) return fail(MCAMD_ERR_INVALID, "the dividend yield q must be finite, got %g", cq->q);
+    if (!std::isfinite(opt->r)) return fail(MCAMD_ERR_INVALID, "option parameters must be finite with T > 0");
+    // as prepare_cliquet, on a copy that carries no spot, strike or barrier of its own
+    mcamd_option seen = *opt;
+    seen.S0 = 1.0;
+    seen.K = seen.B = 0.0;
+    const double mu = opt->r - cq->q;
+    if (int rc = check_drift_request("Heston cliquet", seen, sim, &mu, 1)) return rc;
+    if (int rc = check_heston_job(opt, hs)) return rc;
+    if (std::memcmp(&cq->q, &hs->q, sizeof(double)) != 0)
+        return fail(MCAMD_ERR_INVALID, "cliquet->q = %.17g and heston->q = %.17g must be the same dividend yield, bit for bit",
+                    cq->q, hs->q);
+    if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
+    if (sim->n_paths_local == 0) return drive(empty_call());
+    mcamd::HestonCliquetJob job;
+    job.walk = heston_walk(opt, sim, hs);
+    job.scheme = hs->scheme;
+    job.kind = cq->kind;
+    job.reset_every = cq->reset_every;
+    job.first_period = cq->first_period;
+    const bool compound = cq->kind == MCAMD_CLIQUET_COMPOUND;
+    job.local_lo = compound ? std::log(1.0 + cq->local_floor) : cq->local_floor;
+    job.local_hi = compound ? std::log(1.0 + cq->local_cap) : cq->local_cap;
+    job.global_lo = cq->global_floor;
+    job.global_hi = cq->global_cap;
+    const double P = static_cast<double>(sim->n_steps / cq->reset_every - cq->first_period + 1);
+    job.scale = 1.0 / (P * (static_cast<double>(cq->reset_every) * job.walk.dt));
+    job.d_samples = d_samples;
+    const uint32_t grid = mcamd::one_path_per_thread_grid(sim->n_paths_local);
+    return drive(DeviceCall{sim->n_paths_local, grid, mcamd::kHestonCliquetRecord, 6, Finish::kFolded,
+                            [&](const mcamd::FinishSpec &fs) {
+                                return mcamd::launch_heston_cliquet(job, ctx->d_partials, grid, fs, ctx->stream);
+                            }});
+}
+
 }  // namespace
 
 extern "C" {
@@ -166,6 +214,41 @@ int mcamd_price_heston_smile_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, co
     if (!d_stats) return fail(MCAMD_ERR_INVALID, "d_stats is NULL");
     return prepare_heston_smile(ctx, opt, sim, heston, n_expiries, n_strikes, h_expiry_steps, h_strikes, d_state,
                                 [&](const SmileCall &call) { return run_smile_enqueue(ctx, call, d_stats); });
+}
+
+int mcamd_price_heston_cliquet(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_heston *heston,
+                               const mcamd_cliquet *cliquet, void *d_samples, mcamd_heston_cliquet_result *res)
+{
+    if (!res) return fail(MCAMD_ERR_INVALID, "opt, sim, heston, cliquet and res must be non-NULL");
+    std::memset(res, 0, sizeof *res);
+    return prepare_heston_cliquet(ctx, opt, sim, heston, cliquet, d_samples, [&](const auto &call) {
+        return run_sync(ctx, call, res, [&](const double *rec) {
+            // {sum, sumsq, paths on the global floor, paths on the global cap, sum of the paths' average variance,
+            // lane-steps entered with v < 0}
+            const uint64_t n = sim->n_paths_local;
+            const Estimate e = estimate(rec[0], rec[1], n, std::exp(-opt->r * opt->T));
+            res->sum = rec[0];
+            res->sumsq = rec[1];
+            res->n = n;
+            res->price = e.value;
+            res->std_err = e.std_err;
+            set_ci(res);
+            res->n_floored = static_cast<uint64_t>(std::llround(rec[2]));
+            res->n_capped = static_cast<uint64_t>(std::llround(rec[3]));
+            res->mean_variance = rec[4] / static_cast<double>(n);
+            res->truncated_steps = rec[5];
+            // there is no early exit: every wavefront runs every step
+            res->work_steps = 64.0 * static_cast<double>((n + 63) / 64) * static_cast<double>(sim->n_steps);
+        });
+    });
+}
+
+int mcamd_price_heston_cliquet_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                                       const mcamd_heston *heston, const mcamd_cliquet *cliquet, void *d_samples,
+                                       double *d_stats)
+{
+    return prepare_heston_cliquet(ctx, opt, sim, heston, cliquet, d_samples,
+                                  [&](const auto &call) { return run_enqueue(ctx, call, d_stats); });
 }
 
 }  // extern "C"

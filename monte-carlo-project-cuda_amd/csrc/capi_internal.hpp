@@ -99,6 +99,7 @@ int check_localvol_grid(const mcamd_localvol_grid *grid, const double *h_sigma, 
 int check_cliquet_kind(int kind);
 int check_cliquet_local(double local_floor, double local_cap);
 int check_cliquet_kind_bounds(int kind, double local_floor, double local_cap);
+int check_cliquet_job(const mcamd_cliquet *cq, uint32_t n_steps);
 // capi_smile.cpp: what every smile call refuses of the nodes, in this order: n_expiries and n_strikes out of range,
 // expiry steps that are not strictly ascending in 1 .. n_steps, a strike that is not finite and > 0.  Nodes that pass
 // are left in *nodes, as a job carries them, with the payoff (checked by the caller) that holds for all of them.

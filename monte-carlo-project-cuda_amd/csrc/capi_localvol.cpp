@@ -87,6 +87,29 @@ int check_cliquet_kind_bounds(int kind, double local_floor, double local_cap)
     return MCAMD_OK;
 }
 
+// ... and of the job whatever walks the paths, in mcamd_price_cliquet's order: kind, reserved, the reset schedule against
+// n_steps, the bounds.
+int check_cliquet_job(const mcamd_cliquet *cq, uint32_t n_steps)
+{
+    if (int rc = check_cliquet_kind(cq->kind)) return rc;
+    if (cq->reserved != 0) return fail(MCAMD_ERR_INVALID, "cliquet->reserved must be 0, got %d", cq->reserved);
+    if (cq->reset_every == 0 || n_steps % cq->reset_every != 0)
+        return fail(MCAMD_ERR_INVALID, "reset_every must be >= 1 and divide n_steps (reset_every = %u, n_steps = %u)",
+                    cq->reset_every, n_steps);
+    const uint32_t M = n_steps / cq->reset_every;
+    if (M != 0 && (cq->first_period < 1 || cq->first_period > M))   // M == 0 is n_steps == 0, refused below
+        return fail(MCAMD_ERR_INVALID, "first_period must be 1..%u (the periods), got %u", M, cq->first_period);
+    if (std::isnan(cq->global_floor) || std::isnan(cq->global_cap))
+        return fail(MCAMD_ERR_INVALID, "a bound must not be NaN (-inf / +inf: none): global_floor = %g, global_cap = %g",
+                    cq->global_floor, cq->global_cap);
+    if (int rc = check_cliquet_local(cq->local_floor, cq->local_cap)) return rc;
+    if (!(cq->global_floor < cq->global_cap))
+        return fail(MCAMD_ERR_INVALID, "global_floor must lie below global_cap, got %g and %g", cq->global_floor,
+                    cq->global_cap);
+    if (int rc = check_cliquet_kind_bounds(cq->kind, cq->local_floor, cq->local_cap)) return rc;
+    return MCAMD_OK;
+}
+
 void finalize_localvol_greeks_into(const double stats[32], double r, double T, uint32_t n_buckets, int gamma_defined,
                                    mcamd_localvol_greeks *out)
 {
@@ -226,22 +249,8 @@ int prepare_cliquet(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *si
                     const mcamd_localvol_surface *surface, void *d_samples, Drive drive)
 {
     if (!opt || !sim || !cq) return fail(MCAMD_ERR_INVALID, "opt, sim, cliquet and surface must be non-NULL");
-    if (int rc = check_cliquet_kind(cq->kind)) return rc;
-    if (cq->reserved != 0) return fail(MCAMD_ERR_INVALID, "cliquet->reserved must be 0, got %d", cq->reserved);
-    if (cq->reset_every == 0 || sim->n_steps % cq->reset_every != 0)
-        return fail(MCAMD_ERR_INVALID, "reset_every must be >= 1 and divide n_steps (reset_every = %u, n_steps = %u)",
-                    cq->reset_every, sim->n_steps);
+    if (int rc = check_cliquet_job(cq, sim->n_steps)) return rc;
     const uint32_t M = sim->n_steps / cq->reset_every;
-    if (M != 0 && (cq->first_period < 1 || cq->first_period > M))   // M == 0 is n_steps == 0, refused below
-        return fail(MCAMD_ERR_INVALID, "first_period must be 1..%u (the periods), got %u", M, cq->first_period);
-    if (std::isnan(cq->global_floor) || std::isnan(cq->global_cap))
-        return fail(MCAMD_ERR_INVALID, "a bound must not be NaN (-inf / +inf: none): global_floor = %g, global_cap = %g",
-                    cq->global_floor, cq->global_cap);
-    if (int rc = check_cliquet_local(cq->local_floor, cq->local_cap)) return rc;
-    if (!(cq->global_floor < cq->global_cap))
-        return fail(MCAMD_ERR_INVALID, "global_floor must lie below global_cap, got %g and %g", cq->global_floor,
-                    cq->global_cap);
-    if (int rc = check_cliquet_kind_bounds(cq->kind, cq->local_floor, cq->local_cap)) return rc;
     // as prepare_localvol, on a copy that carries no spot, strike or barrier of its own either
     mcamd_option seen = *opt;
     seen.S0 = 1.0;

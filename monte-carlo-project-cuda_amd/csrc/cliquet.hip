@@ -8,7 +8,8 @@
 //   SUM       c_p = min(max(e^{D_p} - 1, lo), hi), A = sum c_p: one exponential per counted period;
 //   COMPOUND  l_p = min(max(D_p, ln(1 + lo)), ln(1 + hi)), L = sum l_p, A = e^L - 1: one exponential per path, at the end;
 //   VARIANCE  V = fma(D_p, D_p, V), A = V / (P tau): no exponential at all.
-// y = min(max(A, global floor), global cap) in fp64.
+// y = min(max(A, global floor), global cap) in fp64.  What a counted period adds and what the sum becomes at the end are
+// cliquet_device.hpp's, shared with heston_cliquet.hip.
 //
 // KIND is a template parameter, so the exponential exists in the SUM loop only.  The step index is wave-uniform: the
 // reset test is a scalar compare of the step with the step of the next reset, the period counter and "does this period
@@ -16,6 +17,7 @@
 // step of a Philox block (reset_every may be 1, odd, or larger than a block), so the test sits in the step, not at the
 // block ends.  There is no early exit: every wavefront runs every step.
 #include "cliquet.hpp"
+#include "cliquet_device.hpp"
 #include "localvol_device.hpp"
 #include "path_frame.hpp"
 
@@ -67,16 +69,7 @@ __global__ __launch_bounds__(kBlock) void cliquet_kernel(CliquetArgs<T> a, doubl
             if (index + 1 == next_reset) {   // a scalar compare
                 const T D = X - X_reset;
                 X_reset = X;
-                if (p + 1 >= a.first_period) {
-                    if (KIND == kCliquetSum) {
-                        const T R = exp_of_logreturn(T(1), D * exp_scale, m) - T(1);
-                        sum += lv_min(lv_max(R, lo), hi);
-                    } else if (KIND == kCliquetCompound) {
-                        sum += lv_min(lv_max(D, lo), hi);
-                    } else {
-                        sum = fma_t(D, D, sum);
-                    }
-                }
+                if (p + 1 >= a.first_period) cliquet_add_period<KIND>(sum, D, lo, hi, exp_scale, m);
                 ++p;
                 next_reset += a.reset_every;
             }
@@ -84,10 +77,7 @@ __global__ __launch_bounds__(kBlock) void cliquet_kernel(CliquetArgs<T> a, doubl
         walk_steps<NB>(
             blocks, [&](uint32_t kb) { nz.fill(m, key, subsequence, kb); },
             [&](uint32_t kb, int j) { step(nz.z[j], kb * NB + j); });
-        double A;
-        if (KIND == kCliquetSum) A = static_cast<double>(sum);
-        else if (KIND == kCliquetCompound) A = static_cast<double>(exp_of_logreturn(T(1), sum * exp_scale, m)) - 1.0;
-        else A = static_cast<double>(sum) * a.scale;
+        const double A = cliquet_amount<KIND>(sum, exp_scale, a.scale, m);
         const double y = __builtin_fmin(__builtin_fmax(A, a.g_lo), a.g_hi);
         if (a.samples) a.samples[i] = static_cast<T>(y);
         add_sample(acc5, y);

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <complex>
+#include <vector>
 
 using namespace mcamd::capi;
 
@@ -122,6 +123,68 @@ void gauss_legendre(double x[kGlNodes], double w[kGlNodes])
         w[i] = 2.0 / ((1.0 - t * t) * dp * dp);
     }
 }
+
+// Lewis's integral int_0^U Re[e^{iuk} (phi(u - i/2) - atom)] / (u^2 + 1/4) du of a characteristic function given by its
+// logarithm lnphi(u), by the rule of mcamd_heston_price_f64 (include/mcamd.h): 16 Gauss-Legendre nodes on each panel of
+// width 1/2, U the first of 32, 64, .. 4096 at which the integrand's envelope |phi(U - i/2) - atom| / (U^2 + 1/4) is
+// below 1e-15.  atom: the mass the distribution has at x = 0, which does not decay and which the caller integrates in
+// closed form; 0 for a distribution without one.
+template <typename LogCf>
+double lewis_integral(double k, LogCf lnphi, double atom = 0.0)
+{
+    const auto integrand = [&](double u) {
+        if (atom == 0.0) return (std::exp(lnphi(cplx(u, -0.5)) + cplx(0.0, u * k))).real() / (u * u + 0.25);
+        return ((std::exp(lnphi(cplx(u, -0.5))) - atom) * std::exp(cplx(0.0, u * k))).real() / (u * u + 0.25);
+    };
+    const auto envelope = [&](double u) {
+        if (atom == 0.0) return std::exp(lnphi(cplx(u, -0.5)).real()) / (u * u + 0.25);
+        return std::abs(std::exp(lnphi(cplx(u, -0.5))) - atom) / (u * u + 0.25);
+    };
+    double U = kHestonRangeMin;
+    while (U < kHestonRangeMax && envelope(U) >= kHestonEnvelope) U *= 2.0;
+    double x[kGlNodes], w[kGlNodes];
+    gauss_legendre(x, w);
+    const int panels = static_cast<int>(U / kHestonPanel);
+    double integral = 0.0;
+    for (int p = 0; p < panels; ++p) {
+        const double mid = (p + 0.5) * kHestonPanel;
+        double s = 0.0;
+        for (int i = 0; i < kGlNodes; ++i) s += w[i] * integrand(mid + 0.5 * kHestonPanel * x[i]);
+        integral += 0.5 * kHestonPanel * s;
+    }
+    return integral;
+}
+
+// (1 - e^{-kappa t}) / kappa, t at kappa = 0
+double decay_gain(double kappa, double t)
+{
+    const double kt = kappa * t;
+    return kt > 0.0 ? -std::expm1(-kt) / kappa : t;
+}
+
+// ln E[e^{iu x}] of the forward log-return x = ln(S_{t + tau} / S_t) - (r - q) tau under Heston.  Given v_t the return
+// over [t, t + tau] has the spot characteristic function exp(C(tau, u) + D(tau, u) v_t), heston_log_cf being affine in
+// its v0: C is its value at v0 = 0 and D its value at v0 = 1 with theta = 0.  v_t is a scaled noncentral chi-square:
+//     E[e^{w v_t}] = (1 - 2cw)^{-2 kappa theta / xi^2} exp(w v0 e^{-kappa t} / (1 - 2cw)),  c = xi^2 (1 - e^{-kappa t}) / (4 kappa),
+// and with z = -2cw the power is exp(-(2 kappa theta / xi^2) ln(1 + z)) = exp(kappa theta [(1 - e^{-kappa t}) / kappa] w
+// [ln(1 + z) / z]): the complex logarithm is taken in Kahan's quotient and nothing is divided by xi^2.  Re w <= 0 on
+// the lines the callers use, so 1 + z stays in the right half plane and the principal logarithm is the continuous one.
+// kappa = 0: c = xi^2 t / 4 and the power is 1.  t = 0: e^{w v0}.
+cplx heston_forward_log_cf(cplx u, double t, double tau, double v0, double kappa, double theta, double xi, double rho)
+{
+    const cplx C = heston_log_cf(u, tau, 0.0, kappa, theta, xi, rho);
+    const cplx w = heston_log_cf(u, tau, 1.0, kappa, 0.0, xi, rho);
+    if (!(t > 0.0)) return C + w * v0;
+    const double gain = decay_gain(kappa, t), c = 0.25 * xi * xi * gain;
+    const cplx z = -2.0 * c * w;
+    return C + (kappa * theta * gain) * w * c_log1p_over(z) + w * (v0 * std::exp(-kappa * t)) / (1.0 + z);
+}
+
+// The step of the two central differences that give the first two cumulants of a period's log-return from
+// f = ln phi: with g1(h) = Im f(h) / h = k1 - k3 h^2 / 6 + .. and g2(h) = -2 Re f(h) / h^2 = k2 - k4 h^2 / 12 + ..,
+// (4 g(h) - g(2h)) / 3 leaves an error of order h^4 (k5 h^4 / 30, k6 h^4 / 90).  f is evaluated where it is small with
+// the relative accuracy of its parts (nothing in heston_log_cf cancels at u -> 0), so rounding costs about eps / h.
+constexpr double kCumulantStep = 1.0 / 32.0;
 
 }  // namespace
 
@@ -399,28 +462,82 @@ int mcamd_heston_price_f64(double S0, double K, double T, double r, double q, do
         return MCAMD_OK;
     }
     const double k = std::log(F / K);
-    const auto integrand = [&](double u) {
-        const cplx lnphi = heston_log_cf(cplx(u, -0.5), T, v0, kappa, theta, xi, rho);
-        return (std::exp(lnphi + cplx(0.0, u * k))).real() / (u * u + 0.25);
-    };
-    // the range: the first of 32, 64, .. 4096 at which the integrand's envelope |phi(u - i/2)| / (u^2 + 1/4) is below 1e-15
-    double U = kHestonRangeMin;
-    while (U < kHestonRangeMax &&
-           std::exp(heston_log_cf(cplx(U, -0.5), T, v0, kappa, theta, xi, rho).real()) / (U * U + 0.25) >= kHestonEnvelope)
-        U *= 2.0;
-    double x[kGlNodes], w[kGlNodes];
-    gauss_legendre(x, w);
-    const int panels = static_cast<int>(U / kHestonPanel);
-    double integral = 0.0;
-    for (int p = 0; p < panels; ++p) {
-        const double mid = (p + 0.5) * kHestonPanel;
-        double s = 0.0;
-        for (int i = 0; i < kGlNodes; ++i) s += w[i] * integrand(mid + 0.5 * kHestonPanel * x[i]);
-        integral += 0.5 * kHestonPanel * s;
-    }
+    const double integral =
+        lewis_integral(k, [&](cplx u) { return heston_log_cf(u, T, v0, kappa, theta, xi, rho); });
     const double c = D * (F - std::sqrt(F * K) / M_PI * integral);
     if (!std::isfinite(c)) return fail(MCAMD_ERR_INVALID, "the Heston integral is not finite at these parameters");
     *price = call ? c : c - D * (F - K);
+    return MCAMD_OK;
+}
+
+// The forward characteristic function (heston_forward_log_cf) carries the additive cliquet and the variance swap:
+// expectations add over dependent periods.
+int mcamd_heston_cliquet_price_f64(int kind, double T, double r, double q, double v0, double kappa, double theta,
+                                   double xi, double rho, uint32_t n_periods, uint32_t first_period,
+                                   double local_floor, double local_cap, double *price)
+{
+    if (!price) return fail(MCAMD_ERR_INVALID, "price is NULL");
+    *price = 0.0;
+    if (int rc = check_cliquet_kind(kind)) return rc;
+    if (int rc = check_cliquet_local(local_floor, local_cap)) return rc;
+    if (int rc = check_cliquet_kind_bounds(kind, local_floor, local_cap)) return rc;
+    if (int rc = check_heston_model(q, v0, kappa, theta, xi, rho)) return rc;
+    if (!(T > 0.0) || !std::isfinite(T) || !std::isfinite(r))
+        return fail(MCAMD_ERR_INVALID, "the Heston cliquet closed form needs a finite T > 0 and a finite r");
+    if (n_periods == 0 || first_period < 1 || first_period > n_periods)
+        return fail(MCAMD_ERR_INVALID, "n_periods must be >= 1 and first_period 1..n_periods, got %u and %u", n_periods,
+                    first_period);
+    const double tau = T / static_cast<double>(n_periods);
+    if (xi < MCAMD_HESTON_XI_MIN) {
+        // v is deterministic: the periods are independent, at the rms volatility of each
+        std::vector<double> vol(n_periods);
+        for (uint32_t p = 0; p < n_periods; ++p)
+            vol[p] = std::sqrt(theta + (v0 - theta) * std::exp(-kappa * (p * tau)) * (decay_gain(kappa, tau) / tau));
+        return mcamd_cliquet_price_f64(kind, T, r, q, n_periods, first_period, vol.data(), local_floor, local_cap, price);
+    }
+    if (kind == MCAMD_CLIQUET_COMPOUND) {
+        if (first_period != n_periods)
+            return fail(MCAMD_ERR_INVALID, "a compounding cliquet over %u periods has no closed form under Heston: the "
+                                           "periods depend on each other through v, so the mean of their product is not "
+                                           "the product of their means (one counted period, or xi < %g, is served)",
+                        n_periods - first_period + 1, MCAMD_HESTON_XI_MIN);
+        kind = MCAMD_CLIQUET_SUM;   // one period: e^{l} - 1 is the clipped return itself
+    }
+    const double fwd = std::exp((r - q) * tau);
+    const double F = std::fmax(local_floor, -1.0);   // a floor at or below -1 never binds
+    double sum = 0.0;
+    for (uint32_t p = first_period; p <= n_periods; ++p) {
+        const double t = (p - 1) * tau;
+        const auto lnphi = [&](cplx u) { return heston_forward_log_cf(u, t, tau, v0, kappa, theta, xi, rho); };
+        if (kind == MCAMD_CLIQUET_VARIANCE) {
+            const auto cumulants = [&](double h, double *k1, double *k2) {
+                const cplx f = lnphi(cplx(h, 0.0));
+                *k1 = f.imag() / h + (r - q) * tau;
+                *k2 = -2.0 * f.real() / (h * h);
+            };
+            double a1, a2, b1, b2;
+            cumulants(kCumulantStep, &a1, &a2);
+            cumulants(2.0 * kCumulantStep, &b1, &b2);
+            const double k1 = (4.0 * a1 - b1) / 3.0, k2 = (4.0 * a2 - b2) / 3.0;
+            sum += k2 + k1 * k1;
+        } else {
+            // kappa theta = 0: zero absorbs the variance, and a path that enters the period there earns the forward
+            // exactly.  That mass, lim_{w -> -inf} M_t(w) = exp(-v0 e^{-kappa t} / (2c)), keeps the characteristic
+            // function from decaying; its call is (fwd - k)+ and the integral takes the rest, which decays.
+            const double c = 0.25 * xi * xi * decay_gain(kappa, t);
+            const double atom = (kappa * theta == 0.0 && c > 0.0) ? std::exp(-v0 * std::exp(-kappa * t) / (2.0 * c)) : 0.0;
+            const auto call = [&](double k) {   // E[(e^D - k)+]
+                if (k <= 0.0) return fwd - k;
+                if (k == HUGE_VAL) return 0.0;
+                return fwd - atom * std::fmin(fwd, k) -
+                       std::sqrt(fwd * k) / M_PI * lewis_integral(std::log(fwd / k), lnphi, atom);
+            };
+            sum += (1.0 + F) + call(1.0 + F) - call(1.0 + local_cap) - 1.0;
+        }
+    }
+    if (!std::isfinite(sum)) return fail(MCAMD_ERR_INVALID, "the Heston integral is not finite at these parameters");
+    const double P = static_cast<double>(n_periods - first_period + 1);
+    *price = std::exp(-r * T) * (kind == MCAMD_CLIQUET_VARIANCE ? sum / (P * tau) : sum);
     return MCAMD_OK;
 }
 

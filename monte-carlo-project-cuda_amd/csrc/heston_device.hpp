@@ -1,5 +1,5 @@
 // heston_device.hpp — the step of a Heston path under the full-truncation Euler scheme in the log-price, for any kernel
-// that walks such paths (heston.hip, heston_smile.hip; barriers, Asians and cliquets under Heston can reuse it): the step
+// that walks such paths (heston.hip, heston_smile.hip, heston_cliquet.hip; barriers and Asians can reuse it): the step
 // constants, where the variance's normals come from, and the move of one step.
 //
 // Definitions (include/mcamd.h, mcamd_price_heston): X = ln(S / S0) in NATURAL-log units, v the raw variance, which may
