@@ -197,15 +197,22 @@ MC_HD double neg2log(double u, const D2 *tab)
 // <= 2 ulp for u <= 1 - 2^-9; above that the result is below 2e-3 and the truncation shows as up to ~100 ulp of it,
 // < 2e-17 absolute, which is what the radius feeds into a path's sum.  Strictly positive for every u in (0, 1]: the
 // row that serves u = 1 is biased by 1.55e-17 (tools/gen_tables64.py), so sqrt_unclamped needs no clamp.
+// The exponent's term w = k (-2 ln 2) + b is formed from the word the reduction masks anyway: tmp & 0xfff00000 is
+// k 2^20 as an int32 (k in [-53, 0]), and fma(k 2^20, kM2Ln2 2^-20, b) is fma(k, kM2Ln2, b) bit for bit — both
+// scalings are exact powers of two, so the product is the same real number — without the shift that isolated k.
+MC_HD double neg2log_1k_exponent_term(uint32_t k20, double b)
+{
+    return __builtin_fma(static_cast<double>(static_cast<int32_t>(k20)), kM2Ln2 * 0x1p-20, b);
+}
 MC_HD double neg2log_1k(double u, const D2 *tab1k)
 {
     const uint32_t hx = hi32(u);
     const uint32_t tmp = hx - 0x3fe60000u;
-    const int32_t k = static_cast<int32_t>(tmp) >> 20;
-    const double z = make_double(lo32(u), hx - (tmp & 0xfff00000u));
+    const uint32_t k20 = tmp & 0xfff00000u;
+    const double z = make_double(lo32(u), hx - k20);
     const D2 e = *reinterpret_cast<const D2 *>(reinterpret_cast<const char *>(tab1k) + ((tmp >> 6) & 0x3ff0u));
     const double t = __builtin_fma(z, e.a, 2.0);
-    const double w = __builtin_fma(static_cast<double>(k), kM2Ln2, e.b);
+    const double w = neg2log_1k_exponent_term(k20, e.b);
     double q = fma_usv(t, 1.0 / 32.0, 1.0 / 12.0);
     q = fma_vvv(t, q, 0.25);
     const double h = __builtin_fma(t, q, 1.0);
