@@ -1435,9 +1435,10 @@ int mcamd_cliquet_price_f64(int kind, double T, double r, double q, uint32_t n_p
  * on sim (its fp64 exponent-range bound at the drift r - q alone: the variance is random, and no bound on the request
  * covers it); S0 > 0 and K > 0; then the context.  An empty shard returns zeros and launches nothing; its enqueue form
  * writes a zero record in stream order.
- * Left out on purpose: the QE scheme and exact simulation, barriers and path-dependent payoffs, Greeks, a term
- * structure of the parameters, a mcamd_group_* form and a shim name (the reference has no such model).  The smile of
- * the model is mcamd_price_heston_smile, below.
+ * Left out on purpose: the QE scheme and exact simulation, Asians and lookbacks, Greeks, a term structure of the
+ * parameters, a mcamd_group_* form and a shim name (the reference has no such model).  The smile of the model is
+ * mcamd_price_heston_smile, its cliquets mcamd_price_heston_cliquet and its single barriers
+ * mcamd_price_heston_barrier, below.
  * New. */
 #define MCAMD_HESTON_FULL_TRUNCATION 0
 
@@ -1555,8 +1556,9 @@ int mcamd_price_heston_smile_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, co
  * theta, xi, rho finite; v0, kappa, theta, xi >= 0; |rho| <= 1; then cliquet->q != heston->q; with equal yields
  * mcamd_price_heston's refusals of sim are those already made, and S0 and K are not looked at.  Then the context.  An
  * empty shard returns zeros and launches nothing; its enqueue form writes a zero record in stream order.
- * Out of scope: the QE scheme, barriers and Asians under Heston, Greeks, volatility (square-root) swaps, non-uniform
- * reset schedules, a mcamd_group_* form and a shim name (the reference has no such product).  New. */
+ * Out of scope: the QE scheme, Asians under Heston (single barriers are mcamd_price_heston_barrier, below), Greeks,
+ * volatility (square-root) swaps, non-uniform reset schedules, a mcamd_group_* form and a shim name (the reference has no
+ * such product).  New. */
 typedef struct mcamd_heston_cliquet_result {   /* 112 bytes */
     double price;            /* exp(-rT) * mean(y) */
     double std_err;
@@ -1579,6 +1581,93 @@ int mcamd_price_heston_cliquet(mcamd_ctx *ctx, const mcamd_option *opt, const mc
 int mcamd_price_heston_cliquet_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
                                        const mcamd_heston *heston, const mcamd_cliquet *cliquet, void *d_samples,
                                        double *d_stats);
+
+/* ---- Single-barrier options under Heston: down / up, knock-out / knock-in, call / put, discrete or continuous ----
+ * Additive to ABI version 5: first carried by the build that ships csrc/heston_barrier.hip (no struct of an earlier call
+ * changed, so MCAMD_ABI_VERSION stays 5; a caller finds out with dlsym).  mcamd_price_barrier's product on
+ * mcamd_price_heston's paths: the volatility moves with and after the spot's approach to the level, which a calibrated
+ * local-volatility surface cannot say.  Both job structs are the earlier calls', unchanged.
+ *   Inputs.  r, T, S0, K and the level B come from opt; opt->v is ignored.  The model, the scheme and q come from
+ *       heston, the kind and the monitoring from barrier.  barrier->payoff is the payoff; heston->payoff states it a
+ *       second time and must be equal.
+ *   Paths.  Those of mcamd_price_heston, draw for draw and operation for operation: X_0 = 0 and v_0 = v0, the same
+ *       full-truncation step in the path precision with dt = T / n_steps, z from Philox blocks 0, 1, .. and z' from
+ *       blocks 2^63, 2^63 + 1, .. of the path's subsequence (the GLOBAL path id).  Nothing else is drawn.  v+_i is the
+ *       variance step i was taken at, max(v_{i-1}, 0), i = 1..n.
+ *   Barrier.  b = ln(B / S0), formed in double on the host and narrowed once.  The tests and distances are those of
+ *       mcamd_price_barrier in the path precision: hit at step end i iff b > X_i (down) or X_i > b (up), strictly;
+ *       d_i = X_i - b (down) or b - X_i (up), d_0 = |b|; a path is alive while no step end has hit.
+ *   Survival weight w.
+ *       MCAMD_MONITOR_DISCRETE    w = 1 on a path that is alive at the end, 0 once hit.
+ *       MCAMD_MONITOR_CONTINUOUS  w = prod_i f_i on such a path, 0 once hit;  q_i = 2 d_{i-1} d_i / (v+_i dt);
+ *           f_i = 1 - exp(-q_i) where the path is alive after step i and q_i < Q, Q = 38 (fp64) / 18 (fp32) in
+ *           natural-log units, and f_i is DEFINED as exactly 1 elsewhere.  The test is made without a division, in the
+ *           path precision: the factor is taken iff kq d_{i-1} d_i < q_cut v+_i, with kq = 2 / dt and q_cut = Q (fp32:
+ *           both divided by ln 2 on the host, the factor being 1 - 2^{-q}); then q_i = (kq d_{i-1} d_i) / v+_i.  So a
+ *           step taken at v+_i = 0 has f_i = 1 by definition, and rightly: it moves along a straight line, and the test
+ *           at its end decides.  The rule is part of the definition: a restatement skips the factors the kernel skips.
+ *       Why this weight.  The scheme freezes v+ over a step, so the bridge between two step ends is a Brownian bridge of
+ *       variance rate v+_i and f_i is its exact probability of staying on the live side.  The continuous sample is
+ *       therefore unbiased for the continuously monitored barrier OF THE SCHEME'S frozen-variance interpolation at
+ *       every n_steps (n_steps = 1 included); against the model it carries the scheme's O(dt) weak error, like every
+ *       price under MCAMD_HESTON_FULL_TRUNCATION.  The discrete sample prices the barrier monitored at the n step ends.
+ *   Sample, in fp64 from the path-precision w and h, as mcamd_price_localvol forms it:  S_T = S0 e^{X_n} through the
+ *       exponential that ends a mcamd_price_heston path, h = max(+-(S_T - K), 0);  knock-out  y = w h(S_T), and 0 for a
+ *       path that was hit, whatever its unfinished price is;  knock-in  y = (1 - w) h(S_T).  No rebate.
+ *   price = exp(-rT) mean(y), std_err as in mcamd_finalize.
+ *   Early exit.  A knock-out wavefront leaves the walk at the first Philox-block end at which every one of its lanes is
+ *       knocked; a knock-in runs to maturity (it needs S_T).
+ *   Diagnostics.  The steps of a path that COUNT are all n for a knock-in and, for a knock-out, the steps it entered not
+ *       yet hit.  live = the steps entered not yet hit (both kinds); trunc = the counted steps entered with v < 0;
+ *       vs = sum of v+ over the counted steps, in the path precision in step order.  All depend on the path's global id
+ *       alone (not on where its wavefront stopped), so shards add.
+ * d_samples (nullable, device): n_paths_local values of the path precision; [local path] receives y.
+ * d_state (nullable, device): 3 n_paths_local values of the path precision; [local path] receives S_T,
+ * [n_paths_local + local path] the raw v_n and [2 n_paths_local + local path] w.  A knock-out path that was hit gets a
+ * quiet NaN for S_T and v_n and w = 0: its walk may stop early, and where depends on its wavefront's other lanes, so no
+ * value is defined there.
+ * res: price .. n as mcamd_result; live_steps = sum of live; work_steps = 64 x the steps each wavefront ran;
+ * truncated_steps = sum of trunc; mean_variance = sum of vs / the counted lane-steps (n_paths_local n_steps for a
+ * knock-in, live_steps for a knock-out), formed on the host.  For a knock-in truncated_steps is mcamd_price_heston's
+ * exactly and mean_variance its value up to rounding.  The block record is {sum, sumsq, live, trunc, vs, wave-steps};
+ * the enqueue form leaves {sum, sumsq, live_steps, truncated_steps, sum of vs, n} in d_stats (device, >= 6 doubles):
+ * mcamd_finalize_stats serves it and mcamd_enqueued_kernel_ms covers it; work_steps is reported by the synchronous call
+ * only.  One launch, one fixed order of summation: two runs of one job give the same bits.
+ * Requirements (MCAMD_ERR_INVALID before any device work, in this order).  opt, sim, heston, barrier, res non-NULL.
+ * Then what mcamd_price_barrier refuses of the barrier: monitoring in range; barrier->reserved == 0; kind and
+ * barrier->payoff in range; B > 0 and finite; S0 strictly on the live side (down: S0 > B, up: 0 < S0 < B).  Then what
+ * mcamd_price_heston refuses: heston->payoff and scheme in range; heston->reserved == 0; q, v0, kappa, theta, xi, rho
+ * finite; v0, kappa, theta, xi >= 0; |rho| <= 1; r finite; use_window, P1, P2, Ik, Sk, Tk and opt->dt all 0; sim->flags
+ * 0 or MCAMD_FLAG_LOG_SPACE; what mcamd_price_paths refuses on sim (its fp64 exponent-range bound at the drift r - q
+ * alone); S0 > 0 and K > 0.  Then heston->payoff != barrier->payoff.  Then the context.  An empty shard returns zeros
+ * and launches nothing; its enqueue form writes a zero record in stream order.
+ * Left out on purpose: rebates; double barriers; lane compaction of knocked paths (live_steps / work_steps is what it
+ * would start from); the QE scheme; Asians and lookbacks under Heston; Greeks; a mcamd_group_* form and a shim name
+ * (the reference has no such product); a closed form of the model's barrier price (none exists in general: with
+ * rho = 0 and r = q the continuous sample's expectation given the variance path is mcamd_barrier_price_f64 at r = 0 and
+ * v = sqrt(sum_i v+_i dt / T), at every n_steps, which tests/test_heston_barrier_cpu.py checks).  New. */
+typedef struct mcamd_heston_barrier_result {   /* 104 bytes */
+    double price;            /* exp(-rT) * mean(y) */
+    double std_err;
+    double ci_lo, ci_hi;     /* 95 % confidence interval */
+    double sum, sumsq;       /* the shard's raw fp64 sums of the undiscounted samples */
+    uint64_t n;              /* paths */
+    double live_steps;       /* lane-steps entered not yet hit */
+    double work_steps;       /* 64 x the steps each wavefront ran */
+    double truncated_steps;  /* counted lane-steps entered with v < 0 */
+    double mean_variance;    /* sum of v+ over the counted lane-steps / their number */
+    float kernel_ms;         /* HIP-event time of the kernel (it finishes its own sum: the whole call's device work) */
+    float total_ms;
+    uint32_t grid;           /* launch shape the engine chose */
+    uint32_t block;
+} mcamd_heston_barrier_result;
+
+int mcamd_price_heston_barrier(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_heston *heston,
+                               const mcamd_barrier *barrier, void *d_samples, void *d_state,
+                               mcamd_heston_barrier_result *res);
+int mcamd_price_heston_barrier_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                                       const mcamd_heston *heston, const mcamd_barrier *barrier, void *d_samples,
+                                       void *d_state, double *d_stats);
 
 /* Host closed form of the model itself (not of the scheme, whose bias is first order in dt).  With F = S0 e^{(r-q)T},
  * D = e^{-rT}, k = ln(F / K) and phi the characteristic function of ln(S_T / F) in the branch-cut-safe form (Albrecher,

@@ -18,7 +18,7 @@ LIB = os.path.join(PKG, "libmcamd.so")
 SOURCES = ["price_f64.hip", "price_f32.hip", "store.hip", "aux.hip", "nmc.hip", "greeks.hip", "american.hip",
            "american_dual.hip", "barrier.hip", "lookback.hip", "basket.hip", "asian.hip", "autocall.hip", "localvol.hip",
            "localvol_smile.hip", "autocall_localvol.hip", "autocall_localvol_f32.hip", "localvol_greeks.hip", "cliquet.hip",
-           "heston.hip", "heston_smile.hip", "heston_cliquet.hip", "smile.hip", "capi_heston.cpp", "capi_smile.cpp",
+           "heston.hip", "heston_smile.hip", "heston_cliquet.hip", "heston_barrier.hip", "smile.hip", "capi_heston.cpp", "capi_smile.cpp",
            "capi.cpp", "capi_american.cpp", "capi_pathdep.cpp", "capi_multi.cpp", "capi_localvol.cpp", "closed_forms.cpp",
            "group.cpp"]
 HEADERS = ["launch.hpp", "mc_device.hpp", "path_consts.hpp", "path_frame.hpp", "fast64.hpp", "tables64.inc", "tables64_consts.inc",
@@ -26,7 +26,7 @@ HEADERS = ["launch.hpp", "mc_device.hpp", "path_consts.hpp", "path_frame.hpp", "
            "american_dual.hpp", "barrier.hpp", "lookback.hpp", "basket.hpp", "basket_device.hpp", "asian.hpp", "autocall.hpp",
            "localvol.hpp", "localvol_device.hpp", "localvol_smile.hpp", "autocall_localvol.hpp",
            "autocall_localvol_impl.hpp", "localvol_greeks.hpp", "cliquet.hpp", "cliquet_device.hpp", "heston.hpp",
-           "heston_cliquet.hpp",
+           "heston_cliquet.hpp", "heston_barrier.hpp",
            "heston_device.hpp", "heston_smile.hpp", "smile.hpp", "smile_device.hpp", "capi_internal.hpp"]
 ARCH = "gfx950"
 

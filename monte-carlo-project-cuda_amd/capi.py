@@ -76,6 +76,7 @@ EXPORTS = [
     "mcamd_price_heston", "mcamd_price_heston_enqueue", "mcamd_heston_price_f64",
     "mcamd_price_heston_smile", "mcamd_price_heston_smile_enqueue",
     "mcamd_price_heston_cliquet", "mcamd_price_heston_cliquet_enqueue", "mcamd_heston_cliquet_price_f64",
+    "mcamd_price_heston_barrier", "mcamd_price_heston_barrier_enqueue",
 ]
 
 
@@ -284,6 +285,20 @@ class HestonCliquetResult(C.Structure):
 assert C.sizeof(HestonCliquetResult) == 112   # pinned in include/mcamd.h
 
 
+class HestonBarrierResult(C.Structure):
+    """mcamd_heston_barrier_result"""
+    _fields_ = [("price", C.c_double), ("std_err", C.c_double), ("ci_lo", C.c_double), ("ci_hi", C.c_double),
+                ("sum", C.c_double), ("sumsq", C.c_double), ("n", C.c_uint64), ("live_steps", C.c_double),
+                ("work_steps", C.c_double), ("truncated_steps", C.c_double), ("mean_variance", C.c_double),
+                ("kernel_ms", C.c_float), ("total_ms", C.c_float), ("grid", C.c_uint32), ("block", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+assert C.sizeof(HestonBarrierResult) == 104   # pinned in include/mcamd.h
+
+
 class Smile(C.Structure):
     """mcamd_smile: the payoff of every node, the numbers of expiries and strikes, and the dividend yield
     mcamd_price_localvol_smile prices a strike-by-expiry set of vanillas with."""
@@ -419,7 +434,11 @@ def load() -> C.CDLL:
                                              vp, C.POINTER(HestonCliquetResult)]
     L.mcamd_price_heston_cliquet_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Heston),
                                                      C.POINTER(Cliquet), vp, vp]
-    L.mcamd_heston_cliquet_price_f64.argtypes = [i32] + [f64] * 8 + [C.c_uint32, C.c_uint32, f64, f64, C.POINTER(f64)]
+    L.mcamd_price_heston_barrier.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Heston), C.POINTER(Barrier),
+                                             vp, vp, C.POINTER(HestonBarrierResult)]
+    L.mcamd_price_heston_barrier_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Heston),
+                                                     C.POINTER(Barrier), vp, vp, vp]
+    L.mcamd_heston_cliquet_price_f64.argtypes =[i32] + [f64] * 8 + [C.c_uint32, C.c_uint32, f64, f64, C.POINTER(f64)]
     L.mcamd_localvol_sigma_f64.argtypes = [C.POINTER(LocalVolGrid), C.POINTER(f64), C.c_uint32, C.c_uint32, f64,
                                            C.POINTER(f64)]
     L.mcamd_bs_price_f64.argtypes = [f64, f64, f64, f64, f64, f64, i32, C.POINTER(f64)]
@@ -956,6 +975,25 @@ class Context:
         tensor `stats` (>= 6 doubles; finalize_stats)."""
         _check(self._L.mcamd_price_heston_cliquet_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(heston),
                                                           C.byref(cliquet), _ptr(samples), _ptr(stats)))
+
+    def price_heston_barrier(self, opt: Option, sim: Sim, heston: Heston, barrier: Barrier, samples=None,
+                             state=None) -> HestonBarrierResult:
+        """Single-barrier option on the paths of price_heston (mcamd_price_heston_barrier); r, T, S0, K and the level B
+        come from opt, opt.v is ignored, and heston.payoff must equal barrier.payoff.  samples: optional device tensor
+        of n_paths_local values of the path precision that receives each path's undiscounted sample; state: optional
+        device tensor of 3 x n_paths_local such values that receives S_T, then the raw final variance, then the
+        survival weight (a knock-out path that was hit: NaN, NaN, 0)."""
+        res = HestonBarrierResult()
+        _check(self._L.mcamd_price_heston_barrier(self._h, C.byref(opt), C.byref(sim), C.byref(heston), C.byref(barrier),
+                                                  _ptr(samples), _ptr(state), C.byref(res)))
+        return res
+
+    def price_heston_barrier_enqueue(self, opt: Option, sim: Sim, heston: Heston, barrier: Barrier, stats, samples=None,
+                                     state=None) -> None:
+        """Asynchronous: leaves {sum, sumsq, live_steps, truncated_steps, sum of v+ over the counted lane-steps, n} in
+        the device tensor `stats` (>= 6 doubles; finalize_stats)."""
+        _check(self._L.mcamd_price_heston_barrier_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(heston),
+                                                          C.byref(barrier), _ptr(samples), _ptr(state), _ptr(stats)))
 
     def price_heston_smile(self, opt: Option, sim: Sim, heston: Heston, expiry_steps, strikes, state=None):
         """len(expiry_steps) x len(strikes) vanillas on one set of price_heston's paths (mcamd_price_heston_smile);

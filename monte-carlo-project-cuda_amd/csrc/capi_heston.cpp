@@ -1,15 +1,17 @@
 // capi_heston.cpp — the calls of the C ABI that walk Heston stochastic-volatility paths under the full-truncation Euler
-// scheme: European options, the strike-by-expiry smile, and cliquets.  Each call is a prepare step (the refusals and the job) and
-// its synchronous and enqueue forms; the refusals keep the order of the other families: the request alone, then the
-// context.
+// scheme: European options, the strike-by-expiry smile, cliquets and single barriers.  Each call is a prepare step (the
+// refusals and the job) and its synchronous and enqueue forms; the refusals keep the order of the other families: the
+// request alone, then the context.
 #include "capi_internal.hpp"
 #include "heston.hpp"
+#include "heston_barrier.hpp"
 #include "heston_cliquet.hpp"
 #include "heston_smile.hpp"
 
 static_assert(sizeof(mcamd_heston) == 64 && sizeof(mcamd_heston_result) == 96,
               "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
 static_assert(sizeof(mcamd_heston_cliquet_result) == 112, "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
+static_assert(sizeof(mcamd_heston_barrier_result) == 104, "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
 static_assert(MCAMD_HESTON_FULL_TRUNCATION == mcamd::kHestonFullTruncation, "the kernels' scheme is MCAMD_HESTON_*");
 
 using namespace mcamd::capi;
@@ -161,6 +163,52 @@ int prepare_heston_cliquet(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_
                             }});
 }
 
+// The Heston barrier calls: mcamd_price_heston's paths with mcamd_price_barrier's tests and samples.  The refusals:
+// what prepare_barrier refuses of the barrier (monitoring, reserved, then kind, payoff, B and the side of S0), what
+// prepare_heston refuses (the job and the model, r, opt's other fields, sim->flags and sim at the drift r - q, S0 and K),
+// the two payoffs that must be one, then the context.  opt->v is ignored.
+template <typename Drive>
+int prepare_heston_barrier(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_heston *hs,
+                           const mcamd_barrier *bar, void *d_samples, void *d_state, Drive drive)
+{
+    if (!opt || !sim || !hs || !bar) return fail(MCAMD_ERR_INVALID, "opt, sim, heston and barrier must be non-NULL");
+    if (bar->monitoring != MCAMD_MONITOR_DISCRETE && bar->monitoring != MCAMD_MONITOR_CONTINUOUS)
+        return fail(MCAMD_ERR_INVALID, "monitoring must be MCAMD_MONITOR_DISCRETE (0) or MCAMD_MONITOR_CONTINUOUS (1), "
+                                       "got %d", bar->monitoring);
+    if (bar->reserved != 0) return fail(MCAMD_ERR_INVALID, "barrier->reserved must be 0, got %d", bar->reserved);
+    if (int rc = check_barrier_kind(opt->S0, opt->B, bar->kind, bar->payoff)) return rc;
+    if (int rc = check_heston_job(opt, hs)) return rc;
+    mcamd::HestonBarrierJob job;
+    job.walk = heston_walk(opt, sim, hs);
+    // as prepare_heston: the level has been looked at above and bounds nothing here
+    mcamd_option seen = *opt;
+    seen.B = 0.0;
+    if (int rc = check_drift_request("Heston barrier", seen, sim, &job.walk.mu, 1)) return rc;
+    if (!(opt->S0 > 0.0) || !(opt->K > 0.0))
+        return fail(MCAMD_ERR_INVALID, "Heston options need S0 > 0 and K > 0 (S0 = %g, K = %g)", opt->S0, opt->K);
+    if (hs->payoff != bar->payoff)
+        return fail(MCAMD_ERR_INVALID, "heston->payoff = %d and barrier->payoff = %d must be the same payoff", hs->payoff,
+                    bar->payoff);
+    if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
+    if (sim->n_paths_local == 0) return drive(empty_call());
+    job.scheme = hs->scheme;
+    job.S0 = opt->S0;
+    job.K = opt->K;
+    job.B = opt->B;
+    const BarrierSides sides = barrier_sides(bar->kind);
+    job.up = sides.up;
+    job.out = sides.out;
+    job.continuous = bar->monitoring == MCAMD_MONITOR_CONTINUOUS;
+    job.put = bar->payoff == MCAMD_PAYOFF_PUT;
+    job.d_samples = d_samples;
+    job.d_state = d_state;
+    const uint32_t grid = mcamd::one_path_per_thread_grid(sim->n_paths_local);
+    return drive(DeviceCall{sim->n_paths_local, grid, mcamd::kHestonBarrierRecord, 6, Finish::kFolded,
+                            [&](const mcamd::FinishSpec &fs) {
+                                return mcamd::launch_heston_barrier(job, ctx->d_partials, grid, fs, ctx->stream);
+                            }});
+}
+
 }  // namespace
 
 extern "C" {
@@ -248,6 +296,44 @@ int mcamd_price_heston_cliquet_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, 
                                        double *d_stats)
 {
     return prepare_heston_cliquet(ctx, opt, sim, heston, cliquet, d_samples,
+                                  [&](const auto &call) { return run_enqueue(ctx, call, d_stats); });
+}
+
+int mcamd_price_heston_barrier(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_heston *heston,
+                               const mcamd_barrier *barrier, void *d_samples, void *d_state,
+                               mcamd_heston_barrier_result *res)
+{
+    if (!res) return fail(MCAMD_ERR_INVALID, "opt, sim, heston, barrier and res must be non-NULL");
+    std::memset(res, 0, sizeof *res);
+    return prepare_heston_barrier(ctx, opt, sim, heston, barrier, d_samples, d_state, [&](const auto &call) {
+        return run_sync(ctx, call, res, [&](const double *rec) {
+            // {sum, sumsq, live lane-steps, counted lane-steps entered with v < 0, sum of v+ over the counted
+            // lane-steps, wave-steps}
+            const uint64_t n = sim->n_paths_local;
+            const Estimate e = estimate(rec[0], rec[1], n, std::exp(-opt->r * opt->T));
+            res->sum = rec[0];
+            res->sumsq = rec[1];
+            res->n = n;
+            res->price = e.value;
+            res->std_err = e.std_err;
+            set_ci(res);
+            res->live_steps = rec[2];
+            res->work_steps = 64.0 * rec[5];
+            res->truncated_steps = rec[3];
+            // the steps that count: a knock-in's all, a knock-out's live ones (every path enters its first step live)
+            const double counted = barrier_sides(barrier->kind).out
+                                       ? rec[2]
+                                       : static_cast<double>(n) * static_cast<double>(sim->n_steps);
+            res->mean_variance = rec[4] / counted;
+        });
+    });
+}
+
+int mcamd_price_heston_barrier_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                                       const mcamd_heston *heston, const mcamd_barrier *barrier, void *d_samples,
+                                       void *d_state, double *d_stats)
+{
+    return prepare_heston_barrier(ctx, opt, sim, heston, barrier, d_samples, d_state,
                                   [&](const auto &call) { return run_enqueue(ctx, call, d_stats); });
 }
 

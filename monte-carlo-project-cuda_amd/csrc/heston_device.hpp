@@ -1,6 +1,6 @@
 // heston_device.hpp — the step of a Heston path under the full-truncation Euler scheme in the log-price, for any kernel
-// that walks such paths (heston.hip, heston_smile.hip, heston_cliquet.hip; barriers and Asians can reuse it): the step
-// constants, where the variance's normals come from, and the move of one step.
+// that walks such paths (heston.hip, heston_smile.hip, heston_cliquet.hip, heston_barrier.hip; Asians can reuse it):
+// the step constants, where the variance's normals come from, and the move of one step.
 //
 // Definitions (include/mcamd.h, mcamd_price_heston): X = ln(S / S0) in NATURAL-log units, v the raw variance, which may
 // go below zero; v+ = max(v, 0) is what the drift, the diffusion and the mean reversion read.  With the step's two
