@@ -23,7 +23,7 @@ SOURCES = ["price_f64.hip", "price_f32.hip", "store.hip", "aux.hip", "nmc.hip", 
            "group.cpp"]
 HEADERS = ["launch.hpp", "mc_device.hpp", "path_consts.hpp", "path_frame.hpp", "fast64.hpp", "tables64.inc", "tables64_consts.inc",
            "price_impl.hpp", "nmc_compact.hpp", "greeks.hpp", "american.hpp", "american_device.hpp",
-           "american_dual.hpp", "barrier.hpp", "lookback.hpp", "basket.hpp", "basket_device.hpp", "asian.hpp", "autocall.hpp",
+           "american_dual.hpp", "barrier.hpp", "barrier_device.hpp", "lookback.hpp", "basket.hpp", "basket_device.hpp", "asian.hpp", "autocall.hpp",
            "localvol.hpp", "localvol_device.hpp", "localvol_smile.hpp", "autocall_localvol.hpp",
            "autocall_localvol_impl.hpp", "localvol_greeks.hpp", "cliquet.hpp", "cliquet_device.hpp", "heston.hpp",
            "heston_cliquet.hpp", "heston_barrier.hpp",

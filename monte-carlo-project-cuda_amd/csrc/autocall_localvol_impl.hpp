@@ -60,7 +60,7 @@ struct AutocallLocalVolArgs {
     GridFinish fin;
 };
 
-// Where the step's floating-point constants live: the per-asset grid constants and drifts follow lv_resident (vector
+// Where the step's floating-point constants live: the per-asset grid constants and drifts follow resident_t (vector
 // registers in fp32 only); the D (D + 1) / 2 entries of the Cholesky factor follow basket_device.hpp's bk_resident
 // (vector registers in fp32, and in fp64 from D = 3): left scalar they do not fit beside the kernel's other scalars and
 // are read back one v_readlane at a time inside the step, which measured 5 % (D = 3) and 7 % (D = 8) slower on the
@@ -84,11 +84,11 @@ __global__ __launch_bounds__(kBlock) void autocall_localvol_kernel(AutocallLocal
 #pragma unroll
     for (int j = 0; j < D; ++j) {
         axis[j] = lv_resident(a.axis(j));
-        mu_dt[j] = lv_resident(a.mu_dt[j]);
+        mu_dt[j] = resident_t(a.mu_dt[j]);
     }
 #pragma unroll
     for (int c = 0; c < NC; ++c) chol[c] = bk_resident<D>(a.chol[c]);
-    const T half_dt = lv_resident(a.half_dt), sqrt_dt = lv_resident(a.sqrt_dt);
+    const T half_dt = resident_t(a.half_dt), sqrt_dt = resident_t(a.sqrt_dt);
     const uint32_t n_groups = a.n_steps / G;
     const uint32_t rem = a.n_steps - n_groups * G;
     double acc[kAutocallRecord] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};

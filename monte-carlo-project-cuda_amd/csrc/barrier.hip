@@ -1,12 +1,7 @@
 // barrier.hip — single-barrier options for gfx950 (both path precisions): down / up, knock-out / knock-in, call / put,
 // monitored at the step ends (discrete) or all the time (continuous, by the Brownian-bridge survival weight).
 //
-// Definitions (include/mcamd.h, mcamd_price_barrier): X_i = ln(S_i / S0) after step i, b = ln(B / S0); a path is hit at
-// step end i when b > X_i (down) or X_i > b (up); d_i = X_i - b (down) or b - X_i (up), d_0 = |b|.  The survival weight
-// w is the product over the steps of 1{no hit at i} and — continuous monitoring — of f_i = 1 - exp(-q_i) with
-// q_i = 2 d_{i-1} d_i / (v^2 dt), where f_i is DEFINED as 1 for q_i >= Q (Q = 38 in fp64, 18 in fp32: there
-// exp(-q) < 2^-54 / 2^-25 and 1 - exp(-q) rounds to 1 anyway).  The sample is w h(S_T) (knock-out) or (1 - w) h(S_T)
-// (knock-in), formed once per path in fp64.
+// Definitions: barrier_device.hpp, with the constant volatility v in the bridge factor and X, b in exponent units.
 //
 // The loop is walk_steps (mc_device.hpp) on the log-space window step of simulate_sample: per Philox block one
 // Exponents<T>::fill, per step acc += x, one subtract for d, the strict compare.  The bridge factor costs one
@@ -14,6 +9,7 @@
 // wavefront (one ballot), and paths spend most of their steps far from the barrier.  A knock-out wavefront leaves the
 // step loop at the first block end where every lane is knocked; a knock-in runs to maturity, because it needs S_T.
 #include "barrier.hpp"
+#include "barrier_device.hpp"
 #include "path_consts.hpp"
 #include "path_frame.hpp"
 
@@ -69,11 +65,9 @@ __global__ __launch_bounds__(kBlock) void barrier_kernel(BarrierArgs<T> a, doubl
             blocks, [&](uint32_t k) { ex.fill(m, c, key, subsequence, k); }, [&](uint32_t, int j) { step(ex.x[j]); },
             [&] { return OUT && __builtin_amdgcn_ballot_w64(alive) == 0; });
         const T St = exp_of_logreturn(c.S_start, acc, m);
-        T h = a.put ? c.K - St : St - c.K;
-        h = h > T(0) ? h : T(0);
+        const T h = vanilla_payoff(a.put, c.K, St);
         const double wd = alive ? static_cast<double>(w) : 0.0;
-        // a knocked path of a knock-out pays 0 whatever its (possibly unfinished) price is
-        const double y = OUT ? (alive ? wd * static_cast<double>(h) : 0.0) : (1.0 - wd) * static_cast<double>(h);
+        const double y = barrier_sample<OUT>(alive, wd, h);
         if (a.samples) a.samples[i] = static_cast<T>(y);
         add_sample(acc4, y);
         add_counters(acc4, steps_run, live);
@@ -82,31 +76,18 @@ __global__ __launch_bounds__(kBlock) void barrier_kernel(BarrierArgs<T> a, doubl
     finish_paths(acc4, partials, a.fin);
 }
 
-template <typename T, bool UP, bool CONT>
-static void launch_barrier_k(const BarrierJob &j, const BarrierArgs<T> &a, double *d_partials, uint32_t grid,
-                             hipStream_t stream)
-{
-    const dim3 g(grid), b(kBlock);
-    if (j.out) hipLaunchKernelGGL((barrier_kernel<T, UP, CONT, true>), g, b, 0, stream, a, d_partials);
-    else hipLaunchKernelGGL((barrier_kernel<T, UP, CONT, false>), g, b, 0, stream, a, d_partials);
-}
-
 template <typename T>
 static hipError_t launch_barrier_t(const BarrierJob &j, double *d_partials, uint32_t grid, const FinishSpec &fs,
                                    hipStream_t stream)
 {
-    const double u = exponent_unit<T>();   // and the natural log per unit of q:
-    const double q_unit = sizeof(T) == 4 ? kLn2 : 1.0;
-    const double q_cut = sizeof(T) == 4 ? 18.0 : 38.0;
-    const BarrierArgs<T> a{make_consts<T>(j.path), static_cast<T>(j.kq * u * u / q_unit), static_cast<T>(q_cut / q_unit),
-                           j.put ? 1 : 0, shard_of(j.path), static_cast<T *>(j.d_samples), grid_finish_of(fs)};
-    if (j.up) {
-        if (j.continuous) launch_barrier_k<T, true, true>(j, a, d_partials, grid, stream);
-        else launch_barrier_k<T, true, false>(j, a, d_partials, grid, stream);
-    } else {
-        if (j.continuous) launch_barrier_k<T, false, true>(j, a, d_partials, grid, stream);
-        else launch_barrier_k<T, false, false>(j, a, d_partials, grid, stream);
-    }
+    const double u = exponent_unit<T>();
+    const BridgeUnits bu = bridge_units<T>();
+    const BarrierArgs<T> a{make_consts<T>(j.path), static_cast<T>(j.kq * u * u / bu.q_unit), static_cast<T>(bu.q_cut),
+                           j.form.put ? 1 : 0, shard_of(j.path), static_cast<T *>(j.d_samples), grid_finish_of(fs)};
+    dispatch_barrier_form(j.form, [&](auto up, auto cont, auto out) {
+        hipLaunchKernelGGL((barrier_kernel<T, decltype(up)::value, decltype(cont)::value, decltype(out)::value>),
+                           dim3(grid), dim3(kBlock), 0, stream, a, d_partials);
+    });
     return hipGetLastError();
 }
 

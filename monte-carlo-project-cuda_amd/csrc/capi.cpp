@@ -243,17 +243,6 @@ Estimate estimate(double sum, double sumsq, uint64_t n, double disc)
     return {disc * mean, n ? disc * std::sqrt(var / N) : 0.0};
 }
 
-void finalize_into(double sum, double sumsq, uint64_t n, double r, double T, mcamd_result *res)
-{
-    const Estimate e = estimate(sum, sumsq, n, std::exp(-r * T));
-    res->sum = sum;
-    res->sumsq = sumsq;
-    res->n = n;
-    res->price = e.value;
-    res->std_err = e.std_err;
-    set_ci(res);
-}
-
 void finalize_cv_into(const double s[5], uint64_t n, double r, double T, mcamd_result *res)
 {
     const double disc = std::exp(-r * T);

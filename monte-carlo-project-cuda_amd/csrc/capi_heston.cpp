@@ -1,7 +1,8 @@
 // capi_heston.cpp — the calls of the C ABI that walk Heston stochastic-volatility paths under the full-truncation Euler
 // scheme: European options, the strike-by-expiry smile, cliquets and single barriers.  Each call is a prepare step (the
 // refusals and the job) and its synchronous and enqueue forms; the refusals keep the order of the other families: the
-// request alone, then the context.
+// request alone, then the context.  The stages the prepare steps share are check_heston_job and check_heston_walk
+// here, check_barrier_terms and barrier_form in capi_pathdep.cpp and check_smile_nodes in capi_smile.cpp.
 #include "capi_internal.hpp"
 #include "heston.hpp"
 #include "heston_barrier.hpp"
@@ -49,11 +50,33 @@ int check_heston_job(const mcamd_option *opt, const mcamd_heston *hs)
     return MCAMD_OK;
 }
 
-// The walk of both jobs, read once check_heston_job has passed.  The refusals of sim and opt come after it: until then
+// The walk of every job, read once check_heston_job has passed.  The refusals of sim and opt come after it: until then
 // dt may be anything (n_steps == 0 divides by zero, in floating point) and nothing reads it.
 mcamd::HestonWalk heston_walk(const mcamd_option *opt, const mcamd_sim *sim, const mcamd_heston *hs)
 {
-    return {path_range(sim), opt->r - hs->q, even_dt(opt, sim), hs->v0, hs->kappa, hs->theta, hs->xi, hs->rho};
+    return {path_range(sim), opt->r - hs->q, even_dt(opt, sim), hs->v0, hs->kappa, hs->theta, hs->xi, hs->rho, hs->scheme};
+}
+
+// The walk stage of the calls that price off the spot (European, smile, barrier), after check_heston_job: the walk,
+// then opt and sim at the drift r - q (what: how check_drift_request's messages call the product), then S0 and, with a
+// strike of the option's own, K.  The drift check runs as the local-volatility calls' does, on a copy whose ignored
+// fields are harmless (the variance is random: no bound on the request can cover it, so the drift stands alone in the
+// fp64 exponent-range bound): the level bounds nothing here, and without a strike (the smile, whose nodes carry
+// theirs) K does not either.  The cliquet keeps its own order (prepare_heston_cliquet).
+int check_heston_walk(const char *what, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_heston *hs,
+                      bool with_strike, mcamd::HestonWalk *walk)
+{
+    *walk = heston_walk(opt, sim, hs);
+    mcamd_option seen = *opt;
+    seen.B = 0.0;
+    if (!with_strike) seen.K = 1.0;
+    if (int rc = check_drift_request(what, seen, sim, &walk->mu, 1)) return rc;
+    if (!with_strike) {
+        if (!(opt->S0 > 0.0)) return fail(MCAMD_ERR_INVALID, "Heston smile options need S0 > 0 (S0 = %g)", opt->S0);
+    } else if (!(opt->S0 > 0.0) || !(opt->K > 0.0)) {
+        return fail(MCAMD_ERR_INVALID, "Heston options need S0 > 0 and K > 0 (S0 = %g, K = %g)", opt->S0, opt->K);
+    }
+    return MCAMD_OK;
 }
 
 // The Heston calls.  The kernel always finishes its own sum (one_path_per_thread_grid caps the grid); every refusal
@@ -65,17 +88,9 @@ int prepare_heston(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim
     if (!opt || !sim || !hs) return fail(MCAMD_ERR_INVALID, "opt, sim and heston must be non-NULL");
     if (int rc = check_heston_job(opt, hs)) return rc;
     mcamd::HestonJob job;
-    job.walk = heston_walk(opt, sim, hs);
-    // as the local-volatility calls: on a copy whose ignored fields are harmless (the variance is random: no bound on
-    // the request can cover it, so the drift r - q stands alone in the fp64 exponent-range bound)
-    mcamd_option seen = *opt;
-    seen.B = 0.0;
-    if (int rc = check_drift_request("Heston", seen, sim, &job.walk.mu, 1)) return rc;
-    if (!(opt->S0 > 0.0) || !(opt->K > 0.0))
-        return fail(MCAMD_ERR_INVALID, "Heston options need S0 > 0 and K > 0 (S0 = %g, K = %g)", opt->S0, opt->K);
+    if (int rc = check_heston_walk("Heston", opt, sim, hs, true, &job.walk)) return rc;
     if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
     if (sim->n_paths_local == 0) return drive(empty_call());
-    job.scheme = hs->scheme;
     job.S0 = opt->S0;
     job.K = opt->K;
     job.put = hs->payoff == MCAMD_PAYOFF_PUT;
@@ -103,13 +118,7 @@ int prepare_heston_smile(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_si
     mcamd::HestonSmileJob job;
     if (int rc = check_smile_nodes(n_expiries, n_strikes, h_expiry_steps, sim->n_steps, h_strikes, hs->payoff, &job.nodes))
         return rc;
-    job.walk = heston_walk(opt, sim, hs);
-    // as prepare_heston, on a copy that carries no strike of its own either
-    mcamd_option seen = *opt;
-    seen.B = 0.0;
-    seen.K = 1.0;
-    if (int rc = check_drift_request("Heston smile", seen, sim, &job.walk.mu, 1)) return rc;
-    if (!(opt->S0 > 0.0)) return fail(MCAMD_ERR_INVALID, "Heston smile options need S0 > 0 (S0 = %g)", opt->S0);
+    if (int rc = check_heston_walk("Heston smile", opt, sim, hs, false, &job.walk)) return rc;
     if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
     job.S0 = opt->S0;
     job.d_state = d_state;
@@ -144,7 +153,6 @@ int prepare_heston_cliquet(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_
     if (sim->n_paths_local == 0) return drive(empty_call());
     mcamd::HestonCliquetJob job;
     job.walk = heston_walk(opt, sim, hs);
-    job.scheme = hs->scheme;
     job.kind = cq->kind;
     job.reset_every = cq->reset_every;
     job.first_period = cq->first_period;
@@ -172,34 +180,19 @@ int prepare_heston_barrier(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_
                            const mcamd_barrier *bar, void *d_samples, void *d_state, Drive drive)
 {
     if (!opt || !sim || !hs || !bar) return fail(MCAMD_ERR_INVALID, "opt, sim, heston and barrier must be non-NULL");
-    if (bar->monitoring != MCAMD_MONITOR_DISCRETE && bar->monitoring != MCAMD_MONITOR_CONTINUOUS)
-        return fail(MCAMD_ERR_INVALID, "monitoring must be MCAMD_MONITOR_DISCRETE (0) or MCAMD_MONITOR_CONTINUOUS (1), "
-                                       "got %d", bar->monitoring);
-    if (bar->reserved != 0) return fail(MCAMD_ERR_INVALID, "barrier->reserved must be 0, got %d", bar->reserved);
-    if (int rc = check_barrier_kind(opt->S0, opt->B, bar->kind, bar->payoff)) return rc;
+    if (int rc = check_barrier_terms(bar, opt->S0, opt->B)) return rc;
     if (int rc = check_heston_job(opt, hs)) return rc;
     mcamd::HestonBarrierJob job;
-    job.walk = heston_walk(opt, sim, hs);
-    // as prepare_heston: the level has been looked at above and bounds nothing here
-    mcamd_option seen = *opt;
-    seen.B = 0.0;
-    if (int rc = check_drift_request("Heston barrier", seen, sim, &job.walk.mu, 1)) return rc;
-    if (!(opt->S0 > 0.0) || !(opt->K > 0.0))
-        return fail(MCAMD_ERR_INVALID, "Heston options need S0 > 0 and K > 0 (S0 = %g, K = %g)", opt->S0, opt->K);
+    if (int rc = check_heston_walk("Heston barrier", opt, sim, hs, true, &job.walk)) return rc;
     if (hs->payoff != bar->payoff)
         return fail(MCAMD_ERR_INVALID, "heston->payoff = %d and barrier->payoff = %d must be the same payoff", hs->payoff,
                     bar->payoff);
     if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
     if (sim->n_paths_local == 0) return drive(empty_call());
-    job.scheme = hs->scheme;
     job.S0 = opt->S0;
     job.K = opt->K;
     job.B = opt->B;
-    const BarrierSides sides = barrier_sides(bar->kind);
-    job.up = sides.up;
-    job.out = sides.out;
-    job.continuous = bar->monitoring == MCAMD_MONITOR_CONTINUOUS;
-    job.put = bar->payoff == MCAMD_PAYOFF_PUT;
+    job.form = barrier_form(bar->kind, bar->monitoring, bar->payoff);
     job.d_samples = d_samples;
     job.d_state = d_state;
     const uint32_t grid = mcamd::one_path_per_thread_grid(sim->n_paths_local);
@@ -222,17 +215,10 @@ int mcamd_price_heston(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim 
         return run_sync(ctx, call, res, [&](const double *rec) {
             // {sum, sumsq, lane-steps entered with v < 0, sum of the paths' average variance}
             const uint64_t n = sim->n_paths_local;
-            const Estimate e = estimate(rec[0], rec[1], n, std::exp(-opt->r * opt->T));
-            res->sum = rec[0];
-            res->sumsq = rec[1];
-            res->n = n;
-            res->price = e.value;
-            res->std_err = e.std_err;
-            set_ci(res);
+            finalize_into(rec[0], rec[1], n, opt->r, opt->T, res);
             res->truncated_steps = rec[2];
             res->mean_variance = rec[3] / static_cast<double>(n);
-            // there is no early exit: every wavefront runs every step
-            res->work_steps = 64.0 * static_cast<double>((n + 63) / 64) * static_cast<double>(sim->n_steps);
+            res->work_steps = full_walk_work_steps(n, sim->n_steps);
         });
     });
 }
@@ -274,19 +260,12 @@ int mcamd_price_heston_cliquet(mcamd_ctx *ctx, const mcamd_option *opt, const mc
             // {sum, sumsq, paths on the global floor, paths on the global cap, sum of the paths' average variance,
             // lane-steps entered with v < 0}
             const uint64_t n = sim->n_paths_local;
-            const Estimate e = estimate(rec[0], rec[1], n, std::exp(-opt->r * opt->T));
-            res->sum = rec[0];
-            res->sumsq = rec[1];
-            res->n = n;
-            res->price = e.value;
-            res->std_err = e.std_err;
-            set_ci(res);
+            finalize_into(rec[0], rec[1], n, opt->r, opt->T, res);
             res->n_floored = static_cast<uint64_t>(std::llround(rec[2]));
             res->n_capped = static_cast<uint64_t>(std::llround(rec[3]));
             res->mean_variance = rec[4] / static_cast<double>(n);
             res->truncated_steps = rec[5];
-            // there is no early exit: every wavefront runs every step
-            res->work_steps = 64.0 * static_cast<double>((n + 63) / 64) * static_cast<double>(sim->n_steps);
+            res->work_steps = full_walk_work_steps(n, sim->n_steps);
         });
     });
 }
@@ -310,13 +289,7 @@ int mcamd_price_heston_barrier(mcamd_ctx *ctx, const mcamd_option *opt, const mc
             // {sum, sumsq, live lane-steps, counted lane-steps entered with v < 0, sum of v+ over the counted
             // lane-steps, wave-steps}
             const uint64_t n = sim->n_paths_local;
-            const Estimate e = estimate(rec[0], rec[1], n, std::exp(-opt->r * opt->T));
-            res->sum = rec[0];
-            res->sumsq = rec[1];
-            res->n = n;
-            res->price = e.value;
-            res->std_err = e.std_err;
-            set_ci(res);
+            finalize_into(rec[0], rec[1], n, opt->r, opt->T, res);
             res->live_steps = rec[2];
             res->work_steps = 64.0 * rec[5];
             res->truncated_steps = rec[3];

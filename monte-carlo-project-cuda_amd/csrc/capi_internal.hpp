@@ -20,6 +20,7 @@ int mcamd_set_error_(int code, const char *msg);
 
 namespace mcamd {
 struct AutocallSchedule;   // autocall.hpp
+struct BarrierForm;        // barrier.hpp
 struct SmileNodes;         // smile.hpp
 }
 
@@ -66,7 +67,12 @@ inline BarrierSides barrier_sides(int kind)
 // ---- the checks a call shares with another family or with its closed form ------------------------------------------
 
 // capi_pathdep.cpp
+int check_monitoring(int monitoring);   // MCAMD_MONITOR_DISCRETE or MCAMD_MONITOR_CONTINUOUS
 int check_barrier_kind(double S0, double B, int kind, int payoff);
+// what the barrier calls of every model refuse of the barrier: monitoring, reserved, then check_barrier_kind
+int check_barrier_terms(const mcamd_barrier *bar, double S0, double B);
+// a job's form from enums that passed these checks; MCAMD_LOCALVOL_NO_BARRIER: neither up, out nor continuous
+mcamd::BarrierForm barrier_form(int kind, int monitoring, int payoff);
 int check_lookback_kind(double K, int strike, int payoff);
 int check_asian_kind(double K, int strike, int payoff, int include_spot);
 // capi_multi.cpp
@@ -248,15 +254,30 @@ struct Estimate {
 };
 Estimate estimate(double sum, double sumsq, uint64_t n, double disc);
 
-template <typename Result>   // mcamd_result, mcamd_american_result, mcamd_autocall_result, mcamd_cliquet_result,
-                             // mcamd_heston_result
+template <typename Result>   // mcamd_result, mcamd_american_result and every result struct finalize_into fills
 void set_ci(Result *res)
 {
     res->ci_lo = res->price - kZ95 * res->std_err;
     res->ci_hi = res->price + kZ95 * res->std_err;
 }
 
-void finalize_into(double sum, double sumsq, uint64_t n, double r, double T, mcamd_result *res);
+// the seven fields every price result starts with: sum, sumsq, n, price, std_err and the interval
+template <typename Result>   // mcamd_result, mcamd_autocall_result, mcamd_cliquet_result, mcamd_heston*_result
+void finalize_into(double sum, double sumsq, uint64_t n, double r, double T, Result *res)
+{
+    const Estimate e = estimate(sum, sumsq, n, std::exp(-r * T));
+    res->sum = sum;
+    res->sumsq = sumsq;
+    res->n = n;
+    res->price = e.value;
+    res->std_err = e.std_err;
+    set_ci(res);
+}
+// the lane-steps of a walk without an early exit: every wavefront that holds a path runs every step
+inline double full_walk_work_steps(uint64_t n, uint32_t n_steps)
+{
+    return 64.0 * static_cast<double>((n + 63) / 64) * static_cast<double>(n_steps);
+}
 void finalize_cv_into(const double s[5], uint64_t n, double r, double T, mcamd_result *res);
 // a price record with the work counters behind it: {sum, sumsq, wave-steps, live lane-steps}
 void finalize_counted_into(const double rec[4], uint64_t n, double r, double T, mcamd_result *res);

@@ -208,9 +208,7 @@ int prepare_localvol(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *s
     if (lv->barrier != MCAMD_LOCALVOL_NO_BARRIER && (lv->barrier < MCAMD_BARRIER_DOWN_OUT || lv->barrier > MCAMD_BARRIER_UP_IN))
         return fail(MCAMD_ERR_INVALID, "localvol->barrier must be MCAMD_LOCALVOL_NO_BARRIER (-1) or MCAMD_BARRIER_DOWN_OUT (0) "
                                        ".. MCAMD_BARRIER_UP_IN (3), got %d", lv->barrier);
-    if (lv->monitoring != MCAMD_MONITOR_DISCRETE && lv->monitoring != MCAMD_MONITOR_CONTINUOUS)
-        return fail(MCAMD_ERR_INVALID, "monitoring must be MCAMD_MONITOR_DISCRETE (0) or MCAMD_MONITOR_CONTINUOUS (1), "
-                                       "got %d", lv->monitoring);
+    if (int rc = check_monitoring(lv->monitoring)) return rc;
     if (lv->reserved != 0) return fail(MCAMD_ERR_INVALID, "localvol->reserved must be 0, got %d", lv->reserved);
     // a non-finite q is refused ahead of the barrier, which the drift stage comes after
     if (!std::isfinite(lv->q)) return fail(MCAMD_ERR_INVALID, "the dividend yield q must be finite, got %g", lv->q);
@@ -229,11 +227,7 @@ int prepare_localvol(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *s
     job.K = opt->K;
     job.B = opt->B;
     job.barrier = barrier;
-    const BarrierSides sides = barrier_sides(lv->barrier);   // MCAMD_LOCALVOL_NO_BARRIER: neither up nor out
-    job.up = sides.up;
-    job.out = sides.out;
-    job.continuous = barrier && lv->monitoring == MCAMD_MONITOR_CONTINUOUS;
-    job.put = lv->payoff == MCAMD_PAYOFF_PUT;
+    job.form = barrier_form(lv->barrier, lv->monitoring, lv->payoff);
     job.d_samples = d_samples;
     const uint32_t grid = mcamd::one_path_per_thread_grid(sim->n_paths_local);
     return drive(DeviceCall{sim->n_paths_local, grid, mcamd::kLocalVolRecord, 6, Finish::kFolded,
@@ -495,13 +489,7 @@ int mcamd_price_cliquet(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim
     return prepare_cliquet(ctx, opt, sim, cliquet, surface, d_samples, [&](const auto &call) {
         return run_sync(ctx, call, res, [&](const double *rec) {
             // {sum, sumsq, paths on the global floor, paths on the global cap, wave-steps}
-            const Estimate e = estimate(rec[0], rec[1], sim->n_paths_local, std::exp(-opt->r * opt->T));
-            res->sum = rec[0];
-            res->sumsq = rec[1];
-            res->n = sim->n_paths_local;
-            res->price = e.value;
-            res->std_err = e.std_err;
-            set_ci(res);
+            finalize_into(rec[0], rec[1], sim->n_paths_local, opt->r, opt->T, res);
             res->n_floored = static_cast<uint64_t>(std::llround(rec[2]));
             res->n_capped = static_cast<uint64_t>(std::llround(rec[3]));
             res->work_steps = 64.0 * rec[4];   // wave-steps x 64 lanes

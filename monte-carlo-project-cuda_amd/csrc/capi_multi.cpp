@@ -135,13 +135,7 @@ void make_autocall_schedule(const AutocallTerms &t, uint32_t M, double r, double
 
 void fill_autocall_result(const double *rec, uint64_t n, double r, double T, mcamd_autocall_result *res)
 {
-    const Estimate e = estimate(rec[0], rec[1], n, std::exp(-r * T));
-    res->sum = rec[0];
-    res->sumsq = rec[1];
-    res->n = n;
-    res->price = e.value;
-    res->std_err = e.std_err;
-    set_ci(res);
+    finalize_into(rec[0], rec[1], n, r, T, res);
     res->n_called = static_cast<uint64_t>(std::llround(rec[2]));
     res->sum_t_call = rec[3];
     res->n_knocked_in = static_cast<uint64_t>(std::llround(rec[4]));

@@ -13,6 +13,15 @@ using namespace mcamd::capi;
 
 namespace mcamd::capi {
 
+// What the barrier, lookback, local-volatility and Heston barrier calls refuse of a monitoring.
+int check_monitoring(int monitoring)
+{
+    if (monitoring != MCAMD_MONITOR_DISCRETE && monitoring != MCAMD_MONITOR_CONTINUOUS)
+        return fail(MCAMD_ERR_INVALID, "monitoring must be MCAMD_MONITOR_DISCRETE (0) or MCAMD_MONITOR_CONTINUOUS (1), "
+                                       "got %d", monitoring);
+    return MCAMD_OK;
+}
+
 // The refusals of the barrier calls that depend on the request's enums and levels alone (shared with the closed form
 // and the local-volatility call).
 int check_barrier_kind(double S0, double B, int kind, int payoff)
@@ -27,6 +36,20 @@ int check_barrier_kind(double S0, double B, int kind, int payoff)
         return fail(MCAMD_ERR_INVALID, "the spot must lie strictly on the live side of the barrier: %s (S0 = %g, B = %g)",
                     up ? "an up-barrier needs 0 < S0 < B" : "a down-barrier needs S0 > B", S0, B);
     return MCAMD_OK;
+}
+
+int check_barrier_terms(const mcamd_barrier *bar, double S0, double B)
+{
+    if (int rc = check_monitoring(bar->monitoring)) return rc;
+    if (bar->reserved != 0) return fail(MCAMD_ERR_INVALID, "barrier->reserved must be 0, got %d", bar->reserved);
+    return check_barrier_kind(S0, B, bar->kind, bar->payoff);
+}
+
+mcamd::BarrierForm barrier_form(int kind, int monitoring, int payoff)
+{
+    const BarrierSides sides = barrier_sides(kind);   // neither up nor out outside MCAMD_BARRIER_*
+    const bool barrier = kind >= MCAMD_BARRIER_DOWN_OUT && kind <= MCAMD_BARRIER_UP_IN;
+    return {sides.up, sides.out, barrier && monitoring == MCAMD_MONITOR_CONTINUOUS, payoff == MCAMD_PAYOFF_PUT};
 }
 
 // The refusals of the lookback calls that depend on the product alone (shared with the closed form).
@@ -65,22 +88,14 @@ int prepare_barrier(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *si
                     void *d_samples, Drive drive)
 {
     if (!opt || !sim || !bar) return fail(MCAMD_ERR_INVALID, "opt, sim and barrier must be non-NULL");
-    if (bar->monitoring != MCAMD_MONITOR_DISCRETE && bar->monitoring != MCAMD_MONITOR_CONTINUOUS)
-        return fail(MCAMD_ERR_INVALID, "monitoring must be MCAMD_MONITOR_DISCRETE (0) or MCAMD_MONITOR_CONTINUOUS (1), "
-                                       "got %d", bar->monitoring);
-    if (bar->reserved != 0) return fail(MCAMD_ERR_INVALID, "barrier->reserved must be 0, got %d", bar->reserved);
-    if (int rc = check_barrier_kind(opt->S0, opt->B, bar->kind, bar->payoff)) return rc;
+    if (int rc = check_barrier_terms(bar, opt->S0, opt->B)) return rc;
     if (int rc = check_spot_start("barrier", false, opt, sim)) return rc;
     if (int rc = check_request(opt, sim)) return rc;
     if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
     if (sim->n_paths_local == 0) return drive(empty_call());
     mcamd::BarrierJob job;
     job.path = make_plain_job(opt, sim, false, true);
-    const BarrierSides sides = barrier_sides(bar->kind);
-    job.up = sides.up;
-    job.out = sides.out;
-    job.continuous = bar->monitoring == MCAMD_MONITOR_CONTINUOUS;
-    job.put = bar->payoff == MCAMD_PAYOFF_PUT;
+    job.form = barrier_form(bar->kind, bar->monitoring, bar->payoff);
     job.kq = 2.0 / (opt->v * opt->v * even_dt(opt, sim));
     job.d_samples = d_samples;
     const uint32_t grid = mcamd::one_path_per_thread_grid(job.path.n_local);
@@ -97,9 +112,7 @@ int prepare_lookback(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *s
                      void *d_samples, Drive drive)
 {
     if (!opt || !sim || !lb) return fail(MCAMD_ERR_INVALID, "opt, sim and lookback must be non-NULL");
-    if (lb->monitoring != MCAMD_MONITOR_DISCRETE && lb->monitoring != MCAMD_MONITOR_CONTINUOUS)
-        return fail(MCAMD_ERR_INVALID, "monitoring must be MCAMD_MONITOR_DISCRETE (0) or MCAMD_MONITOR_CONTINUOUS (1), "
-                                       "got %d", lb->monitoring);
+    if (int rc = check_monitoring(lb->monitoring)) return rc;
     if (lb->reserved != 0) return fail(MCAMD_ERR_INVALID, "lookback->reserved must be 0, got %d", lb->reserved);
     if (int rc = check_lookback_kind(opt->K, lb->strike, lb->payoff)) return rc;
     if (int rc = check_spot_start("lookback", false, opt, sim)) return rc;

@@ -100,7 +100,7 @@ int run_smile_sync(mcamd_ctx *ctx, const SmileCall &call, double *h_stats, mcamd
         return fail(MCAMD_ERR_HIP, "the smile kernels left no result (the finishing kernel did not write every node)");
     std::memcpy(h_stats, ctx->h_smile, n_stats * sizeof(double));
     finalize_into(h_stats[nodes - 1], h_stats[n_stats - 1], call.n, call.r, call.t_last, res);
-    res->work_steps = 64.0 * static_cast<double>((call.n + 63) / 64) * static_cast<double>(call.last_step);
+    res->work_steps = full_walk_work_steps(call.n, call.last_step);
     res->live_steps = res->work_steps;
     res->kernel_ms = kernel_ms;
     res->total_ms = total_ms;

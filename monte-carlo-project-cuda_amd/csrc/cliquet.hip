@@ -47,8 +47,8 @@ __global__ __launch_bounds__(kBlock) void cliquet_kernel(CliquetArgs<T> a, doubl
     const MathCtx<T> m = MathCtx<T>::init();
     const PhiloxKeys key = PhiloxKeys::make(a.shard.seed);
     const LvAxis<T> axis = lv_resident(a.surf.axis);
-    const T mu_dt = lv_resident(a.mu_dt), half_dt = lv_resident(a.half_dt), sqrt_dt = lv_resident(a.sqrt_dt);
-    const T lo = lv_resident(a.lo), hi = lv_resident(a.hi), exp_scale = lv_resident(a.exp_scale);
+    const T mu_dt = resident_t(a.mu_dt), half_dt = resident_t(a.half_dt), sqrt_dt = resident_t(a.sqrt_dt);
+    const T lo = resident_t(a.lo), hi = resident_t(a.hi), exp_scale = resident_t(a.exp_scale);
     const StepBlocks blocks = step_blocks<NB>(a.n_steps);
     // an infinite bound never binds and counts nothing, whatever the arithmetic made of A
     const bool has_floor = a.g_lo > -__builtin_huge_val(), has_cap = a.g_hi < __builtin_huge_val();

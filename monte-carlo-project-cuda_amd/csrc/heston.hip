@@ -47,20 +47,15 @@ __global__ __launch_bounds__(kBlock) void heston_kernel(HestonArgs<T> a, double 
         T v = a.v0;           // the raw variance
         T v_sum = T(0);       // sum of v+ over the steps
         uint32_t trunc = 0;   // steps entered with v < 0
-        Normals<T> nz, nv;
+        HestonNormals<T> nz;
         walk_steps<NB>(
-            blocks,
-            [&](uint32_t kb) {
-                nz.fill(m, key, subsequence, kb);
-                nv.fill(m, key, subsequence, kHestonVarianceBlocks + kb);
-            },
+            blocks, [&](uint32_t kb) { nz.fill(m, key, subsequence, kb); },
             [&](uint32_t, int j) {
                 trunc += v < T(0) ? 1u : 0u;
-                v_sum += heston_move(X, v, nz.z[j], nv.z[j], c);
+                v_sum += heston_move(X, v, nz.z.z[j], nz.zv.z[j], c);
             });
         const T St = exp_of_logreturn(a.S0, X * a.exp_scale, m);
-        T h = a.put ? a.K - St : St - a.K;
-        h = h > T(0) ? h : T(0);
+        const T h = vanilla_payoff(a.put, a.K, St);
         const double y = static_cast<double>(h);
         if (a.samples) a.samples[i] = h;
         if (a.state) {
@@ -79,15 +74,12 @@ static hipError_t launch_heston_t(const HestonJob &j, double *d_partials, uint32
                                   hipStream_t stream)
 {
     HestonArgs<T> a;
-    a.c = heston_consts<T>(j.walk);
-    a.exp_scale = heston_exp_scale<T>();
-    a.v0 = static_cast<T>(j.walk.v0);
+    heston_walk_args<T>(a, j.walk);
     a.K = static_cast<T>(j.K);
     a.S0 = static_cast<T>(j.S0);
     a.inv_n = 1.0 / static_cast<double>(j.walk.paths.n_steps);
     a.put = j.put ? 1 : 0;
     a.n_steps = j.walk.paths.n_steps;
-    a.shard = shard_of(j.walk.paths);
     a.samples = static_cast<T *>(j.d_samples);
     a.state = static_cast<T *>(j.d_state);
     a.fin = grid_finish_of(fs);
@@ -99,9 +91,8 @@ hipError_t launch_heston(const HestonJob &job, double *d_partials, uint32_t grid
                          hipStream_t stream)
 {
     if (!finish_ok(finish, grid)) return hipErrorInvalidValue;
-    const PathRange &paths = job.walk.paths;
-    if (job.scheme != kHestonFullTruncation || paths.n_steps == 0 || paths.n_local == 0) return hipErrorInvalidValue;
-    return dispatch_precision(paths.precision, [&](auto p) {
+    if (!heston_walk_ok(job.walk)) return hipErrorInvalidValue;
+    return dispatch_precision(job.walk.paths.precision, [&](auto p) {
         return launch_heston_t<typename decltype(p)::type>(job, d_partials, grid, finish, stream);
     });
 }

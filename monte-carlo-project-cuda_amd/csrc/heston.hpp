@@ -14,17 +14,22 @@ namespace mcamd {
 constexpr int kHestonRecord = 4;
 constexpr int kHestonFullTruncation = 0;   // MCAMD_HESTON_FULL_TRUNCATION
 
-// What every job that walks Heston paths carries: the paths, the drift, the step and the model.
+// What every job that walks Heston paths carries: the paths, the drift, the step, the model and the scheme.
 struct HestonWalk {
     PathRange paths;
     double mu;           // r - q
     double dt;           // T / n_steps
     double v0, kappa, theta, xi, rho;
+    int scheme;          // kHestonFullTruncation
 };
+// what every launcher of these paths needs of the walk
+inline bool heston_walk_ok(const HestonWalk &w)
+{
+    return w.scheme == kHestonFullTruncation && w.paths.n_steps != 0 && w.paths.n_local != 0;
+}
 
 struct HestonJob {
     HestonWalk walk;
-    int scheme;          // kHestonFullTruncation
     double S0, K;
     bool put;            // h(S) = (K - S)+ (else (S - K)+)
     void *d_samples;     // nullable: n_local samples of the path precision

@@ -4,9 +4,9 @@
 // Definitions (include/mcamd.h, mcamd_price_heston_barrier): the path is mcamd_price_heston's, X_i = ln(S_i / S0) in
 // NATURAL-log units and the raw variance v_i, moved by heston_device.hpp's heston_move on the two normals of heston.hip
 // (z of Philox blocks 0, 1, .., z' of blocks 2^63, 2^63 + 1, .. of the path's subsequence).  The barrier tests,
-// distances, survival weight and samples are those of barrier.hip as localvol.hip states them for a volatility that
-// changes from step to step: b = ln(B / S0) in natural units and, in the bridge factor, the variance v+ the step was
-// taken at (what heston_move returns), q_i = 2 d d' / (v+ dt).  The scheme freezes v+ over a step, so the bridge between
+// distances, survival weight and samples are barrier_device.hpp's for a volatility that changes from step to step, as
+// in localvol.hip: b = ln(B / S0) in natural units and, in the bridge factor, the variance v+ the step was taken at
+// (what heston_move returns), q_i = 2 d d' / (v+ dt).  The scheme freezes v+ over a step, so the bridge between
 // two step ends is Brownian with that variance rate and the factor is its exact survival probability.
 //
 // The factor is taken iff kq d d' < q_cut v+ (division-free, in the path precision): a step taken at v+ = 0 takes none
@@ -19,6 +19,7 @@
 // v < 0 and the sum of v+ (in the path precision, in step order).  All of these depend on the path's global id alone.
 // Put / call is a wave-uniform select after the walk.  There is no table in LDS beyond what MathCtx<T> needs.
 #include "heston_barrier.hpp"
+#include "barrier_device.hpp"
 #include "heston_device.hpp"
 #include "path_consts.hpp"
 #include "path_frame.hpp"
@@ -42,10 +43,6 @@ struct HestonBarrierArgs {
     GridFinish fin;
 };
 
-// Where the barrier's three constants live: as heston_resident keeps the step's.
-__device__ __forceinline__ float hb_resident(float s) { return vgpr_resident(s); }
-__device__ __forceinline__ double hb_resident(double s) { return s; }
-
 template <typename T, bool UP, bool CONT, bool OUT>
 __global__ __launch_bounds__(kBlock) void heston_barrier_kernel(HestonBarrierArgs<T> a, double *__restrict__ partials)
 {
@@ -53,7 +50,8 @@ __global__ __launch_bounds__(kBlock) void heston_barrier_kernel(HestonBarrierArg
     const MathCtx<T> m = MathCtx<T>::init();
     const PhiloxKeys key = PhiloxKeys::make(a.shard.seed);
     const HestonConsts<T> c = heston_resident(a.c);
-    const T b = hb_resident(a.b), kq = hb_resident(a.kq), q_cut = hb_resident(a.q_cut);
+    // the barrier's three constants live as heston_resident keeps the step's
+    const T b = resident_t(a.b), kq = resident_t(a.kq), q_cut = resident_t(a.q_cut);
     const StepBlocks blocks = step_blocks<NB>(a.n_steps);
     const T d0 = UP ? b : -b;   // |b|: the spot is strictly on the live side (checked on the host)
     double acc6[kHestonBarrierRecord] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -67,7 +65,7 @@ __global__ __launch_bounds__(kBlock) void heston_barrier_kernel(HestonBarrierArg
         bool alive = true;
         uint32_t live = 0;    // steps this path entered not yet knocked
         uint32_t trunc = 0;   // counted steps entered with v < 0
-        Normals<T> nz, nv;
+        HestonNormals<T> nz;
         auto step = [&](T z, T zv) {
             const bool counted = OUT ? alive : true;   // a knock-out's diagnostics stop where its walk may
             live += alive ? 1u : 0u;
@@ -88,20 +86,14 @@ __global__ __launch_bounds__(kBlock) void heston_barrier_kernel(HestonBarrierArg
             }
         };
         const uint32_t steps_run = walk_steps<NB>(
-            blocks,
-            [&](uint32_t kb) {
-                nz.fill(m, key, subsequence, kb);
-                nv.fill(m, key, subsequence, kHestonVarianceBlocks + kb);
-            },
-            [&](uint32_t, int j) { step(nz.z[j], nv.z[j]); },
+            blocks, [&](uint32_t kb) { nz.fill(m, key, subsequence, kb); },
+            [&](uint32_t, int j) { step(nz.z.z[j], nz.zv.z[j]); },
             [&] { return OUT && __builtin_amdgcn_ballot_w64(alive) == 0; });
         const T St = exp_of_logreturn(a.S0, X * a.exp_scale, m);
-        T h = a.put ? a.K - St : St - a.K;
-        h = h > T(0) ? h : T(0);
+        const T h = vanilla_payoff(a.put, a.K, St);
         const T w_end = alive ? w : T(0);
         const double wd = static_cast<double>(w_end);
-        // a knocked path of a knock-out pays 0 whatever its (possibly unfinished) price is
-        const double y = OUT ? (alive ? wd * static_cast<double>(h) : 0.0) : (1.0 - wd) * static_cast<double>(h);
+        const double y = barrier_sample<OUT>(alive, wd, h);
         if (a.samples) a.samples[i] = static_cast<T>(y);
         if (a.state) {
             // where a knocked knock-out path stops depends on its wavefront's other lanes: nothing is defined there
@@ -120,49 +112,27 @@ __global__ __launch_bounds__(kBlock) void heston_barrier_kernel(HestonBarrierArg
     finish_paths(acc6, partials, a.fin);
 }
 
-template <typename T, bool UP, bool CONT, bool OUT>
-static void launch_heston_barrier_k(const HestonBarrierArgs<T> &a, double *d_partials, uint32_t grid, hipStream_t stream)
-{
-    hipLaunchKernelGGL((heston_barrier_kernel<T, UP, CONT, OUT>), dim3(grid), dim3(kBlock), 0, stream, a, d_partials);
-}
-
-template <typename T, bool UP>
-static void launch_heston_barrier_b(const HestonBarrierJob &j, const HestonBarrierArgs<T> &a, double *d_partials,
-                                    uint32_t grid, hipStream_t stream)
-{
-    if (j.continuous) {
-        if (j.out) launch_heston_barrier_k<T, UP, true, true>(a, d_partials, grid, stream);
-        else launch_heston_barrier_k<T, UP, true, false>(a, d_partials, grid, stream);
-    } else {
-        if (j.out) launch_heston_barrier_k<T, UP, false, true>(a, d_partials, grid, stream);
-        else launch_heston_barrier_k<T, UP, false, false>(a, d_partials, grid, stream);
-    }
-}
-
 template <typename T>
 static hipError_t launch_heston_barrier_t(const HestonBarrierJob &j, double *d_partials, uint32_t grid, const FinishSpec &fs,
                                           hipStream_t stream)
 {
-    // natural log per unit of q: the fp32 bridge factor is 1 - 2^-q
-    const double q_unit = sizeof(T) == 4 ? kLn2 : 1.0;
-    const double q_cut = sizeof(T) == 4 ? 18.0 : 38.0;
+    const BridgeUnits bu = bridge_units<T>();
     HestonBarrierArgs<T> a;
-    a.c = heston_consts<T>(j.walk);
-    a.exp_scale = heston_exp_scale<T>();
-    a.v0 = static_cast<T>(j.walk.v0);
+    heston_walk_args<T>(a, j.walk);
     a.b = static_cast<T>(std::log(j.B / j.S0));
-    a.kq = static_cast<T>(2.0 / (j.walk.dt * q_unit));
-    a.q_cut = static_cast<T>(q_cut / q_unit);
+    a.kq = static_cast<T>(2.0 / (j.walk.dt * bu.q_unit));
+    a.q_cut = static_cast<T>(bu.q_cut);
     a.K = static_cast<T>(j.K);
     a.S0 = static_cast<T>(j.S0);
-    a.put = j.put ? 1 : 0;
+    a.put = j.form.put ? 1 : 0;
     a.n_steps = j.walk.paths.n_steps;
-    a.shard = shard_of(j.walk.paths);
     a.samples = static_cast<T *>(j.d_samples);
     a.state = static_cast<T *>(j.d_state);
     a.fin = grid_finish_of(fs);
-    if (j.up) launch_heston_barrier_b<T, true>(j, a, d_partials, grid, stream);
-    else launch_heston_barrier_b<T, false>(j, a, d_partials, grid, stream);
+    dispatch_barrier_form(j.form, [&](auto up, auto cont, auto out) {
+        hipLaunchKernelGGL((heston_barrier_kernel<T, decltype(up)::value, decltype(cont)::value, decltype(out)::value>),
+                           dim3(grid), dim3(kBlock), 0, stream, a, d_partials);
+    });
     return hipGetLastError();
 }
 
@@ -170,10 +140,9 @@ hipError_t launch_heston_barrier(const HestonBarrierJob &job, double *d_partials
                                  hipStream_t stream)
 {
     if (!finish_ok(finish, grid)) return hipErrorInvalidValue;
-    const PathRange &paths = job.walk.paths;
-    if (job.scheme != kHestonFullTruncation || paths.n_steps == 0 || paths.n_local == 0) return hipErrorInvalidValue;
-    if (!(job.B > 0.0) || !(job.S0 > 0.0) || !(job.up ? job.S0 < job.B : job.S0 > job.B)) return hipErrorInvalidValue;
-    return dispatch_precision(paths.precision, [&](auto p) {
+    if (!heston_walk_ok(job.walk)) return hipErrorInvalidValue;
+    if (!(job.B > 0.0) || !(job.S0 > 0.0) || !(job.form.up ? job.S0 < job.B : job.S0 > job.B)) return hipErrorInvalidValue;
+    return dispatch_precision(job.walk.paths.precision, [&](auto p) {
         return launch_heston_barrier_t<typename decltype(p)::type>(job, d_partials, grid, finish, stream);
     });
 }

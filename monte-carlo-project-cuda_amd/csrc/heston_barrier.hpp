@@ -8,6 +8,7 @@
 // lane-steps, wave-steps}.  The wave-steps sit last: the statistics layout of an enqueue keeps n there.
 #pragma once
 
+#include "barrier.hpp"
 #include "heston.hpp"
 
 namespace mcamd {
@@ -16,12 +17,9 @@ constexpr int kHestonBarrierRecord = 6;
 
 struct HestonBarrierJob {
     HestonWalk walk;
-    int scheme;          // kHestonFullTruncation
     double S0, K, B;
-    bool up, out;        // the side of the barrier, what touching it does
-    bool continuous;     // MCAMD_MONITOR_CONTINUOUS (else the step ends alone)
-    bool put;            // h(S) = (K - S)+ (else (S - K)+)
-    void *d_samples;     // nullable: n_local samples of the path precision
+    BarrierForm form;
+    void *d_samples;    // nullable: n_local samples of the path precision
     void *d_state;       // nullable: 3 n_local values of the path precision: S_T, the raw v_n, w
 };
 

@@ -40,10 +40,6 @@ struct HestonCliquetArgs {
     GridFinish fin;
 };
 
-// Where the payoff's three constants live: as heston_resident keeps the step's.
-__device__ __forceinline__ float hc_resident(float s) { return vgpr_resident(s); }
-__device__ __forceinline__ double hc_resident(double s) { return s; }
-
 template <typename T, int KIND>
 __global__ __launch_bounds__(kBlock) void heston_cliquet_kernel(HestonCliquetArgs<T> a, double *__restrict__ partials)
 {
@@ -51,7 +47,8 @@ __global__ __launch_bounds__(kBlock) void heston_cliquet_kernel(HestonCliquetArg
     const MathCtx<T> m = MathCtx<T>::init();
     const PhiloxKeys key = PhiloxKeys::make(a.shard.seed);
     const HestonConsts<T> c = heston_resident(a.c);
-    const T lo = hc_resident(a.lo), hi = hc_resident(a.hi), exp_scale = hc_resident(a.exp_scale);
+    // the payoff's three constants live as heston_resident keeps the step's
+    const T lo = resident_t(a.lo), hi = resident_t(a.hi), exp_scale = resident_t(a.exp_scale);
     const StepBlocks blocks = step_blocks<NB>(a.n_steps);
     // an infinite bound never binds and counts nothing, whatever the arithmetic made of A
     const bool has_floor = a.g_lo > -__builtin_huge_val(), has_cap = a.g_hi < __builtin_huge_val();
@@ -66,7 +63,7 @@ __global__ __launch_bounds__(kBlock) void heston_cliquet_kernel(HestonCliquetArg
         uint32_t trunc = 0;   // steps entered with v < 0
         uint32_t p = 0;                         // reset dates behind the wavefront
         uint32_t next_reset = a.reset_every;    // the step that ends on date p + 1
-        Normals<T> nz, nv;
+        HestonNormals<T> nz;
         // step `index` (wave-uniform) with the log-price normal z and the variance's own zv
         auto step = [&](T z, T zv, uint32_t index) {
             trunc += v < T(0) ? 1u : 0u;
@@ -80,12 +77,8 @@ __global__ __launch_bounds__(kBlock) void heston_cliquet_kernel(HestonCliquetArg
             }
         };
         walk_steps<NB>(
-            blocks,
-            [&](uint32_t kb) {
-                nz.fill(m, key, subsequence, kb);
-                nv.fill(m, key, subsequence, kHestonVarianceBlocks + kb);
-            },
-            [&](uint32_t kb, int j) { step(nz.z[j], nv.z[j], kb * NB + j); });
+            blocks, [&](uint32_t kb) { nz.fill(m, key, subsequence, kb); },
+            [&](uint32_t kb, int j) { step(nz.z.z[j], nz.zv.z[j], kb * NB + j); });
         const double A = cliquet_amount<KIND>(sum, exp_scale, a.scale, m);
         const double y = __builtin_fmin(__builtin_fmax(A, a.g_lo), a.g_hi);
         if (a.samples) a.samples[i] = static_cast<T>(y);
@@ -109,9 +102,7 @@ static hipError_t launch_heston_cliquet_t(const HestonCliquetJob &j, double *d_p
                                           hipStream_t stream)
 {
     HestonCliquetArgs<T> a;
-    a.c = heston_consts<T>(j.walk);
-    a.exp_scale = heston_exp_scale<T>();
-    a.v0 = static_cast<T>(j.walk.v0);
+    heston_walk_args<T>(a, j.walk);
     a.lo = static_cast<T>(j.local_lo);
     a.hi = static_cast<T>(j.local_hi);
     a.g_lo = j.global_lo;
@@ -121,7 +112,6 @@ static hipError_t launch_heston_cliquet_t(const HestonCliquetJob &j, double *d_p
     a.n_steps = j.walk.paths.n_steps;
     a.reset_every = j.reset_every;
     a.first_period = j.first_period;
-    a.shard = shard_of(j.walk.paths);
     a.samples = static_cast<T *>(j.d_samples);
     a.fin = grid_finish_of(fs);
     if (j.kind == kCliquetSum) launch_heston_cliquet_k<T, kCliquetSum>(a, d_partials, grid, stream);
@@ -134,8 +124,8 @@ hipError_t launch_heston_cliquet(const HestonCliquetJob &job, double *d_partials
                                  hipStream_t stream)
 {
     if (!finish_ok(finish, grid)) return hipErrorInvalidValue;
+    if (!heston_walk_ok(job.walk)) return hipErrorInvalidValue;
     const PathRange &paths = job.walk.paths;
-    if (job.scheme != kHestonFullTruncation || paths.n_steps == 0 || paths.n_local == 0) return hipErrorInvalidValue;
     if (job.kind < kCliquetSum || job.kind > kCliquetVariance || job.reset_every == 0 ||
         paths.n_steps % job.reset_every != 0 || job.first_period == 0 ||
         job.first_period > paths.n_steps / job.reset_every)

@@ -19,8 +19,7 @@ constexpr int kHestonCliquetRecord = 6;
 
 struct HestonCliquetJob {
     HestonWalk walk;
-    int scheme;              // kHestonFullTruncation
-    int kind;                // kCliquet*
+    int kind;               // kCliquet*
     uint32_t reset_every;    // steps per period; divides n_steps
     uint32_t first_period;   // 1 .. n_steps / reset_every: the first period that counts
     double local_lo, local_hi;     // SUM: the bounds of R_p; COMPOUND: ln(1 + bound), -inf / +inf included; VARIANCE: unread

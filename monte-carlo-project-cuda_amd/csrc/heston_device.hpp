@@ -1,6 +1,7 @@
 // heston_device.hpp — the step of a Heston path under the full-truncation Euler scheme in the log-price, for any kernel
 // that walks such paths (heston.hip, heston_smile.hip, heston_cliquet.hip, heston_barrier.hip; Asians can reuse it):
-// the step constants, where the variance's normals come from, and the move of one step.
+// the step constants, the four kernel arguments every launcher fills from the walk, the two normals of a step, and the
+// move of one step.
 //
 // Definitions (include/mcamd.h, mcamd_price_heston): X = ln(S / S0) in NATURAL-log units, v the raw variance, which may
 // go below zero; v+ = max(v, 0) is what the drift, the diffusion and the mean reversion read.  With the step's two
@@ -25,6 +26,18 @@ namespace mcamd {
 // The variance normals' block of a step block: same key and subsequence, 2^63 beyond (n_steps is 32-bit: the
 // log-price normals never get there).
 constexpr uint64_t kHestonVarianceBlocks = 1ull << 63;
+
+// The normals of one block of the walk: two Philox blocks, two Box-Muller fills.  Step j of block kb takes z.z[j] for
+// the log-price and zv.z[j] for the variance.
+template <typename T>
+struct HestonNormals {
+    Normals<T> z, zv;
+    __device__ __forceinline__ void fill(const MathCtx<T> &m, const PhiloxKeys &key, uint64_t subsequence, uint32_t kb)
+    {
+        z.fill(m, key, subsequence, kb);
+        zv.fill(m, key, subsequence, kHestonVarianceBlocks + kb);
+    }
+};
 
 // The floating-point constants of a step, formed in double on the host and narrowed once.
 template <typename T>
@@ -61,6 +74,16 @@ template <typename T>
 inline T heston_exp_scale()
 {
     return static_cast<T>(sizeof(T) == 4 ? 1.4426950408889634 : f64::kExpScale);
+}
+// What the argument structs of the four kernels have in common, from the walk of their job (as lv_step_args: the
+// structs share no sub-struct, each kernel's scalar loads are compiled against its own layout).
+template <typename T, typename Args>
+inline void heston_walk_args(Args &a, const HestonWalk &w)
+{
+    a.c = heston_consts<T>(w);
+    a.exp_scale = heston_exp_scale<T>();
+    a.v0 = static_cast<T>(w.v0);
+    a.shard = shard_of(w.paths);
 }
 
 // Where they live.  fp32: in vector registers, because a scalar operand doubles the issue time of the full-rate fp32

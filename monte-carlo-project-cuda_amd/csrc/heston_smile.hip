@@ -73,7 +73,7 @@ __global__ __launch_bounds__(kBlock) void heston_smile_kernel(HestonSmileArgs<T>
         T v = args.v0;            // the raw variance
         uint32_t mi = 0;          // the next expiry, wave-uniform
         uint32_t next = args.expiry_steps[0];
-        Normals<T> nz, nv;
+        HestonNormals<T> nz;
         auto expiry = [&]() {
             const T S = exp_of_logreturn(args.S0, X * args.exp_scale, m);
             if (args.state && valid) {
@@ -86,16 +86,15 @@ __global__ __launch_bounds__(kBlock) void heston_smile_kernel(HestonSmileArgs<T>
         };
         for (uint32_t kb = 0; kb < n_blocks; ++kb) {
             nz.fill(m, key, subsequence, kb);
-            nv.fill(m, key, subsequence, kHestonVarianceBlocks + kb);
             const uint32_t base = kb * NB;
             if (next > base + NB) {   // no expiry inside this block, hence a full one
 #pragma unroll
-                for (int j = 0; j < NB; ++j) heston_move(X, v, nz.z[j], nv.z[j], c);
+                for (int j = 0; j < NB; ++j) heston_move(X, v, nz.z.z[j], nz.zv.z[j], c);
             } else {
 #pragma unroll
                 for (int j = 0; j < NB; ++j) {
                     if (base + j < last) {
-                        heston_move(X, v, nz.z[j], nv.z[j], c);
+                        heston_move(X, v, nz.z.z[j], nz.zv.z[j], c);
                         if (base + j + 1 == next) expiry();
                     }
                 }
@@ -109,12 +108,9 @@ template <typename T>
 static hipError_t launch_heston_smile_t(const HestonSmileJob &j, double *d_partials, uint32_t grid, hipStream_t stream)
 {
     HestonSmileArgs<T> a;
-    a.c = heston_consts<T>(j.walk);
-    a.exp_scale = heston_exp_scale<T>();
-    a.v0 = static_cast<T>(j.walk.v0);
+    heston_walk_args<T>(a, j.walk);
     a.S0 = static_cast<T>(j.S0);
     smile_node_args<T>(a, j.nodes);
-    a.shard = shard_of(j.walk.paths);
     a.state = static_cast<T *>(j.d_state);
     hipLaunchKernelGGL((heston_smile_kernel<T>), dim3(grid), dim3(kBlock), 0, stream, a, d_partials);
     return hipGetLastError();
@@ -123,7 +119,7 @@ static hipError_t launch_heston_smile_t(const HestonSmileJob &j, double *d_parti
 hipError_t launch_heston_smile(const HestonSmileJob &job, double *d_partials, uint32_t grid, hipStream_t stream)
 {
     if (!d_partials || grid == 0 || grid > kFoldMaxRecords) return hipErrorInvalidValue;
-    if (job.walk.paths.n_steps == 0 || job.walk.paths.n_local == 0) return hipErrorInvalidValue;
+    if (!heston_walk_ok(job.walk)) return hipErrorInvalidValue;
     if (!smile_nodes_ok(job.nodes, job.walk.paths.n_steps)) return hipErrorInvalidValue;
     return dispatch_precision(job.walk.paths.precision, [&](auto p) {
         return launch_heston_smile_t<typename decltype(p)::type>(job, d_partials, grid, stream);

@@ -44,6 +44,8 @@ struct Precision { using type = T; };
 template <typename F>
 hipError_t dispatch_precision(int precision, F f) { return precision == 32 ? f(Precision<float>{}) : f(Precision<double>{}); }
 
+constexpr double kLn2 = 0.69314718055994531;   // the launchers' unit conversions (path_consts.hpp, barrier.hpp)
+
 constexpr uint32_t kMaxGrid = 1u << 20;  // blocks; beyond this the kernels grid-stride
 constexpr uint32_t kBlockThreads = 256;  // threads per workgroup of every kernel (mc_device.hpp kBlock; reported as block)
 

@@ -3,7 +3,7 @@
 // Definitions (include/mcamd.h, mcamd_price_localvol): X_i = ln(S_i / S0) in NATURAL-log units (the surface's axis);
 // the lookup of the step's volatility s, the row carry and the move X += ((r - q) - s^2/2) dt + s sqrt(dt) z are
 // localvol_device.hpp's, which the smile and the autocallable kernels walk as well.  The barrier tests, distances,
-// survival weight and samples are those of barrier.hip with b = ln(B / S0) in natural units and the step's own s in
+// survival weight and samples are barrier_device.hpp's with b = ln(B / S0) in natural units and the step's own s in
 // the bridge factor, q_i = 2 d d' / (s^2 dt).
 //
 // The table — n_t n_x (sigma_k, slope_k) pairs of the path precision — is copied from global memory into dynamic LDS
@@ -11,6 +11,7 @@
 // base plus the lane's k, and FMAs.  The volatility differs per lane and per step, so the exponent cannot be pre-scaled
 // as Exponents<T> does: the loop takes plain normals (Normals<T>) and converts X to the exponential's unit once, at the
 // end of the path.
+#include "barrier_device.hpp"
 #include "localvol_device.hpp"
 #include "path_frame.hpp"
 
@@ -44,7 +45,7 @@ __global__ __launch_bounds__(kBlock) void localvol_kernel(LocalVolArgs<T> a, dou
     const MathCtx<T> m = MathCtx<T>::init();
     const PhiloxKeys key = PhiloxKeys::make(a.shard.seed);
     const LvAxis<T> axis = lv_resident(a.surf.axis);
-    const T mu_dt = lv_resident(a.mu_dt), half_dt = lv_resident(a.half_dt), sqrt_dt = lv_resident(a.sqrt_dt);
+    const T mu_dt = resident_t(a.mu_dt), half_dt = resident_t(a.half_dt), sqrt_dt = resident_t(a.sqrt_dt);
     const ThreadPaths paths(a.shard.n_local);   // made at the loop, one fp64 kernel spills 8 scalars for 4
     const StepBlocks blocks = step_blocks<NB>(a.n_steps);
     const T d0 = UP ? a.b : -a.b;   // |b|: the spot is strictly on the live side (checked on the host)
@@ -81,15 +82,13 @@ __global__ __launch_bounds__(kBlock) void localvol_kernel(LocalVolArgs<T> a, dou
             blocks, [&](uint32_t kb) { nz.fill(m, key, subsequence, kb); }, [&](uint32_t, int j) { step(nz.z[j]); },
             [&] { return BAR != 0 && OUT && __builtin_amdgcn_ballot_w64(alive) == 0; });
         const T St = exp_of_logreturn(a.S0, X * a.exp_scale, m);
-        T h = a.put ? a.K - St : St - a.K;
-        h = h > T(0) ? h : T(0);
+        const T h = vanilla_payoff(a.put, a.K, St);
         double y;
         if (BAR == 0) {
             y = static_cast<double>(h);
         } else {
             const double wd = alive ? static_cast<double>(w) : 0.0;
-            // a knocked path of a knock-out pays 0 whatever its (possibly unfinished) price is
-            y = OUT ? (alive ? wd * static_cast<double>(h) : 0.0) : (1.0 - wd) * static_cast<double>(h);
+            y = barrier_sample<OUT>(alive, wd, h);
         }
         if (a.samples) a.samples[i] = static_cast<T>(y);
         add_sample(acc4, y);
@@ -106,41 +105,31 @@ static void launch_localvol_k(const LocalVolArgs<T> &a, double *d_partials, uint
     hipLaunchKernelGGL((localvol_kernel<T, BAR, CONT, OUT>), dim3(grid), dim3(kBlock), lds_bytes, stream, a, d_partials);
 }
 
-template <typename T, int BAR>
-static void launch_localvol_b(const LocalVolJob &j, const LocalVolArgs<T> &a, double *d_partials, uint32_t grid,
-                              hipStream_t stream)
-{
-    if (j.continuous) {
-        if (j.out) launch_localvol_k<T, BAR, true, true>(a, d_partials, grid, stream);
-        else launch_localvol_k<T, BAR, true, false>(a, d_partials, grid, stream);
-    } else {
-        if (j.out) launch_localvol_k<T, BAR, false, true>(a, d_partials, grid, stream);
-        else launch_localvol_k<T, BAR, false, false>(a, d_partials, grid, stream);
-    }
-}
-
 template <typename T>
 static hipError_t launch_localvol_t(const LocalVolJob &j, double *d_partials, uint32_t grid, const FinishSpec &fs,
                                     hipStream_t stream)
 {
-    // natural log per unit of q: the fp32 bridge factor is 1 - 2^-q
-    const double q_unit = sizeof(T) == 4 ? kLn2 : 1.0;
-    const double q_cut = sizeof(T) == 4 ? 18.0 : 38.0;
+    const BridgeUnits bu = bridge_units<T>();
     LocalVolArgs<T> a;
     lv_step_args<T>(a, j.walk);
     a.shard = shard_of(j.walk.paths);
-    a.b =j.barrier ? static_cast<T>(std::log(j.B / j.S0)) : T(0);
-    a.kq = static_cast<T>(2.0 / (j.walk.dt * q_unit));
-    a.q_cut = static_cast<T>(q_cut / q_unit);
+    a.b = j.barrier ? static_cast<T>(std::log(j.B / j.S0)) : T(0);
+    a.kq = static_cast<T>(2.0 / (j.walk.dt * bu.q_unit));
+    a.q_cut = static_cast<T>(bu.q_cut);
     a.K = static_cast<T>(j.K);
     a.S0 = static_cast<T>(j.S0);
-    a.put = j.put ? 1 : 0;
+    a.put = j.form.put ? 1 : 0;
     a.n_steps = j.walk.paths.n_steps;
     a.samples = static_cast<T *>(j.d_samples);
     a.fin = grid_finish_of(fs);
-    if (!j.barrier) launch_localvol_k<T, 0, false, false>(a, d_partials, grid, stream);
-    else if (j.up) launch_localvol_b<T, 2>(j, a, d_partials, grid, stream);
-    else launch_localvol_b<T, 1>(j, a, d_partials, grid, stream);
+    if (!j.barrier) {
+        launch_localvol_k<T, 0, false, false>(a, d_partials, grid, stream);
+    } else {
+        dispatch_barrier_form(j.form, [&](auto up, auto cont, auto out) {
+            launch_localvol_k<T, decltype(up)::value ? 2 : 1, decltype(cont)::value, decltype(out)::value>(
+                a, d_partials, grid, stream);
+        });
+    }
     return hipGetLastError();
 }
 

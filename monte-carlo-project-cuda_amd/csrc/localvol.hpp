@@ -7,7 +7,7 @@
 // {sum y, sum y^2, wave-steps executed, lane-steps of paths not yet knocked}.
 #pragma once
 
-#include "launch.hpp"
+#include "barrier.hpp"
 
 namespace mcamd {
 
@@ -39,11 +39,8 @@ struct LocalVolWalk {
 struct LocalVolJob {
     LocalVolWalk walk;
     double S0, K, B;     // B read with a barrier only
-    bool barrier;        // knock-out / knock-in at B (else European)
-    bool up;             // the barrier lies above the spot (else below)
-    bool out;            // knock-out (else knock-in)
-    bool continuous;     // Brownian-bridge survival factors with the step's frozen volatility
-    bool put;            // h(S) = (K - S)+ (else (S - K)+)
+    bool barrier;        // knock-out / knock-in at B (else European: of form, put alone is read)
+    BarrierForm form;    // continuous: with the step's frozen volatility in the bridge factor
     void *d_samples;     // nullable: n_local samples of the path precision
 };
 

@@ -101,15 +101,11 @@ __device__ __forceinline__ double lv_min(double a, double b) { return __builtin_
 __device__ __forceinline__ float lv_max(float a, float b) { return __builtin_fmaxf(a, b); }
 __device__ __forceinline__ double lv_max(double a, double b) { return __builtin_fmax(a, b); }
 
-// Where the step's floating-point constants live.  fp32: in vector registers, because a scalar operand doubles the
-// issue time of the full-rate fp32 instructions (mc_device.hpp vgpr_resident).  fp64: an operation issues in 4 cycles
-// with or without a scalar operand, so they stay where the compiler puts them.
-__device__ __forceinline__ float lv_resident(float s) { return vgpr_resident(s); }
-__device__ __forceinline__ double lv_resident(double s) { return s; }
+// Where the axis' floating-point constants live: where resident_t (mc_device.hpp) keeps the step's.
 template <typename T>
 __device__ __forceinline__ LvAxis<T> lv_resident(const LvAxis<T> &a)
 {
-    return {lv_resident(a.x_min), lv_resident(a.inv_dx), lv_resident(a.u_max)};
+    return {resident_t(a.x_min), resident_t(a.inv_dx), resident_t(a.u_max)};
 }
 
 // The tables of a workgroup, back to back in dynamic LDS (entries of VolPair<T>).

@@ -59,6 +59,7 @@ template <typename T>
 __device__ __forceinline__ LvPathEnd lv_path_end(T X, const LvGreeksArgs<T> &a, const MathCtx<T> &m)
 {
     const T St = exp_of_logreturn(a.S0, X * a.exp_scale, m);
+    // not vanilla_payoff: the counted opcodes and figures stay, but the assembly's text does not
     T h = a.put ? a.K - St : St - a.K;
     h = h > T(0) ? h : T(0);
     const double Sd = static_cast<double>(St);
@@ -76,8 +77,8 @@ __global__ __launch_bounds__(kBlock) void localvol_greeks_kernel(LvGreeksArgs<T>
     const MathCtx<T> m = MathCtx<T>::init();
     const PhiloxKeys key = PhiloxKeys::make(a.shard.seed);
     const LvAxis<T> axis = lv_resident(a.surf.axis);
-    const T mu_dt = lv_resident(a.mu_dt), half_dt = lv_resident(a.half_dt), sqrt_dt = lv_resident(a.sqrt_dt);
-    const T dt = lv_resident(a.dt);
+    const T mu_dt = resident_t(a.mu_dt), half_dt = resident_t(a.half_dt), sqrt_dt = resident_t(a.sqrt_dt);
+    const T dt = resident_t(a.dt);
     const ThreadPaths paths(a.shard.n_local);   // made at the loop, seven of the eight kernels spill otherwise
     const uint32_t n_full = a.n_steps / NB;
     const uint32_t rem = a.n_steps - n_full * NB;

@@ -45,7 +45,7 @@ __global__ __launch_bounds__(kBlock) void smile_kernel(SmileArgs<T> args, double
     const MathCtx<T> m = MathCtx<T>::init();
     const PhiloxKeys key = PhiloxKeys::make(args.seed);
     const LvAxis<T> axis = lv_resident(args.surf.axis);
-    const T mu_dt = lv_resident(args.mu_dt), half_dt = lv_resident(args.half_dt), sqrt_dt = lv_resident(args.sqrt_dt);
+    const T mu_dt = resident_t(args.mu_dt), half_dt = resident_t(args.half_dt), sqrt_dt = resident_t(args.sqrt_dt);
     const uint32_t lane = threadIdx.x & (kWave - 1);
     const uint32_t wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     const uint32_t wave = blockIdx.x * (kBlock / kWave) + wave_in_block;

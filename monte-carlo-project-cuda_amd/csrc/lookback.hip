@@ -78,9 +78,6 @@ __device__ __forceinline__ double min_t(double a, double b) { return __builtin_f
 __device__ __forceinline__ float root_t(float a) { return __builtin_amdgcn_sqrtf(a); }   // a >= 0
 // a > 0: x^2 + kb l with l = f64::neg2log(U) strictly positive for every U in (0, 1] (fast64.hpp)
 __device__ __forceinline__ double root_t(double a) { return f64::sqrt_unclamped(a); }
-// the bridge constants of the full-rate fp32 instructions belong in vector registers (vgpr_resident)
-__device__ __forceinline__ float resident_t(float s) { return vgpr_resident(s); }
-__device__ __forceinline__ double resident_t(double s) { return s; }
 
 template <typename T, bool MAXIMUM, bool CONT>
 __global__ __launch_bounds__(kBlock) void lookback_kernel(LookbackArgs<T> a, double *__restrict__ partials)
@@ -89,6 +86,7 @@ __global__ __launch_bounds__(kBlock) void lookback_kernel(LookbackArgs<T> a, dou
     const MathCtx<T> m = MathCtx<T>::init();
     const PhiloxKeys key = PhiloxKeys::make(a.shard.seed);
     const StepConsts<T> c = resident(a.c);
+    // the bridge constants of the full-rate fp32 instructions belong in vector registers
     const T kq = resident_t(a.kq), kb = resident_t(a.kb), q_cut = resident_t(a.q_cut);
     const StepBlocks blocks = step_blocks<NB>(c.n_sim);
     double acc4[kLookbackRecord] = {0.0, 0.0, 0.0, 0.0};

@@ -45,6 +45,10 @@ __device__ __forceinline__ float vgpr_resident(float s)
     asm volatile("v_mov_b32 %0, %1" : "=v"(v) : "s"(s));
     return v;
 }
+// Where a kernel's own floating-point constant of the path precision lives: fp32 in a vector register; fp64 where the
+// compiler puts it, because an fp64 operation issues in 4 cycles with or without a scalar operand.
+__device__ __forceinline__ float resident_t(float s) { return vgpr_resident(s); }
+__device__ __forceinline__ double resident_t(double s) { return s; }
 
 // Two scalars copied into a vector register pair by one v_mov_b64 (4 cycles whatever its source; a v_mov_b32 from a
 // scalar register costs as much for one: profiles/philox_head_operand_costs.txt).  Not volatile: the scheduler may place it.

@@ -9,8 +9,6 @@
 
 namespace mcamd {
 
-constexpr double kLn2 = 0.69314718055994531;
-
 // Natural log per exponent unit: ln 2 for fp32's log2 units, ln 2 / 65536 for fp64's.  make_consts' scale is the
 // reciprocal, kept as its own literals: 1 / unit does not round to them.
 template <typename T>

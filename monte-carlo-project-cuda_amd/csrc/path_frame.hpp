@@ -25,6 +25,14 @@ struct ThreadPaths {
     __device__ __forceinline__ Iterator end() const { return {n, 0}; }
 };
 
+// h(S) = (K - S)+ for a put, (S - K)+ for a call, in the path precision; put is wave-uniform.
+template <typename T>
+__device__ __forceinline__ T vanilla_payoff(int put, T K, T St)
+{
+    const T h = put ? K - St : St - K;
+    return h > T(0) ? h : T(0);
+}
+
 // One path's sample into the record's first two slots: the sum and the sum of squares.
 template <int N>
 __device__ __forceinline__ void add_sample(double (&acc)[N], double y)

@@ -3,7 +3,9 @@
 list of small jobs on the kernels that walk a local-volatility surface — mcamd_price_localvol, mcamd_price_localvol_smile,
 mcamd_price_autocall_localvol, mcamd_price_cliquet, mcamd_price_localvol_greeks — on mcamd_price_heston (a put and a
 call, with the samples and the final state) and mcamd_price_heston_smile (1 x 1 and 3 x 63 nodes, expiries at step 1 and
-at the last step, with the spots and variances at every expiry), and on the one-path-per-thread kernels of constant volatility — mcamd_price_barrier, mcamd_price_lookback, mcamd_price_asian, the likelihood-ratio and pathwise
+at the last step, with the spots and variances at every expiry), mcamd_price_heston_cliquet (three kinds over the
+periods) and mcamd_price_heston_barrier (every kind x monitoring x payoff, with the samples and the final state), and on
+the one-path-per-thread kernels of constant volatility — mcamd_price_barrier, mcamd_price_lookback, mcamd_price_asian, the likelihood-ratio and pathwise
 mcamd_price_greeks, mcamd_price_american, mcamd_american_upper_bound, and on d = 1..8 correlated assets
 mcamd_price_basket and mcamd_price_autocall — and prints a SHA-256 per job over the per-path
 outputs where the call has them (samples, spots, continuation values, coefficients) and the result record without its
@@ -20,8 +22,9 @@ with every barrier, at d = 1..8 over the step counts of the one-path-per-thread 
 steps is 1, 2 or 4 steps, so they leave every remainder, no whole group, and whole groups only; the constant-volatility
 autocallable takes d = 1..8 and the three knock-in modes over the (n_steps, period) pairs.  Some jobs make whole
 wavefronts leave the step loop after a whole block or group, and their names carry the proof: a knock-out barrier beside
-the spot on 100 000 paths and a worst-of knock-out basket with the barrier beside the aggregate (d = 3 and 8; their
-work_steps fall short of the full count — the worker refuses to go on otherwise); an American put so deep in the money
+the spot on 100 000 paths, under constant volatility and under Heston, and a worst-of knock-out basket with the barrier
+beside the aggregate (d = 3 and 8; their work_steps fall short of the full count — for the Heston barrier and the
+baskets the worker refuses to go on otherwise); an American put so deep in the money
 (K = 10 S0) that every priced path is exercised at the first date, step 4 of 48, so that every wavefront of the
 pricing kernel leaves 44 steps early; and a 3-asset note with a call level of 0.01 under mcamd_price_autocall and under
 mcamd_price_autocall_localvol, every path called at the first date, step 4 of 48, after 4 wave-steps per wavefront —
@@ -151,6 +154,43 @@ def worker():
                     state = torch.zeros(2 * len(steps) * N, dtype=dtype[prec], device="cuda")
                     _, _, stats, res = ctx.price_heston_smile(opt, sim(n_steps, prec, off), hs, steps, strikes, state)
                     emit(f"heston smile {tag} n={n_steps} expiries={list(steps)} n_K={n_K}", res, state, stats)
+            # mcamd_price_heston_cliquet on the same model: every kind, resets inside a block, at its end and at the
+            # path's end only
+            opt = capi.make_option(S0=100.0, K=0.0, r=0.05, v=0.0, T=1.0)
+            hs = capi.make_heston(capi.PAYOFF_CALL, q=0.02, v0=0.04, kappa=2.0, theta=0.04, xi=1.0, rho=-0.7)
+            for n_steps, every in PERIODS:
+                for kind in (capi.CLIQUET_SUM, capi.CLIQUET_COMPOUND, capi.CLIQUET_VARIANCE):
+                    local = {} if kind == capi.CLIQUET_VARIANCE else dict(local_floor=-0.03, local_cap=0.05)
+                    cq = capi.make_cliquet(kind, every, 1 + (n_steps // every) // 3, global_floor=0.0, global_cap=0.2,
+                                           q=0.02, **local)
+                    res = ctx.price_heston_cliquet(opt, sim(n_steps, prec, off), hs, cq, out.zero_())
+                    emit(f"heston cliquet {tag} n={n_steps} every={every} kind={kind}", res, out)
+            # mcamd_price_heston_barrier on the same model: every kind, monitoring and payoff, with S_T, the variance
+            # and the survival weight of every path
+            state = torch.empty(3 * N, dtype=dtype[prec], device="cuda")
+            for n_steps in STEPS_WALK:
+                for kind in range(4):
+                    up = kind in (capi.BARRIER_UP_OUT, capi.BARRIER_UP_IN)
+                    opt = capi.make_option(S0=100.0, K=100.0, B=110.0 if up else 90.0, r=0.05, v=0.0, T=1.0)
+                    for mon in (capi.MONITOR_DISCRETE, capi.MONITOR_CONTINUOUS):
+                        for pay in (capi.PAYOFF_CALL, capi.PAYOFF_PUT):
+                            hs = capi.make_heston(pay, q=0.02, v0=0.04, kappa=2.0, theta=0.04, xi=1.0, rho=-0.7)
+                            res = ctx.price_heston_barrier(opt, sim(n_steps, prec, off), hs, capi.make_barrier(kind, pay, mon),
+                                                           out.zero_(), state.zero_())
+                            emit(f"heston barrier {tag} n={n_steps} kind={kind} mon={mon} pay={pay}", res, out, state)
+            # ... and a knock-out with the barrier beside the spot under a drift of -0.5: whole wavefronts leave after a
+            # whole block
+            n_ko = 100_000
+            opt = capi.make_option(S0=100.0, K=100.0, B=99.9, r=0.0, v=0.0, T=1.0)
+            hs = capi.make_heston(capi.PAYOFF_CALL, q=0.5, v0=0.16, kappa=2.0, theta=0.16, xi=1.0, rho=-0.7)
+            many, state = (torch.empty(k * n_ko, dtype=dtype[prec], device="cuda") for k in (1, 3))
+            res = ctx.price_heston_barrier(opt, sim(51, prec, off, n_ko), hs,
+                                           capi.make_barrier(capi.BARRIER_DOWN_OUT, capi.PAYOFF_CALL, capi.MONITOR_CONTINUOUS),
+                                           many.zero_(), state.zero_())
+            full = 64.0 * 51 * ((n_ko + 63) // 64)
+            if not res.work_steps < full:
+                raise SystemExit(f"heston barrier {tag}: no wavefront left the loop early ({res.work_steps} of {full})")
+            emit(f"heston barrier {tag} early exit work={res.work_steps:.0f} of {full:.0f}", res, many, state)
             # mcamd_price_barrier: every kind, monitoring and payoff
             for n_steps in STEPS_WALK:
                 for kind in range(4):
