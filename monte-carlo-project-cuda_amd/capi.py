@@ -3,6 +3,9 @@
 Host-side plumbing only: device buffers and streams come from the caller (torch tensors'
 data_ptr / torch.cuda.current_stream in the tests and bench).  Nothing here computes a price:
 every call goes to the HIP library, and loading fails loudly if the library is missing.
+
+The header is restated here once: the struct classes and the PROTOTYPES table.  tests/test_capi_header_cpu.py parses
+include/mcamd.h and compares both with it, field by field and parameter by parameter.
 """
 from __future__ import annotations
 
@@ -48,36 +51,12 @@ BASKET_MAX_ASSETS = 8
 BASKET_ARITHMETIC, BASKET_GEOMETRIC, BASKET_BEST_OF, BASKET_WORST_OF = 0, 1, 2, 3
 BASKET_NO_BARRIER, BASKET_DOWN_OUT, BASKET_DOWN_IN, BASKET_UP_OUT, BASKET_UP_IN = 0, 1, 2, 3, 4
 
-# every symbol include/mcamd.h declares
-EXPORTS = [
-    "mcamd_abi_version", "mcamd_last_error", "mcamd_build_id", "mcamd_device_count", "mcamd_ctx_create", "mcamd_ctx_destroy",
-    "mcamd_get_device_info", "mcamd_device_malloc", "mcamd_device_free", "mcamd_memcpy_to_host",
-    "mcamd_memcpy_to_device", "mcamd_price_paths", "mcamd_price_paths_enqueue", "mcamd_enqueued_kernel_ms",
-    "mcamd_finalize_stats", "mcamd_group_create", "mcamd_group_destroy", "mcamd_group_size",
-    "mcamd_group_price_paths", "mcamd_group_ctx", "mcamd_group_shard", "mcamd_group_simulate_trajectories",
-    "mcamd_group_nmc_inner", "mcamd_group_nmc_fused", "mcamd_simulate_trajectories_enqueue", "mcamd_diag_store_pattern", "mcamd_nmc_inner_enqueue",
-    "mcamd_nmc_fused_enqueue", "mcamd_finalize_nmc_stats", "mcamd_simulate_trajectories", "mcamd_price_from_normals",
-    "mcamd_generate_normals", "mcamd_reduce_sum", "mcamd_reduce_partials", "mcamd_cpu_mc_f32", "mcamd_nmc_inner", "mcamd_nmc_fused", "mcamd_finalize", "mcamd_finalize_cv", "mcamd_cnd_f32",
-    "mcamd_bs_call_f32", "mcamd_bs_call_f64", "mcamd_price_greeks", "mcamd_price_greeks_enqueue",
-    "mcamd_finalize_greeks_stats", "mcamd_group_price_greeks", "mcamd_bs_greeks_f64",
-    "mcamd_american_workspace_bytes", "mcamd_price_american",
-    "mcamd_american_dual_workspace_bytes", "mcamd_american_upper_bound",
-    "mcamd_price_barrier", "mcamd_price_barrier_enqueue", "mcamd_barrier_price_f64",
-    "mcamd_price_lookback", "mcamd_price_lookback_enqueue", "mcamd_lookback_price_f64",
-    "mcamd_price_basket", "mcamd_price_basket_enqueue", "mcamd_basket_geometric_price_f64", "mcamd_exchange_price_f64",
-    "mcamd_price_asian", "mcamd_price_asian_enqueue", "mcamd_asian_geometric_price_f64",
-    "mcamd_price_autocall", "mcamd_price_autocall_enqueue", "mcamd_autocall_single_date_price_f64",
-    "mcamd_localvol_surface_create", "mcamd_localvol_surface_destroy", "mcamd_price_localvol",
-    "mcamd_price_localvol_enqueue", "mcamd_localvol_sigma_f64", "mcamd_bs_price_f64",
-    "mcamd_bs_implied_vol_f64", "mcamd_price_localvol_smile", "mcamd_price_localvol_smile_enqueue", "mcamd_finalize_smile",
-    "mcamd_price_autocall_localvol", "mcamd_price_autocall_localvol_enqueue",
-    "mcamd_price_localvol_greeks", "mcamd_price_localvol_greeks_enqueue", "mcamd_finalize_localvol_greeks_stats",
-    "mcamd_price_cliquet", "mcamd_price_cliquet_enqueue", "mcamd_cliquet_price_f64",
-    "mcamd_price_heston", "mcamd_price_heston_enqueue", "mcamd_heston_price_f64",
-    "mcamd_price_heston_smile", "mcamd_price_heston_smile_enqueue",
-    "mcamd_price_heston_cliquet", "mcamd_price_heston_cliquet_enqueue", "mcamd_heston_cliquet_price_f64",
-    "mcamd_price_heston_barrier", "mcamd_price_heston_barrier_enqueue",
-]
+
+class _Record(C.Structure):
+    """a result struct of scalars: as_dict is its fields by name"""
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class Option(C.Structure):
@@ -92,15 +71,12 @@ class Sim(C.Structure):
                 ("precision", C.c_int32), ("flags", C.c_int32)]
 
 
-class Result(C.Structure):
+class Result(_Record):
     _fields_ = [("sum", C.c_double), ("sumsq", C.c_double), ("n", C.c_uint64), ("price", C.c_double),
                 ("std_err", C.c_double), ("ci_lo", C.c_double), ("ci_hi", C.c_double), ("kernel_ms", C.c_float),
                 ("total_ms", C.c_float), ("grid", C.c_uint32), ("block", C.c_uint32), ("sum_c", C.c_double),
                 ("sum_cc", C.c_double), ("sum_yc", C.c_double), ("cv_beta", C.c_double), ("cv_rho", C.c_double),
                 ("work_steps", C.c_double), ("live_steps", C.c_double)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class Greeks(C.Structure):
@@ -120,7 +96,7 @@ class American(C.Structure):
                 ("reserved", C.c_uint32), ("n_train", C.c_uint64), ("train_seed", C.c_uint64)]
 
 
-class AmericanResult(C.Structure):
+class AmericanResult(_Record):
     """mcamd_american_result: out-of-sample and in-sample estimates, raw shard sums, dates, timings."""
     _fields_ = [("price", C.c_double), ("std_err", C.c_double), ("ci_lo", C.c_double), ("ci_hi", C.c_double),
                 ("sum", C.c_double), ("sumsq", C.c_double), ("n", C.c_uint64), ("in_sample_price", C.c_double),
@@ -130,25 +106,19 @@ class AmericanResult(C.Structure):
                 ("train_ms", C.c_float), ("price_ms", C.c_float), ("total_ms", C.c_float), ("grid", C.c_uint32),
                 ("block", C.c_uint32), ("train_grid", C.c_uint32), ("reserved", C.c_int32)]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
-
 
 class AmericanDual(C.Structure):
     """mcamd_american_dual: the nested sample of mcamd_american_upper_bound."""
     _fields_ = [("n_inner", C.c_uint32), ("reserved", C.c_uint32), ("inner_seed", C.c_uint64)]
 
 
-class AmericanDualResult(C.Structure):
+class AmericanDualResult(_Record):
     """mcamd_american_dual_result: the dual (upper) estimate, raw shard sums, lane-step counts, timings."""
     _fields_ = [("upper", C.c_double), ("std_err", C.c_double), ("ci_hi", C.c_double), ("sum", C.c_double),
                 ("sumsq", C.c_double), ("n", C.c_uint64), ("sum_q0", C.c_double), ("work_steps", C.c_double),
                 ("live_steps", C.c_double), ("n_dates", C.c_uint32), ("immediate_exercise", C.c_int32),
                 ("outer_ms", C.c_float), ("inner_ms", C.c_float), ("scan_ms", C.c_float), ("total_ms", C.c_float),
                 ("grid", C.c_uint32), ("block", C.c_uint32)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class Barrier(C.Structure):
@@ -184,16 +154,13 @@ class Autocall(C.Structure):
                 ("v", C.c_double * 8), ("corr", C.c_double * 64)]
 
 
-class AutocallResult(C.Structure):
+class AutocallResult(_Record):
     """mcamd_autocall_result"""
     _fields_ = [("price", C.c_double), ("std_err", C.c_double), ("ci_lo", C.c_double), ("ci_hi", C.c_double),
                 ("sum", C.c_double), ("sumsq", C.c_double), ("n", C.c_uint64), ("n_called", C.c_uint64),
                 ("sum_t_call", C.c_double), ("n_knocked_in", C.c_uint64), ("work_steps", C.c_double),
                 ("live_steps", C.c_double), ("kernel_ms", C.c_float), ("total_ms", C.c_float), ("grid", C.c_uint32),
                 ("block", C.c_uint32)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class AutocallLocalVol(C.Structure):
@@ -244,15 +211,12 @@ class Cliquet(C.Structure):
                 ("global_cap", C.c_double), ("q", C.c_double)]
 
 
-class CliquetResult(C.Structure):
+class CliquetResult(_Record):
     """mcamd_cliquet_result"""
     _fields_ = [("price", C.c_double), ("std_err", C.c_double), ("ci_lo", C.c_double), ("ci_hi", C.c_double),
                 ("sum", C.c_double), ("sumsq", C.c_double), ("n", C.c_uint64), ("n_floored", C.c_uint64),
                 ("n_capped", C.c_uint64), ("work_steps", C.c_double), ("kernel_ms", C.c_float), ("total_ms", C.c_float),
                 ("grid", C.c_uint32), ("block", C.c_uint32)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class Heston(C.Structure):
@@ -263,40 +227,25 @@ class Heston(C.Structure):
                 ("reserved", C.c_double)]
 
 
-class HestonResult(C.Structure):
+class HestonResult(_Record):
     """mcamd_heston_result"""
     _fields_ = [("price", C.c_double), ("std_err", C.c_double), ("ci_lo", C.c_double), ("ci_hi", C.c_double),
                 ("sum", C.c_double), ("sumsq", C.c_double), ("n", C.c_uint64), ("truncated_steps", C.c_double),
                 ("mean_variance", C.c_double), ("work_steps", C.c_double), ("kernel_ms", C.c_float),
                 ("total_ms", C.c_float), ("grid", C.c_uint32), ("block", C.c_uint32)]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class HestonCliquetResult(C.Structure):
+class HestonCliquetResult(_Record):
     """mcamd_heston_cliquet_result: mcamd_cliquet_result's fields, then mcamd_heston_result's two diagnostics"""
     _fields_ = CliquetResult._fields_ + [("truncated_steps", C.c_double), ("mean_variance", C.c_double)]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-assert C.sizeof(HestonCliquetResult) == 112   # pinned in include/mcamd.h
-
-
-class HestonBarrierResult(C.Structure):
+class HestonBarrierResult(_Record):
     """mcamd_heston_barrier_result"""
     _fields_ = [("price", C.c_double), ("std_err", C.c_double), ("ci_lo", C.c_double), ("ci_hi", C.c_double),
                 ("sum", C.c_double), ("sumsq", C.c_double), ("n", C.c_uint64), ("live_steps", C.c_double),
                 ("work_steps", C.c_double), ("truncated_steps", C.c_double), ("mean_variance", C.c_double),
                 ("kernel_ms", C.c_float), ("total_ms", C.c_float), ("grid", C.c_uint32), ("block", C.c_uint32)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
-
-
-assert C.sizeof(HestonBarrierResult) == 104   # pinned in include/mcamd.h
 
 
 class Smile(C.Structure):
@@ -313,6 +262,119 @@ class DeviceInfo(C.Structure):
                 ("mem_bus_bits", C.c_int32), ("lds_per_block", C.c_int32), ("regs_per_block", C.c_int32),
                 ("l2_bytes", C.c_int32), ("device_index", C.c_int32), ("device_count", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+def _prototypes():
+    """{name: (restype, argtypes)} of every function include/mcamd.h declares.  Device pointers and opaque handles are
+    c_void_p (a torch data_ptr goes in as it is), host arrays and out-parameters POINTER(...)."""
+    P, vp, u32, u64, i32, f32, f64 = C.POINTER, C.c_void_p, C.c_uint32, C.c_uint64, C.c_int, C.c_float, C.c_double
+    pvp, pu32, pf32, pf64, res = P(vp), P(u32), P(f32), P(f64), P(Result)
+    job = (vp, P(Option), P(Sim))   # the head of a pricing call: the context (or group), the option, the simulation
+    table = {}
+
+    def fn(name, *argtypes, restype=i32):
+        table[name] = (restype, list(argtypes))
+
+    def pair(name, *terms, result=Result):
+        """a synchronous call that fills a result and its _enqueue form, which leaves device statistics instead"""
+        fn(name, *job, *terms, P(result))
+        fn(name + "_enqueue", *job, *terms, vp)
+
+    fn("mcamd_abi_version")
+    fn("mcamd_last_error", restype=C.c_char_p)
+    fn("mcamd_build_id", restype=C.c_char_p)
+    fn("mcamd_device_count", P(i32))
+    fn("mcamd_ctx_create", i32, vp, pvp)
+    fn("mcamd_ctx_destroy", vp)
+    fn("mcamd_get_device_info", vp, P(DeviceInfo))
+    fn("mcamd_device_malloc", vp, u64, pvp)
+    fn("mcamd_device_free", vp, vp)
+    fn("mcamd_memcpy_to_host", vp, vp, vp, u64)
+    fn("mcamd_memcpy_to_device", vp, vp, vp, u64)
+    fn("mcamd_enqueued_kernel_ms", vp, u32, pf32)
+    fn("mcamd_diag_store_pattern", vp, u64, u32, i32, vp, vp, pf32)
+    fn("mcamd_generate_normals", vp, u64, u64, i32, vp, pf32)
+    fn("mcamd_reduce_sum", vp, vp, u64, i32, i32, pf64, pf32)
+    fn("mcamd_reduce_partials", vp, vp, u64, i32, i32, u32, pf64, pf32)
+    fn("mcamd_cpu_mc_f32", P(Option), u64, u32, u64, i32, pf32, pf32)
+
+    # the paths of constant volatility: (ctx, opt, sim, the job's terms and device buffers, result or statistics)
+    pair("mcamd_price_paths")
+    pair("mcamd_simulate_trajectories", i32, vp, vp, vp)
+    pair("mcamd_nmc_inner", i32, i32, vp, vp, vp)
+    pair("mcamd_nmc_fused", u64, i32, vp, vp, vp)
+    fn("mcamd_price_from_normals", *job, vp, vp, res)
+    pair("mcamd_price_greeks", i32, result=Greeks)
+    pair("mcamd_price_barrier", P(Barrier), vp)
+    pair("mcamd_price_lookback", P(Lookback), vp)
+    pair("mcamd_price_basket", P(Basket), vp)
+    pair("mcamd_price_asian", P(Asian), vp)
+    pair("mcamd_price_autocall", P(Autocall), vp, result=AutocallResult)
+    fn("mcamd_american_workspace_bytes", P(American), P(Sim), P(u64))
+    fn("mcamd_price_american", *job, P(American), vp, u64, pf64, P(AmericanResult))
+    fn("mcamd_american_dual_workspace_bytes", P(American), P(Sim), P(AmericanDual), P(u64))
+    fn("mcamd_american_upper_bound", *job, P(American), P(AmericanDual), pf64, vp, u64, vp, P(AmericanDualResult))
+
+    # under a local-volatility surface
+    fn("mcamd_localvol_surface_create", vp, P(LocalVolGrid), pf64, pvp)
+    fn("mcamd_localvol_surface_destroy", vp)
+    pair("mcamd_price_localvol", P(LocalVol), vp, vp)
+    pair("mcamd_price_autocall_localvol", P(AutocallLocalVol), pvp, vp, result=AutocallResult)
+    pair("mcamd_price_localvol_greeks", P(LocalVolGreeksJob), vp, vp, result=LocalVolGreeks)
+    pair("mcamd_price_cliquet", P(Cliquet), vp, vp, result=CliquetResult)
+    fn("mcamd_price_localvol_smile", *job, P(Smile), pu32, pf64, vp, vp, pf64, res)
+    fn("mcamd_price_localvol_smile_enqueue", *job, P(Smile), pu32, pf64, vp, vp, vp)
+
+    # under Heston
+    pair("mcamd_price_heston", P(Heston), vp, vp, result=HestonResult)
+    pair("mcamd_price_heston_cliquet", P(Heston), P(Cliquet), vp, result=HestonCliquetResult)
+    pair("mcamd_price_heston_barrier", P(Heston), P(Barrier), vp, vp, result=HestonBarrierResult)
+    fn("mcamd_price_heston_smile", *job, P(Heston), u32, u32, pu32, pf64, vp, pf64, res)
+    fn("mcamd_price_heston_smile_enqueue", *job, P(Heston), u32, u32, pu32, pf64, vp, vp)
+
+    # a group: the first argument is the group, the device buffers are host arrays of one pointer per device
+    fn("mcamd_group_create", i32, P(i32), pvp)
+    fn("mcamd_group_destroy", vp)
+    fn("mcamd_group_size", vp, P(i32))
+    fn("mcamd_group_ctx", vp, i32, pvp)
+    fn("mcamd_group_shard", vp, P(Sim), i32, P(u64), P(u64))
+    fn("mcamd_group_price_paths", *job, res)
+    fn("mcamd_group_price_greeks", *job, i32, P(Greeks))
+    fn("mcamd_group_simulate_trajectories", *job, i32, pvp, pvp, pvp, res)
+    fn("mcamd_group_nmc_inner", *job, i32, i32, pvp, pvp, pvp, res)
+    fn("mcamd_group_nmc_fused", *job, u64, i32, pvp, pvp, pvp, res)
+
+    # host: statistics records into results
+    fn("mcamd_finalize", f64, f64, u64, f64, f64, res)
+    fn("mcamd_finalize_cv", pf64, u64, f64, f64, res)
+    fn("mcamd_finalize_stats", pf64, f64, f64, i32, res)
+    fn("mcamd_finalize_nmc_stats", pf64, res)
+    fn("mcamd_finalize_greeks_stats", pf64, f64, f64, i32, P(Greeks))
+    fn("mcamd_finalize_localvol_greeks_stats", pf64, f64, f64, u32, i32, P(LocalVolGreeks))
+    fn("mcamd_finalize_smile", pf64, u64, P(Option), u32, P(Smile), pu32, pf64, pf64)
+
+    # host: closed forms
+    fn("mcamd_cnd_f32", f32, restype=f32)
+    fn("mcamd_bs_call_f32", *[f32] * 5, restype=f32)
+    fn("mcamd_bs_call_f64", *[f64] * 5, restype=f64)
+    fn("mcamd_bs_greeks_f64", f64, f64, f64, f64, f64, pf64)
+    fn("mcamd_bs_price_f64", f64, f64, f64, f64, f64, f64, i32, pf64)
+    fn("mcamd_bs_implied_vol_f64", f64, f64, f64, f64, f64, i32, f64, pf64)
+    fn("mcamd_barrier_price_f64", f64, f64, f64, f64, f64, f64, i32, i32, pf64)
+    fn("mcamd_lookback_price_f64", f64, f64, f64, f64, f64, i32, i32, pf64)
+    fn("mcamd_basket_geometric_price_f64", P(Basket), f64, f64, f64, pf64)
+    fn("mcamd_exchange_price_f64", f64, f64, f64, f64, f64, f64, pf64)
+    fn("mcamd_asian_geometric_price_f64", f64, f64, f64, f64, f64, u32, i32, i32, i32, pf64)
+    fn("mcamd_autocall_single_date_price_f64", f64, f64, f64, f64, f64, f64, i32, pf64)
+    fn("mcamd_localvol_sigma_f64", P(LocalVolGrid), pf64, u32, u32, f64, pf64)
+    fn("mcamd_cliquet_price_f64", i32, f64, f64, f64, u32, u32, pf64, f64, f64, pf64)
+    fn("mcamd_heston_price_f64", *[f64] * 10, i32, pf64)
+    fn("mcamd_heston_cliquet_price_f64", i32, *[f64] * 8, u32, u32, f64, f64, pf64)
+    return table
+
+
+PROTOTYPES = _prototypes()
+EXPORTS = list(PROTOTYPES)   # every symbol include/mcamd.h declares
 
 
 class McamdError(RuntimeError):
@@ -333,137 +395,9 @@ def load() -> C.CDLL:
         raise ImportError(f"{LIB_PATH} not built: run `python __graft_entry__.py build` "
                           "(hipcc --offload-arch=gfx950); the engine has no CPU fallback")
     L = C.CDLL(LIB_PATH)
-    vp, u64, i32, f32, f64 = C.c_void_p, C.c_uint64, C.c_int, C.c_float, C.c_double
-    L.mcamd_abi_version.restype = i32
-    L.mcamd_last_error.restype = C.c_char_p
-    L.mcamd_build_id.restype = C.c_char_p
-    L.mcamd_device_count.argtypes = [C.POINTER(i32)]
-    L.mcamd_ctx_create.argtypes = [i32, vp, C.POINTER(vp)]
-    L.mcamd_ctx_destroy.argtypes = [vp]
-    L.mcamd_get_device_info.argtypes = [vp, C.POINTER(DeviceInfo)]
-    L.mcamd_device_malloc.argtypes = [vp, u64, C.POINTER(vp)]
-    L.mcamd_device_free.argtypes = [vp, vp]
-    L.mcamd_memcpy_to_host.argtypes = [vp, vp, vp, u64]
-    L.mcamd_memcpy_to_device.argtypes = [vp, vp, vp, u64]
-    L.mcamd_price_paths.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Result)]
-    L.mcamd_price_paths_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), vp]
-    L.mcamd_enqueued_kernel_ms.argtypes = [vp, C.c_uint32, C.POINTER(f32)]
-    L.mcamd_finalize_stats.argtypes = [C.POINTER(f64), f64, f64, i32, C.POINTER(Result)]
-    L.mcamd_group_create.argtypes = [i32, C.POINTER(i32), C.POINTER(vp)]
-    L.mcamd_group_destroy.argtypes = [vp]
-    L.mcamd_group_size.argtypes = [vp, C.POINTER(i32)]
-    L.mcamd_group_price_paths.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Result)]
-    L.mcamd_simulate_trajectories.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), i32, vp, vp, vp,
-                                              C.POINTER(Result)]
-    L.mcamd_simulate_trajectories_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), i32, vp, vp, vp, vp]
-    L.mcamd_nmc_inner_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), i32, i32, vp, vp, vp, vp]
-    L.mcamd_nmc_fused_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), u64, i32, vp, vp, vp, vp]
-    L.mcamd_finalize_nmc_stats.argtypes = [C.POINTER(f64), C.POINTER(Result)]
-    pvp = C.POINTER(vp)
-    L.mcamd_group_ctx.argtypes = [vp, i32, C.POINTER(vp)]
-    L.mcamd_group_shard.argtypes = [vp, C.POINTER(Sim), i32, C.POINTER(u64), C.POINTER(u64)]
-    L.mcamd_group_simulate_trajectories.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), i32, pvp, pvp, pvp,
-                                                    C.POINTER(Result)]
-    L.mcamd_group_nmc_inner.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), i32, i32, pvp, pvp, pvp, C.POINTER(Result)]
-    L.mcamd_group_nmc_fused.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), u64, i32, pvp, pvp, pvp, C.POINTER(Result)]
-    L.mcamd_diag_store_pattern.argtypes = [vp, u64, C.c_uint32, i32, vp, vp, C.POINTER(f32)]
-    L.mcamd_price_from_normals.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), vp, vp, C.POINTER(Result)]
-    L.mcamd_generate_normals.argtypes = [vp, u64, u64, i32, vp, C.POINTER(f32)]
-    L.mcamd_reduce_sum.argtypes = [vp, vp, u64, i32, i32, C.POINTER(f64), C.POINTER(f32)]
-    L.mcamd_reduce_partials.argtypes = [vp, vp, u64, i32, i32, C.c_uint32, C.POINTER(f64), C.POINTER(f32)]
-    L.mcamd_cpu_mc_f32.argtypes = [C.POINTER(Option), u64, C.c_uint32, u64, i32, C.POINTER(f32), C.POINTER(f32)]
-    L.mcamd_nmc_inner.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), i32, i32, vp, vp, vp, C.POINTER(Result)]
-    L.mcamd_nmc_fused.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), u64, i32, vp, vp, vp, C.POINTER(Result)]
-    L.mcamd_finalize.argtypes = [f64, f64, u64, f64, f64, C.POINTER(Result)]
-    L.mcamd_finalize_cv.argtypes = [C.POINTER(f64), u64, f64, f64, C.POINTER(Result)]
-    L.mcamd_cnd_f32.argtypes = [f32]
-    L.mcamd_cnd_f32.restype = f32
-    L.mcamd_bs_call_f32.argtypes = [f32] * 5
-    L.mcamd_bs_call_f32.restype = f32
-    L.mcamd_bs_call_f64.argtypes = [f64] * 5
-    L.mcamd_bs_call_f64.restype = f64
-    L.mcamd_price_greeks.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), i32, C.POINTER(Greeks)]
-    L.mcamd_price_greeks_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), i32, vp]
-    L.mcamd_finalize_greeks_stats.argtypes = [C.POINTER(f64), f64, f64, i32, C.POINTER(Greeks)]
-    L.mcamd_group_price_greeks.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), i32, C.POINTER(Greeks)]
-    L.mcamd_bs_greeks_f64.argtypes = [f64, f64, f64, f64, f64, C.POINTER(f64)]
-    L.mcamd_american_workspace_bytes.argtypes = [C.POINTER(American), C.POINTER(Sim), C.POINTER(u64)]
-    L.mcamd_price_american.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(American), vp, u64,
-                                       C.POINTER(f64), C.POINTER(AmericanResult)]
-    L.mcamd_american_dual_workspace_bytes.argtypes = [C.POINTER(American), C.POINTER(Sim), C.POINTER(AmericanDual),
-                                                      C.POINTER(u64)]
-    L.mcamd_american_upper_bound.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(American),
-                                             C.POINTER(AmericanDual), C.POINTER(f64), vp, u64, vp,
-                                             C.POINTER(AmericanDualResult)]
-    L.mcamd_price_barrier.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Barrier), vp, C.POINTER(Result)]
-    L.mcamd_price_barrier_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Barrier), vp, vp]
-    L.mcamd_barrier_price_f64.argtypes = [f64, f64, f64, f64, f64, f64, i32, i32, C.POINTER(f64)]
-    L.mcamd_price_lookback.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Lookback), vp, C.POINTER(Result)]
-    L.mcamd_price_lookback_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Lookback), vp, vp]
-    L.mcamd_lookback_price_f64.argtypes = [f64, f64, f64, f64, f64, i32, i32, C.POINTER(f64)]
-    L.mcamd_price_basket.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Basket), vp, C.POINTER(Result)]
-    L.mcamd_price_basket_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Basket), vp, vp]
-    L.mcamd_basket_geometric_price_f64.argtypes = [C.POINTER(Basket), f64, f64, f64, C.POINTER(f64)]
-    L.mcamd_exchange_price_f64.argtypes = [f64, f64, f64, f64, f64, f64, C.POINTER(f64)]
-    L.mcamd_price_asian.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Asian), vp, C.POINTER(Result)]
-    L.mcamd_price_asian_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Asian), vp, vp]
-    L.mcamd_asian_geometric_price_f64.argtypes = [f64, f64, f64, f64, f64, C.c_uint32, i32, i32, i32, C.POINTER(f64)]
-    L.mcamd_price_autocall.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Autocall), vp,
-                                       C.POINTER(AutocallResult)]
-    L.mcamd_price_autocall_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Autocall), vp, vp]
-    L.mcamd_price_autocall_localvol.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(AutocallLocalVol),
-                                                C.POINTER(vp), vp, C.POINTER(AutocallResult)]
-    L.mcamd_price_autocall_localvol_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim),
-                                                        C.POINTER(AutocallLocalVol), C.POINTER(vp), vp, vp]
-    L.mcamd_autocall_single_date_price_f64.argtypes = [f64, f64, f64, f64, f64, f64, i32, C.POINTER(f64)]
-    L.mcamd_localvol_surface_create.argtypes = [vp, C.POINTER(LocalVolGrid), C.POINTER(f64), C.POINTER(vp)]
-    L.mcamd_localvol_surface_destroy.argtypes = [vp]
-    L.mcamd_price_localvol.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(LocalVol), vp, vp,
-                                       C.POINTER(Result)]
-    L.mcamd_price_localvol_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(LocalVol), vp, vp, vp]
-    L.mcamd_price_cliquet.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Cliquet), vp, vp,
-                                      C.POINTER(CliquetResult)]
-    L.mcamd_price_cliquet_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Cliquet), vp, vp, vp]
-    L.mcamd_cliquet_price_f64.argtypes = [i32, f64, f64, f64, C.c_uint32, C.c_uint32, C.POINTER(f64), f64, f64,
-                                          C.POINTER(f64)]
-    L.mcamd_price_heston.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Heston), vp, vp,
-                                     C.POINTER(HestonResult)]
-    L.mcamd_price_heston_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Heston), vp, vp, vp]
-    L.mcamd_heston_price_f64.argtypes = [f64] * 10 + [i32, C.POINTER(f64)]
-    L.mcamd_price_heston_cliquet.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Heston), C.POINTER(Cliquet),
-                                             vp, C.POINTER(HestonCliquetResult)]
-    L.mcamd_price_heston_cliquet_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Heston),
-                                                     C.POINTER(Cliquet), vp, vp]
-    L.mcamd_price_heston_barrier.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Heston), C.POINTER(Barrier),
-                                             vp, vp, C.POINTER(HestonBarrierResult)]
-    L.mcamd_price_heston_barrier_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Heston),
-                                                     C.POINTER(Barrier), vp, vp, vp]
-    L.mcamd_heston_cliquet_price_f64.argtypes =[i32] + [f64] * 8 + [C.c_uint32, C.c_uint32, f64, f64, C.POINTER(f64)]
-    L.mcamd_localvol_sigma_f64.argtypes = [C.POINTER(LocalVolGrid), C.POINTER(f64), C.c_uint32, C.c_uint32, f64,
-                                           C.POINTER(f64)]
-    L.mcamd_bs_price_f64.argtypes = [f64, f64, f64, f64, f64, f64, i32, C.POINTER(f64)]
-    L.mcamd_bs_implied_vol_f64.argtypes = [f64, f64, f64, f64, f64, i32, f64, C.POINTER(f64)]
-    u32p = C.POINTER(C.c_uint32)
-    L.mcamd_price_localvol_smile.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Smile), u32p,
-                                             C.POINTER(f64), vp, vp, C.POINTER(f64), C.POINTER(Result)]
-    L.mcamd_price_localvol_smile_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Smile), u32p,
-                                                     C.POINTER(f64), vp, vp, vp]
-    L.mcamd_finalize_smile.argtypes = [C.POINTER(f64), u64, C.POINTER(Option), C.c_uint32, C.POINTER(Smile), u32p,
-                                       C.POINTER(f64), C.POINTER(f64)]
-    L.mcamd_price_heston_smile.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Heston), C.c_uint32, C.c_uint32,
-                                           u32p, C.POINTER(f64), vp, C.POINTER(f64), C.POINTER(Result)]
-    L.mcamd_price_heston_smile_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(Heston), C.c_uint32,
-                                                   C.c_uint32, u32p, C.POINTER(f64), vp, vp]
-    L.mcamd_price_localvol_greeks.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(LocalVolGreeksJob), vp, vp,
-                                              C.POINTER(LocalVolGreeks)]
-    L.mcamd_price_localvol_greeks_enqueue.argtypes = [vp, C.POINTER(Option), C.POINTER(Sim), C.POINTER(LocalVolGreeksJob),
-                                                      vp, vp, vp]
-    L.mcamd_finalize_localvol_greeks_stats.argtypes = [C.POINTER(f64), f64, f64, C.c_uint32, i32,
-                                                       C.POINTER(LocalVolGreeks)]
-    for name in EXPORTS:
+    for name, (restype, argtypes) in PROTOTYPES.items():
         fn = getattr(L, name)
-        if fn.restype is C.c_int and name not in ("mcamd_abi_version",):
-            fn.restype = C.c_int
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -471,6 +405,32 @@ def load() -> C.CDLL:
 def _check(rc: int):
     if rc != OK:
         raise McamdError(rc, load().mcamd_last_error().decode())
+
+
+def _filled(fn, result, *args):
+    """what the C function fn leaves in its last parameter: fn(*args, &out) on a fresh out = result(), checked.  A
+    struct or scalar passed where the prototype says POINTER(its type) goes by reference, and None goes as NULL:
+    ctypes does both from argtypes."""
+    out = result()
+    _check(getattr(load(), fn)(*args, out))
+    return out
+
+
+def _out_double(fn, *args) -> float:
+    """the value a closed form leaves in its last parameter, a double *"""
+    return _filled(fn, C.c_double, *args).value
+
+
+def _doubles(values, n):
+    """values as a C array of n doubles (fewer are padded with zeros; more are an IndexError)"""
+    return (C.c_double * n)(*[float(x) for x in values])
+
+
+def _fill_corr(table, corr, d):
+    """the d x d correlations into a struct's table, whose rows are 8 apart"""
+    for j in range(d):
+        for k in range(d):
+            table[8 * j + k] = float(corr[j][k])
 
 
 def make_option(S0=100.0, T=1.0, K=100.0, r=0.1, v=0.2, B=0.0, P1=0, P2=0, use_window=0, Ik=0, Sk=0.0,
@@ -512,9 +472,7 @@ def make_barrier(kind=BARRIER_DOWN_OUT, payoff=PAYOFF_CALL, monitoring=MONITOR_C
 
 def barrier_price_f64(S0, K, B, T, r, sigma, kind=BARRIER_DOWN_OUT, payoff=PAYOFF_CALL) -> float:
     """closed form of the continuously monitored single barrier (Reiner-Rubinstein), rebate 0"""
-    p = C.c_double(0)
-    _check(load().mcamd_barrier_price_f64(S0, K, B, T, r, sigma, kind, payoff, C.byref(p)))
-    return p.value
+    return _out_double("mcamd_barrier_price_f64", S0, K, B, T, r, sigma, kind, payoff)
 
 
 def make_lookback(strike=LOOKBACK_FLOATING, payoff=PAYOFF_CALL, monitoring=MONITOR_CONTINUOUS) -> Lookback:
@@ -523,9 +481,7 @@ def make_lookback(strike=LOOKBACK_FLOATING, payoff=PAYOFF_CALL, monitoring=MONIT
 
 def lookback_price_f64(S0, K, T, r, sigma, strike=LOOKBACK_FLOATING, payoff=PAYOFF_CALL) -> float:
     """closed form of the continuously monitored, newly issued lookback (Goldman-Sosin-Gatto, Conze-Viswanathan)"""
-    p = C.c_double(0)
-    _check(load().mcamd_lookback_price_f64(S0, K, T, r, sigma, strike, payoff, C.byref(p)))
-    return p.value
+    return _out_double("mcamd_lookback_price_f64", S0, K, T, r, sigma, strike, payoff)
 
 
 def make_basket(S0, v, w, corr, kind=BASKET_ARITHMETIC, payoff=PAYOFF_CALL, barrier=BASKET_NO_BARRIER) -> Basket:
@@ -536,23 +492,18 @@ def make_basket(S0, v, w, corr, kind=BASKET_ARITHMETIC, payoff=PAYOFF_CALL, barr
     b = Basket(d, kind, payoff, barrier)
     for j in range(d):
         b.S0[j], b.v[j], b.w[j] = float(S0[j]), float(v[j]), float(w[j])
-        for k in range(d):
-            b.corr[8 * j + k] = float(corr[j][k])
+    _fill_corr(b.corr, corr, d)
     return b
 
 
 def basket_geometric_price_f64(basket: Basket, K, T, r) -> float:
     """closed form of the geometric basket (a lognormal); basket.payoff selects call or put"""
-    p = C.c_double(0)
-    _check(load().mcamd_basket_geometric_price_f64(C.byref(basket), K, T, r, C.byref(p)))
-    return p.value
+    return _out_double("mcamd_basket_geometric_price_f64", basket, K, T, r)
 
 
 def exchange_price_f64(a_S1, b_S2, T, v1, v2, rho) -> float:
     """Margrabe's closed form of (a S1 - b S2)+, with a_S1 = a S1(0) and b_S2 = b S2(0)"""
-    p = C.c_double(0)
-    _check(load().mcamd_exchange_price_f64(a_S1, b_S2, T, v1, v2, rho, C.byref(p)))
-    return p.value
+    return _out_double("mcamd_exchange_price_f64", a_S1, b_S2, T, v1, v2, rho)
 
 
 def make_asian(average=ASIAN_ARITHMETIC, strike=ASIAN_FIXED, payoff=PAYOFF_CALL, include_spot=0,
@@ -562,39 +513,34 @@ def make_asian(average=ASIAN_ARITHMETIC, strike=ASIAN_FIXED, payoff=PAYOFF_CALL,
 
 def asian_geometric_price_f64(S0, K, T, r, sigma, n_steps, include_spot=0, strike=ASIAN_FIXED, payoff=PAYOFF_CALL) -> float:
     """closed form of the discrete geometric-average option over the n_steps step ends (and t = 0 with include_spot)"""
-    p = C.c_double(0)
-    _check(load().mcamd_asian_geometric_price_f64(S0, K, T, r, sigma, n_steps, include_spot, strike, payoff, C.byref(p)))
-    return p.value
+    return _out_double("mcamd_asian_geometric_price_f64", S0, K, T, r, sigma, n_steps, include_spot, strike, payoff)
+
+
+def _autocall_terms(cls, field, per_asset, corr, observe_every, call_level, coupon, ki_level, ki_monitoring,
+                    call_step_down, first_call_date):
+    """an Autocall or AutocallLocalVol: they differ in the per-asset field, v or q"""
+    d = len(per_asset)
+    if not 1 <= d <= BASKET_MAX_ASSETS or len(corr) != d or any(len(row) != d for row in corr):
+        raise ValueError(f"an autocallable takes 1..{BASKET_MAX_ASSETS} assets, {field} of d and corr of d x d values")
+    a = cls(d, ki_monitoring, observe_every, first_call_date)
+    a.call_level, a.call_step_down, a.coupon, a.ki_level = call_level, call_step_down, coupon, ki_level
+    getattr(a, field)[:d] = [float(x) for x in per_asset]
+    _fill_corr(a.corr, corr, d)
+    return a
 
 
 def make_autocall(v, corr, observe_every=1, call_level=1.0, coupon=0.0, ki_level=0.0,
                   ki_monitoring=AUTOCALL_KI_NONE, call_step_down=0.0, first_call_date=1) -> Autocall:
     """v: d volatilities (d at most BASKET_MAX_ASSETS); corr: d x d (nested sequences or an array)."""
-    d = len(v)
-    if not 1 <= d <= BASKET_MAX_ASSETS or len(corr) != d or any(len(row) != d for row in corr):
-        raise ValueError(f"an autocallable takes 1..{BASKET_MAX_ASSETS} assets, v of d and corr of d x d values")
-    a = Autocall(d, ki_monitoring, observe_every, first_call_date)
-    a.call_level, a.call_step_down, a.coupon, a.ki_level = call_level, call_step_down, coupon, ki_level
-    for j in range(d):
-        a.v[j] = float(v[j])
-        for k in range(d):
-            a.corr[8 * j + k] = float(corr[j][k])
-    return a
+    return _autocall_terms(Autocall, "v", v, corr, observe_every, call_level, coupon, ki_level, ki_monitoring,
+                           call_step_down, first_call_date)
 
 
 def make_autocall_localvol(q, corr, observe_every=1, call_level=1.0, coupon=0.0, ki_level=0.0,
                            ki_monitoring=AUTOCALL_KI_NONE, call_step_down=0.0, first_call_date=1) -> AutocallLocalVol:
     """q: d dividend yields (d at most BASKET_MAX_ASSETS); corr: d x d (nested sequences or an array)."""
-    d = len(q)
-    if not 1 <= d <= BASKET_MAX_ASSETS or len(corr) != d or any(len(row) != d for row in corr):
-        raise ValueError(f"an autocallable takes 1..{BASKET_MAX_ASSETS} assets, q of d and corr of d x d values")
-    a = AutocallLocalVol(d, ki_monitoring, observe_every, first_call_date)
-    a.call_level, a.call_step_down, a.coupon, a.ki_level = call_level, call_step_down, coupon, ki_level
-    for j in range(d):
-        a.q[j] = float(q[j])
-        for k in range(d):
-            a.corr[8 * j + k] = float(corr[j][k])
-    return a
+    return _autocall_terms(AutocallLocalVol, "q", q, corr, observe_every, call_level, coupon, ki_level, ki_monitoring,
+                           call_step_down, first_call_date)
 
 
 def surface_array(surfaces):
@@ -607,10 +553,7 @@ def surface_array(surfaces):
 
 def autocall_single_date_price_f64(T, r, sigma, call_level, coupon, ki_level=0.0, ki_monitoring=AUTOCALL_KI_NONE) -> float:
     """closed form of the autocallable on one asset with one date (no knock-in, or a knock-in at maturity)"""
-    p = C.c_double(0)
-    _check(load().mcamd_autocall_single_date_price_f64(T, r, sigma, call_level, coupon, ki_level, ki_monitoring,
-                                                       C.byref(p)))
-    return p.value
+    return _out_double("mcamd_autocall_single_date_price_f64", T, r, sigma, call_level, coupon, ki_level, ki_monitoring)
 
 
 def make_localvol(payoff=PAYOFF_CALL, barrier=LOCALVOL_NO_BARRIER, monitoring=MONITOR_DISCRETE, q=0.0) -> LocalVol:
@@ -625,11 +568,8 @@ def make_cliquet(kind=CLIQUET_SUM, reset_every=1, first_period=1, local_floor=-m
 def cliquet_price(kind, T, r, q, period_vol, first_period=1, local_floor=-math.inf, local_cap=math.inf) -> float:
     """Closed form of a cliquet without a global clip where the volatility varies in time only
     (mcamd_cliquet_price_f64); period_vol: the rms volatility of each of the n_periods = len(period_vol) periods."""
-    vols = (C.c_double * len(period_vol))(*[float(v) for v in period_vol])
-    out = C.c_double()
-    _check(load().mcamd_cliquet_price_f64(kind, T, r, q, len(period_vol), first_period, vols, local_floor, local_cap,
-                                          C.byref(out)))
-    return out.value
+    return _out_double("mcamd_cliquet_price_f64", kind, T, r, q, len(period_vol), first_period,
+                       _doubles(period_vol, len(period_vol)), local_floor, local_cap)
 
 
 def make_heston(payoff=PAYOFF_CALL, q=0.0, v0=0.04, kappa=2.0, theta=0.04, xi=0.3, rho=-0.7,
@@ -640,9 +580,7 @@ def make_heston(payoff=PAYOFF_CALL, q=0.0, v0=0.04, kappa=2.0, theta=0.04, xi=0.
 def heston_price(S0, K, T, r, q, v0, kappa, theta, xi, rho, payoff=PAYOFF_CALL) -> float:
     """Closed form of a European option under Heston (mcamd_heston_price_f64): the model's price, which the
     full-truncation scheme of price_heston approaches at first order in the step."""
-    out = C.c_double()
-    _check(load().mcamd_heston_price_f64(S0, K, T, r, q, v0, kappa, theta, xi, rho, payoff, C.byref(out)))
-    return out.value
+    return _out_double("mcamd_heston_price_f64", S0, K, T, r, q, v0, kappa, theta, xi, rho, payoff)
 
 
 def heston_cliquet_price(kind, T, r, q, v0, kappa, theta, xi, rho, n_periods, first_period=1, local_floor=-math.inf,
@@ -650,10 +588,8 @@ def heston_cliquet_price(kind, T, r, q, v0, kappa, theta, xi, rho, n_periods, fi
     """Closed form of an additive cliquet, a one-period compounding one or a discretely sampled variance swap under
     Heston, without a global clip (mcamd_heston_cliquet_price_f64): the model's price, through the forward
     characteristic function of the period returns."""
-    out = C.c_double()
-    _check(load().mcamd_heston_cliquet_price_f64(kind, T, r, q, v0, kappa, theta, xi, rho, n_periods, first_period,
-                                                 local_floor, local_cap, C.byref(out)))
-    return out.value
+    return _out_double("mcamd_heston_cliquet_price_f64", kind, T, r, q, v0, kappa, theta, xi, rho, n_periods,
+                       first_period, local_floor, local_cap)
 
 
 def heston_smile_prices(S0, strikes, times, r, q, v0, kappa, theta, xi, rho, payoff=PAYOFF_CALL):
@@ -684,24 +620,18 @@ def localvol_sigma_f64(grid, sigma, n_steps, step, x) -> float:
     """the volatility step `step` of n_steps uses at x = ln(S / S0) (mcamd_localvol_sigma_f64); grid: a LocalVolGrid
     or its (n_t, n_x, x_min, x_max)"""
     g = grid if isinstance(grid, LocalVolGrid) else make_localvol_grid(*grid)
-    out = C.c_double(0)
-    _check(load().mcamd_localvol_sigma_f64(C.byref(g), _sigma_array(g, sigma), n_steps, step, x, C.byref(out)))
-    return out.value
+    return _out_double("mcamd_localvol_sigma_f64", g, _sigma_array(g, sigma), n_steps, step, x)
 
 
 def bs_price_f64(S0, K, T, r, q, sigma, payoff=PAYOFF_CALL) -> float:
     """Black-Scholes with a continuous dividend yield q"""
-    p = C.c_double(0)
-    _check(load().mcamd_bs_price_f64(S0, K, T, r, q, sigma, payoff, C.byref(p)))
-    return p.value
+    return _out_double("mcamd_bs_price_f64", S0, K, T, r, q, sigma, payoff)
 
 
 def bs_implied_vol(S0, K, T, r, q, price, payoff=PAYOFF_CALL) -> float:
     """the volatility at which bs_price_f64 gives `price` (mcamd_bs_implied_vol_f64); raises McamdError for a price
     that is not strictly inside the no-arbitrage bounds"""
-    v = C.c_double(0)
-    _check(load().mcamd_bs_implied_vol_f64(S0, K, T, r, q, payoff, price, C.byref(v)))
-    return v.value
+    return _out_double("mcamd_bs_implied_vol_f64", S0, K, T, r, q, payoff, price)
 
 
 def make_smile(n_expiries, n_strikes, payoff=PAYOFF_CALL, q=0.0) -> Smile:
@@ -722,7 +652,7 @@ def finalize_smile(stats, n, opt: Option, n_steps, smile: Smile, expiry_steps):
     (mcamd_finalize_smile): every node is discounted to its own expiry"""
     import numpy as np
     nodes = smile.n_expiries * smile.n_strikes
-    arr = (C.c_double * (2 * nodes))(*[float(x) for x in list(stats)[:2 * nodes]])
+    arr = _doubles(list(stats)[:2 * nodes], 2 * nodes)
     steps, _ = _smile_arrays(smile, expiry_steps, [1.0] * smile.n_strikes)
     price, se = (C.c_double * nodes)(), (C.c_double * nodes)()
     _check(load().mcamd_finalize_smile(arr, int(n), C.byref(opt), n_steps, C.byref(smile), steps, price, se))
@@ -765,46 +695,30 @@ def _ptr(t):
 
 
 def finalize(sum_, sumsq, n, r, T) -> Result:
-    res = Result()
-    _check(load().mcamd_finalize(sum_, sumsq, n, r, T, C.byref(res)))
-    return res
+    return _filled("mcamd_finalize", Result, sum_, sumsq, n, r, T)
 
 
 def finalize_cv(sums, n, r, T) -> Result:
-    res = Result()
-    arr = (C.c_double * 5)(*sums)
-    _check(load().mcamd_finalize_cv(arr, n, r, T, C.byref(res)))
-    return res
+    return _filled("mcamd_finalize_cv", Result, _doubles(sums, 5), n, r, T)
 
 
 def finalize_stats(stats6, r, T, control_variate=False) -> Result:
-    res = Result()
-    arr = (C.c_double * 6)(*[float(x) for x in stats6])
-    _check(load().mcamd_finalize_stats(arr, r, T, int(control_variate), C.byref(res)))
-    return res
+    return _filled("mcamd_finalize_stats", Result, _doubles(stats6, 6), r, T, int(control_variate))
 
 
 def finalize_nmc_stats(stats6) -> Result:
-    res = Result()
-    arr = (C.c_double * 6)(*[float(x) for x in stats6])
-    _check(load().mcamd_finalize_nmc_stats(arr, C.byref(res)))
-    return res
+    return _filled("mcamd_finalize_nmc_stats", Result, _doubles(stats6, 6))
 
 
 def finalize_greeks_stats(stats16, r, T, theta_defined=True) -> Greeks:
     """Greeks of a (possibly all-reduced) 16-double record left by Context.price_greeks_enqueue."""
-    out = Greeks()
-    arr = (C.c_double * GREEKS_STATS)(*[float(x) for x in stats16])
-    _check(load().mcamd_finalize_greeks_stats(arr, r, T, int(theta_defined), C.byref(out)))
-    return out
+    return _filled("mcamd_finalize_greeks_stats", Greeks, _doubles(stats16, GREEKS_STATS), r, T, int(theta_defined))
 
 
 def finalize_localvol_greeks_stats(stats32, r, T, n_vega_buckets=0, gamma_defined=True) -> LocalVolGreeks:
     """Greeks of a (possibly all-reduced) 32-double record left by Context.price_localvol_greeks_enqueue."""
-    out = LocalVolGreeks()
-    arr = (C.c_double * LOCALVOL_GREEKS_STATS)(*[float(x) for x in stats32])
-    _check(load().mcamd_finalize_localvol_greeks_stats(arr, r, T, n_vega_buckets, int(gamma_defined), C.byref(out)))
-    return out
+    return _filled("mcamd_finalize_localvol_greeks_stats", LocalVolGreeks, _doubles(stats32, LOCALVOL_GREEKS_STATS),
+                   r, T, n_vega_buckets, int(gamma_defined))
 
 
 def bs_greeks_f64(S0, K, T, r, sigma):
@@ -843,20 +757,21 @@ def device_count() -> int:
     return n.value if rc == OK else 0
 
 
-class Context:
-    """Owns one mcamd_ctx (one device, one stream)."""
+class _Handle:
+    """Owns one opaque handle of the library (_h, on the loaded library _L); a subclass names the function that
+    destroys it and creates the handle in its __init__."""
+    _destroy = None
 
-    def __init__(self, device: int = 0, stream: int | None = None):
+    def __init__(self):
         self._L = load()
         self._h = C.c_void_p()
-        _check(self._L.mcamd_ctx_create(device, C.c_void_p(stream) if stream else None, C.byref(self._h)))
 
     def close(self):
         if self._h:
-            self._L.mcamd_ctx_destroy(self._h)
+            getattr(self._L, self._destroy)(self._h)
             self._h = C.c_void_p()
 
-    def __del__(self):
+    def _close_quietly(self):
         try:
             self.close()
         except Exception:
@@ -868,41 +783,49 @@ class Context:
     def __exit__(self, *exc):
         self.close()
 
+    def _sync(self, fn, result, *args):
+        """a synchronous call: fn(handle, *args, &res) on a fresh result(), which it returns"""
+        return _filled(fn, result, self._h, *args)
+
+    def _enqueue(self, fn, *args):
+        """an asynchronous call: fn(handle, *args), whose last argument is the device record it leaves"""
+        _check(getattr(self._L, fn)(self._h, *args))
+
+
+class Context(_Handle):
+    """Owns one mcamd_ctx (one device, one stream)."""
+    _destroy = "mcamd_ctx_destroy"
+    __del__ = _Handle._close_quietly
+
+    def __init__(self, device: int = 0, stream: int | None = None):
+        super().__init__()
+        _check(self._L.mcamd_ctx_create(device, C.c_void_p(stream) if stream else None, C.byref(self._h)))
+
     def device_info(self) -> DeviceInfo:
-        info = DeviceInfo()
-        _check(self._L.mcamd_get_device_info(self._h, C.byref(info)))
-        return info
+        return self._sync("mcamd_get_device_info", DeviceInfo)
 
     def price_paths(self, opt: Option, sim: Sim) -> Result:
-        res = Result()
-        _check(self._L.mcamd_price_paths(self._h, C.byref(opt), C.byref(sim), C.byref(res)))
-        return res
+        return self._sync("mcamd_price_paths", Result, opt, sim)
 
     def price_paths_enqueue(self, opt: Option, sim: Sim, stats) -> None:
         """Asynchronous: leaves {sum, sumsq, sum_c, sum_cc, sum_yc, n} in the device tensor `stats` (>= 6 doubles)."""
-        _check(self._L.mcamd_price_paths_enqueue(self._h, C.byref(opt), C.byref(sim), _ptr(stats)))
+        self._enqueue("mcamd_price_paths_enqueue", opt, sim, _ptr(stats))
 
     def price_greeks(self, opt: Option, sim: Sim, method: int = GREEKS_AUTO) -> Greeks:
-        out = Greeks()
-        _check(self._L.mcamd_price_greeks(self._h, C.byref(opt), C.byref(sim), method, C.byref(out)))
-        return out
+        return self._sync("mcamd_price_greeks", Greeks, opt, sim, method)
 
     def price_greeks_enqueue(self, opt: Option, sim: Sim, stats, method: int = GREEKS_AUTO) -> None:
         """Asynchronous: leaves the 16-double Greeks record in the device tensor `stats` (finalize_greeks_stats)."""
-        _check(self._L.mcamd_price_greeks_enqueue(self._h, C.byref(opt), C.byref(sim), method, _ptr(stats)))
+        self._enqueue("mcamd_price_greeks_enqueue", opt, sim, method, _ptr(stats))
 
     def price_barrier(self, opt: Option, sim: Sim, barrier: Barrier, samples=None) -> Result:
         """Single-barrier option (mcamd_price_barrier); opt.B is the level.  samples: optional device tensor of
         n_paths_local values of the path precision that receives each path's undiscounted sample."""
-        res = Result()
-        _check(self._L.mcamd_price_barrier(self._h, C.byref(opt), C.byref(sim), C.byref(barrier), _ptr(samples),
-                                           C.byref(res)))
-        return res
+        return self._sync("mcamd_price_barrier", Result, opt, sim, barrier, _ptr(samples))
 
     def price_barrier_enqueue(self, opt: Option, sim: Sim, barrier: Barrier, stats, samples=None) -> None:
         """Asynchronous: leaves {sum, sumsq, 0, 0, 0, n} in the device tensor `stats` (>= 6 doubles; finalize_stats)."""
-        _check(self._L.mcamd_price_barrier_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(barrier),
-                                                   _ptr(samples), _ptr(stats)))
+        self._enqueue("mcamd_price_barrier_enqueue", opt, sim, barrier, _ptr(samples), _ptr(stats))
 
     def localvol_surface(self, grid_args, sigma) -> "LocalVolSurface":
         """An immutable local-volatility surface on this context (mcamd_localvol_surface_create).  grid_args: a
@@ -914,49 +837,37 @@ class Context:
         """European or single-barrier option under a local-volatility surface (mcamd_price_localvol); opt.v is
         ignored, opt.B is the barrier level.  samples: optional device tensor of n_paths_local values of the path
         precision that receives each path's undiscounted sample."""
-        res = Result()
-        _check(self._L.mcamd_price_localvol(self._h, C.byref(opt), C.byref(sim), C.byref(localvol), surface._h,
-                                            _ptr(samples), C.byref(res)))
-        return res
+        return self._sync("mcamd_price_localvol", Result, opt, sim, localvol, surface._h, _ptr(samples))
 
     def price_localvol_enqueue(self, opt: Option, sim: Sim, localvol: LocalVol, surface: "LocalVolSurface", stats,
                                samples=None) -> None:
         """Asynchronous: leaves {sum, sumsq, 0, 0, 0, n} in the device tensor `stats` (>= 6 doubles; finalize_stats)."""
-        _check(self._L.mcamd_price_localvol_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(localvol), surface._h,
-                                                    _ptr(samples), _ptr(stats)))
+        self._enqueue("mcamd_price_localvol_enqueue", opt, sim, localvol, surface._h, _ptr(samples), _ptr(stats))
 
     def price_cliquet(self, opt: Option, sim: Sim, cliquet: Cliquet, surface: "LocalVolSurface",
                       samples=None) -> CliquetResult:
         """Cliquet, forward-start option or realized-variance swap on the paths of price_localvol
         (mcamd_price_cliquet); r, T and S0 come from opt, opt.v, opt.K and opt.B are ignored.  samples: optional device
         tensor of n_paths_local values of the path precision that receives each path's undiscounted sample."""
-        res = CliquetResult()
-        _check(self._L.mcamd_price_cliquet(self._h, C.byref(opt), C.byref(sim), C.byref(cliquet), surface._h,
-                                           _ptr(samples), C.byref(res)))
-        return res
+        return self._sync("mcamd_price_cliquet", CliquetResult, opt, sim, cliquet, surface._h, _ptr(samples))
 
     def price_cliquet_enqueue(self, opt: Option, sim: Sim, cliquet: Cliquet, surface: "LocalVolSurface", stats,
                               samples=None) -> None:
         """Asynchronous: leaves {sum, sumsq, n_floored, n_capped, 0, n} in the device tensor `stats` (>= 6 doubles;
         finalize_stats)."""
-        _check(self._L.mcamd_price_cliquet_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(cliquet), surface._h,
-                                                   _ptr(samples), _ptr(stats)))
+        self._enqueue("mcamd_price_cliquet_enqueue", opt, sim, cliquet, surface._h, _ptr(samples), _ptr(stats))
 
     def price_heston(self, opt: Option, sim: Sim, heston: Heston, samples=None, state=None) -> HestonResult:
         """European option under Heston stochastic volatility, full-truncation Euler in the log-price
         (mcamd_price_heston); r, T, S0 and K come from opt, opt.v and opt.B are ignored.  samples: optional device
         tensor of n_paths_local values of the path precision that receives each path's undiscounted sample; state:
         optional device tensor of 2 x n_paths_local such values that receives S_T, then the raw final variance."""
-        res = HestonResult()
-        _check(self._L.mcamd_price_heston(self._h, C.byref(opt), C.byref(sim), C.byref(heston), _ptr(samples),
-                                          _ptr(state), C.byref(res)))
-        return res
+        return self._sync("mcamd_price_heston", HestonResult, opt, sim, heston, _ptr(samples), _ptr(state))
 
     def price_heston_enqueue(self, opt: Option, sim: Sim, heston: Heston, stats, samples=None, state=None) -> None:
         """Asynchronous: leaves {sum, sumsq, truncated_steps, sum of the paths' average variance, 0, n} in the device
         tensor `stats` (>= 6 doubles; finalize_stats)."""
-        _check(self._L.mcamd_price_heston_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(heston), _ptr(samples),
-                                                  _ptr(state), _ptr(stats)))
+        self._enqueue("mcamd_price_heston_enqueue", opt, sim, heston, _ptr(samples), _ptr(state), _ptr(stats))
 
     def price_heston_cliquet(self, opt: Option, sim: Sim, heston: Heston, cliquet: Cliquet,
                              samples=None) -> HestonCliquetResult:
@@ -964,17 +875,13 @@ class Context:
         (mcamd_price_heston_cliquet); r, T and S0 come from opt, opt.v, opt.K and opt.B are ignored, heston.payoff is
         not read and cliquet.q must equal heston.q.  samples: optional device tensor of n_paths_local values of the
         path precision that receives each path's undiscounted sample."""
-        res = HestonCliquetResult()
-        _check(self._L.mcamd_price_heston_cliquet(self._h, C.byref(opt), C.byref(sim), C.byref(heston), C.byref(cliquet),
-                                                  _ptr(samples), C.byref(res)))
-        return res
+        return self._sync("mcamd_price_heston_cliquet", HestonCliquetResult, opt, sim, heston, cliquet, _ptr(samples))
 
     def price_heston_cliquet_enqueue(self, opt: Option, sim: Sim, heston: Heston, cliquet: Cliquet, stats,
                                      samples=None) -> None:
         """Asynchronous: leaves {sum, sumsq, n_floored, n_capped, sum of the paths' average variance, n} in the device
         tensor `stats` (>= 6 doubles; finalize_stats)."""
-        _check(self._L.mcamd_price_heston_cliquet_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(heston),
-                                                          C.byref(cliquet), _ptr(samples), _ptr(stats)))
+        self._enqueue("mcamd_price_heston_cliquet_enqueue", opt, sim, heston, cliquet, _ptr(samples), _ptr(stats))
 
     def price_heston_barrier(self, opt: Option, sim: Sim, heston: Heston, barrier: Barrier, samples=None,
                              state=None) -> HestonBarrierResult:
@@ -983,17 +890,15 @@ class Context:
         of n_paths_local values of the path precision that receives each path's undiscounted sample; state: optional
         device tensor of 3 x n_paths_local such values that receives S_T, then the raw final variance, then the
         survival weight (a knock-out path that was hit: NaN, NaN, 0)."""
-        res = HestonBarrierResult()
-        _check(self._L.mcamd_price_heston_barrier(self._h, C.byref(opt), C.byref(sim), C.byref(heston), C.byref(barrier),
-                                                  _ptr(samples), _ptr(state), C.byref(res)))
-        return res
+        return self._sync("mcamd_price_heston_barrier", HestonBarrierResult, opt, sim, heston, barrier, _ptr(samples),
+                          _ptr(state))
 
     def price_heston_barrier_enqueue(self, opt: Option, sim: Sim, heston: Heston, barrier: Barrier, stats, samples=None,
                                      state=None) -> None:
         """Asynchronous: leaves {sum, sumsq, live_steps, truncated_steps, sum of v+ over the counted lane-steps, n} in
         the device tensor `stats` (>= 6 doubles; finalize_stats)."""
-        _check(self._L.mcamd_price_heston_barrier_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(heston),
-                                                          C.byref(barrier), _ptr(samples), _ptr(state), _ptr(stats)))
+        self._enqueue("mcamd_price_heston_barrier_enqueue", opt, sim, heston, barrier, _ptr(samples), _ptr(state),
+                      _ptr(stats))
 
     def price_heston_smile(self, opt: Option, sim: Sim, heston: Heston, expiry_steps, strikes, state=None):
         """len(expiry_steps) x len(strikes) vanillas on one set of price_heston's paths (mcamd_price_heston_smile);
@@ -1013,9 +918,8 @@ class Context:
         finalize_smile serves the sums)."""
         smile = make_smile(len(expiry_steps), len(strikes), heston.payoff, heston.q)
         steps, ks = _smile_arrays(smile, expiry_steps, strikes)
-        _check(self._L.mcamd_price_heston_smile_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(heston),
-                                                        smile.n_expiries, smile.n_strikes, steps, ks, _ptr(state),
-                                                        _ptr(stats)))
+        self._enqueue("mcamd_price_heston_smile_enqueue", opt, sim, heston, smile.n_expiries, smile.n_strikes, steps, ks,
+                      _ptr(state), _ptr(stats))
 
     def price_localvol_greeks(self, opt: Option, sim: Sim, job: LocalVolGreeksJob, surface: "LocalVolSurface",
                               samples=None) -> LocalVolGreeks:
@@ -1023,16 +927,12 @@ class Context:
         surface from one walk of the paths (mcamd_price_localvol_greeks); opt.v is ignored.  samples: optional device
         tensor of (6 + n_vega_buckets) x n_paths_local doubles, estimator-major, that receives every path's
         undiscounted samples."""
-        out = LocalVolGreeks()
-        _check(self._L.mcamd_price_localvol_greeks(self._h, C.byref(opt), C.byref(sim), C.byref(job), surface._h,
-                                                   _ptr(samples), C.byref(out)))
-        return out
+        return self._sync("mcamd_price_localvol_greeks", LocalVolGreeks, opt, sim, job, surface._h, _ptr(samples))
 
     def price_localvol_greeks_enqueue(self, opt: Option, sim: Sim, job: LocalVolGreeksJob, surface: "LocalVolSurface",
                                       stats, samples=None) -> None:
         """Asynchronous: leaves the 32-double record in the device tensor `stats` (finalize_localvol_greeks_stats)."""
-        _check(self._L.mcamd_price_localvol_greeks_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(job), surface._h,
-                                                           _ptr(samples), _ptr(stats)))
+        self._enqueue("mcamd_price_localvol_greeks_enqueue", opt, sim, job, surface._h, _ptr(samples), _ptr(stats))
 
     def price_localvol_smile(self, opt: Option, sim: Sim, smile: Smile, expiry_steps, strikes,
                              surface: "LocalVolSurface", spots=None):
@@ -1050,92 +950,72 @@ class Context:
         """Asynchronous: leaves the 2 n_e n_K sums and then n in the device tensor `stats` (>= 2 n_e n_K + 1 doubles;
         finalize_smile serves the sums)."""
         steps, ks = _smile_arrays(smile, expiry_steps, strikes)
-        _check(self._L.mcamd_price_localvol_smile_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(smile), steps, ks,
-                                                          surface._h, _ptr(spots), _ptr(stats)))
+        self._enqueue("mcamd_price_localvol_smile_enqueue", opt, sim, smile, steps, ks, surface._h, _ptr(spots),
+                      _ptr(stats))
 
     def price_lookback(self, opt: Option, sim: Sim, lookback: Lookback, samples=None) -> Result:
         """Lookback option (mcamd_price_lookback).  samples: optional device tensor of n_paths_local values of the path
         precision that receives each path's undiscounted sample."""
-        res = Result()
-        _check(self._L.mcamd_price_lookback(self._h, C.byref(opt), C.byref(sim), C.byref(lookback), _ptr(samples),
-                                            C.byref(res)))
-        return res
+        return self._sync("mcamd_price_lookback", Result, opt, sim, lookback, _ptr(samples))
 
     def price_lookback_enqueue(self, opt: Option, sim: Sim, lookback: Lookback, stats, samples=None) -> None:
         """Asynchronous: leaves {sum, sumsq, 0, 0, 0, n} in the device tensor `stats` (>= 6 doubles; finalize_stats)."""
-        _check(self._L.mcamd_price_lookback_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(lookback),
-                                                    _ptr(samples), _ptr(stats)))
+        self._enqueue("mcamd_price_lookback_enqueue", opt, sim, lookback, _ptr(samples), _ptr(stats))
 
     def price_asian(self, opt: Option, sim: Sim, asian: Asian, samples=None) -> Result:
         """Asian option (mcamd_price_asian).  samples: optional device tensor of n_paths_local values of the path
         precision; receives the undiscounted sample of every path (never the control-adjusted value)."""
-        res = Result()
-        _check(self._L.mcamd_price_asian(self._h, C.byref(opt), C.byref(sim), C.byref(asian), _ptr(samples),
-                                         C.byref(res)))
-        return res
+        return self._sync("mcamd_price_asian", Result, opt, sim, asian, _ptr(samples))
 
     def price_asian_enqueue(self, opt: Option, sim: Sim, asian: Asian, stats, samples=None) -> None:
         """Asynchronous: leaves {sum y, sum y^2, sum c, sum c^2, sum y c, n} in the device tensor `stats` (>= 6 doubles;
         finalize_stats, with control_variate=True for a controlled job)."""
-        _check(self._L.mcamd_price_asian_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(asian), _ptr(samples),
-                                                 _ptr(stats)))
+        self._enqueue("mcamd_price_asian_enqueue", opt, sim, asian, _ptr(samples), _ptr(stats))
 
     def price_autocall(self, opt: Option, sim: Sim, autocall: Autocall, samples=None) -> AutocallResult:
         """Worst-of autocallable note (mcamd_price_autocall): r and T come from opt.  samples: optional device tensor of
         n_paths_local values of the path precision that receives every path's sample, in maturity money."""
-        res = AutocallResult()
-        _check(self._L.mcamd_price_autocall(self._h, C.byref(opt), C.byref(sim), C.byref(autocall), _ptr(samples),
-                                            C.byref(res)))
-        return res
+        return self._sync("mcamd_price_autocall", AutocallResult, opt, sim, autocall, _ptr(samples))
 
     def price_autocall_enqueue(self, opt: Option, sim: Sim, autocall: Autocall, stats, samples=None) -> None:
         """Asynchronous: leaves {sum, sumsq, n_called, sum_t_call, n_knocked_in, n} in the device tensor `stats`
         (>= 6 doubles; finalize_stats without the control variate)."""
-        _check(self._L.mcamd_price_autocall_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(autocall),
-                                                    _ptr(samples), _ptr(stats)))
+        self._enqueue("mcamd_price_autocall_enqueue", opt, sim, autocall, _ptr(samples), _ptr(stats))
 
     def price_autocall_localvol(self, opt: Option, sim: Sim, autocall: AutocallLocalVol, surfaces,
                                 samples=None) -> AutocallResult:
         """Worst-of autocallable note under per-asset local-volatility surfaces (mcamd_price_autocall_localvol): r and T
         come from opt; surfaces: one LocalVolSurface per asset (the same one may appear several times).  samples:
         optional device tensor of n_paths_local values of the path precision that receives every path's sample."""
-        res = AutocallResult()
-        _check(self._L.mcamd_price_autocall_localvol(self._h, C.byref(opt), C.byref(sim), C.byref(autocall),
-                                                     surface_array(surfaces), _ptr(samples), C.byref(res)))
-        return res
+        return self._sync("mcamd_price_autocall_localvol", AutocallResult, opt, sim, autocall, surface_array(surfaces),
+                          _ptr(samples))
 
     def price_autocall_localvol_enqueue(self, opt: Option, sim: Sim, autocall: AutocallLocalVol, surfaces, stats,
                                         samples=None) -> None:
         """Asynchronous: leaves {sum, sumsq, n_called, sum_t_call, n_knocked_in, n} in the device tensor `stats`
         (>= 6 doubles; finalize_stats without the control variate).  The surfaces must outlive the enqueued work."""
-        _check(self._L.mcamd_price_autocall_localvol_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(autocall),
-                                                             surface_array(surfaces), _ptr(samples), _ptr(stats)))
+        self._enqueue("mcamd_price_autocall_localvol_enqueue", opt, sim, autocall, surface_array(surfaces),
+                      _ptr(samples), _ptr(stats))
 
     def price_basket(self, opt: Option, sim: Sim, basket: Basket, samples=None) -> Result:
         """Basket, spread or rainbow option on correlated assets (mcamd_price_basket): r, T, K and the barrier level B
         come from opt.  samples: optional device tensor of n_paths_local values of the path precision that receives
         each path's undiscounted sample."""
-        res = Result()
-        _check(self._L.mcamd_price_basket(self._h, C.byref(opt), C.byref(sim), C.byref(basket), _ptr(samples),
-                                          C.byref(res)))
-        return res
+        return self._sync("mcamd_price_basket", Result, opt, sim, basket, _ptr(samples))
 
     def price_basket_enqueue(self, opt: Option, sim: Sim, basket: Basket, stats, samples=None) -> None:
         """Asynchronous: leaves {sum, sumsq, 0, 0, 0, n} in the device tensor `stats` (>= 6 doubles; finalize_stats)."""
-        _check(self._L.mcamd_price_basket_enqueue(self._h, C.byref(opt), C.byref(sim), C.byref(basket),
-                                                  _ptr(samples), _ptr(stats)))
+        self._enqueue("mcamd_price_basket_enqueue", opt, sim, basket, _ptr(samples), _ptr(stats))
 
     def price_american(self, opt: Option, sim: Sim, am: American, work, coeffs: bool = False):
         """Least-squares Monte Carlo price of an American / Bermudan put or call (mcamd_price_american).  work: a device
         tensor of at least american_workspace_bytes(am, sim) bytes.  Returns the AmericanResult, and with coeffs=True
         also the (M, n_basis + 1) array of per-date coefficients and regressed flags."""
-        res = AmericanResult()
         nb = am.n_basis or 3
         M = sim.n_steps // am.exercise_every if am.exercise_every else 0
         arr = (C.c_double * (M * (nb + 1)))() if coeffs and M > 0 else None
         nbytes = work.numel() * work.element_size() if work is not None else 0
-        _check(self._L.mcamd_price_american(self._h, C.byref(opt), C.byref(sim), C.byref(am), _ptr(work), nbytes, arr,
-                                            C.byref(res)))
+        res = self._sync("mcamd_price_american", AmericanResult, opt, sim, am, _ptr(work), nbytes, arr)
         if not coeffs:
             return res
         import numpy as np
@@ -1148,7 +1028,6 @@ class Context:
         american_dual_workspace_bytes(am, sim, dual) bytes; cont: optional device tensor of M * n_paths_local doubles
         that receives the continuation values Q[j, p]."""
         import numpy as np
-        res = AmericanDualResult()
         table = None
         if coeffs is not None:
             table = np.ascontiguousarray(coeffs, dtype=np.float64)
@@ -1157,11 +1036,9 @@ class Context:
             if table.size != M * (nb + 1):
                 raise ValueError(f"coeffs holds {table.size} doubles; {M} dates x ({nb} + 1) expected")
         nbytes = work.numel() * work.element_size() if work is not None else 0
-        _check(self._L.mcamd_american_upper_bound(
-            self._h, C.byref(opt), C.byref(sim), C.byref(am), C.byref(dual),
-            None if table is None else table.ctypes.data_as(C.POINTER(C.c_double)), _ptr(work), nbytes, _ptr(cont),
-            C.byref(res)))
-        return res
+        return self._sync("mcamd_american_upper_bound", AmericanDualResult, opt, sim, am, dual,
+                          None if table is None else table.ctypes.data_as(C.POINTER(C.c_double)), _ptr(work), nbytes,
+                          _ptr(cont))
 
     def enqueued_kernel_ms(self, n_last: int):
         arr = (C.c_float * n_last)()
@@ -1170,132 +1047,88 @@ class Context:
 
     def simulate_trajectories(self, opt: Option, sim: Sim, traj, counts=None, payoffs=None,
                               layout=STEP_MAJOR) -> Result:
-        res = Result()
-        _check(self._L.mcamd_simulate_trajectories(self._h, C.byref(opt), C.byref(sim), layout, _ptr(traj),
-                                                   _ptr(counts), _ptr(payoffs), C.byref(res)))
-        return res
+        return self._sync("mcamd_simulate_trajectories", Result, opt, sim, layout, _ptr(traj), _ptr(counts),
+                          _ptr(payoffs))
 
     def simulate_trajectories_enqueue(self, opt: Option, sim: Sim, traj, counts, payoffs, stats, layout=STEP_MAJOR) -> None:
-        _check(self._L.mcamd_simulate_trajectories_enqueue(self._h, C.byref(opt), C.byref(sim), layout, _ptr(traj),
-                                                           _ptr(counts), _ptr(payoffs), _ptr(stats)))
+        self._enqueue("mcamd_simulate_trajectories_enqueue", opt, sim, layout, _ptr(traj), _ptr(counts), _ptr(payoffs),
+                      _ptr(stats))
 
     def nmc_inner_enqueue(self, opt: Option, sim: Sim, prices, counts, point_prices, stats, layout=STEP_MAJOR,
                           variant=NMC_WAVE_PER_POINT) -> None:
-        _check(self._L.mcamd_nmc_inner_enqueue(self._h, C.byref(opt), C.byref(sim), layout, variant, _ptr(prices),
-                                               _ptr(counts), _ptr(point_prices), _ptr(stats)))
+        self._enqueue("mcamd_nmc_inner_enqueue", opt, sim, layout, variant, _ptr(prices), _ptr(counts),
+                      _ptr(point_prices), _ptr(stats))
 
     def nmc_fused_enqueue(self, opt: Option, sim: Sim, outer_seed: int, prices, counts, point_prices, stats,
                           layout=STEP_MAJOR) -> None:
-        _check(self._L.mcamd_nmc_fused_enqueue(self._h, C.byref(opt), C.byref(sim), outer_seed, layout, _ptr(prices),
-                                               _ptr(counts), _ptr(point_prices), _ptr(stats)))
+        self._enqueue("mcamd_nmc_fused_enqueue", opt, sim, outer_seed, layout, _ptr(prices), _ptr(counts),
+                      _ptr(point_prices), _ptr(stats))
 
     def diag_store_pattern(self, n_paths_local: int, n_steps: int, precision: int, traj, payoffs=None) -> float:
         """kernel ms of the store kernel's pure store stream (diagnostic: the same-run HBM write ceiling)"""
-        ms = C.c_float(0)
-        _check(self._L.mcamd_diag_store_pattern(self._h, n_paths_local, n_steps, precision, _ptr(traj), _ptr(payoffs),
-                                                C.byref(ms)))
-        return ms.value
+        return self._sync("mcamd_diag_store_pattern", C.c_float, n_paths_local, n_steps, precision, _ptr(traj),
+                          _ptr(payoffs)).value
 
     def price_from_normals(self, opt: Option, sim: Sim, normals, payoffs=None) -> Result:
-        res = Result()
-        _check(self._L.mcamd_price_from_normals(self._h, C.byref(opt), C.byref(sim), _ptr(normals), _ptr(payoffs),
-                                                C.byref(res)))
-        return res
+        return self._sync("mcamd_price_from_normals", Result, opt, sim, _ptr(normals), _ptr(payoffs))
 
     def generate_normals(self, seed: int, n: int, precision: int, out) -> float:
-        ms = C.c_float(0)
-        _check(self._L.mcamd_generate_normals(self._h, seed, n, precision, _ptr(out), C.byref(ms)))
-        return ms.value
+        return self._sync("mcamd_generate_normals", C.c_float, seed, n, precision, _ptr(out)).value
 
     def reduce_sum(self, x, n: int, precision: int, variant: int = REDUCE_GRID_STRIDE):
-        s, ms = C.c_double(0), C.c_float(0)
-        _check(self._L.mcamd_reduce_sum(self._h, _ptr(x), n, precision, variant, C.byref(s), C.byref(ms)))
+        s = C.c_double(0)
+        ms = self._sync("mcamd_reduce_sum", C.c_float, _ptr(x), n, precision, variant, s)
         return s.value, ms.value
 
     def reduce_partials(self, x, n: int, precision: int, variant: int, n_blocks: int):
         """one partial sum per workgroup (they add up to the complete sum) and the kernel's ms"""
-        arr, ms = (C.c_double * n_blocks)(), C.c_float(0)
-        _check(self._L.mcamd_reduce_partials(self._h, _ptr(x), n, precision, variant, n_blocks, arr, C.byref(ms)))
+        arr = (C.c_double * n_blocks)()
+        ms = self._sync("mcamd_reduce_partials", C.c_float, _ptr(x), n, precision, variant, n_blocks, arr)
         return list(arr), ms.value
 
     def nmc_inner(self, opt: Option, sim: Sim, prices, counts, point_prices, layout=STEP_MAJOR,
                   variant=NMC_WAVE_PER_POINT) -> Result:
-        res = Result()
-        _check(self._L.mcamd_nmc_inner(self._h, C.byref(opt), C.byref(sim), layout, variant, _ptr(prices),
-                                       _ptr(counts), _ptr(point_prices), C.byref(res)))
-        return res
+        return self._sync("mcamd_nmc_inner", Result, opt, sim, layout, variant, _ptr(prices), _ptr(counts),
+                          _ptr(point_prices))
 
     def nmc_fused(self, opt: Option, sim: Sim, outer_seed: int, prices, counts, point_prices,
                   layout=STEP_MAJOR) -> Result:
-        res = Result()
-        _check(self._L.mcamd_nmc_fused(self._h, C.byref(opt), C.byref(sim), outer_seed, layout, _ptr(prices),
-                                       _ptr(counts), _ptr(point_prices), C.byref(res)))
-        return res
+        return self._sync("mcamd_nmc_fused", Result, opt, sim, outer_seed, layout, _ptr(prices), _ptr(counts),
+                          _ptr(point_prices))
 
 
-class LocalVolSurface:
+class LocalVolSurface(_Handle):
     """Owns one mcamd_localvol_surface: the pair tables of a local-volatility surface in the memory of one context's
     device.  Immutable; several may be alive in one context."""
+    _destroy = "mcamd_localvol_surface_destroy"
+    __del__ = _Handle._close_quietly
 
     def __init__(self, ctx: Context, grid_args, sigma):
-        self._L = load()
-        self._h = C.c_void_p()
+        super().__init__()
         self.grid = grid_args if isinstance(grid_args, LocalVolGrid) else make_localvol_grid(*grid_args)
         _check(self._L.mcamd_localvol_surface_create(ctx._h, C.byref(self.grid), _sigma_array(self.grid, sigma),
                                                      C.byref(self._h)))
 
-    def close(self):
-        if self._h:
-            self._L.mcamd_localvol_surface_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-
-class Group:
+class Group(_Handle):
     """Single-process multi-GPU group: one context per device + an RCCL communicator clique (mcamd_group_*)."""
+    # no __del__, unlike Context and LocalVolSurface: the garbage collector must not tear RCCL down at interpreter
+    # exit; a group ends with close() or its with block
+    _destroy = "mcamd_group_destroy"
 
     def __init__(self, n_devices: int = 0, devices=None):
-        self._L = load()
-        self._h = C.c_void_p()
+        super().__init__()
         arr = (C.c_int * len(devices))(*devices) if devices else None
         _check(self._L.mcamd_group_create(len(devices) if devices else n_devices, arr, C.byref(self._h)))
 
-    def close(self):
-        if self._h:
-            self._L.mcamd_group_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
     def size(self) -> int:
-        n = C.c_int(0)
-        _check(self._L.mcamd_group_size(self._h, C.byref(n)))
-        return n.value
+        return self._sync("mcamd_group_size", C.c_int).value
 
     def price_paths(self, opt: Option, sim: Sim) -> Result:
-        res = Result()
-        _check(self._L.mcamd_group_price_paths(self._h, C.byref(opt), C.byref(sim), C.byref(res)))
-        return res
+        return self._sync("mcamd_group_price_paths", Result, opt, sim)
 
     def price_greeks(self, opt: Option, sim: Sim, method: int = GREEKS_AUTO) -> Greeks:
-        out = Greeks()
-        _check(self._L.mcamd_group_price_greeks(self._h, C.byref(opt), C.byref(sim), method, C.byref(out)))
-        return out
+        return self._sync("mcamd_group_price_greeks", Greeks, opt, sim, method)
 
     def shard(self, sim: Sim, i: int):
         """(first global path id, number of paths) device i of the group works on for this job."""
@@ -1311,20 +1144,14 @@ class Group:
         return (C.c_void_p * len(per_device))(*[None if t is None else t.data_ptr() for t in per_device])
 
     def simulate_trajectories(self, opt: Option, sim: Sim, traj, counts=None, payoffs=None, layout=STEP_MAJOR) -> Result:
-        res = Result()
-        _check(self._L.mcamd_group_simulate_trajectories(self._h, C.byref(opt), C.byref(sim), layout, self._ptrs(traj),
-                                                         self._ptrs(counts), self._ptrs(payoffs), C.byref(res)))
-        return res
+        return self._sync("mcamd_group_simulate_trajectories", Result, opt, sim, layout, self._ptrs(traj),
+                          self._ptrs(counts), self._ptrs(payoffs))
 
     def nmc_inner(self, opt: Option, sim: Sim, prices, counts, point_prices, layout=STEP_MAJOR,
                   variant=NMC_WAVE_PER_POINT) -> Result:
-        res = Result()
-        _check(self._L.mcamd_group_nmc_inner(self._h, C.byref(opt), C.byref(sim), layout, variant, self._ptrs(prices),
-                                             self._ptrs(counts), self._ptrs(point_prices), C.byref(res)))
-        return res
+        return self._sync("mcamd_group_nmc_inner", Result, opt, sim, layout, variant, self._ptrs(prices),
+                          self._ptrs(counts), self._ptrs(point_prices))
 
     def nmc_fused(self, opt: Option, sim: Sim, outer_seed: int, prices, counts, point_prices, layout=STEP_MAJOR) -> Result:
-        res = Result()
-        _check(self._L.mcamd_group_nmc_fused(self._h, C.byref(opt), C.byref(sim), outer_seed, layout, self._ptrs(prices),
-                                             self._ptrs(counts), self._ptrs(point_prices), C.byref(res)))
-        return res
+        return self._sync("mcamd_group_nmc_fused", Result, opt, sim, outer_seed, layout, self._ptrs(prices),
+                          self._ptrs(counts), self._ptrs(point_prices))
