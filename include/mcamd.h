@@ -221,10 +221,25 @@ int mcamd_price_paths(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *
  * the context's stream and returns without waiting.  d_stats (device, >= 6 doubles) receives {sum, sumsq, sum_c, sum_cc, sum_yc, n}
  * (the cross sums are zero without MCAMD_FLAG_CONTROL_VARIATE).  The caller orders later work on the same stream —
  * typically ONE all-reduce of d_stats over the ranks — and finalizes after synchronising (mcamd_finalize_stats), so
- * a multi-step driver pays no host round trip per step.  New (the reference is fully synchronous). */
+ * a multi-step driver pays no host round trip per step.  New (the reference is fully synchronous).
+ *   Overlap: a job whose block records need the separate final reduction (more than 8192 workgroups; fp64 without a
+ * window: 4.2M paths and up) runs its simulation kernel on one of two non-blocking streams the context owns, into a
+ * scratch buffer of that stream, and only the reduction into d_stats on the context's stream, behind the kernel.
+ * Consecutive such jobs take the two streams in turn, so the next job's kernel fills the chip while this one's last
+ * workgroups drain.  What holds as before: d_stats is written on the context's stream, after everything enqueued there
+ * before the call and before everything enqueued after it, and any later call on the context starts after the
+ * simulation kernels of all earlier ones.  What is new: such a job's simulation kernel may START before earlier work
+ * on the context's stream has finished; it reads no memory of the caller's.  A stream that is being captured into a
+ * graph, a failure to create the internal streams, and MCAMD_ENQUEUE_OVERLAP=0 in the environment when the context
+ * is created keep every job in order on the context's stream. */
 int mcamd_price_paths_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, double *d_stats);
 /* HIP-event times (ms) of the simulation kernels of the last n_last (<= 64) enqueued calls, oldest first.
- * Synchronises the stream. */
+ * Synchronises the stream (and the context's internal streams).  An overlapped job (mcamd_price_paths_enqueue) that
+ * follows another is charged the part of its kernel's interval after the earlier job's kernel ended,
+ * end_N - max(start_N, end_{N-1}), never less than 0, where "earlier" is taken in the order in which the kernels of the
+ * run ended (two kernels that share the device may end in either order): the times of a run of overlapped jobs are
+ * disjoint parts of the time the device was busy with them.  Every other call's time is its kernel's own
+ * start-to-end interval. */
 int mcamd_enqueued_kernel_ms(mcamd_ctx *ctx, uint32_t n_last, float *ms);
 /* Host: finalize a (possibly all-reduced) 6-double stats record copied back from the device. */
 int mcamd_finalize_stats(const double stats[6], double r, double T, int control_variate, mcamd_result *res);

@@ -27,7 +27,8 @@ HEADERS = ["launch.hpp", "mc_device.hpp", "path_consts.hpp", "path_frame.hpp", "
            "localvol.hpp", "localvol_device.hpp", "localvol_smile.hpp", "autocall_localvol.hpp",
            "autocall_localvol_impl.hpp", "localvol_greeks.hpp", "cliquet.hpp", "cliquet_device.hpp", "heston.hpp",
            "heston_cliquet.hpp", "heston_barrier.hpp",
-           "heston_device.hpp", "heston_smile.hpp", "smile.hpp", "smile_device.hpp", "capi_internal.hpp"]
+           "heston_device.hpp", "heston_smile.hpp", "smile.hpp", "smile_device.hpp", "capi_internal.hpp",
+           "enqueue_intervals.hpp"]
 ARCH = "gfx950"
 
 

@@ -9,6 +9,7 @@
 #include <atomic>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <random>
 #include <string>
 
@@ -87,6 +88,79 @@ int ensure_partials_enqueued(mcamd_ctx *ctx, uint32_t records, int record_double
     // wait for work that may still read the old buffer
     if (static_cast<uint64_t>(records) * record_doubles > ctx->partial_capacity) HIP_TRY(hipStreamSynchronize(ctx->stream));
     return ensure_partials(ctx, records, record_doubles);
+}
+
+int overlap_failed(mcamd_ctx *ctx, int rc)
+{
+    ctx->overlap = false;
+    return rc;
+}
+
+int overlap_begin(mcamd_ctx *ctx, uint32_t records, int record_doubles, int *lane)
+{
+    *lane = -1;
+    // a capture records the caller's stream alone: the in-order path keeps the whole job inside it
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(ctx->stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) {
+        (void)hipGetLastError();
+        return MCAMD_OK;
+    }
+    if (!ctx->overlap_ready) {
+        hipError_t e = hipSuccess;
+        for (int l = 0; l < 2 && e == hipSuccess; ++l) {
+            e = hipStreamCreateWithFlags(&ctx->lane_stream[l], hipStreamNonBlocking);
+            if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->lane_reduced[l], hipEventDisableTiming);
+        }
+        if (e != hipSuccess) {   // mcamd_ctx_destroy frees what was created
+            (void)hipGetLastError();
+            return overlap_failed(ctx, MCAMD_OK);
+        }
+        ctx->overlap_ready = true;
+    }
+    const int l = static_cast<int>(ctx->n_overlapped % 2);
+    const uint64_t need = static_cast<uint64_t>(records) * record_doubles;
+    if (need > ctx->lane_capacity[l]) {
+        // the old buffer may still be written by the lane's last kernel and read by its reduction on the caller's stream
+        HIP_TRY(hipStreamSynchronize(ctx->lane_stream[0]));
+        HIP_TRY(hipStreamSynchronize(ctx->lane_stream[1]));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if (ctx->lane_partials[l]) HIP_TRY(hipFree(ctx->lane_partials[l]));
+        ctx->lane_partials[l] = nullptr;
+        ctx->lane_capacity[l] = 0;
+        HIP_TRY(hipMalloc(&ctx->lane_partials[l], need * sizeof(double)));
+        ctx->lane_capacity[l] = need;
+    }
+    const uint32_t slot = ring_slot(ctx->n_enqueued);
+    hipError_t e = ctx->lane_read[l] ? hipStreamWaitEvent(ctx->lane_stream[l], ctx->lane_reduced[l], 0) : hipSuccess;
+    if (e == hipSuccess) e = hipEventRecord(ctx->ring0[slot], ctx->lane_stream[l]);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return overlap_failed(ctx, fail(MCAMD_ERR_HIP, "internal stream %d: %s", l, hipGetErrorString(e)));
+    }
+    *lane = l;
+    return MCAMD_OK;
+}
+
+int overlap_finish(mcamd_ctx *ctx, int lane, uint32_t records, int record_doubles, double *d_stats, double n_value)
+{
+    const uint32_t slot = ring_slot(ctx->n_enqueued);
+    hipError_t e = hipEventRecord(ctx->ring1[slot], ctx->lane_stream[lane]);
+    // the reduction, and with it everything the caller enqueues later, waits for the kernel
+    if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ctx->ring1[slot], 0);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return overlap_failed(ctx, fail(MCAMD_ERR_HIP, "internal stream %d: %s", lane, hipGetErrorString(e)));
+    }
+    HIP_TRY(launch_final_reduce(ctx->lane_partials[lane], records, record_doubles, d_stats, ctx->stream, n_value));
+    HIP_TRY(hipEventRecord(ctx->lane_reduced[lane], ctx->stream));
+    ctx->lane_read[lane] = true;
+    OverlapSlot &s = ctx->ring_overlap[slot];
+    s.chained = ctx->n_enqueued > 0 && slot_overlapped(ctx->ring_overlap, ctx->n_enqueued - 1);
+    s.call = ctx->n_enqueued + 1;
+    s.lane = static_cast<uint8_t>(lane);
+    ctx->n_overlapped++;
+    ctx->n_enqueued++;
+    return MCAMD_OK;
 }
 
 int check_request(const mcamd_option *opt, const mcamd_sim *sim)
@@ -316,6 +390,21 @@ namespace {
 // synchronous and an enqueue form.  Once every check has passed they hand the DeviceCall to drive (the form's driver)
 // and return what it returns.
 
+// The pricing kernel's launch: on the context's stream into its scratch buffer, as every DeviceCall launches, or where
+// run_enqueue aims it (an overlapped job).  A job that run_enqueue aims elsewhere is a kReduce one, of more
+// than kFoldMaxRecords workgroups, and so not one of the lane-compacting kernel's (4 workgroups per CU), the only
+// pricing kernel that uses d_queue.
+struct PriceLaunch {
+    const mcamd::PathJob &job;
+    mcamd_ctx *ctx;
+    uint32_t grid;
+    hipError_t operator()(const mcamd::FinishSpec &fs) const { return (*this)(fs, ctx->d_partials, ctx->stream); }
+    hipError_t operator()(const mcamd::FinishSpec &fs, double *d_partials, hipStream_t stream) const
+    {
+        return mcamd::launch_price(job, ctx->compute_units, d_partials, ctx->d_queue, grid, fs, stream);
+    }
+};
+
 template <typename Drive>
 int prepare_paths(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, Drive drive)
 {
@@ -327,9 +416,7 @@ int prepare_paths(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
     // call (the reference's shape, inc/trajectories.cuh:77-111 + one cudaMemcpy)
     const Finish how = grid > mcamd::kFoldMaxRecords ? Finish::kReduce
                        : (sim->flags & MCAMD_FLAG_SEPARATE_REDUCE) ? Finish::kSmall : Finish::kFolded;
-    return drive(DeviceCall{job.n_local, grid, (job.vr & 2) ? 5 : 2, 6, how, [&](const mcamd::FinishSpec &fs) {
-        return mcamd::launch_price(job, ctx->compute_units, ctx->d_partials, ctx->d_queue, grid, fs, ctx->stream);
-    }});
+    return drive(DeviceCall{job.n_local, grid, (job.vr & 2) ? 5 : 2, 6, how, PriceLaunch{job, ctx, grid}});
 }
 
 template <typename Drive>
@@ -531,6 +618,10 @@ int mcamd_ctx_create(int device, void *hip_stream, mcamd_ctx **out)
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e == hipSuccess) ctx->d_ticket = reinterpret_cast<unsigned int *>(ctx->d_queue + 2);
     ctx->compute_units = static_cast<uint32_t>(prop.multiProcessorCount);
+    // read once, here: MCAMD_ENQUEUE_OVERLAP=0 keeps every enqueue of this context in order on its stream.  A device on
+    // which the lane-compacting kernel's grid (4 workgroups per CU) could need the separate reduction does the same.
+    const char *overlap_env = std::getenv("MCAMD_ENQUEUE_OVERLAP");
+    ctx->overlap = !(overlap_env && std::strcmp(overlap_env, "0") == 0) && ctx->compute_units * 4 <= mcamd::kFoldMaxRecords;
     if (e == hipSuccess) e = hipHostMalloc(&ctx->h_rec, mcamd_ctx::kRecord * sizeof(double), hipHostMallocDefault);
     if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void **>(&ctx->h_rec_dev), ctx->h_rec, 0);
     if (e != hipSuccess) {
@@ -545,7 +636,14 @@ int mcamd_ctx_destroy(mcamd_ctx *ctx)
 {
     if (!ctx) return MCAMD_OK;
     (void)hipSetDevice(ctx->device);
+    for (int l = 0; l < 2; ++l)
+        if (ctx->lane_stream[l]) (void)hipStreamSynchronize(ctx->lane_stream[l]);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+    for (int l = 0; l < 2; ++l) {
+        if (ctx->lane_partials[l]) (void)hipFree(ctx->lane_partials[l]);
+        if (ctx->lane_reduced[l]) (void)hipEventDestroy(ctx->lane_reduced[l]);
+        if (ctx->lane_stream[l]) (void)hipStreamDestroy(ctx->lane_stream[l]);
+    }
     if (ctx->d_partials) (void)hipFree(ctx->d_partials);
     if (ctx->d_out) (void)hipFree(ctx->d_out);
     if (ctx->d_queue) (void)hipFree(ctx->d_queue);
@@ -686,10 +784,36 @@ int mcamd_enqueued_kernel_ms(mcamd_ctx *ctx, uint32_t n_last, float *ms)
     if (n_last > mcamd_ctx::kRing || n_last > ctx->n_enqueued)
         return fail(MCAMD_ERR_INVALID, "only the last min(%u, enqueued) calls are kept", mcamd_ctx::kRing);
     HIP_TRY(hipSetDevice(ctx->device));
+    for (int l = 0; l < 2; ++l)
+        if (ctx->lane_stream[l]) HIP_TRY(hipStreamSynchronize(ctx->lane_stream[l]));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const uint64_t first = ctx->n_enqueued - n_last;
     for (uint32_t i = 0; i < n_last; ++i) {
-        const uint32_t slot = static_cast<uint32_t>((ctx->n_enqueued - n_last + i) % mcamd_ctx::kRing);
+        const uint32_t slot = ring_slot(first + i);
         HIP_TRY(hipEventElapsedTime(&ms[i], ctx->ring0[slot], ctx->ring1[slot]));
+    }
+    // Runs of overlapped jobs [b, e): each job is charged the part of its interval that enqueue_intervals.hpp gives it,
+    // on the clock that starts at the run's first start event.  A run may reach back past the calls asked for.
+    const OverlapSlot *ring = ctx->ring_overlap;
+    for (uint64_t call = first; call < ctx->n_enqueued;) {
+        uint64_t b = call, e = call + 1;
+        while (continues_run(ring, b, ctx->n_enqueued)) --b;
+        while (continues_run(ring, e, ctx->n_enqueued)) ++e;
+        call = e;
+        if (e - b < 2) continue;
+        double start[mcamd_ctx::kRing], end[mcamd_ctx::kRing], charged[mcamd_ctx::kRing];
+        const uint32_t n = static_cast<uint32_t>(e - b);
+        for (uint32_t k = 0; k < n; ++k) {
+            const uint32_t slot = ring_slot(b + k);
+            float since_base = 0.0f, own = 0.0f;
+            if (k) HIP_TRY(hipEventElapsedTime(&since_base, ctx->ring0[ring_slot(b)], ctx->ring0[slot]));
+            HIP_TRY(hipEventElapsedTime(&own, ctx->ring0[slot], ctx->ring1[slot]));
+            start[k] = since_base;
+            end[k] = static_cast<double>(since_base) + own;
+        }
+        exclusive_run_ms(start, end, n, charged);
+        for (uint32_t k = 0; k < n; ++k)
+            if (b + k >= first) ms[b + k - first] = static_cast<float>(charged[k]);
     }
     return MCAMD_OK;
 }

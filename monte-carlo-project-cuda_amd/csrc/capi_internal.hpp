@@ -10,8 +10,10 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <type_traits>
 
 #ifndef MCAMD_CAPI_HOST_ONLY
+#include "enqueue_intervals.hpp"
 #include "launch.hpp"
 #endif
 
@@ -152,6 +154,19 @@ struct mcamd_ctx {
     static constexpr uint32_t kRing = 64;
     hipEvent_t ring0[kRing] = {}, ring1[kRing] = {};
     uint64_t n_enqueued = 0;
+    // Overlapped enqueues: the simulation kernels of consecutive large mcamd_price_paths_enqueue jobs run
+    // on two internal non-blocking streams in turn, each into a scratch buffer of its own, and only the final
+    // reduction runs on `stream`.  The streams and events are created by the first such job.
+    static_assert(kRing == mcamd::capi::kEnqueueRing, "the interval arithmetic walks this ring");
+    bool overlap = false;         // MCAMD_ENQUEUE_OVERLAP as mcamd_ctx_create found it; cleared for good by a failure
+    bool overlap_ready = false;   // the two streams and events exist
+    hipStream_t lane_stream[2] = {};
+    hipEvent_t lane_reduced[2] = {};   // on `stream`, after the reduction that last read the lane's buffer
+    bool lane_read[2] = {};            // lane_reduced has been recorded
+    double *lane_partials[2] = {};
+    uint64_t lane_capacity[2] = {};    // in doubles
+    uint64_t n_overlapped = 0;         // the next overlapped job takes lane n_overlapped % 2
+    mcamd::capi::OverlapSlot ring_overlap[kRing];
     uint64_t id = 0;   // unique per context of the process: what a local-volatility surface remembers of its owner
     // pinned: the node sums of a synchronous smile call (allocated by the first one, at the largest smile's size)
     static constexpr uint32_t kSmileStats = 2 * MCAMD_SMILE_MAX_EXPIRIES * MCAMD_SMILE_MAX_STRIKES;
@@ -350,6 +365,17 @@ int ensure_partials_enqueued(mcamd_ctx *ctx, uint32_t records, int record_double
 // Asynchronous driver: the kernel runs between a pair of ring events, and its record reaches d_stats in the statistics
 // layout with n_value = n, from the kernel itself (kFolded) or from the separate sum.  Nothing waits on the host but the
 // growth of the scratch buffer.  An empty shard leaves all-zero statistics, still ordered on the stream.
+//
+// A kReduce call whose launch can also be aimed at another buffer and stream, launch(fs, d_partials, stream), and whose
+// kernel touches neither the ticket nor the queue (mcamd_price_paths_enqueue's large jobs) is overlapped where the
+// context allows it: overlap_begin picks the lane, or none for the in-order path below, and readies it up
+// to the start event; the kernel runs on the lane's stream into the lane's buffer; overlap_finish records the end
+// event there and enqueues the reduction into d_stats on ctx->stream behind it.
+int overlap_begin(mcamd_ctx *ctx, uint32_t records, int record_doubles, int *lane);
+int overlap_finish(mcamd_ctx *ctx, int lane, uint32_t records, int record_doubles, double *d_stats, double n_value);
+// a failure on an internal stream: the context takes the in-order path from now on; returns rc
+int overlap_failed(mcamd_ctx *ctx, int rc);
+
 template <typename Launch>
 int run_enqueue(mcamd_ctx *ctx, const DeviceCall<Launch> &call, double *d_stats)
 {
@@ -358,6 +384,21 @@ int run_enqueue(mcamd_ctx *ctx, const DeviceCall<Launch> &call, double *d_stats)
     if (call.n == 0) return enqueue_empty_shard(ctx, d_stats, static_cast<uint32_t>(call.stats));
     const uint32_t slot = static_cast<uint32_t>(ctx->n_enqueued % mcamd_ctx::kRing);
     const double n_value = static_cast<double>(call.n);
+    if constexpr (std::is_invocable_v<const Launch &, const FinishSpec &, double *, hipStream_t>) {
+        if (call.how == Finish::kReduce && ctx->overlap) {
+            int lane = -1;
+            if (int rc = overlap_begin(ctx, call.grid, call.rec, &lane)) return rc;
+            if (lane >= 0) {
+                const hipError_t e = call.launch(FinishSpec{}, ctx->lane_partials[lane], ctx->lane_stream[lane]);
+                if (e != hipSuccess) {
+                    (void)hipGetLastError();
+                    return overlap_failed(ctx, fail(MCAMD_ERR_HIP, "simulation kernel on an internal stream: %s",
+                                                    hipGetErrorString(e)));
+                }
+                return overlap_finish(ctx, lane, call.grid, call.rec, d_stats, n_value);
+            }
+        }
+    }
     if (int rc = ensure_partials_enqueued(ctx, call.grid, call.rec)) return rc;
     FinishSpec fs;
     if (call.how == Finish::kFolded) {
