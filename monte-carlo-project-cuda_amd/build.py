@@ -18,7 +18,7 @@ LIB = os.path.join(PKG, "libmcamd.so")
 SOURCES = ["price_f64.hip", "price_f32.hip", "store.hip", "aux.hip", "nmc.hip", "greeks.hip", "american.hip",
            "american_dual.hip", "barrier.hip", "lookback.hip", "basket.hip", "asian.hip", "autocall.hip", "localvol.hip",
            "localvol_smile.hip", "autocall_localvol.hip", "autocall_localvol_f32.hip", "localvol_greeks.hip", "cliquet.hip",
-           "heston.hip", "heston_smile.hip", "heston_cliquet.hip", "heston_barrier.hip", "smile.hip", "capi_heston.cpp", "capi_smile.cpp",
+           "heston.hip", "heston_smile.hip", "heston_cliquet.hip", "heston_barrier.hip", "heston_greeks.hip", "smile.hip", "capi_heston.cpp", "capi_smile.cpp",
            "capi.cpp", "capi_american.cpp", "capi_pathdep.cpp", "capi_multi.cpp", "capi_localvol.cpp", "closed_forms.cpp",
            "group.cpp"]
 HEADERS = ["launch.hpp", "mc_device.hpp", "path_consts.hpp", "path_frame.hpp", "fast64.hpp", "tables64.inc", "tables64_consts.inc",
@@ -26,9 +26,10 @@ HEADERS = ["launch.hpp", "mc_device.hpp", "path_consts.hpp", "path_frame.hpp", "
            "american_dual.hpp", "barrier.hpp", "barrier_device.hpp", "lookback.hpp", "basket.hpp", "basket_device.hpp", "asian.hpp", "autocall.hpp",
            "localvol.hpp", "localvol_device.hpp", "localvol_smile.hpp", "autocall_localvol.hpp",
            "autocall_localvol_impl.hpp", "localvol_greeks.hpp", "cliquet.hpp", "cliquet_device.hpp", "heston.hpp",
-           "heston_cliquet.hpp", "heston_barrier.hpp",
+           "heston_cliquet.hpp", "heston_barrier.hpp", "heston_greeks.hpp",
            "heston_device.hpp", "heston_smile.hpp", "smile.hpp", "smile_device.hpp", "capi_internal.hpp",
            "enqueue_intervals.hpp"]
+PUBLIC_HEADERS = ["mcamd.h", "mcamd_heston_greeks.h"]   # include/: what a caller compiles against
 ARCH = "gfx950"
 
 
@@ -45,7 +46,7 @@ def _flags(extra=()):
 
 
 def build_id(extra=()) -> str:
-    """Hash of everything the device code is made from (kernel sources, headers, the public header, the compile
+    """Hash of everything the device code is made from (kernel sources, headers, the public headers, the compile
     flags).  Compiled into the library (mcamd_build_id) and written beside the ISA slot counts
     (profiles/valu_slots.json), so bench.py can tell whether the counts describe the kernels it is running."""
     import hashlib
@@ -53,8 +54,9 @@ def build_id(extra=()) -> str:
     for name in sorted(SOURCES + HEADERS):
         with open(os.path.join(CSRC, name), "rb") as f:
             h.update(name.encode() + b"\0" + f.read())
-    with open(os.path.join(ROOT, "include", "mcamd.h"), "rb") as f:
-        h.update(f.read())
+    for name in PUBLIC_HEADERS:
+        with open(os.path.join(ROOT, "include", name), "rb") as f:
+            h.update(f.read())
     # every flag that can change the device code (include paths are machine-dependent and carry no code)
     h.update(" ".join(f for f in _flags(extra) if not f.startswith("-I")).encode())
     return h.hexdigest()[:16]
@@ -70,7 +72,7 @@ def _stale(target: str, deps) -> bool:
 def _compile(src: str, force: bool, extra, obj_dir: str = OBJ) -> str:
     obj = os.path.join(obj_dir, os.path.splitext(src)[0] + ".o")
     deps = [os.path.join(CSRC, src)] + [os.path.join(CSRC, h) for h in HEADERS] + [
-        os.path.join(ROOT, "include", "mcamd.h"), os.path.abspath(__file__)]
+        os.path.join(ROOT, "include", h) for h in PUBLIC_HEADERS] + [os.path.abspath(__file__)]
     if src == "capi.cpp":   # carries the build id, a hash over EVERY source
         deps += [os.path.join(CSRC, s_) for s_ in SOURCES]
     if force or _stale(obj, deps):

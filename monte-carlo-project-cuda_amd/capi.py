@@ -921,6 +921,19 @@ class Context(_Handle):
         self._enqueue("mcamd_price_heston_smile_enqueue", opt, sim, heston, smile.n_expiries, smile.n_strikes, steps, ks,
                       _ptr(state), _ptr(stats))
 
+    def price_heston_greeks(self, opt: Option, sim: Sim, heston: Heston, job, samples=None):
+        """Price, delta, gamma, rho, rho_q and the sensitivities to v0, kappa, theta, xi and rho of price_heston's option
+        from one simulation on shared draws (mcamd_price_heston_greeks of include/mcamd_heston_greeks.h).  job:
+        heston_greeks.make_job(...); returns a heston_greeks.HestonGreeks.  The binding lives in the module
+        heston_greeks, imported here and not at the top: the structs of this module are those of mcamd.h."""
+        from . import heston_greeks
+        return heston_greeks.price(self, opt, sim, heston, job, samples)
+
+    def price_heston_greeks_enqueue(self, opt: Option, sim: Sim, heston: Heston, job, stats, samples=None) -> None:
+        """Asynchronous: leaves the 32-double record in the device tensor `stats` (heston_greeks.finalize_stats)."""
+        from . import heston_greeks
+        heston_greeks.enqueue(self, opt, sim, heston, job, stats, samples)
+
     def price_localvol_greeks(self, opt: Option, sim: Sim, job: LocalVolGreeksJob, surface: "LocalVolSurface",
                               samples=None) -> LocalVolGreeks:
         """Price, delta, gamma, vega, bucketed vega, rho and dividend rho of a European option under a local-volatility

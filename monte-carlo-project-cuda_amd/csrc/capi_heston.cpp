@@ -1,18 +1,28 @@
 // capi_heston.cpp — the calls of the C ABI that walk Heston stochastic-volatility paths under the full-truncation Euler
-// scheme: European options, the strike-by-expiry smile, cliquets and single barriers.  Each call is a prepare step (the
-// refusals and the job) and its synchronous and enqueue forms; the refusals keep the order of the other families: the
-// request alone, then the context.  The stages the prepare steps share are check_heston_job and check_heston_walk
+// scheme: European options and their Greeks (include/mcamd_heston_greeks.h), the strike-by-expiry smile, cliquets and
+// single barriers.  Each call is a prepare step (the refusals and the job) and its synchronous and enqueue forms; the
+// refusals keep the order of the other families: the request alone, then the context.  The stages the prepare steps share are check_heston_job and check_heston_walk
 // here, check_barrier_terms and barrier_form in capi_pathdep.cpp and check_smile_nodes in capi_smile.cpp.
 #include "capi_internal.hpp"
 #include "heston.hpp"
 #include "heston_barrier.hpp"
 #include "heston_cliquet.hpp"
+#include "heston_greeks.hpp"
 #include "heston_smile.hpp"
+#include "mcamd_heston_greeks.h"
+
+#include <cstdio>
 
 static_assert(sizeof(mcamd_heston) == 64 && sizeof(mcamd_heston_result) == 96,
               "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
 static_assert(sizeof(mcamd_heston_cliquet_result) == 112, "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
 static_assert(sizeof(mcamd_heston_barrier_result) == 104, "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
+static_assert(sizeof(mcamd_heston_greeks_job) == 56 && sizeof(mcamd_heston_greeks) == 208,
+              "C ABI struct layout changed: bump MCAMD_ABI_VERSION");
+static_assert(MCAMD_HESTON_GREEKS_STATS == mcamd::kHestonGreeksStats && MCAMD_HESTON_GREEKS_STATS <= mcamd_ctx::kRecord &&
+                  MCAMD_HESTON_GREEKS == 5 + mcamd::kHestonGreeksMaxParams &&
+                  mcamd::heston_greeks_record(mcamd::kHestonGreeksMaxParams) < MCAMD_HESTON_GREEKS_STATS,
+              "the Greeks record is the header's");
 static_assert(MCAMD_HESTON_FULL_TRUNCATION == mcamd::kHestonFullTruncation, "the kernels' scheme is MCAMD_HESTON_*");
 
 using namespace mcamd::capi;
@@ -202,9 +212,142 @@ int prepare_heston_barrier(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_
                             }});
 }
 
+// ---- the Heston Greeks (include/mcamd_heston_greeks.h) ---------------------------------------------------------------
+
+const char *const kGreekParam[mcamd::kHestonGreeksMaxParams] = {"v0", "kappa", "theta", "xi", "rho"};
+
+// What the Greeks calls and their finalize refuse of the job alone: reserved, gamma_eta, the bumps.
+int check_heston_greeks_job(const mcamd_heston_greeks_job *gj)
+{
+    if (gj->reserved != 0.0) return fail(MCAMD_ERR_INVALID, "job->reserved must be 0, got %g", gj->reserved);
+    if (!std::isfinite(gj->gamma_eta) || gj->gamma_eta < 0.0)
+        return fail(MCAMD_ERR_INVALID, "gamma_eta must be finite and >= 0 (0: no gamma), got %g", gj->gamma_eta);
+    for (int k = 0; k < mcamd::kHestonGreeksMaxParams; ++k)
+        if (!std::isfinite(gj->bump[k]) || gj->bump[k] < 0.0)
+            return fail(MCAMD_ERR_INVALID, "bump[%d] (of %s) must be finite and >= 0 (0: not requested), got %g", k,
+                        kGreekParam[k], gj->bump[k]);
+    return MCAMD_OK;
+}
+
+// the model with parameter k (0 .. 4: v0, kappa, theta, xi, rho) moved by delta, formed in double
+mcamd_heston bumped_heston(const mcamd_heston &hs, int k, double delta)
+{
+    mcamd_heston b = hs;
+    double *const field[mcamd::kHestonGreeksMaxParams] = {&b.v0, &b.kappa, &b.theta, &b.xi, &b.rho};
+    *field[k] = *field[k] + delta;
+    return b;
+}
+
+// The Greeks calls: prepare_heston's refusals, then the job's own, then every bumped model, then the context.  The
+// kernel finishes its own sum into the 32-double statistics record.  opt->v and opt->B are ignored.
+template <typename Drive>
+int prepare_heston_greeks(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_heston *hs,
+                          const mcamd_heston_greeks_job *gj, void *d_samples, Drive drive)
+{
+    if (!opt || !sim || !hs) return fail(MCAMD_ERR_INVALID, "opt, sim and heston must be non-NULL");
+    if (int rc = check_heston_job(opt, hs)) return rc;
+    mcamd::HestonGreeksJob job;
+    if (int rc = check_heston_walk("Heston Greeks", opt, sim, hs, true, &job.walk[0])) return rc;
+    if (!gj) return fail(MCAMD_ERR_INVALID, "job is NULL");
+    if (int rc = check_heston_greeks_job(gj)) return rc;
+    job.n_params = 0;
+    for (int k = 0; k < mcamd::kHestonGreeksMaxParams; ++k) {
+        if (!(gj->bump[k] > 0.0)) continue;
+        for (int side = 0; side < 2; ++side) {
+            const mcamd_heston b = bumped_heston(*hs, k, side == 0 ? gj->bump[k] : -gj->bump[k]);
+            if (check_heston_model(b.q, b.v0, b.kappa, b.theta, b.xi, b.rho)) {
+                char why[256];
+                std::snprintf(why, sizeof why, "%s", mcamd_last_error());
+                const double base[mcamd::kHestonGreeksMaxParams] = {hs->v0, hs->kappa, hs->theta, hs->xi, hs->rho};
+                return fail(MCAMD_ERR_INVALID, "%s %c bump[%d] = %g %c %g leaves the model: %s", kGreekParam[k],
+                            side == 0 ? '+' : '-', k, base[k], side == 0 ? '+' : '-', gj->bump[k], why);
+            }
+            job.walk[1 + 2 * job.n_params + side] = heston_walk(opt, sim, &b);
+        }
+        job.n_params++;
+    }
+    if (!ctx) return fail(MCAMD_ERR_INVALID, "ctx is NULL");
+    if (sim->n_paths_local == 0) return drive(empty_call(mcamd::kHestonGreeksStats));
+    job.S0 = opt->S0;
+    job.K = opt->K;
+    job.put = hs->payoff == MCAMD_PAYOFF_PUT;
+    job.gamma_eta = gj->gamma_eta;
+    job.d_samples = d_samples;
+    const uint32_t grid = mcamd::one_path_per_thread_grid(sim->n_paths_local);
+    return drive(DeviceCall{sim->n_paths_local, grid, mcamd::heston_greeks_record(job.n_params), mcamd::kHestonGreeksStats,
+                            Finish::kFolded, [&](const mcamd::FinishSpec &fs) {
+                                return mcamd::launch_heston_greeks(job, ctx->d_partials, grid, fs, ctx->stream);
+                            }});
+}
+
+// value / std_err of a (possibly all-reduced) 32-double Greeks record; S0, r and T of the option, eta and the bumps of
+// the job (checked by the caller).  Fills value, std_err, n, truncated_steps and mean_variance.
+void finalize_heston_greeks_into(const double stats[MCAMD_HESTON_GREEKS_STATS], double S0, double r, double T,
+                                 const mcamd_heston_greeks_job *gj, mcamd_heston_greeks *out)
+{
+    int P = 0;
+    for (int k = 0; k < mcamd::kHestonGreeksMaxParams; ++k) P += gj->bump[k] > 0.0 ? 1 : 0;
+    const double disc = std::exp(-r * T);
+    const uint64_t n = static_cast<uint64_t>(std::llround(stats[9 + 2 * P]));
+    const auto set = [&](int which, double sum, double sumsq, double factor) {
+        const Estimate e = estimate(sum, sumsq, n, disc);
+        out->value[which] = factor * e.value;
+        out->std_err[which] = std::fabs(factor) * e.std_err;
+    };
+    out->n = n;
+    set(MCAMD_HESTON_GREEK_PRICE, stats[0], stats[1], 1.0);
+    set(MCAMD_HESTON_GREEK_DELTA, stats[2], stats[3], 1.0 / S0);
+    if (gj->gamma_eta > 0.0)
+        set(MCAMD_HESTON_GREEK_GAMMA, stats[5], stats[6],
+            1.0 / (S0 * S0 * (std::exp(gj->gamma_eta) - std::exp(-gj->gamma_eta))));
+    set(MCAMD_HESTON_GREEK_RHO, stats[2] - stats[0], stats[4], T);
+    set(MCAMD_HESTON_GREEK_RHO_Q, stats[2], stats[3], -T);
+    for (int k = 0, j = 0; k < mcamd::kHestonGreeksMaxParams; ++k) {
+        if (!(gj->bump[k] > 0.0)) continue;
+        set(MCAMD_HESTON_GREEK_V0 + k, stats[7 + 2 * j], stats[8 + 2 * j], 1.0 / (2.0 * gj->bump[k]));
+        ++j;
+    }
+    out->truncated_steps = stats[7 + 2 * P];
+    out->mean_variance = n ? stats[8 + 2 * P] / static_cast<double>(n) : 0.0;
+}
+
 }  // namespace
 
 extern "C" {
+
+int mcamd_price_heston_greeks(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_heston *heston,
+                              const mcamd_heston_greeks_job *job, void *d_samples, mcamd_heston_greeks *out)
+{
+    if (!out) return fail(MCAMD_ERR_INVALID, "opt, sim, heston, job and out must be non-NULL");
+    std::memset(out, 0, sizeof *out);
+    return prepare_heston_greeks(ctx, opt, sim, heston, job, d_samples, [&](const auto &call) {
+        return run_sync(ctx, call, out, [&](const double *stats) {
+            finalize_heston_greeks_into(stats, opt->S0, opt->r, opt->T, job, out);
+            out->work_steps = full_walk_work_steps(sim->n_paths_local, sim->n_steps);
+        });
+    });
+}
+
+int mcamd_price_heston_greeks_enqueue(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim,
+                                      const mcamd_heston *heston, const mcamd_heston_greeks_job *job, void *d_samples,
+                                      double *d_stats)
+{
+    return prepare_heston_greeks(ctx, opt, sim, heston, job, d_samples,
+                                 [&](const auto &call) { return run_enqueue(ctx, call, d_stats); });
+}
+
+int mcamd_finalize_heston_greeks_stats(const double stats[32], const mcamd_option *opt,
+                                       const mcamd_heston_greeks_job *job, mcamd_heston_greeks *out)
+{
+    if (!stats || !opt || !job || !out) return fail(MCAMD_ERR_INVALID, "stats, opt, job and out must be non-NULL");
+    std::memset(out, 0, sizeof *out);
+    if (int rc = check_heston_greeks_job(job)) return rc;
+    if (!(opt->S0 > 0.0) || !std::isfinite(opt->S0) || !std::isfinite(opt->T) || !std::isfinite(opt->r))
+        return fail(MCAMD_ERR_INVALID, "the Heston Greeks need S0 > 0 and finite S0, T and r (S0 = %g, T = %g, r = %g)",
+                    opt->S0, opt->T, opt->r);
+    finalize_heston_greeks_into(stats, opt->S0, opt->r, opt->T, job, out);
+    return MCAMD_OK;
+}
 
 int mcamd_price_heston(mcamd_ctx *ctx, const mcamd_option *opt, const mcamd_sim *sim, const mcamd_heston *heston,
                        void *d_samples, void *d_state, mcamd_heston_result *res)

@@ -3,6 +3,7 @@
 // the other C ABI files (no contraction), so a formula a prepare_* step shares gives the bits it gives here.
 #define MCAMD_CAPI_HOST_ONLY
 #include "capi_internal.hpp"
+#include "mcamd_heston_greeks.h"
 
 #include <algorithm>
 #include <complex>
@@ -153,6 +154,53 @@ double lewis_integral(double k, LogCf lnphi, double atom = 0.0)
         integral += 0.5 * kHestonPanel * s;
     }
     return integral;
+}
+
+// The integral of the spot derivative of Lewis's formula, int_0^U Re[(1/2 + iu) e^{iuk} phi(u - i/2)] / (u^2 + 1/4) du,
+// by lewis_integral's rule (the same panels and nodes) with the envelope multiplied by U: the integrand gains the
+// factor |1/2 + iu| and decays one power of u more slowly.  For a distribution without an atom.
+template <typename LogCf>
+double lewis_delta_integral(double k, LogCf lnphi)
+{
+    const auto integrand = [&](double u) {
+        return (cplx(0.5, u) * std::exp(lnphi(cplx(u, -0.5)) + cplx(0.0, u * k))).real() / (u * u + 0.25);
+    };
+    const auto envelope = [&](double u) { return u * std::exp(lnphi(cplx(u, -0.5)).real()) / (u * u + 0.25); };
+    double U = kHestonRangeMin;
+    while (U < kHestonRangeMax && envelope(U) >= kHestonEnvelope) U *= 2.0;
+    double x[kGlNodes], w[kGlNodes];
+    gauss_legendre(x, w);
+    const int panels = static_cast<int>(U / kHestonPanel);
+    double integral = 0.0;
+    for (int p = 0; p < panels; ++p) {
+        const double mid = (p + 0.5) * kHestonPanel;
+        double s = 0.0;
+        for (int i = 0; i < kGlNodes; ++i) s += w[i] * integrand(mid + 0.5 * kHestonPanel * x[i]);
+        integral += 0.5 * kHestonPanel * s;
+    }
+    return integral;
+}
+
+// d(price) / dS0 of mcamd_heston_price_f64 on arguments it accepts (include/mcamd_heston_greeks.h):
+//     delta_call = (D / S0) (F - sqrt(F K) / pi  int Re[(1/2 + iu) e^{iuk} phi(u - i/2)] / (u^2 + 1/4) du),
+// the put by parity; below MCAMD_HESTON_XI_MIN the Black-Scholes delta at the average variance.
+double heston_delta(double S0, double K, double T, double r, double q, double v0, double kappa, double theta, double xi,
+                    double rho, bool call)
+{
+    const double D = std::exp(-r * T), F = S0 * std::exp((r - q) * T), Dq = std::exp(-q * T);
+    if (xi < MCAMD_HESTON_XI_MIN) {
+        const double kT = kappa * T;
+        const double mean_v = theta + (v0 - theta) * (kT > 0.0 ? -std::expm1(-kT) / kT : 1.0);
+        if (!(mean_v > 0.0)) return call ? (F > K ? Dq : 0.0) : (F < K ? -Dq : 0.0);
+        const double v = std::sqrt(mean_v), sqrtT = std::sqrt(T);
+        const double d1 = (std::log(S0 / K) + (r - q + 0.5 * v * v) * T) / (v * sqrtT);
+        return call ? Dq * norm_cdf(d1) : -Dq * norm_cdf(-d1);
+    }
+    const double k = std::log(F / K);
+    const double integral =
+        lewis_delta_integral(k, [&](cplx u) { return heston_log_cf(u, T, v0, kappa, theta, xi, rho); });
+    const double dc = D / S0 * (F - std::sqrt(F * K) / M_PI * integral);
+    return call ? dc : dc - D * F / S0;
 }
 
 // (1 - e^{-kappa t}) / kappa, t at kappa = 0
@@ -467,6 +515,48 @@ int mcamd_heston_price_f64(double S0, double K, double T, double r, double q, do
     const double c = D * (F - std::sqrt(F * K) / M_PI * integral);
     if (!std::isfinite(c)) return fail(MCAMD_ERR_INVALID, "the Heston integral is not finite at these parameters");
     *price = call ? c : c - D * (F - K);
+    return MCAMD_OK;
+}
+
+// The model's values of what mcamd_price_heston_greeks estimates (include/mcamd_heston_greeks.h).
+int mcamd_heston_greeks_f64(double S0, double K, double T, double r, double q, double v0, double kappa, double theta,
+                            double xi, double rho, int payoff, double gamma_eta, const double bump[5], double out[10])
+{
+    if (out)
+        for (int k = 0; k < MCAMD_HESTON_GREEKS; ++k) out[k] = 0.0;
+    if (!bump || !out) return fail(MCAMD_ERR_INVALID, "bump and out must be non-NULL");
+    double price = 0.0;
+    if (int rc = mcamd_heston_price_f64(S0, K, T, r, q, v0, kappa, theta, xi, rho, payoff, &price)) return rc;
+    if (!std::isfinite(gamma_eta) || gamma_eta < 0.0)
+        return fail(MCAMD_ERR_INVALID, "gamma_eta must be finite and >= 0 (0: no gamma), got %g", gamma_eta);
+    for (int k = 0; k < 5; ++k)
+        if (!std::isfinite(bump[k]) || bump[k] < 0.0)
+            return fail(MCAMD_ERR_INVALID, "bump[%d] must be finite and >= 0 (0: not requested), got %g", k, bump[k]);
+    const bool call = payoff == MCAMD_PAYOFF_CALL;
+    const double delta = heston_delta(S0, K, T, r, q, v0, kappa, theta, xi, rho, call);
+    if (!std::isfinite(delta)) return fail(MCAMD_ERR_INVALID, "the Heston integral is not finite at these parameters");
+    double values[MCAMD_HESTON_GREEKS] = {};
+    values[MCAMD_HESTON_GREEK_PRICE] = price;
+    values[MCAMD_HESTON_GREEK_DELTA] = delta;
+    if (gamma_eta > 0.0) {
+        const double up = std::exp(gamma_eta), dn = std::exp(-gamma_eta);
+        const double d_up = heston_delta(S0 * up, K, T, r, q, v0, kappa, theta, xi, rho, call);
+        const double d_dn = heston_delta(S0 * dn, K, T, r, q, v0, kappa, theta, xi, rho, call);
+        values[MCAMD_HESTON_GREEK_GAMMA] = (d_up - d_dn) / (S0 * (up - dn));
+    }
+    values[MCAMD_HESTON_GREEK_RHO] = T * (S0 * delta - price);
+    values[MCAMD_HESTON_GREEK_RHO_Q] = -T * S0 * delta;
+    for (int k = 0; k < 5; ++k) {
+        if (!(bump[k] > 0.0)) continue;
+        double side[2];
+        for (int s = 0; s < 2; ++s) {
+            double p[5] = {v0, kappa, theta, xi, rho};
+            p[k] = p[k] + (s == 0 ? bump[k] : -bump[k]);
+            if (int rc = mcamd_heston_price_f64(S0, K, T, r, q, p[0], p[1], p[2], p[3], p[4], payoff, &side[s])) return rc;
+        }
+        values[MCAMD_HESTON_GREEK_V0 + k] = (side[0] - side[1]) / (2.0 * bump[k]);
+    }
+    for (int k = 0; k < MCAMD_HESTON_GREEKS; ++k) out[k] = values[k];
     return MCAMD_OK;
 }
 

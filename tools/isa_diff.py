@@ -13,7 +13,7 @@ import collections, importlib.util, os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = "monte-carlo-project-cuda_amd"
 DEFAULT = ["localvol.hip", "localvol_smile.hip", "autocall_localvol.hip", "autocall_localvol_f32.hip", "barrier.hip",
-           "basket.hip", "autocall.hip", "heston.hip", "heston_smile.hip", "heston_cliquet.hip", "heston_barrier.hip", "smile.hip", "cliquet.hip", "localvol_greeks.hip",
+           "basket.hip", "autocall.hip", "heston.hip", "heston_smile.hip", "heston_cliquet.hip", "heston_barrier.hip", "heston_greeks.hip", "smile.hip", "cliquet.hip", "localvol_greeks.hip",
            "lookback.hip", "asian.hip", "american.hip", "american_dual.hip", "greeks.hip"]
 OPCODE = re.compile(r"^\s+((?:v|ds|global|flat|buffer)_[a-z0-9_]+)\b")
 FIGURES = {"vgpr": ".vgpr_count", "agpr": ".agpr_count", "vgpr_spill": ".vgpr_spill_count",
